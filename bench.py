@@ -70,6 +70,17 @@ Extra objects on the JSON line:
 (process start to raytracer_screen.txt on disk: the reference's own Run_Time /
 us/pixel, src/RayTracer.cpp:1089-1104, 1576-1577) beside the CPU oracle doing
 the same job; see shipped_workload().
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the LAST timed step
+computed, the image a caller of the timed path receives, as DIR/image.npy
+(float32; W x H x 3, x-major), and the sphere-grid line's image as
+DIR/sphere_grid_image.npy; the shipped workloads write the executable's last
+raytracer_screen.txt read back as DIR/image.npy (float64, the printed values).
+An image of more than DUMP_SAMPLE_PIXELS pixels is written as a fixed sample of
+that many of its pixels (dump_sample_index: seeded, the same pixels on every
+run), so that the files stay under 64 MB in all.  The workloads are hard-coded
+scenes: the same arguments give the same inputs, and two builds can be compared
+output for output.
 """
 import argparse
 import json
@@ -102,6 +113,10 @@ CLOCK_HZ = 2.4e9                 # MI355X_MICROARCH.md: 2.4 GHz peak engine cloc
 N_SIMDS = 256 * 4                # 256 CUs x 4 SIMD-32
 VALU_PEAK_LANE_OPS = 256 * 4 * 32 * CLOCK_HZ     # one non-fused fp32 op per SIMD lane and clock (157.3 TF counts FMA = 2)
 KERNEL_SOURCES = ("rt_kernel.hip", "rt_capi.hip", "rt_tables.h")
+# --dump-outputs: at most two images per run (headline + sphere grid), each whole or a sample of this many pixels:
+# 2 x 12 MiB of float32 (a shipped image is at most 512 x 512 x 3 float64, 6 MiB), under the 64 MB the dumps may take
+DUMP_SAMPLE_PIXELS = 1 << 20
+DUMP_SAMPLE_SEED = 20240601
 
 
 def kernel_source_digest():
@@ -155,11 +170,57 @@ def valu_issue_roofline(rec, kernel_ms):
     }
 
 
+def dump_sample_index(n_pixels):
+    """The pixels --dump-outputs writes of an image of n_pixels pixels: all of them (None) up to DUMP_SAMPLE_PIXELS, else
+    DUMP_SAMPLE_PIXELS distinct flat indices x * H + z drawn with a fixed seed, ascending."""
+    if n_pixels <= DUMP_SAMPLE_PIXELS:
+        return None
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    return np.sort(rng.choice(n_pixels, size=DUMP_SAMPLE_PIXELS, replace=False))
+
+
+def dump_image(directory, name, image):
+    """Write a W x H x 3 image (numpy, or a torch tensor on the GPU) as directory/<name>.npy: whole, or as the
+    (DUMP_SAMPLE_PIXELS, 3) rows dump_sample_index picks.  Returns the path."""
+    if hasattr(image, "cpu"):
+        image = image.cpu().numpy()
+    assert image.ndim == 3 and image.shape[2] == 3 and image.dtype in (np.float32, np.float64), (image.shape, image.dtype)
+    index = dump_sample_index(image.shape[0] * image.shape[1])
+    if index is not None:
+        image = image.reshape(-1, 3)[index]
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, f"{name}.npy")
+    np.save(path, np.ascontiguousarray(image))
+    what = "whole" if index is None else f"{len(index)} sampled pixels"
+    print(f"bench.py: wrote {path} ({what}, {image.dtype}, {os.path.getsize(path)} bytes)", file=sys.stderr, flush=True)
+    return path
+
+
+def read_screen_txt(path, W, H):
+    """A raytracer_screen.txt back as a (W, H, 3) float64 array: ten header lines, then one "(r, g, b)" line per pixel,
+    x outer / z inner (tilecoderaytracer_amd/csrc/host/screen_txt.hpp)."""
+    with open(path) as f:
+        lines = f.read().splitlines()[10:]
+    if len(lines) != W * H:
+        raise ValueError(f"{path}: {len(lines)} pixel lines, expected {W * H}")
+    values = [float(v) for line in lines for v in line.strip("()").split(",")]
+    return np.array(values, dtype=np.float64).reshape(W, H, 3)
+
+
+def _count(least):
+    def parse(text):
+        n = int(text)
+        if n < least:
+            raise argparse.ArgumentTypeError(f"must be at least {least}, got {n}")
+        return n
+    return parse
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=_count(1), default=50, help="timed steps: exactly this many")
+    ap.add_argument("--warmup", type=_count(0), default=5)
     ap.add_argument("--workload", default="builtin", choices=sorted(WORKLOADS))
     ap.add_argument("--size", type=int, default=0, help="override W=H (a non-standard run; recorded in config)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -193,6 +254,9 @@ def parse_args(argv=None):
                          "with TCRT_BENCH_ONE_DEVICE=1: RCCL refuses that) and carries the direct transport only")
     ap.add_argument("--no-pipelined", action="store_true",
                     help="N > 1: skip the second, pipelined measurement (gather of frame k under the render of frame k+1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the image(s) the last timed step computed as DIR/<name>.npy "
+                         "(whole, or a fixed seeded sample of a large image; see the module docstring)")
     return ap.parse_args(argv)
 
 
@@ -337,7 +401,7 @@ def shipped_workload(args):
     exe = os.path.join(ROOT, "tilecoderaytracer_amd", "bin", "tcrt_raytracer")
     if not os.path.exists(exe):
         sys.exit(f"{exe} not built (make -C tilecoderaytracer_amd/csrc)")
-    steps = max(1, min(args.steps, 10))
+    steps = args.steps
     gpu_wall, gpu_md5 = [], None
     with tempfile.TemporaryDirectory() as d:
         out_txt = os.path.join(d, "raytracer_screen.txt")
@@ -352,6 +416,8 @@ def shipped_workload(args):
         body = b"".join(open(out_txt, "rb").readlines()[10:])           # the pixel lines (the header carries the timing)
         gpu_md5 = hashlib.md5(body).hexdigest()
         gpu_bytes = os.path.getsize(out_txt)
+        if args.dump_outputs:                                           # the last timed run's file, as its caller reads it
+            dump_image(args.dump_outputs, "image", read_screen_txt(out_txt, W, H))
         # the CPU oracle doing the same job: render (one core), then the same writer
         cpu = None
         if not args.no_cpu_baseline:
@@ -765,6 +831,12 @@ def main(argv=None):
             "partition": pm["partition"],
             "partition_note": pm["partition_note"],
         }
+
+    if args.dump_outputs and rank == 0:
+        # the frames the timed regions ended with (the headline's transport on N > 1), copied out after every clock has stopped
+        dump_image(args.dump_outputs, "image", m["pipe"].image(W))
+        if grid is not None:
+            dump_image(args.dump_outputs, "sphere_grid_image", g["pipe"].image(g["W"]))
 
     if rank == 0:
         li = renderer.launch_info()
