@@ -88,8 +88,8 @@ struct rt_scene {
     int help_spin_opt = RT_HELP_SPIN_LIMIT;   /* the owner's bounded wait at its desk; -1: every wait counts as timed out (tests) */
     unsigned int *h_error = nullptr;          /* pinned host word the kernels can write: a HELP wait timed out */
     int timeline_opt = 0;                     /* diagnostic: every launch records per tile when and by whom it was rendered */
-    unsigned long long *d_timeline = nullptr;
-    size_t timeline_words = 0, timeline_valid = 0;
+    void *d_timeline = nullptr;
+    size_t d_timeline_bytes = 0, timeline_valid = 0;        /* (timeline_valid: words) */
     int wide_opt = -1;            /* experiments: which clustered-scene kernel (-1 automatic, 0 the 80-register one, 1 the 96-register one) */
     int pairs_opt = 1;            /* scenes with clustered runs: the kernel that compacts (ray, leaf) pairs (0: the plain kernel) */
     int tables_opt = 0;           /* where the kernel reads the tables: 0 = automatic, 1 = LDS, 2 = global memory (any size) */
@@ -390,23 +390,40 @@ bool shadow_voxels(const std::vector<Quad> &items, int first_leaf, const std::ve
     return true;
 }
 
-/* Build the LDS image + run lists from the stored description. */
-int pack_scene(rt_scene *s) {
-    const int n = (int)s->objects.size();
-    const rt_object_desc *objs = s->objects.data();
-    const int sb = s->shadow_begin, se = s->shadow_end;
-    /* option "cull" = 0: every object is a plain item in Scene index order */
-    const int cluster_leaf_opt = s->cull_opt ? s->cluster_leaf : 0;
-    const bool aa_planes = s->cull_opt && s->aa_planes;
+/* ---- pack_scene(): the table sections (rt_tables.h), one stage each, in this order ---- */
+struct LeafItem { float lo[3], hi[3]; uint32_t member_off, count, cidx_slot; bool in_shadow; };
 
+/* What the stages hand on to each other.  Everything is a temporary: pack_scene() commits to the handle only when all of
+ * them succeeded. */
+struct Packing {
+    explicit Packing(int n)
+        : geom_off((size_t)n, 0), mat_of((size_t)n, 0), aa_rec_of((size_t)n, -1), aa_cls_of((size_t)n, -1), clustered((size_t)n, 0) {}
     std::vector<Quad> geom, lights, mats, texs;
-    std::vector<uint32_t> objinfo((size_t)n, 0u), cidx;
-    std::vector<int> geom_off((size_t)n, 0), mat_of((size_t)n, 0);
-    std::map<std::vector<uint32_t>, int> mat_index;
+    std::vector<int> geom_off, mat_of;               /* per object: its full record in geom, its material */
+    std::vector<uint32_t> cidx;                      /* Scene indices of the clustered runs' members, leaf by leaf */
+    std::vector<LeafItem> leaf_items;
+    int n_clusters = 0;
+    std::vector<int> aa_all;                         /* axis-aligned finite planes (Scene indices) */
+    std::vector<int> aa_rec_of;                      /* their AA test record (quad offset within aa_recs) */
+    std::vector<int> aa_cls_of;
+    std::vector<char> clustered;
+    std::vector<Quad> aa_recs;
+    int aa_off = 0, cidx_off = 0;                    /* where the item tables' image puts aa_recs and cidx */
+    std::vector<Quad> near_items, shadow_items;
+    bool fast = false;                               /* FAST tables instead of the two item tables */
+    std::vector<uint32_t> fast_ctl;
+    std::vector<Quad> fast_boxes, fast_recs;
+    int fast_n_shadow = 0;
+    RtParams b{};
+    std::vector<Quad> image;
+};
 
-    /* materials (de-duplicated bit-wise), lights */
+/* materials (de-duplicated bit-wise), lights, textures */
+int pack_materials_and_lights(const rt_scene *s, Packing &P) {
+    const int n = (int)s->objects.size();
+    std::map<std::vector<uint32_t>, int> mat_index;
     for (int i = 0; i < n; ++i) {
-        const rt_object_desc &o = objs[i];
+        const rt_object_desc &o = s->objects[(size_t)i];
         const uint32_t mbits = (o.is_light ? 1u : 0u) | ((uint32_t)(o.texture + 1) << 1);
         Quad m0 = {{o.color[0], o.color[1], o.color[2], o.diffuse}};
         Quad m1 = {{o.specular, o.reflective, o.intensity, bits_to_float(mbits)}};
@@ -418,23 +435,48 @@ int pack_scene(rt_scene *s) {
             const int mi = (int)mat_index.size();
             if (mi > RT_MAX_MATERIALS) return fail(RT_ERR_CAPACITY, "too many distinct materials");
             mat_index.emplace(key, mi);
-            mats.push_back(m0);
-            mats.push_back(m1);
-            mat_of[(size_t)i] = mi;
+            P.mats.push_back(m0);
+            P.mats.push_back(m1);
+            P.mat_of[(size_t)i] = mi;
         } else {
-            mat_of[(size_t)i] = it->second;
+            P.mat_of[(size_t)i] = it->second;
         }
         if (o.is_light) {
-            lights.push_back({{o.origin[0], o.origin[1], o.origin[2], o.intensity}});
-            lights.push_back({{o.color[0], o.color[1], o.color[2], bits_to_float((uint32_t)i)}});
+            P.lights.push_back({{o.origin[0], o.origin[1], o.origin[2], o.intensity}});
+            P.lights.push_back({{o.color[0], o.color[1], o.color[2], bits_to_float((uint32_t)i)}});
         }
     }
     for (const rt_texture_desc &x : s->textures) {
-        texs.push_back({{x.light[0], x.light[1], x.light[2], x.width}});
-        texs.push_back({{x.dark[0], x.dark[1], x.dark[2], x.height}});
+        P.texs.push_back({{x.light[0], x.light[1], x.light[2], x.width}});
+        P.texs.push_back({{x.dark[0], x.dark[1], x.dark[2], x.height}});
     }
+    return RT_OK;
+}
 
-    /* runs of consecutive objects of one kind and one light flag, in index order */
+void emit_geometry(const rt_object_desc *objs, int i, Packing &P) {
+    const rt_object_desc &o = objs[i];
+    P.geom_off[(size_t)i] = (int)P.geom.size();
+    if (o.kind == RT_KIND_SPHERE) {
+        P.geom.push_back({{o.origin[0], o.origin[1], o.origin[2], o.radius_squared}});
+    } else {
+        const float *anchor = (o.kind == RT_KIND_INFINITE_PLANE) ? o.origin : o.plane_origin;
+        P.geom.push_back({{o.normal[0], o.normal[1], o.normal[2], o.distance_to_origin}});
+        P.geom.push_back({{anchor[0], anchor[1], anchor[2], o.h_distance}});
+        P.geom.push_back({{o.horizontal[0], o.horizontal[1], o.horizontal[2], o.v_distance}});
+        P.geom.push_back({{o.vertical[0], o.vertical[1], o.vertical[2], 0.0f}});
+        P.geom.push_back({{o.reverse_normal[0], o.reverse_normal[1], o.reverse_normal[2], 0.0f}});
+    }
+}
+
+/* Runs of consecutive objects of one kind and one light flag, in index order: their full records, long sphere runs regrouped
+ * into cluster leaves, and the axis-aligned finite planes picked out for the class-sorted tables (option "cull" = 0: every
+ * object is a plain item in Scene index order). */
+int pack_runs_and_clusters(const rt_scene *s, Packing &P) {
+    const int n = (int)s->objects.size();
+    const rt_object_desc *objs = s->objects.data();
+    const int sb = s->shadow_begin, se = s->shadow_end;
+    const int cluster_leaf_opt = s->cull_opt ? s->cluster_leaf : 0;
+    const bool aa_planes = s->cull_opt && s->aa_planes;
     struct Span { int kind, first, count; bool light; };
     std::vector<Span> spans;
     for (int i = 0; i < n; ++i) {
@@ -444,33 +486,6 @@ int pack_scene(rt_scene *s) {
         else
             spans.push_back(Span{objs[i].kind, i, 1, light});
     }
-
-    auto emit_geometry = [&](int i) {
-        const rt_object_desc &o = objs[i];
-        geom_off[(size_t)i] = (int)geom.size();
-        if (o.kind == RT_KIND_SPHERE) {
-            geom.push_back({{o.origin[0], o.origin[1], o.origin[2], o.radius_squared}});
-        } else {
-            const float *anchor = (o.kind == RT_KIND_INFINITE_PLANE) ? o.origin : o.plane_origin;
-            geom.push_back({{o.normal[0], o.normal[1], o.normal[2], o.distance_to_origin}});
-            geom.push_back({{anchor[0], anchor[1], anchor[2], o.h_distance}});
-            geom.push_back({{o.horizontal[0], o.horizontal[1], o.horizontal[2], o.v_distance}});
-            geom.push_back({{o.vertical[0], o.vertical[1], o.vertical[2], 0.0f}});
-            geom.push_back({{o.reverse_normal[0], o.reverse_normal[1], o.reverse_normal[2], 0.0f}});
-        }
-    };
-
-    int n_clusters = 0;
-    /* Cluster/idx offsets are patched once the section bases are known. */
-    std::vector<int> aa_all;                         /* axis-aligned finite planes (Scene indices) */
-    std::vector<int> aa_rec_of((size_t)n, -1);       /* their AA test record (quad offset within aa_recs) */
-    std::vector<int> aa_cls_of((size_t)n, -1);
-    std::vector<char> clustered((size_t)n, 0);
-    struct LeafItem { float lo[3], hi[3]; uint32_t member_off, count, cidx_slot; bool in_shadow; };
-    std::vector<LeafItem> leaf_items;
-    std::vector<Quad> shadow_items, near_items;
-    std::vector<Quad> aa_recs;
-
     for (const Span &sp : spans) {
         const int first = sp.first, last = sp.first + sp.count;             /* [first, last) */
         /* part of the span inside the shadow scan range (lights never cast shadows) */
@@ -489,289 +504,305 @@ int pack_scene(rt_scene *s) {
             split_leaves(objs, ids, cluster_leaf, leaves);
             /* the leaves come out of the k-d split in spatial order; each becomes one item of both scans */
             for (const Leaf &L : leaves) {
-                const int member_off = (int)geom.size();
-                const int slot = (int)cidx.size();
-                for (int i : L.members) { emit_geometry(i); cidx.push_back((uint32_t)i); clustered[(size_t)i] = 1; }
+                const int member_off = (int)P.geom.size();
+                const int slot = (int)P.cidx.size();
+                for (int i : L.members) { emit_geometry(objs, i, P); P.cidx.push_back((uint32_t)i); P.clustered[(size_t)i] = 1; }
                 LeafItem li;
                 for (int k = 0; k < 3; ++k) { li.lo[k] = L.lo[k]; li.hi[k] = L.hi[k]; }
                 li.member_off = (uint32_t)member_off;
                 li.count = (uint32_t)L.members.size();
                 li.cidx_slot = (uint32_t)slot;
                 li.in_shadow = in_shadow_all;
-                leaf_items.push_back(li);
+                P.leaf_items.push_back(li);
             }
-            n_clusters += (int)leaves.size();
-        } else if (sp.kind == RT_KIND_FINITE_PLANE && aa_planes) {
-            /* axis-aligned members leave the in-order run for the class-sorted tables built below */
-            for (int i = first; i < last; ++i) emit_geometry(i);
-            int i = first;
-            while (i < last) {
-                float sn, sh, sv; int ka, kb;
-                const bool aa = aa_class(objs[i], &sn, &sh, &sv, &ka, &kb) >= 0;
-                int j = i;
-                while (j < last) {
-                    const bool aj = aa_class(objs[j], &sn, &sh, &sv, &ka, &kb) >= 0;
-                    if (aj != aa) break;
-                    ++j;
-                }
-                if (aa) {
-                    for (int k = i; k < j; ++k) aa_all.push_back(k);
-                }
-                i = j;
-            }
+            P.n_clusters += (int)leaves.size();
         } else {
-            for (int i = first; i < last; ++i) emit_geometry(i);
+            for (int i = first; i < last; ++i) emit_geometry(objs, i, P);
+            /* axis-aligned members leave the in-order run for the class-sorted tables */
+            if (sp.kind == RT_KIND_FINITE_PLANE && aa_planes)
+                for (int i = first; i < last; ++i) {
+                    float sn, sh, sv; int ka, kb;
+                    if (aa_class(objs[i], &sn, &sh, &sv, &ka, &kb) >= 0) P.aa_all.push_back(i);
+                }
         }
-        if (geom.size() > RT_MAX_GEOM_QUADS) return fail(RT_ERR_CAPACITY, "geometry table too large");
+        if (P.geom.size() > RT_MAX_GEOM_QUADS) return fail(RT_ERR_CAPACITY, "geometry table too large");
     }
-    /* axis-aligned rectangles: their two-quad test records (rt_tables.h) */
-    for (int i : aa_all) {
+    return RT_OK;
+}
+
+/* axis-aligned rectangles: their two-quad test records (rt_tables.h) */
+void pack_aa_records(const rt_scene *s, Packing &P) {
+    for (int i : P.aa_all) {
         float sn, sh, sv; int ka, kb;
-        const int cls = aa_class(objs[i], &sn, &sh, &sv, &ka, &kb);
-        const rt_object_desc &o = objs[i];
-        aa_rec_of[(size_t)i] = (int)aa_recs.size();
-        aa_cls_of[(size_t)i] = cls % 3;
+        const rt_object_desc &o = s->objects[(size_t)i];
+        const int cls = aa_class(o, &sn, &sh, &sv, &ka, &kb);
+        P.aa_rec_of[(size_t)i] = (int)P.aa_recs.size();
+        P.aa_cls_of[(size_t)i] = cls % 3;
         const bool swapped = cls >= 3;                   /* first in-plane axis is the plane's "vertical" */
-        aa_recs.push_back({{o.distance_to_origin, sn, sh, sv}});
-        aa_recs.push_back({{o.plane_origin[ka], o.plane_origin[kb], swapped ? o.v_distance : o.h_distance,
-                            swapped ? o.h_distance : o.v_distance}});
+        P.aa_recs.push_back({{o.distance_to_origin, sn, sh, sv}});
+        P.aa_recs.push_back({{o.plane_origin[ka], o.plane_origin[kb], swapped ? o.v_distance : o.h_distance,
+                              swapped ? o.h_distance : o.v_distance}});
     }
-    for (int i = 0; i < n; ++i)
-        objinfo[(size_t)i] = (uint32_t)geom_off[(size_t)i] | ((uint32_t)objs[i].kind << 16) |
-                             ((uint32_t)mat_of[(size_t)i] << 20);
+}
 
-    /* assemble the image (into temporaries: a failure below leaves the handle as it was) */
-    RtParams b;
-    std::memset(&b, 0, sizeof(b));
-    std::vector<Quad> image;
-    image.insert(image.end(), geom.begin(), geom.end());
-    const int aa_off = (int)image.size();
-    image.insert(image.end(), aa_recs.begin(), aa_recs.end());
-    /* Scene-index tables of the clustered / class-sorted runs */
-    const int cidx_off = (int)image.size();
-    image.resize(image.size() + (cidx.size() + 3) / 4, Quad{{0, 0, 0, 0}});
-    if (!cidx.empty()) std::memcpy(image[(size_t)cidx_off].v, cidx.data(), cidx.size() * 4);
+/* Padding.  A sphere's box also has to hold what the reference's coarse float sphere test reports
+ * (box_needed() in rt_kernel.hip): 1 % of its extent here plus the kernel's distance-proportional
+ * RT_SPHERE_SLACK.  A plane item (RT_ITEM_TIGHT) gets 2e-5 + 2e-5 of the box's magnitude: 170 ulp of the
+ * largest coordinate.  What it has to cover is the part of the hit point's error that scales with WHERE the
+ * rectangle is: p = t d + o is rounded twice per component (2 ulp of |p_k|) and the bounds test
+ * (p - plane_origin).h, 0 <= x <= h_dist adds a few ulp of the rectangle's coordinates -- well under 20 ulp
+ * in all.  The part that scales with the distance TRAVELLED -- t d_k and o_k cancel when a ray comes from
+ * far away, and t itself carries the relative error of n.o + dto: about 1e-6 of the distance for origins
+ * 1e4-6e4 away, grazing or not -- is the kernel's per-axis RT_PLANE_SLACK, 1e-5 of the distance on that
+ * axis (an axis on which the ray hardly moves has a hit-point error that small, too: the error of t is
+ * multiplied by d_k).  tests/scene_gen.py's far-origin grazing scenes and scripts/fuzz_gpu.py's `far` mode
+ * exercise exactly that against the oracle.  (With the sphere padding a 14-unit wall was 0.28 thick and,
+ * e.g., a light 0.01 in front of it made it a candidate of every shadow scan towards that light; at 170 ulp
+ * a plane is not even a candidate of the shadow rays that START on it, 1e-3 in front of it --
+ * src/SceneFinitePlane.h:11 --, in scenes up to a few tens of units across.) */
+void box_item(std::vector<Quad> &out, const double lo[3], const double hi[3], uint32_t bits, uint32_t word1, bool unbounded) {
+    const float INF = INFINITY;
+    double ext = 0.0, mag = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) continue;       /* an axis the item is unbounded on */
+        ext = std::max(ext, hi[k] - lo[k]);
+        mag = std::max(mag, std::max(std::fabs(lo[k]), std::fabs(hi[k])));
+    }
+    const double pad = (bits & RT_ITEM_TIGHT) ? 2e-5 + 2e-5 * mag : 1e-4 + 1e-4 * mag + 1e-2 * ext;
+    Quad q0, q1;
+    for (int k = 0; k < 3; ++k) {
+        const bool ok = !unbounded && std::isfinite(lo[k]) && std::isfinite(hi[k]) && std::isfinite(pad);
+        centre_half(ok ? (double)std::nextafter((float)(lo[k] - pad), -INF) : -(double)INF,
+                    ok ? (double)std::nextafter((float)(hi[k] + pad), INF) : (double)INF, &q0.v[k], &q1.v[k]);
+    }
+    q0.v[3] = bits_to_float(bits);
+    q1.v[3] = bits_to_float(word1);
+    out.push_back(q0);
+    out.push_back(q1);
+}
 
-    /* FAST tables (rt_tables.h): scenes without clustered runs get one kind-sorted item list with direct test
-     * records instead of the two item tables (and the sections only those refer to) */
-    /* (only while the tables go to LDS: the large-scene kernel reads the item tables) */
-    const size_t fast_quads = geom.size() + (size_t)n * (RT_FAST_BOX_QUADS + RT_FAST_REC_QUADS) + lights.size() + mats.size() +
-                              texs.size() + 2 * (((size_t)n + 3) / 4);
-    const bool fast = s->cull_opt && s->fast_opt && n_clusters == 0 && n > 0 && s->tables_opt != 2 &&
-                      fast_quads * 16 <= (s->tables_opt == 1 ? (size_t)RT_MAX_LDS_BYTES : (size_t)RT_LDS_TABLE_BYTES);
-    std::vector<uint32_t> fast_ctl;
-    std::vector<Quad> fast_boxes, fast_recs;
-    int fast_n_shadow = 0;
-    /* Item tables (rt_tables.h): one item per object that is not part of a clustered run, in
-     * Scene order, then one per leaf (or group) of each clustered run.  `near_items` covers every object,
-     * `shadow_items` the non-light objects of the shadow scan range. */
-    {
-        const float INF = INFINITY;
-        /* Padding.  A sphere's box also has to hold what the reference's coarse float sphere test reports
-         * (box_needed() in rt_kernel.hip): 1 % of its extent here plus the kernel's distance-proportional
-         * RT_SPHERE_SLACK.  A plane item (RT_ITEM_TIGHT) gets 2e-5 + 2e-5 of the box's magnitude: 170 ulp of the
-         * largest coordinate.  What it has to cover is the part of the hit point's error that scales with WHERE the
-         * rectangle is: p = t d + o is rounded twice per component (2 ulp of |p_k|) and the bounds test
-         * (p - plane_origin).h, 0 <= x <= h_dist adds a few ulp of the rectangle's coordinates -- well under 20 ulp
-         * in all.  The part that scales with the distance TRAVELLED -- t d_k and o_k cancel when a ray comes from
-         * far away, and t itself carries the relative error of n.o + dto: about 1e-6 of the distance for origins
-         * 1e4-6e4 away, grazing or not -- is the kernel's per-axis RT_PLANE_SLACK, 1e-5 of the distance on that
-         * axis (an axis on which the ray hardly moves has a hit-point error that small, too: the error of t is
-         * multiplied by d_k).  tests/scene_gen.py's far-origin grazing scenes and scripts/fuzz_gpu.py's `far` mode
-         * exercise exactly that against the oracle.  (With the sphere padding a 14-unit wall was 0.28 thick and,
-         * e.g., a light 0.01 in front of it made it a candidate of every shadow scan towards that light; at 170 ulp
-         * a plane is not even a candidate of the shadow rays that START on it, 1e-3 in front of it --
-         * src/SceneFinitePlane.h:11 --, in scenes up to a few tens of units across.) */
-        auto box_item = [&](std::vector<Quad> &out, const double lo[3], const double hi[3], uint32_t bits,
-                            uint32_t word1, bool unbounded) {
-            double ext = 0.0, mag = 0.0;
-            for (int k = 0; k < 3; ++k) {
-                if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) continue;       /* an axis the item is unbounded on */
-                ext = std::max(ext, hi[k] - lo[k]);
-                mag = std::max(mag, std::max(std::fabs(lo[k]), std::fabs(hi[k])));
-            }
-            const double pad = (bits & RT_ITEM_TIGHT) ? 2e-5 + 2e-5 * mag : 1e-4 + 1e-4 * mag + 1e-2 * ext;
-            Quad q0, q1;
-            for (int k = 0; k < 3; ++k) {
-                const bool ok = !unbounded && std::isfinite(lo[k]) && std::isfinite(hi[k]) && std::isfinite(pad);
-                centre_half(ok ? (double)std::nextafter((float)(lo[k] - pad), -INF) : -(double)INF,
-                            ok ? (double)std::nextafter((float)(hi[k] + pad), INF) : (double)INF, &q0.v[k], &q1.v[k]);
-            }
-            q0.v[3] = bits_to_float(bits);
-            q1.v[3] = bits_to_float(word1);
-            out.push_back(q0);
-            out.push_back(q1);
-        };
-        auto object_item = [&](std::vector<Quad> &out, int i) {
-            const rt_object_desc &o = objs[i];
-            double lo[3], hi[3];
-            const uint32_t full = (uint32_t)geom_off[(size_t)i];
-            const uint32_t word1 = (uint32_t)i | (full << 12);          /* Scene index | full record offset */
-            if (o.kind == RT_KIND_SPHERE) {
-                const double r = std::fabs((double)o.radius);
-                for (int k = 0; k < 3; ++k) { lo[k] = (double)o.origin[k] - r; hi[k] = (double)o.origin[k] + r; }
-                box_item(out, lo, hi, (uint32_t)RT_KIND_SPHERE | (full << 16), word1, false);
-            } else if (o.kind == RT_KIND_INFINITE_PLANE) {
-                /* An infinite plane whose normal is a +-unit axis vector is a SLAB: bounded on that axis (at
-                 * x_k = -dto * sign: sign * x_k + dto = 0), unbounded on the others, and tight like a finite
-                 * plane -- the hit point's k component is t d_k + o_k with t = (-dto - o_k sign) / (d_k sign)
-                 * (src/SceneInfinitePlane.cpp:40-55), off the plane by a few ulp of |o_k - x_k| + |x_k|.  Any
-                 * other infinite plane is unbounded on every axis: a candidate of every scan. */
-                float sign = 0.0f;
-                const int axis = (s->tight_planes && std::isfinite(o.distance_to_origin)) ? unit_axis(o.normal, &sign) : -1;
-                for (int k = 0; k < 3; ++k) { lo[k] = -(double)INF; hi[k] = (double)INF; }
-                if (axis >= 0) lo[axis] = hi[axis] = -(double)o.distance_to_origin * (double)sign;
-                box_item(out, lo, hi, (uint32_t)RT_KIND_INFINITE_PLANE | (axis >= 0 ? (uint32_t)RT_ITEM_TIGHT : 0u) | (full << 16),
-                         word1, axis < 0);
-            } else {
-                /* The hit region is {p on the plane : 0 <= (p-po).h <= h_dist, 0 <= (p-po).v <= v_dist}
-                 * (src/SceneFinitePlane.cpp:117-124).  h and v need be neither orthogonal to each
-                 * other nor to the normal (axis constructor with arbitrary vectors), so the
-                 * corners come from solving  u.n = 0, u.h = x, u.v = y  for u = p - po. */
-                bool unbounded = false;
-                for (int k = 0; k < 3; ++k) { lo[k] = 1e300; hi[k] = -1e300; }
-                {
-                    const double n[3] = {o.normal[0], o.normal[1], o.normal[2]};
-                    const double h[3] = {o.horizontal[0], o.horizontal[1], o.horizontal[2]};
-                    const double v[3] = {o.vertical[0], o.vertical[1], o.vertical[2]};
-                    auto cross3 = [](const double a[3], const double c[3], double r[3]) {
-                        r[0] = a[1] * c[2] - a[2] * c[1]; r[1] = a[2] * c[0] - a[0] * c[2]; r[2] = a[0] * c[1] - a[1] * c[0];
-                    };
-                    double hv[3], vn[3], nh[3];
-                    cross3(h, v, hv); cross3(v, n, vn); cross3(n, h, nh);
-                    const double det = n[0] * hv[0] + n[1] * hv[1] + n[2] * hv[2];
-                    if (!(std::fabs(det) > 1e-6) || !std::isfinite(det)) {
-                        unbounded = true;
-                    } else {
-                        for (int a = 0; a < 2; ++a)
-                            for (int c = 0; c < 2; ++c) {
-                                const double x = a * (double)o.h_distance, y = c * (double)o.v_distance;
-                                for (int k = 0; k < 3; ++k) {          /* u = (x (v x n) + y (n x h)) / det */
-                                    const double u = (x * vn[k] + y * nh[k]) / det;
-                                    const double pk = (double)o.plane_origin[k] + u;
-                                    lo[k] = std::min(lo[k], pk);
-                                    hi[k] = std::max(hi[k], pk);
-                                }
-                            }
-                    }
-                }
-                if (unbounded) { for (int k = 0; k < 3; ++k) { lo[k] = hi[k] = 0.0; } }
-                const uint32_t tight = s->tight_planes ? (uint32_t)RT_ITEM_TIGHT : 0u;
-                if (aa_rec_of[(size_t)i] >= 0)
-                    box_item(out, lo, hi, (uint32_t)(RT_KIND_FINITE_AA + aa_cls_of[(size_t)i]) | tight |
-                                              ((uint32_t)(aa_off + aa_rec_of[(size_t)i]) << 16), word1, unbounded);
-                else
-                    box_item(out, lo, hi, (uint32_t)RT_KIND_FINITE_PLANE | tight | (full << 16), word1, unbounded);
-            }
-        };
-        for (int i = 0; i < n; ++i)
-            if (!clustered[(size_t)i]) object_item(near_items, i);
-        auto leaf_item = [&](std::vector<Quad> &out, const LeafItem &l) {
-            Quad q0 = {{0, 0, 0, bits_to_float((uint32_t)RT_KIND_SPHERE_LEAF | (l.count << 8) | (l.member_off << 16))}};
-            Quad q1 = {{0, 0, 0, bits_to_float((uint32_t)(cidx_off * 4) + l.cidx_slot)}};
-            for (int k = 0; k < 3; ++k) centre_half((double)l.lo[k], (double)l.hi[k], &q0.v[k], &q1.v[k]);
-            out.push_back(q0);
-            out.push_back(q1);
-        };
-        b.near_first_leaf = (int)(near_items.size() / 2);
-        for (const LeafItem &l : leaf_items) leaf_item(near_items, l);
-        for (int i = sb; i < se; ++i)
-            if (!objs[i].is_light && !clustered[(size_t)i]) object_item(shadow_items, i);
-        b.shadow_first_leaf = (int)(shadow_items.size() / 2);
-        for (const LeafItem &l : leaf_items)
-            if (l.in_shadow) leaf_item(shadow_items, l);
-        if (fast) {
-            auto kind_rank = [&](int i) {
-                if (aa_rec_of[(size_t)i] >= 0) return aa_cls_of[(size_t)i];                 /* 0..2: AA rectangles by normal axis */
-                return objs[i].kind == RT_KIND_SPHERE ? 3 : objs[i].kind == RT_KIND_FINITE_PLANE ? 4 : 5;
+/* the item of object i (one that is not part of a clustered run) */
+void object_item(const rt_scene *s, const Packing &P, std::vector<Quad> &out, int i) {
+    const float INF = INFINITY;
+    const rt_object_desc &o = s->objects[(size_t)i];
+    double lo[3], hi[3];
+    const uint32_t full = (uint32_t)P.geom_off[(size_t)i];
+    const uint32_t word1 = (uint32_t)i | (full << 12);          /* Scene index | full record offset */
+    if (o.kind == RT_KIND_SPHERE) {
+        const double r = std::fabs((double)o.radius);
+        for (int k = 0; k < 3; ++k) { lo[k] = (double)o.origin[k] - r; hi[k] = (double)o.origin[k] + r; }
+        box_item(out, lo, hi, (uint32_t)RT_KIND_SPHERE | (full << 16), word1, false);
+    } else if (o.kind == RT_KIND_INFINITE_PLANE) {
+        /* An infinite plane whose normal is a +-unit axis vector is a SLAB: bounded on that axis (at
+         * x_k = -dto * sign: sign * x_k + dto = 0), unbounded on the others, and tight like a finite
+         * plane -- the hit point's k component is t d_k + o_k with t = (-dto - o_k sign) / (d_k sign)
+         * (src/SceneInfinitePlane.cpp:40-55), off the plane by a few ulp of |o_k - x_k| + |x_k|.  Any
+         * other infinite plane is unbounded on every axis: a candidate of every scan. */
+        float sign = 0.0f;
+        const int axis = (s->tight_planes && std::isfinite(o.distance_to_origin)) ? unit_axis(o.normal, &sign) : -1;
+        for (int k = 0; k < 3; ++k) { lo[k] = -(double)INF; hi[k] = (double)INF; }
+        if (axis >= 0) lo[axis] = hi[axis] = -(double)o.distance_to_origin * (double)sign;
+        box_item(out, lo, hi, (uint32_t)RT_KIND_INFINITE_PLANE | (axis >= 0 ? (uint32_t)RT_ITEM_TIGHT : 0u) | (full << 16),
+                 word1, axis < 0);
+    } else {
+        /* The hit region is {p on the plane : 0 <= (p-po).h <= h_dist, 0 <= (p-po).v <= v_dist}
+         * (src/SceneFinitePlane.cpp:117-124).  h and v need be neither orthogonal to each
+         * other nor to the normal (axis constructor with arbitrary vectors), so the
+         * corners come from solving  u.n = 0, u.h = x, u.v = y  for u = p - po. */
+        bool unbounded = false;
+        for (int k = 0; k < 3; ++k) { lo[k] = 1e300; hi[k] = -1e300; }
+        {
+            const double n[3] = {o.normal[0], o.normal[1], o.normal[2]};
+            const double h[3] = {o.horizontal[0], o.horizontal[1], o.horizontal[2]};
+            const double v[3] = {o.vertical[0], o.vertical[1], o.vertical[2]};
+            auto cross3 = [](const double a[3], const double c[3], double r[3]) {
+                r[0] = a[1] * c[2] - a[2] * c[1]; r[1] = a[2] * c[0] - a[0] * c[2]; r[2] = a[0] * c[1] - a[1] * c[0];
             };
-            std::vector<int> order;
-            for (int part = 0; part < 2; ++part)
-                for (int rank = 0; rank < 6; ++rank)
-                    for (int i = 0; i < n; ++i) {
-                        const bool in_shadow = i >= sb && i < se && !objs[i].is_light;
-                        if ((part == 0) == in_shadow && kind_rank(i) == rank) order.push_back(i);
+            double hv[3], vn[3], nh[3];
+            cross3(h, v, hv); cross3(v, n, vn); cross3(n, h, nh);
+            const double det = n[0] * hv[0] + n[1] * hv[1] + n[2] * hv[2];
+            if (!(std::fabs(det) > 1e-6) || !std::isfinite(det)) {
+                unbounded = true;
+            } else {
+                for (int a = 0; a < 2; ++a)
+                    for (int c = 0; c < 2; ++c) {
+                        const double x = a * (double)o.h_distance, y = c * (double)o.v_distance;
+                        for (int k = 0; k < 3; ++k) {          /* u = (x (v x n) + y (n x h)) / det */
+                            const double u = (x * vn[k] + y * nh[k]) / det;
+                            const double pk = (double)o.plane_origin[k] + u;
+                            lo[k] = std::min(lo[k], pk);
+                            hi[k] = std::max(hi[k], pk);
+                        }
                     }
-            for (int i : order) {
-                const rt_object_desc &o = objs[i];
-                if (i >= sb && i < se && !o.is_light) ++fast_n_shadow;
-                std::vector<Quad> item;
-                object_item(item, i);
-                const uint32_t kind = aa_rec_of[(size_t)i] >= 0 ? (uint32_t)(RT_KIND_FINITE_AA + aa_cls_of[(size_t)i]) : (uint32_t)o.kind;
-                const uint32_t ctl = kind | ((uint32_t)i << 8);
-                uint32_t bits0; std::memcpy(&bits0, &item[0].v[3], 4);
-                item[0].v[3] = bits_to_float(kind | (bits0 & RT_ITEM_TIGHT));
-                item[1].v[3] = bits_to_float(ctl);
-                fast_boxes.push_back(item[0]);
-                fast_boxes.push_back(item[1]);
-                fast_ctl.push_back(ctl);
-                if (aa_rec_of[(size_t)i] >= 0) {
-                    fast_recs.push_back(aa_recs[(size_t)aa_rec_of[(size_t)i]]);
-                    fast_recs.push_back(aa_recs[(size_t)aa_rec_of[(size_t)i] + 1]);
-                } else if (o.kind == RT_KIND_SPHERE) {
-                    fast_recs.push_back({{o.origin[0], o.origin[1], o.origin[2], o.radius_squared}});
-                    fast_recs.push_back({{0, 0, 0, 0}});
-                } else {
-                    fast_recs.push_back({{o.normal[0], o.normal[1], o.normal[2], o.distance_to_origin}});
-                    fast_recs.push_back({{bits_to_float((uint32_t)geom_off[(size_t)i]), 0, 0, 0}});
-                }
             }
         }
+        if (unbounded) { for (int k = 0; k < 3; ++k) { lo[k] = hi[k] = 0.0; } }
+        const uint32_t tight = s->tight_planes ? (uint32_t)RT_ITEM_TIGHT : 0u;
+        if (P.aa_rec_of[(size_t)i] >= 0)
+            box_item(out, lo, hi, (uint32_t)(RT_KIND_FINITE_AA + P.aa_cls_of[(size_t)i]) | tight |
+                                      ((uint32_t)(P.aa_off + P.aa_rec_of[(size_t)i]) << 16), word1, unbounded);
+        else
+            box_item(out, lo, hi, (uint32_t)RT_KIND_FINITE_PLANE | tight | (full << 16), word1, unbounded);
     }
-    if (fast) {
-        image.assign(geom.begin(), geom.end());                /* no leaves, no aa section, no cidx */
-        b.n_fast_items = (int)fast_ctl.size();
-        b.n_fast_shadow = fast_n_shadow;
+}
+
+void leaf_item(const Packing &P, std::vector<Quad> &out, const LeafItem &l) {
+    Quad q0 = {{0, 0, 0, bits_to_float((uint32_t)RT_KIND_SPHERE_LEAF | (l.count << 8) | (l.member_off << 16))}};
+    Quad q1 = {{0, 0, 0, bits_to_float((uint32_t)(P.cidx_off * 4) + l.cidx_slot)}};
+    for (int k = 0; k < 3; ++k) centre_half((double)l.lo[k], (double)l.hi[k], &q0.v[k], &q1.v[k]);
+    out.push_back(q0);
+    out.push_back(q1);
+}
+
+/* Item tables (rt_tables.h): one item per object that is not part of a clustered run, in Scene order, then one per leaf of
+ * each clustered run.  `near_items` covers every object, `shadow_items` the non-light objects of the shadow scan range.
+ * FAST tables (rt_tables.h): scenes without clustered runs get one kind-sorted item list with direct test records instead of
+ * the two item tables (and the sections only those refer to) -- only while the tables go to LDS: the large-scene kernel reads
+ * the item tables. */
+void pack_items(const rt_scene *s, Packing &P) {
+    const int n = (int)s->objects.size();
+    const rt_object_desc *objs = s->objects.data();
+    const int sb = s->shadow_begin, se = s->shadow_end;
+    /* the item tables' image starts geom, aa_recs, cidx */
+    P.aa_off = (int)P.geom.size();
+    P.cidx_off = P.aa_off + (int)P.aa_recs.size();
+    const size_t fast_quads = P.geom.size() + (size_t)n * (RT_FAST_BOX_QUADS + RT_FAST_REC_QUADS) + P.lights.size() +
+                              P.mats.size() + P.texs.size() + 2 * (((size_t)n + 3) / 4);
+    P.fast = s->cull_opt && s->fast_opt && P.n_clusters == 0 && n > 0 && s->tables_opt != 2 &&
+             fast_quads * 16 <= (s->tables_opt == 1 ? (size_t)RT_MAX_LDS_BYTES : (size_t)RT_LDS_TABLE_BYTES);
+    for (int i = 0; i < n; ++i)
+        if (!P.clustered[(size_t)i]) object_item(s, P, P.near_items, i);
+    P.b.near_first_leaf = (int)(P.near_items.size() / 2);
+    for (const LeafItem &l : P.leaf_items) leaf_item(P, P.near_items, l);
+    for (int i = sb; i < se; ++i)
+        if (!objs[i].is_light && !P.clustered[(size_t)i]) object_item(s, P, P.shadow_items, i);
+    P.b.shadow_first_leaf = (int)(P.shadow_items.size() / 2);
+    for (const LeafItem &l : P.leaf_items)
+        if (l.in_shadow) leaf_item(P, P.shadow_items, l);
+    if (!P.fast) return;
+    auto kind_rank = [&](int i) {
+        if (P.aa_rec_of[(size_t)i] >= 0) return P.aa_cls_of[(size_t)i];                 /* 0..2: AA rectangles by normal axis */
+        return objs[i].kind == RT_KIND_SPHERE ? 3 : objs[i].kind == RT_KIND_FINITE_PLANE ? 4 : 5;
+    };
+    std::vector<int> order;
+    for (int part = 0; part < 2; ++part)
+        for (int rank = 0; rank < 6; ++rank)
+            for (int i = 0; i < n; ++i) {
+                const bool in_shadow = i >= sb && i < se && !objs[i].is_light;
+                if ((part == 0) == in_shadow && kind_rank(i) == rank) order.push_back(i);
+            }
+    for (int i : order) {
+        const rt_object_desc &o = objs[i];
+        if (i >= sb && i < se && !o.is_light) ++P.fast_n_shadow;
+        std::vector<Quad> item;
+        object_item(s, P, item, i);
+        const int aa_rec = P.aa_rec_of[(size_t)i];
+        const uint32_t kind = aa_rec >= 0 ? (uint32_t)(RT_KIND_FINITE_AA + P.aa_cls_of[(size_t)i]) : (uint32_t)o.kind;
+        const uint32_t ctl = kind | ((uint32_t)i << 8);
+        uint32_t bits0; std::memcpy(&bits0, &item[0].v[3], 4);
+        item[0].v[3] = bits_to_float(kind | (bits0 & RT_ITEM_TIGHT));
+        item[1].v[3] = bits_to_float(ctl);
+        P.fast_boxes.push_back(item[0]);
+        P.fast_boxes.push_back(item[1]);
+        P.fast_ctl.push_back(ctl);
+        if (aa_rec >= 0) {
+            P.fast_recs.push_back(P.aa_recs[(size_t)aa_rec]);
+            P.fast_recs.push_back(P.aa_recs[(size_t)aa_rec + 1]);
+        } else if (o.kind == RT_KIND_SPHERE) {
+            P.fast_recs.push_back({{o.origin[0], o.origin[1], o.origin[2], o.radius_squared}});
+            P.fast_recs.push_back({{0, 0, 0, 0}});
+        } else {
+            P.fast_recs.push_back({{o.normal[0], o.normal[1], o.normal[2], o.distance_to_origin}});
+            P.fast_recs.push_back({{bits_to_float((uint32_t)P.geom_off[(size_t)i]), 0, 0, 0}});
+        }
+    }
+}
+
+/* append `count` 32-bit words, padded to whole quads; returns the first word's quad */
+int append_words(std::vector<Quad> &image, const uint32_t *words, size_t count) {
+    const int off = (int)image.size();
+    image.resize(image.size() + (count + 3) / 4, Quad{{0, 0, 0, 0}});
+    if (count) std::memcpy(image[(size_t)off].v, words, count * 4);
+    return off;
+}
+
+/* the image and its section offsets: the full records, then (item tables) the AA records and the clustered runs' Scene
+ * indices or (FAST tables) the FAST boxes and records, then the items, lights, materials, textures, per-object words and
+ * (FAST tables) the control words */
+void assemble_image(const rt_scene *s, Packing &P) {
+    const int n = (int)s->objects.size();
+    RtParams &b = P.b;
+    std::vector<Quad> &image = P.image;
+    image.assign(P.geom.begin(), P.geom.end());
+    if (P.fast) {
+        b.n_fast_items = (int)P.fast_ctl.size();
+        b.n_fast_shadow = P.fast_n_shadow;
         b.fast_box_off = (int)image.size();
-        image.insert(image.end(), fast_boxes.begin(), fast_boxes.end());
+        image.insert(image.end(), P.fast_boxes.begin(), P.fast_boxes.end());
         b.fast_rec_off = (int)image.size();
-        image.insert(image.end(), fast_recs.begin(), fast_recs.end());
-        near_items.clear();
-        shadow_items.clear();
+        image.insert(image.end(), P.fast_recs.begin(), P.fast_recs.end());
+        b.near_items_off = b.shadow_items_off = (int)image.size();
+        b.n_near_items = b.n_fast_items;
+        b.n_shadow_items = b.n_fast_shadow;
+    } else {
+        image.insert(image.end(), P.aa_recs.begin(), P.aa_recs.end());
+        append_words(image, P.cidx.data(), P.cidx.size());
+        b.near_items_off = (int)image.size();
+        b.n_near_items = (int)(P.near_items.size() / 2);
+        image.insert(image.end(), P.near_items.begin(), P.near_items.end());
+        b.shadow_items_off = (int)image.size();
+        b.n_shadow_items = (int)(P.shadow_items.size() / 2);
+        image.insert(image.end(), P.shadow_items.begin(), P.shadow_items.end());
     }
-    b.near_items_off = (int)image.size();
-    b.n_near_items = fast ? b.n_fast_items : (int)(near_items.size() / 2);
-    image.insert(image.end(), near_items.begin(), near_items.end());
-    b.shadow_items_off = (int)image.size();
-    b.n_shadow_items = fast ? b.n_fast_shadow : (int)(shadow_items.size() / 2);
-    image.insert(image.end(), shadow_items.begin(), shadow_items.end());
     b.lights_off = (int)image.size();
-    image.insert(image.end(), lights.begin(), lights.end());
+    image.insert(image.end(), P.lights.begin(), P.lights.end());
     b.mat_off = (int)image.size();
-    image.insert(image.end(), mats.begin(), mats.end());
+    image.insert(image.end(), P.mats.begin(), P.mats.end());
     b.tex_off = (int)image.size();
-    image.insert(image.end(), texs.begin(), texs.end());
-    b.objinfo_off = (int)image.size();
-    image.resize(image.size() + ((size_t)n + 3) / 4, Quad{{0, 0, 0, 0}});
-    if (n > 0) std::memcpy(image[(size_t)b.objinfo_off].v, objinfo.data(), (size_t)n * 4);
-    if (fast) {
-        b.fast_ctl_off = (int)image.size() * 4;
-        image.resize(image.size() + (fast_ctl.size() + 3) / 4, Quad{{0, 0, 0, 0}});
-        std::memcpy(image[(size_t)b.fast_ctl_off / 4].v, fast_ctl.data(), fast_ctl.size() * 4);
-    }
+    image.insert(image.end(), P.texs.begin(), P.texs.end());
+    std::vector<uint32_t> objinfo((size_t)n);
+    for (int i = 0; i < n; ++i)
+        objinfo[(size_t)i] = (uint32_t)P.geom_off[(size_t)i] | ((uint32_t)s->objects[(size_t)i].kind << 16) |
+                             ((uint32_t)P.mat_of[(size_t)i] << 20);
+    b.objinfo_off = append_words(image, objinfo.data(), objinfo.size());
+    if (P.fast) b.fast_ctl_off = append_words(image, P.fast_ctl.data(), P.fast_ctl.size()) * 4;
     if (image.empty()) image.push_back(Quad{{0, 0, 0, 0}});   /* keep uploads non-empty */
     b.image_quads = (int)image.size();
-    /* SHADOW VOXELS: behind the staged part; read from the global copy by the clustered-scene kernels */
-    b.svox_off = 0;
-    if (!fast && s->cull_opt && s->svox_opt != 0 && n_clusters > 0) {
-        ShadowVoxels sv;
-        /* automatic: from RT_SVOX_MIN_LEAVES leaves on.  With fewer the bundle cull leaves little to take away -- the 256-sphere
-         * grid (16 leaves) at depth 8: 3.8 -> 2.6 candidates per scan, frame 3.94 -> 4.03 ms with the table; the 1 024-sphere grid
-         * (43 leaves): 8.9 -> 4.4, 3.87 -> 3.71 ms (profiles/r04_experiments.txt 8) */
-        if (shadow_voxels(shadow_items, b.shadow_first_leaf, lights, s->svox_opt > 0 ? s->svox_opt : RT_SVOX_MAX_CELLS,
-                          s->svox_opt > 0 ? 4 : RT_SVOX_MIN_LEAVES, &sv)) {
-            b.svox_off = (int)image.size();
-            image.resize(image.size() + (sv.masks.size() + 1) / 2, Quad{{0, 0, 0, 0}});
-            std::memcpy(image[(size_t)b.svox_off].v, sv.masks.data(), sv.masks.size() * 8);
-            for (int k = 0; k < 3; ++k) { b.svox_n[k] = sv.n[k]; b.svox_lo[k] = sv.lo[k]; b.svox_scale[k] = sv.scale[k]; }
-        }
-    }
-    b.n_clusters = n_clusters;
-    b.n_lights = (int)(lights.size() / RT_LIGHT_QUADS);
+    b.n_clusters = P.n_clusters;
+    b.n_lights = (int)(P.lights.size() / RT_LIGHT_QUADS);
     for (int c = 0; c < 3; ++c) b.null_color[c] = s->null_color[c];
-    s->image.swap(image);
-    s->base = b;
-    s->n_clusters = n_clusters;
+}
+
+/* SHADOW VOXELS: behind the staged part; read from the global copy by the clustered-scene kernels */
+void pack_shadow_voxels(const rt_scene *s, Packing &P) {
+    if (P.fast || !s->cull_opt || s->svox_opt == 0 || P.n_clusters <= 0) return;
+    ShadowVoxels sv;
+    /* automatic: from RT_SVOX_MIN_LEAVES leaves on.  With fewer the bundle cull leaves little to take away -- the 256-sphere
+     * grid (16 leaves) at depth 8: 3.8 -> 2.6 candidates per scan, frame 3.94 -> 4.03 ms with the table; the 1 024-sphere grid
+     * (43 leaves): 8.9 -> 4.4, 3.87 -> 3.71 ms (profiles/r04_experiments.txt 8) */
+    if (!shadow_voxels(P.shadow_items, P.b.shadow_first_leaf, P.lights, s->svox_opt > 0 ? s->svox_opt : RT_SVOX_MAX_CELLS,
+                       s->svox_opt > 0 ? 4 : RT_SVOX_MIN_LEAVES, &sv))
+        return;
+    RtParams &b = P.b;
+    b.svox_off = (int)P.image.size();
+    P.image.resize(P.image.size() + (sv.masks.size() + 1) / 2, Quad{{0, 0, 0, 0}});
+    std::memcpy(P.image[(size_t)b.svox_off].v, sv.masks.data(), sv.masks.size() * 8);
+    for (int k = 0; k < 3; ++k) { b.svox_n[k] = sv.n[k]; b.svox_lo[k] = sv.lo[k]; b.svox_scale[k] = sv.scale[k]; }
+}
+
+/* Build the LDS image + run lists from the stored description; the handle changes only on success. */
+int pack_scene(rt_scene *s) {
+    Packing P((int)s->objects.size());
+    int rc = pack_materials_and_lights(s, P);
+    if (rc == RT_OK) rc = pack_runs_and_clusters(s, P);
+    if (rc) return rc;
+    pack_aa_records(s, P);
+    pack_items(s, P);
+    assemble_image(s, P);
+    pack_shadow_voxels(s, P);
+    s->image.swap(P.image);
+    s->base = P.b;
+    s->n_clusters = P.n_clusters;
     return RT_OK;
 }
 
@@ -1025,30 +1056,31 @@ bool primary_table(const rt_scene *s, const rt_camera_desc *cam, int W, int H, u
     return true;
 }
 
+int primary_quads(const rt_scene *s) {
+    return (s->primary_opt && s->base.n_fast_items > 0 && s->base.n_fast_items <= RT_PRIMARY_ITEMS) ? s->base.n_fast_items : 0;
+}
+
+struct BlockChoice { int block = 0, lds_bytes = 0, stack_lds_levels = 0; bool global_tables = false; };
+
 /* Workgroup size and where the bounce stack goes.  The stack is 16 B per level
  * per thread.  As many of its lowest levels as fit share LDS with the scene
  * tables while RT_STACK_LDS_SHARE workgroups per CU still fit in the 160 KiB
  * (nearly every reflection chain uses the first levels, few the deep ones); the
  * rest lives in HBM.  Option "stack": 1 = all of it in LDS, 2 = all in HBM. */
-int primary_quads(const rt_scene *s) {
-    return (s->primary_opt && s->base.n_fast_items > 0 && s->base.n_fast_items <= RT_PRIMARY_ITEMS) ? s->base.n_fast_items : 0;
-}
-
-int choose_block(const rt_scene *s, int max_depth, bool counting, int *block, int *lds_bytes, int *stack_lds_levels, bool *global_tables,
-                 int block_override = 0) {
+int choose_block(const rt_scene *s, int max_depth, bool counting, int block_override, BlockChoice *c) {
     /* Tables in LDS (staged once per workgroup), or -- large scenes -- left in global memory and read
      * through the L2 (rt_render_kernel_large): automatic beyond RT_LDS_TABLE_BYTES, where LDS would hold
      * fewer than two workgroups per CU; beyond 160 KiB it is the only way.  Option "tables". */
     /* (FAST tables carry this launch's PRIMARY table behind the image: one quad per item) */
-    size_t scene_bytes = ((size_t)s->base.image_quads + (primary_quads(s) > 0 ? (size_t)primary_quads(s) : 0)) * 16;
+    size_t scene_bytes = ((size_t)s->base.image_quads + (size_t)primary_quads(s)) * 16;
     /* the counting build has no global-memory variant: automatic means LDS for it whenever the tables fit at all */
-    *global_tables = s->tables_opt == 2 ||
-                     (s->tables_opt == 0 && scene_bytes > (counting ? (size_t)RT_MAX_LDS_BYTES : (size_t)RT_LDS_TABLE_BYTES));
-    if (!*global_tables && scene_bytes > RT_MAX_LDS_BYTES)
+    c->global_tables = s->tables_opt == 2 ||
+                       (s->tables_opt == 0 && scene_bytes > (counting ? (size_t)RT_MAX_LDS_BYTES : (size_t)RT_LDS_TABLE_BYTES));
+    if (!c->global_tables && scene_bytes > RT_MAX_LDS_BYTES)
         return fail(RT_ERR_CAPACITY, "option tables=1: the scene tables do not fit in LDS (160 KiB)");
-    if (*global_tables) scene_bytes = 0;
-    *block = block_override ? block_override : (s->block_threads_opt ? s->block_threads_opt : 256);
-    const double per_level = (double)RT_STACK_ENTRY_BYTES * (double)*block;
+    if (c->global_tables) scene_bytes = 0;
+    c->block = block_override ? block_override : (s->block_threads_opt ? s->block_threads_opt : 256);
+    const double per_level = (double)RT_STACK_ENTRY_BYTES * (double)c->block;
     /* levels 0 .. max_depth - 1 can push an entry (the last level's reflection is folded where it is found: rt_kernel.hip) */
     const double levels = (double)max_depth;
     double in_lds = 0.0;
@@ -1059,14 +1091,272 @@ int choose_block(const rt_scene *s, int max_depth, bool counting, int *block, in
     } else if (s->stack_opt == 0) {
         /* the clustered-scene kernels run six wavefronts per SIMD (80 registers, no spills), the others seven */
         const int share256 = (s->n_clusters > 0 && s->pairs_opt && s->cull_opt) ? 6 : RT_STACK_LDS_SHARE;
-        const int share = std::max(1, share256 * 256 / *block);       /* (workgroups per CU: the same wavefronts in larger ones) */
+        const int share = std::max(1, share256 * 256 / c->block);      /* (workgroups per CU: the same wavefronts in larger ones) */
         const double room = (double)(RT_MAX_LDS_BYTES / share) - (double)scene_bytes;
         in_lds = room > 0.0 ? std::floor(room / per_level) : 0.0;
         if (in_lds > levels) in_lds = levels;
     }
-    *stack_lds_levels = (int)in_lds;
-    *lds_bytes = (int)((double)scene_bytes + in_lds * per_level);
-    if (*lds_bytes < 16) *lds_bytes = 16;
+    c->stack_lds_levels = (int)in_lds;
+    c->lds_bytes = (int)((double)scene_bytes + in_lds * per_level);
+    if (c->lds_bytes < 16) c->lds_bytes = 16;
+    return RT_OK;
+}
+
+/* The launch's workgroup: choose_block(), and for scenes with clustered runs the widening to 512 threads where it pays. */
+int launch_block(const rt_scene *s, int W, int x0, int x1, int max_depth, bool counting, BlockChoice *c) {
+    int rc = choose_block(s, max_depth, counting, 0, c);
+    if (rc) return rc;
+    if (c->global_tables && counting)
+        return fail(RT_ERR_CAPACITY, s->tables_opt == 2
+                        ? "the counting build keeps the tables in LDS: set option tables to 0 or 1 for it"
+                        : "the counting build keeps the tables in LDS: this scene's exceed 160 KiB");
+    /* Scenes with clustered runs whose tables are large (the 1 024-sphere grid: 28 KB): five workgroups of four wavefronts are
+     * all that LDS admits per CU, five wavefronts per SIMD.  Workgroups of EIGHT wavefronts share one copy of the tables among
+     * twice as many: three of them fit with room for bounce-stack levels, six wavefronts per SIMD in the 80-register kernel
+     * (grid-32 frame 4.49 -> 4.36 ms, longest of 8 strips 0.98 -> 0.93 ms on one box, profiles/r04_experiments.txt 1).  Only
+     * where it raises the occupancy: with small tables the larger workgroup gains one LDS stack level and loses in strips
+     * (seven of eight wavefronts stand at the desk of a HEAVY tile). */
+    /* Small tables and a deep recursion (the 256-sphere grid at depth 8), WHOLE frames: eight-wavefront workgroups at the same six
+     * wavefronts per SIMD keep one bounce-stack level more in LDS (one copy of the tables less per CU), and every level that
+     * stays out of HBM takes a row per workgroup out of a working set that is as large as the XCD's L2 (HBM traffic of that
+     * frame 7.0 -> 5.x times the algorithmic bytes at the same frame time; strips keep four wavefronts per workgroup: seven
+     * helpers at the desk of a HEAVY tile lose more than the level gains).  profiles/r04_experiments.txt 4 */
+    if (counting || c->global_tables || s->block_threads_opt != 0 || s->n_clusters <= 0 || !s->pairs_opt || s->wide_opt >= 0)
+        return RT_OK;
+    const bool few_waves = (RT_MAX_LDS_BYTES / (size_t)c->lds_bytes) * 4 < 24;
+    const bool whole_frame = (long long)(x1 - x0) * 4 > (long long)W * 3;
+    if (few_waves || (whole_frame && c->stack_lds_levels < max_depth)) {
+        BlockChoice wide;
+        if (choose_block(s, max_depth, false, 512, &wide) == RT_OK && !wide.global_tables &&
+            (RT_MAX_LDS_BYTES / (size_t)wide.lds_bytes) * 8 >= 24 && (few_waves || wide.stack_lds_levels > c->stack_lds_levels))
+            *c = wide;
+    }
+    return RT_OK;
+}
+
+int check_launch_args(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *d_out) {
+    if (!cam) return fail(RT_ERR_INVALID, "camera is NULL");
+    if (W <= 0 || H <= 0) return fail(RT_ERR_INVALID, "W and H must be positive");
+    if (x0 < 0 || x1 > W || x0 > x1) return fail(RT_ERR_INVALID, "need 0 <= x0 <= x1 <= W");
+    if (max_depth < 0) return fail(RT_ERR_INVALID, "max_depth < 0");
+    if (!d_out && x1 > x0) return fail(RT_ERR_INVALID, "output pointer is NULL");
+    if ((double)(x1 - x0) * (double)H * 3.0 > 2.0e9 * 4.0)
+        return fail(RT_ERR_INVALID, "strip too large");
+    return RT_OK;
+}
+
+void camera_params(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, RtParams &p) {
+    for (int c = 0; c < 3; ++c) {
+        p.so[c] = cam->screen_origin[c];
+        p.ch[c] = cam->vector_horizontal[c];
+        p.cv[c] = cam->vector_vertical[c];
+        p.eye[c] = cam->eye_origin[c];
+    }
+    p.sw = cam->screen_width; p.sh = cam->screen_height;
+    p.shw = cam->screen_halfwidth; p.shh = cam->screen_halfheight;
+    p.W = W; p.H = H; p.x0 = x0; p.x1 = x1; p.max_depth = max_depth;
+}
+
+/* Wavefront tile shape (speed only).  4 x 16 (x by z) makes every lane-row's
+ * stores whole 64-byte sectors (16 pixels x 12 B = 192 B, aligned): measured
+ * WRITE_SIZE = 1.08 x the framebuffer bytes vs 1.27 x for 16 x 4.  On the
+ * sphere-grid scenes the wider 16 x 4 tile diverges less and is 5-7 % faster,
+ * while on small scenes the two run alike; hence the default. */
+struct TileShape { int z_log2, x, z; long long tiles_x, tiles_z; };
+
+TileShape tile_shape(const rt_scene *s, int H, int x0, int x1) {
+    TileShape t;
+    t.z_log2 = s->tile_z_log2 >= 0 ? s->tile_z_log2 : (s->objects.size() <= 128 ? 4 : 2);
+    t.z = 1 << t.z_log2;
+    t.x = 64 >> t.z_log2;
+    t.tiles_z = ((long long)H + t.z - 1) / t.z;
+    t.tiles_x = ((long long)(x1 - x0) + t.x - 1) / t.x;
+    return t;
+}
+
+/* Automatic order for scenes with a horizon and clustered sphere runs: start a little ABOVE the horizon row and go DOWN -- the
+ * horizon rows are the most expensive of the frame, the rows below them (the ground, with the spheres on it) get cheaper
+ * towards the bottom, and the rows above the horizon, which come last after the wrap-around, are the cheapest: the queues then
+ * hand out tiles roughly in order of decreasing cost, which keeps the tail of a frame -- or of a GPU's strip of it -- short.
+ * "first_row" given: from there upwards. */
+void start_row(const rt_scene *s, const rt_camera_desc *cam, long long tiles_z, RtParams &p) {
+    const long long macro_rows = (tiles_z + RT_MACRO_ROWS - 1) / RT_MACRO_ROWS;
+    const int horizon = horizon_start(s, cam);                    /* thousandths of the image height; 8 below the horizon row; 0 = none */
+    const bool automatic = s->first_row_permille < 0 && horizon > 0;
+    const int permille = s->first_row_permille >= 0 ? s->first_row_permille : (automatic ? std::min(999, horizon + 8 + 30) : 0);
+    p.rows_downwards = automatic ? 1 : 0;
+    p.first_macro_row = (int)std::min(macro_rows - 1, macro_rows * (long long)permille / 1000);
+    if (p.first_macro_row < 0) p.first_macro_row = 0;
+}
+
+/* HELP (rt_kernel.hip): the clustered-scene kernels keep a desk of a few LDS words behind tables and stack.  Automatic: for
+ * launches of at most three quarters of the image's width.  The owners' look at the desk before every long shadow scan costs
+ * a whole frame 1-1.4 % (grid-32 4.55 -> 4.49 ms, grid-16 d8 4.22 -> 4.17 without it), and a whole frame has tiles enough to
+ * end well without help; a strip does not (longest of 2 / 4 strips of the grid-32 frame: 2.79 / 1.53 ms with help, 3.10 /
+ * 2.28 without).  profiles/r03_experiments.txt 16 */
+void help_desk(const rt_scene *s, bool clusters_kernel, int W, int x0, int x1, int block, int stack_lds_levels, RtParams &p,
+               int *lds_bytes) {
+    p.desk_off = 0;
+    p.help_rays_quads = 0;
+    p.help_leaves = s->help_opt >= 2 ? s->help_opt : RT_HELP_LEAVES;
+    p.help_spin_limit = s->help_spin_opt;
+    const bool help_wanted = s->help_opt > 0 || (s->help_opt < 0 && (long long)(x1 - x0) * 4 <= (long long)W * 3);
+    if (!clusters_kernel || !help_wanted || block <= 64) return;
+    const int desk_off = p.stack_off + stack_lds_levels * block;
+    const int with_desk = (desk_off + (RT_DESK_WORDS * 4 + 15) / 16) * 16;
+    if ((size_t)with_desk <= RT_MAX_LDS_BYTES) {
+        p.desk_off = desk_off;
+        p.help_rays_quads = 128;
+        *lds_bytes = with_desk;
+    }
+}
+
+/* OLD TILES FIRST, automatic: for strips of up to three fifths of the width -- halves re-cut by cost included.  Longest of 2
+ * strips with / without: grid-32 2.48 / 2.66 ms, grid-16 d8 2.36 / 2.44, built-in 0.410 / 0.428; of 4: 1.50 / 1.52, 1.38 /
+ * 1.44, 0.274 / 0.323; whole frames lose 0.3-0.8 % to it */
+int tile_prio(const rt_scene *s, int W, int x0, int x1) {
+    return s->tile_prio_opt >= 0 ? s->tile_prio_opt : ((long long)(x1 - x0) * 5 <= (long long)W * 3 ? 1 : 0);
+}
+
+/* HEAVY tiles (rt_kernel.hip, render_body): with HELP on, the band of tile rows along the horizon line.  Automatic: only when
+ * the launch renders a strip of at most a third of the image's width -- one GPU's share on three or more.  There the strip
+ * waits for its horizon tiles (4096^2, 1 024-sphere grid, longest of 8 strips: 1.39 -> 1.05 ms with the band, 4 strips 1.68 ->
+ * 1.63 ms); a whole frame has enough other tiles to run beside them, and giving three of a workgroup's four wavefronts to one
+ * tile only costs it throughput (4.83 -> 5.02 ms; with a band of 0.9 % of the height 5.32 ms).  profiles/r03_experiments.txt */
+void heavy_band(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, const TileShape &t, RtParams &p) {
+    p.heavy_half = -1;
+    p.heavy_row0_q16 = p.heavy_slope_q16 = 0;
+    const bool heavy_wanted = s->heavy_opt > 0 || (s->heavy_opt < 0 && (long long)(x1 - x0) * 3 <= (long long)W);
+    if (p.help_rays_quads == 0 || !heavy_wanted) return;
+    double dz_centre = 0.0;
+    const rt_object_desc *plane = horizon_plane(s, cam, &dz_centre);
+    if (!plane) return;
+    /* tile row (as a real number) of the line at the centre of tile column c: linear in c */
+    auto row_at = [&](double c, double *row) {
+        double dz;
+        if (!horizon_dz(*plane, cam, ((double)x0 + (c + 0.5) * t.x) / (double)W, &dz)) return false;
+        *row = dz * (double)H / (double)t.z;
+        return true;
+    };
+    double r0, r1;
+    const double c1 = (double)std::max<long long>(t.tiles_x - 1, 1);
+    if (row_at(0.0, &r0) && row_at(c1, &r1) && std::fabs(r0) < 30000.0 && std::fabs(r1) < 30000.0) {
+        p.heavy_half = s->heavy_opt > 0 ? s->heavy_opt - 1 : (int)std::ceil((double)RT_HEAVY_PERMILLE10 * 1e-4 * (double)H / (double)t.z);
+        p.heavy_row0_q16 = (int)std::floor(r0 * 65536.0);
+        p.heavy_slope_q16 = (int)std::lround((r1 - r0) / c1 * 65536.0);
+    }
+}
+
+/* LEARNED START ROW (rt_learn_tile_order): the queues start a little before the macro row that held the longest tile of the
+ * counting frame -- outside the HEAVY band, whose tiles have their own queue -- and sweep towards the side where most of the
+ * frame's cost lies (rows in image order: long and short tiles stay interleaved on the SIMDs; rows sorted by cost measured
+ * slower, profiles/r03_experiments.txt 23).  Only for the launch shape the order was learned from. */
+void learned_start_row(const rt_scene *s, int W, int H, int x0, int x1, int max_depth, const TileShape &t, RtParams &p) {
+    const int key[6] = {W, H, x0, x1, max_depth, t.z_log2};
+    const long long macro_rows = (t.tiles_z + RT_MACRO_ROWS - 1) / RT_MACRO_ROWS;
+    if (s->first_row_permille >= 0 || s->learned_sweep < 0 || s->row_peak.size() != (size_t)macro_rows ||
+        !std::equal(key, key + 6, s->order_key))
+        return;
+    long long best = -1;
+    double total = 0.0;
+    for (long long m = 0; m < macro_rows; ++m) {
+        bool in_band = false;
+        if (p.heavy_half >= 0) {
+            const int mid_col = (int)(t.tiles_x / 2);
+            const int line = (p.heavy_row0_q16 + mid_col * p.heavy_slope_q16) >> 16;
+            const long long lo = (line - p.heavy_half - 1) / RT_MACRO_ROWS, hi = (line + p.heavy_half + 1) / RT_MACRO_ROWS;
+            in_band = m >= lo && m <= hi;
+        }
+        total += s->row_sum[(size_t)m];
+        if (!in_band && (best < 0 || s->row_peak[(size_t)m] > s->row_peak[(size_t)best])) best = m;
+    }
+    if (best >= 0 && total > 0.0) {
+        const bool upwards = s->learned_sweep == 0;
+        p.rows_downwards = upwards ? 0 : 1;
+        const long long margin = std::max<long long>(1, macro_rows / 64);
+        p.first_macro_row = (int)std::min(macro_rows - 1, std::max<long long>(0, upwards ? best - margin : best + margin));
+    }
+}
+
+struct Kernel { const void *fn; const char *name; };
+#define RT_KERNEL(k) Kernel{(const void *)k, #k}
+
+/* the kernel: FAST tables, item tables, the one for clustered scenes (in the register budget that fits the occupancy LDS
+ * allows), or the large-scene one */
+Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int block, int lds_bytes) {
+    const bool fast_tables = s->base.n_fast_items > 0;
+    if (counting) return fast_tables ? RT_KERNEL(rt_render_kernel_fast_stats) : RT_KERNEL(rt_render_kernel_stats);
+    if (global_tables) return RT_KERNEL(rt_render_kernel_large);
+    if (s->n_clusters > 0 && s->pairs_opt) {
+        /* the 96-register kernel when LDS leaves room for fewer than six wavefronts per SIMD anyway (24 per CU) */
+        const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
+        return wide ? RT_KERNEL(rt_render_kernel_clusters_wide) : RT_KERNEL(rt_render_kernel_clusters);
+    }
+    return fast_tables ? RT_KERNEL(rt_render_kernel) : RT_KERNEL(rt_render_kernel_items);
+}
+
+/* Everything a launch decides before it touches the device. */
+struct LaunchPlan {
+    RtParams p{};                 /* all but the device addresses (timeline, error word, next counters) */
+    Kernel kernel{nullptr, nullptr};   /* (none for an empty strip) */
+    int block = 0, lds_bytes = 0, scene_lds_bytes = 0, stack_lds_levels = 0;
+    TileShape tiles{};
+    long long n_tiles = 0;
+    bool help = false;            /* the launch carries HELP areas (p.help_rays_quads != 0) */
+};
+
+/* Host-only: the checks and every decision of a launch, in this order.  An empty strip is planned up to its tile count. */
+int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *d_out,
+                bool counting, LaunchPlan *plan) {
+    int rc = check_launch_args(cam, W, H, x0, x1, max_depth, d_out);
+    if (rc) return rc;
+    BlockChoice bc;
+    rc = launch_block(s, W, x0, x1, max_depth, counting, &bc);
+    if (rc) return rc;
+    RtParams &p = plan->p;
+    p = s->base;
+    camera_params(cam, W, H, x0, x1, max_depth, p);
+    p.stack_lds_levels = bc.stack_lds_levels;
+    p.stack_stride = bc.block;
+    p.n_primary = 0;
+    p.primary_off = s->base.image_quads;
+    if (!bc.global_tables && primary_quads(s) > 0 && primary_table(s, cam, W, H, p.primary)) p.n_primary = primary_quads(s);
+    /* (the LDS place of the table is reserved whether or not this camera admits one) */
+    p.stack_off = bc.global_tables ? 0 : s->base.image_quads + primary_quads(s);
+    p.cull = s->cull_opt;
+    const TileShape t = tile_shape(s, H, x0, x1);
+    const long long n_tiles = t.tiles_z * t.tiles_x;
+    if (n_tiles > 0x7fffffffLL) return fail(RT_ERR_INVALID, "too many tiles");
+    p.tile_z_log2 = t.z_log2;
+    p.tiles_z = (int)t.tiles_z;
+    p.tiles_x = (int)t.tiles_x;
+    p.n_tiles = (int)n_tiles;
+    start_row(s, cam, t.tiles_z, p);
+    plan->block = bc.block;
+    plan->lds_bytes = bc.lds_bytes;
+    plan->scene_lds_bytes = bc.global_tables ? 0 : (s->base.image_quads + primary_quads(s)) * 16;
+    plan->stack_lds_levels = bc.stack_lds_levels;
+    plan->tiles = t;
+    plan->n_tiles = n_tiles;
+    if (n_tiles == 0) return RT_OK;
+    const bool clusters_kernel = !counting && !bc.global_tables && s->n_clusters > 0 && s->pairs_opt;
+    help_desk(s, clusters_kernel, W, x0, x1, bc.block, bc.stack_lds_levels, p, &plan->lds_bytes);
+    p.tile_prio = tile_prio(s, W, x0, x1);
+    heavy_band(s, cam, W, H, x0, x1, t, p);
+    if (!counting) learned_start_row(s, W, H, x0, x1, max_depth, t, p);
+    plan->kernel = choose_kernel(s, counting, bc.global_tables, bc.block, plan->lds_bytes);
+    plan->help = p.help_rays_quads != 0;
+    return RT_OK;
+}
+
+/* A device buffer of the handle that only grows.  Launches in flight may still use the old one: the device is synchronised
+ * before it is freed. */
+int grow_device_buffer(void **buf, size_t *bytes, size_t need) {
+    if (need <= *bytes) return RT_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    if (*buf) { HIP_TRY(hipFree(*buf)); *buf = nullptr; *bytes = 0; }
+    HIP_TRY(hipMalloc(buf, need));
+    *bytes = need;
     return RT_OK;
 }
 
@@ -1080,113 +1370,25 @@ int device_report(rt_scene *s) {
     return RT_OK;
 }
 
+/* plan_launch(), then the device work: counters, timeline, occupancy and grid, bounce stack and HELP areas, the event ring */
 int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
            float *d_out, hipStream_t stream, unsigned long long *d_stats = nullptr) {
-    if (!cam) return fail(RT_ERR_INVALID, "camera is NULL");
-    if (W <= 0 || H <= 0) return fail(RT_ERR_INVALID, "W and H must be positive");
-    if (x0 < 0 || x1 > W || x0 > x1) return fail(RT_ERR_INVALID, "need 0 <= x0 <= x1 <= W");
-    if (max_depth < 0) return fail(RT_ERR_INVALID, "max_depth < 0");
-    if (!d_out && x1 > x0) return fail(RT_ERR_INVALID, "output pointer is NULL");
-    if ((double)(x1 - x0) * (double)H * 3.0 > 2.0e9 * 4.0)
-        return fail(RT_ERR_INVALID, "strip too large");
-
-    int block = 0, lds_bytes = 0, stack_lds_levels = 0;
-    bool global_tables = false;
-    int rc = choose_block(s, max_depth, d_stats != nullptr, &block, &lds_bytes, &stack_lds_levels, &global_tables);
+    LaunchPlan plan;
+    int rc = plan_launch(s, cam, W, H, x0, x1, max_depth, d_out, d_stats != nullptr, &plan);
     if (rc) return rc;
-    /* Scenes with clustered runs whose tables are large (the 1 024-sphere grid: 28 KB): five workgroups of four wavefronts are
-     * all that LDS admits per CU, five wavefronts per SIMD.  Workgroups of EIGHT wavefronts share one copy of the tables among
-     * twice as many: three of them fit with room for bounce-stack levels, six wavefronts per SIMD in the 80-register kernel
-     * (grid-32 frame 4.49 -> 4.36 ms, longest of 8 strips 0.98 -> 0.93 ms on one box, profiles/r04_experiments.txt 1).  Only
-     * where it raises the occupancy: with small tables the larger workgroup gains one LDS stack level and loses in strips
-     * (seven of eight wavefronts stand at the desk of a HEAVY tile). */
-    /* Small tables and a deep recursion (the 256-sphere grid at depth 8), WHOLE frames: eight-wavefront workgroups at the same six
-     * wavefronts per SIMD keep one bounce-stack level more in LDS (one copy of the tables less per CU), and every level that
-     * stays out of HBM takes a row per workgroup out of a working set that is as large as the XCD's L2 (HBM traffic of that
-     * frame 7.0 -> 5.x times the algorithmic bytes at the same frame time; strips keep four wavefronts per workgroup: seven
-     * helpers at the desk of a HEAVY tile lose more than the level gains).  profiles/r04_experiments.txt 4 */
-    if (!d_stats && !global_tables && s->block_threads_opt == 0 && s->n_clusters > 0 && s->pairs_opt && s->wide_opt < 0) {
-        const bool few_waves = (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * 4 < 24;
-        const bool whole_frame = (long long)(x1 - x0) * 4 > (long long)W * 3;
-        if (few_waves || (whole_frame && stack_lds_levels < max_depth)) {
-            int block2 = 0, lds2 = 0, levels2 = 0;
-            bool global2 = false;
-            if (choose_block(s, max_depth, false, &block2, &lds2, &levels2, &global2, 512) == RT_OK && !global2 &&
-                (RT_MAX_LDS_BYTES / (size_t)lds2) * 8 >= 24 && (few_waves || levels2 > stack_lds_levels)) {
-                block = block2; lds_bytes = lds2; stack_lds_levels = levels2;
-            }
-        }
-    }
-    if (global_tables && d_stats)
-        return fail(RT_ERR_CAPACITY, s->tables_opt == 2
-                        ? "the counting build keeps the tables in LDS: set option tables to 0 or 1 for it"
-                        : "the counting build keeps the tables in LDS: this scene's exceed 160 KiB");
-
-    RtParams p = s->base;
-    for (int c = 0; c < 3; ++c) {
-        p.so[c] = cam->screen_origin[c];
-        p.ch[c] = cam->vector_horizontal[c];
-        p.cv[c] = cam->vector_vertical[c];
-        p.eye[c] = cam->eye_origin[c];
-    }
-    p.sw = cam->screen_width; p.sh = cam->screen_height;
-    p.shw = cam->screen_halfwidth; p.shh = cam->screen_halfheight;
-    p.W = W; p.H = H; p.x0 = x0; p.x1 = x1; p.max_depth = max_depth;
-    p.stack_lds_levels = stack_lds_levels;
-    p.stack_stride = block;
-    p.n_primary = 0;
-    p.primary_off = s->base.image_quads;
-    if (!global_tables && primary_quads(s) > 0 && primary_table(s, cam, W, H, p.primary)) p.n_primary = primary_quads(s);
-    /* (the LDS place of the table is reserved whether or not this camera admits one) */
-    p.stack_off = global_tables ? 0 : s->base.image_quads + primary_quads(s);
-    p.cull = s->cull_opt;
-    /* Wavefront tile shape (speed only).  4 x 16 (x by z) makes every lane-row's
-     * stores whole 64-byte sectors (16 pixels x 12 B = 192 B, aligned): measured
-     * WRITE_SIZE = 1.08 x the framebuffer bytes vs 1.27 x for 16 x 4.  On the
-     * sphere-grid scenes the wider 16 x 4 tile diverges less and is 5-7 % faster,
-     * while on small scenes the two run alike; hence the default. */
-    const int tile_z_log2 = s->tile_z_log2 >= 0 ? s->tile_z_log2 : (s->objects.size() <= 128 ? 4 : 2);
-    p.tile_z_log2 = tile_z_log2;
-    const int tile_z = 1 << tile_z_log2, tile_x = 64 >> tile_z_log2;
-    const long long tiles_z = ((long long)H + tile_z - 1) / tile_z;
-    const long long tiles_x = ((long long)(x1 - x0) + tile_x - 1) / tile_x;
-    const long long n_tiles = tiles_z * tiles_x;
-    if (n_tiles > 0x7fffffffLL) return fail(RT_ERR_INVALID, "too many tiles");
-    p.tiles_z = (int)tiles_z;
-    p.tiles_x = (int)tiles_x;
-    {
-        const long long macro_rows = (tiles_z + RT_MACRO_ROWS - 1) / RT_MACRO_ROWS;
-        /* Automatic order for scenes with a horizon and clustered sphere runs: start a little ABOVE the
-         * horizon row and go DOWN -- the horizon rows are the most expensive of the frame, the rows
-         * below them (the ground, with the spheres on it) get cheaper towards the bottom, and the rows
-         * above the horizon, which come last after the wrap-around, are the cheapest: the queues then
-         * hand out tiles roughly in order of decreasing cost, which keeps the tail of a frame -- or of
-         * a GPU's strip of it -- short.  "first_row" given: from there upwards, as before. */
-        const int horizon = horizon_start(s, cam);                    /* thousandths of the image height; 8 below the horizon row; 0 = none */
-        const bool automatic = s->first_row_permille < 0 && horizon > 0;
-        const int permille = s->first_row_permille >= 0 ? s->first_row_permille : (automatic ? std::min(999, horizon + 8 + 30) : 0);
-        p.rows_downwards = automatic ? 1 : 0;
-        p.first_macro_row = (int)std::min(macro_rows - 1, macro_rows * (long long)permille / 1000);
-        if (p.first_macro_row < 0) p.first_macro_row = 0;
-    }
-    p.n_tiles = (int)n_tiles;
-    const int waves_per_block = block / 64;
-    const long long blocks_all = (n_tiles + waves_per_block - 1) / waves_per_block;
-
+    RtParams &p = plan.p;
+    const int block = plan.block;
     s->launch.block_threads = block;
-    s->launch.lds_bytes = lds_bytes;
-    s->launch.scene_lds_bytes = global_tables ? 0 : (s->base.image_quads + primary_quads(s)) * 16;
-    s->launch.tile_x = tile_x;
-    s->launch.tile_z = tile_z;
+    s->launch.lds_bytes = plan.lds_bytes;
+    s->launch.scene_lds_bytes = plan.scene_lds_bytes;
+    s->launch.tile_x = plan.tiles.x;
+    s->launch.tile_z = plan.tiles.z;
     s->launch.grid_blocks = 0;
-    if (blocks_all == 0) return RT_OK;
+    if (plan.n_tiles == 0) return RT_OK;
 
     HIP_TRY(hipSetDevice(s->device));
     rc = ensure_events(s);
     if (rc) return rc;
-    /* persistent grid: as many workgroups as the chip holds at once (by the
-     * occupancy query; a larger grid would also be correct, its surplus
-     * workgroups simply find the queue empty), never more than there are tiles */
     if (!s->d_counters) {
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_counters),
                           (size_t)kEventRing * kCounterWords * sizeof(unsigned int)));
@@ -1197,167 +1399,51 @@ int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1,
         HIP_TRY(hipGetDeviceProperties(&prop, s->device));
         s->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
-    /* the kernel: FAST tables, item tables, the one for clustered scenes (in the register budget that fits the
-     * occupancy LDS allows), or the large-scene one */
-    /* HELP (rt_kernel.hip): the clustered-scene kernels keep a desk of a few LDS words behind tables and stack */
-    const bool clusters_kernel = !d_stats && !global_tables && s->n_clusters > 0 && s->pairs_opt;
-    p.desk_off = 0;
-    p.help_rays_quads = 0;
-    p.help_leaves = s->help_opt >= 2 ? s->help_opt : RT_HELP_LEAVES;
-    /* automatic: for launches of at most three quarters of the image's width.  The owners' look at the desk before every long
-     * shadow scan costs a whole frame 1-1.4 % (grid-32 4.55 -> 4.49 ms, grid-16 d8 4.22 -> 4.17 without it), and a whole frame
-     * has tiles enough to end well without help; a strip does not (longest of 2 / 4 strips of the grid-32 frame: 2.79 / 1.53 ms
-     * with help, 3.10 / 2.28 without).  profiles/r03_experiments.txt 16 */
-    const bool help_wanted = s->help_opt > 0 || (s->help_opt < 0 && (long long)(x1 - x0) * 4 <= (long long)W * 3);
-    if (clusters_kernel && help_wanted && block > 64) {
-        const int desk_off = p.stack_off + stack_lds_levels * block;
-        const int with_desk = (desk_off + (RT_DESK_WORDS * 4 + 15) / 16) * 16;
-        if ((size_t)with_desk <= RT_MAX_LDS_BYTES) {
-            p.desk_off = desk_off;
-            p.help_rays_quads = 128;
-            lds_bytes = with_desk;
-            s->launch.lds_bytes = lds_bytes;
-        }
-    }
-    /* HEAVY tiles (rt_kernel.hip, render_body): with HELP on, the band of tile rows along the horizon line */
-    p.heavy_half = -1;
-    p.heavy_row0_q16 = p.heavy_slope_q16 = 0;
-    p.help_spin_limit = s->help_spin_opt;
     p.timeline = 0;
     if (s->timeline_opt) {
-        const size_t words = (size_t)n_tiles * RT_TIMELINE_WORDS;
-        if (words > s->timeline_words) {
-            HIP_TRY(hipSetDevice(s->device));
-            HIP_TRY(hipDeviceSynchronize());
-            if (s->d_timeline) { HIP_TRY(hipFree(s->d_timeline)); s->d_timeline = nullptr; s->timeline_words = 0; }
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_timeline), words * sizeof(unsigned long long)));
-            s->timeline_words = words;
-        }
-        HIP_TRY(hipMemsetAsync(s->d_timeline, 0, words * sizeof(unsigned long long), stream));
-        s->timeline_valid = words;
+        const size_t bytes = (size_t)plan.n_tiles * RT_TIMELINE_WORDS * sizeof(unsigned long long);
+        rc = grow_device_buffer(&s->d_timeline, &s->d_timeline_bytes, bytes);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(s->d_timeline, 0, bytes, stream));
+        s->timeline_valid = (size_t)plan.n_tiles * RT_TIMELINE_WORDS;
         p.timeline = (uint64_t)(uintptr_t)s->d_timeline;
     }
     p.error_word = (uint64_t)(uintptr_t)s->h_error;
-    /* automatic: only when the launch renders a strip of at most a third of the image's width -- one GPU's share on three
-     * or more.  There the strip waits for its horizon tiles (4096^2, 1 024-sphere grid, longest of 8 strips: 1.39 -> 1.05 ms
-     * with the band, 4 strips 1.68 -> 1.63 ms); a whole frame has enough other tiles to run beside them, and giving three
-     * of a workgroup's four wavefronts to one tile only costs it throughput (4.83 -> 5.02 ms; with a band of 0.9 % of the
-     * height 5.32 ms).  profiles/r03_experiments.txt */
-    /* (automatic: for strips of up to three fifths of the width -- halves re-cut by cost included.  Longest of 2 strips with /
-     * without: grid-32 2.48 / 2.66 ms, grid-16 d8 2.36 / 2.44, built-in 0.410 / 0.428; of 4: 1.50 / 1.52, 1.38 / 1.44, 0.274 /
-     * 0.323; whole frames lose 0.3-0.8 % to it) */
-    p.tile_prio = s->tile_prio_opt >= 0 ? s->tile_prio_opt : ((long long)(x1 - x0) * 5 <= (long long)W * 3 ? 1 : 0);
-    const bool heavy_wanted = s->heavy_opt > 0 || (s->heavy_opt < 0 && (long long)(x1 - x0) * 3 <= (long long)W);
-    if (p.help_rays_quads != 0 && heavy_wanted) {
-        double dz_centre = 0.0;
-        if (const rt_object_desc *plane = horizon_plane(s, cam, &dz_centre)) {
-            /* tile row (as a real number) of the line at the centre of tile column c: linear in c */
-            auto row_at = [&](double c, double *row) {
-                double dz;
-                if (!horizon_dz(*plane, cam, ((double)x0 + (c + 0.5) * tile_x) / (double)W, &dz)) return false;
-                *row = dz * (double)H / (double)tile_z;
-                return true;
-            };
-            double r0, r1;
-            const double c1 = (double)std::max<long long>(tiles_x - 1, 1);
-            if (row_at(0.0, &r0) && row_at(c1, &r1) && std::fabs(r0) < 30000.0 && std::fabs(r1) < 30000.0) {
-                p.heavy_half = s->heavy_opt > 0 ? s->heavy_opt - 1
-                                                : (int)std::ceil((double)RT_HEAVY_PERMILLE10 * 1e-4 * (double)H / (double)tile_z);
-                p.heavy_row0_q16 = (int)std::floor(r0 * 65536.0);
-                p.heavy_slope_q16 = (int)std::lround((r1 - r0) / c1 * 65536.0);
-            }
-        }
-    }
-    /* LEARNED START ROW (rt_learn_tile_order): the queues start a little before the macro row that held the longest tile of the
-     * counting frame -- outside the HEAVY band, whose tiles have their own queue -- and sweep towards the side where most of the
-     * frame's cost lies (rows in image order: long and short tiles stay interleaved on the SIMDs; rows sorted by cost measured
-     * slower, profiles/r03_experiments.txt 23) */
-    {
-        const int key[6] = {W, H, x0, x1, max_depth, tile_z_log2};
-        const long long macro_rows = (tiles_z + RT_MACRO_ROWS - 1) / RT_MACRO_ROWS;
-        if (!d_stats && s->first_row_permille < 0 && s->learned_sweep >= 0 && s->row_peak.size() == (size_t)macro_rows &&
-            std::equal(key, key + 6, s->order_key)) {
-            long long best = -1;
-            double weighted = 0.0, total = 0.0;
-            for (long long m = 0; m < macro_rows; ++m) {
-                bool in_band = false;
-                if (p.heavy_half >= 0) {
-                    const int mid_col = (int)(tiles_x / 2);
-                    const int line = (p.heavy_row0_q16 + mid_col * p.heavy_slope_q16) >> 16;
-                    const long long lo = (line - p.heavy_half - 1) / RT_MACRO_ROWS, hi = (line + p.heavy_half + 1) / RT_MACRO_ROWS;
-                    in_band = m >= lo && m <= hi;
-                }
-                weighted += s->row_sum[(size_t)m] * (double)m;
-                total += s->row_sum[(size_t)m];
-                if (!in_band && (best < 0 || s->row_peak[(size_t)m] > s->row_peak[(size_t)best])) best = m;
-            }
-            if (best >= 0 && total > 0.0) {
-                (void)weighted;
-                const bool upwards = s->learned_sweep == 0;
-                p.rows_downwards = upwards ? 0 : 1;
-                const long long margin = std::max<long long>(1, macro_rows / 64);
-                p.first_macro_row = (int)std::min(macro_rows - 1, std::max<long long>(0, upwards ? best - margin : best + margin));
-            }
-        }
-    }
-    /* the 96-register kernel when LDS leaves room for fewer than six wavefronts per SIMD anyway (24 per CU) */
-    const bool clusters_wide = s->wide_opt >= 0 ? s->wide_opt != 0
-                                                : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
-    const bool fast_tables = s->base.n_fast_items > 0;
-    struct Kernel { const void *fn; const char *name; };
-#define RT_KERNEL(k) Kernel{(const void *)k, #k}
-    const Kernel first_kernel = d_stats ? (fast_tables ? RT_KERNEL(rt_render_kernel_fast_stats) : RT_KERNEL(rt_render_kernel_stats))
-                                : global_tables ? RT_KERNEL(rt_render_kernel_large)
-                                : (s->n_clusters > 0 && s->pairs_opt)
-                                      ? (clusters_wide ? RT_KERNEL(rt_render_kernel_clusters_wide) : RT_KERNEL(rt_render_kernel_clusters))
-                                : fast_tables ? RT_KERNEL(rt_render_kernel)
-                                : RT_KERNEL(rt_render_kernel_items);
-    const void *first = first_kernel.fn;
-    std::snprintf(s->launch.kernel, sizeof(s->launch.kernel), "%s", first_kernel.name);
+    const void *kernel = plan.kernel.fn;
+    std::snprintf(s->launch.kernel, sizeof(s->launch.kernel), "%s", plan.kernel.name);
     {
         /* a workgroup larger than the kernel was compiled for (__launch_bounds__) must never be launched */
         hipFuncAttributes attr;
-        HIP_TRY(hipFuncGetAttributes(&attr, first));
+        HIP_TRY(hipFuncGetAttributes(&attr, kernel));
         if (block > attr.maxThreadsPerBlock)
             return fail(RT_ERR_INVALID, "block_threads " + std::to_string(block) + " exceeds the launch bounds of " +
-                                            first_kernel.name + " (" + std::to_string(attr.maxThreadsPerBlock) + ")");
+                                            plan.kernel.name + " (" + std::to_string(attr.maxThreadsPerBlock) + ")");
     }
+    /* persistent grid: as many workgroups as the chip holds at once (by the
+     * occupancy query; a larger grid would also be correct, its surplus
+     * workgroups simply find the queue empty), never more than there are tiles */
     int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, first, block, (size_t)lds_bytes));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, (size_t)plan.lds_bytes));
     if (per_cu < 1) per_cu = 1;
+    const long long blocks_all = (plan.n_tiles + block / 64 - 1) / (block / 64);
     const long long blocks = s->grid_mult > 0
         ? std::min(blocks_all, (long long)per_cu * (long long)s->n_cus * (long long)s->grid_mult)
         : blocks_all;
     s->launch.grid_blocks = (int)blocks;
-    HIP_TRY(hipFuncSetAttribute(first, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, plan.lds_bytes));
     /* bounce stack: one slice per workgroup of the persistent grid */
-    {
-        const double need_d = stack_lds_levels >= max_depth ? 16.0
-                                           : (double)blocks * (double)block * (double)(max_depth + 1) * RT_STACK_ENTRY_BYTES;
-        if (need_d > 8.0e9)
-            return fail(RT_ERR_CAPACITY, "max_depth too large: the bounce stack would exceed 8 GB of HBM");
-        const size_t need = (size_t)need_d;
-        /* the stack (and nothing else) is shared by successive launches of this handle:
-         * launches must be stream-ordered, so fence when the caller switches streams */
-        if (s->has_last_stream && s->last_stream != stream) HIP_TRY(hipStreamSynchronize(s->last_stream));
-        s->last_stream = stream;
-        s->has_last_stream = true;
-        if (need > s->d_stack_bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (s->d_stack) { HIP_TRY(hipFree(s->d_stack)); s->d_stack = nullptr; s->d_stack_bytes = 0; }
-            HIP_TRY(hipMalloc(&s->d_stack, need));
-            s->d_stack_bytes = need;
-        }
-    }
-    if (p.help_rays_quads != 0) {
-        const size_t need = (size_t)blocks * (size_t)p.help_rays_quads * 16;
-        if (need > s->d_help_bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (s->d_help) { HIP_TRY(hipFree(s->d_help)); s->d_help = nullptr; s->d_help_bytes = 0; }
-            HIP_TRY(hipMalloc(&s->d_help, need));
-            s->d_help_bytes = need;
-        }
-    }
+    const double stack_bytes = plan.stack_lds_levels >= max_depth ? 16.0
+                             : (double)blocks * (double)block * (double)(max_depth + 1) * RT_STACK_ENTRY_BYTES;
+    if (stack_bytes > 8.0e9)
+        return fail(RT_ERR_CAPACITY, "max_depth too large: the bounce stack would exceed 8 GB of HBM");
+    /* the stack (and nothing else) is shared by successive launches of this handle:
+     * launches must be stream-ordered, so fence when the caller switches streams */
+    if (s->has_last_stream && s->last_stream != stream) HIP_TRY(hipStreamSynchronize(s->last_stream));
+    s->last_stream = stream;
+    s->has_last_stream = true;
+    rc = grow_device_buffer(&s->d_stack, &s->d_stack_bytes, (size_t)stack_bytes);
+    if (rc == RT_OK && plan.help) rc = grow_device_buffer(&s->d_help, &s->d_help_bytes, (size_t)blocks * (size_t)p.help_rays_quads * 16);
+    if (rc) return rc;
     /* This launch's block of counters is at zero (the invariant: the block of slot ev_next is, whenever a launch of this scene
      * starts -- all of them at allocation, and every launch zeroes the next slot's while it runs; launches of one scene are
      * stream-ordered, above).  The next slot's old launch, 63 launches ago, must be over before this one writes its block. */
@@ -1371,16 +1457,24 @@ int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1,
     const float4 *image_arg = reinterpret_cast<const float4 *>(s->d_image);
     float4 *stack_arg = reinterpret_cast<float4 *>(s->d_stack);
     unsigned int *list_arg = reinterpret_cast<unsigned int *>(s->d_help);      /* the clustered-scene kernels' HELP areas (unused by the others) */
-    {
-        void *args6[] = {&p, &image_arg, &d_out, &counter, &stack_arg, &list_arg};
-        void *args7[] = {&p, &image_arg, &d_out, &counter, &stack_arg, &d_stats, &list_arg};
-        HIP_TRY(hipLaunchKernel(first, dim3((unsigned)blocks), dim3((unsigned)block), d_stats ? args7 : args6, (size_t)lds_bytes, stream));
-    }
+    void *args6[] = {&p, &image_arg, &d_out, &counter, &stack_arg, &list_arg};
+    void *args7[] = {&p, &image_arg, &d_out, &counter, &stack_arg, &d_stats, &list_arg};
+    HIP_TRY(hipLaunchKernel(kernel, dim3((unsigned)blocks), dim3((unsigned)block), d_stats ? args7 : args6, (size_t)plan.lds_bytes, stream));
     HIP_TRY(hipGetLastError());
     s->ev_next = next_slot;               /* (only now: a launch that did not happen has zeroed nothing) */
     HIP_TRY(hipEventRecord(s->ev[slot].stop, stream));
     s->ev[slot].pending = true;
     return RT_OK;
+}
+
+/* rt_render and rt_render_stats, under the handle's lock: the strip's checks, the device, and the framebuffer the frame is
+ * rendered into (*bytes of it) */
+int frame_preamble(rt_scene *s, int W, int H, int x0, int x1, const float *out_rgb, bool out_required, size_t *bytes) {
+    if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 > x1) return fail(RT_ERR_INVALID, "need 0 <= x0 <= x1 <= W, W,H > 0");
+    *bytes = (size_t)(x1 - x0) * (size_t)H * 3 * sizeof(float);
+    if (out_required && *bytes && !out_rgb) return fail(RT_ERR_INVALID, "out_rgb is NULL");
+    HIP_TRY(hipSetDevice(s->device));
+    return grow_device_buffer(&s->d_fb, &s->d_fb_bytes, *bytes);
 }
 
 } // namespace
@@ -1460,16 +1554,10 @@ int rt_render(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int 
               float *out_rgb) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
     std::lock_guard<std::mutex> lock(s->mu);
-    if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 > x1) return fail(RT_ERR_INVALID, "need 0 <= x0 <= x1 <= W, W,H > 0");
-    const size_t bytes = (size_t)(x1 - x0) * (size_t)H * 3 * sizeof(float);
-    if (bytes && !out_rgb) return fail(RT_ERR_INVALID, "out_rgb is NULL");
-    HIP_TRY(hipSetDevice(s->device));
-    if (bytes > s->d_fb_bytes) {
-        if (s->d_fb) { HIP_TRY(hipFree(s->d_fb)); s->d_fb = nullptr; s->d_fb_bytes = 0; }
-        HIP_TRY(hipMalloc(&s->d_fb, bytes));
-        s->d_fb_bytes = bytes;
-    }
-    int rc = launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr);
+    size_t bytes = 0;
+    int rc = frame_preamble(s, W, H, x0, x1, out_rgb, true, &bytes);
+    if (rc) return rc;
+    rc = launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr);
     if (rc) return rc;
     s->timing.last_download_ms = 0.0;
     if (bytes) {
@@ -1494,24 +1582,18 @@ int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0
                     float *out_rgb, uint64_t *stats, int n_stats, uint64_t *wave_cycles, int n_wave_cycles) {
     if (!s || !stats || n_stats < 0) return fail(RT_ERR_INVALID, "scene/stats is NULL");
     std::lock_guard<std::mutex> lock(s->mu);
-    if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 > x1) return fail(RT_ERR_INVALID, "need 0 <= x0 <= x1 <= W, W,H > 0");
-    const size_t bytes = (size_t)(x1 - x0) * (size_t)H * 3 * sizeof(float);
-    HIP_TRY(hipSetDevice(s->device));
-    if (bytes > s->d_fb_bytes) {
-        if (s->d_fb) { HIP_TRY(hipFree(s->d_fb)); s->d_fb = nullptr; s->d_fb_bytes = 0; }
-        HIP_TRY(hipMalloc(&s->d_fb, bytes));
-        s->d_fb_bytes = bytes;
-    }
+    size_t bytes = 0;
+    int rc = frame_preamble(s, W, H, x0, x1, out_rgb, false, &bytes);
+    if (rc) return rc;
     /* counters, then one cycle count per wavefront tile */
-    const int tzl = s->tile_z_log2 >= 0 ? s->tile_z_log2 : (s->objects.size() <= 128 ? 4 : 2);
-    const int tile_z = 1 << tzl, tile_x = 64 >> tzl;
-    const size_t n_tiles = (size_t)((H + tile_z - 1) / tile_z) * (size_t)((x1 - x0 + tile_x - 1) / tile_x);
+    const TileShape t = tile_shape(s, H, x0, x1);
+    const size_t n_tiles = (size_t)(t.tiles_z * t.tiles_x);
     const size_t words = RT_STATS_COUNT + n_tiles * RT_TILE_STATS;
     unsigned long long *d_stats = nullptr;
     HIP_TRY(hipMalloc(&d_stats, words * sizeof(unsigned long long)));
     hipError_t e = hipMemset(d_stats, 0, words * sizeof(unsigned long long));
-    int rc = e == hipSuccess ? launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr, d_stats)
-                             : fail(RT_ERR_HIP, hipGetErrorString(e));
+    rc = e == hipSuccess ? launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr, d_stats)
+                         : fail(RT_ERR_HIP, hipGetErrorString(e));
     unsigned long long host[RT_STATS_COUNT] = {0};
     if (rc == RT_OK) {
         e = hipMemcpy(host, d_stats, sizeof(host), hipMemcpyDeviceToHost);
@@ -1533,14 +1615,13 @@ int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0
 int rt_learn_tile_order(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
     if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 >= x1) return fail(RT_ERR_INVALID, "need 0 <= x0 < x1 <= W, W,H > 0");
-    int tzl;
+    TileShape t;
     {
         std::lock_guard<std::mutex> lock(s->mu);
         s->row_peak.clear(); s->row_sum.clear();
-        tzl = s->tile_z_log2 >= 0 ? s->tile_z_log2 : (s->objects.size() <= 128 ? 4 : 2);
+        t = tile_shape(s, H, x0, x1);
     }
-    const int tile_z = 1 << tzl, tile_x = 64 >> tzl;
-    const size_t tiles_z = (size_t)((H + tile_z - 1) / tile_z), tiles_x = (size_t)((x1 - x0 + tile_x - 1) / tile_x);
+    const size_t tiles_z = (size_t)t.tiles_z, tiles_x = (size_t)t.tiles_x;
     std::vector<uint64_t> stats(RT_STATS_COUNT), tiles(tiles_z * tiles_x * RT_TILE_STATS);
     int rc = rt_render_stats(s, cam, W, H, x0, x1, max_depth, nullptr, stats.data(), RT_STATS_COUNT, tiles.data(), (int)tiles.size());
     if (rc) return rc;
@@ -1553,7 +1634,7 @@ int rt_learn_tile_order(rt_scene *s, const rt_camera_desc *cam, int W, int H, in
             sum[row / RT_MACRO_ROWS] += c;
         }
     std::lock_guard<std::mutex> lock(s->mu);
-    const int key[6] = {W, H, x0, x1, max_depth, tzl};
+    const int key[6] = {W, H, x0, x1, max_depth, t.z_log2};
     std::copy(key, key + 6, s->order_key);
     s->row_peak.swap(peak);
     s->row_sum.swap(sum);
