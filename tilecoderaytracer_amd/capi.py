@@ -142,6 +142,12 @@ def load_library():
     lib.rt_reset_timing.argtypes = [vp]
     lib.rt_get_launch_info.argtypes = [vp, C.POINTER(RtLaunchInfo)]
     lib.rt_set_option.argtypes = [vp, C.c_char_p, i]
+    # include/rt_capi_ssaa.h (absent from builds older than it, which TCRT_LIBRARY may name for A/B timing)
+    if hasattr(lib, "rt_render_ssaa"):
+        lib.rt_capi_ssaa_version.restype = i
+        lib.rt_render_ssaa.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, i, vp]
+        lib.rt_render_ssaa_device.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, i, vp, vp]
+        lib.rt_render_ssaa.restype = lib.rt_render_ssaa_device.restype = i
     for name in ("rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_render",
                  "rt_render_device", "rt_render_multi", "rt_render_stats", "rt_learn_tile_order", "rt_get_timing", "rt_reset_timing",
                  "rt_get_launch_info", "rt_set_option", "rt_chunk_bounds", "rt_multi_create", "rt_multi_render",

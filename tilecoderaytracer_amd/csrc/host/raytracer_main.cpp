@@ -13,6 +13,7 @@
  *   --scene 1 | 2 | grid:N | grid:N:noshadow
  *   --gpus G            x-strips over G GPUs, cut by measured cost, sent to GPU 0 with RCCL
  *   --out FILE          (default raytracer_screen.txt)   --no-txt
+ *   --ssaa K            K x K samples per pixel, averaged in the render kernel (rt_render_ssaa; K = 1, 2, 4; one GPU)
  */
 #include <chrono>
 #include <cstdio>
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "../../../include/rt_capi.h"
+#include "../../../include/rt_capi_ssaa.h"
 #include "celio_model.hpp"
 #include "screen_txt.hpp"
 
@@ -36,12 +38,12 @@ static std::vector<float> pixels;          /* pixels[x][z] as packed fp32 RGB */
 static int usage(const char *argv0) {
     std::fprintf(stderr,
                  "usage: %s [--width W] [--height H] [--depth D] [--scene 1|2|grid:N[:noshadow]]\n"
-                 "          [--gpus G] [--out FILE] [--no-txt]\n", argv0);
+                 "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4]\n", argv0);
     return 1;
 }
 
 int main(int argc, char **argv) {
-    int W = 500, H = 504, depth = 50, gpus = 1;
+    int W = 500, H = 504, depth = 50, gpus = 1, ssaa = 1;
     bool write_txt = true;
     std::string scene_name = "1", out_path = "raytracer_screen.txt";
     for (int i = 1; i < argc; ++i) {
@@ -51,12 +53,14 @@ int main(int argc, char **argv) {
         else if (a == "--height") { if (!need(H)) return usage(argv[0]); }
         else if (a == "--depth") { if (!need(depth)) return usage(argv[0]); }
         else if (a == "--gpus") { if (!need(gpus)) return usage(argv[0]); }
+        else if (a == "--ssaa") { if (!need(ssaa)) return usage(argv[0]); }
         else if (a == "--scene" && i + 1 < argc) scene_name = argv[++i];
         else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
     if (W <= 0 || H <= 0 || depth < 0 || gpus <= 0) return usage(argv[0]);
+    if ((ssaa != 1 && ssaa != 2 && ssaa != 4) || (ssaa > 1 && gpus > 1)) return usage(argv[0]);   /* (no multi-GPU supersampling) */
     verbose() = true;                          /* console output like the reference's */
 
     if (gpus == 1) std::cout << "Single-Core RayTracing!" << std::endl << std::endl;
@@ -96,7 +100,8 @@ int main(int argc, char **argv) {
     if (gpus == 1) {
         rt_scene *scene = nullptr;
         rc = rt_scene_create(&flat.desc, 0, &scene);
-        if (rc == RT_OK) rc = rt_render(scene, &cam, W, H, 0, W, depth, pixels.data());
+        if (rc == RT_OK) rc = ssaa > 1 ? rt_render_ssaa(scene, &cam, W, H, 0, W, depth, ssaa, pixels.data())
+                                       : rt_render(scene, &cam, W, H, 0, W, depth, pixels.data());
         if (rc == RT_OK) {
             rt_timing tm;
             if (rt_get_timing(scene, &tm) == RT_OK) kernel_ms = tm.last_kernel_ms;
@@ -140,7 +145,7 @@ int main(int argc, char **argv) {
     std::printf("Render call (s)            : %f\n", render_s);
     if (kernel_ms > 0.0)
         std::printf("Render kernel (ms)         : %f  (%.1f Mrays/s)%s\n", kernel_ms,
-                    (double)W * (double)H / (kernel_ms * 1e3), gpus > 1 ? "  [the GPU whose kernels took longest]" : "");
+                    (double)ssaa * (double)ssaa * (double)W * (double)H / (kernel_ms * 1e3), gpus > 1 ? "  [the GPU whose kernels took longest]" : "");
     std::printf("AverageRoundTime (us/pixel): %f\n", run_time_us / ((double)W * (double)H));
 
     if (write_txt) {

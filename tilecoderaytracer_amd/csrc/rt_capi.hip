@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/rt_capi_ssaa.h"
 #include "../../include/rt_capi_tuning.h"
 #include "rt_tables.h"
 
@@ -32,6 +33,11 @@ RT_DECLARE_KERNEL(rt_render_kernel_items);            /* the two item tables, no
 RT_DECLARE_KERNEL(rt_render_kernel_large);            /* tables in global memory                     */
 RT_DECLARE_KERNEL(rt_render_kernel_clusters);         /* clustered sphere runs, six wavefronts per SIMD */
 RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide);    /* ... five */
+RT_DECLARE_KERNEL(rt_render_kernel_ssaa);             /* the same five, supersampled (rt_kernel_ssaa.hip) */
+RT_DECLARE_KERNEL(rt_render_kernel_items_ssaa);
+RT_DECLARE_KERNEL(rt_render_kernel_large_ssaa);
+RT_DECLARE_KERNEL(rt_render_kernel_clusters_ssaa);
+RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_ssaa);
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_stats);      /* the counting builds */
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_fast_stats);
 
@@ -1164,9 +1170,12 @@ void camera_params(const rt_camera_desc *cam, int W, int H, int x0, int x1, int 
  * while on small scenes the two run alike; hence the default. */
 struct TileShape { int z_log2, x, z; long long tiles_x, tiles_z; };
 
-TileShape tile_shape(const rt_scene *s, int H, int x0, int x1) {
+/* SUPERSAMPLING (ssaa_log2 > 0): both sides must be multiples of k, so that a pixel's k x k samples lie in one tile; an option
+ * asking for another shape gets the nearest one that qualifies (the defaults, 4 x 16 and 16 x 4, always do). */
+TileShape tile_shape(const rt_scene *s, int H, int x0, int x1, int ssaa_log2 = 0) {
     TileShape t;
     t.z_log2 = s->tile_z_log2 >= 0 ? s->tile_z_log2 : (s->objects.size() <= 128 ? 4 : 2);
+    if (ssaa_log2 > 0) t.z_log2 = std::min(std::max(t.z_log2, ssaa_log2), 6 - ssaa_log2);
     t.z = 1 << t.z_log2;
     t.x = 64 >> t.z_log2;
     t.tiles_z = ((long long)H + t.z - 1) / t.z;
@@ -1282,16 +1291,18 @@ struct Kernel { const void *fn; const char *name; };
 #define RT_KERNEL(k) Kernel{(const void *)k, #k}
 
 /* the kernel: FAST tables, item tables, the one for clustered scenes (in the register budget that fits the occupancy LDS
- * allows), or the large-scene one */
-Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int block, int lds_bytes) {
+ * allows), or the large-scene one; supersampled (ssaa): the *_ssaa sibling of the same */
+Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int block, int lds_bytes, bool ssaa = false) {
     const bool fast_tables = s->base.n_fast_items > 0;
     if (counting) return fast_tables ? RT_KERNEL(rt_render_kernel_fast_stats) : RT_KERNEL(rt_render_kernel_stats);
-    if (global_tables) return RT_KERNEL(rt_render_kernel_large);
+    if (global_tables) return ssaa ? RT_KERNEL(rt_render_kernel_large_ssaa) : RT_KERNEL(rt_render_kernel_large);
     if (s->n_clusters > 0 && s->pairs_opt) {
         /* the 96-register kernel when LDS leaves room for fewer than six wavefronts per SIMD anyway (24 per CU) */
         const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
+        if (ssaa) return wide ? RT_KERNEL(rt_render_kernel_clusters_wide_ssaa) : RT_KERNEL(rt_render_kernel_clusters_ssaa);
         return wide ? RT_KERNEL(rt_render_kernel_clusters_wide) : RT_KERNEL(rt_render_kernel_clusters);
     }
+    if (ssaa) return fast_tables ? RT_KERNEL(rt_render_kernel_ssaa) : RT_KERNEL(rt_render_kernel_items_ssaa);
     return fast_tables ? RT_KERNEL(rt_render_kernel) : RT_KERNEL(rt_render_kernel_items);
 }
 
@@ -1305,9 +1316,11 @@ struct LaunchPlan {
     bool help = false;            /* the launch carries HELP areas (p.help_rays_quads != 0) */
 };
 
-/* Host-only: the checks and every decision of a launch, in this order.  An empty strip is planned up to its tile count. */
+/* Host-only: the checks and every decision of a launch, in this order.  An empty strip is planned up to its tile count.
+ * ssaa_log2 > 0 (rt_render_ssaa): W, H, x0, x1 are the VIRTUAL image's, every decision is taken on it, and the kernel averages
+ * each pixel's k x k samples into a W / k x H / k output. */
 int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *d_out,
-                bool counting, LaunchPlan *plan) {
+                bool counting, LaunchPlan *plan, int ssaa_log2 = 0) {
     int rc = check_launch_args(cam, W, H, x0, x1, max_depth, d_out);
     if (rc) return rc;
     BlockChoice bc;
@@ -1324,7 +1337,8 @@ int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int 
     /* (the LDS place of the table is reserved whether or not this camera admits one) */
     p.stack_off = bc.global_tables ? 0 : s->base.image_quads + primary_quads(s);
     p.cull = s->cull_opt;
-    const TileShape t = tile_shape(s, H, x0, x1);
+    p.ssaa_log2 = ssaa_log2;
+    const TileShape t = tile_shape(s, H, x0, x1, ssaa_log2);
     const long long n_tiles = t.tiles_z * t.tiles_x;
     if (n_tiles > 0x7fffffffLL) return fail(RT_ERR_INVALID, "too many tiles");
     p.tile_z_log2 = t.z_log2;
@@ -1344,7 +1358,7 @@ int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int 
     p.tile_prio = tile_prio(s, W, x0, x1);
     heavy_band(s, cam, W, H, x0, x1, t, p);
     if (!counting) learned_start_row(s, W, H, x0, x1, max_depth, t, p);
-    plan->kernel = choose_kernel(s, counting, bc.global_tables, bc.block, plan->lds_bytes);
+    plan->kernel = choose_kernel(s, counting, bc.global_tables, bc.block, plan->lds_bytes, ssaa_log2 > 0);
     plan->help = p.help_rays_quads != 0;
     return RT_OK;
 }
@@ -1372,9 +1386,9 @@ int device_report(rt_scene *s) {
 
 /* plan_launch(), then the device work: counters, timeline, occupancy and grid, bounce stack and HELP areas, the event ring */
 int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
-           float *d_out, hipStream_t stream, unsigned long long *d_stats = nullptr) {
+           float *d_out, hipStream_t stream, unsigned long long *d_stats = nullptr, int ssaa_log2 = 0) {
     LaunchPlan plan;
-    int rc = plan_launch(s, cam, W, H, x0, x1, max_depth, d_out, d_stats != nullptr, &plan);
+    int rc = plan_launch(s, cam, W, H, x0, x1, max_depth, d_out, d_stats != nullptr, &plan, ssaa_log2);
     if (rc) return rc;
     RtParams &p = plan.p;
     const int block = plan.block;
@@ -1477,6 +1491,47 @@ int frame_preamble(rt_scene *s, int W, int H, int x0, int x1, const float *out_r
     return grow_device_buffer(&s->d_fb, &s->d_fb_bytes, *bytes);
 }
 
+/* rt_render and rt_render_ssaa, under the handle's lock, after frame_preamble(): the launch into the handle's framebuffer, the
+ * download of its `bytes`, the synchronisation */
+int render_to_host(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, float *out_rgb,
+                   size_t bytes, int ssaa_log2) {
+    int rc = launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr, nullptr, ssaa_log2);
+    if (rc) return rc;
+    s->timing.last_download_ms = 0.0;
+    if (bytes) {
+        hipEvent_t t0, t1;
+        HIP_TRY(hipEventCreate(&t0));
+        HIP_TRY(hipEventCreate(&t1));
+        HIP_TRY(hipEventRecord(t0, nullptr));
+        HIP_TRY(hipMemcpy(out_rgb, s->d_fb, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventRecord(t1, nullptr));
+        HIP_TRY(hipEventSynchronize(t1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
+        s->timing.last_download_ms = ms;
+        (void)hipEventDestroy(t0);
+        (void)hipEventDestroy(t1);
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return device_report(s);
+}
+
+/* rt_render_ssaa*: samples -> log2 k, then the output strip and the virtual one (k W x k H, columns [k x0, k x1)) checked as
+ * every launch is -- all before the device is touched */
+int ssaa_args(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, int samples, const void *out, int *log2k) {
+    if (samples != 1 && samples != 2 && samples != 4)
+        return fail(RT_ERR_INVALID, "samples must be 1, 2 or 4 (got " + std::to_string(samples) + ")");
+    const int kl = samples == 4 ? 2 : samples - 1;
+    int rc = check_launch_args(cam, W, H, x0, x1, max_depth, out);
+    if (rc) return rc;
+    if (((long long)W << kl) > 0x7fffffffLL || ((long long)H << kl) > 0x7fffffffLL)
+        return fail(RT_ERR_INVALID, "samples * W and samples * H must stay below 2^31");
+    rc = check_launch_args(cam, W << kl, H << kl, x0 << kl, x1 << kl, max_depth, out);
+    if (rc) return rc;
+    *log2k = kl;
+    return RT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1557,25 +1612,37 @@ int rt_render(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int 
     size_t bytes = 0;
     int rc = frame_preamble(s, W, H, x0, x1, out_rgb, true, &bytes);
     if (rc) return rc;
-    rc = launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr);
+    return render_to_host(s, cam, W, H, x0, x1, max_depth, out_rgb, bytes, 0);
+}
+
+int rt_capi_ssaa_version(void) { return RT_CAPI_SSAA_VERSION; }
+
+/* SUPERSAMPLING (include/rt_capi_ssaa.h): the launch of the virtual kW x kH image's columns [k x0, k x1), into an output of
+ * the W x H strip's size; samples = 1 is rt_render itself */
+int rt_render_ssaa(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, int samples,
+                   float *out_rgb) {
+    if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
+    int kl = 0;
+    int rc = ssaa_args(cam, W, H, x0, x1, max_depth, samples, out_rgb, &kl);
     if (rc) return rc;
-    s->timing.last_download_ms = 0.0;
-    if (bytes) {
-        hipEvent_t t0, t1;
-        HIP_TRY(hipEventCreate(&t0));
-        HIP_TRY(hipEventCreate(&t1));
-        HIP_TRY(hipEventRecord(t0, nullptr));
-        HIP_TRY(hipMemcpy(out_rgb, s->d_fb, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipEventRecord(t1, nullptr));
-        HIP_TRY(hipEventSynchronize(t1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, t0, t1));
-        s->timing.last_download_ms = ms;
-        (void)hipEventDestroy(t0);
-        (void)hipEventDestroy(t1);
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    return device_report(s);
+    if (kl == 0) return rt_render(s, cam, W, H, x0, x1, max_depth, out_rgb);
+    std::lock_guard<std::mutex> lock(s->mu);
+    size_t bytes = 0;
+    rc = frame_preamble(s, W, H, x0, x1, out_rgb, true, &bytes);
+    if (rc) return rc;
+    return render_to_host(s, cam, W << kl, H << kl, x0 << kl, x1 << kl, max_depth, out_rgb, bytes, kl);
+}
+
+int rt_render_ssaa_device(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, int samples,
+                          void *d_out_rgb, void *hip_stream) {
+    if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
+    int kl = 0;
+    int rc = ssaa_args(cam, W, H, x0, x1, max_depth, samples, d_out_rgb, &kl);
+    if (rc) return rc;
+    if (kl == 0) return rt_render_device(s, cam, W, H, x0, x1, max_depth, d_out_rgb, hip_stream);
+    std::lock_guard<std::mutex> lock(s->mu);
+    return launch(s, cam, W << kl, H << kl, x0 << kl, x1 << kl, max_depth, static_cast<float *>(d_out_rgb),
+                  static_cast<hipStream_t>(hip_stream), nullptr, kl);
 }
 
 int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,

@@ -1722,8 +1722,10 @@ __device__ __forceinline__ size_t hbm_stack_entry(const RtParams &p, const int l
     return (size_t)(row * (unsigned int)here(p.stack_stride) + threadIdx.x);
 }
 
-/* One wavefront tile: camera rays, the bounce loop, the unwind, the store. */
-template <bool kStats, int kMode>
+/* One wavefront tile: camera rays, the bounce loop, the unwind, the store.  kSsaa: the tile is a rectangle of SAMPLES of a
+ * virtual kW x kH image (k = 1 << p.ssaa_log2, both tile sides multiples of k: rt_capi.hip, tile_shape()); the store box-filters
+ * them into the W x H output (below). */
+template <bool kStats, int kMode, bool kSsaa = false>
 __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds, float4 *wlds, float4 *help_rays,
                                             const uint32_t *__restrict__ ctl_words, float *__restrict__ out,
                                             float4 *__restrict__ bounce_stack, unsigned long long *__restrict__ stats_out,
@@ -2033,7 +2035,39 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
      * stores count too: a wavefront that reads the entry after its stores waits until the pixels have reached the L2, 3.5 us
      * between two 13 us tiles of the built-in scene (timeline of round 3: "gap between consecutive tiles of a slot"). */
     next_pop = __builtin_amdgcn_readfirstlane(next_pop);
-    if (inside) {
+    if constexpr (kSsaa) {
+        /* SUPERSAMPLING: sample (i, j) of output pixel (x, z) is virtual pixel (k x + i, k z + j).  Tile origins and sides are
+         * multiples of k, so a pixel's k x k samples are lanes base + (i << tile_z_log2) + j of ONE wavefront, with base the lane
+         * of sample (0, 0), and all inside the image or all outside.  The wave is converged here: every lane pulls the samples
+         * of the pixel whose (0, 0) it would hold and adds them in fp32 in the order s = i k + j (the other lanes' sums are
+         * discarded), divides by k^2 -- a power of two: the multiply is exact, the same bits as the divide -- and the base lane
+         * alone stores.  3 (k^2 - 1) ds_bpermute per tile: 9 at k = 2, 45 at k = 4. */
+        const int kl = here(p.ssaa_log2);
+        const int tzl_s = here(p.tile_z_log2);
+        const int k = 1 << kl;
+        V3 acc = C;
+        for (int i = 0; i < k; ++i) {
+            for (int j = (i == 0 ? 1 : 0); j < k; ++j) {
+                const int from = (lane + (i << tzl_s) + j) << 2;       /* ds_bpermute: byte address, lane = (from >> 2) & 63 */
+                acc.x = acc.x + lane_pull_f(from, C.x);
+                acc.y = acc.y + lane_pull_f(from, C.y);
+                acc.z = acc.z + lane_pull_f(from, C.z);
+            }
+        }
+        const float inv = kl == 1 ? 0.25f : 0.0625f;                 /* 1 / k^2, k in {2, 4} */
+        const bool base = ((lane >> tzl_s) & (k - 1)) == 0 && (lane & (k - 1)) == 0;
+        if (inside && base) {
+            const int sx = (here(tile_col) * (64 >> tzl_s) + (lane >> tzl_s)) >> kl;   /* output column - output x0 */
+            const int sz = ((here(tile_row) << tzl_s) + (lane & ((1 << tzl_s) - 1))) >> kl;
+            float *dst = out + ((size_t)sx * (size_t)(here(p.H) >> kl) + (size_t)sz) * 3;
+            const float r = acc.x * inv, g = acc.y * inv, b = acc.z * inv;
+#if RT_NT_STORES
+            __builtin_nontemporal_store(r, dst); __builtin_nontemporal_store(g, dst + 1); __builtin_nontemporal_store(b, dst + 2);
+#else
+            dst[0] = r; dst[1] = g; dst[2] = b;
+#endif
+        }
+    } else if (inside) {
         const int tzl_b = here(p.tile_z_log2);
         const int sx = here(tile_col) * (64 >> tzl_b) + (lane >> tzl_b);   /* x - x0 */
         const int sz = (here(tile_row) << tzl_b) + (lane & ((1 << tzl_b) - 1));
@@ -2094,7 +2128,7 @@ __device__ RT_SCAN_INLINE unsigned int queues_with_tiles(const unsigned int *til
     return (unsigned int)__builtin_amdgcn_ballot_w64(left > 0) & 0xFFu;
 }
 
-template <bool kStats, bool kGlobalTables = false, bool kClusters = false, bool kRoomy = false, bool kFast = false>
+template <bool kStats, bool kGlobalTables = false, bool kClusters = false, bool kRoomy = false, bool kFast = false, bool kSsaa = false>
 __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__restrict__ image,
                                             float *__restrict__ out, unsigned int *__restrict__ tile_counter,
                                             float4 *__restrict__ bounce_stack,
@@ -2303,8 +2337,8 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
          * successor comes from the HEAVY tiles' own head) */
         unsigned int *const ask_head = (ask_ahead || (kHelp && heavy_phase != 0)) ? nullptr
                                      : tile_counter + ((my_xcc + steal) & (RT_TILE_QUEUES - 1)) * RT_QUEUE_STRIDE;
-        render_tile<kStats, kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0)>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave, my_xcc, steal,
-                                                                           next_pop, ask_head);
+        render_tile<kStats, kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0), kSsaa>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave, my_xcc,
+                                                                                  steal, next_pop, ask_head);
 #ifdef RT_TIMELINE
         if (p.timeline != 0ull && lane == 0) {                   /* ... when it was done, and by whom */
             unsigned long long *rec = reinterpret_cast<unsigned long long *>(p.timeline) + (size_t)tile_number * RT_TIMELINE_WORDS;
@@ -2354,12 +2388,29 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
     unsigned int *__restrict__ tile_counter, float4 *__restrict__ bounce_stack,                                   \
     unsigned long long *__restrict__ stats_out, unsigned int *__restrict__ help_area
 
-/* Scenes without clustered sphere runs, FAST tables (the built-in scene: the bench headline).  72 VGPRs: seven
- * wavefronts per SIMD where LDS allows (the bounce stack keeps its LDS place up to seven workgroups per CU,
- * RT_STACK_LDS_SHARE) */
+/* launch bounds: wavefronts per SIMD of the kernels for scenes without clustered sphere runs, of the clustered-scene kernels and
+ * of their wide variant; the clustered-scene kernels' largest workgroup */
 #ifndef RT_WAVES_PER_SIMD
 #define RT_WAVES_PER_SIMD 7
 #endif
+#ifndef RT_WAVES_PER_SIMD_CLUSTERS
+#define RT_WAVES_PER_SIMD_CLUSTERS 6
+#endif
+#ifndef RT_WAVES_PER_SIMD_WIDE
+#define RT_WAVES_PER_SIMD_WIDE 5
+#endif
+#ifndef RT_BLOCK_BOUND_CLUSTERS
+#define RT_BLOCK_BOUND_CLUSTERS 512
+#endif
+
+/* rt_kernel_ssaa.hip includes this file for the body alone and defines the supersampling kernels: in a translation unit of
+ * their own, the seven kernels below compile to the code they have without them (next to five more instantiations of the
+ * body in one module, the item-table kernel's allocation moved: one more spilled scalar) */
+#ifndef RT_KERNEL_BODY_ONLY
+
+/* Scenes without clustered sphere runs, FAST tables (the built-in scene: the bench headline).  72 VGPRs: seven
+ * wavefronts per SIMD where LDS allows (the bounce stack keeps its LDS place up to seven workgroups per CU,
+ * RT_STACK_LDS_SHARE) */
 extern "C" __global__ void __launch_bounds__(RT_BLOCK_BOUND, RT_WAVES_PER_SIMD)
 rt_render_kernel(RT_KERNEL_ARGS) {
 #ifdef RT_FAST_PARAMS_BY_VALUE
@@ -2384,14 +2435,8 @@ rt_render_kernel_large(RT_KERNEL_ARGS) {
     render_body<false, true>(p, image, out, tile_counter, bounce_stack, nullptr, help_area);
 }
 
-/* scenes with clustered sphere runs (PAIRS, NEAREST PAIRS, HELP, HEAVY tiles): 80 registers, six wavefronts per SIMD */
-#ifndef RT_WAVES_PER_SIMD_CLUSTERS
-#define RT_WAVES_PER_SIMD_CLUSTERS 6
-#endif
-/* (workgroups of up to eight wavefronts: scenes whose tables are large share one LDS copy among more of them, launch() in rt_capi.hip) */
-#ifndef RT_BLOCK_BOUND_CLUSTERS
-#define RT_BLOCK_BOUND_CLUSTERS 512
-#endif
+/* scenes with clustered sphere runs (PAIRS, NEAREST PAIRS, HELP, HEAVY tiles): 80 registers, six wavefronts per SIMD
+ * (workgroups of up to eight wavefronts: scenes whose tables are large share one LDS copy among more of them, launch() in rt_capi.hip) */
 extern "C" __global__ void __launch_bounds__(RT_BLOCK_BOUND_CLUSTERS, RT_WAVES_PER_SIMD_CLUSTERS)
 rt_render_kernel_clusters(RT_KERNEL_ARGS) {
     RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);
@@ -2400,9 +2445,6 @@ rt_render_kernel_clusters(RT_KERNEL_ARGS) {
 
 /* the same with the registers of five wavefronts per SIMD, for scenes whose tables leave room for no more than
  * five workgroups per CU anyway (the 1 024-sphere grid: 31.5 KB); the pair flush tests four members abreast here */
-#ifndef RT_WAVES_PER_SIMD_WIDE
-#define RT_WAVES_PER_SIMD_WIDE 5
-#endif
 extern "C" __global__ void __launch_bounds__(RT_BLOCK_BOUND_CLUSTERS, RT_WAVES_PER_SIMD_WIDE)
 rt_render_kernel_clusters_wide(RT_KERNEL_ARGS) {
     RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);
@@ -2423,3 +2465,4 @@ rt_render_kernel_fast_stats(RT_KERNEL_ARGS_STATS) {
     RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);
     render_body<true, false, false, false, true>(p, image, out, tile_counter, bounce_stack, stats_out, help_area);
 }
+#endif /* RT_KERNEL_BODY_ONLY */

@@ -207,6 +207,12 @@ typedef struct RtParams {
     /* diagnostic (option "timeline"): 0, or device memory for RT_TIMELINE_WORDS u64 per wavefront tile, row-major:
      * {start, end (100 MHz constant clock), workgroup * 16 + wavefront, 1 if rendered as a HEAVY tile} */
     uint64_t timeline;
+    /* SUPERSAMPLING (include/rt_capi_ssaa.h; the *_ssaa kernels only): log2 k of k x k samples per output pixel.  Every other
+     * field describes the VIRTUAL kW x kH launch; the store averages each pixel's samples into the W x H output.  (Last, so
+     * that no other field moves; padded to 16 bytes, so that the kernel arguments behind the struct keep their kernarg
+     * offsets modulo 16: the scalar loads of those merge as before, and the other kernels' code differs in those offsets only.) */
+    int32_t ssaa_log2;
+    int32_t ssaa_pad[3];
 } RtParams;
 #define RT_TIMELINE_WORDS 4
 

@@ -54,6 +54,20 @@ class Renderer:
         capi.check(self._lib.rt_render_device(self._scene, self._cam, W, H, x0, x1, max_depth,
                                               C.c_void_p(device_ptr), C.c_void_p(stream)))
 
+    def render_ssaa(self, W, H, max_depth, samples, x0=0, x1=None):
+        """Columns [x0, x1) of a W x H image with samples x samples samples per pixel, box-filtered in the render kernel
+        (include/rt_capi_ssaa.h; samples 1, 2 or 4) -> float32 array (x1-x0, H, 3)."""
+        x1 = W if x1 is None else x1
+        out = np.empty((max(x1 - x0, 0), H, 3), dtype=np.float32)
+        capi.check(self._lib.rt_render_ssaa(self._scene, self._cam, W, H, x0, x1, max_depth, samples,
+                                            out.ctypes.data))
+        return out
+
+    def render_ssaa_device(self, W, H, max_depth, samples, x0, x1, device_ptr, stream=0):
+        """Enqueue a supersampled render (W x H output columns [x0, x1)) into device memory on a HIP stream (no sync)."""
+        capi.check(self._lib.rt_render_ssaa_device(self._scene, self._cam, W, H, x0, x1, max_depth, samples,
+                                                   C.c_void_p(device_ptr), C.c_void_p(stream)))
+
     STAT_NAMES = ("nearest_rays", "shadow_rays", "wave_nearest_scans", "wave_shadow_scans",
                   "wave_sphere_tests", "wave_plane_tests", "wave_box_tests", "lane_sphere_tests",
                   "cycles_nearest", "cycles_shadow", "cycles_tile",
