@@ -148,6 +148,12 @@ def load_library():
         lib.rt_render_ssaa.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, i, vp]
         lib.rt_render_ssaa_device.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, i, vp, vp]
         lib.rt_render_ssaa.restype = lib.rt_render_ssaa_device.restype = i
+    # include/rt_capi_rays.h (likewise absent from older builds)
+    if hasattr(lib, "rt_trace_rays"):
+        lib.rt_capi_rays_version.restype = i
+        lib.rt_trace_rays.argtypes = [vp, i, i, vp, i, vp]
+        lib.rt_trace_rays_device.argtypes = [vp, i, i, vp, i, vp, vp]
+        lib.rt_trace_rays.restype = lib.rt_trace_rays_device.restype = i
     for name in ("rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_render",
                  "rt_render_device", "rt_render_multi", "rt_render_stats", "rt_learn_tile_order", "rt_get_timing", "rt_reset_timing",
                  "rt_get_launch_info", "rt_set_option", "rt_chunk_bounds", "rt_multi_create", "rt_multi_render",

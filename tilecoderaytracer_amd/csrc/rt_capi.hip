@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/rt_capi_rays.h"
 #include "../../include/rt_capi_ssaa.h"
 #include "../../include/rt_capi_tuning.h"
 #include "rt_tables.h"
@@ -38,8 +40,18 @@ RT_DECLARE_KERNEL(rt_render_kernel_items_ssaa);
 RT_DECLARE_KERNEL(rt_render_kernel_large_ssaa);
 RT_DECLARE_KERNEL(rt_render_kernel_clusters_ssaa);
 RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_ssaa);
+RT_DECLARE_KERNEL(rt_render_kernel_rays);             /* ... over a caller's rays (rt_kernel_rays.hip) */
+RT_DECLARE_KERNEL(rt_render_kernel_items_rays);
+RT_DECLARE_KERNEL(rt_render_kernel_large_rays);
+RT_DECLARE_KERNEL(rt_render_kernel_clusters_rays);
+RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_rays);
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_stats);      /* the counting builds */
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_fast_stats);
+
+/* the kernels' view of RtParams: the ray-batch fields took the place of the supersampling padding, nothing else moved */
+static_assert(offsetof(RtParams, ssaa_log2) == 1336 && offsetof(RtParams, n_rays) == 1340 && offsetof(RtParams, rays) == 1344 &&
+                  sizeof(RtParams) == 1352,
+              "RtParams layout");
 
 namespace {
 
@@ -83,6 +95,9 @@ struct rt_scene {
     /* scratch framebuffer for rt_render (host destination) */
     void *d_fb = nullptr;
     size_t d_fb_bytes = 0;
+    /* rt_trace_rays: the host batch's device copy */
+    void *d_rays = nullptr;
+    size_t d_rays_bytes = 0;
     /* options */
     int tile_z_log2 = -1;         /* wavefront tile height: -1 = auto (see launch()), else log2 */
     int block_threads_opt = 0;    /* 0 = auto */
@@ -1140,13 +1155,16 @@ int launch_block(const rt_scene *s, int W, int x0, int x1, int max_depth, bool c
     return RT_OK;
 }
 
+/* the largest output of one launch, in floats */
+constexpr double kMaxStripFloats = 2.0e9 * 4.0;
+
 int check_launch_args(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *d_out) {
     if (!cam) return fail(RT_ERR_INVALID, "camera is NULL");
     if (W <= 0 || H <= 0) return fail(RT_ERR_INVALID, "W and H must be positive");
     if (x0 < 0 || x1 > W || x0 > x1) return fail(RT_ERR_INVALID, "need 0 <= x0 <= x1 <= W");
     if (max_depth < 0) return fail(RT_ERR_INVALID, "max_depth < 0");
     if (!d_out && x1 > x0) return fail(RT_ERR_INVALID, "output pointer is NULL");
-    if ((double)(x1 - x0) * (double)H * 3.0 > 2.0e9 * 4.0)
+    if ((double)(x1 - x0) * (double)H * 3.0 > kMaxStripFloats)
         return fail(RT_ERR_INVALID, "strip too large");
     return RT_OK;
 }
@@ -1163,6 +1181,16 @@ void camera_params(const rt_camera_desc *cam, int W, int H, int x0, int x1, int 
     p.W = W; p.H = H; p.x0 = x0; p.x1 = x1; p.max_depth = max_depth;
 }
 
+/* RAY BATCH (include/rt_capi_rays.h): n rays {E, T} at a device address, laid out as an n_cols x rows grid -- launched as the
+ * image of that size (W = x1 = n_cols, H = rows, x0 = 0) without a camera */
+struct RayBatch { int n = 0, rows = 0, n_cols = 0; const void *d_rays = nullptr; };
+
+void batch_params(const RayBatch &b, int max_depth, RtParams &p) {
+    p.W = b.n_cols; p.H = b.rows; p.x0 = 0; p.x1 = b.n_cols; p.max_depth = max_depth;
+    p.n_rays = b.n;
+    p.rays = (uint64_t)(uintptr_t)b.d_rays;
+}
+
 /* Wavefront tile shape (speed only).  4 x 16 (x by z) makes every lane-row's
  * stores whole 64-byte sectors (16 pixels x 12 B = 192 B, aligned): measured
  * WRITE_SIZE = 1.08 x the framebuffer bytes vs 1.27 x for 16 x 4.  On the
@@ -1171,11 +1199,15 @@ void camera_params(const rt_camera_desc *cam, int W, int H, int x0, int x1, int 
 struct TileShape { int z_log2, x, z; long long tiles_x, tiles_z; };
 
 /* SUPERSAMPLING (ssaa_log2 > 0): both sides must be multiples of k, so that a pixel's k x k samples lie in one tile; an option
- * asking for another shape gets the nearest one that qualifies (the defaults, 4 x 16 and 16 x 4, always do). */
-TileShape tile_shape(const rt_scene *s, int H, int x0, int x1, int ssaa_log2 = 0) {
+ * asking for another shape gets the nearest one that qualifies (the defaults, 4 x 16 and 16 x 4, always do).
+ * RAY BATCH (rays), without a "tile_z" option: the tile is no wider than the grid, rounded up to a power of two, and as much
+ * taller -- a flat list (n_cols = 1) gets 1 x 64 tiles, not lanes three quarters idle. */
+TileShape tile_shape(const rt_scene *s, int H, int x0, int x1, int ssaa_log2 = 0, bool rays = false) {
     TileShape t;
     t.z_log2 = s->tile_z_log2 >= 0 ? s->tile_z_log2 : (s->objects.size() <= 128 ? 4 : 2);
     if (ssaa_log2 > 0) t.z_log2 = std::min(std::max(t.z_log2, ssaa_log2), 6 - ssaa_log2);
+    if (rays && s->tile_z_log2 < 0)
+        while (t.z_log2 < 6 && (64LL >> t.z_log2) >= 2LL * (x1 - x0)) ++t.z_log2;    /* (tile_x >= 2 n_cols: wider than needed) */
     t.z = 1 << t.z_log2;
     t.x = 64 >> t.z_log2;
     t.tiles_z = ((long long)H + t.z - 1) / t.z;
@@ -1187,10 +1219,10 @@ TileShape tile_shape(const rt_scene *s, int H, int x0, int x1, int ssaa_log2 = 0
  * horizon rows are the most expensive of the frame, the rows below them (the ground, with the spheres on it) get cheaper
  * towards the bottom, and the rows above the horizon, which come last after the wrap-around, are the cheapest: the queues then
  * hand out tiles roughly in order of decreasing cost, which keeps the tail of a frame -- or of a GPU's strip of it -- short.
- * "first_row" given: from there upwards. */
+ * "first_row" given: from there upwards.  No camera (a ray batch): no horizon, the option or row 0. */
 void start_row(const rt_scene *s, const rt_camera_desc *cam, long long tiles_z, RtParams &p) {
     const long long macro_rows = (tiles_z + RT_MACRO_ROWS - 1) / RT_MACRO_ROWS;
-    const int horizon = horizon_start(s, cam);                    /* thousandths of the image height; 8 below the horizon row; 0 = none */
+    const int horizon = cam ? horizon_start(s, cam) : 0;          /* thousandths of the image height; 8 below the horizon row; 0 = none */
     const bool automatic = s->first_row_permille < 0 && horizon > 0;
     const int permille = s->first_row_permille >= 0 ? s->first_row_permille : (automatic ? std::min(999, horizon + 8 + 30) : 0);
     p.rows_downwards = automatic ? 1 : 0;
@@ -1231,12 +1263,13 @@ int tile_prio(const rt_scene *s, int W, int x0, int x1) {
  * the launch renders a strip of at most a third of the image's width -- one GPU's share on three or more.  There the strip
  * waits for its horizon tiles (4096^2, 1 024-sphere grid, longest of 8 strips: 1.39 -> 1.05 ms with the band, 4 strips 1.68 ->
  * 1.63 ms); a whole frame has enough other tiles to run beside them, and giving three of a workgroup's four wavefronts to one
- * tile only costs it throughput (4.83 -> 5.02 ms; with a band of 0.9 % of the height 5.32 ms).  profiles/r03_experiments.txt */
+ * tile only costs it throughput (4.83 -> 5.02 ms; with a band of 0.9 % of the height 5.32 ms).  profiles/r03_experiments.txt
+ * No camera (a ray batch): no horizon, no band, whatever the option says. */
 void heavy_band(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, const TileShape &t, RtParams &p) {
     p.heavy_half = -1;
     p.heavy_row0_q16 = p.heavy_slope_q16 = 0;
     const bool heavy_wanted = s->heavy_opt > 0 || (s->heavy_opt < 0 && (long long)(x1 - x0) * 3 <= (long long)W);
-    if (p.help_rays_quads == 0 || !heavy_wanted) return;
+    if (!cam || p.help_rays_quads == 0 || !heavy_wanted) return;
     double dz_centre = 0.0;
     const rt_object_desc *plane = horizon_plane(s, cam, &dz_centre);
     if (!plane) return;
@@ -1289,21 +1322,24 @@ void learned_start_row(const rt_scene *s, int W, int H, int x0, int x1, int max_
 
 struct Kernel { const void *fn; const char *name; };
 #define RT_KERNEL(k) Kernel{(const void *)k, #k}
+/* a kernel and its supersampling and ray-batch siblings */
+struct Siblings { Kernel plain, ssaa, rays; };
+#define RT_SIBLINGS(k) Siblings{RT_KERNEL(k), RT_KERNEL(k##_ssaa), RT_KERNEL(k##_rays)}
 
 /* the kernel: FAST tables, item tables, the one for clustered scenes (in the register budget that fits the occupancy LDS
- * allows), or the large-scene one; supersampled (ssaa): the *_ssaa sibling of the same */
-Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int block, int lds_bytes, bool ssaa = false) {
+ * allows), or the large-scene one; supersampled (ssaa) or over a ray batch (rays): the *_ssaa or *_rays sibling of the same */
+Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int block, int lds_bytes, bool ssaa = false,
+                     bool rays = false) {
     const bool fast_tables = s->base.n_fast_items > 0;
     if (counting) return fast_tables ? RT_KERNEL(rt_render_kernel_fast_stats) : RT_KERNEL(rt_render_kernel_stats);
-    if (global_tables) return ssaa ? RT_KERNEL(rt_render_kernel_large_ssaa) : RT_KERNEL(rt_render_kernel_large);
+    const auto pick = [&](const Siblings &k) { return ssaa ? k.ssaa : (rays ? k.rays : k.plain); };
+    if (global_tables) return pick(RT_SIBLINGS(rt_render_kernel_large));
     if (s->n_clusters > 0 && s->pairs_opt) {
         /* the 96-register kernel when LDS leaves room for fewer than six wavefronts per SIMD anyway (24 per CU) */
         const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
-        if (ssaa) return wide ? RT_KERNEL(rt_render_kernel_clusters_wide_ssaa) : RT_KERNEL(rt_render_kernel_clusters_ssaa);
-        return wide ? RT_KERNEL(rt_render_kernel_clusters_wide) : RT_KERNEL(rt_render_kernel_clusters);
+        return wide ? pick(RT_SIBLINGS(rt_render_kernel_clusters_wide)) : pick(RT_SIBLINGS(rt_render_kernel_clusters));
     }
-    if (ssaa) return fast_tables ? RT_KERNEL(rt_render_kernel_ssaa) : RT_KERNEL(rt_render_kernel_items_ssaa);
-    return fast_tables ? RT_KERNEL(rt_render_kernel) : RT_KERNEL(rt_render_kernel_items);
+    return fast_tables ? pick(RT_SIBLINGS(rt_render_kernel)) : pick(RT_SIBLINGS(rt_render_kernel_items));
 }
 
 /* Everything a launch decides before it touches the device. */
@@ -1318,27 +1354,30 @@ struct LaunchPlan {
 
 /* Host-only: the checks and every decision of a launch, in this order.  An empty strip is planned up to its tile count.
  * ssaa_log2 > 0 (rt_render_ssaa): W, H, x0, x1 are the VIRTUAL image's, every decision is taken on it, and the kernel averages
- * each pixel's k x k samples into a W / k x H / k output. */
+ * each pixel's k x k samples into a W / k x H / k output.
+ * rays (rt_trace_rays; cam is NULL, the batch checked by rays_args()): W, H, x0, x1 are its grid's, n_cols x rows from column 0;
+ * every decision that needs a camera -- PRIMARY table, automatic start row, HEAVY band, learned order -- is "none". */
 int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *d_out,
-                bool counting, LaunchPlan *plan, int ssaa_log2 = 0) {
-    int rc = check_launch_args(cam, W, H, x0, x1, max_depth, d_out);
+                bool counting, LaunchPlan *plan, int ssaa_log2 = 0, const RayBatch *rays = nullptr) {
+    int rc = rays ? RT_OK : check_launch_args(cam, W, H, x0, x1, max_depth, d_out);
     if (rc) return rc;
     BlockChoice bc;
     rc = launch_block(s, W, x0, x1, max_depth, counting, &bc);
     if (rc) return rc;
     RtParams &p = plan->p;
     p = s->base;
-    camera_params(cam, W, H, x0, x1, max_depth, p);
+    if (rays) batch_params(*rays, max_depth, p);
+    else camera_params(cam, W, H, x0, x1, max_depth, p);
     p.stack_lds_levels = bc.stack_lds_levels;
     p.stack_stride = bc.block;
     p.n_primary = 0;
     p.primary_off = s->base.image_quads;
-    if (!bc.global_tables && primary_quads(s) > 0 && primary_table(s, cam, W, H, p.primary)) p.n_primary = primary_quads(s);
+    if (!rays && !bc.global_tables && primary_quads(s) > 0 && primary_table(s, cam, W, H, p.primary)) p.n_primary = primary_quads(s);
     /* (the LDS place of the table is reserved whether or not this camera admits one) */
     p.stack_off = bc.global_tables ? 0 : s->base.image_quads + primary_quads(s);
     p.cull = s->cull_opt;
     p.ssaa_log2 = ssaa_log2;
-    const TileShape t = tile_shape(s, H, x0, x1, ssaa_log2);
+    const TileShape t = tile_shape(s, H, x0, x1, ssaa_log2, rays != nullptr);
     const long long n_tiles = t.tiles_z * t.tiles_x;
     if (n_tiles > 0x7fffffffLL) return fail(RT_ERR_INVALID, "too many tiles");
     p.tile_z_log2 = t.z_log2;
@@ -1357,8 +1396,8 @@ int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int 
     help_desk(s, clusters_kernel, W, x0, x1, bc.block, bc.stack_lds_levels, p, &plan->lds_bytes);
     p.tile_prio = tile_prio(s, W, x0, x1);
     heavy_band(s, cam, W, H, x0, x1, t, p);
-    if (!counting) learned_start_row(s, W, H, x0, x1, max_depth, t, p);
-    plan->kernel = choose_kernel(s, counting, bc.global_tables, bc.block, plan->lds_bytes, ssaa_log2 > 0);
+    if (!counting && !rays) learned_start_row(s, W, H, x0, x1, max_depth, t, p);
+    plan->kernel = choose_kernel(s, counting, bc.global_tables, bc.block, plan->lds_bytes, ssaa_log2 > 0, rays != nullptr);
     plan->help = p.help_rays_quads != 0;
     return RT_OK;
 }
@@ -1386,9 +1425,9 @@ int device_report(rt_scene *s) {
 
 /* plan_launch(), then the device work: counters, timeline, occupancy and grid, bounce stack and HELP areas, the event ring */
 int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
-           float *d_out, hipStream_t stream, unsigned long long *d_stats = nullptr, int ssaa_log2 = 0) {
+           float *d_out, hipStream_t stream, unsigned long long *d_stats = nullptr, int ssaa_log2 = 0, const RayBatch *rays = nullptr) {
     LaunchPlan plan;
-    int rc = plan_launch(s, cam, W, H, x0, x1, max_depth, d_out, d_stats != nullptr, &plan, ssaa_log2);
+    int rc = plan_launch(s, cam, W, H, x0, x1, max_depth, d_out, d_stats != nullptr, &plan, ssaa_log2, rays);
     if (rc) return rc;
     RtParams &p = plan.p;
     const int block = plan.block;
@@ -1491,11 +1530,11 @@ int frame_preamble(rt_scene *s, int W, int H, int x0, int x1, const float *out_r
     return grow_device_buffer(&s->d_fb, &s->d_fb_bytes, *bytes);
 }
 
-/* rt_render and rt_render_ssaa, under the handle's lock, after frame_preamble(): the launch into the handle's framebuffer, the
- * download of its `bytes`, the synchronisation */
+/* rt_render, rt_render_ssaa and rt_trace_rays, under the handle's lock, after frame_preamble() (or its ray-batch equivalent):
+ * the launch into the handle's framebuffer, the download of its `bytes`, the synchronisation */
 int render_to_host(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, float *out_rgb,
-                   size_t bytes, int ssaa_log2) {
-    int rc = launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr, nullptr, ssaa_log2);
+                   size_t bytes, int ssaa_log2, const RayBatch *rays = nullptr) {
+    int rc = launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr, nullptr, ssaa_log2, rays);
     if (rc) return rc;
     s->timing.last_download_ms = 0.0;
     if (bytes) {
@@ -1529,6 +1568,25 @@ int ssaa_args(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_d
     rc = check_launch_args(cam, W << kl, H << kl, x0 << kl, x1 << kl, max_depth, out);
     if (rc) return rc;
     *log2k = kl;
+    return RT_OK;
+}
+
+/* rt_trace_rays*: the checks of include/rt_capi_rays.h in its order, all before the device is touched, and the batch's grid.
+ * rows past n are read as n (the same cells, without columns of empty tiles).  The grid's cells -- fewer than n + rows <= 2 n
+ * -- must stay below 2^31 - 64, so that the kernel's cell numbers and row numbers fit an int. */
+int rays_args(const rt_scene *s, int n, int rows, const void *rays, int max_depth, const void *out, RayBatch *b) {
+    if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
+    if (n < 0) return fail(RT_ERR_INVALID, "n < 0");
+    if (rows < 1) return fail(RT_ERR_INVALID, "rows must be positive");
+    if (max_depth < 0) return fail(RT_ERR_INVALID, "max_depth < 0");
+    if (n > 0 && !rays) return fail(RT_ERR_INVALID, "rays pointer is NULL");
+    if (n > 0 && !out) return fail(RT_ERR_INVALID, "output pointer is NULL");
+    if ((double)n * 3.0 > kMaxStripFloats) return fail(RT_ERR_INVALID, "ray batch too large");
+    b->n = n;
+    b->rows = std::min(rows, std::max(n, 1));
+    b->n_cols = (int)(((long long)n + b->rows - 1) / b->rows);
+    if ((long long)b->n_cols * b->rows > 0x7fffffffLL - 64) return fail(RT_ERR_INVALID, "ray batch too large for its rows");
+    b->d_rays = rays;
     return RT_OK;
 }
 
@@ -1583,11 +1641,12 @@ int rt_scene_create(const rt_scene_desc *desc, int device, rt_scene **out) {
 
 int rt_scene_destroy(rt_scene *s) {
     if (!s) return RT_OK;
-    if (s->d_image || s->d_fb || s->d_counters || s->ev_ready) (void)hipSetDevice(s->device);
+    if (s->d_image || s->d_fb || s->d_rays || s->d_counters || s->ev_ready) (void)hipSetDevice(s->device);
     if (s->ev_ready)
         for (int i = 0; i < kEventRing; ++i) { (void)hipEventDestroy(s->ev[i].start); (void)hipEventDestroy(s->ev[i].stop); }
     if (s->d_image) (void)hipFree(s->d_image);
     if (s->d_fb) (void)hipFree(s->d_fb);
+    if (s->d_rays) (void)hipFree(s->d_rays);
     if (s->d_counters) (void)hipFree(s->d_counters);
     if (s->d_help) (void)hipFree(s->d_help);
     if (s->d_stack) (void)hipFree(s->d_stack);
@@ -1643,6 +1702,33 @@ int rt_render_ssaa_device(rt_scene *s, const rt_camera_desc *cam, int W, int H, 
     std::lock_guard<std::mutex> lock(s->mu);
     return launch(s, cam, W << kl, H << kl, x0 << kl, x1 << kl, max_depth, static_cast<float *>(d_out_rgb),
                   static_cast<hipStream_t>(hip_stream), nullptr, kl);
+}
+
+int rt_capi_rays_version(void) { return RT_CAPI_RAYS_VERSION; }
+
+/* RAY BATCH (include/rt_capi_rays.h): the batch into the handle's buffer for it, the launch of its grid, 3 n floats back */
+int rt_trace_rays(rt_scene *s, int n, int rows, const float *rays, int max_depth, float *out_rgb) {
+    RayBatch b;
+    int rc = rays_args(s, n, rows, rays, max_depth, out_rgb, &b);
+    if (rc || n == 0) return rc;
+    std::lock_guard<std::mutex> lock(s->mu);
+    const size_t in_bytes = (size_t)n * 6 * sizeof(float), bytes = (size_t)n * 3 * sizeof(float);
+    HIP_TRY(hipSetDevice(s->device));
+    rc = grow_device_buffer(&s->d_rays, &s->d_rays_bytes, in_bytes);
+    if (rc == RT_OK) rc = grow_device_buffer(&s->d_fb, &s->d_fb_bytes, bytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(s->d_rays, rays, in_bytes, hipMemcpyHostToDevice));
+    b.d_rays = s->d_rays;
+    return render_to_host(s, nullptr, b.n_cols, b.rows, 0, b.n_cols, max_depth, out_rgb, bytes, 0, &b);
+}
+
+int rt_trace_rays_device(rt_scene *s, int n, int rows, const void *d_rays, int max_depth, void *d_out_rgb, void *hip_stream) {
+    RayBatch b;
+    int rc = rays_args(s, n, rows, d_rays, max_depth, d_out_rgb, &b);
+    if (rc || n == 0) return rc;
+    std::lock_guard<std::mutex> lock(s->mu);
+    return launch(s, nullptr, b.n_cols, b.rows, 0, b.n_cols, max_depth, static_cast<float *>(d_out_rgb),
+                  static_cast<hipStream_t>(hip_stream), nullptr, 0, &b);
 }
 
 int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,

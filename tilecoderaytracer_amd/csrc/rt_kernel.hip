@@ -1724,8 +1724,10 @@ __device__ __forceinline__ size_t hbm_stack_entry(const RtParams &p, const int l
 
 /* One wavefront tile: camera rays, the bounce loop, the unwind, the store.  kSsaa: the tile is a rectangle of SAMPLES of a
  * virtual kW x kH image (k = 1 << p.ssaa_log2, both tile sides multiples of k: rt_capi.hip, tile_shape()); the store box-filters
- * them into the W x H output (below). */
-template <bool kStats, int kMode, bool kSsaa = false>
+ * them into the W x H output (below).  kRays: the tile is a rectangle of cells of the n_cols x rows grid of a caller's ray batch
+ * (include/rt_capi_rays.h; launched with W = x1 = n_cols, H = rows, x0 = 0): cell (x, z) is ray x * rows + z, read from
+ * p.rays instead of made by the camera. */
+template <bool kStats, int kMode, bool kSsaa = false, bool kRays = false>
 __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds, float4 *wlds, float4 *help_rays,
                                             const uint32_t *__restrict__ ctl_words, float *__restrict__ out,
                                             float4 *__restrict__ bounce_stack, unsigned long long *__restrict__ stats_out,
@@ -1749,13 +1751,25 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
     const int tzl_a = here(p.tile_z_log2);
     const int x = p.x0 + tile_col * (64 >> tzl_a) + (lane >> tzl_a);
     const int z = (tile_row << tzl_a) + (lane & ((1 << tzl_a) - 1));
-    const bool inside = (x < p.x1) && (z < p.H);
+    /* RAY BATCH: this cell's ray; below 2^31 for cells of the grid (rt_capi.hip, rays_args()), wrapped for the others */
+    const unsigned int ray = kRays ? (unsigned int)x * (unsigned int)here(p.H) + (unsigned int)z : 0u;
+    const bool inside = (x < p.x1) && (z < p.H) && (!kRays || ray < (unsigned int)p.n_rays);   /* (the batch may end inside a tile) */
 
-    /* Camera::createEyeRay, src/Camera.cpp:71-84, with dx = (float)x / W,
-     * dz = (float)z / H from the pixel loop, src/RayTracer.cpp:916-918 */
-    V3 o = mk(p.eye[0], p.eye[1], p.eye[2]);
-    V3 d;
-    {
+    V3 o, d;
+    if constexpr (kRays) {
+        /* RAY BATCH: {E, T}, 24 bytes per ray, consecutive lanes read consecutive records.  Lanes outside read the last ray
+         * instead (n_rays >= 1 in every launch): every read is inside the batch, with no branch around the loads -- the branch's
+         * lane mask cost the clustered-scene kernels six more spilled scalars -- and they go on with an ordinary direction,
+         * so that the wavefront keeps normalize3()'s short path.  The direction is createEyeRay's arithmetic on the caller's
+         * points: normalize(T - E). */
+        const float *rec = reinterpret_cast<const float *>(p.rays) + (size_t)min(ray, (unsigned int)p.n_rays - 1u) * 6;
+        const V3 e = mk(rec[0], rec[1], rec[2]), tgt = mk(rec[3], rec[4], rec[5]);
+        o = inside ? e : mk(0.0f, 0.0f, 0.0f);
+        d = normalize3(sub3(inside ? tgt : mk(1.0f, 1.0f, 1.0f), o));
+    } else {
+        /* Camera::createEyeRay, src/Camera.cpp:71-84, with dx = (float)x / W,
+         * dz = (float)z / H from the pixel loop, src/RayTracer.cpp:916-918 */
+        o = mk(p.eye[0], p.eye[1], p.eye[2]);
         const float dx_percent = ((float)x) / (float)here(p.W);
         const float dy_percent = ((float)z) / (float)here(p.H);
         const float scalar_x = dx_percent * p.sw - p.shw;
@@ -1773,8 +1787,12 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
 
     /* calculatePixel, src/RayTracer.cpp:448-638, levels 0..max_depth */
     /* a box around the origins of the rays about to be traced: the eye at level 0,
-     * afterwards the shading points of the level before (reflected rays start there) */
+     * afterwards the shading points of the level before (reflected rays start there).
+     * RAY BATCH: no eye -- the box of the level-0 origins is the wavefront's bounds of the lanes' origins, taken here, where
+     * the level-0 scans would take them (have_box = false there, the same bounds: alive == inside): as a box carried in, the
+     * clustered-scene kernels spill fewer scalars. */
     V3 box_lo = o, box_hi = o;
+    if constexpr (kRays) wave_bounds3(o, inside, &box_lo, &box_hi);
     bool have_box = true;
     for (int level = 0; level <= p.max_depth; ++level) {
         if (__ballot(alive) == 0ull) break;
@@ -1796,7 +1814,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
         }
         if constexpr (kMode == 6) {
             const int tzl_n = here(p.tile_z_log2);
-            nearest_hit_fast<kStats>(p, lds, ctl_words, alive, o, d, have_box, box_lo, box_hi, level == 0,
+            nearest_hit_fast<kStats>(p, lds, ctl_words, alive, o, d, have_box, box_lo, box_hi, !kRays && level == 0,
                                      p.x0 + here(tile_col) * (64 >> tzl_n), here(tile_row) << tzl_n, &t, &idx, st);
         }
         else nearest_hit_items<kStats, kMode>(p, lds, wlds, alive, o, d, have_box, box_lo, box_hi, &t, &idx, st);   /* whole wavefront, converged */
@@ -2128,7 +2146,8 @@ __device__ RT_SCAN_INLINE unsigned int queues_with_tiles(const unsigned int *til
     return (unsigned int)__builtin_amdgcn_ballot_w64(left > 0) & 0xFFu;
 }
 
-template <bool kStats, bool kGlobalTables = false, bool kClusters = false, bool kRoomy = false, bool kFast = false, bool kSsaa = false>
+template <bool kStats, bool kGlobalTables = false, bool kClusters = false, bool kRoomy = false, bool kFast = false, bool kSsaa = false,
+          bool kRays = false>
 __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__restrict__ image,
                                             float *__restrict__ out, unsigned int *__restrict__ tile_counter,
                                             float4 *__restrict__ bounce_stack,
@@ -2337,8 +2356,8 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
          * successor comes from the HEAVY tiles' own head) */
         unsigned int *const ask_head = (ask_ahead || (kHelp && heavy_phase != 0)) ? nullptr
                                      : tile_counter + ((my_xcc + steal) & (RT_TILE_QUEUES - 1)) * RT_QUEUE_STRIDE;
-        render_tile<kStats, kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0), kSsaa>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave, my_xcc,
-                                                                                  steal, next_pop, ask_head);
+        render_tile<kStats, kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0), kSsaa, kRays>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
+                                                                                         my_xcc, steal, next_pop, ask_head);
 #ifdef RT_TIMELINE
         if (p.timeline != 0ull && lane == 0) {                   /* ... when it was done, and by whom */
             unsigned long long *rec = reinterpret_cast<unsigned long long *>(p.timeline) + (size_t)tile_number * RT_TIMELINE_WORDS;
@@ -2403,8 +2422,8 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
 #define RT_BLOCK_BOUND_CLUSTERS 512
 #endif
 
-/* rt_kernel_ssaa.hip includes this file for the body alone and defines the supersampling kernels: in a translation unit of
- * their own, the seven kernels below compile to the code they have without them (next to five more instantiations of the
+/* rt_kernel_ssaa.hip and rt_kernel_rays.hip include this file for the body alone and define the supersampling and the ray-batch
+ * kernels: in translation units of their own, the seven kernels below compile to the code they have without them (next to five more instantiations of the
  * body in one module, the item-table kernel's allocation moved: one more spilled scalar) */
 #ifndef RT_KERNEL_BODY_ONLY
 

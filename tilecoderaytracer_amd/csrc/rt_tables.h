@@ -212,7 +212,11 @@ typedef struct RtParams {
      * that no other field moves; padded to 16 bytes, so that the kernel arguments behind the struct keep their kernarg
      * offsets modulo 16: the scalar loads of those merge as before, and the other kernels' code differs in those offsets only.) */
     int32_t ssaa_log2;
-    int32_t ssaa_pad[3];
+    /* RAY BATCH (include/rt_capi_rays.h; the *_rays kernels only): n_rays rays of {E.xyz, T.xyz} fp32 at device address `rays`,
+     * ray i at cell (i / H, i % H) of a W x H launch (W = x1 = n_cols, x0 = 0); no camera, no PRIMARY table.  (Where ssaa_pad[3]
+     * was: `rays` at offset 1344 is 8-aligned, so no other field moves and the struct keeps its 1352 bytes.) */
+    int32_t n_rays;
+    uint64_t rays;
 } RtParams;
 #define RT_TIMELINE_WORDS 4
 

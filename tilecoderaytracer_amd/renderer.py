@@ -68,6 +68,27 @@ class Renderer:
         capi.check(self._lib.rt_render_ssaa_device(self._scene, self._cam, W, H, x0, x1, max_depth, samples,
                                                    C.c_void_p(device_ptr), C.c_void_p(stream)))
 
+    def trace_rays(self, rays, max_depth, rows=None):
+        """Trace a batch of primary rays (include/rt_capi_rays.h).  rays: C-contiguous float32, (n, 6) -- rows defaults to n --
+        or (X, Z, 6), ray [x, z] = cell (x, z) of the grid, rows = Z; each ray {E.xyz, T.xyz} starts at E towards T.
+        -> float32 (n, 3) or (X, Z, 3).  rows only shapes the launch; the results do not depend on it."""
+        if not isinstance(rays, np.ndarray) or rays.dtype != np.float32 or not rays.flags.c_contiguous:
+            raise TypeError("rays must be a C-contiguous float32 numpy array")
+        if rays.ndim not in (2, 3) or rays.shape[-1] != 6:
+            raise ValueError(f"rays must have shape (n, 6) or (X, Z, 6), not {rays.shape}")
+        n = rays.size // 6
+        if rows is None:
+            rows = max(rays.shape[1] if rays.ndim == 3 else n, 1)       # (an empty batch: any rows)
+        out = np.empty(rays.shape[:-1] + (3,), dtype=np.float32)
+        capi.check(self._lib.rt_trace_rays(self._scene, n, int(rows), rays.ctypes.data, max_depth, out.ctypes.data))
+        return out
+
+    def trace_rays_device(self, n, rows, rays_ptr, max_depth, out_ptr, stream=0):
+        """Enqueue the tracing of n rays (6 float32 each) at device address rays_ptr into 3 n float32 at out_ptr on a HIP
+        stream (no sync; rays_ptr must stay valid until the stream has drained)."""
+        capi.check(self._lib.rt_trace_rays_device(self._scene, n, rows, C.c_void_p(rays_ptr), max_depth, C.c_void_p(out_ptr),
+                                                  C.c_void_p(stream)))
+
     STAT_NAMES = ("nearest_rays", "shadow_rays", "wave_nearest_scans", "wave_shadow_scans",
                   "wave_sphere_tests", "wave_plane_tests", "wave_box_tests", "lane_sphere_tests",
                   "cycles_nearest", "cycles_shadow", "cycles_tile",
