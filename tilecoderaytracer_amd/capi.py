@@ -154,6 +154,13 @@ def load_library():
         lib.rt_trace_rays.argtypes = [vp, i, i, vp, i, vp]
         lib.rt_trace_rays_device.argtypes = [vp, i, i, vp, i, vp, vp]
         lib.rt_trace_rays.restype = lib.rt_trace_rays_device.restype = i
+    # include/rt_capi_query.h (likewise absent from older builds)
+    if hasattr(lib, "rt_intersect_rays"):
+        lib.rt_capi_query_version.restype = i
+        lib.rt_intersect_rays.argtypes = lib.rt_occluded_rays.argtypes = [vp, i, i, vp, vp]
+        lib.rt_intersect_rays_device.argtypes = lib.rt_occluded_rays_device.argtypes = [vp, i, i, vp, vp, vp]
+        for name in ("rt_intersect_rays", "rt_intersect_rays_device", "rt_occluded_rays", "rt_occluded_rays_device"):
+            getattr(lib, name).restype = i
     for name in ("rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_render",
                  "rt_render_device", "rt_render_multi", "rt_render_stats", "rt_learn_tile_order", "rt_get_timing", "rt_reset_timing",
                  "rt_get_launch_info", "rt_set_option", "rt_chunk_bounds", "rt_multi_create", "rt_multi_render",

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/rt_capi_query.h"
 #include "../../include/rt_capi_rays.h"
 #include "../../include/rt_capi_ssaa.h"
 #include "../../include/rt_capi_tuning.h"
@@ -45,6 +46,16 @@ RT_DECLARE_KERNEL(rt_render_kernel_items_rays);
 RT_DECLARE_KERNEL(rt_render_kernel_large_rays);
 RT_DECLARE_KERNEL(rt_render_kernel_clusters_rays);
 RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_rays);
+RT_DECLARE_KERNEL(rt_render_kernel_hits);             /* ... asking about a caller's rays (rt_kernel_query.hip) */
+RT_DECLARE_KERNEL(rt_render_kernel_items_hits);
+RT_DECLARE_KERNEL(rt_render_kernel_large_hits);
+RT_DECLARE_KERNEL(rt_render_kernel_clusters_hits);
+RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_hits);
+RT_DECLARE_KERNEL(rt_render_kernel_occluded);
+RT_DECLARE_KERNEL(rt_render_kernel_items_occluded);
+RT_DECLARE_KERNEL(rt_render_kernel_large_occluded);
+RT_DECLARE_KERNEL(rt_render_kernel_clusters_occluded);
+RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_occluded);
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_stats);      /* the counting builds */
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_fast_stats);
 
@@ -52,6 +63,7 @@ RT_DECLARE_STATS_KERNEL(rt_render_kernel_fast_stats);
 static_assert(offsetof(RtParams, ssaa_log2) == 1336 && offsetof(RtParams, n_rays) == 1340 && offsetof(RtParams, rays) == 1344 &&
                   sizeof(RtParams) == 1352,
               "RtParams layout");
+static_assert(sizeof(rt_hit) == RT_HIT_BYTES && offsetof(rt_hit, normal) == 20 && offsetof(rt_hit, flags) == 44, "rt_hit layout");
 
 namespace {
 
@@ -1182,8 +1194,9 @@ void camera_params(const rt_camera_desc *cam, int W, int H, int x0, int x1, int 
 }
 
 /* RAY BATCH (include/rt_capi_rays.h): n rays {E, T} at a device address, laid out as an n_cols x rows grid -- launched as the
- * image of that size (W = x1 = n_cols, H = rows, x0 = 0) without a camera */
-struct RayBatch { int n = 0, rows = 0, n_cols = 0; const void *d_rays = nullptr; };
+ * image of that size (W = x1 = n_cols, H = rows, x0 = 0) without a camera.  query (include/rt_capi_query.h): RT_QUERY_HITS or
+ * RT_QUERY_OCCLUDED asks the *_hits or *_occluded kernels instead of shading the rays. */
+struct RayBatch { int n = 0, rows = 0, n_cols = 0; const void *d_rays = nullptr; int query = RT_QUERY_NONE; };
 
 void batch_params(const RayBatch &b, int max_depth, RtParams &p) {
     p.W = b.n_cols; p.H = b.rows; p.x0 = 0; p.x1 = b.n_cols; p.max_depth = max_depth;
@@ -1322,17 +1335,22 @@ void learned_start_row(const rt_scene *s, int W, int H, int x0, int x1, int max_
 
 struct Kernel { const void *fn; const char *name; };
 #define RT_KERNEL(k) Kernel{(const void *)k, #k}
-/* a kernel and its supersampling and ray-batch siblings */
-struct Siblings { Kernel plain, ssaa, rays; };
-#define RT_SIBLINGS(k) Siblings{RT_KERNEL(k), RT_KERNEL(k##_ssaa), RT_KERNEL(k##_rays)}
+/* a kernel and its supersampling, ray-batch and ray-query siblings */
+struct Siblings { Kernel plain, ssaa, rays, hits, occluded; };
+#define RT_SIBLINGS(k) Siblings{RT_KERNEL(k), RT_KERNEL(k##_ssaa), RT_KERNEL(k##_rays), RT_KERNEL(k##_hits), RT_KERNEL(k##_occluded)}
 
 /* the kernel: FAST tables, item tables, the one for clustered scenes (in the register budget that fits the occupancy LDS
- * allows), or the large-scene one; supersampled (ssaa) or over a ray batch (rays): the *_ssaa or *_rays sibling of the same */
+ * allows), or the large-scene one; supersampled (ssaa) or over a ray batch (rays): the *_ssaa or *_rays sibling of the same;
+ * a ray batch's query (RT_QUERY_*): the *_hits or *_occluded sibling */
 Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int block, int lds_bytes, bool ssaa = false,
-                     bool rays = false) {
+                     bool rays = false, int query = RT_QUERY_NONE) {
     const bool fast_tables = s->base.n_fast_items > 0;
     if (counting) return fast_tables ? RT_KERNEL(rt_render_kernel_fast_stats) : RT_KERNEL(rt_render_kernel_stats);
-    const auto pick = [&](const Siblings &k) { return ssaa ? k.ssaa : (rays ? k.rays : k.plain); };
+    const auto pick = [&](const Siblings &k) {
+        if (query == RT_QUERY_HITS) return k.hits;
+        if (query == RT_QUERY_OCCLUDED) return k.occluded;
+        return ssaa ? k.ssaa : (rays ? k.rays : k.plain);
+    };
     if (global_tables) return pick(RT_SIBLINGS(rt_render_kernel_large));
     if (s->n_clusters > 0 && s->pairs_opt) {
         /* the 96-register kernel when LDS leaves room for fewer than six wavefronts per SIMD anyway (24 per CU) */
@@ -1356,7 +1374,8 @@ struct LaunchPlan {
  * ssaa_log2 > 0 (rt_render_ssaa): W, H, x0, x1 are the VIRTUAL image's, every decision is taken on it, and the kernel averages
  * each pixel's k x k samples into a W / k x H / k output.
  * rays (rt_trace_rays; cam is NULL, the batch checked by rays_args()): W, H, x0, x1 are its grid's, n_cols x rows from column 0;
- * every decision that needs a camera -- PRIMARY table, automatic start row, HEAVY band, learned order -- is "none". */
+ * every decision that needs a camera -- PRIMARY table, automatic start row, HEAVY band, learned order -- is "none".
+ * A ray batch's query (rays->query, include/rt_capi_query.h; max_depth 0: no bounce stack) has no HELP desk either. */
 int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *d_out,
                 bool counting, LaunchPlan *plan, int ssaa_log2 = 0, const RayBatch *rays = nullptr) {
     int rc = rays ? RT_OK : check_launch_args(cam, W, H, x0, x1, max_depth, d_out);
@@ -1393,11 +1412,12 @@ int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int 
     plan->n_tiles = n_tiles;
     if (n_tiles == 0) return RT_OK;
     const bool clusters_kernel = !counting && !bc.global_tables && s->n_clusters > 0 && s->pairs_opt;
-    help_desk(s, clusters_kernel, W, x0, x1, bc.block, bc.stack_lds_levels, p, &plan->lds_bytes);
+    const int query = rays ? rays->query : RT_QUERY_NONE;
+    help_desk(s, clusters_kernel && query == RT_QUERY_NONE, W, x0, x1, bc.block, bc.stack_lds_levels, p, &plan->lds_bytes);
     p.tile_prio = tile_prio(s, W, x0, x1);
     heavy_band(s, cam, W, H, x0, x1, t, p);
     if (!counting && !rays) learned_start_row(s, W, H, x0, x1, max_depth, t, p);
-    plan->kernel = choose_kernel(s, counting, bc.global_tables, bc.block, plan->lds_bytes, ssaa_log2 > 0, rays != nullptr);
+    plan->kernel = choose_kernel(s, counting, bc.global_tables, bc.block, plan->lds_bytes, ssaa_log2 > 0, rays != nullptr, query);
     plan->help = p.help_rays_quads != 0;
     return RT_OK;
 }
@@ -1530,7 +1550,7 @@ int frame_preamble(rt_scene *s, int W, int H, int x0, int x1, const float *out_r
     return grow_device_buffer(&s->d_fb, &s->d_fb_bytes, *bytes);
 }
 
-/* rt_render, rt_render_ssaa and rt_trace_rays, under the handle's lock, after frame_preamble() (or its ray-batch equivalent):
+/* rt_render, rt_render_ssaa, rt_trace_rays and the host ray queries, under the handle's lock, after frame_preamble() (or its ray-batch equivalent):
  * the launch into the handle's framebuffer, the download of its `bytes`, the synchronisation */
 int render_to_host(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, float *out_rgb,
                    size_t bytes, int ssaa_log2, const RayBatch *rays = nullptr) {
@@ -1588,6 +1608,40 @@ int rays_args(const rt_scene *s, int n, int rows, const void *rays, int max_dept
     if ((long long)b->n_cols * b->rows > 0x7fffffffLL - 64) return fail(RT_ERR_INVALID, "ray batch too large for its rows");
     b->d_rays = rays;
     return RT_OK;
+}
+
+/* rt_intersect_rays* and rt_occluded_rays*: the checks of include/rt_capi_query.h in its order -- rays_args()'s without the
+ * depth -- and the batch's grid */
+int query_args(const rt_scene *s, int n, int rows, const void *in, const void *out, int query, RayBatch *b) {
+    int rc = rays_args(s, n, rows, in, 0, out, b);
+    b->query = query;
+    return rc;
+}
+
+/* a host batch: into the handle's buffers, the launch of its grid at depth 0, out_bytes_per_ray * n bytes back */
+int query_to_host(rt_scene *s, int n, int rows, const float *in, void *out, int query, size_t out_bytes_per_ray) {
+    RayBatch b;
+    int rc = query_args(s, n, rows, in, out, query, &b);
+    if (rc || n == 0) return rc;
+    std::lock_guard<std::mutex> lock(s->mu);
+    const size_t in_bytes = (size_t)n * 6 * sizeof(float), bytes = (size_t)n * out_bytes_per_ray;
+    HIP_TRY(hipSetDevice(s->device));
+    rc = grow_device_buffer(&s->d_rays, &s->d_rays_bytes, in_bytes);
+    if (rc == RT_OK) rc = grow_device_buffer(&s->d_fb, &s->d_fb_bytes, bytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(s->d_rays, in, in_bytes, hipMemcpyHostToDevice));
+    b.d_rays = s->d_rays;
+    return render_to_host(s, nullptr, b.n_cols, b.rows, 0, b.n_cols, 0, static_cast<float *>(out), bytes, 0, &b);
+}
+
+/* a device batch, enqueued on the caller's stream */
+int query_on_device(rt_scene *s, int n, int rows, const void *d_in, void *d_out, int query, void *hip_stream) {
+    RayBatch b;
+    int rc = query_args(s, n, rows, d_in, d_out, query, &b);
+    if (rc || n == 0) return rc;
+    std::lock_guard<std::mutex> lock(s->mu);
+    return launch(s, nullptr, b.n_cols, b.rows, 0, b.n_cols, 0, static_cast<float *>(d_out), static_cast<hipStream_t>(hip_stream),
+                  nullptr, 0, &b);
 }
 
 } // namespace
@@ -1729,6 +1783,25 @@ int rt_trace_rays_device(rt_scene *s, int n, int rows, const void *d_rays, int m
     std::lock_guard<std::mutex> lock(s->mu);
     return launch(s, nullptr, b.n_cols, b.rows, 0, b.n_cols, max_depth, static_cast<float *>(d_out_rgb),
                   static_cast<hipStream_t>(hip_stream), nullptr, 0, &b);
+}
+
+int rt_capi_query_version(void) { return RT_CAPI_QUERY_VERSION; }
+
+/* RAY QUERIES (include/rt_capi_query.h): a ray batch at depth 0 through the *_hits or *_occluded kernels */
+int rt_intersect_rays(rt_scene *s, int n, int rows, const float *rays, rt_hit *out_hits) {
+    return query_to_host(s, n, rows, rays, out_hits, RT_QUERY_HITS, sizeof(rt_hit));
+}
+
+int rt_intersect_rays_device(rt_scene *s, int n, int rows, const void *d_rays, void *d_out_hits, void *hip_stream) {
+    return query_on_device(s, n, rows, d_rays, d_out_hits, RT_QUERY_HITS, hip_stream);
+}
+
+int rt_occluded_rays(rt_scene *s, int n, int rows, const float *segs, uint8_t *out_blocked) {
+    return query_to_host(s, n, rows, segs, out_blocked, RT_QUERY_OCCLUDED, 1);
+}
+
+int rt_occluded_rays_device(rt_scene *s, int n, int rows, const void *d_segs, void *d_out_blocked, void *hip_stream) {
+    return query_on_device(s, n, rows, d_segs, d_out_blocked, RT_QUERY_OCCLUDED, hip_stream);
 }
 
 int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,

@@ -1714,6 +1714,57 @@ __device__ __forceinline__ V3 entry_colour(const RtParams &p, const float4 *lds,
 
 } // namespace
 
+/* The winner's CollisionObject for the record of a *_hits kernel -- render_tile()'s phase 1 written as a function (render_tile()
+ * keeps its own copy: taking this function there moved the register allocation of the existing kernels and added scratch
+ * stores): Scene index idx at distance t along
+ * the ray (o, d) gives the intersection point P, the normal N (before the CollisionObject ctor re-normalises it) and the texture
+ * selector (0: the material's colour); returns the material's second quad (m1.w: its bits), with its number and the kind. */
+__device__ __forceinline__ float4 winner_geometry(const RtParams &p, const float4 *lds, const int idx, const float t, const V3 o,
+                                                  const V3 d, V3 *P_out, V3 *N_out, int *texsel_out, int *mat_out, int *kind_out) {
+    const uint32_t *lds_u32 = reinterpret_cast<const uint32_t *>(lds);
+    const uint32_t info = lds_u32[p.objinfo_off * 4 + idx];
+    const float4 *g = lds + (info & 0xFFFFu);
+    const int kind = (int)((info >> 16) & 3u);
+    const int mat = (int)(info >> 20);
+    const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
+    const uint32_t mbits = __float_as_uint(m1.w);
+    V3 P, N;                                     /* (locals, stored once at the end: through the pointers they went to scratch) */
+    int texsel = 0;
+    if (kind == RT_KIND_SPHERE) {                /* src/SceneSphere.cpp:118-149 */
+        const float4 s = g[0];
+        P = add3(scale3(d, t), o);
+        N = normalize3(sub3(P, xyz(s)));
+    } else {                                     /* src/SceneInfinitePlane.cpp:53-95, src/SceneFinitePlane.cpp:106-150 */
+        const float4 q0 = g[0], q1 = g[1], q2 = g[2], q3 = g[3], q4 = g[4];
+        const V3 ip = add3(scale3(d, t), o);
+        if ((mbits >> 1) != 0u) {
+            const V3 PO = sub3(ip, xyz(q1));
+            const float tx = dot3(PO, xyz(q2));
+            const float ty = dot3(PO, xyz(q3));
+            const int tex = (int)(mbits >> 1) - 1;
+            const float4 t0 = lds[p.tex_off + tex * RT_TEX_QUADS];
+            const float4 t1 = lds[p.tex_off + tex * RT_TEX_QUADS + 1];
+            texsel = checkerboard_select(t0.w, t1.w, tx, ty);
+        }
+        N = (dot3(xyz(q0), d) < 0) ? xyz(q0) : xyz(q4);
+        P = add3(ip, scale3(N, (float)1E-3));
+    }
+    *P_out = P;
+    *N_out = N;
+    *texsel_out = texsel;
+    *mat_out = mat;
+    *kind_out = kind;
+    return m1;
+}
+
+/* RAY BATCH: ray `ray` = {E, T} of p.rays, 24 bytes, consecutive lanes read consecutive records, as render_tile() reads them
+ * (kRays).  Lanes outside read the last ray instead (n_rays >= 1 in every launch) and go on from the origin towards (1, 1, 1). */
+__device__ __forceinline__ void batch_ray(const RtParams &p, const unsigned int ray, const bool inside, V3 *e, V3 *tgt) {
+    const float *rec = reinterpret_cast<const float *>(p.rays) + (size_t)min(ray, (unsigned int)p.n_rays - 1u) * 6;
+    *e = inside ? mk(rec[0], rec[1], rec[2]) : mk(0.0f, 0.0f, 0.0f);
+    *tgt = inside ? mk(rec[3], rec[4], rec[5]) : mk(1.0f, 1.0f, 1.0f);
+}
+
 /* Entry [level][threadIdx.x] of this workgroup's slice of the HBM bounce stack.
  * Computed where it is used, from scalar pieces (the host keeps the whole
  * buffer below 2^32 entries), so no per-lane address lives across the scans. */
@@ -2116,6 +2167,134 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
     }
 }
 
+/* ---- RAY QUERIES (include/rt_capi_query.h): the tiles of the *_hits and *_occluded kernels --------------------------------
+ * A ray-batch tile (render_tile(), kRays: cell (x, z) of the n_cols x rows grid is ray x * rows + z) that asks the scene one
+ * question per lane and stores the answer: no shading, no bounce stack, no HELP. */
+
+/* this lane's cell of the grid and whether it holds a ray of the batch (render_tile()'s, with x0 = 0) */
+__device__ __forceinline__ unsigned int query_cell(const RtParams &p, const int wave, bool *inside) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int tile_row = wave / p.tiles_x;
+    const int tile_col = wave - tile_row * p.tiles_x;
+    const int tzl = here(p.tile_z_log2);
+    const int x = tile_col * (64 >> tzl) + (lane >> tzl);
+    const int z = (tile_row << tzl) + (lane & ((1 << tzl) - 1));
+    const unsigned int ray = (unsigned int)x * (unsigned int)here(p.H) + (unsigned int)z;
+    *inside = (x < p.x1) && (z < p.H) && ray < (unsigned int)p.n_rays;
+    return ray;
+}
+
+/* The clustered-scene kernels ask for their next tile when a tile's rays are through (render_body(): ask_head); the answer
+ * becomes a scalar before the tile's stores, as in render_tile() */
+__device__ __forceinline__ void query_next_tile(int &next_pop, unsigned int *const ask_head) {
+    if (ask_head != nullptr && (threadIdx.x & 63u) == 0u) next_pop = (int)atomicAdd(ask_head, 1u);
+    next_pop = __builtin_amdgcn_readfirstlane(next_pop);
+}
+
+/* HITS: getCollision(Ray(E, normalize(T - E))) over the whole Scene -- phase 1 of render_tile()'s level 0 on a ray batch, the
+ * same scan and the same winner arithmetic -- stored as one rt_hit record of 48 bytes per ray: three 16-byte stores per lane,
+ * consecutive lanes writing consecutive records.  The normal is the CollisionObject's normal_ray direction, i.e. the winner's
+ * normal re-normalised (src/SceneObject.h:62): sqrtf(1) = 1 and v / 1 = v when N.N rounds to 1, so the divide is only taken
+ * where it is not (as renormalize3()).  A miss: object -1 and zeros. */
+template <int kMode>
+__device__ __forceinline__ void hits_tile(const RtParams &p, const float4 *lds, float4 *wlds, const uint32_t *__restrict__ ctl_words,
+                                          float *__restrict__ out, const int wave_in, int &next_pop, unsigned int *const ask_head) {
+    Stats<false> st;
+    const int wave = __builtin_amdgcn_readfirstlane(wave_in);
+    bool inside;
+    const unsigned int ray = query_cell(p, wave, &inside);
+    V3 o, tgt;
+    batch_ray(p, ray, inside, &o, &tgt);
+    const V3 d = normalize3(sub3(tgt, o));
+    float t = 0.0f;
+    int idx = -1;
+    if (wave_any(inside)) {
+        V3 box_lo, box_hi;
+        wave_bounds3(o, inside, &box_lo, &box_hi);
+        if constexpr (kMode == 6) nearest_hit_fast<false>(p, lds, ctl_words, inside, o, d, true, box_lo, box_hi, false, 0, 0, &t, &idx, st);
+        else nearest_hit_items<false, kMode>(p, lds, wlds, inside, o, d, true, box_lo, box_hi, &t, &idx, st);
+    }
+    query_next_tile(next_pop, ask_head);
+    float4 q0 = make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f), q1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q2 = q1;
+    if (inside && idx >= 0) {
+        V3 P, N;
+        int texsel = 0, mat, kind;
+        const float4 m1 = winner_geometry(p, lds, idx, t, o, d, &P, &N, &texsel, &mat, &kind);
+        const uint32_t mbits = __float_as_uint(m1.w);
+        const float nn = N.x * N.x + N.y * N.y + N.z * N.z;
+        if (nn != 1.0f) {
+            const float length = sqrtf(nn);
+            N = mk(N.x / length, N.y / length, N.z / length);
+        }
+        const V3 c = entry_colour(p, lds, lds[p.mat_off + mat * RT_MAT_QUADS], mbits, texsel);
+        /* bit 0: an inside hit -- the sphere's root1 < 0 (src/SceneSphere.cpp:80-95), which is the distance it reports; bit 1: a light */
+        const int flags = (kind == RT_KIND_SPHERE && t < 0.0f ? 1 : 0) | ((mbits & 1u) ? 2 : 0);
+        q0 = make_float4(__int_as_float(idx), t, P.x, P.y);
+        q1 = make_float4(P.z, N.x, N.y, N.z);
+        q2 = make_float4(c.x, c.y, c.z, __int_as_float(flags));
+    }
+    /* Plain stores, not the image's streaming ones: each of the three instructions writes every third quad of the
+     * wavefront's 3 KB, and the lines merge in the L2 only when they stay there (streaming: built-in 4096^2 1.096 -> 0.847 ms,
+     * grid-32 2048^2 0.350 -> 0.222 ms) */
+    if (inside) {
+        float4 *dst = reinterpret_cast<float4 *>(out) + (size_t)ray * 3;
+        dst[0] = q0; dst[1] = q1; dst[2] = q2;
+    }
+}
+
+/* OCCLUDED: inShadeCollisionDetection(Ray(E, T - E), |T - E|) (src/RayTracer.cpp:709-771) -- inShade with the intersection
+ * point E and a light at T: the direction and the distance are the shading's (render_tile(): normalize3() and the length it
+ * takes), the scan in_shade() / in_shade_fast() over [shadow_begin, shadow_end) without lights.  One byte per ray, 0 or 1.
+ *
+ * THE BUNDLE CULL FOR SEGMENTS WITH ENDS OF THEIR OWN.  The shading's cull (above in_shade()) relies on every segment of the
+ * wavefront ending at ONE light: the point at parameter s of any segment is within (1 - s) e of c + s (light - c).  Here each
+ * segment {E_i, T_i} ends elsewhere.  Let c_o, e_o be the centre and half-extent of the box of the lanes' origins, c_e, e_e of
+ * their ends (shading_point_bundle(), each rounded up).  Per axis k,
+ *     |(1 - s) E_i + s T_i - ((1 - s) c_o + s c_e)|_k <= (1 - s) e_o,k + s e_e,k <= e_o,k + e_e,k,
+ * so the slab test of in_shade() with light = c_e, centre c_o and half-extent e = e_o + e_e (rounded up once more) keeps every
+ * item a segment can meet, exactly as it does for the shading: it grows the item boxes by the constant e for every s, never by
+ * (1 - s) e.  The rounding slack is a multiple of `reach` = |light - c|_1 + |e|_1, which bounds the L1 length of every segment
+ * of the wavefront: there |L - E_i|_1 <= |L - c|_1 + |e|_1, here |T_i - E_i|_1 <= |c_e - c_o|_1 + |e_o|_1 + |e_e|_1, the same
+ * expression with e = e_o + e_e.  (The half-extent max(e_o, e_e) would also contain the segments, but its reach would fall
+ * short of the longest segment by up to |min(e_o, e_e)|_1, so the slack argument would no longer hold as written.)  Segments
+ * that end at one point (e_e = 0: hit points towards a light) get the shading's own cull.  A lane whose origin or end has a
+ * NaN is not in the boxes (v_min / v_max skip it) and needs nothing: its direction is NaN, and no test reports a distance
+ * below its distance then; an infinite coordinate makes the boxes' arithmetic NaN, which every slab comparison reads as
+ * "candidate".  The shadow voxels describe segments towards the lights and are not used; there is no HELP. */
+template <int kMode>
+__device__ __forceinline__ void occluded_tile(const RtParams &p, const float4 *lds, float4 *wlds, const uint32_t *__restrict__ ctl_words,
+                                              float *__restrict__ out, const int wave_in, int &next_pop, unsigned int *const ask_head) {
+    Stats<false> st;
+    const int wave = __builtin_amdgcn_readfirstlane(wave_in);
+    bool inside;
+    const unsigned int ray = query_cell(p, wave, &inside);
+    V3 o, tgt;
+    batch_ray(p, ray, inside, &o, &tgt);
+    float dist;                                          /* |T - E|, :748 */
+    const V3 d = normalize3(sub3(tgt, o), &dist);        /* Ray(E, T - E).direction */
+    bool blocked = false;
+    if (wave_any(inside)) {
+        V3 lo, hi, c_o, e_o, c_e, e_e;
+        wave_bounds3(o, inside, &lo, &hi);
+        shading_point_bundle(lo, hi, &c_o, &e_o);
+        wave_bounds3(tgt, inside, &lo, &hi);
+        shading_point_bundle(lo, hi, &c_e, &e_e);
+        const V3 e = mk(uniform_f((e_o.x + e_e.x) * 1.000001f), uniform_f((e_o.y + e_e.y) * 1.000001f),
+                        uniform_f((e_o.z + e_e.z) * 1.000001f));
+        if constexpr (kMode == 6) blocked = in_shade_fast<false>(p, lds, ctl_words, inside, o, d, dist, c_e, c_o, e, false, 0ull, st);
+        else blocked = in_shade<false, kMode>(p, lds, wlds, nullptr, inside, o, d, dist, c_e, c_o, e, ~0ull, st);
+    }
+    query_next_tile(next_pop, ask_head);
+    if (inside) {
+        unsigned char *dst = reinterpret_cast<unsigned char *>(out) + ray;
+#if RT_NT_STORES
+        __builtin_nontemporal_store((unsigned char)(blocked ? 1 : 0), dst);
+#else
+        *dst = blocked ? 1 : 0;
+#endif
+    }
+}
+
 /* which of the tile queues still have tiles to hand out (bit q: queue q).  Its own function, called once per exhausted
  * queue */
 #ifndef RT_SCAN_INLINE
@@ -2147,7 +2326,7 @@ __device__ RT_SCAN_INLINE unsigned int queues_with_tiles(const unsigned int *til
 }
 
 template <bool kStats, bool kGlobalTables = false, bool kClusters = false, bool kRoomy = false, bool kFast = false, bool kSsaa = false,
-          bool kRays = false>
+          bool kRays = false, int kQuery = RT_QUERY_NONE>
 __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__restrict__ image,
                                             float *__restrict__ out, unsigned int *__restrict__ tile_counter,
                                             float4 *__restrict__ bounce_stack,
@@ -2356,8 +2535,11 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
          * successor comes from the HEAVY tiles' own head) */
         unsigned int *const ask_head = (ask_ahead || (kHelp && heavy_phase != 0)) ? nullptr
                                      : tile_counter + ((my_xcc + steal) & (RT_TILE_QUEUES - 1)) * RT_QUEUE_STRIDE;
-        render_tile<kStats, kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0), kSsaa, kRays>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
-                                                                                         my_xcc, steal, next_pop, ask_head);
+        constexpr int kMode = kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0);
+        if constexpr (kQuery == RT_QUERY_HITS) hits_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
+        else if constexpr (kQuery == RT_QUERY_OCCLUDED) occluded_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
+        else render_tile<kStats, kMode, kSsaa, kRays>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
+                                                      my_xcc, steal, next_pop, ask_head);
 #ifdef RT_TIMELINE
         if (p.timeline != 0ull && lane == 0) {                   /* ... when it was done, and by whom */
             unsigned long long *rec = reinterpret_cast<unsigned long long *>(p.timeline) + (size_t)tile_number * RT_TIMELINE_WORDS;
@@ -2422,8 +2604,8 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
 #define RT_BLOCK_BOUND_CLUSTERS 512
 #endif
 
-/* rt_kernel_ssaa.hip and rt_kernel_rays.hip include this file for the body alone and define the supersampling and the ray-batch
- * kernels: in translation units of their own, the seven kernels below compile to the code they have without them (next to five more instantiations of the
+/* rt_kernel_ssaa.hip, rt_kernel_rays.hip and rt_kernel_query.hip include this file for the body alone and define the
+ * supersampling, the ray-batch and the ray-query kernels: in translation units of their own, the seven kernels below compile to the code they have without them (next to five more instantiations of the
  * body in one module, the item-table kernel's allocation moved: one more spilled scalar) */
 #ifndef RT_KERNEL_BODY_ONLY
 

@@ -220,6 +220,12 @@ typedef struct RtParams {
 } RtParams;
 #define RT_TIMELINE_WORDS 4
 
+/* RAY QUERIES (include/rt_capi_query.h): what a ray-batch launch computes -- colours (rt_trace_rays), the *_hits kernels'
+ * 48-byte records or the *_occluded kernels' one-byte verdicts.  A template argument of the kernels and the host's choice of
+ * sibling, not an RtParams field. */
+enum { RT_QUERY_NONE = 0, RT_QUERY_HITS = 1, RT_QUERY_OCCLUDED = 2 };
+#define RT_HIT_BYTES 48
+
 /* FAST tables.  Scenes without clustered sphere runs (the reference's built-in Scene: 32 objects) are walked
  * through ONE item list that serves both scans: first the objects of the shadow scan (the non-light objects of
  * the scan range), then the others; within each part sorted by kind.  Neither scan depends on the order: the

@@ -5,6 +5,11 @@ import numpy as np
 
 from . import capi
 
+# rt_hit of include/rt_capi_query.h: 48 bytes
+HIT_DTYPE = np.dtype([("object", "<i4"), ("distance", "<f4"), ("point", "<f4", (3,)), ("normal", "<f4", (3,)),
+                      ("color", "<f4", (3,)), ("flags", "<i4")])
+assert HIT_DTYPE.itemsize == 48
+
 
 class Renderer:
     """Owns an ``rt_scene`` (device tables for one HostScene on one GPU)."""
@@ -88,6 +93,45 @@ class Renderer:
         stream (no sync; rays_ptr must stay valid until the stream has drained)."""
         capi.check(self._lib.rt_trace_rays_device(self._scene, n, rows, C.c_void_p(rays_ptr), max_depth, C.c_void_p(out_ptr),
                                                   C.c_void_p(stream)))
+
+    def _batch(self, rays, what):
+        if not isinstance(rays, np.ndarray) or rays.dtype != np.float32 or not rays.flags.c_contiguous:
+            raise TypeError(f"{what} must be a C-contiguous float32 numpy array")
+        if rays.ndim not in (2, 3) or rays.shape[-1] != 6:
+            raise ValueError(f"{what} must have shape (n, 6) or (X, Z, 6), not {rays.shape}")
+        n = rays.size // 6
+        return n, max(rays.shape[1] if rays.ndim == 3 else n, 1)
+
+    def intersect_rays(self, rays, rows=None):
+        """What each ray hits (include/rt_capi_query.h, rt_intersect_rays).  rays: C-contiguous float32, (n, 6) -- rows defaults
+        to n -- or (X, Z, 6), rows = Z; each ray {E.xyz, T.xyz} starts at E towards T.  -> a structured array of HIT_DTYPE
+        (rt_hit: object -1 = no hit), shape (n,) or (X, Z).  rows only shapes the launch; the results do not depend on it."""
+        n, default_rows = self._batch(rays, "rays")
+        out = np.zeros(rays.shape[:-1], dtype=HIT_DTYPE)
+        capi.check(self._lib.rt_intersect_rays(self._scene, n, int(default_rows if rows is None else rows), rays.ctypes.data,
+                                               out.ctypes.data))
+        return out
+
+    def intersect_rays_device(self, n, rows, rays_ptr, out_ptr, stream=0):
+        """Enqueue the records (48 bytes each, out_ptr 16-byte aligned) of n rays (6 float32 each) at device address rays_ptr
+        on a HIP stream (no sync; rays_ptr must stay valid until the stream has drained)."""
+        capi.check(self._lib.rt_intersect_rays_device(self._scene, n, rows, C.c_void_p(rays_ptr), C.c_void_p(out_ptr),
+                                                      C.c_void_p(stream)))
+
+    def occluded_rays(self, segs, rows=None):
+        """Whether each segment {E.xyz, T.xyz} is blocked (include/rt_capi_query.h, rt_occluded_rays): inShade with the point E
+        and a light at T.  segs as intersect_rays' rays.  -> bool, shape (n,) or (X, Z)."""
+        n, default_rows = self._batch(segs, "segs")
+        out = np.zeros(segs.shape[:-1], dtype=np.uint8)
+        capi.check(self._lib.rt_occluded_rays(self._scene, n, int(default_rows if rows is None else rows), segs.ctypes.data,
+                                              out.ctypes.data))
+        return out.view(np.bool_)
+
+    def occluded_rays_device(self, n, rows, segs_ptr, out_ptr, stream=0):
+        """Enqueue the verdicts (one byte each, 0 or 1) of n segments (6 float32 each) at device address segs_ptr on a HIP
+        stream (no sync; segs_ptr must stay valid until the stream has drained)."""
+        capi.check(self._lib.rt_occluded_rays_device(self._scene, n, rows, C.c_void_p(segs_ptr), C.c_void_p(out_ptr),
+                                                     C.c_void_p(stream)))
 
     STAT_NAMES = ("nearest_rays", "shadow_rays", "wave_nearest_scans", "wave_shadow_scans",
                   "wave_sphere_tests", "wave_plane_tests", "wave_box_tests", "lane_sphere_tests",
