@@ -161,6 +161,12 @@ def load_library():
         lib.rt_intersect_rays_device.argtypes = lib.rt_occluded_rays_device.argtypes = [vp, i, i, vp, vp, vp]
         for name in ("rt_intersect_rays", "rt_intersect_rays_device", "rt_occluded_rays", "rt_occluded_rays_device"):
             getattr(lib, name).restype = i
+    # include/rt_capi_gbuffer.h (likewise absent from older builds)
+    if hasattr(lib, "rt_render_gbuffer"):
+        lib.rt_capi_gbuffer_version.restype = i
+        lib.rt_render_gbuffer.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, vp, vp]
+        lib.rt_render_gbuffer_device.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, vp, vp, vp]
+        lib.rt_render_gbuffer.restype = lib.rt_render_gbuffer_device.restype = i
     for name in ("rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_render",
                  "rt_render_device", "rt_render_multi", "rt_render_stats", "rt_learn_tile_order", "rt_get_timing", "rt_reset_timing",
                  "rt_get_launch_info", "rt_set_option", "rt_chunk_bounds", "rt_multi_create", "rt_multi_render",

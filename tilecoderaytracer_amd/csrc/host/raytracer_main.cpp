@@ -14,6 +14,8 @@
  *   --gpus G            x-strips over G GPUs, cut by measured cost, sent to GPU 0 with RCCL
  *   --out FILE          (default raytracer_screen.txt)   --no-txt
  *   --ssaa K            K x K samples per pixel, averaged in the render kernel (rt_render_ssaa; K = 1, 2, 4; one GPU)
+ *   --hits FILE         also the W x H rt_hit records of the camera rays (rt_render_gbuffer: raw little-endian, 48 bytes each,
+ *                       pixels[x][z] order); one GPU, no supersampling.  The .txt is the one written without it
  */
 #include <chrono>
 #include <cstdio>
@@ -24,6 +26,7 @@
 #include <vector>
 
 #include "../../../include/rt_capi.h"
+#include "../../../include/rt_capi_gbuffer.h"
 #include "../../../include/rt_capi_ssaa.h"
 #include "celio_model.hpp"
 #include "screen_txt.hpp"
@@ -38,14 +41,14 @@ static std::vector<float> pixels;          /* pixels[x][z] as packed fp32 RGB */
 static int usage(const char *argv0) {
     std::fprintf(stderr,
                  "usage: %s [--width W] [--height H] [--depth D] [--scene 1|2|grid:N[:noshadow]]\n"
-                 "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4]\n", argv0);
+                 "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE]\n", argv0);
     return 1;
 }
 
 int main(int argc, char **argv) {
     int W = 500, H = 504, depth = 50, gpus = 1, ssaa = 1;
     bool write_txt = true;
-    std::string scene_name = "1", out_path = "raytracer_screen.txt";
+    std::string scene_name = "1", out_path = "raytracer_screen.txt", hits_path;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](int &dst) { if (i + 1 >= argc) return false; dst = std::atoi(argv[++i]); return true; };
@@ -56,11 +59,13 @@ int main(int argc, char **argv) {
         else if (a == "--ssaa") { if (!need(ssaa)) return usage(argv[0]); }
         else if (a == "--scene" && i + 1 < argc) scene_name = argv[++i];
         else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
+        else if (a == "--hits" && i + 1 < argc) hits_path = argv[++i];
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
     if (W <= 0 || H <= 0 || depth < 0 || gpus <= 0) return usage(argv[0]);
     if ((ssaa != 1 && ssaa != 2 && ssaa != 4) || (ssaa > 1 && gpus > 1)) return usage(argv[0]);   /* (no multi-GPU supersampling) */
+    if (!hits_path.empty() && (gpus > 1 || ssaa > 1)) return usage(argv[0]);   /* (G-buffers: one GPU, no supersampling) */
     verbose() = true;                          /* console output like the reference's */
 
     if (gpus == 1) std::cout << "Single-Core RayTracing!" << std::endl << std::endl;
@@ -92,6 +97,7 @@ int main(int argc, char **argv) {
     my_scene.flatten(flat);
     my_camera.describe(cam);
     pixels.assign((size_t)W * (size_t)H * 3, 0.0f);
+    std::vector<rt_hit> hits(hits_path.empty() ? 0 : (size_t)W * (size_t)H);
 
     std::printf("****** Start Ray Tracing. *******\n");
     const auto t0 = std::chrono::steady_clock::now();
@@ -101,7 +107,8 @@ int main(int argc, char **argv) {
         rt_scene *scene = nullptr;
         rc = rt_scene_create(&flat.desc, 0, &scene);
         if (rc == RT_OK) rc = ssaa > 1 ? rt_render_ssaa(scene, &cam, W, H, 0, W, depth, ssaa, pixels.data())
-                                       : rt_render(scene, &cam, W, H, 0, W, depth, pixels.data());
+                            : !hits.empty() ? rt_render_gbuffer(scene, &cam, W, H, 0, W, depth, pixels.data(), hits.data())
+                                            : rt_render(scene, &cam, W, H, 0, W, depth, pixels.data());
         if (rc == RT_OK) {
             rt_timing tm;
             if (rt_get_timing(scene, &tm) == RT_OK) kernel_ms = tm.last_kernel_ms;
@@ -148,6 +155,18 @@ int main(int argc, char **argv) {
                     (double)ssaa * (double)ssaa * (double)W * (double)H / (kernel_ms * 1e3), gpus > 1 ? "  [the GPU whose kernels took longest]" : "");
     std::printf("AverageRoundTime (us/pixel): %f\n", run_time_us / ((double)W * (double)H));
 
+    if (!hits.empty()) {
+        FILE *f = std::fopen(hits_path.c_str(), "wb");
+        bool ok = f != nullptr;
+        if (f) {
+            ok = std::fwrite(hits.data(), sizeof(rt_hit), hits.size(), f) == hits.size();
+            ok = std::fclose(f) == 0 && ok;
+        }
+        if (!ok) {
+            std::fprintf(stderr, "cannot write %s\n", hits_path.c_str());
+            return 1;
+        }
+    }
     if (write_txt) {
         std::printf("PrintScreen to Log.\n");
         std::printf("Greetings: %d, %d \n", W, H);

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/rt_capi_gbuffer.h"
 #include "../../include/rt_capi_query.h"
 #include "../../include/rt_capi_rays.h"
 #include "../../include/rt_capi_ssaa.h"
@@ -56,13 +57,20 @@ RT_DECLARE_KERNEL(rt_render_kernel_items_occluded);
 RT_DECLARE_KERNEL(rt_render_kernel_large_occluded);
 RT_DECLARE_KERNEL(rt_render_kernel_clusters_occluded);
 RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_occluded);
+RT_DECLARE_KERNEL(rt_render_kernel_gbuffer);          /* ... a camera's frame with each pixel's hit record (rt_kernel_gbuffer.hip) */
+RT_DECLARE_KERNEL(rt_render_kernel_items_gbuffer);
+RT_DECLARE_KERNEL(rt_render_kernel_large_gbuffer);
+RT_DECLARE_KERNEL(rt_render_kernel_clusters_gbuffer);
+RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_gbuffer);
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_stats);      /* the counting builds */
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_fast_stats);
 
-/* the kernels' view of RtParams: the ray-batch fields took the place of the supersampling padding, nothing else moved */
+/* the kernels' view of RtParams: the ray-batch fields took the place of the supersampling padding, nothing else moved; the
+ * G-buffer's record pointer shares the ray batch's place */
 static_assert(offsetof(RtParams, ssaa_log2) == 1336 && offsetof(RtParams, n_rays) == 1340 && offsetof(RtParams, rays) == 1344 &&
                   sizeof(RtParams) == 1352,
               "RtParams layout");
+static_assert(offsetof(RtParams, gbuffer_hits) == offsetof(RtParams, rays), "RtParams: the G-buffer's records share the rays' place");
 static_assert(sizeof(rt_hit) == RT_HIT_BYTES && offsetof(rt_hit, normal) == 20 && offsetof(rt_hit, flags) == 44, "rt_hit layout");
 
 namespace {
@@ -1335,20 +1343,24 @@ void learned_start_row(const rt_scene *s, int W, int H, int x0, int x1, int max_
 
 struct Kernel { const void *fn; const char *name; };
 #define RT_KERNEL(k) Kernel{(const void *)k, #k}
-/* a kernel and its supersampling, ray-batch and ray-query siblings */
-struct Siblings { Kernel plain, ssaa, rays, hits, occluded; };
-#define RT_SIBLINGS(k) Siblings{RT_KERNEL(k), RT_KERNEL(k##_ssaa), RT_KERNEL(k##_rays), RT_KERNEL(k##_hits), RT_KERNEL(k##_occluded)}
+/* a kernel and its supersampling, ray-batch, ray-query and G-buffer siblings */
+struct Siblings { Kernel plain, ssaa, rays, hits, occluded, gbuffer; };
+#define RT_SIBLINGS(k)                                                                                              \
+    Siblings{RT_KERNEL(k), RT_KERNEL(k##_ssaa), RT_KERNEL(k##_rays), RT_KERNEL(k##_hits), RT_KERNEL(k##_occluded), \
+             RT_KERNEL(k##_gbuffer)}
 
 /* the kernel: FAST tables, item tables, the one for clustered scenes (in the register budget that fits the occupancy LDS
  * allows), or the large-scene one; supersampled (ssaa) or over a ray batch (rays): the *_ssaa or *_rays sibling of the same;
- * a ray batch's query (RT_QUERY_*): the *_hits or *_occluded sibling */
+ * a ray batch's query (RT_QUERY_*): the *_hits or *_occluded sibling; a camera frame with hit records (gbuffer): the *_gbuffer
+ * sibling */
 Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int block, int lds_bytes, bool ssaa = false,
-                     bool rays = false, int query = RT_QUERY_NONE) {
+                     bool rays = false, int query = RT_QUERY_NONE, bool gbuffer = false) {
     const bool fast_tables = s->base.n_fast_items > 0;
     if (counting) return fast_tables ? RT_KERNEL(rt_render_kernel_fast_stats) : RT_KERNEL(rt_render_kernel_stats);
     const auto pick = [&](const Siblings &k) {
         if (query == RT_QUERY_HITS) return k.hits;
         if (query == RT_QUERY_OCCLUDED) return k.occluded;
+        if (gbuffer) return k.gbuffer;
         return ssaa ? k.ssaa : (rays ? k.rays : k.plain);
     };
     if (global_tables) return pick(RT_SIBLINGS(rt_render_kernel_large));
@@ -1375,9 +1387,11 @@ struct LaunchPlan {
  * each pixel's k x k samples into a W / k x H / k output.
  * rays (rt_trace_rays; cam is NULL, the batch checked by rays_args()): W, H, x0, x1 are its grid's, n_cols x rows from column 0;
  * every decision that needs a camera -- PRIMARY table, automatic start row, HEAVY band, learned order -- is "none".
- * A ray batch's query (rays->query, include/rt_capi_query.h; max_depth 0: no bounce stack) has no HELP desk either. */
+ * A ray batch's query (rays->query, include/rt_capi_query.h; max_depth 0: no bounce stack) has no HELP desk either.
+ * d_hits (rt_render_gbuffer*: a camera frame, no supersampling, not counting): every decision is rt_render's for the frame;
+ * the kernel is the *_gbuffer sibling of rt_render's, and p.gbuffer_hits = d_hits. */
 int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *d_out,
-                bool counting, LaunchPlan *plan, int ssaa_log2 = 0, const RayBatch *rays = nullptr) {
+                bool counting, LaunchPlan *plan, int ssaa_log2 = 0, const RayBatch *rays = nullptr, void *d_hits = nullptr) {
     int rc = rays ? RT_OK : check_launch_args(cam, W, H, x0, x1, max_depth, d_out);
     if (rc) return rc;
     BlockChoice bc;
@@ -1387,6 +1401,7 @@ int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int 
     p = s->base;
     if (rays) batch_params(*rays, max_depth, p);
     else camera_params(cam, W, H, x0, x1, max_depth, p);
+    if (d_hits) p.gbuffer_hits = (uint64_t)(uintptr_t)d_hits;
     p.stack_lds_levels = bc.stack_lds_levels;
     p.stack_stride = bc.block;
     p.n_primary = 0;
@@ -1417,7 +1432,8 @@ int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int 
     p.tile_prio = tile_prio(s, W, x0, x1);
     heavy_band(s, cam, W, H, x0, x1, t, p);
     if (!counting && !rays) learned_start_row(s, W, H, x0, x1, max_depth, t, p);
-    plan->kernel = choose_kernel(s, counting, bc.global_tables, bc.block, plan->lds_bytes, ssaa_log2 > 0, rays != nullptr, query);
+    plan->kernel = choose_kernel(s, counting, bc.global_tables, bc.block, plan->lds_bytes, ssaa_log2 > 0, rays != nullptr, query,
+                                 d_hits != nullptr);
     plan->help = p.help_rays_quads != 0;
     return RT_OK;
 }
@@ -1445,9 +1461,10 @@ int device_report(rt_scene *s) {
 
 /* plan_launch(), then the device work: counters, timeline, occupancy and grid, bounce stack and HELP areas, the event ring */
 int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
-           float *d_out, hipStream_t stream, unsigned long long *d_stats = nullptr, int ssaa_log2 = 0, const RayBatch *rays = nullptr) {
+           float *d_out, hipStream_t stream, unsigned long long *d_stats = nullptr, int ssaa_log2 = 0, const RayBatch *rays = nullptr,
+           void *d_hits = nullptr) {
     LaunchPlan plan;
-    int rc = plan_launch(s, cam, W, H, x0, x1, max_depth, d_out, d_stats != nullptr, &plan, ssaa_log2, rays);
+    int rc = plan_launch(s, cam, W, H, x0, x1, max_depth, d_out, d_stats != nullptr, &plan, ssaa_log2, rays, d_hits);
     if (rc) return rc;
     RtParams &p = plan.p;
     const int block = plan.block;
@@ -1550,11 +1567,15 @@ int frame_preamble(rt_scene *s, int W, int H, int x0, int x1, const float *out_r
     return grow_device_buffer(&s->d_fb, &s->d_fb_bytes, *bytes);
 }
 
-/* rt_render, rt_render_ssaa, rt_trace_rays and the host ray queries, under the handle's lock, after frame_preamble() (or its ray-batch equivalent):
- * the launch into the handle's framebuffer, the download of its `bytes`, the synchronisation */
+/* rt_render, rt_render_ssaa, rt_trace_rays, the host ray queries and rt_render_gbuffer, under the handle's lock, after
+ * frame_preamble() (or its ray-batch or G-buffer equivalent): the launch into the handle's framebuffer, the download of its
+ * `bytes`, the synchronisation.  out_hits (rt_render_gbuffer): the records are hits_bytes at byte hits_off of the framebuffer,
+ * downloaded after the colours, within the same timing. */
 int render_to_host(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, float *out_rgb,
-                   size_t bytes, int ssaa_log2, const RayBatch *rays = nullptr) {
-    int rc = launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr, nullptr, ssaa_log2, rays);
+                   size_t bytes, int ssaa_log2, const RayBatch *rays = nullptr, void *out_hits = nullptr, size_t hits_off = 0,
+                   size_t hits_bytes = 0) {
+    char *d_hits = out_hits ? static_cast<char *>(s->d_fb) + hits_off : nullptr;
+    int rc = launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr, nullptr, ssaa_log2, rays, d_hits);
     if (rc) return rc;
     s->timing.last_download_ms = 0.0;
     if (bytes) {
@@ -1563,6 +1584,7 @@ int render_to_host(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0,
         HIP_TRY(hipEventCreate(&t1));
         HIP_TRY(hipEventRecord(t0, nullptr));
         HIP_TRY(hipMemcpy(out_rgb, s->d_fb, bytes, hipMemcpyDeviceToHost));
+        if (hits_bytes) HIP_TRY(hipMemcpy(out_hits, d_hits, hits_bytes, hipMemcpyDeviceToHost));
         HIP_TRY(hipEventRecord(t1, nullptr));
         HIP_TRY(hipEventSynchronize(t1));
         float ms = 0.f;
@@ -1642,6 +1664,22 @@ int query_on_device(rt_scene *s, int n, int rows, const void *d_in, void *d_out,
     std::lock_guard<std::mutex> lock(s->mu);
     return launch(s, nullptr, b.n_cols, b.rows, 0, b.n_cols, 0, static_cast<float *>(d_out), static_cast<hipStream_t>(hip_stream),
                   nullptr, 0, &b);
+}
+
+/* rt_render_gbuffer*: the checks of include/rt_capi_gbuffer.h in its order, all before the device is touched -- rt_render's in
+ * rt_render's order (the scene, frame_preamble()'s, check_launch_args()'s), then the records': out_hits, and the strip's
+ * colours and records together within the bytes of kMaxStripFloats floats */
+int gbuffer_args(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *out_rgb,
+                 const void *out_hits) {
+    if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
+    if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 > x1) return fail(RT_ERR_INVALID, "need 0 <= x0 <= x1 <= W, W,H > 0");
+    if (x1 > x0 && !out_rgb) return fail(RT_ERR_INVALID, "out_rgb is NULL");
+    int rc = check_launch_args(cam, W, H, x0, x1, max_depth, out_rgb);
+    if (rc) return rc;
+    if (x1 > x0 && !out_hits) return fail(RT_ERR_INVALID, "out_hits is NULL");
+    if ((double)(x1 - x0) * (double)H * (double)(3 * sizeof(float) + sizeof(rt_hit)) > kMaxStripFloats * sizeof(float))
+        return fail(RT_ERR_INVALID, "strip too large for its colours and records");
+    return RT_OK;
 }
 
 } // namespace
@@ -1802,6 +1840,33 @@ int rt_occluded_rays(rt_scene *s, int n, int rows, const float *segs, uint8_t *o
 
 int rt_occluded_rays_device(rt_scene *s, int n, int rows, const void *d_segs, void *d_out_blocked, void *hip_stream) {
     return query_on_device(s, n, rows, d_segs, d_out_blocked, RT_QUERY_OCCLUDED, hip_stream);
+}
+
+int rt_capi_gbuffer_version(void) { return RT_CAPI_GBUFFER_VERSION; }
+
+/* G-BUFFER (include/rt_capi_gbuffer.h): rt_render's launch of the frame through the *_gbuffer sibling; the host variant renders
+ * into the handle's framebuffer -- the colours, then the records from the next 16-byte boundary -- and downloads both */
+int rt_render_gbuffer(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, float *out_rgb,
+                      rt_hit *out_hits) {
+    int rc = gbuffer_args(s, cam, W, H, x0, x1, max_depth, out_rgb, out_hits);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(s->mu);
+    const size_t pixels = (size_t)(x1 - x0) * (size_t)H;
+    const size_t bytes = pixels * 3 * sizeof(float), hits_off = (bytes + 15) & ~(size_t)15, hits_bytes = pixels * sizeof(rt_hit);
+    HIP_TRY(hipSetDevice(s->device));
+    rc = grow_device_buffer(&s->d_fb, &s->d_fb_bytes, hits_off + hits_bytes);
+    if (rc) return rc;
+    return render_to_host(s, cam, W, H, x0, x1, max_depth, out_rgb, bytes, 0, nullptr, out_hits, hits_off, hits_bytes);
+}
+
+int rt_render_gbuffer_device(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, void *d_out_rgb,
+                             void *d_out_hits, void *hip_stream) {
+    int rc = gbuffer_args(s, cam, W, H, x0, x1, max_depth, d_out_rgb, d_out_hits);
+    if (rc) return rc;
+    if (((uintptr_t)d_out_hits & 15u) != 0) return fail(RT_ERR_INVALID, "d_out_hits must be 16-byte aligned");
+    std::lock_guard<std::mutex> lock(s->mu);
+    return launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(d_out_rgb), static_cast<hipStream_t>(hip_stream), nullptr, 0,
+                  nullptr, d_out_hits);
 }
 
 int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,

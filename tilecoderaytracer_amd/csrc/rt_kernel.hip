@@ -1773,12 +1773,51 @@ __device__ __forceinline__ size_t hbm_stack_entry(const RtParams &p, const int l
     return (size_t)(row * (unsigned int)here(p.stack_stride) + threadIdx.x);
 }
 
+/* G-BUFFER (include/rt_capi_gbuffer.h): the rt_hit record of a camera ray's level-0 winner, built from what phase 1 of
+ * render_tile() has at hand -- Scene index idx at distance t, the point P, the normal N before the CollisionObject ctor
+ * re-normalises it, the texture selector, the material (its number, its second quad's bits) and the kind -- with hits_tile()'s
+ * arithmetic: the normal re-normalised where N.N does not round to 1, the material's or the checker tile's colour, flags
+ * bit 0 an inside sphere hit (t < 0), bit 1 a light.  As three quads, the three 16-byte stores of hits_tile(). */
+struct HitQuads { float4 q0, q1, q2; };
+
+__device__ __forceinline__ HitQuads gbuffer_miss() {
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    return HitQuads{make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f), zero, zero};
+}
+
+__device__ __forceinline__ HitQuads gbuffer_hit(const RtParams &p, const float4 *lds, const int idx, const float t, const V3 P,
+                                                V3 N, const int texsel, const int mat, const uint32_t mbits, const int kind) {
+    const float nn = N.x * N.x + N.y * N.y + N.z * N.z;
+    if (nn != 1.0f) {
+        const float length = sqrtf(nn);
+        N = mk(N.x / length, N.y / length, N.z / length);
+    }
+    const V3 c = entry_colour(p, lds, lds[p.mat_off + mat * RT_MAT_QUADS], mbits, texsel);
+    const int flags = (kind == RT_KIND_SPHERE && t < 0.0f ? 1 : 0) | ((mbits & 1u) ? 2 : 0);
+    return HitQuads{make_float4(__int_as_float(idx), t, P.x, P.y), make_float4(P.z, N.x, N.y, N.z),
+                    make_float4(c.x, c.y, c.z, __int_as_float(flags))};
+}
+
+/* Pixel (x0 + sx, sz)'s record: plain stores, as hits_tile()'s (the three instructions each write every
+ * third quad of the wavefront's 3 KB, and the lines merge in the L2 only when they stay there) */
+__device__ __forceinline__ void gbuffer_store(const RtParams &p, const int sx, const int sz, const HitQuads &h) {
+    float4 *dst = reinterpret_cast<float4 *>(p.gbuffer_hits) + ((size_t)sx * (size_t)p.H + (size_t)sz) * 3;
+    dst[0] = h.q0; dst[1] = h.q1; dst[2] = h.q2;
+}
+
+/* Where the *_gbuffer kernels store the record: 0 at level 0, right after phase 1; 1 at the end of
+ * the tile, beside the colour (the 12 words stay live through the bounces) */
+#ifndef RT_GBUFFER_STORE_LATE
+#define RT_GBUFFER_STORE_LATE 0
+#endif
+
 /* One wavefront tile: camera rays, the bounce loop, the unwind, the store.  kSsaa: the tile is a rectangle of SAMPLES of a
  * virtual kW x kH image (k = 1 << p.ssaa_log2, both tile sides multiples of k: rt_capi.hip, tile_shape()); the store box-filters
  * them into the W x H output (below).  kRays: the tile is a rectangle of cells of the n_cols x rows grid of a caller's ray batch
  * (include/rt_capi_rays.h; launched with W = x1 = n_cols, H = rows, x0 = 0): cell (x, z) is ray x * rows + z, read from
- * p.rays instead of made by the camera. */
-template <bool kStats, int kMode, bool kSsaa = false, bool kRays = false>
+ * p.rays instead of made by the camera.  kGbuffer: a camera tile that also stores each pixel's rt_hit record of its level-0
+ * winner at p.gbuffer_hits (include/rt_capi_gbuffer.h); the colours are the plain tile's. */
+template <bool kStats, int kMode, bool kSsaa = false, bool kRays = false, bool kGbuffer = false>
 __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds, float4 *wlds, float4 *help_rays,
                                             const uint32_t *__restrict__ ctl_words, float *__restrict__ out,
                                             float4 *__restrict__ bounce_stack, unsigned long long *__restrict__ stats_out,
@@ -1845,6 +1884,9 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
     V3 box_lo = o, box_hi = o;
     if constexpr (kRays) wave_bounds3(o, inside, &box_lo, &box_hi);
     bool have_box = true;
+#if RT_GBUFFER_STORE_LATE
+    [[maybe_unused]] HitQuads late_record = gbuffer_miss();
+#endif
     for (int level = 0; level <= p.max_depth; ++level) {
         if (__ballot(alive) == 0ull) break;
         levels = level + 1;
@@ -1871,6 +1913,8 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
         else nearest_hit_items<kStats, kMode>(p, lds, wlds, alive, o, d, have_box, box_lo, box_hi, &t, &idx, st);   /* whole wavefront, converged */
         st_cycles(st, ST_CYCLES_NEAREST, t_scan);
         const unsigned long long t_winner = st_clock<kStats>();
+        [[maybe_unused]] HitQuads record;                    /* G-BUFFER: level 0 only (alive == inside there) */
+        if constexpr (kGbuffer) record = gbuffer_miss();
         if (alive) {
             if (idx < 0) {                                   /* :507-509 */
                 C = null_color;
@@ -1902,6 +1946,9 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                     N = (dot3(xyz(q0), d) < 0) ? xyz(q0) : xyz(q4);
                     P = add3(ip, scale3(N, (float)1E-3));
                 }
+                if constexpr (kGbuffer) {
+                    if (level == 0) record = gbuffer_hit(p, lds, idx, t, P, N, texsel, mat, mbits, kind);
+                }
                 if (mbits & 1u) {                            /* hit a light: :520-527 */
                     const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
                     C = scale3(entry_colour(p, lds, m0, mbits, texsel), m1.z);
@@ -1909,6 +1956,19 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                 } else {
                     shade = true;
                 }
+            }
+        }
+        if constexpr (kGbuffer) {
+            if (level == 0) {
+#if RT_GBUFFER_STORE_LATE
+                late_record = record;
+#else
+                if (inside) {
+                    const int tzl_g = here(p.tile_z_log2);
+                    gbuffer_store(p, here(tile_col) * (64 >> tzl_g) + (lane >> tzl_g),
+                                  (here(tile_row) << tzl_g) + (lane & ((1 << tzl_g) - 1)), record);
+                }
+#endif
             }
         }
 
@@ -2147,6 +2207,9 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
 #else
         dst[0] = C.x; dst[1] = C.y; dst[2] = C.z;
 #endif
+#if RT_GBUFFER_STORE_LATE
+        if constexpr (kGbuffer) gbuffer_store(p, sx, sz, late_record);
+#endif
     }
     if constexpr (kStats) {
         st_cycles(st, ST_CYCLES_TILE, t_start);
@@ -2326,7 +2389,7 @@ __device__ RT_SCAN_INLINE unsigned int queues_with_tiles(const unsigned int *til
 }
 
 template <bool kStats, bool kGlobalTables = false, bool kClusters = false, bool kRoomy = false, bool kFast = false, bool kSsaa = false,
-          bool kRays = false, int kQuery = RT_QUERY_NONE>
+          bool kRays = false, int kQuery = RT_QUERY_NONE, bool kGbuffer = false>
 __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__restrict__ image,
                                             float *__restrict__ out, unsigned int *__restrict__ tile_counter,
                                             float4 *__restrict__ bounce_stack,
@@ -2538,8 +2601,8 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
         constexpr int kMode = kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0);
         if constexpr (kQuery == RT_QUERY_HITS) hits_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
         else if constexpr (kQuery == RT_QUERY_OCCLUDED) occluded_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
-        else render_tile<kStats, kMode, kSsaa, kRays>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
-                                                      my_xcc, steal, next_pop, ask_head);
+        else render_tile<kStats, kMode, kSsaa, kRays, kGbuffer>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
+                                                                my_xcc, steal, next_pop, ask_head);
 #ifdef RT_TIMELINE
         if (p.timeline != 0ull && lane == 0) {                   /* ... when it was done, and by whom */
             unsigned long long *rec = reinterpret_cast<unsigned long long *>(p.timeline) + (size_t)tile_number * RT_TIMELINE_WORDS;
@@ -2604,8 +2667,8 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
 #define RT_BLOCK_BOUND_CLUSTERS 512
 #endif
 
-/* rt_kernel_ssaa.hip, rt_kernel_rays.hip and rt_kernel_query.hip include this file for the body alone and define the
- * supersampling, the ray-batch and the ray-query kernels: in translation units of their own, the seven kernels below compile to the code they have without them (next to five more instantiations of the
+/* rt_kernel_ssaa.hip, rt_kernel_rays.hip, rt_kernel_query.hip and rt_kernel_gbuffer.hip include this file for the body alone
+ * and define the supersampling, the ray-batch, the ray-query and the G-buffer kernels: in translation units of their own, the seven kernels below compile to the code they have without them (next to five more instantiations of the
  * body in one module, the item-table kernel's allocation moved: one more spilled scalar) */
 #ifndef RT_KERNEL_BODY_ONLY
 

@@ -214,9 +214,15 @@ typedef struct RtParams {
     int32_t ssaa_log2;
     /* RAY BATCH (include/rt_capi_rays.h; the *_rays kernels only): n_rays rays of {E.xyz, T.xyz} fp32 at device address `rays`,
      * ray i at cell (i / H, i % H) of a W x H launch (W = x1 = n_cols, x0 = 0); no camera, no PRIMARY table.  (Where ssaa_pad[3]
-     * was: `rays` at offset 1344 is 8-aligned, so no other field moves and the struct keeps its 1352 bytes.) */
+     * was: `rays` at offset 1344 is 8-aligned, so no other field moves and the struct keeps its 1352 bytes.)
+     * G-BUFFER (include/rt_capi_gbuffer.h; the *_gbuffer kernels only): gbuffer_hits is the device address of the strip's
+     * rt_hit records, 48 bytes per pixel in the colours' order, 16-byte aligned.  A camera launch never reads `rays`, so the
+     * two share one place and nothing moves. */
     int32_t n_rays;
-    uint64_t rays;
+    union {
+        uint64_t rays;
+        uint64_t gbuffer_hits;
+    };
 } RtParams;
 #define RT_TIMELINE_WORDS 4
 

@@ -73,6 +73,23 @@ class Renderer:
         capi.check(self._lib.rt_render_ssaa_device(self._scene, self._cam, W, H, x0, x1, max_depth, samples,
                                                    C.c_void_p(device_ptr), C.c_void_p(stream)))
 
+    def render_gbuffer(self, W, H, max_depth, x0=0, x1=None):
+        """Columns [x0, x1) of a W x H image with each pixel's hit record (include/rt_capi_gbuffer.h) -> (rgb float32
+        (x1-x0, H, 3), hits HIT_DTYPE (x1-x0, H)): rgb is render()'s, hits[x - x0, z] the rt_hit of the pixel's camera ray
+        (object -1 = no hit)."""
+        x1 = W if x1 is None else x1
+        rgb = np.empty((max(x1 - x0, 0), H, 3), dtype=np.float32)
+        hits = np.empty((max(x1 - x0, 0), H), dtype=HIT_DTYPE)
+        capi.check(self._lib.rt_render_gbuffer(self._scene, self._cam, W, H, x0, x1, max_depth, rgb.ctypes.data,
+                                               hits.ctypes.data))
+        return rgb, hits
+
+    def render_gbuffer_device(self, W, H, max_depth, x0, x1, rgb_ptr, hits_ptr, stream=0):
+        """Enqueue a G-buffer frame (colours at rgb_ptr, 48-byte records at hits_ptr, 16-byte aligned) into device memory on a
+        HIP stream (no sync)."""
+        capi.check(self._lib.rt_render_gbuffer_device(self._scene, self._cam, W, H, x0, x1, max_depth, C.c_void_p(rgb_ptr),
+                                                      C.c_void_p(hits_ptr), C.c_void_p(stream)))
+
     def trace_rays(self, rays, max_depth, rows=None):
         """Trace a batch of primary rays (include/rt_capi_rays.h).  rays: C-contiguous float32, (n, 6) -- rows defaults to n --
         or (X, Z, 6), ray [x, z] = cell (x, z) of the grid, rows = Z; each ray {E.xyz, T.xyz} starts at E towards T.
