@@ -33,6 +33,16 @@ class RtTextureDesc(C.Structure):
     _fields_ = [("light", F3), ("dark", F3), ("width", C.c_float), ("height", C.c_float)]
 
 
+RT_TEX_WRAP_CHECKER, RT_TEX_WRAP_REPEAT, RT_TEX_WRAP_CLAMP = 0, 1, 2
+RT_MAX_SCENE_TEXELS = 1 << 20
+
+
+class RtImageTextureDesc(C.Structure):
+    """include/rt_capi_texture.h: an image texture for planes, texel (i, j) at texels[(j * texels_w + i) * 3 + c]."""
+    _fields_ = [("texels_w", C.c_int32), ("texels_h", C.c_int32), ("width", C.c_float), ("height", C.c_float),
+                ("wrap", C.c_int32), ("texels", C.POINTER(C.c_float))]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [
         ("n_objects", C.c_int32), ("objects", C.POINTER(RtObjectDesc)),
@@ -167,6 +177,11 @@ def load_library():
         lib.rt_render_gbuffer.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, vp, vp]
         lib.rt_render_gbuffer_device.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, vp, vp, vp]
         lib.rt_render_gbuffer.restype = lib.rt_render_gbuffer_device.restype = i
+    # include/rt_capi_texture.h (likewise absent from older builds)
+    if hasattr(lib, "rt_scene_create_textured"):
+        lib.rt_capi_texture_version.restype = i
+        lib.rt_scene_create_textured.argtypes = [C.POINTER(RtSceneDesc), i, C.POINTER(RtImageTextureDesc), i, C.POINTER(vp)]
+        lib.rt_scene_create_textured.restype = i
     for name in ("rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_render",
                  "rt_render_device", "rt_render_multi", "rt_render_stats", "rt_learn_tile_order", "rt_get_timing", "rt_reset_timing",
                  "rt_get_launch_info", "rt_set_option", "rt_chunk_bounds", "rt_multi_create", "rt_multi_render",

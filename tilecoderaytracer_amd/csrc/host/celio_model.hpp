@@ -1,7 +1,7 @@
 /*
  * celio_model.hpp -- host-side object model with the API surface of
  * ccelio/TileCodeRayTracer (namespace CelioRayTracer): vector3d / Color, Ray,
- * ObjTexture / Texture_CheckerBoard, ObjMaterial, SceneObject and its three
+ * ObjTexture / Texture_CheckerBoard (and Texture_Image, a bitmap: include/rt_capi_texture.h), ObjMaterial, SceneObject and its three
  * primitives, Scene, Camera.  A user of the reference builds a scene with the
  * same calls; `Scene::flatten()` / `Camera::describe()` then lower the object
  * graph to the plain-old-data tables of include/rt_capi.h, which is all the
@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../../include/rt_capi.h"
+#include "../../../include/rt_capi_texture.h"
 
 namespace CelioRayTracer {
 
@@ -101,7 +102,9 @@ private:
 };
 
 /* src/ObjTexture.h:14-55.  getTexturePixel() is evaluated on the device; the
- * host class only carries the parameters (describe()). */
+ * host class only carries the parameters (describe()).  A subclass that is a
+ * bitmap describes itself as an image instead (describe_image() returns true,
+ * include/rt_capi_texture.h); Scene::flatten() asks that first. */
 class ObjTexture {
 public:
     ObjTexture() : width(1), height(1) {}
@@ -110,6 +113,8 @@ public:
     void setWidth(sdecimal32 w) { width = w; }
     void setHeight(sdecimal32 h) { height = h; }
     virtual void describe(rt_texture_desc &out) const = 0;
+    /* an image: fill `out` (its texels stay owned by the texture) and return true; a checkerboard returns false */
+    virtual bool describe_image(rt_image_texture_desc &out) const { (void)out; return false; }
 protected:
     float width, height;
 };
@@ -127,6 +132,37 @@ public:
     }
 private:
     Color light_color, dark_color;
+};
+
+/* A bitmap texture: texels_w x texels_h fp32 rgb texels, texel (i, j) at texels[(j * texels_w + i) * 3 + c], one copy of the
+ * image spanning width x height of the plane, folded by `wrap` (RT_TEX_WRAP_*).  getTexturePixel(x, y) is the texel the
+ * header's rule names (nearest texel, no filtering); the device samples it.  As a checkerboard it has no description. */
+class Texture_Image : public ObjTexture {
+public:
+    Texture_Image(int texels_w, int texels_h, const float *rgb, sdecimal32 w, sdecimal32 h, int wrap = RT_TEX_WRAP_REPEAT)
+        : ObjTexture(w, h), texels_w(texels_w), texels_h(texels_h),
+          texels(rgb, rgb + (size_t)(texels_w > 0 ? texels_w : 0) * (size_t)(texels_h > 0 ? texels_h : 0) * 3), wrap(wrap) {}
+    void setWrap(int w) { wrap = w; }
+    int getWrap() const { return wrap; }
+    Color getTexel(int i, int j) const {
+        const float *t = &texels[((size_t)j * (size_t)texels_w + (size_t)i) * 3];
+        return Color(t[0], t[1], t[2]);
+    }
+    void describe(rt_texture_desc &out) const override {   /* (not a checkerboard: flatten() takes describe_image()) */
+        std::memset(&out, 0, sizeof out);
+        out.width = width; out.height = height;
+    }
+    bool describe_image(rt_image_texture_desc &out) const override {
+        out.texels_w = texels_w; out.texels_h = texels_h;
+        out.width = width; out.height = height;
+        out.wrap = wrap;
+        out.texels = texels.data();
+        return true;
+    }
+private:
+    int texels_w, texels_h;
+    std::vector<float> texels;
+    int wrap;
 };
 
 /* src/ObjMaterial.h:10-81 */
@@ -343,11 +379,18 @@ private:
     vector3d eye_origin;
 };
 
-/* The flattened scene: owns the arrays an rt_scene_desc points into. */
+/* The flattened scene: owns the arrays an rt_scene_desc points into.  images: the bitmap textures
+ * (include/rt_capi_texture.h), texture indices desc.n_textures + k; their texels stay owned by the Texture_Image objects.
+ * create(): rt_scene_create_textured when there are images, rt_scene_create otherwise. */
 struct FlatScene {
     std::vector<rt_object_desc> objects;
     std::vector<rt_texture_desc> textures;
+    std::vector<rt_image_texture_desc> images;
     rt_scene_desc desc;
+    int create(int device, rt_scene **out) const {
+        if (images.empty()) return rt_scene_create(&desc, device, out);
+        return rt_scene_create_textured(&desc, (int)images.size(), images.data(), device, out);
+    }
 };
 
 /* src/Scene.h:15-43, src/Scene.cpp */
@@ -382,11 +425,14 @@ public:
     int getSceneObjectStartIndex() const { return scene_object_start_index; }
     int getSceneObjectFinalIndex() const { return scene_object_final_index; }
 
-    /* lower the object graph to rt_capi.h tables (Scene index order) */
+    /* lower the object graph to rt_capi.h tables (Scene index order): each distinct texture once, in order of first use --
+     * the checkerboards as textures, the bitmaps as images after them (include/rt_capi_texture.h) */
     void flatten(FlatScene &out) const {
         out.objects.resize((size_t)object_count);
         out.textures.clear();
+        out.images.clear();
         std::vector<const ObjTexture *> seen;
+        std::vector<int> slot;                          /* per seen texture: its checkerboard index, or -2 - its image index */
         for (int i = 0; i < object_count; ++i) {
             rt_object_desc &d = out.objects[(size_t)i];
             objects[(size_t)i]->describe(d);
@@ -396,13 +442,22 @@ public:
                 while (k < seen.size() && seen[k] != t) ++k;
                 if (k == seen.size()) {
                     seen.push_back(t);
-                    rt_texture_desc td;
-                    t->describe(td);
-                    out.textures.push_back(td);
+                    rt_image_texture_desc im;
+                    if (t->describe_image(im)) {
+                        slot.push_back(-2 - (int)out.images.size());
+                        out.images.push_back(im);
+                    } else {
+                        slot.push_back((int)out.textures.size());
+                        rt_texture_desc td;
+                        t->describe(td);
+                        out.textures.push_back(td);
+                    }
                 }
-                d.texture = (int32_t)k;
+                d.texture = (int32_t)slot[k];
             }
         }
+        for (int i = 0; i < object_count; ++i)          /* images after the checkerboards */
+            if (out.objects[(size_t)i].texture < -1) out.objects[(size_t)i].texture = (int32_t)out.textures.size() - 2 - out.objects[(size_t)i].texture;
         out.desc.n_objects = object_count;
         out.desc.objects = out.objects.empty() ? nullptr : out.objects.data();
         out.desc.n_textures = (int32_t)out.textures.size();

@@ -96,6 +96,10 @@ int main(int argc, char **argv) {
     rt_camera_desc cam;
     my_scene.flatten(flat);
     my_camera.describe(cam);
+    if (!flat.images.empty() && gpus > 1) {         /* the multi-GPU path takes no images (include/rt_capi_texture.h) */
+        std::fprintf(stderr, "bitmap textures render on one GPU\n");
+        return 1;
+    }
     pixels.assign((size_t)W * (size_t)H * 3, 0.0f);
     std::vector<rt_hit> hits(hits_path.empty() ? 0 : (size_t)W * (size_t)H);
 
@@ -105,7 +109,7 @@ int main(int argc, char **argv) {
     double kernel_ms = 0.0;
     if (gpus == 1) {
         rt_scene *scene = nullptr;
-        rc = rt_scene_create(&flat.desc, 0, &scene);
+        rc = flat.create(0, &scene);                /* rt_scene_create_textured when the scene has bitmap textures */
         if (rc == RT_OK) rc = ssaa > 1 ? rt_render_ssaa(scene, &cam, W, H, 0, W, depth, ssaa, pixels.data())
                             : !hits.empty() ? rt_render_gbuffer(scene, &cam, W, H, 0, W, depth, pixels.data(), hits.data())
                                             : rt_render(scene, &cam, W, H, 0, W, depth, pixels.data());

@@ -131,6 +131,13 @@ int rth_set_checkerboard(rth_scene *s, int idx, const float light[3], const floa
     s->dirty = true;
     return 0;
 }
+int rth_set_image_texture(rth_scene *s, int idx, int texels_w, int texels_h, const float *texels, float w, float h, int wrap) {
+    SceneObject *o = object_at(s, idx);
+    if (!o || !texels || texels_w < 1 || texels_h < 1) return 1;
+    o->getMaterial()->setTexture(new Texture_Image(texels_w, texels_h, texels, w, h, wrap));
+    s->dirty = true;
+    return 0;
+}
 int rth_set_light(rth_scene *s, int idx) {
     SceneObject *o = object_at(s, idx);
     if (!o) return 1;
@@ -167,6 +174,13 @@ const rt_camera_desc *rth_camera_desc(rth_scene *s) {
     if (!s) return nullptr;
     refresh(s);
     return &s->cam_desc;
+}
+
+int rth_scene_images(rth_scene *s, const rt_image_texture_desc **images) {
+    if (!s || !images) return 0;
+    refresh(s);
+    *images = s->flat.images.empty() ? nullptr : s->flat.images.data();
+    return (int)s->flat.images.size();
 }
 
 int rth_write_screen_txt(const char *path, int W, int H, const float *rgb, double run_time_s,

@@ -10,6 +10,7 @@
 #define RT_HOST_CAPI_H_
 
 #include "../../../include/rt_capi.h"
+#include "../../../include/rt_capi_texture.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -37,6 +38,8 @@ int rth_set_diffuse(rth_scene *s, int idx, float f);
 int rth_set_specular(rth_scene *s, int idx, float f);
 int rth_set_reflective(rth_scene *s, int idx, float f);
 int rth_set_checkerboard(rth_scene *s, int idx, const float light[3], const float dark[3], float w, float h);
+/* a Texture_Image (include/rt_capi_texture.h): texels_w x texels_h fp32 rgb texels, copied; 1 on a bad argument */
+int rth_set_image_texture(rth_scene *s, int idx, int texels_w, int texels_h, const float *texels, float w, float h, int wrap);
 int rth_set_light(rth_scene *s, int idx);
 int rth_set_intensity(rth_scene *s, int idx, float f);
 int rth_set_object_indices(rth_scene *s, int my_rank, int group_size);   /* Scene::SetObjectIndices */
@@ -46,6 +49,8 @@ int rth_camera_eye_ray(const rth_scene *s, float dx, float dy, float origin[3], 
 /* flattened views; valid until the scene is modified or freed */
 const rt_scene_desc  *rth_scene_desc(rth_scene *s);
 const rt_camera_desc *rth_camera_desc(rth_scene *s);
+/* the flattened scene's images (texture indices n_textures + k): their count, *images set to the array (NULL if none) */
+int rth_scene_images(rth_scene *s, const rt_image_texture_desc **images);
 
 /* byte-exact raytracer_screen.txt (src/RayTracer.cpp:2022-2061, 1574-1626) */
 int rth_write_screen_txt(const char *path, int W, int H, const float *rgb,

@@ -21,6 +21,7 @@
 #include "../../include/rt_capi_query.h"
 #include "../../include/rt_capi_rays.h"
 #include "../../include/rt_capi_ssaa.h"
+#include "../../include/rt_capi_texture.h"
 #include "../../include/rt_capi_tuning.h"
 #include "rt_tables.h"
 
@@ -62,6 +63,18 @@ RT_DECLARE_KERNEL(rt_render_kernel_items_gbuffer);
 RT_DECLARE_KERNEL(rt_render_kernel_large_gbuffer);
 RT_DECLARE_KERNEL(rt_render_kernel_clusters_gbuffer);
 RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_gbuffer);
+/* ... with image textures (rt_kernel_texture.hip): the *_image sibling of each of the above but the *_occluded ones */
+#define RT_DECLARE_IMAGE_KERNELS(suffix)                      \
+    RT_DECLARE_KERNEL(rt_render_kernel##suffix##_image);       \
+    RT_DECLARE_KERNEL(rt_render_kernel_items##suffix##_image); \
+    RT_DECLARE_KERNEL(rt_render_kernel_large##suffix##_image); \
+    RT_DECLARE_KERNEL(rt_render_kernel_clusters##suffix##_image); \
+    RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide##suffix##_image)
+RT_DECLARE_IMAGE_KERNELS();
+RT_DECLARE_IMAGE_KERNELS(_ssaa);
+RT_DECLARE_IMAGE_KERNELS(_rays);
+RT_DECLARE_IMAGE_KERNELS(_hits);
+RT_DECLARE_IMAGE_KERNELS(_gbuffer);
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_stats);      /* the counting builds */
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_fast_stats);
 
@@ -105,6 +118,14 @@ struct rt_scene {
     /* the caller's description, copied */
     std::vector<rt_object_desc> objects;
     std::vector<rt_texture_desc> textures;
+    /* IMAGE TEXTURES (include/rt_capi_texture.h): the caller's images, texels copied until they are on the device;
+     * images_used: a plane's texture is one of them -- the tables then hold every texture as an image (pack_images()) and
+     * the *_image kernels run */
+    struct Image { int w, h; float width, height; int wrap; std::vector<float> texels; };
+    std::vector<Image> images;
+    bool images_used = false;
+    void *d_texels = nullptr;                 /* every texture's block (rt_tables.h), texture by texture */
+    std::vector<size_t> texel_blocks;         /* each texture's block: its first float in d_texels */
     int shadow_begin = 0, shadow_end = 0;
     float null_color[3] = {0.75f, 0.75f, 0.75f};
     /* packed tables (host copies) */
@@ -459,13 +480,56 @@ struct Packing {
     std::vector<Quad> image;
 };
 
+/* IMAGE TEXTURES: f(texels_w, texels_h, width, height, wrap, texels) for each texture of a scene with images, checkerboards
+ * first, each as the 2 x 2 CHECKER image that reproduces it (include/rt_capi_texture.h); an image's texels are NULL once they
+ * are on the device (upload_texels()) */
+template <class Fn>
+void for_each_image(const rt_scene *s, Fn fn) {
+    for (const rt_texture_desc &x : s->textures) {
+        float t[12];
+        const float *c[4] = {x.light, x.dark, x.dark, x.light};
+        for (int k = 0; k < 4; ++k) std::memcpy(t + 3 * k, c[k], 3 * sizeof(float));
+        fn(2, 2, x.width, x.height, (int)RT_TEX_WRAP_CHECKER, (const float *)t);
+    }
+    for (const rt_scene::Image &im : s->images)
+        fn(im.w, im.h, im.width, im.height, im.wrap, im.texels.empty() ? (const float *)nullptr : im.texels.data());
+}
+
+/* The texel buffer (rt_tables.h): per texture its block -- texels, then b_k = fl(fl(w k) / n) for k in [0, n) of the columns and
+ * of the rows, in IEEE fp32 (this file is built without contraction or fast math) -- and where each block starts */
+std::vector<float> texel_buffer(const rt_scene *s, std::vector<size_t> *blocks) {
+    std::vector<float> buf;
+    blocks->clear();
+    for_each_image(s, [&](int w, int h, float width, float height, int, const float *texels) {
+        blocks->push_back(buf.size());
+        buf.insert(buf.end(), texels, texels + (size_t)w * (size_t)h * 3);
+        for (int k = 0; k < w; ++k) buf.push_back((width * (float)k) / (float)w);
+        for (int k = 0; k < h; ++k) buf.push_back((height * (float)k) / (float)h);
+    });
+    return buf;
+}
+
+/* the texture table of a scene with images: two quads per texture, its block's device address in the second */
+void pack_images(const rt_scene *s, Packing &P) {
+    size_t t = 0;
+    for_each_image(s, [&](int w, int h, float width, float height, int wrap, const float *) {
+        const uint64_t addr = s->d_texels ? (uint64_t)(uintptr_t)(static_cast<const float *>(s->d_texels) + s->texel_blocks[t]) : 0u;
+        P.texs.push_back({{width, height, bits_to_float((uint32_t)w), bits_to_float((uint32_t)h)}});
+        P.texs.push_back({{bits_to_float((uint32_t)wrap), 0.0f, bits_to_float((uint32_t)(addr & 0xFFFFFFFFu)),
+                           bits_to_float((uint32_t)(addr >> 32))}});
+        ++t;
+    });
+}
+
 /* materials (de-duplicated bit-wise), lights, textures */
 int pack_materials_and_lights(const rt_scene *s, Packing &P) {
     const int n = (int)s->objects.size();
     std::map<std::vector<uint32_t>, int> mat_index;
     for (int i = 0; i < n; ++i) {
         const rt_object_desc &o = s->objects[(size_t)i];
-        const uint32_t mbits = (o.is_light ? 1u : 0u) | ((uint32_t)(o.texture + 1) << 1);
+        /* (in a scene with images only planes keep their texture: a sphere's is never sampled, and a texel selector of 0 is a texel) */
+        const int texture = (s->images_used && o.kind == RT_KIND_SPHERE) ? -1 : o.texture;
+        const uint32_t mbits = (o.is_light ? 1u : 0u) | ((uint32_t)(texture + 1) << 1);
         Quad m0 = {{o.color[0], o.color[1], o.color[2], o.diffuse}};
         Quad m1 = {{o.specular, o.reflective, o.intensity, bits_to_float(mbits)}};
         std::vector<uint32_t> key(8);
@@ -486,6 +550,10 @@ int pack_materials_and_lights(const rt_scene *s, Packing &P) {
             P.lights.push_back({{o.origin[0], o.origin[1], o.origin[2], o.intensity}});
             P.lights.push_back({{o.color[0], o.color[1], o.color[2], bits_to_float((uint32_t)i)}});
         }
+    }
+    if (s->images_used) {
+        pack_images(s, P);
+        return RT_OK;
     }
     for (const rt_texture_desc &x : s->textures) {
         P.texs.push_back({{x.light[0], x.light[1], x.light[2], x.width}});
@@ -848,7 +916,7 @@ int pack_scene(rt_scene *s) {
 }
 
 /* validate + copy the caller's description into the handle */
-int adopt_desc(const rt_scene_desc *desc, rt_scene *s) {
+int adopt_desc(const rt_scene_desc *desc, rt_scene *s, int n_images = 0) {
     const int n = desc->n_objects;
     if (n < 0) return fail(RT_ERR_INVALID, "n_objects < 0");
     if (n > 0 && !desc->objects) return fail(RT_ERR_INVALID, "objects is NULL");
@@ -862,11 +930,14 @@ int adopt_desc(const rt_scene_desc *desc, rt_scene *s) {
         const rt_object_desc &o = desc->objects[i];
         if (o.kind != RT_KIND_SPHERE && o.kind != RT_KIND_INFINITE_PLANE && o.kind != RT_KIND_FINITE_PLANE)
             return fail(RT_ERR_INVALID, "object " + std::to_string(i) + ": unknown kind");
-        if (o.texture < -1 || o.texture >= desc->n_textures)
+        if (o.texture < -1 || (int64_t)o.texture >= (int64_t)desc->n_textures + n_images)
             return fail(RT_ERR_INVALID, "object " + std::to_string(i) + ": texture index out of range");
     }
     s->objects.assign(desc->objects, desc->objects + n);
     s->textures.assign(desc->textures, desc->textures + desc->n_textures);
+    s->images_used = false;
+    for (int i = 0; i < n; ++i)
+        if (desc->objects[i].kind != RT_KIND_SPHERE && desc->objects[i].texture >= desc->n_textures) s->images_used = true;
     s->shadow_begin = desc->shadow_begin;
     s->shadow_end = desc->shadow_end;
     for (int c = 0; c < 3; ++c) s->null_color[c] = desc->null_color[c];
@@ -891,6 +962,40 @@ int upload_scene(rt_scene *s) {
     s->timing.last_upload_ms = ms;
     (void)hipEventDestroy(t0);
     (void)hipEventDestroy(t1);
+    return RT_OK;
+}
+
+/* IMAGE TEXTURES: the texel buffer's one upload (rt_tables.h) */
+int upload_texels(rt_scene *s) {
+    const std::vector<float> buf = texel_buffer(s, &s->texel_blocks);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMalloc(&s->d_texels, buf.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(s->d_texels, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
+    for (rt_scene::Image &im : s->images) std::vector<float>().swap(im.texels);     /* (the device copy is the only one kept) */
+    return RT_OK;
+}
+
+/* rt_scene_create*, after the description is adopted and packed: the device, the texel buffer of a scene with images (and the
+ * tables packed again with its address), the tables' upload, the error word */
+int finish_create(rt_scene *s, int device, rt_scene **out) {
+    s->device = device;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        delete s;
+        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
+    }
+    if (device < 0 || device >= ndev) { delete s; return fail(RT_ERR_INVALID, "device index out of range"); }
+    int rc = s->images_used ? upload_texels(s) : RT_OK;
+    if (rc == RT_OK && s->images_used) rc = pack_scene(s);
+    if (rc == RT_OK) rc = upload_scene(s);
+    if (rc) { rt_scene_destroy(s); return rc; }
+    {
+        /* one word of pinned host memory for what a kernel has to tell the host (a HELP wait that timed out) */
+        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&s->h_error), sizeof(unsigned int), hipHostMallocDefault);
+        if (e != hipSuccess) { rt_scene_destroy(s); return fail(RT_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
+        *s->h_error = 0u;
+    }
+    *out = s;
     return RT_OK;
 }
 
@@ -1343,8 +1448,12 @@ void learned_start_row(const rt_scene *s, int W, int H, int x0, int x1, int max_
 
 struct Kernel { const void *fn; const char *name; };
 #define RT_KERNEL(k) Kernel{(const void *)k, #k}
-/* a kernel and its supersampling, ray-batch, ray-query and G-buffer siblings */
+/* a kernel and its supersampling, ray-batch, ray-query and G-buffer siblings; with image textures the *_image siblings (the
+ * occlusion query reads no colour and keeps its kernel) */
 struct Siblings { Kernel plain, ssaa, rays, hits, occluded, gbuffer; };
+#define RT_SIBLINGS_IMAGE(k)                                                                                              \
+    Siblings{RT_KERNEL(k##_image), RT_KERNEL(k##_ssaa_image), RT_KERNEL(k##_rays_image), RT_KERNEL(k##_hits_image), \
+             RT_KERNEL(k##_occluded), RT_KERNEL(k##_gbuffer_image)}
 #define RT_SIBLINGS(k)                                                                                              \
     Siblings{RT_KERNEL(k), RT_KERNEL(k##_ssaa), RT_KERNEL(k##_rays), RT_KERNEL(k##_hits), RT_KERNEL(k##_occluded), \
              RT_KERNEL(k##_gbuffer)}
@@ -1363,13 +1472,16 @@ Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int b
         if (gbuffer) return k.gbuffer;
         return ssaa ? k.ssaa : (rays ? k.rays : k.plain);
     };
-    if (global_tables) return pick(RT_SIBLINGS(rt_render_kernel_large));
+    const bool img = s->images_used;
+    if (global_tables) return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel_large) : RT_SIBLINGS(rt_render_kernel_large));
     if (s->n_clusters > 0 && s->pairs_opt) {
         /* the 96-register kernel when LDS leaves room for fewer than six wavefronts per SIMD anyway (24 per CU) */
         const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
-        return wide ? pick(RT_SIBLINGS(rt_render_kernel_clusters_wide)) : pick(RT_SIBLINGS(rt_render_kernel_clusters));
+        if (wide) return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel_clusters_wide) : RT_SIBLINGS(rt_render_kernel_clusters_wide));
+        return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel_clusters) : RT_SIBLINGS(rt_render_kernel_clusters));
     }
-    return fast_tables ? pick(RT_SIBLINGS(rt_render_kernel)) : pick(RT_SIBLINGS(rt_render_kernel_items));
+    if (fast_tables) return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel) : RT_SIBLINGS(rt_render_kernel));
+    return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel_items) : RT_SIBLINGS(rt_render_kernel_items));
 }
 
 /* Everything a launch decides before it touches the device. */
@@ -1712,31 +1824,55 @@ int rt_scene_create(const rt_scene_desc *desc, int device, rt_scene **out) {
     int rc = adopt_desc(desc, s);
     if (rc == RT_OK) rc = pack_scene(s);
     if (rc) { delete s; return rc; }
-    s->device = device;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        delete s;
-        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
+    return finish_create(s, device, out);
+}
+
+int rt_capi_texture_version(void) { return RT_CAPI_TEXTURE_VERSION; }
+
+/* IMAGE TEXTURES (include/rt_capi_texture.h): the images' checks in the header's order, then rt_scene_create's path with them */
+int rt_scene_create_textured(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images, int device,
+                             rt_scene **out) {
+    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
+    *out = nullptr;
+    if (n_images < 0) return fail(RT_ERR_INVALID, "n_images < 0");
+    if (n_images > 0 && !images) return fail(RT_ERR_INVALID, "images is NULL");
+    uint64_t total = 0;
+    for (int k = 0; k < n_images; ++k) {
+        const rt_image_texture_desc &im = images[k];
+        const std::string which = "image " + std::to_string(k) + ": ";
+        if (!im.texels) return fail(RT_ERR_INVALID, which + "texels is NULL");
+        if (im.texels_w < 1 || im.texels_h < 1) return fail(RT_ERR_INVALID, which + "texels_w and texels_h must be >= 1");
+        if (!(std::isfinite(im.width) && im.width > 0.0f && std::isfinite(im.height) && im.height > 0.0f))
+            return fail(RT_ERR_INVALID, which + "width and height must be finite and > 0");
+        if (im.wrap != RT_TEX_WRAP_CHECKER && im.wrap != RT_TEX_WRAP_REPEAT && im.wrap != RT_TEX_WRAP_CLAMP)
+            return fail(RT_ERR_INVALID, which + "unknown wrap");
+        total += (uint64_t)im.texels_w * (uint64_t)im.texels_h;
     }
-    if (device < 0 || device >= ndev) { delete s; return fail(RT_ERR_INVALID, "device index out of range"); }
-    rc = upload_scene(s);
-    if (rc) { rt_scene_destroy(s); return rc; }
-    {
-        /* one word of pinned host memory for what a kernel has to tell the host (a HELP wait that timed out) */
-        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&s->h_error), sizeof(unsigned int), hipHostMallocDefault);
-        if (e != hipSuccess) { rt_scene_destroy(s); return fail(RT_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
-        *s->h_error = 0u;
+    if (total > (uint64_t)RT_MAX_SCENE_TEXELS)
+        return fail(RT_ERR_CAPACITY, "more than " + std::to_string(RT_MAX_SCENE_TEXELS) + " texels in the scene's images");
+    if (n_images == 0) return rt_scene_create(desc, device, out);
+    rt_scene *s = new (std::nothrow) rt_scene();
+    if (!s) return fail(RT_ERR_INVALID, "out of memory");
+    int rc = adopt_desc(desc, s, n_images);
+    if (rc == RT_OK) {
+        for (int k = 0; k < n_images; ++k) {
+            const rt_image_texture_desc &im = images[k];
+            s->images.push_back({im.texels_w, im.texels_h, im.width, im.height, im.wrap,
+                                 std::vector<float>(im.texels, im.texels + (size_t)im.texels_w * (size_t)im.texels_h * 3)});
+        }
+        rc = pack_scene(s);          /* (every table check before the device is touched; packed again with the texels' address) */
     }
-    *out = s;
-    return RT_OK;
+    if (rc) { delete s; return rc; }
+    return finish_create(s, device, out);
 }
 
 int rt_scene_destroy(rt_scene *s) {
     if (!s) return RT_OK;
-    if (s->d_image || s->d_fb || s->d_rays || s->d_counters || s->ev_ready) (void)hipSetDevice(s->device);
+    if (s->d_image || s->d_texels || s->d_fb || s->d_rays || s->d_counters || s->ev_ready) (void)hipSetDevice(s->device);
     if (s->ev_ready)
         for (int i = 0; i < kEventRing; ++i) { (void)hipEventDestroy(s->ev[i].start); (void)hipEventDestroy(s->ev[i].stop); }
     if (s->d_image) (void)hipFree(s->d_image);
+    if (s->d_texels) (void)hipFree(s->d_texels);
     if (s->d_fb) (void)hipFree(s->d_fb);
     if (s->d_rays) (void)hipFree(s->d_rays);
     if (s->d_counters) (void)hipFree(s->d_counters);
@@ -1872,6 +2008,7 @@ int rt_render_gbuffer_device(rt_scene *s, const rt_camera_desc *cam, int W, int 
 int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
                     float *out_rgb, uint64_t *stats, int n_stats, uint64_t *wave_cycles, int n_wave_cycles) {
     if (!s || !stats || n_stats < 0) return fail(RT_ERR_INVALID, "scene/stats is NULL");
+    if (s->images_used) return fail(RT_ERR_INVALID, "the counting build does not sample image textures (include/rt_capi_texture.h)");
     std::lock_guard<std::mutex> lock(s->mu);
     size_t bytes = 0;
     int rc = frame_preamble(s, W, H, x0, x1, out_rgb, false, &bytes);
@@ -1905,6 +2042,8 @@ int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0
  * shape (W, H, x0, x1, max_depth, tile shape) start their queues at the row of the longest tile (launch(), LEARNED START ROW). */
 int rt_learn_tile_order(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
+    if (s->images_used)
+        return fail(RT_ERR_INVALID, "the counting build does not sample image textures, so no tile order is learned (include/rt_capi_texture.h)");
     if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 >= x1) return fail(RT_ERR_INVALID, "need 0 <= x0 < x1 <= W, W,H > 0");
     TileShape t;
     {

@@ -40,6 +40,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/rt_capi_texture.h"     /* RT_TEX_WRAP_*: the *_image kernels' folds */
 #include "../../include/rt_capi_tuning.h"      /* RT_STATS_COUNT: the counting build's counters are part of the (tuning) ABI */
 #include "rt_tables.h"
 
@@ -1704,9 +1705,74 @@ __device__ __forceinline__ int checkerboard_select(const float width, const floa
     return (y < height / 2) ? 2 : 1;
 }
 
-/* colour of a stack entry / hit: material colour, or one of the texture's two */
+/* IMAGE TEXTURES (include/rt_capi_texture.h; the *_image kernels only).  One coordinate folded into one copy of the image:
+ * CHECKER is the checkerboard's fold above, REPEAT the non-negative remainder, CLAMP [0, w] (a NaN passes).  fmodf(x, w) =
+ * +-fmodf(|x|, w) with the sign of x; `fast`: every lane of the wavefront may take the short remainder (as checkerboard_select()). */
+__device__ __forceinline__ float image_fold(const float x, const float w, const float rw, const int wrap, const bool fast) {
+    if (wrap == RT_TEX_WRAP_CLAMP) {
+        float c = x;
+        if (c < 0.0f) c = 0.0f;
+        if (c > w) c = w;
+        return c;
+    }
+    const float m = fast ? fmod_small_quotient(fabsf(x), w, rw) : fmodf(fabsf(x), w);
+    if (x >= 0) return m;
+    if (wrap == RT_TEX_WRAP_CHECKER) return fast ? fmod_small_quotient(m + w / 2.0f, w, rw) : fmodf(m + w / 2.0f, w);
+    const float r = -m;                                          /* REPEAT: fmodf(x, w) of a negative x */
+    return (r < 0.0f) ? r + w : r;
+}
+
+/* The texel column of a folded coordinate u in an image n texels wide spanning w: with b_k = fl(fl(w k) / n), the largest i in
+ * [0, n) with b_i <= u (b_0 = 0), i.e. (n - 1) - #{k in [1, n) : u < b_k}; a NaN gives n - 1.  `b` holds b_0 .. b_(n-1), made on
+ * the host in IEEE fp32 (rt_capi.hip, pack_images()).  The b_k do not decrease, so an estimate from u n / w is corrected with
+ * the exact comparisons: one step either way, or none, for any u in [0, w].  u / w is taken from w's
+ * mantissa m in [0.5, 1) and exponent e, (u 2^-e) / m: no factor overflows or flushes for any finite w > 0, however large
+ * or small, so the estimate stays within a step of the answer there too. */
+__device__ __forceinline__ int image_cell(const float u, const float w, const int n, const float *__restrict__ b) {
+    int e;
+    const float m = __builtin_frexpf(w, &e);
+    const float q = __builtin_ldexpf(u, -e) * __builtin_amdgcn_rcpf(m);
+    int i = (int)fminf(fmaxf(q * (float)n, 0.0f), (float)(n - 1));
+    if (u != u) i = n - 1;
+    while (i > 0 && u < b[i]) --i;
+    while (i < n - 1 && !(u < b[i + 1])) ++i;
+    return i;
+}
+
+/* An image's block in the scene's texel buffer: texels_w x texels_h rgb texels, then the column bounds, then the row bounds */
+__device__ __forceinline__ const float *image_block(const float4 q1) {
+    return reinterpret_cast<const float *>(((uint64_t)__float_as_uint(q1.w) << 32) | (uint64_t)__float_as_uint(q1.z));
+}
+
+/* The *_image kernels' texture selector of a plane hit at (tx, ty) whose material has a texture: the index of the texel it
+ * samples within its image.  (In a scene with images every checkerboard is packed as the 2 x 2 CHECKER image that reproduces
+ * it, include/rt_capi_texture.h.)  q0, q1: the image's two table quads. */
+__device__ __forceinline__ int image_select(const float4 q0, const float4 q1, const float x, const float y) {
+    const int wrap = __float_as_int(q1.x);
+    const int tw = __float_as_int(q0.z), th = __float_as_int(q0.w);
+    const bool fast = !wave_any(!(fmod_small_quotient_ok(x, q0.x) && fmod_small_quotient_ok(y, q0.y)));
+    const float u = image_fold(x, q0.x, __builtin_amdgcn_rcpf(q0.x), wrap, fast);
+    const float v = image_fold(y, q0.y, __builtin_amdgcn_rcpf(q0.y), wrap, fast);
+    const float *cols = image_block(q1) + (size_t)tw * (size_t)th * 3;
+    return image_cell(v, q0.y, th, cols + tw) * tw + image_cell(u, q0.x, tw, cols);
+}
+
+__device__ __forceinline__ int plane_texsel(const RtParams &p, const float4 *lds, const uint32_t mbits, const float tx, const float ty) {
+    const int tex = (int)(mbits >> 1) - 1;
+    return image_select(lds[p.tex_off + tex * RT_TEX_QUADS], lds[p.tex_off + tex * RT_TEX_QUADS + 1], tx, ty);
+}
+
+/* colour of a stack entry / hit: material colour, or one of the texture's two; in the *_image kernels, where every texture is an
+ * image and only planes have a textured material row, the texel's (a plain load from the image's block) */
+template <bool kImages = false>
 __device__ __forceinline__ V3 entry_colour(const RtParams &p, const float4 *lds, const float4 m0,
                                            const uint32_t mbits, const int texsel) {
+    if constexpr (kImages) {
+        if ((mbits >> 1) == 0u) return xyz(m0);
+        const int tex = (int)(mbits >> 1) - 1;
+        const float *t = image_block(lds[p.tex_off + tex * RT_TEX_QUADS + 1]) + (size_t)(unsigned int)texsel * 3;
+        return mk(t[0], t[1], t[2]);
+    }
     if (texsel == 0) return xyz(m0);
     const int tex = (int)(mbits >> 1) - 1;
     return xyz(lds[p.tex_off + tex * RT_TEX_QUADS + (texsel - 1)]);
@@ -1719,6 +1785,7 @@ __device__ __forceinline__ V3 entry_colour(const RtParams &p, const float4 *lds,
  * stores): Scene index idx at distance t along
  * the ray (o, d) gives the intersection point P, the normal N (before the CollisionObject ctor re-normalises it) and the texture
  * selector (0: the material's colour); returns the material's second quad (m1.w: its bits), with its number and the kind. */
+template <bool kImages = false>
 __device__ __forceinline__ float4 winner_geometry(const RtParams &p, const float4 *lds, const int idx, const float t, const V3 o,
                                                   const V3 d, V3 *P_out, V3 *N_out, int *texsel_out, int *mat_out, int *kind_out) {
     const uint32_t *lds_u32 = reinterpret_cast<const uint32_t *>(lds);
@@ -1741,10 +1808,14 @@ __device__ __forceinline__ float4 winner_geometry(const RtParams &p, const float
             const V3 PO = sub3(ip, xyz(q1));
             const float tx = dot3(PO, xyz(q2));
             const float ty = dot3(PO, xyz(q3));
-            const int tex = (int)(mbits >> 1) - 1;
-            const float4 t0 = lds[p.tex_off + tex * RT_TEX_QUADS];
-            const float4 t1 = lds[p.tex_off + tex * RT_TEX_QUADS + 1];
-            texsel = checkerboard_select(t0.w, t1.w, tx, ty);
+            if constexpr (kImages) {
+                texsel = plane_texsel(p, lds, mbits, tx, ty);
+            } else {
+                const int tex = (int)(mbits >> 1) - 1;
+                const float4 t0 = lds[p.tex_off + tex * RT_TEX_QUADS];
+                const float4 t1 = lds[p.tex_off + tex * RT_TEX_QUADS + 1];
+                texsel = checkerboard_select(t0.w, t1.w, tx, ty);
+            }
         }
         N = (dot3(xyz(q0), d) < 0) ? xyz(q0) : xyz(q4);
         P = add3(ip, scale3(N, (float)1E-3));
@@ -1785,6 +1856,7 @@ __device__ __forceinline__ HitQuads gbuffer_miss() {
     return HitQuads{make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f), zero, zero};
 }
 
+template <bool kImages>
 __device__ __forceinline__ HitQuads gbuffer_hit(const RtParams &p, const float4 *lds, const int idx, const float t, const V3 P,
                                                 V3 N, const int texsel, const int mat, const uint32_t mbits, const int kind) {
     const float nn = N.x * N.x + N.y * N.y + N.z * N.z;
@@ -1792,7 +1864,7 @@ __device__ __forceinline__ HitQuads gbuffer_hit(const RtParams &p, const float4 
         const float length = sqrtf(nn);
         N = mk(N.x / length, N.y / length, N.z / length);
     }
-    const V3 c = entry_colour(p, lds, lds[p.mat_off + mat * RT_MAT_QUADS], mbits, texsel);
+    const V3 c = entry_colour<kImages>(p, lds, lds[p.mat_off + mat * RT_MAT_QUADS], mbits, texsel);
     const int flags = (kind == RT_KIND_SPHERE && t < 0.0f ? 1 : 0) | ((mbits & 1u) ? 2 : 0);
     return HitQuads{make_float4(__int_as_float(idx), t, P.x, P.y), make_float4(P.z, N.x, N.y, N.z),
                     make_float4(c.x, c.y, c.z, __int_as_float(flags))};
@@ -1816,8 +1888,10 @@ __device__ __forceinline__ void gbuffer_store(const RtParams &p, const int sx, c
  * them into the W x H output (below).  kRays: the tile is a rectangle of cells of the n_cols x rows grid of a caller's ray batch
  * (include/rt_capi_rays.h; launched with W = x1 = n_cols, H = rows, x0 = 0): cell (x, z) is ray x * rows + z, read from
  * p.rays instead of made by the camera.  kGbuffer: a camera tile that also stores each pixel's rt_hit record of its level-0
- * winner at p.gbuffer_hits (include/rt_capi_gbuffer.h); the colours are the plain tile's. */
-template <bool kStats, int kMode, bool kSsaa = false, bool kRays = false, bool kGbuffer = false>
+ * winner at p.gbuffer_hits (include/rt_capi_gbuffer.h); the colours are the plain tile's.  kImages: planes may sample image
+ * textures (include/rt_capi_texture.h): a texel selector is a texel's index, and a stack entry keeps it above 12 bits of object
+ * index (rt_tables.h, RT_IMAGE_SEL_SHIFT). */
+template <bool kStats, int kMode, bool kSsaa = false, bool kRays = false, bool kGbuffer = false, bool kImages = false>
 __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds, float4 *wlds, float4 *help_rays,
                                             const uint32_t *__restrict__ ctl_words, float *__restrict__ out,
                                             float4 *__restrict__ bounce_stack, unsigned long long *__restrict__ stats_out,
@@ -1826,6 +1900,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
     const int wave = __builtin_amdgcn_readfirstlane(wave_in);      /* the tile number is the same in all lanes: a scalar register's worth */
     const uint32_t *lds_u32 = reinterpret_cast<const uint32_t *>(lds);
     const int lane = (int)(threadIdx.x & 63u);
+    constexpr uint32_t kSelShift = kImages ? RT_IMAGE_SEL_SHIFT : 16;   /* stack entry: bits(object index | texsel << kSelShift) */
     unsigned long long t_start = 0ull, t_start_real = 0ull;
     const int tile_row = wave / p.tiles_x;                  /* tile number, row-major */
     const int tile_col = wave - tile_row * p.tiles_x;
@@ -1938,20 +2013,24 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                         const V3 PO = sub3(ip, xyz(q1));
                         const float tx = dot3(PO, xyz(q2));
                         const float ty = dot3(PO, xyz(q3));
-                        const int tex = (int)(mbits >> 1) - 1;
-                        const float4 t0 = lds[p.tex_off + tex * RT_TEX_QUADS];
-                        const float4 t1 = lds[p.tex_off + tex * RT_TEX_QUADS + 1];
-                        texsel = checkerboard_select(t0.w, t1.w, tx, ty);
+                        if constexpr (kImages) {
+                            texsel = plane_texsel(p, lds, mbits, tx, ty);
+                        } else {
+                            const int tex = (int)(mbits >> 1) - 1;
+                            const float4 t0 = lds[p.tex_off + tex * RT_TEX_QUADS];
+                            const float4 t1 = lds[p.tex_off + tex * RT_TEX_QUADS + 1];
+                            texsel = checkerboard_select(t0.w, t1.w, tx, ty);
+                        }
                     }
                     N = (dot3(xyz(q0), d) < 0) ? xyz(q0) : xyz(q4);
                     P = add3(ip, scale3(N, (float)1E-3));
                 }
                 if constexpr (kGbuffer) {
-                    if (level == 0) record = gbuffer_hit(p, lds, idx, t, P, N, texsel, mat, mbits, kind);
+                    if (level == 0) record = gbuffer_hit<kImages>(p, lds, idx, t, P, N, texsel, mat, mbits, kind);
                 }
                 if (mbits & 1u) {                            /* hit a light: :520-527 */
                     const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
-                    C = scale3(entry_colour(p, lds, m0, mbits, texsel), m1.z);
+                    C = scale3(entry_colour<kImages>(p, lds, m0, mbits, texsel), m1.z);
                     alive = false;
                 } else {
                     shade = true;
@@ -2060,7 +2139,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                     const int mat = (int)(lds_u32[p.objinfo_off * 4 + idx] >> 20);
                     const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
                     const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
-                    const V3 object_color = entry_colour(p, lds, m0, __float_as_uint(m1.w), texsel);
+                    const V3 object_color = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), texsel);
                     const float diffuse_factor = m0.w, specular_factor = m1.x;
                     /* CollisionObject ctor: Ray(point, normal) re-normalises, src/SceneObject.h:62.  (The rare path goes through an
                      * opaque copy: left to itself the compiler computes the square root and the three divides before the light
@@ -2113,7 +2192,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                 const int mat_last = (int)(info >> 20);
                 const float4 m0 = lds[p.mat_off + mat_last * RT_MAT_QUADS];
                 const float4 m1 = lds[p.mat_off + mat_last * RT_MAT_QUADS + 1];
-                const V3 oc = entry_colour(p, lds, m0, __float_as_uint(m1.w), texsel);
+                const V3 oc = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), texsel);
                 const V3 refl = mk(null_color.x * m1.y * oc.x, null_color.y * m1.y * oc.y, null_color.z * m1.y * oc.z);
                 C = add3(C, refl);
                 alive = false;
@@ -2123,7 +2202,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                                         -2 * N.z * n_dot_incoming + d.z);
                 float4 e;
                 e.x = C.x; e.y = C.y; e.z = C.z;
-                e.w = __uint_as_float((uint32_t)idx | ((uint32_t)texsel << 16));
+                e.w = __uint_as_float((uint32_t)idx | ((uint32_t)texsel << kSelShift));
                 if (level < p.stack_lds_levels) wlds[here(p.stack_off) + level * here(p.stack_stride) + threadIdx.x] = e;
                 else                            bounce_stack[hbm_stack_entry(p, level)] = e;
                 top = level + 1;
@@ -2149,11 +2228,11 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
             if (k < p.stack_lds_levels) e = wlds[here(p.stack_off) + k * here(p.stack_stride) + threadIdx.x];
             else                        e = bounce_stack[hbm_stack_entry(p, k)];
             const uint32_t bits = __float_as_uint(e.w);
-            const uint32_t info = lds_u32[p.objinfo_off * 4 + (bits & 0xFFFFu)];
+            const uint32_t info = lds_u32[p.objinfo_off * 4 + (bits & ((1u << kSelShift) - 1u))];
             const int mat = (int)(info >> 20);
             const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
             const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
-            const V3 oc = entry_colour(p, lds, m0, __float_as_uint(m1.w), (int)(bits >> 16));
+            const V3 oc = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), (int)(bits >> kSelShift));
             const V3 refl = mk(C.x * m1.y * oc.x, C.y * m1.y * oc.y, C.z * m1.y * oc.z);
             C = add3(mk(e.x, e.y, e.z), refl);
         }
@@ -2259,7 +2338,7 @@ __device__ __forceinline__ void query_next_tile(int &next_pop, unsigned int *con
  * consecutive lanes writing consecutive records.  The normal is the CollisionObject's normal_ray direction, i.e. the winner's
  * normal re-normalised (src/SceneObject.h:62): sqrtf(1) = 1 and v / 1 = v when N.N rounds to 1, so the divide is only taken
  * where it is not (as renormalize3()).  A miss: object -1 and zeros. */
-template <int kMode>
+template <int kMode, bool kImages = false>
 __device__ __forceinline__ void hits_tile(const RtParams &p, const float4 *lds, float4 *wlds, const uint32_t *__restrict__ ctl_words,
                                           float *__restrict__ out, const int wave_in, int &next_pop, unsigned int *const ask_head) {
     Stats<false> st;
@@ -2282,14 +2361,14 @@ __device__ __forceinline__ void hits_tile(const RtParams &p, const float4 *lds, 
     if (inside && idx >= 0) {
         V3 P, N;
         int texsel = 0, mat, kind;
-        const float4 m1 = winner_geometry(p, lds, idx, t, o, d, &P, &N, &texsel, &mat, &kind);
+        const float4 m1 = winner_geometry<kImages>(p, lds, idx, t, o, d, &P, &N, &texsel, &mat, &kind);
         const uint32_t mbits = __float_as_uint(m1.w);
         const float nn = N.x * N.x + N.y * N.y + N.z * N.z;
         if (nn != 1.0f) {
             const float length = sqrtf(nn);
             N = mk(N.x / length, N.y / length, N.z / length);
         }
-        const V3 c = entry_colour(p, lds, lds[p.mat_off + mat * RT_MAT_QUADS], mbits, texsel);
+        const V3 c = entry_colour<kImages>(p, lds, lds[p.mat_off + mat * RT_MAT_QUADS], mbits, texsel);
         /* bit 0: an inside hit -- the sphere's root1 < 0 (src/SceneSphere.cpp:80-95), which is the distance it reports; bit 1: a light */
         const int flags = (kind == RT_KIND_SPHERE && t < 0.0f ? 1 : 0) | ((mbits & 1u) ? 2 : 0);
         q0 = make_float4(__int_as_float(idx), t, P.x, P.y);
@@ -2389,7 +2468,7 @@ __device__ RT_SCAN_INLINE unsigned int queues_with_tiles(const unsigned int *til
 }
 
 template <bool kStats, bool kGlobalTables = false, bool kClusters = false, bool kRoomy = false, bool kFast = false, bool kSsaa = false,
-          bool kRays = false, int kQuery = RT_QUERY_NONE, bool kGbuffer = false>
+          bool kRays = false, int kQuery = RT_QUERY_NONE, bool kGbuffer = false, bool kImages = false>
 __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__restrict__ image,
                                             float *__restrict__ out, unsigned int *__restrict__ tile_counter,
                                             float4 *__restrict__ bounce_stack,
@@ -2599,9 +2678,9 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
         unsigned int *const ask_head = (ask_ahead || (kHelp && heavy_phase != 0)) ? nullptr
                                      : tile_counter + ((my_xcc + steal) & (RT_TILE_QUEUES - 1)) * RT_QUEUE_STRIDE;
         constexpr int kMode = kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0);
-        if constexpr (kQuery == RT_QUERY_HITS) hits_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
+        if constexpr (kQuery == RT_QUERY_HITS) hits_tile<kMode, kImages>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
         else if constexpr (kQuery == RT_QUERY_OCCLUDED) occluded_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
-        else render_tile<kStats, kMode, kSsaa, kRays, kGbuffer>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
+        else render_tile<kStats, kMode, kSsaa, kRays, kGbuffer, kImages>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
                                                                 my_xcc, steal, next_pop, ask_head);
 #ifdef RT_TIMELINE
         if (p.timeline != 0ull && lane == 0) {                   /* ... when it was done, and by whom */
@@ -2667,8 +2746,8 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
 #define RT_BLOCK_BOUND_CLUSTERS 512
 #endif
 
-/* rt_kernel_ssaa.hip, rt_kernel_rays.hip, rt_kernel_query.hip and rt_kernel_gbuffer.hip include this file for the body alone
- * and define the supersampling, the ray-batch, the ray-query and the G-buffer kernels: in translation units of their own, the seven kernels below compile to the code they have without them (next to five more instantiations of the
+/* rt_kernel_ssaa.hip, rt_kernel_rays.hip, rt_kernel_query.hip, rt_kernel_gbuffer.hip and rt_kernel_texture.hip include this
+ * file for the body alone and define the supersampling, the ray-batch, the ray-query, the G-buffer and the image-texture kernels: in translation units of their own, the seven kernels below compile to the code they have without them (next to five more instantiations of the
  * body in one module, the item-table kernel's allocation moved: one more spilled scalar) */
 #ifndef RT_KERNEL_BODY_ONLY
 

@@ -25,7 +25,11 @@
  *   materials  2 quads per DISTINCT (ObjMaterial, intensity, light flag) row:
  *                {colour.rgb, diffuse}, {specular, reflective, intensity,
  *                 bits(is_light | (texture+1) << 1)}
- *   textures   2 quads per checkerboard: {light.rgb, width}, {dark.rgb, height}
+ *   textures   2 quads per checkerboard: {light.rgb, width}, {dark.rgb, height}; in a scene with images
+ *              (include/rt_capi_texture.h) instead 2 quads per texture, checkerboards first, each one packed as its 2 x 2
+ *              CHECKER image: {width, height, bits(texels_w), bits(texels_h)}, {bits(wrap), 0, bits(the image's block in the
+ *              texel buffer: low word), bits(high word)}; a block is texels_w x texels_h rgb fp32 texels, then the column
+ *              bounds b_0 .. b_(texels_w - 1), then the row bounds (rt_kernel.hip, image_cell())
  *   objinfo    one u32 per object (4 per quad):
  *                bits 0-15 geometry offset (quads), 16-17 kind, 20-31 material row
  *
@@ -120,6 +124,12 @@ enum { RT_DESK_STATE = 0, RT_DESK_CURSOR, RT_DESK_INSIDE, RT_DESK_FINISHED, RT_D
 #endif
 
 #define RT_STACK_ENTRY_BYTES 16   /* {local.rgb, bits(object index | texsel << 16)} per bounce level per lane */
+
+/* IMAGE TEXTURES (include/rt_capi_texture.h; the *_image kernels only).  Only planes get a textured material row there (a
+ * sphere's texture is dropped), and the texel selector of a hit is the index of its texel within its image (< 2^20, the
+ * scene's texel limit).  A bounce-stack entry is {local.rgb, bits(object index | texsel << 12)}: 12 bits of object index
+ * (RT_MAX_OBJECTS), 20 of selector. */
+#define RT_IMAGE_SEL_SHIFT 12
 
 #define RT_PRIMARY_ITEMS 64          /* scenes with more FAST items than this have no PRIMARY table */
 

@@ -9,7 +9,9 @@ flattened plain-old-data views that cross the C ABI.  Nothing here renders.
 import ctypes as C
 import os
 
-from .capi import LIB_DIR, RtCameraDesc, RtSceneDesc, F3
+import numpy as np
+
+from .capi import LIB_DIR, RtCameraDesc, RtImageTextureDesc, RtSceneDesc, F3
 
 _hlib = None
 
@@ -44,6 +46,7 @@ def load_host_library():
     lib.rth_set_specular.argtypes = [vp, i, f]
     lib.rth_set_reflective.argtypes = [vp, i, f]
     lib.rth_set_checkerboard.argtypes = [vp, i, pf, pf, f, f]
+    lib.rth_set_image_texture.argtypes = [vp, i, i, i, vp, f, f, i]
     lib.rth_set_light.argtypes = [vp, i]
     lib.rth_set_intensity.argtypes = [vp, i, f]
     lib.rth_set_object_indices.argtypes = [vp, i, i]
@@ -51,6 +54,8 @@ def load_host_library():
     lib.rth_camera_eye_ray.argtypes = [vp, f, f, pf, pf]
     lib.rth_scene_desc.argtypes = [vp]
     lib.rth_scene_desc.restype = C.POINTER(RtSceneDesc)
+    lib.rth_scene_images.argtypes = [vp, C.POINTER(C.POINTER(RtImageTextureDesc))]
+    lib.rth_scene_images.restype = i
     lib.rth_camera_desc.argtypes = [vp]
     lib.rth_camera_desc.restype = C.POINTER(RtCameraDesc)
     lib.rth_write_screen_txt.argtypes = [C.c_char_p, i, i, vp, C.c_double, C.c_double]
@@ -151,6 +156,14 @@ class HostScene:
     def set_reflective(self, idx, f): self._ok(self._lib.rth_set_reflective(self._h, idx, f))
     def set_checkerboard(self, idx, light, dark, w, h):
         self._ok(self._lib.rth_set_checkerboard(self._h, idx, _v(light), _v(dark), w, h))
+    def set_image_texture(self, idx, texels, w, h, wrap):
+        """a Texture_Image (include/rt_capi_texture.h): texels float32 (texels_h, texels_w, 3), texels[j, i] texel (i, j),
+        copied; w, h the world size of one copy, wrap RT_TEX_WRAP_*"""
+        t = np.ascontiguousarray(texels, dtype=np.float32)
+        if t.ndim != 3 or t.shape[2] != 3:
+            raise ValueError("texels must be (texels_h, texels_w, 3)")
+        self._ok(self._lib.rth_set_image_texture(self._h, idx, t.shape[1], t.shape[0], t.ctypes.data, w, h, wrap))
+
     def set_light(self, idx): self._ok(self._lib.rth_set_light(self._h, idx))
     def set_intensity(self, idx, f): self._ok(self._lib.rth_set_intensity(self._h, idx, f))
     def set_object_indices(self, my_rank, group_size):
@@ -166,6 +179,13 @@ class HostScene:
     @property
     def desc(self):
         return self._lib.rth_scene_desc(self._h)
+
+    @property
+    def images(self):
+        """the flattened scene's images (texture indices n_textures + k): (count, pointer to RtImageTextureDesc or None)"""
+        ptr = C.POINTER(RtImageTextureDesc)()
+        n = self._lib.rth_scene_images(self._h, C.byref(ptr))
+        return n, (ptr if n else None)
 
     @property
     def camera(self):

@@ -11,6 +11,18 @@ HIT_DTYPE = np.dtype([("object", "<i4"), ("distance", "<f4"), ("point", "<f4", (
 assert HIT_DTYPE.itemsize == 48
 
 
+def image_descs(images):
+    """(texels, width, height, wrap) tuples -> (the C-contiguous float32 arrays, an RtImageTextureDesc array over them)."""
+    arrays = [np.ascontiguousarray(t, dtype=np.float32) for t, _, _, _ in images]
+    descs = (capi.RtImageTextureDesc * max(len(images), 1))()
+    for k, (a, (_, width, height, wrap)) in enumerate(zip(arrays, images)):
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("image %d: texels must be (texels_h, texels_w, 3)" % k)
+        descs[k] = capi.RtImageTextureDesc(a.shape[1], a.shape[0], width, height, wrap,
+                                           a.ctypes.data_as(C.POINTER(C.c_float)))
+    return arrays, descs
+
+
 class Renderer:
     """Owns an ``rt_scene`` (device tables for one HostScene on one GPU)."""
 
@@ -18,17 +30,30 @@ class Renderer:
         self._lib = capi.load_library()
         self._host = host_scene          # keeps the desc arrays alive
         self._scene = C.c_void_p()
-        capi.check(self._lib.rt_scene_create(host_scene.desc, device, C.byref(self._scene)))
+        n_images, images = host_scene.images        # the scene's Texture_Image objects (include/rt_capi_texture.h)
+        if n_images:
+            capi.check(self._lib.rt_scene_create_textured(host_scene.desc, n_images, images, device, C.byref(self._scene)))
+        else:
+            capi.check(self._lib.rt_scene_create(host_scene.desc, device, C.byref(self._scene)))
         self._cam = host_scene.camera
 
     @classmethod
-    def from_desc(cls, desc, camera, device=0, keepalive=None):
-        """Build from raw RtSceneDesc / RtCameraDesc (tests with hand-made tables)."""
+    def from_desc(cls, desc, camera, device=0, keepalive=None, images=None):
+        """Build from raw RtSceneDesc / RtCameraDesc (tests with hand-made tables).  images (include/rt_capi_texture.h): a
+        list of (texels, width, height, wrap) -- texels a float32 (texels_h, texels_w, 3) array, texels[j, i] texel (i, j),
+        width / height the world size of one copy, wrap RT_TEX_WRAP_* -- that texture indices n_textures + k name.  With
+        images (even an empty list) the scene is made by rt_scene_create_textured, else by rt_scene_create."""
         self = cls.__new__(cls)
         self._lib = capi.load_library()
         self._host = keepalive
         self._scene = C.c_void_p()
-        capi.check(self._lib.rt_scene_create(C.byref(desc), device, C.byref(self._scene)))
+        if images is None:
+            capi.check(self._lib.rt_scene_create(C.byref(desc), device, C.byref(self._scene)))
+        else:
+            arrays, descs = image_descs(images)
+            self._images = (arrays, descs)         # the texels stay alive with the scene (the library copies them too)
+            ptr = descs if len(images) else None
+            capi.check(self._lib.rt_scene_create_textured(C.byref(desc), len(images), ptr, device, C.byref(self._scene)))
         self._cam = C.pointer(camera)
         return self
 
