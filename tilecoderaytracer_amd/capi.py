@@ -43,6 +43,11 @@ class RtImageTextureDesc(C.Structure):
                 ("wrap", C.c_int32), ("texels", C.POINTER(C.c_float))]
 
 
+class RtRefractionDesc(C.Structure):
+    """include/rt_capi_refract.h: a refractive object -- Scene index, transmission factor tf, a sphere interior's ior."""
+    _fields_ = [("object", C.c_int32), ("refractive", C.c_float), ("ior", C.c_float)]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [
         ("n_objects", C.c_int32), ("objects", C.POINTER(RtObjectDesc)),
@@ -182,6 +187,12 @@ def load_library():
         lib.rt_capi_texture_version.restype = i
         lib.rt_scene_create_textured.argtypes = [C.POINTER(RtSceneDesc), i, C.POINTER(RtImageTextureDesc), i, C.POINTER(vp)]
         lib.rt_scene_create_textured.restype = i
+    # include/rt_capi_refract.h (likewise absent from older builds)
+    if hasattr(lib, "rt_scene_create_refractive"):
+        lib.rt_capi_refract_version.restype = i
+        lib.rt_scene_create_refractive.argtypes = [C.POINTER(RtSceneDesc), i, C.POINTER(RtImageTextureDesc), i,
+                                                   C.POINTER(RtRefractionDesc), i, C.POINTER(vp)]
+        lib.rt_scene_create_refractive.restype = i
     for name in ("rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_render",
                  "rt_render_device", "rt_render_multi", "rt_render_stats", "rt_learn_tile_order", "rt_get_timing", "rt_reset_timing",
                  "rt_get_launch_info", "rt_set_option", "rt_chunk_bounds", "rt_multi_create", "rt_multi_render",

@@ -27,6 +27,7 @@
 
 #include "../../../include/rt_capi.h"
 #include "../../../include/rt_capi_texture.h"
+#include "../../../include/rt_capi_refract.h"
 
 namespace CelioRayTracer {
 
@@ -170,7 +171,7 @@ class ObjMaterial {
 public:
     ObjMaterial()
         : myColor(1.0f, 1.0f, 1.0f), myObjTexture_ptr(nullptr), absorption_factor(0.0f),
-          diffuse_factor(1.0), specular_factor(1.0), reflective_factor(0), refractive_factor(0) {}
+          diffuse_factor(1.0), specular_factor(1.0), reflective_factor(0), refractive_factor(0), refractive_index(1.0f) {}
     void setColor(vector3d c) { myColor = c; }
     void setAbsorptionFactor(float a) { absorption_factor = a; warn("Absorption"); }
     void setDiffuseFactor(float d) { diffuse_factor = d; }
@@ -185,6 +186,9 @@ public:
     float getAbsorptionFactor() const { return absorption_factor; }
     float getReflectiveFactor() const { return reflective_factor; }
     float getRefractiveFactor() const { return refractive_factor; }
+    /* not in the reference: the index of refraction of a sphere's interior (include/rt_capi_refract.h), 1 by default */
+    void setRefractiveIndex(float n) { refractive_index = n; }
+    float getRefractiveIndex() const { return refractive_index; }
 private:
     void warn(const char *which) const {        /* the reference's sanity print, :34,47,54 */
         if (verbose() && (absorption_factor + reflective_factor + refractive_factor) > 1)
@@ -194,6 +198,7 @@ private:
     Color myColor;
     ObjTexture *myObjTexture_ptr;
     float absorption_factor, diffuse_factor, specular_factor, reflective_factor, refractive_factor;
+    float refractive_index;
 };
 
 /* src/SceneObject.h:26-200, src/SceneObject.cpp:9-27 */
@@ -381,13 +386,19 @@ private:
 
 /* The flattened scene: owns the arrays an rt_scene_desc points into.  images: the bitmap textures
  * (include/rt_capi_texture.h), texture indices desc.n_textures + k; their texels stay owned by the Texture_Image objects.
- * create(): rt_scene_create_textured when there are images, rt_scene_create otherwise. */
+ * refractions: one entry per non-light object whose material has refractive_factor > 0 (include/rt_capi_refract.h).
+ * create(): rt_scene_create_refractive when there are refractions, else rt_scene_create_textured when there are images,
+ * rt_scene_create otherwise. */
 struct FlatScene {
     std::vector<rt_object_desc> objects;
     std::vector<rt_texture_desc> textures;
     std::vector<rt_image_texture_desc> images;
+    std::vector<rt_refraction_desc> refractions;
     rt_scene_desc desc;
     int create(int device, rt_scene **out) const {
+        if (!refractions.empty())
+            return rt_scene_create_refractive(&desc, (int)images.size(), images.empty() ? nullptr : images.data(),
+                                              (int)refractions.size(), refractions.data(), device, out);
         if (images.empty()) return rt_scene_create(&desc, device, out);
         return rt_scene_create_textured(&desc, (int)images.size(), images.data(), device, out);
     }
@@ -458,6 +469,12 @@ public:
         }
         for (int i = 0; i < object_count; ++i)          /* images after the checkerboards */
             if (out.objects[(size_t)i].texture < -1) out.objects[(size_t)i].texture = (int32_t)out.textures.size() - 2 - out.objects[(size_t)i].texture;
+        out.refractions.clear();
+        for (int i = 0; i < object_count; ++i) {         /* refractive materials (include/rt_capi_refract.h) */
+            const ObjMaterial *m = objects[(size_t)i]->getMaterial();
+            if (!out.objects[(size_t)i].is_light && m->getRefractiveFactor() > 0.0f)
+                out.refractions.push_back(rt_refraction_desc{(int32_t)i, m->getRefractiveFactor(), m->getRefractiveIndex()});
+        }
         out.desc.n_objects = object_count;
         out.desc.objects = out.objects.empty() ? nullptr : out.objects.data();
         out.desc.n_textures = (int32_t)out.textures.size();

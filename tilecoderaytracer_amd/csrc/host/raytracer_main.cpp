@@ -41,7 +41,7 @@ static std::vector<float> pixels;          /* pixels[x][z] as packed fp32 RGB */
 static int usage(const char *argv0) {
     std::fprintf(stderr,
                  "usage: %s [--width W] [--height H] [--depth D] [--scene 1|2|grid:N[:noshadow]]\n"
-                 "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE]\n", argv0);
+                 "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE] [--glass I:TF:IOR ...]\n", argv0);
     return 1;
 }
 
@@ -49,6 +49,7 @@ int main(int argc, char **argv) {
     int W = 500, H = 504, depth = 50, gpus = 1, ssaa = 1;
     bool write_txt = true;
     std::string scene_name = "1", out_path = "raytracer_screen.txt", hits_path;
+    std::vector<std::string> glass;              /* --glass I:TF:IOR: object I refractive (include/rt_capi_refract.h) */
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](int &dst) { if (i + 1 >= argc) return false; dst = std::atoi(argv[++i]); return true; };
@@ -60,6 +61,7 @@ int main(int argc, char **argv) {
         else if (a == "--scene" && i + 1 < argc) scene_name = argv[++i];
         else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
         else if (a == "--hits" && i + 1 < argc) hits_path = argv[++i];
+        else if (a == "--glass" && i + 1 < argc) glass.push_back(argv[++i]);
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
@@ -92,12 +94,25 @@ int main(int argc, char **argv) {
         return usage(argv[0]);
     }
 
+    for (const std::string &g : glass) {
+        int idx = -1;
+        float tf = 0.0f, ior = 1.0f;
+        if (std::sscanf(g.c_str(), "%d:%f:%f", &idx, &tf, &ior) != 3 || idx < 0 || idx >= my_scene.getObjectCount())
+            return usage(argv[0]);
+        my_scene.getObject(idx)->getMaterial()->setRefractiveFactor(tf);
+        my_scene.getObject(idx)->getMaterial()->setRefractiveIndex(ior);
+    }
+
     FlatScene flat;
     rt_camera_desc cam;
     my_scene.flatten(flat);
     my_camera.describe(cam);
     if (!flat.images.empty() && gpus > 1) {         /* the multi-GPU path takes no images (include/rt_capi_texture.h) */
         std::fprintf(stderr, "bitmap textures render on one GPU\n");
+        return 1;
+    }
+    if (!flat.refractions.empty() && gpus > 1) {    /* nor refraction (include/rt_capi_refract.h) */
+        std::fprintf(stderr, "refraction renders on one GPU\n");
         return 1;
     }
     pixels.assign((size_t)W * (size_t)H * 3, 0.0f);

@@ -121,6 +121,14 @@ int rth_set_reflective(rth_scene *s, int idx, float f) {
     if (!o) return 1;
     o->getMaterial()->setReflectiveFactor(f); s->dirty = true; return 0;
 }
+int rth_set_refraction(rth_scene *s, int idx, float factor, float ior) {
+    SceneObject *o = object_at(s, idx);
+    if (!o) return 1;
+    o->getMaterial()->setRefractiveFactor(factor);
+    o->getMaterial()->setRefractiveIndex(ior);
+    s->dirty = true;
+    return 0;
+}
 int rth_set_checkerboard(rth_scene *s, int idx, const float light[3], const float dark[3], float w, float h) {
     SceneObject *o = object_at(s, idx);
     if (!o || !light || !dark) return 1;
@@ -174,6 +182,13 @@ const rt_camera_desc *rth_camera_desc(rth_scene *s) {
     if (!s) return nullptr;
     refresh(s);
     return &s->cam_desc;
+}
+
+int rth_scene_refractions(rth_scene *s, const rt_refraction_desc **refractions) {
+    if (!s || !refractions) return 0;
+    refresh(s);
+    *refractions = s->flat.refractions.empty() ? nullptr : s->flat.refractions.data();
+    return (int)s->flat.refractions.size();
 }
 
 int rth_scene_images(rth_scene *s, const rt_image_texture_desc **images) {

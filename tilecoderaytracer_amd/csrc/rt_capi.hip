@@ -22,6 +22,7 @@
 #include "../../include/rt_capi_rays.h"
 #include "../../include/rt_capi_ssaa.h"
 #include "../../include/rt_capi_texture.h"
+#include "../../include/rt_capi_refract.h"
 #include "../../include/rt_capi_tuning.h"
 #include "rt_tables.h"
 
@@ -75,6 +76,17 @@ RT_DECLARE_IMAGE_KERNELS(_ssaa);
 RT_DECLARE_IMAGE_KERNELS(_rays);
 RT_DECLARE_IMAGE_KERNELS(_hits);
 RT_DECLARE_IMAGE_KERNELS(_gbuffer);
+/* ... with refraction (rt_kernel_refract.hip): the *_refract sibling of the camera, supersampling, ray-batch and G-buffer kernels */
+#define RT_DECLARE_REFRACT_KERNELS(suffix)                      \
+    RT_DECLARE_KERNEL(rt_render_kernel##suffix##_refract);       \
+    RT_DECLARE_KERNEL(rt_render_kernel_items##suffix##_refract); \
+    RT_DECLARE_KERNEL(rt_render_kernel_large##suffix##_refract); \
+    RT_DECLARE_KERNEL(rt_render_kernel_clusters##suffix##_refract); \
+    RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide##suffix##_refract)
+RT_DECLARE_REFRACT_KERNELS();
+RT_DECLARE_REFRACT_KERNELS(_ssaa);
+RT_DECLARE_REFRACT_KERNELS(_rays);
+RT_DECLARE_REFRACT_KERNELS(_gbuffer);
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_stats);      /* the counting builds */
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_fast_stats);
 
@@ -126,6 +138,10 @@ struct rt_scene {
     bool images_used = false;
     void *d_texels = nullptr;                 /* every texture's block (rt_tables.h), texture by texture */
     std::vector<size_t> texel_blocks;         /* each texture's block: its first float in d_texels */
+    /* REFRACTION (include/rt_capi_refract.h): per object {tf, ior} ({0, 1}: none); refract_used: some tf > 0 -- the scene is then
+     * packed as an image scene with a refraction section (rt_tables.h) and the *_refract kernels run */
+    std::vector<float> refr_tf, refr_ior;
+    bool refract_used = false;
     int shadow_begin = 0, shadow_end = 0;
     float null_color[3] = {0.75f, 0.75f, 0.75f};
     /* packed tables (host copies) */
@@ -460,7 +476,7 @@ struct LeafItem { float lo[3], hi[3]; uint32_t member_off, count, cidx_slot; boo
 struct Packing {
     explicit Packing(int n)
         : geom_off((size_t)n, 0), mat_of((size_t)n, 0), aa_rec_of((size_t)n, -1), aa_cls_of((size_t)n, -1), clustered((size_t)n, 0) {}
-    std::vector<Quad> geom, lights, mats, texs;
+    std::vector<Quad> geom, lights, mats, texs, refr;
     std::vector<int> geom_off, mat_of;               /* per object: its full record in geom, its material */
     std::vector<uint32_t> cidx;                      /* Scene indices of the clustered runs' members, leaf by leaf */
     std::vector<LeafItem> leaf_items;
@@ -532,9 +548,12 @@ int pack_materials_and_lights(const rt_scene *s, Packing &P) {
         const uint32_t mbits = (o.is_light ? 1u : 0u) | ((uint32_t)(texture + 1) << 1);
         Quad m0 = {{o.color[0], o.color[1], o.color[2], o.diffuse}};
         Quad m1 = {{o.specular, o.reflective, o.intensity, bits_to_float(mbits)}};
-        std::vector<uint32_t> key(8);
+        /* REFRACTION: the row's {tf, ior} is part of the key */
+        const Quad r = s->refract_used ? Quad{{s->refr_tf[(size_t)i], s->refr_ior[(size_t)i], 0.0f, 0.0f}} : Quad{{0, 0, 0, 0}};
+        std::vector<uint32_t> key(s->refract_used ? 12 : 8);
         std::memcpy(key.data(), m0.v, 16);
         std::memcpy(key.data() + 4, m1.v, 16);
+        if (s->refract_used) std::memcpy(key.data() + 8, r.v, 16);
         auto it = mat_index.find(key);
         if (it == mat_index.end()) {
             const int mi = (int)mat_index.size();
@@ -542,6 +561,7 @@ int pack_materials_and_lights(const rt_scene *s, Packing &P) {
             mat_index.emplace(key, mi);
             P.mats.push_back(m0);
             P.mats.push_back(m1);
+            if (s->refract_used) P.refr.push_back(r);
             P.mat_of[(size_t)i] = mi;
         } else {
             P.mat_of[(size_t)i] = it->second;
@@ -865,10 +885,16 @@ void assemble_image(const rt_scene *s, Packing &P) {
     }
     b.lights_off = (int)image.size();
     image.insert(image.end(), P.lights.begin(), P.lights.end());
+    const size_t refr_header = image.size();
+    if (s->refract_used) image.push_back(Quad{{0, 0, 0, 0}});       /* REFRACTION: the rows' offset, below */
     b.mat_off = (int)image.size();
     image.insert(image.end(), P.mats.begin(), P.mats.end());
     b.tex_off = (int)image.size();
     image.insert(image.end(), P.texs.begin(), P.texs.end());
+    if (s->refract_used) {
+        image[refr_header].v[0] = bits_to_float((uint32_t)image.size());
+        image.insert(image.end(), P.refr.begin(), P.refr.end());
+    }
     std::vector<uint32_t> objinfo((size_t)n);
     for (int i = 0; i < n; ++i)
         objinfo[(size_t)i] = (uint32_t)P.geom_off[(size_t)i] | ((uint32_t)s->objects[(size_t)i].kind << 16) |
@@ -969,7 +995,7 @@ int upload_scene(rt_scene *s) {
 int upload_texels(rt_scene *s) {
     const std::vector<float> buf = texel_buffer(s, &s->texel_blocks);
     HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipMalloc(&s->d_texels, buf.size() * sizeof(float)));
+    HIP_TRY(hipMalloc(&s->d_texels, std::max<size_t>(buf.size(), 4) * sizeof(float)));   /* (a refractive scene may have no texture) */
     HIP_TRY(hipMemcpy(s->d_texels, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
     for (rt_scene::Image &im : s->images) std::vector<float>().swap(im.texels);     /* (the device copy is the only one kept) */
     return RT_OK;
@@ -1208,6 +1234,9 @@ int primary_quads(const rt_scene *s) {
 
 struct BlockChoice { int block = 0, lds_bytes = 0, stack_lds_levels = 0; bool global_tables = false; };
 
+/* quads per bounce-stack level and lane: 1, or RT_REFRACT_ENTRY_QUADS in the *_refract kernels */
+int stack_entry_quads(const rt_scene *s) { return s->refract_used ? RT_REFRACT_ENTRY_QUADS : 1; }
+
 /* Workgroup size and where the bounce stack goes.  The stack is 16 B per level
  * per thread.  As many of its lowest levels as fit share LDS with the scene
  * tables while RT_STACK_LDS_SHARE workgroups per CU still fit in the 160 KiB
@@ -1226,7 +1255,8 @@ int choose_block(const rt_scene *s, int max_depth, bool counting, int block_over
         return fail(RT_ERR_CAPACITY, "option tables=1: the scene tables do not fit in LDS (160 KiB)");
     if (c->global_tables) scene_bytes = 0;
     c->block = block_override ? block_override : (s->block_threads_opt ? s->block_threads_opt : 256);
-    const double per_level = (double)RT_STACK_ENTRY_BYTES * (double)c->block;
+    /* (REFRACTION: three quads a level, rt_tables.h) */
+    const double per_level = (double)RT_STACK_ENTRY_BYTES * (double)stack_entry_quads(s) * (double)c->block;
     /* levels 0 .. max_depth - 1 can push an entry (the last level's reflection is folded where it is found: rt_kernel.hip) */
     const double levels = (double)max_depth;
     double in_lds = 0.0;
@@ -1369,7 +1399,7 @@ void help_desk(const rt_scene *s, bool clusters_kernel, int W, int x0, int x1, i
     p.help_spin_limit = s->help_spin_opt;
     const bool help_wanted = s->help_opt > 0 || (s->help_opt < 0 && (long long)(x1 - x0) * 4 <= (long long)W * 3);
     if (!clusters_kernel || !help_wanted || block <= 64) return;
-    const int desk_off = p.stack_off + stack_lds_levels * block;
+    const int desk_off = p.stack_off + stack_lds_levels * stack_entry_quads(s) * block;
     const int with_desk = (desk_off + (RT_DESK_WORDS * 4 + 15) / 16) * 16;
     if ((size_t)with_desk <= RT_MAX_LDS_BYTES) {
         p.desk_off = desk_off;
@@ -1454,6 +1484,11 @@ struct Siblings { Kernel plain, ssaa, rays, hits, occluded, gbuffer; };
 #define RT_SIBLINGS_IMAGE(k)                                                                                              \
     Siblings{RT_KERNEL(k##_image), RT_KERNEL(k##_ssaa_image), RT_KERNEL(k##_rays_image), RT_KERNEL(k##_hits_image), \
              RT_KERNEL(k##_occluded), RT_KERNEL(k##_gbuffer_image)}
+/* with refraction the *_refract siblings: the name of the kernel the same call runs on a scene with neither images nor
+ * refraction, + "_refract" (the ray queries answer geometry: the *_image ones, which sample the same tables) */
+#define RT_SIBLINGS_REFRACT(k)                                                                                              \
+    Siblings{RT_KERNEL(k##_refract), RT_KERNEL(k##_ssaa_refract), RT_KERNEL(k##_rays_refract), RT_KERNEL(k##_hits_image), \
+             RT_KERNEL(k##_occluded), RT_KERNEL(k##_gbuffer_refract)}
 #define RT_SIBLINGS(k)                                                                                              \
     Siblings{RT_KERNEL(k), RT_KERNEL(k##_ssaa), RT_KERNEL(k##_rays), RT_KERNEL(k##_hits), RT_KERNEL(k##_occluded), \
              RT_KERNEL(k##_gbuffer)}
@@ -1472,6 +1507,14 @@ Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int b
         if (gbuffer) return k.gbuffer;
         return ssaa ? k.ssaa : (rays ? k.rays : k.plain);
     };
+    if (s->refract_used) {
+        if (global_tables) return pick(RT_SIBLINGS_REFRACT(rt_render_kernel_large));
+        if (s->n_clusters > 0 && s->pairs_opt) {
+            const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
+            return wide ? pick(RT_SIBLINGS_REFRACT(rt_render_kernel_clusters_wide)) : pick(RT_SIBLINGS_REFRACT(rt_render_kernel_clusters));
+        }
+        return fast_tables ? pick(RT_SIBLINGS_REFRACT(rt_render_kernel)) : pick(RT_SIBLINGS_REFRACT(rt_render_kernel_items));
+    }
     const bool img = s->images_used;
     if (global_tables) return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel_large) : RT_SIBLINGS(rt_render_kernel_large));
     if (s->n_clusters > 0 && s->pairs_opt) {
@@ -1635,7 +1678,7 @@ int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1,
     HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, plan.lds_bytes));
     /* bounce stack: one slice per workgroup of the persistent grid */
     const double stack_bytes = plan.stack_lds_levels >= max_depth ? 16.0
-                             : (double)blocks * (double)block * (double)(max_depth + 1) * RT_STACK_ENTRY_BYTES;
+                             : (double)blocks * (double)block * (double)(max_depth + 1) * RT_STACK_ENTRY_BYTES * stack_entry_quads(s);
     if (stack_bytes > 8.0e9)
         return fail(RT_ERR_CAPACITY, "max_depth too large: the bounce stack would exceed 8 GB of HBM");
     /* the stack (and nothing else) is shared by successive launches of this handle:
@@ -1830,8 +1873,10 @@ int rt_scene_create(const rt_scene_desc *desc, int device, rt_scene **out) {
 int rt_capi_texture_version(void) { return RT_CAPI_TEXTURE_VERSION; }
 
 /* IMAGE TEXTURES (include/rt_capi_texture.h): the images' checks in the header's order, then rt_scene_create's path with them */
-int rt_scene_create_textured(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images, int device,
-                             rt_scene **out) {
+namespace {
+/* rt_scene_create_textured's path; refr: {tf, ior} per object of a refractive scene (REFRACTION), else NULL */
+int create_textured(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
+                    const std::vector<float> *refr_tf, const std::vector<float> *refr_ior, int device, rt_scene **out) {
     if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
     *out = nullptr;
     if (n_images < 0) return fail(RT_ERR_INVALID, "n_images < 0");
@@ -1850,10 +1895,17 @@ int rt_scene_create_textured(const rt_scene_desc *desc, int n_images, const rt_i
     }
     if (total > (uint64_t)RT_MAX_SCENE_TEXELS)
         return fail(RT_ERR_CAPACITY, "more than " + std::to_string(RT_MAX_SCENE_TEXELS) + " texels in the scene's images");
-    if (n_images == 0) return rt_scene_create(desc, device, out);
+    if (n_images == 0 && !refr_tf) return rt_scene_create(desc, device, out);
     rt_scene *s = new (std::nothrow) rt_scene();
     if (!s) return fail(RT_ERR_INVALID, "out of memory");
     int rc = adopt_desc(desc, s, n_images);
+    if (rc == RT_OK && refr_tf) {
+        /* (a refractive scene is packed as an image scene: checkerboards as their 2 x 2 CHECKER images, rt_tables.h) */
+        s->refr_tf = *refr_tf;
+        s->refr_ior = *refr_ior;
+        s->refract_used = true;
+        s->images_used = true;
+    }
     if (rc == RT_OK) {
         for (int k = 0; k < n_images; ++k) {
             const rt_image_texture_desc &im = images[k];
@@ -1864,6 +1916,44 @@ int rt_scene_create_textured(const rt_scene_desc *desc, int n_images, const rt_i
     }
     if (rc) { delete s; return rc; }
     return finish_create(s, device, out);
+}
+} // namespace
+
+int rt_scene_create_textured(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images, int device,
+                             rt_scene **out) {
+    return create_textured(desc, n_images, images, nullptr, nullptr, device, out);
+}
+
+int rt_capi_refract_version(void) { return RT_CAPI_REFRACT_VERSION; }
+
+/* REFRACTION (include/rt_capi_refract.h): the list's checks in the header's order; entries with tf == 0 dropped, none left:
+ * rt_scene_create_textured itself */
+int rt_scene_create_refractive(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
+                               int n_refractive, const rt_refraction_desc *refractive, int device, rt_scene **out) {
+    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
+    *out = nullptr;
+    if (n_refractive < 0) return fail(RT_ERR_INVALID, "n_refractive < 0");
+    if (n_refractive > 0 && !refractive) return fail(RT_ERR_INVALID, "refractive is NULL");
+    const int n = desc->n_objects;
+    std::vector<float> tf(n > 0 ? (size_t)n : 0u, 0.0f), ior(n > 0 ? (size_t)n : 0u, 1.0f);
+    std::vector<char> listed(tf.size(), 0);
+    bool any = false;
+    for (int k = 0; k < n_refractive; ++k) {
+        const rt_refraction_desc &r = refractive[k];
+        const std::string which = "refractive entry " + std::to_string(k) + ": ";
+        if (r.object < 0 || r.object >= n) return fail(RT_ERR_INVALID, which + "object index out of range");
+        if (listed[(size_t)r.object]) return fail(RT_ERR_INVALID, which + "object " + std::to_string(r.object) + " listed twice");
+        listed[(size_t)r.object] = 1;
+        if (desc->objects && desc->objects[r.object].is_light) return fail(RT_ERR_INVALID, which + "a light cannot be refractive");
+        if (std::isnan(r.refractive) || r.refractive < 0.0f) return fail(RT_ERR_INVALID, which + "refractive must be >= 0");
+        if (!(std::isfinite(r.ior) && r.ior > 0.0f)) return fail(RT_ERR_INVALID, which + "ior must be finite and > 0");
+        if (r.refractive == 0.0f) continue;                  /* (ignored) */
+        tf[(size_t)r.object] = r.refractive;
+        ior[(size_t)r.object] = r.ior;
+        any = true;
+    }
+    if (!any) return create_textured(desc, n_images, images, nullptr, nullptr, device, out);
+    return create_textured(desc, n_images, images, &tf, &ior, device, out);
 }
 
 int rt_scene_destroy(rt_scene *s) {
@@ -2008,6 +2098,7 @@ int rt_render_gbuffer_device(rt_scene *s, const rt_camera_desc *cam, int W, int 
 int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
                     float *out_rgb, uint64_t *stats, int n_stats, uint64_t *wave_cycles, int n_wave_cycles) {
     if (!s || !stats || n_stats < 0) return fail(RT_ERR_INVALID, "scene/stats is NULL");
+    if (s->refract_used) return fail(RT_ERR_INVALID, "the counting build does not trace refraction (include/rt_capi_refract.h)");
     if (s->images_used) return fail(RT_ERR_INVALID, "the counting build does not sample image textures (include/rt_capi_texture.h)");
     std::lock_guard<std::mutex> lock(s->mu);
     size_t bytes = 0;
@@ -2042,6 +2133,8 @@ int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0
  * shape (W, H, x0, x1, max_depth, tile shape) start their queues at the row of the longest tile (launch(), LEARNED START ROW). */
 int rt_learn_tile_order(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
+    if (s->refract_used)
+        return fail(RT_ERR_INVALID, "the counting build does not trace refraction, so no tile order is learned (include/rt_capi_refract.h)");
     if (s->images_used)
         return fail(RT_ERR_INVALID, "the counting build does not sample image textures, so no tile order is learned (include/rt_capi_texture.h)");
     if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 >= x1) return fail(RT_ERR_INVALID, "need 0 <= x0 < x1 <= W, W,H > 0");

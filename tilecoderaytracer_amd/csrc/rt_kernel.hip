@@ -1844,6 +1844,50 @@ __device__ __forceinline__ size_t hbm_stack_entry(const RtParams &p, const int l
     return (size_t)(row * (unsigned int)here(p.stack_stride) + threadIdx.x);
 }
 
+/* REFRACTION (include/rt_capi_refract.h; the *_refract kernels only).  A level's stack entry is three quads (rt_tables.h,
+ * RT_REFRACT_ENTRY_QUADS): quad q of level j is row 3 j + q, in LDS below p.stack_lds_levels levels, else in this workgroup's
+ * HBM slice of 3 (max_depth + 1) rows. */
+__device__ __forceinline__ float4 *refract_entry(const RtParams &p, float4 *wlds, float4 *bounce_stack, const int level, const int q) {
+    const int row = level * RT_REFRACT_ENTRY_QUADS + q;
+    if (level < p.stack_lds_levels) return wlds + here(p.stack_off) + row * here(p.stack_stride) + threadIdx.x;
+    const unsigned int r = (unsigned int)here((int)blockIdx.x) * (unsigned int)((p.max_depth + 1) * RT_REFRACT_ENTRY_QUADS) + (unsigned int)row;
+    return bounce_stack + (size_t)(r * (unsigned int)here(p.stack_stride) + threadIdx.x);
+}
+
+/* The transmitted child of a shaded hit on a refractive object (include/rt_capi_refract.h, with the oracle's v_* operations in
+ * their order): a sphere hit from outside (t >= 0) is crossed along one chord, a plane is a thin pane.  P, N: the record's
+ * point and normal; g: the object's geometry; ior: the sphere interior's.  false: no child. */
+__device__ __forceinline__ bool transmitted_ray(const int kind, const float4 *g, const float t, const V3 o, const V3 d,
+                                                const V3 P, const V3 N, const float ior, V3 *o_out, V3 *d_out) {
+    if (kind == RT_KIND_SPHERE) {
+        if (!(t >= 0.0f)) return false;                              /* inside hit: no child */
+        const V3 centre = xyz(g[0]);
+        const V3 Q = sub3(P, centre);
+        const float eta = 1.0f / ior;
+        const float c1 = -dot3(N, d);
+        const float k1 = 1.0f - (eta * eta) * (1.0f - c1 * c1);
+        if (k1 < 0.0f) return false;
+        const V3 T1 = normalize3(add3(scale3(d, eta), scale3(N, eta * c1 - sqrtf(k1))));
+        const float s = -2.0f * dot3(T1, Q);
+        if (!(s > 0.0f)) return false;
+        const V3 P2 = add3(P, scale3(T1, s));
+        const V3 N2 = normalize3(sub3(P2, centre));
+        const float c2 = dot3(N2, T1);
+        const float k2 = 1.0f - (ior * ior) * (1.0f - c2 * c2);
+        if (k2 < 0.0f) return false;
+        const V3 T2 = sub3(scale3(T1, ior), scale3(N2, ior * c2 - sqrtf(k2)));
+        *o_out = add3(P2, scale3(N2, (float)1E-3));
+        *d_out = normalize3(T2);
+        return true;
+    }
+    const V3 q0 = xyz(g[0]), q4 = xyz(g[4]);
+    const V3 ip = add3(scale3(d, t), o);
+    const V3 other = (dot3(q0, d) < 0) ? q4 : q0;                     /* the normal the record did not choose */
+    *o_out = add3(ip, scale3(other, (float)1E-3));
+    *d_out = d;
+    return true;
+}
+
 /* G-BUFFER (include/rt_capi_gbuffer.h): the rt_hit record of a camera ray's level-0 winner, built from what phase 1 of
  * render_tile() has at hand -- Scene index idx at distance t, the point P, the normal N before the CollisionObject ctor
  * re-normalises it, the texture selector, the material (its number, its second quad's bits) and the kind -- with hits_tile()'s
@@ -1890,8 +1934,12 @@ __device__ __forceinline__ void gbuffer_store(const RtParams &p, const int sx, c
  * p.rays instead of made by the camera.  kGbuffer: a camera tile that also stores each pixel's rt_hit record of its level-0
  * winner at p.gbuffer_hits (include/rt_capi_gbuffer.h); the colours are the plain tile's.  kImages: planes may sample image
  * textures (include/rt_capi_texture.h): a texel selector is a texel's index, and a stack entry keeps it above 12 bits of object
- * index (rt_tables.h, RT_IMAGE_SEL_SHIFT). */
-template <bool kStats, int kMode, bool kSsaa = false, bool kRays = false, bool kGbuffer = false, bool kImages = false>
+ * index (rt_tables.h, RT_IMAGE_SEL_SHIFT).  kRefract: refractive objects (include/rt_capi_refract.h, always with kImages): the
+ * bounce chain becomes a per-lane depth-first walk of the ray tree -- each step traces one ray per live lane, whatever its
+ * level; a node with a reflected and a transmitted child keeps the transmitted ray on its stack entry while the reflected
+ * subtree is walked. */
+template <bool kStats, int kMode, bool kSsaa = false, bool kRays = false, bool kGbuffer = false, bool kImages = false,
+          bool kRefract = false>
 __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds, float4 *wlds, float4 *help_rays,
                                             const uint32_t *__restrict__ ctl_words, float *__restrict__ out,
                                             float4 *__restrict__ bounce_stack, unsigned long long *__restrict__ stats_out,
@@ -1962,9 +2010,20 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
 #if RT_GBUFFER_STORE_LATE
     [[maybe_unused]] HitQuads late_record = gbuffer_miss();
 #endif
-    for (int level = 0; level <= p.max_depth; ++level) {
+    /* REFRACTION: the level of this lane's ray (the loop counter below counts steps there), and the refraction rows' offset
+     * (rt_tables.h: the quad before the materials holds it) */
+    [[maybe_unused]] int lvl = 0;
+    [[maybe_unused]] int refr_off = 0;
+    if constexpr (kRefract) refr_off = __builtin_amdgcn_readfirstlane(__float_as_int(lds[p.mat_off - 1].x));
+    for (int level = 0; kRefract || level <= p.max_depth; ++level) {
         if (__ballot(alive) == 0ull) break;
         levels = level + 1;
+        /* REFRACTION: after the first step the live rays start anywhere -- at reflection points, at the far side of a glass
+         * sphere, behind a pane or at a node popped off the stack: the scans bound the origins of the rays live now */
+        if constexpr (kRefract) {
+            if (level > 0) have_box = false;
+        }
+        [[maybe_unused]] const bool traced = alive;      /* REFRACTION: this lane traces a ray in this step */
         if (level >= 1 && level <= 3 && p.tile_prio != 0) {       /* OLD TILES FIRST */
             if (level == 1) __builtin_amdgcn_s_setprio(1);
             else if (level == 2) __builtin_amdgcn_s_setprio(2);
@@ -2179,6 +2238,80 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
         /* ---- phase 3 (per lane): reflect or finish, :595-604 ---- */
         st_cycles(st, ST_CYCLES_LIGHTS, t_lights);
         const unsigned long long t_reflect = st_clock<kStats>();
+        if constexpr (kRefract) {
+            if (shade) {
+                /* the node's children: reflected (rf > 0), transmitted (tf > 0 and the geometry gives one) */
+                const uint32_t info = lds_u32[p.objinfo_off * 4 + idx];
+                const int mat = (int)(info >> 20);
+                const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
+                const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
+                const float4 r = lds[refr_off + mat];                    /* {tf, ior, 0, 0} */
+                V3 to = o, td = d;
+                const bool has_t = r.x > 0.0f &&
+                    transmitted_ray((int)((info >> 16) & 3u), lds + (info & 0xFFFFu), t, o, d, P, N, r.y, &to, &td);
+                const bool has_r = m1.y > 0.0f;
+                if (lvl == p.max_depth) {
+                    /* the last level's children are never traced: C_{k+1} = NULL_COLOR, folded in here in the formula's order */
+                    const V3 oc = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), texsel);
+                    if (has_r) C = add3(C, mk(null_color.x * m1.y * oc.x, null_color.y * m1.y * oc.y, null_color.z * m1.y * oc.z));
+                    if (has_t) C = add3(C, mk(null_color.x * r.x * oc.x, null_color.y * r.x * oc.y, null_color.z * r.x * oc.z));
+                    alive = false;
+                } else if (has_r || has_t) {
+                    /* entry: {local.rgb, bits}, {transmitted origin, state}, {transmitted direction, -}; state 0: the reflected
+                     * child is walked, 1: the transmitted one, 2: the reflected one with the transmitted one pending */
+                    const int state = has_r ? (has_t ? 2 : 0) : 1;
+                    *refract_entry(p, wlds, bounce_stack, lvl, 0) =
+                        make_float4(C.x, C.y, C.z, __uint_as_float((uint32_t)idx | ((uint32_t)texsel << kSelShift)));
+                    if (state != 0) {
+                        *refract_entry(p, wlds, bounce_stack, lvl, 1) = make_float4(to.x, to.y, to.z, __int_as_float(state));
+                        if (state == 2) *refract_entry(p, wlds, bounce_stack, lvl, 2) = make_float4(td.x, td.y, td.z, 0.0f);
+                    } else {
+                        refract_entry(p, wlds, bounce_stack, lvl, 1)->w = __int_as_float(0);
+                    }
+                    if (has_r) {
+                        const float n_dot_incoming = dot3(N, d);         /* src/SceneObject.h:65 */
+                        const V3 reflected = mk(-2 * N.x * n_dot_incoming + d.x,
+                                                -2 * N.y * n_dot_incoming + d.y,
+                                                -2 * N.z * n_dot_incoming + d.z);
+                        o = P;
+                        d = normalize3(reflected);
+                    } else {
+                        o = to;
+                        d = td;
+                    }
+                    lvl += 1;
+                } else {
+                    alive = false;                               /* C already holds final_color */
+                }
+            }
+            /* a finished node (a miss, a light, a leaf of the tree): combine up the stack to the nearest pending transmitted
+             * child and trace it next, or -- the root done -- keep the pixel's colour in C */
+            if (traced && !alive) {
+                while (lvl > 0) {
+                    --lvl;
+                    const float4 e = *refract_entry(p, wlds, bounce_stack, lvl, 0);
+                    const float4 e1 = *refract_entry(p, wlds, bounce_stack, lvl, 1);
+                    const uint32_t bits = __float_as_uint(e.w);
+                    const int mat = (int)(lds_u32[p.objinfo_off * 4 + (bits & ((1u << kSelShift) - 1u))] >> 20);
+                    const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
+                    const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
+                    const int state = __float_as_int(e1.w);
+                    const float f = state == 1 ? lds[refr_off + mat].x : m1.y;
+                    const V3 oc = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), (int)(bits >> kSelShift));
+                    C = add3(mk(e.x, e.y, e.z), mk(C.x * f * oc.x, C.y * f * oc.y, C.z * f * oc.z));
+                    if (state == 2) {
+                        /* the reflected subtree is done: the partial sum stays, the transmitted child is walked next */
+                        *refract_entry(p, wlds, bounce_stack, lvl, 0) = make_float4(C.x, C.y, C.z, e.w);
+                        refract_entry(p, wlds, bounce_stack, lvl, 1)->w = __int_as_float(1);
+                        o = mk(e1.x, e1.y, e1.z);
+                        d = xyz(*refract_entry(p, wlds, bounce_stack, lvl, 2));
+                        lvl += 1;
+                        alive = true;
+                        break;
+                    }
+                }
+            }
+        } else
         if (shade) {
             const int mat = (int)(lds_u32[p.objinfo_off * 4 + idx] >> 20);
             const float reflective_factor = lds[p.mat_off + mat * RT_MAT_QUADS + 1].y;
@@ -2223,6 +2356,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
     if (ask_head != nullptr && lane == 0) next_pop = (int)atomicAdd(ask_head, 1u);
     /* unwind: final_k = local_k + (rf_k * C_{k+1}) * oc_k, inside-out (:601) */
     for (int k = levels - 1; k >= 0; --k) {
+        if (kRefract) break;                                 /* (REFRACTION: combined as the walk went) */
         if (k < top) {
             float4 e;
             if (k < p.stack_lds_levels) e = wlds[here(p.stack_off) + k * here(p.stack_stride) + threadIdx.x];
@@ -2468,7 +2602,7 @@ __device__ RT_SCAN_INLINE unsigned int queues_with_tiles(const unsigned int *til
 }
 
 template <bool kStats, bool kGlobalTables = false, bool kClusters = false, bool kRoomy = false, bool kFast = false, bool kSsaa = false,
-          bool kRays = false, int kQuery = RT_QUERY_NONE, bool kGbuffer = false, bool kImages = false>
+          bool kRays = false, int kQuery = RT_QUERY_NONE, bool kGbuffer = false, bool kImages = false, bool kRefract = false>
 __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__restrict__ image,
                                             float *__restrict__ out, unsigned int *__restrict__ tile_counter,
                                             float4 *__restrict__ bounce_stack,
@@ -2680,7 +2814,7 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
         constexpr int kMode = kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0);
         if constexpr (kQuery == RT_QUERY_HITS) hits_tile<kMode, kImages>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
         else if constexpr (kQuery == RT_QUERY_OCCLUDED) occluded_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
-        else render_tile<kStats, kMode, kSsaa, kRays, kGbuffer, kImages>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
+        else render_tile<kStats, kMode, kSsaa, kRays, kGbuffer, kImages, kRefract>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
                                                                 my_xcc, steal, next_pop, ask_head);
 #ifdef RT_TIMELINE
         if (p.timeline != 0ull && lane == 0) {                   /* ... when it was done, and by whom */

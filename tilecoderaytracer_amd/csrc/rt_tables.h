@@ -30,6 +30,8 @@
  *              CHECKER image: {width, height, bits(texels_w), bits(texels_h)}, {bits(wrap), 0, bits(the image's block in the
  *              texel buffer: low word), bits(high word)}; a block is texels_w x texels_h rgb fp32 texels, then the column
  *              bounds b_0 .. b_(texels_w - 1), then the row bounds (rt_kernel.hip, image_cell())
+ *   refraction (scenes with refractive objects only: include/rt_capi_refract.h) one header quad right before the materials,
+ *              {bits(offset of the rows), 0, 0, 0}, and behind the textures one quad per material row: {tf, ior, 0, 0}
  *   objinfo    one u32 per object (4 per quad):
  *                bits 0-15 geometry offset (quads), 16-17 kind, 20-31 material row
  *
@@ -130,6 +132,14 @@ enum { RT_DESK_STATE = 0, RT_DESK_CURSOR, RT_DESK_INSIDE, RT_DESK_FINISHED, RT_D
  * scene's texel limit).  A bounce-stack entry is {local.rgb, bits(object index | texsel << 12)}: 12 bits of object index
  * (RT_MAX_OBJECTS), 20 of selector. */
 #define RT_IMAGE_SEL_SHIFT 12
+
+/* REFRACTION (include/rt_capi_refract.h; the *_refract kernels only, whose scenes are always packed as image scenes).  One more
+ * section, one quad per material row: {tf, ior, 0, 0}; its quad offset is bits of the x word of the quad right before the
+ * materials.  A level's bounce-stack entry is three quads: {local or partial.rgb, bits(object index | texsel << 12)},
+ * {transmitted origin.xyz, bits(state)}, {transmitted direction.xyz, 0}; state 0: the reflected child is walked, 1: the
+ * transmitted child, 2: the reflected child with the transmitted one pending. */
+#define RT_REFR_QUADS 1
+#define RT_REFRACT_ENTRY_QUADS 3
 
 #define RT_PRIMARY_ITEMS 64          /* scenes with more FAST items than this have no PRIMARY table */
 

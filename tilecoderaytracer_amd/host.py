@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .capi import LIB_DIR, RtCameraDesc, RtImageTextureDesc, RtSceneDesc, F3
+from .capi import LIB_DIR, RtCameraDesc, RtImageTextureDesc, RtRefractionDesc, RtSceneDesc, F3
 
 _hlib = None
 
@@ -45,6 +45,7 @@ def load_host_library():
     lib.rth_set_diffuse.argtypes = [vp, i, f]
     lib.rth_set_specular.argtypes = [vp, i, f]
     lib.rth_set_reflective.argtypes = [vp, i, f]
+    lib.rth_set_refraction.argtypes = [vp, i, f, f]
     lib.rth_set_checkerboard.argtypes = [vp, i, pf, pf, f, f]
     lib.rth_set_image_texture.argtypes = [vp, i, i, i, vp, f, f, i]
     lib.rth_set_light.argtypes = [vp, i]
@@ -56,6 +57,8 @@ def load_host_library():
     lib.rth_scene_desc.restype = C.POINTER(RtSceneDesc)
     lib.rth_scene_images.argtypes = [vp, C.POINTER(C.POINTER(RtImageTextureDesc))]
     lib.rth_scene_images.restype = i
+    lib.rth_scene_refractions.argtypes = [vp, C.POINTER(C.POINTER(RtRefractionDesc))]
+    lib.rth_scene_refractions.restype = i
     lib.rth_camera_desc.argtypes = [vp]
     lib.rth_camera_desc.restype = C.POINTER(RtCameraDesc)
     lib.rth_write_screen_txt.argtypes = [C.c_char_p, i, i, vp, C.c_double, C.c_double]
@@ -154,6 +157,9 @@ class HostScene:
     def set_diffuse(self, idx, f): self._ok(self._lib.rth_set_diffuse(self._h, idx, f))
     def set_specular(self, idx, f): self._ok(self._lib.rth_set_specular(self._h, idx, f))
     def set_reflective(self, idx, f): self._ok(self._lib.rth_set_reflective(self._h, idx, f))
+    def set_refraction(self, idx, factor, ior=1.0):
+        """ObjMaterial::setRefractiveFactor(factor) and setRefractiveIndex(ior) (include/rt_capi_refract.h)"""
+        self._ok(self._lib.rth_set_refraction(self._h, idx, factor, ior))
     def set_checkerboard(self, idx, light, dark, w, h):
         self._ok(self._lib.rth_set_checkerboard(self._h, idx, _v(light), _v(dark), w, h))
     def set_image_texture(self, idx, texels, w, h, wrap):
@@ -185,6 +191,13 @@ class HostScene:
         """the flattened scene's images (texture indices n_textures + k): (count, pointer to RtImageTextureDesc or None)"""
         ptr = C.POINTER(RtImageTextureDesc)()
         n = self._lib.rth_scene_images(self._h, C.byref(ptr))
+        return n, (ptr if n else None)
+
+    @property
+    def refractions(self):
+        """the flattened scene's refractive objects: (count, pointer to RtRefractionDesc or None)"""
+        ptr = C.POINTER(RtRefractionDesc)()
+        n = self._lib.rth_scene_refractions(self._h, C.byref(ptr))
         return n, (ptr if n else None)
 
     @property

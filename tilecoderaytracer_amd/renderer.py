@@ -23,6 +23,14 @@ def image_descs(images):
     return arrays, descs
 
 
+def refraction_descs(refractive):
+    """(object, tf, ior) tuples -> an RtRefractionDesc array (include/rt_capi_refract.h)."""
+    descs = (capi.RtRefractionDesc * max(len(refractive), 1))()
+    for k, (obj, tf, ior) in enumerate(refractive):
+        descs[k] = capi.RtRefractionDesc(obj, tf, ior)
+    return descs
+
+
 class Renderer:
     """Owns an ``rt_scene`` (device tables for one HostScene on one GPU)."""
 
@@ -31,23 +39,36 @@ class Renderer:
         self._host = host_scene          # keeps the desc arrays alive
         self._scene = C.c_void_p()
         n_images, images = host_scene.images        # the scene's Texture_Image objects (include/rt_capi_texture.h)
-        if n_images:
+        n_refr, refr = host_scene.refractions       # its refractive materials (include/rt_capi_refract.h)
+        if n_refr:
+            capi.check(self._lib.rt_scene_create_refractive(host_scene.desc, n_images, images, n_refr, refr, device,
+                                                            C.byref(self._scene)))
+        elif n_images:
             capi.check(self._lib.rt_scene_create_textured(host_scene.desc, n_images, images, device, C.byref(self._scene)))
         else:
             capi.check(self._lib.rt_scene_create(host_scene.desc, device, C.byref(self._scene)))
         self._cam = host_scene.camera
 
     @classmethod
-    def from_desc(cls, desc, camera, device=0, keepalive=None, images=None):
+    def from_desc(cls, desc, camera, device=0, keepalive=None, images=None, refractive=None):
         """Build from raw RtSceneDesc / RtCameraDesc (tests with hand-made tables).  images (include/rt_capi_texture.h): a
         list of (texels, width, height, wrap) -- texels a float32 (texels_h, texels_w, 3) array, texels[j, i] texel (i, j),
         width / height the world size of one copy, wrap RT_TEX_WRAP_* -- that texture indices n_textures + k name.  With
-        images (even an empty list) the scene is made by rt_scene_create_textured, else by rt_scene_create."""
+        images (even an empty list) the scene is made by rt_scene_create_textured, else by rt_scene_create.  refractive
+        (include/rt_capi_refract.h): a list of (object, tf, ior); with it (even an empty list) the scene is made by
+        rt_scene_create_refractive, with the images if any."""
         self = cls.__new__(cls)
         self._lib = capi.load_library()
         self._host = keepalive
         self._scene = C.c_void_p()
-        if images is None:
+        if refractive is not None:
+            arrays, descs = image_descs(images or [])
+            rdescs = refraction_descs(refractive)
+            self._images = (arrays, descs, rdescs)
+            capi.check(self._lib.rt_scene_create_refractive(
+                C.byref(desc), len(images or []), descs if images else None, len(refractive),
+                rdescs if len(refractive) else None, device, C.byref(self._scene)))
+        elif images is None:
             capi.check(self._lib.rt_scene_create(C.byref(desc), device, C.byref(self._scene)))
         else:
             arrays, descs = image_descs(images)
