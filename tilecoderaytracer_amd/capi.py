@@ -48,6 +48,11 @@ class RtRefractionDesc(C.Structure):
     _fields_ = [("object", C.c_int32), ("refractive", C.c_float), ("ior", C.c_float)]
 
 
+class RtAreaLightDesc(C.Structure):
+    """include/rt_capi_soft.h: an area light -- Scene index of a light, n (n x n samples), the disc's radius."""
+    _fields_ = [("object", C.c_int32), ("samples", C.c_int32), ("radius", C.c_float)]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [
         ("n_objects", C.c_int32), ("objects", C.POINTER(RtObjectDesc)),
@@ -193,6 +198,14 @@ def load_library():
         lib.rt_scene_create_refractive.argtypes = [C.POINTER(RtSceneDesc), i, C.POINTER(RtImageTextureDesc), i,
                                                    C.POINTER(RtRefractionDesc), i, C.POINTER(vp)]
         lib.rt_scene_create_refractive.restype = i
+    # include/rt_capi_soft.h (likewise absent from older builds)
+    if hasattr(lib, "rt_scene_create_soft"):
+        lib.rt_capi_soft_version.restype = i
+        lib.rt_scene_create_soft.argtypes = [C.POINTER(RtSceneDesc), i, C.POINTER(RtImageTextureDesc), i,
+                                             C.POINTER(RtRefractionDesc), i, C.POINTER(RtAreaLightDesc), i, C.POINTER(vp)]
+        lib.rt_scene_create_soft.restype = i
+        lib.rt_scene_set_shadow_seed.argtypes = [vp, C.c_uint32]
+        lib.rt_scene_set_shadow_seed.restype = i
     for name in ("rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_render",
                  "rt_render_device", "rt_render_multi", "rt_render_stats", "rt_learn_tile_order", "rt_get_timing", "rt_reset_timing",
                  "rt_get_launch_info", "rt_set_option", "rt_chunk_bounds", "rt_multi_create", "rt_multi_render",

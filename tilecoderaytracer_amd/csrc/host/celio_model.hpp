@@ -28,6 +28,7 @@
 #include "../../../include/rt_capi.h"
 #include "../../../include/rt_capi_texture.h"
 #include "../../../include/rt_capi_refract.h"
+#include "../../../include/rt_capi_soft.h"
 
 namespace CelioRayTracer {
 
@@ -204,10 +205,11 @@ private:
 /* src/SceneObject.h:26-200, src/SceneObject.cpp:9-27 */
 class SceneObject {
 public:
-    SceneObject() : origin(), isaLightSource(false), intensity(1.0), my_object_index(0) {
+    SceneObject() : origin(), isaLightSource(false), intensity(1.0), my_object_index(0), area_samples(0), area_radius(0.0f) {
         myMaterial.setDiffuseFactor(0.25f);     /* only the default ctor lowers diffuse */
     }
-    explicit SceneObject(vector3d _o) : origin(_o), isaLightSource(false), intensity(1.0), my_object_index(0) {}
+    explicit SceneObject(vector3d _o)
+        : origin(_o), isaLightSource(false), intensity(1.0), my_object_index(0), area_samples(0), area_radius(0.0f) {}
     virtual ~SceneObject() {}
 
     /* replaces `virtual CollisionObject* collision(Ray*)` (src/SceneObject.h:166):
@@ -225,6 +227,15 @@ public:
     bool checkIsaLightSource() const { return isaLightSource; }
     void setIntensity(sdecimal32 d) { intensity = d; }
     sdecimal32 getIntensity() const { return intensity; }
+    /* not in the reference: sample this light as an area light (include/rt_capi_soft.h), n x n samples on a disc of the given
+     * radius -- a negative radius: the object's own (a sphere's radius, 0 for a plane); samples 0 or radius 0: a hard light */
+    void setAreaLight(int samples, float radius = -1.0f) {
+        area_samples = samples;
+        area_radius = radius < 0.0f ? ownRadius() : radius;
+    }
+    int getAreaSamples() const { return area_samples; }
+    float getAreaRadius() const { return area_radius; }
+    virtual float ownRadius() const { return 0.0f; }
 
 protected:
     void describe_base(rt_object_desc &out, int kind) const {
@@ -244,6 +255,8 @@ protected:
     bool isaLightSource;
     sdecimal32 intensity;
     int my_object_index;
+    int area_samples;
+    float area_radius;
 };
 
 /* src/SceneSphere.h:10-20, src/SceneSphere.cpp:38-48 */
@@ -257,6 +270,7 @@ public:
         out.radius = radius;
         out.radius_squared = radius_squared;
     }
+    float ownRadius() const override { return radius; }
 private:
     sdecimal32 radius, radius_squared;
 };
@@ -387,15 +401,21 @@ private:
 /* The flattened scene: owns the arrays an rt_scene_desc points into.  images: the bitmap textures
  * (include/rt_capi_texture.h), texture indices desc.n_textures + k; their texels stay owned by the Texture_Image objects.
  * refractions: one entry per non-light object whose material has refractive_factor > 0 (include/rt_capi_refract.h).
- * create(): rt_scene_create_refractive when there are refractions, else rt_scene_create_textured when there are images,
- * rt_scene_create otherwise. */
+ * area_lights: one entry per light made an area light with samples > 0 and radius > 0 (include/rt_capi_soft.h).
+ * create(): rt_scene_create_soft when there are area lights, else rt_scene_create_refractive when there are refractions, else
+ * rt_scene_create_textured when there are images, rt_scene_create otherwise. */
 struct FlatScene {
     std::vector<rt_object_desc> objects;
     std::vector<rt_texture_desc> textures;
     std::vector<rt_image_texture_desc> images;
     std::vector<rt_refraction_desc> refractions;
+    std::vector<rt_area_light_desc> area_lights;
     rt_scene_desc desc;
     int create(int device, rt_scene **out) const {
+        if (!area_lights.empty())
+            return rt_scene_create_soft(&desc, (int)images.size(), images.empty() ? nullptr : images.data(),
+                                        (int)refractions.size(), refractions.empty() ? nullptr : refractions.data(),
+                                        (int)area_lights.size(), area_lights.data(), device, out);
         if (!refractions.empty())
             return rt_scene_create_refractive(&desc, (int)images.size(), images.empty() ? nullptr : images.data(),
                                               (int)refractions.size(), refractions.data(), device, out);
@@ -474,6 +494,12 @@ public:
             const ObjMaterial *m = objects[(size_t)i]->getMaterial();
             if (!out.objects[(size_t)i].is_light && m->getRefractiveFactor() > 0.0f)
                 out.refractions.push_back(rt_refraction_desc{(int32_t)i, m->getRefractiveFactor(), m->getRefractiveIndex()});
+        }
+        out.area_lights.clear();
+        for (int i = 0; i < object_count; ++i) {         /* area lights (include/rt_capi_soft.h) */
+            const SceneObject *o = objects[(size_t)i];
+            if (out.objects[(size_t)i].is_light && o->getAreaSamples() > 0 && o->getAreaRadius() > 0.0f)
+                out.area_lights.push_back(rt_area_light_desc{(int32_t)i, (int32_t)o->getAreaSamples(), o->getAreaRadius()});
         }
         out.desc.n_objects = object_count;
         out.desc.objects = out.objects.empty() ? nullptr : out.objects.data();

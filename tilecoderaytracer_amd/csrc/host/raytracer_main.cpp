@@ -41,7 +41,8 @@ static std::vector<float> pixels;          /* pixels[x][z] as packed fp32 RGB */
 static int usage(const char *argv0) {
     std::fprintf(stderr,
                  "usage: %s [--width W] [--height H] [--depth D] [--scene 1|2|grid:N[:noshadow]]\n"
-                 "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE] [--glass I:TF:IOR ...]\n", argv0);
+                 "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE] [--glass I:TF:IOR ...]\n"
+                 "          [--soft I:N[:R] ...]\n", argv0);
     return 1;
 }
 
@@ -50,6 +51,7 @@ int main(int argc, char **argv) {
     bool write_txt = true;
     std::string scene_name = "1", out_path = "raytracer_screen.txt", hits_path;
     std::vector<std::string> glass;              /* --glass I:TF:IOR: object I refractive (include/rt_capi_refract.h) */
+    std::vector<std::string> soft;               /* --soft I:N[:R]: light I an area light, N x N samples, radius R (include/rt_capi_soft.h) */
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](int &dst) { if (i + 1 >= argc) return false; dst = std::atoi(argv[++i]); return true; };
@@ -62,6 +64,7 @@ int main(int argc, char **argv) {
         else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
         else if (a == "--hits" && i + 1 < argc) hits_path = argv[++i];
         else if (a == "--glass" && i + 1 < argc) glass.push_back(argv[++i]);
+        else if (a == "--soft" && i + 1 < argc) soft.push_back(argv[++i]);
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
@@ -103,6 +106,15 @@ int main(int argc, char **argv) {
         my_scene.getObject(idx)->getMaterial()->setRefractiveIndex(ior);
     }
 
+    for (const std::string &g : soft) {
+        int idx = -1, n = 0;
+        float r = -1.0f;                         /* (no R: the light's own radius) */
+        const int got = std::sscanf(g.c_str(), "%d:%d:%f", &idx, &n, &r);
+        if (got < 2 || idx < 0 || idx >= my_scene.getObjectCount() || !my_scene.getObject(idx)->checkIsaLightSource() || n < 1)
+            return usage(argv[0]);
+        my_scene.getObject(idx)->setAreaLight(n, r);
+    }
+
     FlatScene flat;
     rt_camera_desc cam;
     my_scene.flatten(flat);
@@ -113,6 +125,10 @@ int main(int argc, char **argv) {
     }
     if (!flat.refractions.empty() && gpus > 1) {    /* nor refraction (include/rt_capi_refract.h) */
         std::fprintf(stderr, "refraction renders on one GPU\n");
+        return 1;
+    }
+    if (!soft.empty() && gpus > 1) {                /* nor area lights (include/rt_capi_soft.h) */
+        std::fprintf(stderr, "soft shadows render on one GPU\n");
         return 1;
     }
     pixels.assign((size_t)W * (size_t)H * 3, 0.0f);

@@ -129,6 +129,13 @@ int rth_set_refraction(rth_scene *s, int idx, float factor, float ior) {
     s->dirty = true;
     return 0;
 }
+int rth_set_area_light(rth_scene *s, int idx, int samples, float radius) {
+    SceneObject *o = object_at(s, idx);
+    if (!o) return 1;
+    o->setAreaLight(samples, radius);
+    s->dirty = true;
+    return 0;
+}
 int rth_set_checkerboard(rth_scene *s, int idx, const float light[3], const float dark[3], float w, float h) {
     SceneObject *o = object_at(s, idx);
     if (!o || !light || !dark) return 1;
@@ -189,6 +196,13 @@ int rth_scene_refractions(rth_scene *s, const rt_refraction_desc **refractions) 
     refresh(s);
     *refractions = s->flat.refractions.empty() ? nullptr : s->flat.refractions.data();
     return (int)s->flat.refractions.size();
+}
+
+int rth_scene_area_lights(rth_scene *s, const rt_area_light_desc **area_lights) {
+    if (!s || !area_lights) return 0;
+    refresh(s);
+    *area_lights = s->flat.area_lights.empty() ? nullptr : s->flat.area_lights.data();
+    return (int)s->flat.area_lights.size();
 }
 
 int rth_scene_images(rth_scene *s, const rt_image_texture_desc **images) {

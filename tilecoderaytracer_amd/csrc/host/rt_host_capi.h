@@ -12,6 +12,7 @@
 #include "../../../include/rt_capi.h"
 #include "../../../include/rt_capi_texture.h"
 #include "../../../include/rt_capi_refract.h"
+#include "../../../include/rt_capi_soft.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -40,6 +41,8 @@ int rth_set_specular(rth_scene *s, int idx, float f);
 int rth_set_reflective(rth_scene *s, int idx, float f);
 /* ObjMaterial::setRefractiveFactor and setRefractiveIndex (include/rt_capi_refract.h) */
 int rth_set_refraction(rth_scene *s, int idx, float factor, float ior);
+/* SceneObject::setAreaLight (include/rt_capi_soft.h): n x n samples on a disc of the radius (< 0: the object's own) */
+int rth_set_area_light(rth_scene *s, int idx, int samples, float radius);
 int rth_set_checkerboard(rth_scene *s, int idx, const float light[3], const float dark[3], float w, float h);
 /* a Texture_Image (include/rt_capi_texture.h): texels_w x texels_h fp32 rgb texels, copied; 1 on a bad argument */
 int rth_set_image_texture(rth_scene *s, int idx, int texels_w, int texels_h, const float *texels, float w, float h, int wrap);
@@ -56,6 +59,8 @@ const rt_camera_desc *rth_camera_desc(rth_scene *s);
 int rth_scene_images(rth_scene *s, const rt_image_texture_desc **images);
 /* the flattened scene's refractive objects: their count, *refractions set to the array (NULL if none) */
 int rth_scene_refractions(rth_scene *s, const rt_refraction_desc **refractions);
+/* the flattened scene's area lights: their count, *area_lights set to the array (NULL if none) */
+int rth_scene_area_lights(rth_scene *s, const rt_area_light_desc **area_lights);
 
 /* byte-exact raytracer_screen.txt (src/RayTracer.cpp:2022-2061, 1574-1626) */
 int rth_write_screen_txt(const char *path, int W, int H, const float *rgb,

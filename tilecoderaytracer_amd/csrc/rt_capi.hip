@@ -23,6 +23,7 @@
 #include "../../include/rt_capi_ssaa.h"
 #include "../../include/rt_capi_texture.h"
 #include "../../include/rt_capi_refract.h"
+#include "../../include/rt_capi_soft.h"
 #include "../../include/rt_capi_tuning.h"
 #include "rt_tables.h"
 
@@ -87,6 +88,25 @@ RT_DECLARE_REFRACT_KERNELS();
 RT_DECLARE_REFRACT_KERNELS(_ssaa);
 RT_DECLARE_REFRACT_KERNELS(_rays);
 RT_DECLARE_REFRACT_KERNELS(_gbuffer);
+/* ... with area lights (rt_kernel_soft.hip): the *_soft and *_refract_soft siblings; one more argument, the sampling seed */
+#define RT_DECLARE_SOFT_KERNEL(name)                                                                              \
+    extern "C" __global__ void name(const RtParams p, const float4 *__restrict__ image, float *__restrict__ out, \
+                                    unsigned int *__restrict__ tile_counter, float4 *__restrict__ bounce_stack,  \
+                                    unsigned int *__restrict__ help_area, const uint32_t shadow_seed)
+#define RT_DECLARE_SOFT_KERNELS(suffix)                                   \
+    RT_DECLARE_SOFT_KERNEL(rt_render_kernel##suffix);                      \
+    RT_DECLARE_SOFT_KERNEL(rt_render_kernel_items##suffix);                \
+    RT_DECLARE_SOFT_KERNEL(rt_render_kernel_large##suffix);                \
+    RT_DECLARE_SOFT_KERNEL(rt_render_kernel_clusters##suffix);             \
+    RT_DECLARE_SOFT_KERNEL(rt_render_kernel_clusters_wide##suffix)
+RT_DECLARE_SOFT_KERNELS(_soft);
+RT_DECLARE_SOFT_KERNELS(_ssaa_soft);
+RT_DECLARE_SOFT_KERNELS(_rays_soft);
+RT_DECLARE_SOFT_KERNELS(_gbuffer_soft);
+RT_DECLARE_SOFT_KERNELS(_refract_soft);
+RT_DECLARE_SOFT_KERNELS(_ssaa_refract_soft);
+RT_DECLARE_SOFT_KERNELS(_rays_refract_soft);
+RT_DECLARE_SOFT_KERNELS(_gbuffer_refract_soft);
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_stats);      /* the counting builds */
 RT_DECLARE_STATS_KERNEL(rt_render_kernel_fast_stats);
 
@@ -142,6 +162,13 @@ struct rt_scene {
      * packed as an image scene with a refraction section (rt_tables.h) and the *_refract kernels run */
     std::vector<float> refr_tf, refr_ior;
     bool refract_used = false;
+    /* SOFT SHADOWS (include/rt_capi_soft.h): per object {n, r} ({1, 0}: a hard light, or not a light); soft_used: some r > 0 --
+     * the scene is then packed as an image scene with an area-light section (rt_tables.h) and the *_soft kernels run, each
+     * launch with shadow_seed (rt_scene_set_shadow_seed) */
+    std::vector<int> soft_n;
+    std::vector<float> soft_r;
+    bool soft_used = false;
+    uint32_t shadow_seed = 0u;
     int shadow_begin = 0, shadow_end = 0;
     float null_color[3] = {0.75f, 0.75f, 0.75f};
     /* packed tables (host copies) */
@@ -304,6 +331,18 @@ int aa_class(const rt_object_desc &o, float *sn, float *sh, float *sv, int *a_ax
     return kn;
 }
 
+/* SOFT SHADOWS (rt_tables.h): r', the reach of a light's samples from its centre C on every axis, for the culls and the SHADOW
+ * VOXELS -- r (1 + 2^-10) covers |(dx, dy)| <= 1 and U, V off unit length by their rounding; 2^-22 max |C_k| more covers the
+ * rounding of add(C, .) (half an ulp of a coordinate of Q); rounded up */
+float soft_reach(const float r, const float C[3]) {
+    if (!(r > 0.0f)) return 0.0f;
+    const double m = std::max(std::fabs((double)C[0]), std::max(std::fabs((double)C[1]), std::fabs((double)C[2])));
+    const double want = (double)r * (1.0 + 0x1p-10) + 0x1p-22 * m;
+    float f = (float)want;
+    if ((double)f < want) f = std::nextafter(f, INFINITY);
+    return f;
+}
+
 bool all_finite(const rt_object_desc &o) {
     return std::isfinite(o.origin[0]) && std::isfinite(o.origin[1]) && std::isfinite(o.origin[2]) &&
            std::isfinite(o.radius);
@@ -332,13 +371,16 @@ struct ShadowVoxels {
     float lo[3] = {0, 0, 0}, scale[3] = {0, 0, 0};
 };
 
-bool hull_meets_box(const double c[3], const double e[3], const double L[3], const double lo[3], const double hi[3]) {
+bool hull_meets_box(const double c[3], const double e[3], const double L[3], const double lo[3], const double hi[3],
+                    const double reach = 0.0) {
     double s_lo = 0.0, s_hi = 1.0;
     for (int k = 0; k < 3; ++k) {
         const double m = 0.5 * (lo[k] + hi[k]), h = 0.5 * (hi[k] - lo[k]);
         const double a = c[k] - m, g = L[k] - c[k], r = h + e[k];
-        /* |a + s g| <= r - s e:   s (g + e) <= r - a   and   s (e - g) <= r + a */
-        const double A[2] = {g + e[k], e[k] - g}, B[2] = {r - a, r + a};
+        /* |a + s g| <= r - s e (+ s reach: SOFT SHADOWS, the hull of the voxel and the light's box [L - reach, L + reach]):
+         * s (g + e - reach) <= r - a   and   s (e - reach - g) <= r + a */
+        const double w = e[k] - reach;
+        const double A[2] = {g + w, w - g}, B[2] = {r - a, r + a};
         for (int j = 0; j < 2; ++j) {
             if (A[j] > 0.0) s_hi = std::min(s_hi, B[j] / A[j]);
             else if (A[j] < 0.0) s_lo = std::max(s_lo, B[j] / A[j]);
@@ -382,8 +424,10 @@ void svox_axis_bounds(float lo_f, float scale_f, int n, std::vector<double> &cel
     }
 }
 
-/* items: 2 quads each ({lo.xyz, bits}, {hi.xyz, word}); the leaves are the items from first_leaf on; lights: RT_LIGHT_QUADS each */
-bool shadow_voxels(const std::vector<Quad> &items, int first_leaf, const std::vector<Quad> &lights, int max_cells, int min_leaves, ShadowVoxels *out) {
+/* items: 2 quads each ({lo.xyz, bits}, {hi.xyz, word}); the leaves are the items from first_leaf on; lights: RT_LIGHT_QUADS each;
+ * soft: SOFT SHADOWS, the area-light rows (rt_tables.h: r' in w; empty for a scene without area lights) */
+bool shadow_voxels(const std::vector<Quad> &items, int first_leaf, const std::vector<Quad> &lights, int max_cells, int min_leaves, ShadowVoxels *out,
+                   const std::vector<Quad> &soft = std::vector<Quad>()) {
     const int n_items = (int)(items.size() / 2), n_lights = (int)(lights.size() / RT_LIGHT_QUADS);
     const int n_leaves = n_items - first_leaf;
     if (n_items > RT_SVOX_MAX_ITEMS || n_lights < 1 || n_lights > RT_SVOX_MAX_LIGHTS || n_leaves < min_leaves) return false;
@@ -462,7 +506,7 @@ bool shadow_voxels(const std::vector<Quad> &items, int first_leaf, const std::ve
                     const double grow = ((double)RT_SPHERE_SLACK + 1e-5) * far + 1e-5;
                     for (int k = 0; k < 3; ++k) { blo[k] -= grow; bhi[k] += grow; }
                     for (int l = 0; l < n_lights; ++l)
-                        if (hull_meets_box(c, e, L[l], blo, bhi)) m[l] |= 1ull << i;
+                        if (hull_meets_box(c, e, L[l], blo, bhi, soft.empty() ? 0.0 : (double)soft[(size_t)l].v[3])) m[l] |= 1ull << i;
                 }
             }
     return true;
@@ -476,7 +520,7 @@ struct LeafItem { float lo[3], hi[3]; uint32_t member_off, count, cidx_slot; boo
 struct Packing {
     explicit Packing(int n)
         : geom_off((size_t)n, 0), mat_of((size_t)n, 0), aa_rec_of((size_t)n, -1), aa_cls_of((size_t)n, -1), clustered((size_t)n, 0) {}
-    std::vector<Quad> geom, lights, mats, texs, refr;
+    std::vector<Quad> geom, lights, mats, texs, refr, soft;
     std::vector<int> geom_off, mat_of;               /* per object: its full record in geom, its material */
     std::vector<uint32_t> cidx;                      /* Scene indices of the clustered runs' members, leaf by leaf */
     std::vector<LeafItem> leaf_items;
@@ -569,6 +613,12 @@ int pack_materials_and_lights(const rt_scene *s, Packing &P) {
         if (o.is_light) {
             P.lights.push_back({{o.origin[0], o.origin[1], o.origin[2], o.intensity}});
             P.lights.push_back({{o.color[0], o.color[1], o.color[2], bits_to_float((uint32_t)i)}});
+            if (s->soft_used) {
+                /* SOFT SHADOWS: the light's row {r, step, bits(n), r'} (rt_tables.h) */
+                const int sn = s->soft_n[(size_t)i];
+                const float r = s->soft_r[(size_t)i];
+                P.soft.push_back({{r, 2.0f / (float)sn, bits_to_float((uint32_t)sn), soft_reach(r, o.origin)}});
+            }
         }
     }
     if (s->images_used) {
@@ -886,7 +936,8 @@ void assemble_image(const rt_scene *s, Packing &P) {
     b.lights_off = (int)image.size();
     image.insert(image.end(), P.lights.begin(), P.lights.end());
     const size_t refr_header = image.size();
-    if (s->refract_used) image.push_back(Quad{{0, 0, 0, 0}});       /* REFRACTION: the rows' offset, below */
+    /* REFRACTION: the rows' offset, below; SOFT SHADOWS: the area-light rows' offset in the y word */
+    if (s->refract_used || s->soft_used) image.push_back(Quad{{0, 0, 0, 0}});
     b.mat_off = (int)image.size();
     image.insert(image.end(), P.mats.begin(), P.mats.end());
     b.tex_off = (int)image.size();
@@ -894,6 +945,10 @@ void assemble_image(const rt_scene *s, Packing &P) {
     if (s->refract_used) {
         image[refr_header].v[0] = bits_to_float((uint32_t)image.size());
         image.insert(image.end(), P.refr.begin(), P.refr.end());
+    }
+    if (s->soft_used) {
+        image[refr_header].v[1] = bits_to_float((uint32_t)image.size());
+        image.insert(image.end(), P.soft.begin(), P.soft.end());
     }
     std::vector<uint32_t> objinfo((size_t)n);
     for (int i = 0; i < n; ++i)
@@ -916,7 +971,7 @@ void pack_shadow_voxels(const rt_scene *s, Packing &P) {
      * grid (16 leaves) at depth 8: 3.8 -> 2.6 candidates per scan, frame 3.94 -> 4.03 ms with the table; the 1 024-sphere grid
      * (43 leaves): 8.9 -> 4.4, 3.87 -> 3.71 ms (profiles/r04_experiments.txt 8) */
     if (!shadow_voxels(P.shadow_items, P.b.shadow_first_leaf, P.lights, s->svox_opt > 0 ? s->svox_opt : RT_SVOX_MAX_CELLS,
-                       s->svox_opt > 0 ? 4 : RT_SVOX_MIN_LEAVES, &sv))
+                       s->svox_opt > 0 ? 4 : RT_SVOX_MIN_LEAVES, &sv, P.soft))
         return;
     RtParams &b = P.b;
     b.svox_off = (int)P.image.size();
@@ -1476,8 +1531,9 @@ void learned_start_row(const rt_scene *s, int W, int H, int x0, int x1, int max_
     }
 }
 
-struct Kernel { const void *fn; const char *name; };
+struct Kernel { const void *fn; const char *name; bool seeded = false; };    /* seeded: takes the sampling seed (SOFT SHADOWS) */
 #define RT_KERNEL(k) Kernel{(const void *)k, #k}
+#define RT_SOFT_KERNEL(k) Kernel{(const void *)k, #k, true}
 /* a kernel and its supersampling, ray-batch, ray-query and G-buffer siblings; with image textures the *_image siblings (the
  * occlusion query reads no colour and keeps its kernel) */
 struct Siblings { Kernel plain, ssaa, rays, hits, occluded, gbuffer; };
@@ -1489,6 +1545,11 @@ struct Siblings { Kernel plain, ssaa, rays, hits, occluded, gbuffer; };
 #define RT_SIBLINGS_REFRACT(k)                                                                                              \
     Siblings{RT_KERNEL(k##_refract), RT_KERNEL(k##_ssaa_refract), RT_KERNEL(k##_rays_refract), RT_KERNEL(k##_hits_image), \
              RT_KERNEL(k##_occluded), RT_KERNEL(k##_gbuffer_refract)}
+/* with area lights the *_soft siblings: the name of the kernel the same call runs on the scene packed as an image scene without
+ * them, + "_soft" (the ray queries answer geometry: the *_image ones) */
+#define RT_SIBLINGS_SOFT(k, r)                                                                                            \
+    Siblings{RT_SOFT_KERNEL(k##r##_soft), RT_SOFT_KERNEL(k##_ssaa##r##_soft), RT_SOFT_KERNEL(k##_rays##r##_soft),           \
+             RT_KERNEL(k##_hits_image), RT_KERNEL(k##_occluded), RT_SOFT_KERNEL(k##_gbuffer##r##_soft)}
 #define RT_SIBLINGS(k)                                                                                              \
     Siblings{RT_KERNEL(k), RT_KERNEL(k##_ssaa), RT_KERNEL(k##_rays), RT_KERNEL(k##_hits), RT_KERNEL(k##_occluded), \
              RT_KERNEL(k##_gbuffer)}
@@ -1507,6 +1568,23 @@ Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int b
         if (gbuffer) return k.gbuffer;
         return ssaa ? k.ssaa : (rays ? k.rays : k.plain);
     };
+    if (s->soft_used && s->refract_used) {
+        if (global_tables) return pick(RT_SIBLINGS_SOFT(rt_render_kernel_large, _refract));
+        if (s->n_clusters > 0 && s->pairs_opt) {
+            const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
+            return wide ? pick(RT_SIBLINGS_SOFT(rt_render_kernel_clusters_wide, _refract))
+                        : pick(RT_SIBLINGS_SOFT(rt_render_kernel_clusters, _refract));
+        }
+        return fast_tables ? pick(RT_SIBLINGS_SOFT(rt_render_kernel, _refract)) : pick(RT_SIBLINGS_SOFT(rt_render_kernel_items, _refract));
+    }
+    if (s->soft_used) {
+        if (global_tables) return pick(RT_SIBLINGS_SOFT(rt_render_kernel_large, ));
+        if (s->n_clusters > 0 && s->pairs_opt) {
+            const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
+            return wide ? pick(RT_SIBLINGS_SOFT(rt_render_kernel_clusters_wide, )) : pick(RT_SIBLINGS_SOFT(rt_render_kernel_clusters, ));
+        }
+        return fast_tables ? pick(RT_SIBLINGS_SOFT(rt_render_kernel, )) : pick(RT_SIBLINGS_SOFT(rt_render_kernel_items, ));
+    }
     if (s->refract_used) {
         if (global_tables) return pick(RT_SIBLINGS_REFRACT(rt_render_kernel_large));
         if (s->n_clusters > 0 && s->pairs_opt) {
@@ -1704,7 +1782,10 @@ int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1,
     unsigned int *list_arg = reinterpret_cast<unsigned int *>(s->d_help);      /* the clustered-scene kernels' HELP areas (unused by the others) */
     void *args6[] = {&p, &image_arg, &d_out, &counter, &stack_arg, &list_arg};
     void *args7[] = {&p, &image_arg, &d_out, &counter, &stack_arg, &d_stats, &list_arg};
-    HIP_TRY(hipLaunchKernel(kernel, dim3((unsigned)blocks), dim3((unsigned)block), d_stats ? args7 : args6, (size_t)plan.lds_bytes, stream));
+    uint32_t seed = s->shadow_seed;       /* SOFT SHADOWS: copied into the launch's arguments here, so it is this launch's */
+    void *args_seeded[] = {&p, &image_arg, &d_out, &counter, &stack_arg, &list_arg, &seed};
+    HIP_TRY(hipLaunchKernel(kernel, dim3((unsigned)blocks), dim3((unsigned)block),
+                            plan.kernel.seeded ? args_seeded : (d_stats ? args7 : args6), (size_t)plan.lds_bytes, stream));
     HIP_TRY(hipGetLastError());
     s->ev_next = next_slot;               /* (only now: a launch that did not happen has zeroed nothing) */
     HIP_TRY(hipEventRecord(s->ev[slot].stop, stream));
@@ -1874,9 +1955,11 @@ int rt_capi_texture_version(void) { return RT_CAPI_TEXTURE_VERSION; }
 
 /* IMAGE TEXTURES (include/rt_capi_texture.h): the images' checks in the header's order, then rt_scene_create's path with them */
 namespace {
-/* rt_scene_create_textured's path; refr: {tf, ior} per object of a refractive scene (REFRACTION), else NULL */
+/* rt_scene_create_textured's path; refr: {tf, ior} per object of a refractive scene (REFRACTION), else NULL; soft: {n, r} per
+ * object of a scene with area lights (SOFT SHADOWS), else NULL */
 int create_textured(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
-                    const std::vector<float> *refr_tf, const std::vector<float> *refr_ior, int device, rt_scene **out) {
+                    const std::vector<float> *refr_tf, const std::vector<float> *refr_ior, int device, rt_scene **out,
+                    const std::vector<int> *soft_n = nullptr, const std::vector<float> *soft_r = nullptr) {
     if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
     *out = nullptr;
     if (n_images < 0) return fail(RT_ERR_INVALID, "n_images < 0");
@@ -1895,7 +1978,7 @@ int create_textured(const rt_scene_desc *desc, int n_images, const rt_image_text
     }
     if (total > (uint64_t)RT_MAX_SCENE_TEXELS)
         return fail(RT_ERR_CAPACITY, "more than " + std::to_string(RT_MAX_SCENE_TEXELS) + " texels in the scene's images");
-    if (n_images == 0 && !refr_tf) return rt_scene_create(desc, device, out);
+    if (n_images == 0 && !refr_tf && !soft_n) return rt_scene_create(desc, device, out);
     rt_scene *s = new (std::nothrow) rt_scene();
     if (!s) return fail(RT_ERR_INVALID, "out of memory");
     int rc = adopt_desc(desc, s, n_images);
@@ -1904,6 +1987,13 @@ int create_textured(const rt_scene_desc *desc, int n_images, const rt_image_text
         s->refr_tf = *refr_tf;
         s->refr_ior = *refr_ior;
         s->refract_used = true;
+        s->images_used = true;
+    }
+    if (rc == RT_OK && soft_n) {
+        /* (an area-light scene is packed as an image scene too) */
+        s->soft_n = *soft_n;
+        s->soft_r = *soft_r;
+        s->soft_used = true;
         s->images_used = true;
     }
     if (rc == RT_OK) {
@@ -1926,10 +2016,12 @@ int rt_scene_create_textured(const rt_scene_desc *desc, int n_images, const rt_i
 
 int rt_capi_refract_version(void) { return RT_CAPI_REFRACT_VERSION; }
 
+namespace {
 /* REFRACTION (include/rt_capi_refract.h): the list's checks in the header's order; entries with tf == 0 dropped, none left:
- * rt_scene_create_textured itself */
-int rt_scene_create_refractive(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
-                               int n_refractive, const rt_refraction_desc *refractive, int device, rt_scene **out) {
+ * rt_scene_create_textured's path.  soft: SOFT SHADOWS, as create_textured() */
+int create_refractive(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
+                      int n_refractive, const rt_refraction_desc *refractive, int device, rt_scene **out,
+                      const std::vector<int> *soft_n, const std::vector<float> *soft_r) {
     if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
     *out = nullptr;
     if (n_refractive < 0) return fail(RT_ERR_INVALID, "n_refractive < 0");
@@ -1952,8 +2044,55 @@ int rt_scene_create_refractive(const rt_scene_desc *desc, int n_images, const rt
         ior[(size_t)r.object] = r.ior;
         any = true;
     }
-    if (!any) return create_textured(desc, n_images, images, nullptr, nullptr, device, out);
-    return create_textured(desc, n_images, images, &tf, &ior, device, out);
+    if (!any) return create_textured(desc, n_images, images, nullptr, nullptr, device, out, soft_n, soft_r);
+    return create_textured(desc, n_images, images, &tf, &ior, device, out, soft_n, soft_r);
+}
+} // namespace
+
+int rt_scene_create_refractive(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
+                               int n_refractive, const rt_refraction_desc *refractive, int device, rt_scene **out) {
+    return create_refractive(desc, n_images, images, n_refractive, refractive, device, out, nullptr, nullptr);
+}
+
+int rt_capi_soft_version(void) { return RT_CAPI_SOFT_VERSION; }
+
+/* SOFT SHADOWS (include/rt_capi_soft.h): the list's checks in the header's order; entries with radius == 0 dropped, none left:
+ * rt_scene_create_refractive itself */
+int rt_scene_create_soft(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
+                         int n_refractive, const rt_refraction_desc *refractive,
+                         int n_area_lights, const rt_area_light_desc *area_lights, int device, rt_scene **out) {
+    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
+    *out = nullptr;
+    if (n_area_lights < 0) return fail(RT_ERR_INVALID, "n_area_lights < 0");
+    if (n_area_lights > 0 && !area_lights) return fail(RT_ERR_INVALID, "area_lights is NULL");
+    const int n = desc->n_objects;
+    std::vector<int> sn(n > 0 ? (size_t)n : 0u, 1);
+    std::vector<float> sr(sn.size(), 0.0f);
+    std::vector<char> listed(sn.size(), 0);
+    bool any = false;
+    for (int k = 0; k < n_area_lights; ++k) {
+        const rt_area_light_desc &a = area_lights[k];
+        const std::string which = "area light entry " + std::to_string(k) + ": ";
+        if (a.object < 0 || a.object >= n) return fail(RT_ERR_INVALID, which + "object index out of range");
+        if (desc->objects && !desc->objects[a.object].is_light) return fail(RT_ERR_INVALID, which + "object " + std::to_string(a.object) + " is not a light");
+        if (listed[(size_t)a.object]) return fail(RT_ERR_INVALID, which + "object " + std::to_string(a.object) + " listed twice");
+        listed[(size_t)a.object] = 1;
+        if (a.samples < 1 || a.samples > 8) return fail(RT_ERR_INVALID, which + "samples must be in 1..8");
+        if (!(std::isfinite(a.radius) && a.radius >= 0.0f)) return fail(RT_ERR_INVALID, which + "radius must be finite and >= 0");
+        if (a.radius == 0.0f) continue;                      /* (ignored) */
+        sn[(size_t)a.object] = a.samples;
+        sr[(size_t)a.object] = a.radius;
+        any = true;
+    }
+    if (!any) return create_refractive(desc, n_images, images, n_refractive, refractive, device, out, nullptr, nullptr);
+    return create_refractive(desc, n_images, images, n_refractive, refractive, device, out, &sn, &sr);
+}
+
+int rt_scene_set_shadow_seed(rt_scene *s, uint32_t seed) {
+    if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    s->shadow_seed = seed;
+    return RT_OK;
 }
 
 int rt_scene_destroy(rt_scene *s) {
@@ -2098,6 +2237,7 @@ int rt_render_gbuffer_device(rt_scene *s, const rt_camera_desc *cam, int W, int 
 int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
                     float *out_rgb, uint64_t *stats, int n_stats, uint64_t *wave_cycles, int n_wave_cycles) {
     if (!s || !stats || n_stats < 0) return fail(RT_ERR_INVALID, "scene/stats is NULL");
+    if (s->soft_used) return fail(RT_ERR_INVALID, "the counting build does not sample area lights (include/rt_capi_soft.h)");
     if (s->refract_used) return fail(RT_ERR_INVALID, "the counting build does not trace refraction (include/rt_capi_refract.h)");
     if (s->images_used) return fail(RT_ERR_INVALID, "the counting build does not sample image textures (include/rt_capi_texture.h)");
     std::lock_guard<std::mutex> lock(s->mu);
@@ -2133,6 +2273,8 @@ int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0
  * shape (W, H, x0, x1, max_depth, tile shape) start their queues at the row of the longest tile (launch(), LEARNED START ROW). */
 int rt_learn_tile_order(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
+    if (s->soft_used)
+        return fail(RT_ERR_INVALID, "the counting build does not sample area lights, so no tile order is learned (include/rt_capi_soft.h)");
     if (s->refract_used)
         return fail(RT_ERR_INVALID, "the counting build does not trace refraction, so no tile order is learned (include/rt_capi_refract.h)");
     if (s->images_used)

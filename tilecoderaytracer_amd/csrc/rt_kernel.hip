@@ -59,6 +59,14 @@ __device__ __forceinline__ float dot3(const V3 a, const V3 b) { return a.x * b.x
 __device__ __forceinline__ V3 sub3(const V3 a, const V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
 __device__ __forceinline__ V3 add3(const V3 a, const V3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ V3 scale3(const V3 v, const float f) { return mk(v.x * f, v.y * f, v.z * f); }
+__device__ __forceinline__ V3 cross3(const V3 a, const V3 b) {
+    return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+/* the 32-bit integer hash "lowbias32" (SOFT SHADOWS, include/rt_capi_soft.h) */
+__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
 /* sqrtf(x) for 2^-96 <= x <= 2^120 (and for a NaN or negative x, whose result -- NaN -- nobody uses): the compiler's own
  * expansion of the correctly rounded square root -- v_sqrt_f32 (1 ulp), then the two neighbours tried with an exact fma
  * residual each -- without the steps that scale a tiny x up and the result back down and pass 0 and infinity through
@@ -1157,15 +1165,27 @@ __device__ __forceinline__ void shading_point_bundle(const V3 lo, const V3 hi, V
     *centre = mk(uniform_f(c.x), uniform_f(c.y), uniform_f(c.z));
 }
 
+/* SOFT SHADOWS (include/rt_capi_soft.h): the half-extent of a bundle whose segments end anywhere within r' (>= 0) of the light's
+ * centre on every axis -- e + r', rounded up as above; r' == 0 (a hard light) leaves e as it is */
+__device__ __forceinline__ V3 soft_half(const V3 e, const float r_reach) {
+    if (!(r_reach > 0.0f)) return e;
+    return mk((e.x + r_reach) * 1.000001f, (e.y + r_reach) * 1.000001f, (e.z + r_reach) * 1.000001f);
+}
+
 /* BOTH LIGHTS' SHADOW CULLS IN ONE PASS (FAST tables, two lights and at most 32 shadow items: the built-in scene).  A scan's bundle cull gives every item a lane; with 18-30 items half the wavefront idles, and the scan towards the
  * other light repeats the pass.  Here lane i tests item i against the segments towards light 0 and lane 32 + i the same item
  * against those towards light 1: the light's position is a per-lane select, and what the scans derive from it as wavefront-wide
  * scalars (the centre segment, its reciprocals, the slack of its reach: in_shade()) is per-lane arithmetic done once for both
- * -- the same test on the same numbers.  Bits 0-31 of the result: the candidates towards light 0, bits 32-63: towards light 1. */
-__device__ __forceinline__ unsigned long long shadow_cull_two_lights(const float4 *boxes, const int n_items, const V3 c, const V3 half,
-                                                                    const V3 light0, const V3 light1) {
+ * -- the same test on the same numbers.  Bits 0-31 of the result: the candidates towards light 0, bits 32-63: towards light 1.
+ * kSoft (SOFT SHADOWS, include/rt_capi_soft.h): the segments towards light l end anywhere within r'_l of its centre on every
+ * axis (reach0 / reach1; 0 for a hard light), so that light's half-extent grows by r'_l first (in_shade(), SOFT SHADOWS). */
+template <bool kSoft = false>
+__device__ __forceinline__ unsigned long long shadow_cull_two_lights(const float4 *boxes, const int n_items, const V3 c, V3 half,
+                                                                    const V3 light0, const V3 light1,
+                                                                    const float reach0 = 0.0f, const float reach1 = 0.0f) {
     const int lane = (int)(threadIdx.x & 63u);
     const bool second = lane >= 32;
+    if constexpr (kSoft) half = soft_half(half, second ? reach1 : reach0);
     const V3 light = mk(second ? light1.x : light0.x, second ? light1.y : light0.y, second ? light1.z : light0.z);
     const V3 seg = sub3(light, c);
     const V3 sinv = approx_inverse(seg);
@@ -1301,7 +1321,10 @@ __device__ __forceinline__ bool in_shade(const RtParams &p, const float4 *lds, f
      * centre c of [origins_lo, origins_hi], and all segments end at the light, so
      * the point at parameter s of any of them is within (1-s) e of c + s (light - c).
      * An item can matter only if its box, grown by e (and the rounding slack),
-     * meets that centre segment for some s in [0, 1]: a slab test per item-lane. */
+     * meets that centre segment for some s in [0, 1]: a slab test per item-lane.
+     * SOFT SHADOWS (include/rt_capi_soft.h): a sample segment ends at Q, within r' of the light's centre on every axis, so its
+     * point at s is within (1-s) e + s r' <= e + r' of c + s (light - c): the caller passes e + r' (soft_half()) and the same
+     * test stays exact; the reach below then counts 3 r' as well. */
     const bool cull = p.cull != 0 && p.n_shadow_items >= RT_SHADOW_CULL_MIN_ITEMS;
     const V3 c = origins_centre;             /* both from shading_point_bundle(), once per bounce level */
     V3 e = origins_half, sinv = mk(0, 0, 0); /* e: half-extent, plus slack below */
@@ -1937,14 +1960,16 @@ __device__ __forceinline__ void gbuffer_store(const RtParams &p, const int sx, c
  * index (rt_tables.h, RT_IMAGE_SEL_SHIFT).  kRefract: refractive objects (include/rt_capi_refract.h, always with kImages): the
  * bounce chain becomes a per-lane depth-first walk of the ray tree -- each step traces one ray per live lane, whatever its
  * level; a node with a reflected and a transmitted child keeps the transmitted ray on its stack entry while the reflected
- * subtree is walked. */
+ * subtree is walked.  kSoft: area lights (include/rt_capi_soft.h, always with kImages): a light with a
+ * radius runs n x n shadow scans per level, one per sample of its disc, and scales its terms by the visible fraction; the
+ * launch's sampling seed arrives as shadow_seed. */
 template <bool kStats, int kMode, bool kSsaa = false, bool kRays = false, bool kGbuffer = false, bool kImages = false,
-          bool kRefract = false>
+          bool kRefract = false, bool kSoft = false>
 __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds, float4 *wlds, float4 *help_rays,
                                             const uint32_t *__restrict__ ctl_words, float *__restrict__ out,
                                             float4 *__restrict__ bounce_stack, unsigned long long *__restrict__ stats_out,
                                             Stats<kStats> &st, const int wave_in, const int my_xcc, const int steal,
-                                            int &next_pop, unsigned int *const ask_head) {
+                                            int &next_pop, unsigned int *const ask_head, const uint32_t shadow_seed = 0u) {
     const int wave = __builtin_amdgcn_readfirstlane(wave_in);      /* the tile number is the same in all lanes: a scalar register's worth */
     const uint32_t *lds_u32 = reinterpret_cast<const uint32_t *>(lds);
     const int lane = (int)(threadIdx.x & 63u);
@@ -2015,6 +2040,14 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
     [[maybe_unused]] int lvl = 0;
     [[maybe_unused]] int refr_off = 0;
     if constexpr (kRefract) refr_off = __builtin_amdgcn_readfirstlane(__float_as_int(lds[p.mat_off - 1].x));
+    /* SOFT SHADOWS: the area-light rows' offset (the same header quad's y word) and this lane's sampling key: x * H + z of the
+     * launch (the virtual one when supersampled; a ray batch's cell number is its ray index) */
+    [[maybe_unused]] int soft_off = 0;
+    [[maybe_unused]] uint32_t soft_key = 0u;
+    if constexpr (kSoft) {
+        soft_off = __builtin_amdgcn_readfirstlane(__float_as_int(lds[p.mat_off - 1].y));
+        soft_key = (uint32_t)x * (uint32_t)here(p.H) + (uint32_t)z;
+    }
     for (int level = 0; kRefract || level <= p.max_depth; ++level) {
         if (__ballot(alive) == 0ull) break;
         levels = level + 1;
@@ -2173,9 +2206,15 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
             unsigned long long culled_both = 0ull;
             if constexpr (kMode == 6) {
                 both_culls = p.n_lights == 2 && p.n_fast_shadow > 0 && p.n_fast_shadow <= 32;
-                if (both_culls)
-                    culled_both = shadow_cull_two_lights(lds + p.fast_box_off, p.n_fast_shadow, bundle_centre, bundle_half,
-                                                         xyz(lds[p.lights_off]), xyz(lds[p.lights_off + RT_LIGHT_QUADS]));
+                if (both_culls) {
+                    if constexpr (kSoft)           /* SOFT SHADOWS: each light's reach r' (its row's w) */
+                        culled_both = shadow_cull_two_lights<true>(lds + p.fast_box_off, p.n_fast_shadow, bundle_centre, bundle_half,
+                                                                   xyz(lds[p.lights_off]), xyz(lds[p.lights_off + RT_LIGHT_QUADS]),
+                                                                   lds[soft_off].w, lds[soft_off + RT_SOFT_QUADS].w);
+                    else
+                        culled_both = shadow_cull_two_lights(lds + p.fast_box_off, p.n_fast_shadow, bundle_centre, bundle_half,
+                                                             xyz(lds[p.lights_off]), xyz(lds[p.lights_off + RT_LIGHT_QUADS]));
+                }
             }
             for (int l = 0; l < p.n_lights; ++l) {
                 const float4 l0 = lds[p.lights_off + l * RT_LIGHT_QUADS];
@@ -2188,10 +2227,55 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                 const V3 light_ray = normalize3(dir, &dist_to_light);        /* == Ray(P, dir).direction == cosineShade's light_ray == specular L */
                 const unsigned long long t_shadow = st_clock<kStats>();
                 bool blocked;
-                if constexpr (kMode == 6) blocked = in_shade_fast<kStats>(p, lds, ctl_words, shade, P, light_ray, dist_to_light, xyz(l0), bundle_centre, bundle_half,
-                                                                          both_culls, culled, st);
-                else blocked = in_shade<kStats, kMode>(p, lds, wlds, help_rays, shade, P, light_ray, dist_to_light, xyz(l0), bundle_centre, bundle_half,
-                                                       voxels_say, st);
+                [[maybe_unused]] float visible = 1.0f;       /* SOFT SHADOWS: f = m / S */
+                if constexpr (kSoft) {
+                    /* SOFT SHADOWS (include/rt_capi_soft.h): the light's row {r, step, bits(n), r'}; r == 0 (a light not in the
+                     * list): n == 1 and the one scan is the hard shadow's, towards the centre -- no sampling, no hashing */
+                    const float4 sq = lds[soft_off + l * RT_SOFT_QUADS];
+                    const float radius = uniform_f(sq.x), step = uniform_f(sq.y);
+                    const bool area = radius != 0.0f;
+                    const int n = __builtin_amdgcn_readfirstlane(__float_as_int(sq.z));
+                    const V3 soft_e = soft_half(bundle_half, uniform_f(sq.w));
+                    /* what does not depend on the sample: the disc's frame and the lane's hash (L is light_ray, above) */
+                    V3 U = light_ray, V = light_ray;
+                    uint32_t h = 0u;
+                    if (area) {
+                        const V3 A = fabsf(light_ray.x) < 0.5f ? mk(1.0f, 0.0f, 0.0f) : mk(0.0f, 1.0f, 0.0f);
+                        U = normalize3(cross3(A, light_ray));
+                        V = cross3(light_ray, U);
+                        const uint32_t k = (uint32_t)(kRefract ? lvl : level);
+                        h = lowbias32(lowbias32(lowbias32(lowbias32(shadow_seed ^ 0x9e3779b9u) ^ soft_key) ^ k) ^ (uint32_t)l);
+                    }
+                    int m = 0;
+                    for (int i = 0; i < n; ++i) {
+                        for (int j = 0; j < n; ++j) {
+                            V3 ls = light_ray;
+                            float dist_s = dist_to_light;
+                            if (area) {
+                                const uint32_t hs = lowbias32(h ^ (uint32_t)(i * n + j));
+                                const float xi1 = (float)(hs >> 8) * 0x1p-24f;
+                                const float xi2 = (float)(lowbias32(hs ^ 0x9e3779b9u) >> 8) * 0x1p-24f;
+                                const float a = ((float)i + xi1) * step - 1.0f, b = ((float)j + xi2) * step - 1.0f;
+                                const float dx = a * sqrtf(1.0f - (b * b) * 0.5f), dy = b * sqrtf(1.0f - (a * a) * 0.5f);
+                                const V3 Q = add3(xyz(l0), add3(scale3(U, radius * dx), scale3(V, radius * dy)));
+                                ls = normalize3(sub3(Q, P), &dist_s);
+                            }
+                            bool b_s;
+                            if constexpr (kMode == 6) b_s = in_shade_fast<kStats>(p, lds, ctl_words, shade, P, ls, dist_s, xyz(l0), bundle_centre, soft_e,
+                                                                                  both_culls, culled, st);
+                            else b_s = in_shade<kStats, kMode>(p, lds, wlds, help_rays, shade, P, ls, dist_s, xyz(l0), bundle_centre, soft_e,
+                                                               voxels_say, st);
+                            m += b_s ? 0 : 1;
+                        }
+                    }
+                    blocked = m == 0;
+                    visible = (float)m / (float)(n * n);
+                } else {
+                    if constexpr (kMode == 6) blocked = in_shade_fast<kStats>(p, lds, ctl_words, shade, P, light_ray, dist_to_light, xyz(l0), bundle_centre, bundle_half,
+                                                                              both_culls, culled, st);
+                    else blocked = in_shade<kStats, kMode>(p, lds, wlds, help_rays, shade, P, light_ray, dist_to_light, xyz(l0), bundle_centre, bundle_half,
+                                                           voxels_say, st);
+                }
                 st_cycles(st, ST_CYCLES_SHADOW, t_shadow);
                 if (shade && !blocked) {
                     /* the winner's material, re-read here rather than kept in registers across the shadow scan */
@@ -2210,7 +2294,8 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                     if (diffuse_factor > (float)0) {
                         float cosine_dot_factor = dot3(normal_dir, light_ray);
                         if (cosine_dot_factor > (float)0) {
-                            const float factor = cosine_dot_factor * diffuse_factor * l0.w;
+                            float factor = cosine_dot_factor * diffuse_factor * l0.w;
+                            if constexpr (kSoft) factor = factor * visible;
                             C.x += factor * object_color.x * light_color.x;
                             C.y += factor * object_color.y * light_color.y;
                             C.z += factor * object_color.z * light_color.z;
@@ -2228,7 +2313,8 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                         float pow_factor = dot;
 #pragma unroll
                         for (int j = 0; j < 19; ++j) pow_factor *= dot;
-                        const float spec_factor = pow_factor * specular_factor;
+                        float spec_factor = pow_factor * specular_factor;
+                        if constexpr (kSoft) spec_factor = spec_factor * visible;
                         C = add3(C, scale3(light_color, spec_factor));
                     }
                 }
@@ -2602,12 +2688,13 @@ __device__ RT_SCAN_INLINE unsigned int queues_with_tiles(const unsigned int *til
 }
 
 template <bool kStats, bool kGlobalTables = false, bool kClusters = false, bool kRoomy = false, bool kFast = false, bool kSsaa = false,
-          bool kRays = false, int kQuery = RT_QUERY_NONE, bool kGbuffer = false, bool kImages = false, bool kRefract = false>
+          bool kRays = false, int kQuery = RT_QUERY_NONE, bool kGbuffer = false, bool kImages = false, bool kRefract = false,
+          bool kSoft = false>
 __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__restrict__ image,
                                             float *__restrict__ out, unsigned int *__restrict__ tile_counter,
                                             float4 *__restrict__ bounce_stack,
                                             unsigned long long *__restrict__ stats_out,
-                                            unsigned int *__restrict__ help_area) {
+                                            unsigned int *__restrict__ help_area, const uint32_t shadow_seed = 0u) {
     extern __shared__ float4 wlds[];                          /* LDS: the tables, the low levels of the bounce stack, the HELP desk */
     Stats<kStats> st;
     if constexpr (kStats) {
@@ -2814,8 +2901,8 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
         constexpr int kMode = kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0);
         if constexpr (kQuery == RT_QUERY_HITS) hits_tile<kMode, kImages>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
         else if constexpr (kQuery == RT_QUERY_OCCLUDED) occluded_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
-        else render_tile<kStats, kMode, kSsaa, kRays, kGbuffer, kImages, kRefract>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
-                                                                my_xcc, steal, next_pop, ask_head);
+        else render_tile<kStats, kMode, kSsaa, kRays, kGbuffer, kImages, kRefract, kSoft>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
+                                                                my_xcc, steal, next_pop, ask_head, shadow_seed);
 #ifdef RT_TIMELINE
         if (p.timeline != 0ull && lane == 0) {                   /* ... when it was done, and by whom */
             unsigned long long *rec = reinterpret_cast<unsigned long long *>(p.timeline) + (size_t)tile_number * RT_TIMELINE_WORDS;

@@ -32,6 +32,8 @@
  *              bounds b_0 .. b_(texels_w - 1), then the row bounds (rt_kernel.hip, image_cell())
  *   refraction (scenes with refractive objects only: include/rt_capi_refract.h) one header quad right before the materials,
  *              {bits(offset of the rows), 0, 0, 0}, and behind the textures one quad per material row: {tf, ior, 0, 0}
+ *   soft       (scenes with area lights only: include/rt_capi_soft.h) the same header quad, its y word bits(offset of the rows),
+ *              and behind the refraction rows (if any) one quad per light: {r, step, bits(n), r'}
  *   objinfo    one u32 per object (4 per quad):
  *                bits 0-15 geometry offset (quads), 16-17 kind, 20-31 material row
  *
@@ -140,6 +142,14 @@ enum { RT_DESK_STATE = 0, RT_DESK_CURSOR, RT_DESK_INSIDE, RT_DESK_FINISHED, RT_D
  * transmitted child, 2: the reflected child with the transmitted one pending. */
 #define RT_REFR_QUADS 1
 #define RT_REFRACT_ENTRY_QUADS 3
+
+/* SOFT SHADOWS (include/rt_capi_soft.h; the *_soft and *_refract_soft kernels only, whose scenes are always packed as image
+ * scenes).  One more section, one quad per light in light order: {r, step = 2 / n, bits(n), r' = r (1 + 2^-10) rounded up}; a
+ * light that is not an area light has {0, 2, bits(1), 0} and keeps the hard shadow.  Its quad offset is bits of the y word of
+ * the header quad right before the materials (the one whose x word holds the refraction rows' offset; 0 there when the scene
+ * has no refraction).  The launch's sampling seed is not in the image: the *_soft kernels take it as one more kernel argument
+ * behind the ones every render kernel shares (rt_kernel_soft.hip). */
+#define RT_SOFT_QUADS 1
 
 #define RT_PRIMARY_ITEMS 64          /* scenes with more FAST items than this have no PRIMARY table */
 

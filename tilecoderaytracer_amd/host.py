@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .capi import LIB_DIR, RtCameraDesc, RtImageTextureDesc, RtRefractionDesc, RtSceneDesc, F3
+from .capi import LIB_DIR, RtAreaLightDesc, RtCameraDesc, RtImageTextureDesc, RtRefractionDesc, RtSceneDesc, F3
 
 _hlib = None
 
@@ -46,6 +46,7 @@ def load_host_library():
     lib.rth_set_specular.argtypes = [vp, i, f]
     lib.rth_set_reflective.argtypes = [vp, i, f]
     lib.rth_set_refraction.argtypes = [vp, i, f, f]
+    lib.rth_set_area_light.argtypes = [vp, i, i, f]
     lib.rth_set_checkerboard.argtypes = [vp, i, pf, pf, f, f]
     lib.rth_set_image_texture.argtypes = [vp, i, i, i, vp, f, f, i]
     lib.rth_set_light.argtypes = [vp, i]
@@ -59,6 +60,8 @@ def load_host_library():
     lib.rth_scene_images.restype = i
     lib.rth_scene_refractions.argtypes = [vp, C.POINTER(C.POINTER(RtRefractionDesc))]
     lib.rth_scene_refractions.restype = i
+    lib.rth_scene_area_lights.argtypes = [vp, C.POINTER(C.POINTER(RtAreaLightDesc))]
+    lib.rth_scene_area_lights.restype = i
     lib.rth_camera_desc.argtypes = [vp]
     lib.rth_camera_desc.restype = C.POINTER(RtCameraDesc)
     lib.rth_write_screen_txt.argtypes = [C.c_char_p, i, i, vp, C.c_double, C.c_double]
@@ -160,6 +163,10 @@ class HostScene:
     def set_refraction(self, idx, factor, ior=1.0):
         """ObjMaterial::setRefractiveFactor(factor) and setRefractiveIndex(ior) (include/rt_capi_refract.h)"""
         self._ok(self._lib.rth_set_refraction(self._h, idx, factor, ior))
+    def set_area_light(self, idx, samples, radius=None):
+        """SceneObject::setAreaLight (include/rt_capi_soft.h): light idx sampled as an area light, samples x samples per
+        shading point on a disc of the radius (None: the object's own -- a sphere's radius)"""
+        self._ok(self._lib.rth_set_area_light(self._h, idx, samples, -1.0 if radius is None else radius))
     def set_checkerboard(self, idx, light, dark, w, h):
         self._ok(self._lib.rth_set_checkerboard(self._h, idx, _v(light), _v(dark), w, h))
     def set_image_texture(self, idx, texels, w, h, wrap):
@@ -198,6 +205,13 @@ class HostScene:
         """the flattened scene's refractive objects: (count, pointer to RtRefractionDesc or None)"""
         ptr = C.POINTER(RtRefractionDesc)()
         n = self._lib.rth_scene_refractions(self._h, C.byref(ptr))
+        return n, (ptr if n else None)
+
+    @property
+    def area_lights(self):
+        """the flattened scene's area lights: (count, pointer to RtAreaLightDesc or None)"""
+        ptr = C.POINTER(RtAreaLightDesc)()
+        n = self._lib.rth_scene_area_lights(self._h, C.byref(ptr))
         return n, (ptr if n else None)
 
     @property

@@ -31,6 +31,14 @@ def refraction_descs(refractive):
     return descs
 
 
+def area_light_descs(area_lights):
+    """(object, samples, radius) tuples -> an RtAreaLightDesc array (include/rt_capi_soft.h)."""
+    descs = (capi.RtAreaLightDesc * max(len(area_lights), 1))()
+    for k, (obj, n, r) in enumerate(area_lights):
+        descs[k] = capi.RtAreaLightDesc(obj, n, r)
+    return descs
+
+
 class Renderer:
     """Owns an ``rt_scene`` (device tables for one HostScene on one GPU)."""
 
@@ -40,7 +48,11 @@ class Renderer:
         self._scene = C.c_void_p()
         n_images, images = host_scene.images        # the scene's Texture_Image objects (include/rt_capi_texture.h)
         n_refr, refr = host_scene.refractions       # its refractive materials (include/rt_capi_refract.h)
-        if n_refr:
+        n_soft, soft = host_scene.area_lights       # its area lights (include/rt_capi_soft.h)
+        if n_soft:
+            capi.check(self._lib.rt_scene_create_soft(host_scene.desc, n_images, images, n_refr, refr, n_soft, soft, device,
+                                                      C.byref(self._scene)))
+        elif n_refr:
             capi.check(self._lib.rt_scene_create_refractive(host_scene.desc, n_images, images, n_refr, refr, device,
                                                             C.byref(self._scene)))
         elif n_images:
@@ -50,18 +62,29 @@ class Renderer:
         self._cam = host_scene.camera
 
     @classmethod
-    def from_desc(cls, desc, camera, device=0, keepalive=None, images=None, refractive=None):
+    def from_desc(cls, desc, camera, device=0, keepalive=None, images=None, refractive=None, area_lights=None):
         """Build from raw RtSceneDesc / RtCameraDesc (tests with hand-made tables).  images (include/rt_capi_texture.h): a
         list of (texels, width, height, wrap) -- texels a float32 (texels_h, texels_w, 3) array, texels[j, i] texel (i, j),
         width / height the world size of one copy, wrap RT_TEX_WRAP_* -- that texture indices n_textures + k name.  With
         images (even an empty list) the scene is made by rt_scene_create_textured, else by rt_scene_create.  refractive
         (include/rt_capi_refract.h): a list of (object, tf, ior); with it (even an empty list) the scene is made by
-        rt_scene_create_refractive, with the images if any."""
+        rt_scene_create_refractive, with the images if any.  area_lights (include/rt_capi_soft.h): a list of (object,
+        samples, radius); with it (even an empty list) the scene is made by rt_scene_create_soft, with the images and the
+        refractive objects if any."""
         self = cls.__new__(cls)
         self._lib = capi.load_library()
         self._host = keepalive
         self._scene = C.c_void_p()
-        if refractive is not None:
+        if area_lights is not None:
+            arrays, descs = image_descs(images or [])
+            rdescs = refraction_descs(refractive or [])
+            adescs = area_light_descs(area_lights)
+            self._images = (arrays, descs, rdescs, adescs)
+            capi.check(self._lib.rt_scene_create_soft(
+                C.byref(desc), len(images or []), descs if images else None, len(refractive or []),
+                rdescs if refractive else None, len(area_lights), adescs if len(area_lights) else None, device,
+                C.byref(self._scene)))
+        elif refractive is not None:
             arrays, descs = image_descs(images or [])
             rdescs = refraction_descs(refractive)
             self._images = (arrays, descs, rdescs)
@@ -88,6 +111,10 @@ class Renderer:
             self.close()
         except Exception:
             pass
+
+    def set_shadow_seed(self, seed):
+        """the sampling seed of this scene's later launches (include/rt_capi_soft.h; 0 by default)"""
+        capi.check(self._lib.rt_scene_set_shadow_seed(self._scene, C.c_uint32(int(seed) & 0xFFFFFFFF)))
 
     def set_option(self, key, value):
         capi.check(self._lib.rt_set_option(self._scene, key.encode(), int(value)))
