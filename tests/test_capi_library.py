@@ -61,6 +61,24 @@ def test_library_exports_every_declared_symbol():
         assert int(re.search(r"#define %s (\d+)" % macro, text).group(1)) == fn()
 
 
+def test_library_defines_exactly_the_render_kernels_of_the_naming_rule():
+    """Every render kernel is rt_render_kernel<mode><family> (rt_tables.h, RENDER KERNELS): five table modes times 23
+    families, plus the two counting kernels -- each one built, none left over.  (rt_get_launch_info and the GPU tests name
+    them.)"""
+    import subprocess
+    modes = ["", "_items", "_large", "_clusters", "_clusters_wide"]
+    calls = ["", "_ssaa", "_rays", "_gbuffer"]                     # the colour families: camera, supersampled, ray batch, G-buffer
+    families = (calls + ["_hits", "_occluded"] + [c + "_image" for c in calls + ["_hits"]] + [c + "_refract" for c in calls]
+                + [c + shading for shading in ("_soft", "_refract_soft") for c in calls])
+    assert len(families) == 23
+    expected = {"rt_render_kernel" + m + f for m in modes for f in families}
+    expected |= {"rt_render_kernel_stats", "rt_render_kernel_fast_stats"}
+    r = subprocess.run(["nm", "-D", "--defined-only", capi.library_path()], capture_output=True, text=True, check=True)
+    built = {line.split()[-1] for line in r.stdout.splitlines() if line.split() and line.split()[-1].startswith("rt_render_kernel")}
+    assert len(expected) == 117
+    assert built == expected, (sorted(built - expected), sorted(expected - built))
+
+
 def test_headers_are_plain_c(tmp_path):
     """The boundary is a C ABI: both headers compile as C99 with warnings as errors (a maintainer of the reference, or any FFI
     generator, includes them from C)."""

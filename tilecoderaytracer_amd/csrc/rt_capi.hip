@@ -27,88 +27,14 @@
 #include "../../include/rt_capi_tuning.h"
 #include "rt_tables.h"
 
-#define RT_DECLARE_KERNEL(name)                                                                                   \
-    extern "C" __global__ void name(const RtParams p, const float4 *__restrict__ image, float *__restrict__ out, \
-                                    unsigned int *__restrict__ tile_counter, float4 *__restrict__ bounce_stack,  \
-                                    unsigned int *__restrict__ help_area)
-#define RT_DECLARE_STATS_KERNEL(name)                                                                             \
-    extern "C" __global__ void name(const RtParams p, const float4 *__restrict__ image, float *__restrict__ out, \
-                                    unsigned int *__restrict__ tile_counter, float4 *__restrict__ bounce_stack,  \
-                                    unsigned long long *__restrict__ stats_out, unsigned int *__restrict__ help_area)
-RT_DECLARE_KERNEL(rt_render_kernel);                  /* FAST tables (scenes without clustered runs) */
-RT_DECLARE_KERNEL(rt_render_kernel_items);            /* the two item tables, no clustered runs      */
-RT_DECLARE_KERNEL(rt_render_kernel_large);            /* tables in global memory                     */
-RT_DECLARE_KERNEL(rt_render_kernel_clusters);         /* clustered sphere runs, six wavefronts per SIMD */
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide);    /* ... five */
-RT_DECLARE_KERNEL(rt_render_kernel_ssaa);             /* the same five, supersampled (rt_kernel_ssaa.hip) */
-RT_DECLARE_KERNEL(rt_render_kernel_items_ssaa);
-RT_DECLARE_KERNEL(rt_render_kernel_large_ssaa);
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_ssaa);
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_ssaa);
-RT_DECLARE_KERNEL(rt_render_kernel_rays);             /* ... over a caller's rays (rt_kernel_rays.hip) */
-RT_DECLARE_KERNEL(rt_render_kernel_items_rays);
-RT_DECLARE_KERNEL(rt_render_kernel_large_rays);
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_rays);
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_rays);
-RT_DECLARE_KERNEL(rt_render_kernel_hits);             /* ... asking about a caller's rays (rt_kernel_query.hip) */
-RT_DECLARE_KERNEL(rt_render_kernel_items_hits);
-RT_DECLARE_KERNEL(rt_render_kernel_large_hits);
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_hits);
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_hits);
-RT_DECLARE_KERNEL(rt_render_kernel_occluded);
-RT_DECLARE_KERNEL(rt_render_kernel_items_occluded);
-RT_DECLARE_KERNEL(rt_render_kernel_large_occluded);
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_occluded);
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_occluded);
-RT_DECLARE_KERNEL(rt_render_kernel_gbuffer);          /* ... a camera's frame with each pixel's hit record (rt_kernel_gbuffer.hip) */
-RT_DECLARE_KERNEL(rt_render_kernel_items_gbuffer);
-RT_DECLARE_KERNEL(rt_render_kernel_large_gbuffer);
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_gbuffer);
-RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide_gbuffer);
-/* ... with image textures (rt_kernel_texture.hip): the *_image sibling of each of the above but the *_occluded ones */
-#define RT_DECLARE_IMAGE_KERNELS(suffix)                      \
-    RT_DECLARE_KERNEL(rt_render_kernel##suffix##_image);       \
-    RT_DECLARE_KERNEL(rt_render_kernel_items##suffix##_image); \
-    RT_DECLARE_KERNEL(rt_render_kernel_large##suffix##_image); \
-    RT_DECLARE_KERNEL(rt_render_kernel_clusters##suffix##_image); \
-    RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide##suffix##_image)
-RT_DECLARE_IMAGE_KERNELS();
-RT_DECLARE_IMAGE_KERNELS(_ssaa);
-RT_DECLARE_IMAGE_KERNELS(_rays);
-RT_DECLARE_IMAGE_KERNELS(_hits);
-RT_DECLARE_IMAGE_KERNELS(_gbuffer);
-/* ... with refraction (rt_kernel_refract.hip): the *_refract sibling of the camera, supersampling, ray-batch and G-buffer kernels */
-#define RT_DECLARE_REFRACT_KERNELS(suffix)                      \
-    RT_DECLARE_KERNEL(rt_render_kernel##suffix##_refract);       \
-    RT_DECLARE_KERNEL(rt_render_kernel_items##suffix##_refract); \
-    RT_DECLARE_KERNEL(rt_render_kernel_large##suffix##_refract); \
-    RT_DECLARE_KERNEL(rt_render_kernel_clusters##suffix##_refract); \
-    RT_DECLARE_KERNEL(rt_render_kernel_clusters_wide##suffix##_refract)
-RT_DECLARE_REFRACT_KERNELS();
-RT_DECLARE_REFRACT_KERNELS(_ssaa);
-RT_DECLARE_REFRACT_KERNELS(_rays);
-RT_DECLARE_REFRACT_KERNELS(_gbuffer);
-/* ... with area lights (rt_kernel_soft.hip): the *_soft and *_refract_soft siblings; one more argument, the sampling seed */
-#define RT_DECLARE_SOFT_KERNEL(name)                                                                              \
-    extern "C" __global__ void name(const RtParams p, const float4 *__restrict__ image, float *__restrict__ out, \
-                                    unsigned int *__restrict__ tile_counter, float4 *__restrict__ bounce_stack,  \
-                                    unsigned int *__restrict__ help_area, const uint32_t shadow_seed)
-#define RT_DECLARE_SOFT_KERNELS(suffix)                                   \
-    RT_DECLARE_SOFT_KERNEL(rt_render_kernel##suffix);                      \
-    RT_DECLARE_SOFT_KERNEL(rt_render_kernel_items##suffix);                \
-    RT_DECLARE_SOFT_KERNEL(rt_render_kernel_large##suffix);                \
-    RT_DECLARE_SOFT_KERNEL(rt_render_kernel_clusters##suffix);             \
-    RT_DECLARE_SOFT_KERNEL(rt_render_kernel_clusters_wide##suffix)
-RT_DECLARE_SOFT_KERNELS(_soft);
-RT_DECLARE_SOFT_KERNELS(_ssaa_soft);
-RT_DECLARE_SOFT_KERNELS(_rays_soft);
-RT_DECLARE_SOFT_KERNELS(_gbuffer_soft);
-RT_DECLARE_SOFT_KERNELS(_refract_soft);
-RT_DECLARE_SOFT_KERNELS(_ssaa_refract_soft);
-RT_DECLARE_SOFT_KERNELS(_rays_refract_soft);
-RT_DECLARE_SOFT_KERNELS(_gbuffer_refract_soft);
-RT_DECLARE_STATS_KERNEL(rt_render_kernel_stats);      /* the counting builds */
-RT_DECLARE_STATS_KERNEL(rt_render_kernel_fast_stats);
+/* the render kernels (rt_tables.h, RENDER KERNELS), as rt_kernel.hip defines them */
+#define RT_DECLARE_KERNEL(mode, global_tables, clusters, roomy, fast, block_bound, waves, waves_soft,                          \
+                          family, ssaa, rays, query, gbuffer, images, refract, soft, seeded)                                   \
+    extern "C" __global__ void rt_render_kernel##mode##family(RT_KERNEL_ARGS RT_SEED_PARAM_##seeded);
+#define RT_DECLARE_FAMILY(...) RT_TABLE_MODES(RT_DECLARE_KERNEL, __VA_ARGS__)
+RT_RENDER_FAMILIES(RT_DECLARE_FAMILY)
+extern "C" __global__ void rt_render_kernel_stats(RT_KERNEL_ARGS_STATS);        /* the counting builds */
+extern "C" __global__ void rt_render_kernel_fast_stats(RT_KERNEL_ARGS_STATS);
 
 /* the kernels' view of RtParams: the ray-batch fields took the place of the supersampling padding, nothing else moved; the
  * G-buffer's record pointer shares the ray batch's place */
@@ -1532,77 +1458,66 @@ void learned_start_row(const rt_scene *s, int W, int H, int x0, int x1, int max_
 }
 
 struct Kernel { const void *fn; const char *name; bool seeded = false; };    /* seeded: takes the sampling seed (SOFT SHADOWS) */
-#define RT_KERNEL(k) Kernel{(const void *)k, #k}
-#define RT_SOFT_KERNEL(k) Kernel{(const void *)k, #k, true}
-/* a kernel and its supersampling, ray-batch, ray-query and G-buffer siblings; with image textures the *_image siblings (the
- * occlusion query reads no colour and keeps its kernel) */
-struct Siblings { Kernel plain, ssaa, rays, hits, occluded, gbuffer; };
-#define RT_SIBLINGS_IMAGE(k)                                                                                              \
-    Siblings{RT_KERNEL(k##_image), RT_KERNEL(k##_ssaa_image), RT_KERNEL(k##_rays_image), RT_KERNEL(k##_hits_image), \
-             RT_KERNEL(k##_occluded), RT_KERNEL(k##_gbuffer_image)}
-/* with refraction the *_refract siblings: the name of the kernel the same call runs on a scene with neither images nor
- * refraction, + "_refract" (the ray queries answer geometry: the *_image ones, which sample the same tables) */
-#define RT_SIBLINGS_REFRACT(k)                                                                                              \
-    Siblings{RT_KERNEL(k##_refract), RT_KERNEL(k##_ssaa_refract), RT_KERNEL(k##_rays_refract), RT_KERNEL(k##_hits_image), \
-             RT_KERNEL(k##_occluded), RT_KERNEL(k##_gbuffer_refract)}
-/* with area lights the *_soft siblings: the name of the kernel the same call runs on the scene packed as an image scene without
- * them, + "_soft" (the ray queries answer geometry: the *_image ones) */
-#define RT_SIBLINGS_SOFT(k, r)                                                                                            \
-    Siblings{RT_SOFT_KERNEL(k##r##_soft), RT_SOFT_KERNEL(k##_ssaa##r##_soft), RT_SOFT_KERNEL(k##_rays##r##_soft),           \
-             RT_KERNEL(k##_hits_image), RT_KERNEL(k##_occluded), RT_SOFT_KERNEL(k##_gbuffer##r##_soft)}
-#define RT_SIBLINGS(k)                                                                                              \
-    Siblings{RT_KERNEL(k), RT_KERNEL(k##_ssaa), RT_KERNEL(k##_rays), RT_KERNEL(k##_hits), RT_KERNEL(k##_occluded), \
-             RT_KERNEL(k##_gbuffer)}
+#define RT_KERNEL(k, seeded) Kernel{(const void *)k, #k, seeded}
 
-/* the kernel: FAST tables, item tables, the one for clustered scenes (in the register budget that fits the occupancy LDS
- * allows), or the large-scene one; supersampled (ssaa) or over a ray batch (rays): the *_ssaa or *_rays sibling of the same;
- * a ray batch's query (RT_QUERY_*): the *_hits or *_occluded sibling; a camera frame with hit records (gbuffer): the *_gbuffer
- * sibling */
-Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int block, int lds_bytes, bool ssaa = false,
-                     bool rays = false, int query = RT_QUERY_NONE, bool gbuffer = false) {
-    const bool fast_tables = s->base.n_fast_items > 0;
-    if (counting) return fast_tables ? RT_KERNEL(rt_render_kernel_fast_stats) : RT_KERNEL(rt_render_kernel_stats);
-    const auto pick = [&](const Siblings &k) {
-        if (query == RT_QUERY_HITS) return k.hits;
-        if (query == RT_QUERY_OCCLUDED) return k.occluded;
-        if (gbuffer) return k.gbuffer;
-        return ssaa ? k.ssaa : (rays ? k.rays : k.plain);
-    };
-    if (s->soft_used && s->refract_used) {
-        if (global_tables) return pick(RT_SIBLINGS_SOFT(rt_render_kernel_large, _refract));
-        if (s->n_clusters > 0 && s->pairs_opt) {
-            const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
-            return wide ? pick(RT_SIBLINGS_SOFT(rt_render_kernel_clusters_wide, _refract))
-                        : pick(RT_SIBLINGS_SOFT(rt_render_kernel_clusters, _refract));
-        }
-        return fast_tables ? pick(RT_SIBLINGS_SOFT(rt_render_kernel, _refract)) : pick(RT_SIBLINGS_SOFT(rt_render_kernel_items, _refract));
-    }
-    if (s->soft_used) {
-        if (global_tables) return pick(RT_SIBLINGS_SOFT(rt_render_kernel_large, ));
-        if (s->n_clusters > 0 && s->pairs_opt) {
-            const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
-            return wide ? pick(RT_SIBLINGS_SOFT(rt_render_kernel_clusters_wide, )) : pick(RT_SIBLINGS_SOFT(rt_render_kernel_clusters, ));
-        }
-        return fast_tables ? pick(RT_SIBLINGS_SOFT(rt_render_kernel, )) : pick(RT_SIBLINGS_SOFT(rt_render_kernel_items, ));
-    }
-    if (s->refract_used) {
-        if (global_tables) return pick(RT_SIBLINGS_REFRACT(rt_render_kernel_large));
-        if (s->n_clusters > 0 && s->pairs_opt) {
-            const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
-            return wide ? pick(RT_SIBLINGS_REFRACT(rt_render_kernel_clusters_wide)) : pick(RT_SIBLINGS_REFRACT(rt_render_kernel_clusters));
-        }
-        return fast_tables ? pick(RT_SIBLINGS_REFRACT(rt_render_kernel)) : pick(RT_SIBLINGS_REFRACT(rt_render_kernel_items));
-    }
-    const bool img = s->images_used;
-    if (global_tables) return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel_large) : RT_SIBLINGS(rt_render_kernel_large));
-    if (s->n_clusters > 0 && s->pairs_opt) {
+/* the catalogue's table modes and families (rt_tables.h, RENDER KERNELS): kMode is the FAST tables' mode, kFamily the camera's
+ * plain frame; the others are named by their suffix */
+enum TableMode {
+#define RT_MODE_ENUM(mode, ...) kMode##mode,
+    RT_TABLE_MODES(RT_MODE_ENUM, ) kModes
+};
+enum Family {
+#define RT_FAMILY_ENUM(family, ...) kFamily##family,
+    RT_RENDER_FAMILIES(RT_FAMILY_ENUM) kFamilies
+};
+/* every render kernel but the counting ones, [family][mode] */
+#define RT_KERNEL_ENTRY(mode, global_tables, clusters, roomy, fast, block_bound, waves, waves_soft,                            \
+                        family, ssaa, rays, query, gbuffer, images, refract, soft, seeded)                                     \
+    RT_KERNEL(rt_render_kernel##mode##family, seeded),
+#define RT_KERNEL_ROW(...) {RT_TABLE_MODES(RT_KERNEL_ENTRY, __VA_ARGS__)},
+const Kernel kKernels[kFamilies][kModes] = {RT_RENDER_FAMILIES(RT_KERNEL_ROW)};
+
+/* the clustered-scene kernels (PAIRS, HELP): for scenes with clustered sphere runs whose tables are in LDS */
+bool clusters_mode(const rt_scene *s, bool global_tables) { return !global_tables && s->n_clusters > 0 && s->pairs_opt; }
+
+/* the table mode: the large-scene kernel, the one for clustered scenes (in the register budget that fits the occupancy LDS
+ * allows), FAST tables or item tables */
+TableMode table_mode(const rt_scene *s, bool global_tables, int block, int lds_bytes) {
+    if (global_tables) return kMode_large;
+    if (clusters_mode(s, global_tables)) {
         /* the 96-register kernel when LDS leaves room for fewer than six wavefronts per SIMD anyway (24 per CU) */
         const bool wide = s->wide_opt >= 0 ? s->wide_opt != 0 : (RT_MAX_LDS_BYTES / (size_t)lds_bytes) * (size_t)(block / 64) < 24;
-        if (wide) return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel_clusters_wide) : RT_SIBLINGS(rt_render_kernel_clusters_wide));
-        return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel_clusters) : RT_SIBLINGS(rt_render_kernel_clusters));
+        return wide ? kMode_clusters_wide : kMode_clusters;
     }
-    if (fast_tables) return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel) : RT_SIBLINGS(rt_render_kernel));
-    return pick(img ? RT_SIBLINGS_IMAGE(rt_render_kernel_items) : RT_SIBLINGS(rt_render_kernel_items));
+    return s->base.n_fast_items > 0 ? kMode : kMode_items;
+}
+
+/* The family rule: the call -- plain, supersampled (ssaa), over a ray batch (rays), a ray batch's query (RT_QUERY_*), a camera
+ * frame with hit records (gbuffer) -- on the scene's shading: none, image textures, refraction, area lights, both of the last
+ * (refractive and area-light scenes are packed as image scenes).  The one irregularity: the ray queries answer geometry, so
+ * with any shading a nearest-hit query takes the *_hits_image kernel, which samples the same tables, and an occlusion query,
+ * which reads no colour, always the plain *_occluded one. */
+Family family(const rt_scene *s, bool ssaa, bool rays, int query, bool gbuffer) {
+    enum { kNone, kImage, kRefract, kSoft, kRefractSoft };
+    const int shading = s->soft_used ? (s->refract_used ? kRefractSoft : kSoft)
+                                     : (s->refract_used ? kRefract : (s->images_used ? kImage : kNone));
+    if (query == RT_QUERY_HITS) return shading == kNone ? kFamily_hits : kFamily_hits_image;
+    if (query == RT_QUERY_OCCLUDED) return kFamily_occluded;
+    static const Family kByShading[4][5] = {      /* [plain, ssaa, rays, gbuffer][shading] */
+        {kFamily, kFamily_image, kFamily_refract, kFamily_soft, kFamily_refract_soft},
+        {kFamily_ssaa, kFamily_ssaa_image, kFamily_ssaa_refract, kFamily_ssaa_soft, kFamily_ssaa_refract_soft},
+        {kFamily_rays, kFamily_rays_image, kFamily_rays_refract, kFamily_rays_soft, kFamily_rays_refract_soft},
+        {kFamily_gbuffer, kFamily_gbuffer_image, kFamily_gbuffer_refract, kFamily_gbuffer_soft, kFamily_gbuffer_refract_soft},
+    };
+    return kByShading[gbuffer ? 3 : (ssaa ? 1 : (rays ? 2 : 0))][shading];
+}
+
+/* the kernel of a launch: the counting build's, or the family's kernel in the table mode */
+Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int block, int lds_bytes, bool ssaa, bool rays,
+                     int query, bool gbuffer) {
+    if (counting)
+        return s->base.n_fast_items > 0 ? RT_KERNEL(rt_render_kernel_fast_stats, false) : RT_KERNEL(rt_render_kernel_stats, false);
+    return kKernels[family(s, ssaa, rays, query, gbuffer)][table_mode(s, global_tables, block, lds_bytes)];
 }
 
 /* Everything a launch decides before it touches the device. */
@@ -1659,8 +1574,9 @@ int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int 
     plan->tiles = t;
     plan->n_tiles = n_tiles;
     if (n_tiles == 0) return RT_OK;
-    const bool clusters_kernel = !counting && !bc.global_tables && s->n_clusters > 0 && s->pairs_opt;
     const int query = rays ? rays->query : RT_QUERY_NONE;
+    /* (only whether the kernel is a clustered-scene one: which of the two, wide or not, depends on the LDS the desk adds) */
+    const bool clusters_kernel = !counting && clusters_mode(s, bc.global_tables);
     help_desk(s, clusters_kernel && query == RT_QUERY_NONE, W, x0, x1, bc.block, bc.stack_lds_levels, p, &plan->lds_bytes);
     p.tile_prio = tile_prio(s, W, x0, x1);
     heavy_band(s, cam, W, H, x0, x1, t, p);

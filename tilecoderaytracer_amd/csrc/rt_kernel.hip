@@ -29,8 +29,9 @@
  *    nothing else to do (HELP), and the tiles known to be long are rendered one per
  *    workgroup from the start (HEAVY tiles).  The same tests on the same operands;
  *    nearest = minimum of (distance, Scene index), shadow = OR.
- *  - One body, several __global__ entry points (bottom of the file); the host
- *    picks by scene (rt_capi.hip, launch()).
+ *  - One body, many __global__ entry points (bottom of the file, from the
+ *    catalogue in rt_tables.h); the host picks by scene and call
+ *    (rt_capi.hip, choose_kernel()).
  *
  * Arithmetic contract: IEEE-754 binary32, no FMA contraction
  * (-ffp-contract=off and the pragma below), correctly rounded '/' and sqrtf
@@ -2942,16 +2943,6 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
     (void)by_value;                                                                                 \
     const RtParams &name = *(const RtParams *)(__builtin_amdgcn_kernarg_segment_ptr())
 
-/* All render kernels share one signature.  `help_area`: the clustered-scene kernels' HELP areas (128 quads of
- * global memory per workgroup for the rays a wavefront publishes at its workgroup's desk); unused by the others. */
-#define RT_KERNEL_ARGS                                                                                            \
-    const RtParams p_in_kernarg, const float4 *__restrict__ image, float *__restrict__ out,                      \
-    unsigned int *__restrict__ tile_counter, float4 *__restrict__ bounce_stack, unsigned int *__restrict__ help_area
-#define RT_KERNEL_ARGS_STATS                                                                                      \
-    const RtParams p_in_kernarg, const float4 *__restrict__ image, float *__restrict__ out,                      \
-    unsigned int *__restrict__ tile_counter, float4 *__restrict__ bounce_stack,                                   \
-    unsigned long long *__restrict__ stats_out, unsigned int *__restrict__ help_area
-
 /* launch bounds: wavefronts per SIMD of the kernels for scenes without clustered sphere runs, of the clustered-scene kernels and
  * of their wide variant; the clustered-scene kernels' largest workgroup */
 #ifndef RT_WAVES_PER_SIMD
@@ -2967,53 +2958,26 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
 #define RT_BLOCK_BOUND_CLUSTERS 512
 #endif
 
-/* rt_kernel_ssaa.hip, rt_kernel_rays.hip, rt_kernel_query.hip, rt_kernel_gbuffer.hip and rt_kernel_texture.hip include this
- * file for the body alone and define the supersampling, the ray-batch, the ray-query, the G-buffer and the image-texture kernels: in translation units of their own, the seven kernels below compile to the code they have without them (next to five more instantiations of the
- * body in one module, the item-table kernel's allocation moved: one more spilled scalar) */
-#ifndef RT_KERNEL_BODY_ONLY
+/* The render kernels (rt_tables.h, RENDER KERNELS): this file alone is the base unit, rt_kernel.o; with -DRT_KERNEL_TU=<unit>
+ * it is that unit, rt_kernel_<unit>.o.  A unit defines its families in all five table modes, in the catalogue's order. */
+#define RT_SEED_ARG_false 0u
+#define RT_SEED_ARG_true shadow_seed
+#define RT_DEFINE_KERNEL(mode, global_tables, clusters, roomy, fast, block_bound, waves, waves_soft,                           \
+                         family, ssaa, rays, query, gbuffer, images, refract, soft, seeded)                                    \
+    extern "C" __global__ void __launch_bounds__(block_bound, (soft ? waves_soft : waves))                                     \
+    rt_render_kernel##mode##family(RT_KERNEL_ARGS RT_SEED_PARAM_##seeded) {                                                    \
+        RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);                                                                               \
+        render_body<false, global_tables, clusters, roomy, fast, ssaa, rays, query, gbuffer, images, refract, soft>(            \
+            p, image, out, tile_counter, bounce_stack, nullptr, help_area, RT_SEED_ARG_##seeded);                              \
+    }
+#define RT_DEFINE_FAMILY(...) RT_TABLE_MODES(RT_DEFINE_KERNEL, __VA_ARGS__)
+#define RT_UNIT(unit) RT_UNIT_OF(unit)
+#define RT_UNIT_OF(unit) RT_UNIT_##unit
 
-/* Scenes without clustered sphere runs, FAST tables (the built-in scene: the bench headline).  72 VGPRs: seven
- * wavefronts per SIMD where LDS allows (the bounce stack keeps its LDS place up to seven workgroups per CU,
- * RT_STACK_LDS_SHARE) */
-extern "C" __global__ void __launch_bounds__(RT_BLOCK_BOUND, RT_WAVES_PER_SIMD)
-rt_render_kernel(RT_KERNEL_ARGS) {
-#ifdef RT_FAST_PARAMS_BY_VALUE
-    const RtParams &p = p_in_kernarg;
+#ifdef RT_KERNEL_TU
+RT_UNIT(RT_KERNEL_TU)(RT_DEFINE_FAMILY)
 #else
-    RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);
-#endif
-    render_body<false, false, false, false, true>(p, image, out, tile_counter, bounce_stack, nullptr, help_area);
-}
-
-/* the same over the two item tables: option "fast" = 0, and option "cull" = 0 (the plain in-order scans) */
-extern "C" __global__ void __launch_bounds__(RT_BLOCK_BOUND, RT_WAVES_PER_SIMD)
-rt_render_kernel_items(RT_KERNEL_ARGS) {
-    RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);
-    render_body<false>(p, image, out, tile_counter, bounce_stack, nullptr, help_area);
-}
-
-/* scenes whose tables are large (or do not fit LDS at all): the tables stay in global memory */
-extern "C" __global__ void __launch_bounds__(RT_BLOCK_BOUND, RT_WAVES_PER_SIMD)
-rt_render_kernel_large(RT_KERNEL_ARGS) {
-    RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);
-    render_body<false, true>(p, image, out, tile_counter, bounce_stack, nullptr, help_area);
-}
-
-/* scenes with clustered sphere runs (PAIRS, NEAREST PAIRS, HELP, HEAVY tiles): 80 registers, six wavefronts per SIMD
- * (workgroups of up to eight wavefronts: scenes whose tables are large share one LDS copy among more of them, launch() in rt_capi.hip) */
-extern "C" __global__ void __launch_bounds__(RT_BLOCK_BOUND_CLUSTERS, RT_WAVES_PER_SIMD_CLUSTERS)
-rt_render_kernel_clusters(RT_KERNEL_ARGS) {
-    RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);
-    render_body<false, false, true>(p, image, out, tile_counter, bounce_stack, nullptr, help_area);
-}
-
-/* the same with the registers of five wavefronts per SIMD, for scenes whose tables leave room for no more than
- * five workgroups per CU anyway (the 1 024-sphere grid: 31.5 KB); the pair flush tests four members abreast here */
-extern "C" __global__ void __launch_bounds__(RT_BLOCK_BOUND_CLUSTERS, RT_WAVES_PER_SIMD_WIDE)
-rt_render_kernel_clusters_wide(RT_KERNEL_ARGS) {
-    RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);
-    render_body<false, false, true, true>(p, image, out, tile_counter, bounce_stack, nullptr, help_area);
-}
+RT_UNIT_base(RT_DEFINE_FAMILY)
 
 /* the counting builds (rt_render_stats): same arithmetic and control flow plus work counters.  One for the item
  * tables -- with and without clustered runs: the clustered-scene body, which is the plain one when a scene has no
@@ -3029,4 +2993,4 @@ rt_render_kernel_fast_stats(RT_KERNEL_ARGS_STATS) {
     RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);
     render_body<true, false, false, false, true>(p, image, out, tile_counter, bounce_stack, stats_out, help_area);
 }
-#endif /* RT_KERNEL_BODY_ONLY */
+#endif /* RT_KERNEL_TU */

@@ -148,7 +148,7 @@ enum { RT_DESK_STATE = 0, RT_DESK_CURSOR, RT_DESK_INSIDE, RT_DESK_FINISHED, RT_D
  * light that is not an area light has {0, 2, bits(1), 0} and keeps the hard shadow.  Its quad offset is bits of the y word of
  * the header quad right before the materials (the one whose x word holds the refraction rows' offset; 0 there when the scene
  * has no refraction).  The launch's sampling seed is not in the image: the *_soft kernels take it as one more kernel argument
- * behind the ones every render kernel shares (rt_kernel_soft.hip). */
+ * behind the ones every render kernel shares (RENDER KERNELS, below). */
 #define RT_SOFT_QUADS 1
 
 #define RT_PRIMARY_ITEMS 64          /* scenes with more FAST items than this have no PRIMARY table */
@@ -277,5 +277,89 @@ enum { RT_QUERY_NONE = 0, RT_QUERY_HITS = 1, RT_QUERY_OCCLUDED = 2 };
  *            wavefront's dispatch on the kind and the index for ties never touch a vector register) */
 #define RT_FAST_BOX_QUADS 2
 #define RT_FAST_REC_QUADS 2
+
+/* RENDER KERNELS.  Every render kernel but the two counting ones (rt_render_kernel_stats, _fast_stats) is
+ * rt_render_kernel<mode><family>: one of the five TABLE MODES below times one of the FAMILIES after them, all of it the one
+ * body of rt_kernel.hip (render_body<kStats = false, kGlobalTables, kClusters, kRoomy, kFast, kSsaa, kRays, kQuery, kGbuffer,
+ * kImages, kRefract, kSoft>).  rt_kernel.hip defines them, rt_capi.hip declares them and picks one per launch
+ * (choose_kernel()); both expand these lists, so a new family is one line here plus the host's family rule.
+ *
+ * RT_TABLE_MODES(X, family...): X(mode suffix, kGlobalTables, kClusters, kRoomy, kFast, workgroup bound, wavefronts per SIMD,
+ * wavefronts per SIMD of the soft families, family...) -- the launch bounds' names are rt_kernel.hip's.
+ *   ""              FAST tables (scenes without clustered sphere runs; the built-in scene, the bench headline): 72 VGPRs, seven
+ *                   wavefronts per SIMD where LDS allows (the bounce stack keeps its LDS place up to seven workgroups per CU,
+ *                   RT_STACK_LDS_SHARE)
+ *   _items          the same over the two item tables: option "fast" = 0, and option "cull" = 0 (the plain in-order scans)
+ *   _large          scenes whose tables are large (or do not fit LDS at all): the tables stay in global memory.  These need
+ *                   52-62 VGPRs and so run 8 wavefronts per SIMD although their bound asks for RT_WAVES_PER_SIMD only; the
+ *                   sample loop would take their soft siblings to 72 registers and 7 wavefronts, so those ask for the 8 their
+ *                   siblings reach (no *_soft kernel runs below its sibling's occupancy)
+ *   _clusters       scenes with clustered sphere runs (PAIRS, NEAREST PAIRS, HELP, HEAVY tiles): 80 registers, six wavefronts per
+ *                   SIMD (workgroups of up to eight wavefronts: scenes whose tables are large share one LDS copy among more of
+ *                   them, launch_block() in rt_capi.hip)
+ *   _clusters_wide  the same with the registers of five wavefronts per SIMD, for scenes whose tables leave room for no more
+ *                   than five workgroups per CU anyway (the 1 024-sphere grid: 31.5 KB); the pair flush tests four members
+ *                   abreast here */
+#define RT_TABLE_MODES(X, ...)                                                                                                \
+    X(,               false, false, false, true,  RT_BLOCK_BOUND,          RT_WAVES_PER_SIMD,          RT_WAVES_PER_SIMD,          __VA_ARGS__) \
+    X(_items,         false, false, false, false, RT_BLOCK_BOUND,          RT_WAVES_PER_SIMD,          RT_WAVES_PER_SIMD,          __VA_ARGS__) \
+    X(_large,         true,  false, false, false, RT_BLOCK_BOUND,          RT_WAVES_PER_SIMD,          8,                          __VA_ARGS__) \
+    X(_clusters,      false, true,  false, false, RT_BLOCK_BOUND_CLUSTERS, RT_WAVES_PER_SIMD_CLUSTERS, RT_WAVES_PER_SIMD_CLUSTERS, __VA_ARGS__) \
+    X(_clusters_wide, false, true,  true,  false, RT_BLOCK_BOUND_CLUSTERS, RT_WAVES_PER_SIMD_WIDE,     RT_WAVES_PER_SIMD_WIDE,     __VA_ARGS__)
+
+/* The families, one list per translation unit of kernels: rt_kernel.hip is compiled once per unit (-DRT_KERNEL_TU=<unit>,
+ * rt_kernel_<unit>.o; the base unit is rt_kernel.o), each unit's kernels in this order.  The split is part of the speed
+ * contract: next to more instances of the body in one module the item-table kernel's register allocation moved (one more
+ * spilled scalar), and a unit of its own keeps each kernel's code what it is alone.
+ * X(family suffix, kSsaa, kRays, kQuery, kGbuffer, kImages, kRefract, kSoft, takes the sampling seed)
+ *   base     the camera's frame
+ *   ssaa     include/rt_capi_ssaa.h: the virtual kW x kH image of k x k samples per pixel, averaged at the store
+ *   rays     include/rt_capi_rays.h: a caller's rays instead of a camera's
+ *   query    include/rt_capi_query.h: one question per ray of a batch -- getCollision's record, or a segment's shadow verdict
+ *   gbuffer  include/rt_capi_gbuffer.h: a camera's frame and, beside each pixel, the rt_hit record of its camera ray
+ *   texture  include/rt_capi_texture.h: the *_image sibling of the above but the occlusion query (which reads no colour)
+ *   refract  include/rt_capi_refract.h: the *_refract sibling of the colour families, the image body walking a ray tree
+ *   soft     include/rt_capi_soft.h: the *_soft and *_refract_soft siblings, the image body sampling area lights; the
+ *            launch's sampling seed is one more kernel argument behind the shared ones (RT_SEED_PARAM_true), so RtParams
+ *            and the other kernels' arguments do not change */
+#define RT_UNIT_base(X)     X(,                      false, false, RT_QUERY_NONE,     false, false, false, false, false)
+#define RT_UNIT_ssaa(X)     X(_ssaa,                 true,  false, RT_QUERY_NONE,     false, false, false, false, false)
+#define RT_UNIT_rays(X)     X(_rays,                 false, true,  RT_QUERY_NONE,     false, false, false, false, false)
+#define RT_UNIT_query(X)    X(_hits,                 false, true,  RT_QUERY_HITS,     false, false, false, false, false) \
+                            X(_occluded,             false, true,  RT_QUERY_OCCLUDED, false, false, false, false, false)
+#define RT_UNIT_gbuffer(X)  X(_gbuffer,              false, false, RT_QUERY_NONE,     true,  false, false, false, false)
+#define RT_UNIT_texture(X)  X(_image,                false, false, RT_QUERY_NONE,     false, true,  false, false, false) \
+                            X(_ssaa_image,           true,  false, RT_QUERY_NONE,     false, true,  false, false, false) \
+                            X(_rays_image,           false, true,  RT_QUERY_NONE,     false, true,  false, false, false) \
+                            X(_hits_image,           false, true,  RT_QUERY_HITS,     false, true,  false, false, false) \
+                            X(_gbuffer_image,        false, false, RT_QUERY_NONE,     true,  true,  false, false, false)
+#define RT_UNIT_refract(X)  X(_refract,              false, false, RT_QUERY_NONE,     false, true,  true,  false, false) \
+                            X(_ssaa_refract,         true,  false, RT_QUERY_NONE,     false, true,  true,  false, false) \
+                            X(_rays_refract,         false, true,  RT_QUERY_NONE,     false, true,  true,  false, false) \
+                            X(_gbuffer_refract,      false, false, RT_QUERY_NONE,     true,  true,  true,  false, false)
+#define RT_UNIT_soft(X)     X(_soft,                 false, false, RT_QUERY_NONE,     false, true,  false, true,  true)  \
+                            X(_ssaa_soft,            true,  false, RT_QUERY_NONE,     false, true,  false, true,  true)  \
+                            X(_rays_soft,            false, true,  RT_QUERY_NONE,     false, true,  false, true,  true)  \
+                            X(_gbuffer_soft,         false, false, RT_QUERY_NONE,     true,  true,  false, true,  true)  \
+                            X(_refract_soft,         false, false, RT_QUERY_NONE,     false, true,  true,  true,  true)  \
+                            X(_ssaa_refract_soft,    true,  false, RT_QUERY_NONE,     false, true,  true,  true,  true)  \
+                            X(_rays_refract_soft,    false, true,  RT_QUERY_NONE,     false, true,  true,  true,  true)  \
+                            X(_gbuffer_refract_soft, false, false, RT_QUERY_NONE,     true,  true,  true,  true,  true)
+#define RT_RENDER_FAMILIES(X)                                                                                                 \
+    RT_UNIT_base(X) RT_UNIT_ssaa(X) RT_UNIT_rays(X) RT_UNIT_query(X) RT_UNIT_gbuffer(X) RT_UNIT_texture(X) RT_UNIT_refract(X) \
+    RT_UNIT_soft(X)
+
+/* The render kernels' arguments.  `help_area`: the clustered-scene kernels' HELP areas (128 quads of global memory per
+ * workgroup for the rays a wavefront publishes at its workgroup's desk); unused by the others.  The counting kernels have
+ * `stats_out` before it; a family that takes the sampling seed has it last (RT_SEED_PARAM_<takes the seed>). */
+#define RT_KERNEL_ARGS                                                                                            \
+    const RtParams p_in_kernarg, const float4 *__restrict__ image, float *__restrict__ out,                      \
+    unsigned int *__restrict__ tile_counter, float4 *__restrict__ bounce_stack, unsigned int *__restrict__ help_area
+#define RT_KERNEL_ARGS_STATS                                                                                      \
+    const RtParams p_in_kernarg, const float4 *__restrict__ image, float *__restrict__ out,                      \
+    unsigned int *__restrict__ tile_counter, float4 *__restrict__ bounce_stack,                                   \
+    unsigned long long *__restrict__ stats_out, unsigned int *__restrict__ help_area
+#define RT_SEED_PARAM_false
+#define RT_SEED_PARAM_true , const uint32_t shadow_seed
 
 #endif /* RT_TABLES_H_ */
