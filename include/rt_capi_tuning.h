@@ -24,7 +24,8 @@ typedef struct rt_launch_info {
     int32_t scene_lds_bytes;    /* of which scene tables                                        */
     int32_t grid_blocks;        /* workgroups of the last launch                                */
     int32_t tile_x, tile_z;     /* pixels per wavefront tile (tile_x * tile_z == 64)            */
-    char    kernel[48];         /* name of the __global__ function the last launch ran (its first pass) */
+    char    kernel[48];         /* name of the __global__ function the last launch ran (its first pass), cut to 47 characters;
+                                 * rt_get_launch_kernel() (rt_capi_launch.h) gives the whole name */
 } rt_launch_info;
 
 /* Diagnostic "counting build" of rt_render (same arithmetic and control flow,

@@ -43,18 +43,18 @@ def _cross(a, b):
                      a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
 
 
-def visible_fraction(scene, P, key, level, ordinal, C, n, r):
-    """the header's (m, f) for the shading points P (n_pts, 3) with keys key (uint32), at ray-tree level `level`, towards the
-    light of ordinal `ordinal` with centre C, n x n samples, radius r"""
+def disc_samples(seed, P, key, level, ordinal, C, n, r):
+    """the header's n x n sample points on the disc of the light of ordinal `ordinal` (centre C, radius r) facing the shading
+    points P (n_pts, 3) with keys key (uint32), at ray-tree level `level`, the scene's seed `seed` -> float32 (n_pts, 3) for each
+    sample i * n + j, in that order"""
     _normalize = refract_ref._normalize
     with np.errstate(all="ignore"):
         L = _normalize(C[None, :] - P)
         A = np.where((np.abs(L[:, 0]) < F(0.5))[:, None], np.array([1, 0, 0], dtype=F), np.array([0, 1, 0], dtype=F))
         U = _normalize(_cross(A, L))
         V = _cross(L, U)
-        h = H(H(H(H(scene.seed ^ GOLDEN) ^ key) ^ U32(level)) ^ U32(ordinal))
+        h = H(H(H(H(U32(seed) ^ GOLDEN) ^ key) ^ U32(level)) ^ U32(ordinal))
         step = F(2.0) / F(n)
-        m = np.zeros(P.shape[0], dtype=np.int64)
         for i in range(n):
             for j in range(n):
                 hs = H(h ^ U32(i * n + j))
@@ -64,9 +64,16 @@ def visible_fraction(scene, P, key, level, ordinal, C, n, r):
                 b = (F(j) + xi2) * step - F(1.0)
                 dx = a * np.sqrt(F(1.0) - (b * b) * F(0.5))
                 dy = b * np.sqrt(F(1.0) - (a * a) * F(0.5))
-                Q = C[None, :] + (U * (r * dx)[:, None] + V * (r * dy)[:, None])
-                m += ~query_ref.occluded(scene, np.concatenate([P, Q], axis=1))
-        return m, (m.astype(F) / F(n * n))
+                yield C[None, :] + (U * (r * dx)[:, None] + V * (r * dy)[:, None])
+
+
+def visible_fraction(scene, P, key, level, ordinal, C, n, r):
+    """the header's (m, f) for the shading points P (n_pts, 3) with keys key (uint32), at ray-tree level `level`, towards the
+    light of ordinal `ordinal` with centre C, n x n samples, radius r"""
+    m = np.zeros(P.shape[0], dtype=np.int64)
+    for Q in disc_samples(scene.seed, P, key, level, ordinal, C, n, r):
+        m += ~query_ref.occluded(scene, np.concatenate([P, Q], axis=1))
+    return m, (m.astype(F) / F(n * n))
 
 
 def _pixel(scene, E, d, key, level, depth):

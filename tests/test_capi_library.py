@@ -61,22 +61,89 @@ def test_library_exports_every_declared_symbol():
         assert int(re.search(r"#define %s (\d+)" % macro, text).group(1)) == fn()
 
 
-def test_library_defines_exactly_the_render_kernels_of_the_naming_rule():
-    """Every render kernel is rt_render_kernel<mode><family> (rt_tables.h, RENDER KERNELS): five table modes times 23
-    families, plus the two counting kernels -- each one built, none left over.  (rt_get_launch_info and the GPU tests name
-    them.)"""
-    import subprocess
+def naming_rule_kernels():
+    """the render kernels but the counting ones by the naming rule: rt_render_kernel<mode><family>, five table modes times 23
+    families"""
     modes = ["", "_items", "_large", "_clusters", "_clusters_wide"]
     calls = ["", "_ssaa", "_rays", "_gbuffer"]                     # the colour families: camera, supersampled, ray batch, G-buffer
     families = (calls + ["_hits", "_occluded"] + [c + "_image" for c in calls + ["_hits"]] + [c + "_refract" for c in calls]
                 + [c + shading for shading in ("_soft", "_refract_soft") for c in calls])
     assert len(families) == 23
-    expected = {"rt_render_kernel" + m + f for m in modes for f in families}
+    return {"rt_render_kernel" + m + f for m in modes for f in families}
+
+
+def test_library_defines_exactly_the_render_kernels_of_the_naming_rule():
+    """Every render kernel is rt_render_kernel<mode><family> (rt_tables.h, RENDER KERNELS): five table modes times 23
+    families, plus the two counting kernels -- each one built, none left over.  (rt_get_launch_info and the GPU tests name
+    them.)"""
+    import subprocess
+    expected = naming_rule_kernels()
     expected |= {"rt_render_kernel_stats", "rt_render_kernel_fast_stats"}
     r = subprocess.run(["nm", "-D", "--defined-only", capi.library_path()], capture_output=True, text=True, check=True)
     built = {line.split()[-1] for line in r.stdout.splitlines() if line.split() and line.split()[-1].startswith("rt_render_kernel")}
     assert len(expected) == 117
     assert built == expected, (sorted(built - expected), sorted(expected - built))
+
+
+def catalogue():
+    """csrc/rt_tables.h, RENDER KERNELS: the table modes of RT_TABLE_MODES and the families of every RT_UNIT_<unit> list, each
+    the first argument of an X(...) -> (modes, families, the units in the order RT_RENDER_FAMILIES expands them)"""
+    text = open(os.path.join(ROOT, "tilecoderaytracer_amd", "csrc", "rt_tables.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    macros = {m.group(1): m.group(2).replace("\\\n", " ")
+              for m in re.finditer(r"^#define (\w+)\(X(?:, \.\.\.)?\)((?:[^\n]*\\\n)*[^\n]*)", text, flags=re.M)}
+
+    def firsts(body):
+        return [a.strip() for a in re.findall(r"\bX\(([^,]*),", body)]
+
+    units = sorted(k[len("RT_UNIT_"):] for k in macros if k.startswith("RT_UNIT_"))
+    expanded = re.findall(r"\bRT_UNIT_(\w+)\(X\)", macros["RT_RENDER_FAMILIES"])
+    assert sorted(expanded) == units, (expanded, units)      # every unit once, none that is not defined
+    families = [f for u in expanded for f in firsts(macros["RT_UNIT_" + u])]
+    return firsts(macros["RT_TABLE_MODES"]), families, expanded
+
+
+def test_the_kernel_matrix_is_the_catalogue():
+    """tests/kernel_matrix.py has one GPU case per render kernel of the catalogue -- each table mode times each family, none
+    missing, none extra -- and that catalogue is the naming rule's: a new family or mode without its GPU case fails here."""
+    import kernel_matrix
+    modes, families, units = catalogue()
+    assert modes == ["", "_items", "_large", "_clusters", "_clusters_wide"]
+    assert len(families) == len(set(families)) == 23 and len(units) == 8
+    want = {(m, f) for m in modes for f in families}
+    cases = [(c.mode, c.family) for c in kernel_matrix.CASES]
+    assert len(cases) == len(set(cases)), "a case twice"
+    assert set(cases) == want, (sorted(want - set(cases)), sorted(set(cases) - want))
+    assert {"rt_render_kernel" + m + f for m, f in want} == naming_rule_kernels()
+    assert {kernel_matrix.kernel_name(c) for c in kernel_matrix.CASES} == naming_rule_kernels()
+    assert len(kernel_matrix.CASES) == 115
+    assert set(kernel_matrix.MODES) == set(modes)
+    for c in kernel_matrix.CASES:                   # the scene's shading selects the family (rt_capi.hip, family())
+        if c.call == "hits":
+            assert (c.family == "_hits") == (c.shading == ""), c
+        elif c.call == "occluded":
+            assert c.family == "_occluded", c
+        else:
+            assert c.family == {"render": "", "ssaa": "_ssaa", "rays": "_rays", "gbuffer": "_gbuffer"}[c.call] + c.shading, c
+    clustered = [c for c in kernel_matrix.CASES if c.mode.startswith("_clusters") and c.shading == "_refract_soft"]
+    assert {"_occluded", "_hits_image"} <= {c.family for c in clustered}
+    assert {c.mode for c in kernel_matrix.CASES if c.deep} == set(modes)
+
+
+def test_launch_header_names_every_kernel_whole():
+    """include/rt_capi_launch.h: its two entry points, exported, its version, a buffer size that holds every catalogue name with
+    its NUL (rt_launch_info.kernel, 48 bytes, does not: it keeps the first 47 characters), and the checks that need no device."""
+    lib = capi.load_library()
+    assert declared_functions("rt_capi_launch.h") == ["rt_capi_launch_version", "rt_get_launch_kernel"]
+    text = open(os.path.join(ROOT, "include", "rt_capi_launch.h")).read()
+    assert int(re.search(r"#define RT_CAPI_LAUNCH_VERSION (\d+)", text).group(1)) == lib.rt_capi_launch_version() == 1
+    size = int(re.search(r"#define RT_KERNEL_NAME_BYTES (\d+)", text).group(1))
+    assert size == capi.RT_KERNEL_NAME_BYTES
+    longest = max(naming_rule_kernels(), key=len)
+    assert longest == "rt_render_kernel_clusters_wide_gbuffer_refract_soft" and len(longest) + 1 <= size
+    assert len(longest) + 1 > capi.RtLaunchInfo.kernel.size == 48
+    out = C.create_string_buffer(size)
+    assert lib.rt_get_launch_kernel(None, out, size) == capi.RT_ERR_INVALID
 
 
 def test_headers_are_plain_c(tmp_path):
@@ -87,8 +154,9 @@ def test_headers_are_plain_c(tmp_path):
     if not shutil.which("gcc"):
         pytest.skip("no gcc")
     src = tmp_path / "hdr.c"
-    src.write_text('#include "rt_capi.h"\n#include "rt_capi_tuning.h"\n'
-                   "int main(void) { unsigned char h[RT_SHARED_HANDLE_BYTES]; rt_multi_info i; (void)h; (void)i;\n"
+    src.write_text('#include "rt_capi.h"\n#include "rt_capi_tuning.h"\n#include "rt_capi_launch.h"\n'
+                   "int main(void) { unsigned char h[RT_SHARED_HANDLE_BYTES]; rt_multi_info i; char k[RT_KERNEL_NAME_BYTES];\n"
+                   "  (void)h; (void)i; (void)k;\n"
                    "  return (RT_MULTI_TRANSPORT_DIRECT == 2 && RT_CAPI_VERSION == 4) ? 0 : 1; }\n")
     r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
                         "-fsyntax-only", str(src)], capture_output=True, text=True)

@@ -88,6 +88,7 @@ class RtLaunchInfo(C.Structure):
 
 
 RT_MULTI_MAX_GPUS = 16
+RT_KERNEL_NAME_BYTES = 64                 # include/rt_capi_launch.h
 
 
 class RtMultiInfo(C.Structure):
@@ -206,6 +207,11 @@ def load_library():
         lib.rt_scene_create_soft.restype = i
         lib.rt_scene_set_shadow_seed.argtypes = [vp, C.c_uint32]
         lib.rt_scene_set_shadow_seed.restype = i
+    # include/rt_capi_launch.h (likewise absent from older builds)
+    if hasattr(lib, "rt_get_launch_kernel"):
+        lib.rt_capi_launch_version.restype = i
+        lib.rt_get_launch_kernel.argtypes = [vp, C.c_char_p, i]
+        lib.rt_get_launch_kernel.restype = i
     for name in ("rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_render",
                  "rt_render_device", "rt_render_multi", "rt_render_stats", "rt_learn_tile_order", "rt_get_timing", "rt_reset_timing",
                  "rt_get_launch_info", "rt_set_option", "rt_chunk_bounds", "rt_multi_create", "rt_multi_render",

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/rt_capi_gbuffer.h"
+#include "../../include/rt_capi_launch.h"
 #include "../../include/rt_capi_query.h"
 #include "../../include/rt_capi_rays.h"
 #include "../../include/rt_capi_ssaa.h"
@@ -155,6 +156,7 @@ struct rt_scene {
     bool ev_ready = false;
     rt_timing timing{};
     rt_launch_info launch{};
+    char launch_kernel[RT_KERNEL_NAME_BYTES] = {};   /* the whole name; launch.kernel is its first 47 characters */
     std::mutex mu;
 };
 
@@ -1476,6 +1478,17 @@ enum Family {
     RT_KERNEL(rt_render_kernel##mode##family, seeded),
 #define RT_KERNEL_ROW(...) {RT_TABLE_MODES(RT_KERNEL_ENTRY, __VA_ARGS__)},
 const Kernel kKernels[kFamilies][kModes] = {RT_RENDER_FAMILIES(RT_KERNEL_ROW)};
+/* every name fits RT_KERNEL_NAME_BYTES whole, its NUL included (rt_get_launch_kernel(), include/rt_capi_launch.h) */
+#define RT_KERNEL_NAME_SIZE(mode, global_tables, clusters, roomy, fast, block_bound, waves, waves_soft,                        \
+                            family, ssaa, rays, query, gbuffer, images, refract, soft, seeded)                                 \
+    sizeof("rt_render_kernel" #mode #family),
+#define RT_KERNEL_NAME_ROW(...) RT_TABLE_MODES(RT_KERNEL_NAME_SIZE, __VA_ARGS__)
+constexpr size_t kKernelNameBytes[] = {RT_RENDER_FAMILIES(RT_KERNEL_NAME_ROW)};
+constexpr bool kernel_names_fit(size_t i = 0) {
+    return i == sizeof(kKernelNameBytes) / sizeof(kKernelNameBytes[0]) ||
+           (kKernelNameBytes[i] <= RT_KERNEL_NAME_BYTES && kernel_names_fit(i + 1));
+}
+static_assert(kernel_names_fit(), "a render kernel's name does not fit RT_KERNEL_NAME_BYTES");
 
 /* the clustered-scene kernels (PAIRS, HELP): for scenes with clustered sphere runs whose tables are in LDS */
 bool clusters_mode(const rt_scene *s, bool global_tables) { return !global_tables && s->n_clusters > 0 && s->pairs_opt; }
@@ -1650,6 +1663,7 @@ int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1,
     p.error_word = (uint64_t)(uintptr_t)s->h_error;
     const void *kernel = plan.kernel.fn;
     std::snprintf(s->launch.kernel, sizeof(s->launch.kernel), "%s", plan.kernel.name);
+    std::snprintf(s->launch_kernel, sizeof(s->launch_kernel), "%s", plan.kernel.name);
     {
         /* a workgroup larger than the kernel was compiled for (__launch_bounds__) must never be launched */
         hipFuncAttributes attr;
@@ -2294,6 +2308,18 @@ int rt_reset_timing(rt_scene *s) {
 int rt_get_launch_info(const rt_scene *s, rt_launch_info *out) {
     if (!s || !out) return fail(RT_ERR_INVALID, "scene/out is NULL");
     *out = s->launch;
+    return RT_OK;
+}
+
+int rt_capi_launch_version(void) { return RT_CAPI_LAUNCH_VERSION; }
+
+int rt_get_launch_kernel(const rt_scene *s, char *out, int n_bytes) {
+    if (!s || !out) return fail(RT_ERR_INVALID, "scene/out is NULL");
+    const size_t need = std::strlen(s->launch_kernel) + 1;
+    if (n_bytes < 0 || (size_t)n_bytes < need)
+        return fail(RT_ERR_INVALID, "out holds " + std::to_string(n_bytes) + " bytes, the kernel's name and its NUL need " +
+                                        std::to_string(need));
+    std::memcpy(out, s->launch_kernel, need);
     return RT_OK;
 }
 

@@ -269,6 +269,13 @@ class Renderer:
     def reset_timing(self):
         capi.check(self._lib.rt_reset_timing(self._scene))
 
+    def kernel_name(self):
+        """The whole name of the kernel the last launch ran (include/rt_capi_launch.h; launch_info().kernel is its first 47
+        characters)."""
+        buf = C.create_string_buffer(capi.RT_KERNEL_NAME_BYTES)
+        capi.check(self._lib.rt_get_launch_kernel(self._scene, buf, len(buf)))
+        return buf.value.decode()
+
     def launch_info(self):
         li = capi.RtLaunchInfo()
         capi.check(self._lib.rt_get_launch_info(self._scene, C.byref(li)))
