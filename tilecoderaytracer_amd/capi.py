@@ -53,6 +53,11 @@ class RtAreaLightDesc(C.Structure):
     _fields_ = [("object", C.c_int32), ("samples", C.c_int32), ("radius", C.c_float)]
 
 
+class RtDenoiseParams(C.Structure):
+    """include/rt_capi_denoise.h: the filter's iterations (1..5), normal squarings (0..6) and colour sigma (0: no colour term)."""
+    _fields_ = [("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("sigma_color", C.c_float)]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [
         ("n_objects", C.c_int32), ("objects", C.POINTER(RtObjectDesc)),
@@ -207,6 +212,14 @@ def load_library():
         lib.rt_scene_create_soft.restype = i
         lib.rt_scene_set_shadow_seed.argtypes = [vp, C.c_uint32]
         lib.rt_scene_set_shadow_seed.restype = i
+    # include/rt_capi_denoise.h (likewise absent from older builds)
+    if hasattr(lib, "rt_denoise"):
+        lib.rt_capi_denoise_version.restype = i
+        lib.rt_denoise.argtypes = [i, C.POINTER(RtDenoiseParams), i, i, vp, vp, vp, C.POINTER(C.c_double)]
+        lib.rt_denoise_device.argtypes = [i, C.POINTER(RtDenoiseParams), i, i, vp, vp, vp, vp, vp]
+        lib.rt_denoise.restype = lib.rt_denoise_device.restype = i
+        lib.rt_denoise_scratch_bytes.argtypes = [C.POINTER(RtDenoiseParams), i, i]
+        lib.rt_denoise_scratch_bytes.restype = C.c_uint64
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):
         lib.rt_capi_launch_version.restype = i

@@ -16,8 +16,12 @@
  *   --ssaa K            K x K samples per pixel, averaged in the render kernel (rt_render_ssaa; K = 1, 2, 4; one GPU)
  *   --hits FILE         also the W x H rt_hit records of the camera rays (rt_render_gbuffer: raw little-endian, 48 bytes each,
  *                       pixels[x][z] order); one GPU, no supersampling.  The .txt is the one written without it
+ *   --denoise IT[:SIGMA[:K]]  filter the frame by its hit records before it is written (rt_render_gbuffer, then rt_denoise:
+ *                       IT iterations 1..5, colour sigma SIGMA >= 0 (default 1.0), K normal squarings 0..6 (default 3)); one
+ *                       GPU, no supersampling (a supersampled frame has no records)
  */
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +30,7 @@
 #include <vector>
 
 #include "../../../include/rt_capi.h"
+#include "../../../include/rt_capi_denoise.h"
 #include "../../../include/rt_capi_gbuffer.h"
 #include "../../../include/rt_capi_ssaa.h"
 #include "celio_model.hpp"
@@ -42,7 +47,7 @@ static int usage(const char *argv0) {
     std::fprintf(stderr,
                  "usage: %s [--width W] [--height H] [--depth D] [--scene 1|2|grid:N[:noshadow]]\n"
                  "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE] [--glass I:TF:IOR ...]\n"
-                 "          [--soft I:N[:R] ...]\n", argv0);
+                 "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]]\n", argv0);
     return 1;
 }
 
@@ -51,6 +56,7 @@ int main(int argc, char **argv) {
     bool write_txt = true;
     std::string scene_name = "1", out_path = "raytracer_screen.txt", hits_path;
     std::vector<std::string> glass;              /* --glass I:TF:IOR: object I refractive (include/rt_capi_refract.h) */
+    std::string denoise;                         /* --denoise IT[:SIGMA[:K]] (include/rt_capi_denoise.h) */
     std::vector<std::string> soft;               /* --soft I:N[:R]: light I an area light, N x N samples, radius R (include/rt_capi_soft.h) */
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -65,12 +71,23 @@ int main(int argc, char **argv) {
         else if (a == "--hits" && i + 1 < argc) hits_path = argv[++i];
         else if (a == "--glass" && i + 1 < argc) glass.push_back(argv[++i]);
         else if (a == "--soft" && i + 1 < argc) soft.push_back(argv[++i]);
+        else if (a == "--denoise" && i + 1 < argc) denoise = argv[++i];
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
     if (W <= 0 || H <= 0 || depth < 0 || gpus <= 0) return usage(argv[0]);
     if ((ssaa != 1 && ssaa != 2 && ssaa != 4) || (ssaa > 1 && gpus > 1)) return usage(argv[0]);   /* (no multi-GPU supersampling) */
     if (!hits_path.empty() && (gpus > 1 || ssaa > 1)) return usage(argv[0]);   /* (G-buffers: one GPU, no supersampling) */
+    rt_denoise_params dn = {0, 3, 1.0f};
+    if (!denoise.empty()) {
+        char tail = 0;
+        const int got = std::sscanf(denoise.c_str(), "%d:%f:%d%c", &dn.iterations, &dn.sigma_color, &dn.normal_squarings, &tail);
+        if (got < 1 || got > 3 || (got == 1 && denoise.find(':') != std::string::npos)) return usage(argv[0]);
+        if (dn.iterations < 1 || dn.iterations > 5 || dn.normal_squarings < 0 || dn.normal_squarings > 6 ||
+            !(dn.sigma_color >= 0.0f) || std::isinf(dn.sigma_color))
+            return usage(argv[0]);
+        if (gpus > 1 || ssaa > 1) return usage(argv[0]);       /* (one GPU; a supersampled frame has no records) */
+    }
     verbose() = true;                          /* console output like the reference's */
 
     if (gpus == 1) std::cout << "Single-Core RayTracing!" << std::endl << std::endl;
@@ -132,7 +149,7 @@ int main(int argc, char **argv) {
         return 1;
     }
     pixels.assign((size_t)W * (size_t)H * 3, 0.0f);
-    std::vector<rt_hit> hits(hits_path.empty() ? 0 : (size_t)W * (size_t)H);
+    std::vector<rt_hit> hits(hits_path.empty() && denoise.empty() ? 0 : (size_t)W * (size_t)H);
 
     std::printf("****** Start Ray Tracing. *******\n");
     const auto t0 = std::chrono::steady_clock::now();
@@ -147,6 +164,13 @@ int main(int argc, char **argv) {
         if (rc == RT_OK) {
             rt_timing tm;
             if (rt_get_timing(scene, &tm) == RT_OK) kernel_ms = tm.last_kernel_ms;
+        }
+        if (rc == RT_OK && !denoise.empty()) {
+            double denoise_ms = 0.0;
+            rc = rt_denoise(0, &dn, W, H, pixels.data(), hits.data(), pixels.data(), &denoise_ms);
+            if (rc == RT_OK)
+                std::printf("Denoise kernels (ms)       : %f  (%d iteration(s), sigma %g, %d normal squaring(s))\n", denoise_ms,
+                            dn.iterations, (double)dn.sigma_color, dn.normal_squarings);
         }
         rt_scene_destroy(scene);
     } else {
@@ -190,7 +214,7 @@ int main(int argc, char **argv) {
                     (double)ssaa * (double)ssaa * (double)W * (double)H / (kernel_ms * 1e3), gpus > 1 ? "  [the GPU whose kernels took longest]" : "");
     std::printf("AverageRoundTime (us/pixel): %f\n", run_time_us / ((double)W * (double)H));
 
-    if (!hits.empty()) {
+    if (!hits_path.empty()) {
         FILE *f = std::fopen(hits_path.c_str(), "wb");
         bool ok = f != nullptr;
         if (f) {

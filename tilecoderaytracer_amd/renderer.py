@@ -39,6 +39,21 @@ def area_light_descs(area_lights):
     return descs
 
 
+def denoise(rgb, hits, iterations=2, sigma_color=1.0, normal_squarings=3, device=0):
+    """Filter a frame's colours by its hit records (include/rt_capi_denoise.h, rt_denoise): rgb float32 (Wn, H, 3) and hits
+    HIT_DTYPE (Wn, H), as render_gbuffer() returns them (a whole frame or a strip) -> the filtered float32 (Wn, H, 3).  Runs on GPU
+    `device`; there is no CPU path."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or hits.shape != rgb.shape[:2]:
+        raise ValueError(f"rgb must be (Wn, H, 3) and hits (Wn, H), not {rgb.shape} and {hits.shape}")
+    params = capi.RtDenoiseParams(int(iterations), int(normal_squarings), float(sigma_color))
+    out = np.empty_like(rgb)
+    capi.check(capi.load_library().rt_denoise(int(device), C.byref(params), rgb.shape[0], rgb.shape[1], rgb.ctypes.data,
+                                              hits.ctypes.data, out.ctypes.data, None))
+    return out
+
+
 class Renderer:
     """Owns an ``rt_scene`` (device tables for one HostScene on one GPU)."""
 
@@ -46,6 +61,7 @@ class Renderer:
         self._lib = capi.load_library()
         self._host = host_scene          # keeps the desc arrays alive
         self._scene = C.c_void_p()
+        self._device = device
         n_images, images = host_scene.images        # the scene's Texture_Image objects (include/rt_capi_texture.h)
         n_refr, refr = host_scene.refractions       # its refractive materials (include/rt_capi_refract.h)
         n_soft, soft = host_scene.area_lights       # its area lights (include/rt_capi_soft.h)
@@ -75,6 +91,7 @@ class Renderer:
         self._lib = capi.load_library()
         self._host = keepalive
         self._scene = C.c_void_p()
+        self._device = device
         if area_lights is not None:
             arrays, descs = image_descs(images or [])
             rdescs = refraction_descs(refractive or [])
@@ -162,6 +179,36 @@ class Renderer:
         HIP stream (no sync)."""
         capi.check(self._lib.rt_render_gbuffer_device(self._scene, self._cam, W, H, x0, x1, max_depth, C.c_void_p(rgb_ptr),
                                                       C.c_void_p(hits_ptr), C.c_void_p(stream)))
+
+    def render_denoised(self, W, H, max_depth, iterations=2, sigma_color=1.0, normal_squarings=3):
+        """A W x H G-buffer frame filtered on the GPU where it was rendered (include/rt_capi_denoise.h): rt_render_gbuffer_device
+        and rt_denoise_device enqueued on one stream with no host wait between them, then one download -> (rgb float32
+        (W, H, 3), the filtered colours; hits HIT_DTYPE (W, H); kernel_ms, device time from the render's start to the filter's
+        end).  The result is denoise(*render_gbuffer(W, H, max_depth), ...) bit for bit.  The device buffers, the stream and the
+        events are torch's, so the process must have imported torch before the library was loaded."""
+        import torch
+        device = int(self._device)
+        params = capi.RtDenoiseParams(int(iterations), int(normal_squarings), float(sigma_color))
+        scratch_bytes = self._lib.rt_denoise_scratch_bytes(C.byref(params), W, H)
+        if not scratch_bytes:
+            capi.check(self._lib.rt_denoise_device(device, C.byref(params), W, H, None, None, None, None, None))
+        with torch.cuda.device(device):
+            noisy = torch.empty((W, H, 3), dtype=torch.float32, device="cuda")
+            clean = torch.empty((W, H, 3), dtype=torch.float32, device="cuda")
+            records = torch.empty((W * H * 12,), dtype=torch.int32, device="cuda")
+            scratch = torch.empty(((scratch_bytes + 15) // 16 * 4,), dtype=torch.int32, device="cuda")
+            stream = torch.cuda.current_stream()
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record(stream)
+            self.render_gbuffer_device(W, H, max_depth, 0, W, noisy.data_ptr(), records.data_ptr(), stream.cuda_stream)
+            capi.check(self._lib.rt_denoise_device(device, C.byref(params), W, H, noisy.data_ptr(), records.data_ptr(),
+                                                   clean.data_ptr(), scratch.data_ptr(), stream.cuda_stream))
+            stop.record(stream)
+            host = torch.cat((clean.view(torch.int32).reshape(-1), records)).cpu().numpy()      # the one download
+            kernel_ms = start.elapsed_time(stop)
+        rgb = host[:W * H * 3].view(np.float32).reshape(W, H, 3)
+        hits = host[W * H * 3:].view(HIT_DTYPE).reshape(W, H)
+        return rgb, hits, kernel_ms
 
     def trace_rays(self, rays, max_depth, rows=None):
         """Trace a batch of primary rays (include/rt_capi_rays.h).  rays: C-contiguous float32, (n, 6) -- rows defaults to n --
