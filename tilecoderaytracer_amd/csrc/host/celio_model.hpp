@@ -402,8 +402,8 @@ private:
  * (include/rt_capi_texture.h), texture indices desc.n_textures + k; their texels stay owned by the Texture_Image objects.
  * refractions: one entry per non-light object whose material has refractive_factor > 0 (include/rt_capi_refract.h).
  * area_lights: one entry per light made an area light with samples > 0 and radius > 0 (include/rt_capi_soft.h).
- * create(): rt_scene_create_soft when there are area lights, else rt_scene_create_refractive when there are refractions, else
- * rt_scene_create_textured when there are images, rt_scene_create otherwise. */
+ * create(): rt_scene_create_soft with all three lists; a list that is empty selects the plainer path there, down to
+ * rt_scene_create's (include/rt_capi_soft.h). */
 struct FlatScene {
     std::vector<rt_object_desc> objects;
     std::vector<rt_texture_desc> textures;
@@ -412,15 +412,9 @@ struct FlatScene {
     std::vector<rt_area_light_desc> area_lights;
     rt_scene_desc desc;
     int create(int device, rt_scene **out) const {
-        if (!area_lights.empty())
-            return rt_scene_create_soft(&desc, (int)images.size(), images.empty() ? nullptr : images.data(),
-                                        (int)refractions.size(), refractions.empty() ? nullptr : refractions.data(),
-                                        (int)area_lights.size(), area_lights.data(), device, out);
-        if (!refractions.empty())
-            return rt_scene_create_refractive(&desc, (int)images.size(), images.empty() ? nullptr : images.data(),
-                                              (int)refractions.size(), refractions.data(), device, out);
-        if (images.empty()) return rt_scene_create(&desc, device, out);
-        return rt_scene_create_textured(&desc, (int)images.size(), images.data(), device, out);
+        return rt_scene_create_soft(&desc, (int)images.size(), images.empty() ? nullptr : images.data(),
+                                    (int)refractions.size(), refractions.empty() ? nullptr : refractions.data(),
+                                    (int)area_lights.size(), area_lights.empty() ? nullptr : area_lights.data(), device, out);
     }
 };
 

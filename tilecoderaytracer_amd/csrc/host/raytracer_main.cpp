@@ -157,7 +157,7 @@ int main(int argc, char **argv) {
     double kernel_ms = 0.0;
     if (gpus == 1) {
         rt_scene *scene = nullptr;
-        rc = flat.create(0, &scene);                /* rt_scene_create_textured when the scene has bitmap textures */
+        rc = flat.create(0, &scene);                /* with the scene's bitmap textures, refractions and area lights, if any */
         if (rc == RT_OK) rc = ssaa > 1 ? rt_render_ssaa(scene, &cam, W, H, 0, W, depth, ssaa, pixels.data())
                             : !hits.empty() ? rt_render_gbuffer(scene, &cam, W, H, 0, W, depth, pixels.data(), hits.data())
                                             : rt_render(scene, &cam, W, H, 0, W, depth, pixels.data());

@@ -925,7 +925,7 @@ int pack_scene(rt_scene *s) {
 }
 
 /* validate + copy the caller's description into the handle */
-int adopt_desc(const rt_scene_desc *desc, rt_scene *s, int n_images = 0) {
+int adopt_desc(const rt_scene_desc *desc, rt_scene *s, int n_images) {
     const int n = desc->n_objects;
     if (n < 0) return fail(RT_ERR_INVALID, "n_objects < 0");
     if (n > 0 && !desc->objects) return fail(RT_ERR_INVALID, "objects is NULL");
@@ -1307,7 +1307,7 @@ int check_launch_args(const rt_camera_desc *cam, int W, int H, int x0, int x1, i
     return RT_OK;
 }
 
-void camera_params(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, RtParams &p) {
+void camera_params(const rt_camera_desc *cam, RtParams &p) {
     for (int c = 0; c < 3; ++c) {
         p.so[c] = cam->screen_origin[c];
         p.ch[c] = cam->vector_horizontal[c];
@@ -1316,19 +1316,33 @@ void camera_params(const rt_camera_desc *cam, int W, int H, int x0, int x1, int 
     }
     p.sw = cam->screen_width; p.sh = cam->screen_height;
     p.shw = cam->screen_halfwidth; p.shh = cam->screen_halfheight;
-    p.W = W; p.H = H; p.x0 = x0; p.x1 = x1; p.max_depth = max_depth;
 }
 
-/* RAY BATCH (include/rt_capi_rays.h): n rays {E, T} at a device address, laid out as an n_cols x rows grid -- launched as the
- * image of that size (W = x1 = n_cols, H = rows, x0 = 0) without a camera.  query (include/rt_capi_query.h): RT_QUERY_HITS or
- * RT_QUERY_OCCLUDED asks the *_hits or *_occluded kernels instead of shading the rays. */
-struct RayBatch { int n = 0, rows = 0, n_cols = 0; const void *d_rays = nullptr; int query = RT_QUERY_NONE; };
+/* The calls: a camera's frame (rt_render*), its supersampled frame (rt_render_ssaa*, k > 1), its frame with hit records
+ * (rt_render_gbuffer*); a ray batch shaded (rt_trace_rays*) or queried (include/rt_capi_query.h: the *_hits or *_occluded
+ * kernels instead of shading).  With the scene's shading the call names the family of kernels (family()). */
+enum Call { kCallFrame, kCallSsaa, kCallGbuffer, kCallRays, kCallHits, kCallOccluded, kCalls };
+bool is_query(Call c) { return c == kCallHits || c == kCallOccluded; }
+bool is_batch(Call c) { return c == kCallRays || is_query(c); }
 
-void batch_params(const RayBatch &b, int max_depth, RtParams &p) {
-    p.W = b.n_cols; p.H = b.rows; p.x0 = 0; p.x1 = b.n_cols; p.max_depth = max_depth;
-    p.n_rays = b.n;
-    p.rays = (uint64_t)(uintptr_t)b.d_rays;
-}
+/* One launch as its entry point asks for it: built there once, read by plan_launch(), launch() and the policy below them. */
+struct LaunchRequest {
+    Call call;
+    const rt_camera_desc *cam = nullptr;      /* NULL for a batch: every decision that needs a camera -- PRIMARY table, automatic start row, HEAVY band, learned order -- is then "none" */
+    /* RAY BATCH (include/rt_capi_rays.h): n_rays rays {E, T} at a device address, laid out as an n_cols x rows grid (rays_args())
+     * and launched as the image of that size.  A query (max_depth 0: no bounce stack) has no HELP desk either */
+    int n_rays = 0;
+    const void *d_rays = nullptr;
+    /* the image every decision is taken on.  kCallSsaa: the VIRTUAL image (k W x k H, columns [k x0, k x1)); the kernel averages
+     * each pixel's k x k samples into a W / k x H / k output.  A batch: its grid, W = x1 = n_cols, H = rows, x0 = 0 */
+    int W, H, x0, x1, max_depth;
+    int ssaa_log2 = 0;            /* log2 k; > 0 for kCallSsaa only */
+    void *d_out = nullptr;
+    /* kCallGbuffer (a camera frame, no supersampling, not counting): every decision is rt_render's for the frame; the kernel is
+     * the *_gbuffer sibling of rt_render's, and p.gbuffer_hits = d_hits */
+    void *d_hits = nullptr;
+    unsigned long long *d_stats = nullptr;    /* the counting build's counters (rt_render_stats); NULL: not counting */
+};
 
 /* Wavefront tile shape (speed only).  4 x 16 (x by z) makes every lane-row's
  * stores whole 64-byte sectors (16 pixels x 12 B = 192 B, aligned): measured
@@ -1339,18 +1353,18 @@ struct TileShape { int z_log2, x, z; long long tiles_x, tiles_z; };
 
 /* SUPERSAMPLING (ssaa_log2 > 0): both sides must be multiples of k, so that a pixel's k x k samples lie in one tile; an option
  * asking for another shape gets the nearest one that qualifies (the defaults, 4 x 16 and 16 x 4, always do).
- * RAY BATCH (rays), without a "tile_z" option: the tile is no wider than the grid, rounded up to a power of two, and as much
+ * RAY BATCH, without a "tile_z" option: the tile is no wider than the grid, rounded up to a power of two, and as much
  * taller -- a flat list (n_cols = 1) gets 1 x 64 tiles, not lanes three quarters idle. */
-TileShape tile_shape(const rt_scene *s, int H, int x0, int x1, int ssaa_log2 = 0, bool rays = false) {
+TileShape tile_shape(const rt_scene *s, const LaunchRequest &rq) {
     TileShape t;
     t.z_log2 = s->tile_z_log2 >= 0 ? s->tile_z_log2 : (s->objects.size() <= 128 ? 4 : 2);
-    if (ssaa_log2 > 0) t.z_log2 = std::min(std::max(t.z_log2, ssaa_log2), 6 - ssaa_log2);
-    if (rays && s->tile_z_log2 < 0)
-        while (t.z_log2 < 6 && (64LL >> t.z_log2) >= 2LL * (x1 - x0)) ++t.z_log2;    /* (tile_x >= 2 n_cols: wider than needed) */
+    if (rq.ssaa_log2 > 0) t.z_log2 = std::min(std::max(t.z_log2, rq.ssaa_log2), 6 - rq.ssaa_log2);
+    if (is_batch(rq.call) && s->tile_z_log2 < 0)
+        while (t.z_log2 < 6 && (64LL >> t.z_log2) >= 2LL * (rq.x1 - rq.x0)) ++t.z_log2;    /* (tile_x >= 2 n_cols: wider than needed) */
     t.z = 1 << t.z_log2;
     t.x = 64 >> t.z_log2;
-    t.tiles_z = ((long long)H + t.z - 1) / t.z;
-    t.tiles_x = ((long long)(x1 - x0) + t.x - 1) / t.x;
+    t.tiles_z = ((long long)rq.H + t.z - 1) / t.z;
+    t.tiles_x = ((long long)(rq.x1 - rq.x0) + t.x - 1) / t.x;
     return t;
 }
 
@@ -1374,14 +1388,14 @@ void start_row(const rt_scene *s, const rt_camera_desc *cam, long long tiles_z, 
  * a whole frame 1-1.4 % (grid-32 4.55 -> 4.49 ms, grid-16 d8 4.22 -> 4.17 without it), and a whole frame has tiles enough to
  * end well without help; a strip does not (longest of 2 / 4 strips of the grid-32 frame: 2.79 / 1.53 ms with help, 3.10 /
  * 2.28 without).  profiles/r03_experiments.txt 16 */
-void help_desk(const rt_scene *s, bool clusters_kernel, int W, int x0, int x1, int block, int stack_lds_levels, RtParams &p,
+void help_desk(const rt_scene *s, const LaunchRequest &rq, bool clusters_kernel, int block, int stack_lds_levels, RtParams &p,
                int *lds_bytes) {
     p.desk_off = 0;
     p.help_rays_quads = 0;
     p.help_leaves = s->help_opt >= 2 ? s->help_opt : RT_HELP_LEAVES;
     p.help_spin_limit = s->help_spin_opt;
-    const bool help_wanted = s->help_opt > 0 || (s->help_opt < 0 && (long long)(x1 - x0) * 4 <= (long long)W * 3);
-    if (!clusters_kernel || !help_wanted || block <= 64) return;
+    const bool help_wanted = s->help_opt > 0 || (s->help_opt < 0 && (long long)(rq.x1 - rq.x0) * 4 <= (long long)rq.W * 3);
+    if (!clusters_kernel || is_query(rq.call) || !help_wanted || block <= 64) return;
     const int desk_off = p.stack_off + stack_lds_levels * stack_entry_quads(s) * block;
     const int with_desk = (desk_off + (RT_DESK_WORDS * 4 + 15) / 16) * 16;
     if ((size_t)with_desk <= RT_MAX_LDS_BYTES) {
@@ -1505,32 +1519,30 @@ TableMode table_mode(const rt_scene *s, bool global_tables, int block, int lds_b
     return s->base.n_fast_items > 0 ? kMode : kMode_items;
 }
 
-/* The family rule: the call -- plain, supersampled (ssaa), over a ray batch (rays), a ray batch's query (RT_QUERY_*), a camera
- * frame with hit records (gbuffer) -- on the scene's shading: none, image textures, refraction, area lights, both of the last
- * (refractive and area-light scenes are packed as image scenes).  The one irregularity: the ray queries answer geometry, so
- * with any shading a nearest-hit query takes the *_hits_image kernel, which samples the same tables, and an occlusion query,
- * which reads no colour, always the plain *_occluded one. */
-Family family(const rt_scene *s, bool ssaa, bool rays, int query, bool gbuffer) {
+/* The family rule: the call on the scene's shading: none, image textures, refraction, area lights, both of the last (refractive
+ * and area-light scenes are packed as image scenes).  The one irregularity: the ray queries answer geometry, so with any
+ * shading a nearest-hit query takes the *_hits_image kernel, which samples the same tables, and an occlusion query, which
+ * reads no colour, always the plain *_occluded one. */
+Family family(const rt_scene *s, Call call) {
     enum { kNone, kImage, kRefract, kSoft, kRefractSoft };
     const int shading = s->soft_used ? (s->refract_used ? kRefractSoft : kSoft)
                                      : (s->refract_used ? kRefract : (s->images_used ? kImage : kNone));
-    if (query == RT_QUERY_HITS) return shading == kNone ? kFamily_hits : kFamily_hits_image;
-    if (query == RT_QUERY_OCCLUDED) return kFamily_occluded;
-    static const Family kByShading[4][5] = {      /* [plain, ssaa, rays, gbuffer][shading] */
-        {kFamily, kFamily_image, kFamily_refract, kFamily_soft, kFamily_refract_soft},
-        {kFamily_ssaa, kFamily_ssaa_image, kFamily_ssaa_refract, kFamily_ssaa_soft, kFamily_ssaa_refract_soft},
-        {kFamily_rays, kFamily_rays_image, kFamily_rays_refract, kFamily_rays_soft, kFamily_rays_refract_soft},
-        {kFamily_gbuffer, kFamily_gbuffer_image, kFamily_gbuffer_refract, kFamily_gbuffer_soft, kFamily_gbuffer_refract_soft},
+    static const Family kByShading[kCalls][5] = {
+        /* kCallFrame */ {kFamily, kFamily_image, kFamily_refract, kFamily_soft, kFamily_refract_soft},
+        /* kCallSsaa */ {kFamily_ssaa, kFamily_ssaa_image, kFamily_ssaa_refract, kFamily_ssaa_soft, kFamily_ssaa_refract_soft},
+        /* kCallGbuffer */ {kFamily_gbuffer, kFamily_gbuffer_image, kFamily_gbuffer_refract, kFamily_gbuffer_soft, kFamily_gbuffer_refract_soft},
+        /* kCallRays */ {kFamily_rays, kFamily_rays_image, kFamily_rays_refract, kFamily_rays_soft, kFamily_rays_refract_soft},
+        /* kCallHits */ {kFamily_hits, kFamily_hits_image, kFamily_hits_image, kFamily_hits_image, kFamily_hits_image},
+        /* kCallOccluded */ {kFamily_occluded, kFamily_occluded, kFamily_occluded, kFamily_occluded, kFamily_occluded},
     };
-    return kByShading[gbuffer ? 3 : (ssaa ? 1 : (rays ? 2 : 0))][shading];
+    return kByShading[call][shading];
 }
 
 /* the kernel of a launch: the counting build's, or the family's kernel in the table mode */
-Kernel choose_kernel(const rt_scene *s, bool counting, bool global_tables, int block, int lds_bytes, bool ssaa, bool rays,
-                     int query, bool gbuffer) {
-    if (counting)
+Kernel choose_kernel(const rt_scene *s, const LaunchRequest &rq, bool global_tables, int block, int lds_bytes) {
+    if (rq.d_stats)
         return s->base.n_fast_items > 0 ? RT_KERNEL(rt_render_kernel_fast_stats, false) : RT_KERNEL(rt_render_kernel_stats, false);
-    return kKernels[family(s, ssaa, rays, query, gbuffer)][table_mode(s, global_tables, block, lds_bytes)];
+    return kKernels[family(s, rq.call)][table_mode(s, global_tables, block, lds_bytes)];
 }
 
 /* Everything a launch decides before it touches the device. */
@@ -1543,43 +1555,37 @@ struct LaunchPlan {
     bool help = false;            /* the launch carries HELP areas (p.help_rays_quads != 0) */
 };
 
-/* Host-only: the checks and every decision of a launch, in this order.  An empty strip is planned up to its tile count.
- * ssaa_log2 > 0 (rt_render_ssaa): W, H, x0, x1 are the VIRTUAL image's, every decision is taken on it, and the kernel averages
- * each pixel's k x k samples into a W / k x H / k output.
- * rays (rt_trace_rays; cam is NULL, the batch checked by rays_args()): W, H, x0, x1 are its grid's, n_cols x rows from column 0;
- * every decision that needs a camera -- PRIMARY table, automatic start row, HEAVY band, learned order -- is "none".
- * A ray batch's query (rays->query, include/rt_capi_query.h; max_depth 0: no bounce stack) has no HELP desk either.
- * d_hits (rt_render_gbuffer*: a camera frame, no supersampling, not counting): every decision is rt_render's for the frame;
- * the kernel is the *_gbuffer sibling of rt_render's, and p.gbuffer_hits = d_hits. */
-int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *d_out,
-                bool counting, LaunchPlan *plan, int ssaa_log2 = 0, const RayBatch *rays = nullptr, void *d_hits = nullptr) {
-    int rc = rays ? RT_OK : check_launch_args(cam, W, H, x0, x1, max_depth, d_out);
+/* Host-only: the checks and every decision of a launch, in this order.  An empty strip is planned up to its tile count. */
+int plan_launch(const rt_scene *s, const LaunchRequest &rq, LaunchPlan *plan) {
+    const bool batch = is_batch(rq.call), counting = rq.d_stats != nullptr;
+    int rc = batch ? RT_OK : check_launch_args(rq.cam, rq.W, rq.H, rq.x0, rq.x1, rq.max_depth, rq.d_out);
     if (rc) return rc;
     BlockChoice bc;
-    rc = launch_block(s, W, x0, x1, max_depth, counting, &bc);
+    rc = launch_block(s, rq.W, rq.x0, rq.x1, rq.max_depth, counting, &bc);
     if (rc) return rc;
     RtParams &p = plan->p;
     p = s->base;
-    if (rays) batch_params(*rays, max_depth, p);
-    else camera_params(cam, W, H, x0, x1, max_depth, p);
-    if (d_hits) p.gbuffer_hits = (uint64_t)(uintptr_t)d_hits;
+    p.W = rq.W; p.H = rq.H; p.x0 = rq.x0; p.x1 = rq.x1; p.max_depth = rq.max_depth;
+    if (batch) { p.n_rays = rq.n_rays; p.rays = (uint64_t)(uintptr_t)rq.d_rays; }
+    else camera_params(rq.cam, p);
+    if (rq.d_hits) p.gbuffer_hits = (uint64_t)(uintptr_t)rq.d_hits;
     p.stack_lds_levels = bc.stack_lds_levels;
     p.stack_stride = bc.block;
     p.n_primary = 0;
     p.primary_off = s->base.image_quads;
-    if (!rays && !bc.global_tables && primary_quads(s) > 0 && primary_table(s, cam, W, H, p.primary)) p.n_primary = primary_quads(s);
+    if (!batch && !bc.global_tables && primary_quads(s) > 0 && primary_table(s, rq.cam, rq.W, rq.H, p.primary)) p.n_primary = primary_quads(s);
     /* (the LDS place of the table is reserved whether or not this camera admits one) */
     p.stack_off = bc.global_tables ? 0 : s->base.image_quads + primary_quads(s);
     p.cull = s->cull_opt;
-    p.ssaa_log2 = ssaa_log2;
-    const TileShape t = tile_shape(s, H, x0, x1, ssaa_log2, rays != nullptr);
+    p.ssaa_log2 = rq.ssaa_log2;
+    const TileShape t = tile_shape(s, rq);
     const long long n_tiles = t.tiles_z * t.tiles_x;
     if (n_tiles > 0x7fffffffLL) return fail(RT_ERR_INVALID, "too many tiles");
     p.tile_z_log2 = t.z_log2;
     p.tiles_z = (int)t.tiles_z;
     p.tiles_x = (int)t.tiles_x;
     p.n_tiles = (int)n_tiles;
-    start_row(s, cam, t.tiles_z, p);
+    start_row(s, rq.cam, t.tiles_z, p);
     plan->block = bc.block;
     plan->lds_bytes = bc.lds_bytes;
     plan->scene_lds_bytes = bc.global_tables ? 0 : (s->base.image_quads + primary_quads(s)) * 16;
@@ -1587,15 +1593,13 @@ int plan_launch(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int 
     plan->tiles = t;
     plan->n_tiles = n_tiles;
     if (n_tiles == 0) return RT_OK;
-    const int query = rays ? rays->query : RT_QUERY_NONE;
     /* (only whether the kernel is a clustered-scene one: which of the two, wide or not, depends on the LDS the desk adds) */
     const bool clusters_kernel = !counting && clusters_mode(s, bc.global_tables);
-    help_desk(s, clusters_kernel && query == RT_QUERY_NONE, W, x0, x1, bc.block, bc.stack_lds_levels, p, &plan->lds_bytes);
-    p.tile_prio = tile_prio(s, W, x0, x1);
-    heavy_band(s, cam, W, H, x0, x1, t, p);
-    if (!counting && !rays) learned_start_row(s, W, H, x0, x1, max_depth, t, p);
-    plan->kernel = choose_kernel(s, counting, bc.global_tables, bc.block, plan->lds_bytes, ssaa_log2 > 0, rays != nullptr, query,
-                                 d_hits != nullptr);
+    help_desk(s, rq, clusters_kernel, bc.block, bc.stack_lds_levels, p, &plan->lds_bytes);
+    p.tile_prio = tile_prio(s, rq.W, rq.x0, rq.x1);
+    heavy_band(s, rq.cam, rq.W, rq.H, rq.x0, rq.x1, t, p);
+    if (!counting && !batch) learned_start_row(s, rq.W, rq.H, rq.x0, rq.x1, rq.max_depth, t, p);
+    plan->kernel = choose_kernel(s, rq, bc.global_tables, bc.block, plan->lds_bytes);
     plan->help = p.help_rays_quads != 0;
     return RT_OK;
 }
@@ -1622,11 +1626,9 @@ int device_report(rt_scene *s) {
 }
 
 /* plan_launch(), then the device work: counters, timeline, occupancy and grid, bounce stack and HELP areas, the event ring */
-int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
-           float *d_out, hipStream_t stream, unsigned long long *d_stats = nullptr, int ssaa_log2 = 0, const RayBatch *rays = nullptr,
-           void *d_hits = nullptr) {
+int launch(rt_scene *s, LaunchRequest rq, hipStream_t stream) {
     LaunchPlan plan;
-    int rc = plan_launch(s, cam, W, H, x0, x1, max_depth, d_out, d_stats != nullptr, &plan, ssaa_log2, rays, d_hits);
+    int rc = plan_launch(s, rq, &plan);
     if (rc) return rc;
     RtParams &p = plan.p;
     const int block = plan.block;
@@ -1685,8 +1687,8 @@ int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1,
     s->launch.grid_blocks = (int)blocks;
     HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, plan.lds_bytes));
     /* bounce stack: one slice per workgroup of the persistent grid */
-    const double stack_bytes = plan.stack_lds_levels >= max_depth ? 16.0
-                             : (double)blocks * (double)block * (double)(max_depth + 1) * RT_STACK_ENTRY_BYTES * stack_entry_quads(s);
+    const double stack_bytes = plan.stack_lds_levels >= rq.max_depth ? 16.0
+                             : (double)blocks * (double)block * (double)(rq.max_depth + 1) * RT_STACK_ENTRY_BYTES * stack_entry_quads(s);
     if (stack_bytes > 8.0e9)
         return fail(RT_ERR_CAPACITY, "max_depth too large: the bounce stack would exceed 8 GB of HBM");
     /* the stack (and nothing else) is shared by successive launches of this handle:
@@ -1710,12 +1712,12 @@ int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1,
     const float4 *image_arg = reinterpret_cast<const float4 *>(s->d_image);
     float4 *stack_arg = reinterpret_cast<float4 *>(s->d_stack);
     unsigned int *list_arg = reinterpret_cast<unsigned int *>(s->d_help);      /* the clustered-scene kernels' HELP areas (unused by the others) */
-    void *args6[] = {&p, &image_arg, &d_out, &counter, &stack_arg, &list_arg};
-    void *args7[] = {&p, &image_arg, &d_out, &counter, &stack_arg, &d_stats, &list_arg};
+    void *args6[] = {&p, &image_arg, &rq.d_out, &counter, &stack_arg, &list_arg};
+    void *args7[] = {&p, &image_arg, &rq.d_out, &counter, &stack_arg, &rq.d_stats, &list_arg};
     uint32_t seed = s->shadow_seed;       /* SOFT SHADOWS: copied into the launch's arguments here, so it is this launch's */
-    void *args_seeded[] = {&p, &image_arg, &d_out, &counter, &stack_arg, &list_arg, &seed};
+    void *args_seeded[] = {&p, &image_arg, &rq.d_out, &counter, &stack_arg, &list_arg, &seed};
     HIP_TRY(hipLaunchKernel(kernel, dim3((unsigned)blocks), dim3((unsigned)block),
-                            plan.kernel.seeded ? args_seeded : (d_stats ? args7 : args6), (size_t)plan.lds_bytes, stream));
+                            plan.kernel.seeded ? args_seeded : (rq.d_stats ? args7 : args6), (size_t)plan.lds_bytes, stream));
     HIP_TRY(hipGetLastError());
     s->ev_next = next_slot;               /* (only now: a launch that did not happen has zeroed nothing) */
     HIP_TRY(hipEventRecord(s->ev[slot].stop, stream));
@@ -1723,34 +1725,40 @@ int launch(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1,
     return RT_OK;
 }
 
+/* rt_render's checks before the camera's (check_launch_args()): the strip is a strip of the frame, and one that is not empty
+ * has somewhere to go (out_required: not rt_render_stats, whose image is optional) */
+int check_strip(int W, int H, int x0, int x1, const void *out_rgb, bool out_required) {
+    if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 > x1) return fail(RT_ERR_INVALID, "need 0 <= x0 <= x1 <= W, W,H > 0");
+    if (out_required && x1 > x0 && !out_rgb) return fail(RT_ERR_INVALID, "out_rgb is NULL");
+    return RT_OK;
+}
+
 /* rt_render and rt_render_stats, under the handle's lock: the strip's checks, the device, and the framebuffer the frame is
  * rendered into (*bytes of it) */
 int frame_preamble(rt_scene *s, int W, int H, int x0, int x1, const float *out_rgb, bool out_required, size_t *bytes) {
-    if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 > x1) return fail(RT_ERR_INVALID, "need 0 <= x0 <= x1 <= W, W,H > 0");
+    int rc = check_strip(W, H, x0, x1, out_rgb, out_required);
+    if (rc) return rc;
     *bytes = (size_t)(x1 - x0) * (size_t)H * 3 * sizeof(float);
-    if (out_required && *bytes && !out_rgb) return fail(RT_ERR_INVALID, "out_rgb is NULL");
     HIP_TRY(hipSetDevice(s->device));
     return grow_device_buffer(&s->d_fb, &s->d_fb_bytes, *bytes);
 }
 
-/* rt_render, rt_render_ssaa, rt_trace_rays, the host ray queries and rt_render_gbuffer, under the handle's lock, after
- * frame_preamble() (or its ray-batch or G-buffer equivalent): the launch into the handle's framebuffer, the download of its
- * `bytes`, the synchronisation.  out_hits (rt_render_gbuffer): the records are hits_bytes at byte hits_off of the framebuffer,
- * downloaded after the colours, within the same timing. */
-int render_to_host(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, float *out_rgb,
-                   size_t bytes, int ssaa_log2, const RayBatch *rays = nullptr, void *out_hits = nullptr, size_t hits_off = 0,
-                   size_t hits_bytes = 0) {
-    char *d_hits = out_hits ? static_cast<char *>(s->d_fb) + hits_off : nullptr;
-    int rc = launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr, nullptr, ssaa_log2, rays, d_hits);
+/* rt_render, rt_render_ssaa, the host batches and rt_render_gbuffer, under the handle's lock, after frame_preamble() (or its
+ * ray-batch or G-buffer equivalent): the launch into the handle's framebuffer, the downloads from it in their order (rt_render_gbuffer:
+ * the records after the colours) within one timing, the synchronisation. */
+struct Download { void *to; const void *d_from; size_t bytes; };
+
+int render_to_host(rt_scene *s, const LaunchRequest &rq, std::initializer_list<Download> downloads) {
+    int rc = launch(s, rq, nullptr);
     if (rc) return rc;
     s->timing.last_download_ms = 0.0;
-    if (bytes) {
+    if (downloads.begin()->bytes) {
         hipEvent_t t0, t1;
         HIP_TRY(hipEventCreate(&t0));
         HIP_TRY(hipEventCreate(&t1));
         HIP_TRY(hipEventRecord(t0, nullptr));
-        HIP_TRY(hipMemcpy(out_rgb, s->d_fb, bytes, hipMemcpyDeviceToHost));
-        if (hits_bytes) HIP_TRY(hipMemcpy(out_hits, d_hits, hits_bytes, hipMemcpyDeviceToHost));
+        for (const Download &d : downloads)
+            if (d.bytes) HIP_TRY(hipMemcpy(d.to, d.d_from, d.bytes, hipMemcpyDeviceToHost));
         HIP_TRY(hipEventRecord(t1, nullptr));
         HIP_TRY(hipEventSynchronize(t1));
         float ms = 0.f;
@@ -1779,37 +1787,29 @@ int ssaa_args(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_d
     return RT_OK;
 }
 
-/* rt_trace_rays*: the checks of include/rt_capi_rays.h in its order, all before the device is touched, and the batch's grid.
- * rows past n are read as n (the same cells, without columns of empty tiles).  The grid's cells -- fewer than n + rows <= 2 n
- * -- must stay below 2^31 - 64, so that the kernel's cell numbers and row numbers fit an int. */
-int rays_args(const rt_scene *s, int n, int rows, const void *rays, int max_depth, const void *out, RayBatch *b) {
+/* rt_trace_rays*: the checks of include/rt_capi_rays.h in its order, all before the device is touched, and the batch's grid
+ * (rt_intersect_rays* and rt_occluded_rays*: the checks of include/rt_capi_query.h in its order are the same without the
+ * depth, which is 0 for them).  rows past n are read as n (the same cells, without columns of empty tiles).  The grid's cells
+ * -- fewer than n + rows <= 2 n -- must stay below 2^31 - 64, so that the kernel's cell numbers and row numbers fit an int. */
+int rays_args(const rt_scene *s, int n, int *rows, const void *rays, int max_depth, const void *out, int *n_cols) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
     if (n < 0) return fail(RT_ERR_INVALID, "n < 0");
-    if (rows < 1) return fail(RT_ERR_INVALID, "rows must be positive");
+    if (*rows < 1) return fail(RT_ERR_INVALID, "rows must be positive");
     if (max_depth < 0) return fail(RT_ERR_INVALID, "max_depth < 0");
     if (n > 0 && !rays) return fail(RT_ERR_INVALID, "rays pointer is NULL");
     if (n > 0 && !out) return fail(RT_ERR_INVALID, "output pointer is NULL");
     if ((double)n * 3.0 > kMaxStripFloats) return fail(RT_ERR_INVALID, "ray batch too large");
-    b->n = n;
-    b->rows = std::min(rows, std::max(n, 1));
-    b->n_cols = (int)(((long long)n + b->rows - 1) / b->rows);
-    if ((long long)b->n_cols * b->rows > 0x7fffffffLL - 64) return fail(RT_ERR_INVALID, "ray batch too large for its rows");
-    b->d_rays = rays;
+    *rows = std::min(*rows, std::max(n, 1));
+    *n_cols = (int)(((long long)n + *rows - 1) / *rows);
+    if ((long long)*n_cols * *rows > 0x7fffffffLL - 64) return fail(RT_ERR_INVALID, "ray batch too large for its rows");
     return RT_OK;
 }
 
-/* rt_intersect_rays* and rt_occluded_rays*: the checks of include/rt_capi_query.h in its order -- rays_args()'s without the
- * depth -- and the batch's grid */
-int query_args(const rt_scene *s, int n, int rows, const void *in, const void *out, int query, RayBatch *b) {
-    int rc = rays_args(s, n, rows, in, 0, out, b);
-    b->query = query;
-    return rc;
-}
-
-/* a host batch: into the handle's buffers, the launch of its grid at depth 0, out_bytes_per_ray * n bytes back */
-int query_to_host(rt_scene *s, int n, int rows, const float *in, void *out, int query, size_t out_bytes_per_ray) {
-    RayBatch b;
-    int rc = query_args(s, n, rows, in, out, query, &b);
+/* a host batch (kCallRays at the caller's depth, 12 bytes out per ray; a query at depth 0, an rt_hit or a byte per ray): into the
+ * handle's buffers, the launch of its grid, out_bytes_per_ray * n bytes back */
+int batch_to_host(rt_scene *s, Call call, int n, int rows, const float *in, int max_depth, void *out, size_t out_bytes_per_ray) {
+    int n_cols = 0;
+    int rc = rays_args(s, n, &rows, in, max_depth, out, &n_cols);
     if (rc || n == 0) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
     const size_t in_bytes = (size_t)n * 6 * sizeof(float), bytes = (size_t)n * out_bytes_per_ray;
@@ -1818,33 +1818,43 @@ int query_to_host(rt_scene *s, int n, int rows, const float *in, void *out, int 
     if (rc == RT_OK) rc = grow_device_buffer(&s->d_fb, &s->d_fb_bytes, bytes);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(s->d_rays, in, in_bytes, hipMemcpyHostToDevice));
-    b.d_rays = s->d_rays;
-    return render_to_host(s, nullptr, b.n_cols, b.rows, 0, b.n_cols, 0, static_cast<float *>(out), bytes, 0, &b);
+    return render_to_host(s, {.call = call, .n_rays = n, .d_rays = s->d_rays, .W = n_cols, .H = rows, .x0 = 0, .x1 = n_cols,
+                              .max_depth = max_depth, .d_out = s->d_fb},
+                          {{out, s->d_fb, bytes}});
 }
 
 /* a device batch, enqueued on the caller's stream */
-int query_on_device(rt_scene *s, int n, int rows, const void *d_in, void *d_out, int query, void *hip_stream) {
-    RayBatch b;
-    int rc = query_args(s, n, rows, d_in, d_out, query, &b);
+int batch_on_device(rt_scene *s, Call call, int n, int rows, const void *d_in, int max_depth, void *d_out, void *hip_stream) {
+    int n_cols = 0;
+    int rc = rays_args(s, n, &rows, d_in, max_depth, d_out, &n_cols);
     if (rc || n == 0) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
-    return launch(s, nullptr, b.n_cols, b.rows, 0, b.n_cols, 0, static_cast<float *>(d_out), static_cast<hipStream_t>(hip_stream),
-                  nullptr, 0, &b);
+    return launch(s, {.call = call, .n_rays = n, .d_rays = d_in, .W = n_cols, .H = rows, .x0 = 0, .x1 = n_cols, .max_depth = max_depth,
+                      .d_out = d_out},
+                  static_cast<hipStream_t>(hip_stream));
 }
 
 /* rt_render_gbuffer*: the checks of include/rt_capi_gbuffer.h in its order, all before the device is touched -- rt_render's in
- * rt_render's order (the scene, frame_preamble()'s, check_launch_args()'s), then the records': out_hits, and the strip's
+ * rt_render's order (the scene, check_strip()'s, check_launch_args()'s), then the records': out_hits, and the strip's
  * colours and records together within the bytes of kMaxStripFloats floats */
 int gbuffer_args(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *out_rgb,
                  const void *out_hits) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
-    if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 > x1) return fail(RT_ERR_INVALID, "need 0 <= x0 <= x1 <= W, W,H > 0");
-    if (x1 > x0 && !out_rgb) return fail(RT_ERR_INVALID, "out_rgb is NULL");
-    int rc = check_launch_args(cam, W, H, x0, x1, max_depth, out_rgb);
+    int rc = check_strip(W, H, x0, x1, out_rgb, true);
+    if (rc == RT_OK) rc = check_launch_args(cam, W, H, x0, x1, max_depth, out_rgb);
     if (rc) return rc;
     if (x1 > x0 && !out_hits) return fail(RT_ERR_INVALID, "out_hits is NULL");
     if ((double)(x1 - x0) * (double)H * (double)(3 * sizeof(float) + sizeof(rt_hit)) > kMaxStripFloats * sizeof(float))
         return fail(RT_ERR_INVALID, "strip too large for its colours and records");
+    return RT_OK;
+}
+
+/* rt_render_stats and rt_learn_tile_order (so: what the refusal means for the latter's caller): the counting build shades nothing */
+int check_counting(const rt_scene *s, const char *so) {
+    const std::string tail(so);
+    if (s->soft_used) return fail(RT_ERR_INVALID, "the counting build does not sample area lights" + tail + " (include/rt_capi_soft.h)");
+    if (s->refract_used) return fail(RT_ERR_INVALID, "the counting build does not trace refraction" + tail + " (include/rt_capi_refract.h)");
+    if (s->images_used) return fail(RT_ERR_INVALID, "the counting build does not sample image textures" + tail + " (include/rt_capi_texture.h)");
     return RT_OK;
 }
 
@@ -1870,28 +1880,20 @@ int rt_device_count(int *count) {
     return RT_OK;
 }
 
-int rt_scene_create(const rt_scene_desc *desc, int device, rt_scene **out) {
-    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
-    *out = nullptr;
-    rt_scene *s = new (std::nothrow) rt_scene();
-    if (!s) return fail(RT_ERR_INVALID, "out of memory");
-    int rc = adopt_desc(desc, s);
-    if (rc == RT_OK) rc = pack_scene(s);
-    if (rc) { delete s; return rc; }
-    return finish_create(s, device, out);
-}
-
-int rt_capi_texture_version(void) { return RT_CAPI_TEXTURE_VERSION; }
-
-/* IMAGE TEXTURES (include/rt_capi_texture.h): the images' checks in the header's order, then rt_scene_create's path with them */
 namespace {
-/* rt_scene_create_textured's path; refr: {tf, ior} per object of a refractive scene (REFRACTION), else NULL; soft: {n, r} per
- * object of a scene with area lights (SOFT SHADOWS), else NULL */
-int create_textured(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
-                    const std::vector<float> *refr_tf, const std::vector<float> *refr_ior, int device, rt_scene **out,
-                    const std::vector<int> *soft_n = nullptr, const std::vector<float> *soft_r = nullptr) {
-    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
-    *out = nullptr;
+/* What rt_scene_create_textured, _refractive and _soft add to a description; empty: none.  The images (IMAGE TEXTURES) as the
+ * caller gave them, checked by check_images(); {tf, ior} per object of a refractive scene (REFRACTION) and {n, r} per object of a
+ * scene with area lights (SOFT SHADOWS) as their validators leave them. */
+struct Extensions {
+    int n_images = 0;
+    const rt_image_texture_desc *images = nullptr;
+    std::vector<float> refr_tf, refr_ior;
+    std::vector<int> soft_n;
+    std::vector<float> soft_r;
+};
+
+/* IMAGE TEXTURES (include/rt_capi_texture.h): the images' checks in the header's order */
+int check_images(int n_images, const rt_image_texture_desc *images) {
     if (n_images < 0) return fail(RT_ERR_INVALID, "n_images < 0");
     if (n_images > 0 && !images) return fail(RT_ERR_INVALID, "images is NULL");
     uint64_t total = 0;
@@ -1908,52 +1910,11 @@ int create_textured(const rt_scene_desc *desc, int n_images, const rt_image_text
     }
     if (total > (uint64_t)RT_MAX_SCENE_TEXELS)
         return fail(RT_ERR_CAPACITY, "more than " + std::to_string(RT_MAX_SCENE_TEXELS) + " texels in the scene's images");
-    if (n_images == 0 && !refr_tf && !soft_n) return rt_scene_create(desc, device, out);
-    rt_scene *s = new (std::nothrow) rt_scene();
-    if (!s) return fail(RT_ERR_INVALID, "out of memory");
-    int rc = adopt_desc(desc, s, n_images);
-    if (rc == RT_OK && refr_tf) {
-        /* (a refractive scene is packed as an image scene: checkerboards as their 2 x 2 CHECKER images, rt_tables.h) */
-        s->refr_tf = *refr_tf;
-        s->refr_ior = *refr_ior;
-        s->refract_used = true;
-        s->images_used = true;
-    }
-    if (rc == RT_OK && soft_n) {
-        /* (an area-light scene is packed as an image scene too) */
-        s->soft_n = *soft_n;
-        s->soft_r = *soft_r;
-        s->soft_used = true;
-        s->images_used = true;
-    }
-    if (rc == RT_OK) {
-        for (int k = 0; k < n_images; ++k) {
-            const rt_image_texture_desc &im = images[k];
-            s->images.push_back({im.texels_w, im.texels_h, im.width, im.height, im.wrap,
-                                 std::vector<float>(im.texels, im.texels + (size_t)im.texels_w * (size_t)im.texels_h * 3)});
-        }
-        rc = pack_scene(s);          /* (every table check before the device is touched; packed again with the texels' address) */
-    }
-    if (rc) { delete s; return rc; }
-    return finish_create(s, device, out);
-}
-} // namespace
-
-int rt_scene_create_textured(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images, int device,
-                             rt_scene **out) {
-    return create_textured(desc, n_images, images, nullptr, nullptr, device, out);
+    return RT_OK;
 }
 
-int rt_capi_refract_version(void) { return RT_CAPI_REFRACT_VERSION; }
-
-namespace {
-/* REFRACTION (include/rt_capi_refract.h): the list's checks in the header's order; entries with tf == 0 dropped, none left:
- * rt_scene_create_textured's path.  soft: SOFT SHADOWS, as create_textured() */
-int create_refractive(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
-                      int n_refractive, const rt_refraction_desc *refractive, int device, rt_scene **out,
-                      const std::vector<int> *soft_n, const std::vector<float> *soft_r) {
-    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
-    *out = nullptr;
+/* REFRACTION (include/rt_capi_refract.h): the list's checks in the header's order; entries with tf == 0 dropped (none left: none) */
+int check_refractive(const rt_scene_desc *desc, int n_refractive, const rt_refraction_desc *refractive, Extensions *x) {
     if (n_refractive < 0) return fail(RT_ERR_INVALID, "n_refractive < 0");
     if (n_refractive > 0 && !refractive) return fail(RT_ERR_INVALID, "refractive is NULL");
     const int n = desc->n_objects;
@@ -1974,25 +1935,12 @@ int create_refractive(const rt_scene_desc *desc, int n_images, const rt_image_te
         ior[(size_t)r.object] = r.ior;
         any = true;
     }
-    if (!any) return create_textured(desc, n_images, images, nullptr, nullptr, device, out, soft_n, soft_r);
-    return create_textured(desc, n_images, images, &tf, &ior, device, out, soft_n, soft_r);
-}
-} // namespace
-
-int rt_scene_create_refractive(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
-                               int n_refractive, const rt_refraction_desc *refractive, int device, rt_scene **out) {
-    return create_refractive(desc, n_images, images, n_refractive, refractive, device, out, nullptr, nullptr);
+    if (any) { x->refr_tf.swap(tf); x->refr_ior.swap(ior); }
+    return RT_OK;
 }
 
-int rt_capi_soft_version(void) { return RT_CAPI_SOFT_VERSION; }
-
-/* SOFT SHADOWS (include/rt_capi_soft.h): the list's checks in the header's order; entries with radius == 0 dropped, none left:
- * rt_scene_create_refractive itself */
-int rt_scene_create_soft(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
-                         int n_refractive, const rt_refraction_desc *refractive,
-                         int n_area_lights, const rt_area_light_desc *area_lights, int device, rt_scene **out) {
-    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
-    *out = nullptr;
+/* SOFT SHADOWS (include/rt_capi_soft.h): the list's checks in the header's order; entries with radius == 0 dropped (none left: none) */
+int check_area_lights(const rt_scene_desc *desc, int n_area_lights, const rt_area_light_desc *area_lights, Extensions *x) {
     if (n_area_lights < 0) return fail(RT_ERR_INVALID, "n_area_lights < 0");
     if (n_area_lights > 0 && !area_lights) return fail(RT_ERR_INVALID, "area_lights is NULL");
     const int n = desc->n_objects;
@@ -2014,8 +1962,74 @@ int rt_scene_create_soft(const rt_scene_desc *desc, int n_images, const rt_image
         sr[(size_t)a.object] = a.radius;
         any = true;
     }
-    if (!any) return create_refractive(desc, n_images, images, n_refractive, refractive, device, out, nullptr, nullptr);
-    return create_refractive(desc, n_images, images, n_refractive, refractive, device, out, &sn, &sr);
+    if (any) { x->soft_n.swap(sn); x->soft_r.swap(sr); }
+    return RT_OK;
+}
+
+/* every rt_scene_create* once its lists are checked: the description's checks, the extensions into the handle, the tables, the device */
+int create(const rt_scene_desc *desc, const Extensions &x, int device, rt_scene **out) {
+    rt_scene *s = new (std::nothrow) rt_scene();
+    if (!s) return fail(RT_ERR_INVALID, "out of memory");
+    int rc = adopt_desc(desc, s, x.n_images);
+    if (rc == RT_OK) {
+        s->refr_tf = x.refr_tf; s->refr_ior = x.refr_ior;
+        s->soft_n = x.soft_n; s->soft_r = x.soft_r;
+        s->refract_used = !x.refr_tf.empty();
+        s->soft_used = !x.soft_n.empty();
+        /* (refractive and area-light scenes are packed as image scenes: checkerboards as their 2 x 2 CHECKER images, rt_tables.h) */
+        if (s->refract_used || s->soft_used) s->images_used = true;
+        for (int k = 0; k < x.n_images; ++k) {
+            const rt_image_texture_desc &im = x.images[k];
+            s->images.push_back({im.texels_w, im.texels_h, im.width, im.height, im.wrap,
+                                 std::vector<float>(im.texels, im.texels + (size_t)im.texels_w * (size_t)im.texels_h * 3)});
+        }
+        rc = pack_scene(s);          /* (every table check before the device is touched; a scene with images is packed again with the texels' address) */
+    }
+    if (rc) { delete s; return rc; }
+    return finish_create(s, device, out);
+}
+} // namespace
+
+int rt_scene_create(const rt_scene_desc *desc, int device, rt_scene **out) {
+    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
+    *out = nullptr;
+    return create(desc, Extensions{}, device, out);
+}
+
+int rt_capi_texture_version(void) { return RT_CAPI_TEXTURE_VERSION; }
+
+int rt_scene_create_textured(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images, int device,
+                             rt_scene **out) {
+    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
+    *out = nullptr;
+    int rc = check_images(n_images, images);
+    return rc ? rc : create(desc, Extensions{n_images, images}, device, out);
+}
+
+int rt_capi_refract_version(void) { return RT_CAPI_REFRACT_VERSION; }
+
+int rt_scene_create_refractive(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
+                               int n_refractive, const rt_refraction_desc *refractive, int device, rt_scene **out) {
+    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
+    *out = nullptr;
+    Extensions x{n_images, images};
+    int rc = check_refractive(desc, n_refractive, refractive, &x);
+    if (rc == RT_OK) rc = check_images(n_images, images);
+    return rc ? rc : create(desc, x, device, out);
+}
+
+int rt_capi_soft_version(void) { return RT_CAPI_SOFT_VERSION; }
+
+int rt_scene_create_soft(const rt_scene_desc *desc, int n_images, const rt_image_texture_desc *images,
+                         int n_refractive, const rt_refraction_desc *refractive,
+                         int n_area_lights, const rt_area_light_desc *area_lights, int device, rt_scene **out) {
+    if (!desc || !out) return fail(RT_ERR_INVALID, "desc/out is NULL");
+    *out = nullptr;
+    Extensions x{n_images, images};
+    int rc = check_area_lights(desc, n_area_lights, area_lights, &x);
+    if (rc == RT_OK) rc = check_refractive(desc, n_refractive, refractive, &x);
+    if (rc == RT_OK) rc = check_images(n_images, images);
+    return rc ? rc : create(desc, x, device, out);
 }
 
 int rt_scene_set_shadow_seed(rt_scene *s, uint32_t seed) {
@@ -2047,7 +2061,7 @@ int rt_render_device(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x
                      void *d_out_rgb, void *hip_stream) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
     std::lock_guard<std::mutex> lock(s->mu);
-    return launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(d_out_rgb),
+    return launch(s, {.call = kCallFrame, .cam = cam, .W = W, .H = H, .x0 = x0, .x1 = x1, .max_depth = max_depth, .d_out = d_out_rgb},
                   static_cast<hipStream_t>(hip_stream));
 }
 
@@ -2058,7 +2072,8 @@ int rt_render(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int 
     size_t bytes = 0;
     int rc = frame_preamble(s, W, H, x0, x1, out_rgb, true, &bytes);
     if (rc) return rc;
-    return render_to_host(s, cam, W, H, x0, x1, max_depth, out_rgb, bytes, 0);
+    return render_to_host(s, {.call = kCallFrame, .cam = cam, .W = W, .H = H, .x0 = x0, .x1 = x1, .max_depth = max_depth, .d_out = s->d_fb},
+                          {{out_rgb, s->d_fb, bytes}});
 }
 
 int rt_capi_ssaa_version(void) { return RT_CAPI_SSAA_VERSION; }
@@ -2076,7 +2091,9 @@ int rt_render_ssaa(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0,
     size_t bytes = 0;
     rc = frame_preamble(s, W, H, x0, x1, out_rgb, true, &bytes);
     if (rc) return rc;
-    return render_to_host(s, cam, W << kl, H << kl, x0 << kl, x1 << kl, max_depth, out_rgb, bytes, kl);
+    return render_to_host(s, {.call = kCallSsaa, .cam = cam, .W = W << kl, .H = H << kl, .x0 = x0 << kl, .x1 = x1 << kl,
+                              .max_depth = max_depth, .ssaa_log2 = kl, .d_out = s->d_fb},
+                          {{out_rgb, s->d_fb, bytes}});
 }
 
 int rt_render_ssaa_device(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, int samples,
@@ -2087,54 +2104,39 @@ int rt_render_ssaa_device(rt_scene *s, const rt_camera_desc *cam, int W, int H, 
     if (rc) return rc;
     if (kl == 0) return rt_render_device(s, cam, W, H, x0, x1, max_depth, d_out_rgb, hip_stream);
     std::lock_guard<std::mutex> lock(s->mu);
-    return launch(s, cam, W << kl, H << kl, x0 << kl, x1 << kl, max_depth, static_cast<float *>(d_out_rgb),
-                  static_cast<hipStream_t>(hip_stream), nullptr, kl);
+    return launch(s, {.call = kCallSsaa, .cam = cam, .W = W << kl, .H = H << kl, .x0 = x0 << kl, .x1 = x1 << kl, .max_depth = max_depth,
+                      .ssaa_log2 = kl, .d_out = d_out_rgb},
+                  static_cast<hipStream_t>(hip_stream));
 }
 
 int rt_capi_rays_version(void) { return RT_CAPI_RAYS_VERSION; }
 
 /* RAY BATCH (include/rt_capi_rays.h): the batch into the handle's buffer for it, the launch of its grid, 3 n floats back */
 int rt_trace_rays(rt_scene *s, int n, int rows, const float *rays, int max_depth, float *out_rgb) {
-    RayBatch b;
-    int rc = rays_args(s, n, rows, rays, max_depth, out_rgb, &b);
-    if (rc || n == 0) return rc;
-    std::lock_guard<std::mutex> lock(s->mu);
-    const size_t in_bytes = (size_t)n * 6 * sizeof(float), bytes = (size_t)n * 3 * sizeof(float);
-    HIP_TRY(hipSetDevice(s->device));
-    rc = grow_device_buffer(&s->d_rays, &s->d_rays_bytes, in_bytes);
-    if (rc == RT_OK) rc = grow_device_buffer(&s->d_fb, &s->d_fb_bytes, bytes);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(s->d_rays, rays, in_bytes, hipMemcpyHostToDevice));
-    b.d_rays = s->d_rays;
-    return render_to_host(s, nullptr, b.n_cols, b.rows, 0, b.n_cols, max_depth, out_rgb, bytes, 0, &b);
+    return batch_to_host(s, kCallRays, n, rows, rays, max_depth, out_rgb, 3 * sizeof(float));
 }
 
 int rt_trace_rays_device(rt_scene *s, int n, int rows, const void *d_rays, int max_depth, void *d_out_rgb, void *hip_stream) {
-    RayBatch b;
-    int rc = rays_args(s, n, rows, d_rays, max_depth, d_out_rgb, &b);
-    if (rc || n == 0) return rc;
-    std::lock_guard<std::mutex> lock(s->mu);
-    return launch(s, nullptr, b.n_cols, b.rows, 0, b.n_cols, max_depth, static_cast<float *>(d_out_rgb),
-                  static_cast<hipStream_t>(hip_stream), nullptr, 0, &b);
+    return batch_on_device(s, kCallRays, n, rows, d_rays, max_depth, d_out_rgb, hip_stream);
 }
 
 int rt_capi_query_version(void) { return RT_CAPI_QUERY_VERSION; }
 
 /* RAY QUERIES (include/rt_capi_query.h): a ray batch at depth 0 through the *_hits or *_occluded kernels */
 int rt_intersect_rays(rt_scene *s, int n, int rows, const float *rays, rt_hit *out_hits) {
-    return query_to_host(s, n, rows, rays, out_hits, RT_QUERY_HITS, sizeof(rt_hit));
+    return batch_to_host(s, kCallHits, n, rows, rays, 0, out_hits, sizeof(rt_hit));
 }
 
 int rt_intersect_rays_device(rt_scene *s, int n, int rows, const void *d_rays, void *d_out_hits, void *hip_stream) {
-    return query_on_device(s, n, rows, d_rays, d_out_hits, RT_QUERY_HITS, hip_stream);
+    return batch_on_device(s, kCallHits, n, rows, d_rays, 0, d_out_hits, hip_stream);
 }
 
 int rt_occluded_rays(rt_scene *s, int n, int rows, const float *segs, uint8_t *out_blocked) {
-    return query_to_host(s, n, rows, segs, out_blocked, RT_QUERY_OCCLUDED, 1);
+    return batch_to_host(s, kCallOccluded, n, rows, segs, 0, out_blocked, 1);
 }
 
 int rt_occluded_rays_device(rt_scene *s, int n, int rows, const void *d_segs, void *d_out_blocked, void *hip_stream) {
-    return query_on_device(s, n, rows, d_segs, d_out_blocked, RT_QUERY_OCCLUDED, hip_stream);
+    return batch_on_device(s, kCallOccluded, n, rows, d_segs, 0, d_out_blocked, hip_stream);
 }
 
 int rt_capi_gbuffer_version(void) { return RT_CAPI_GBUFFER_VERSION; }
@@ -2151,7 +2153,10 @@ int rt_render_gbuffer(rt_scene *s, const rt_camera_desc *cam, int W, int H, int 
     HIP_TRY(hipSetDevice(s->device));
     rc = grow_device_buffer(&s->d_fb, &s->d_fb_bytes, hits_off + hits_bytes);
     if (rc) return rc;
-    return render_to_host(s, cam, W, H, x0, x1, max_depth, out_rgb, bytes, 0, nullptr, out_hits, hits_off, hits_bytes);
+    char *d_hits = static_cast<char *>(s->d_fb) + hits_off;
+    return render_to_host(s, {.call = kCallGbuffer, .cam = cam, .W = W, .H = H, .x0 = x0, .x1 = x1, .max_depth = max_depth, .d_out = s->d_fb,
+                              .d_hits = d_hits},
+                          {{out_rgb, s->d_fb, bytes}, {out_hits, d_hits, hits_bytes}});
 }
 
 int rt_render_gbuffer_device(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, void *d_out_rgb,
@@ -2160,40 +2165,39 @@ int rt_render_gbuffer_device(rt_scene *s, const rt_camera_desc *cam, int W, int 
     if (rc) return rc;
     if (((uintptr_t)d_out_hits & 15u) != 0) return fail(RT_ERR_INVALID, "d_out_hits must be 16-byte aligned");
     std::lock_guard<std::mutex> lock(s->mu);
-    return launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(d_out_rgb), static_cast<hipStream_t>(hip_stream), nullptr, 0,
-                  nullptr, d_out_hits);
+    return launch(s, {.call = kCallGbuffer, .cam = cam, .W = W, .H = H, .x0 = x0, .x1 = x1, .max_depth = max_depth, .d_out = d_out_rgb,
+                      .d_hits = d_out_hits},
+                  static_cast<hipStream_t>(hip_stream));
 }
 
 int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
                     float *out_rgb, uint64_t *stats, int n_stats, uint64_t *wave_cycles, int n_wave_cycles) {
     if (!s || !stats || n_stats < 0) return fail(RT_ERR_INVALID, "scene/stats is NULL");
-    if (s->soft_used) return fail(RT_ERR_INVALID, "the counting build does not sample area lights (include/rt_capi_soft.h)");
-    if (s->refract_used) return fail(RT_ERR_INVALID, "the counting build does not trace refraction (include/rt_capi_refract.h)");
-    if (s->images_used) return fail(RT_ERR_INVALID, "the counting build does not sample image textures (include/rt_capi_texture.h)");
+    int rc = check_counting(s, "");
+    if (rc) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
     size_t bytes = 0;
-    int rc = frame_preamble(s, W, H, x0, x1, out_rgb, false, &bytes);
+    rc = frame_preamble(s, W, H, x0, x1, out_rgb, false, &bytes);
     if (rc) return rc;
+    LaunchRequest rq{.call = kCallFrame, .cam = cam, .W = W, .H = H, .x0 = x0, .x1 = x1, .max_depth = max_depth, .d_out = s->d_fb};
     /* counters, then one cycle count per wavefront tile */
-    const TileShape t = tile_shape(s, H, x0, x1);
+    const TileShape t = tile_shape(s, rq);
     const size_t n_tiles = (size_t)(t.tiles_z * t.tiles_x);
     const size_t words = RT_STATS_COUNT + n_tiles * RT_TILE_STATS;
-    unsigned long long *d_stats = nullptr;
-    HIP_TRY(hipMalloc(&d_stats, words * sizeof(unsigned long long)));
-    hipError_t e = hipMemset(d_stats, 0, words * sizeof(unsigned long long));
-    rc = e == hipSuccess ? launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr, d_stats)
-                         : fail(RT_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipMalloc(&rq.d_stats, words * sizeof(unsigned long long)));
+    hipError_t e = hipMemset(rq.d_stats, 0, words * sizeof(unsigned long long));
+    rc = e == hipSuccess ? launch(s, rq, nullptr) : fail(RT_ERR_HIP, hipGetErrorString(e));
     unsigned long long host[RT_STATS_COUNT] = {0};
     if (rc == RT_OK) {
-        e = hipMemcpy(host, d_stats, sizeof(host), hipMemcpyDeviceToHost);
+        e = hipMemcpy(host, rq.d_stats, sizeof(host), hipMemcpyDeviceToHost);
         if (e == hipSuccess && out_rgb && bytes) e = hipMemcpy(out_rgb, s->d_fb, bytes, hipMemcpyDeviceToHost);
         if (e == hipSuccess && wave_cycles && n_wave_cycles > 0)
-            e = hipMemcpy(wave_cycles, d_stats + RT_STATS_COUNT,
+            e = hipMemcpy(wave_cycles, rq.d_stats + RT_STATS_COUNT,
                           std::min((size_t)n_wave_cycles, n_tiles * RT_TILE_STATS) * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(RT_ERR_HIP, hipGetErrorString(e));
     }
-    (void)hipFree(d_stats);
+    (void)hipFree(rq.d_stats);
     if (rc) return rc;
     for (int k = 0; k < n_stats; ++k) stats[k] = k < RT_STATS_COUNT ? host[k] : 0;
     return RT_OK;
@@ -2203,22 +2207,19 @@ int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0
  * shape (W, H, x0, x1, max_depth, tile shape) start their queues at the row of the longest tile (launch(), LEARNED START ROW). */
 int rt_learn_tile_order(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
-    if (s->soft_used)
-        return fail(RT_ERR_INVALID, "the counting build does not sample area lights, so no tile order is learned (include/rt_capi_soft.h)");
-    if (s->refract_used)
-        return fail(RT_ERR_INVALID, "the counting build does not trace refraction, so no tile order is learned (include/rt_capi_refract.h)");
-    if (s->images_used)
-        return fail(RT_ERR_INVALID, "the counting build does not sample image textures, so no tile order is learned (include/rt_capi_texture.h)");
+    int rc = check_counting(s, ", so no tile order is learned");
+    if (rc) return rc;
     if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 >= x1) return fail(RT_ERR_INVALID, "need 0 <= x0 < x1 <= W, W,H > 0");
+    LaunchRequest rq{.call = kCallFrame, .cam = cam, .W = W, .H = H, .x0 = x0, .x1 = x1, .max_depth = max_depth};
     TileShape t;
     {
         std::lock_guard<std::mutex> lock(s->mu);
         s->row_peak.clear(); s->row_sum.clear();
-        t = tile_shape(s, H, x0, x1);
+        t = tile_shape(s, rq);
     }
     const size_t tiles_z = (size_t)t.tiles_z, tiles_x = (size_t)t.tiles_x;
     std::vector<uint64_t> stats(RT_STATS_COUNT), tiles(tiles_z * tiles_x * RT_TILE_STATS);
-    int rc = rt_render_stats(s, cam, W, H, x0, x1, max_depth, nullptr, stats.data(), RT_STATS_COUNT, tiles.data(), (int)tiles.size());
+    rc = rt_render_stats(s, cam, W, H, x0, x1, max_depth, nullptr, stats.data(), RT_STATS_COUNT, tiles.data(), (int)tiles.size());
     if (rc) return rc;
     const size_t macro_rows = (tiles_z + RT_MACRO_ROWS - 1) / RT_MACRO_ROWS;
     std::vector<double> peak(macro_rows, 0.0), sum(macro_rows, 0.0);
@@ -2238,6 +2239,7 @@ int rt_learn_tile_order(rt_scene *s, const rt_camera_desc *cam, int W, int H, in
      * from the longest tile's row upwards or downwards.  (Trying the HEAVY band and the tile priorities the other way round per
      * shape as well gave nothing beyond the strip model's +-4 %: profiles/r03_experiments.txt 23-24) */
     HIP_TRY(hipSetDevice(s->device));
+    rq.d_out = s->d_fb;                       /* (rt_render_stats made it large enough for the strip) */
     hipEvent_t e0 = nullptr, e1 = nullptr;
     {
         hipError_t e = hipEventCreate(&e0);
@@ -2253,7 +2255,7 @@ int rt_learn_tile_order(rt_scene *s, const rt_camera_desc *cam, int W, int H, in
         float shortest = 1e30f;
         for (int rep = 0; rep < 7 && rc == RT_OK; ++rep) {
             hipError_t e = hipEventRecord(e0, nullptr);
-            if (e == hipSuccess) rc = launch(s, cam, W, H, x0, x1, max_depth, static_cast<float *>(s->d_fb), nullptr);
+            if (e == hipSuccess) rc = launch(s, rq, nullptr);
             if (rc != RT_OK) break;
             e = hipEventRecord(e1, nullptr);
             if (e == hipSuccess) e = hipEventSynchronize(e1);

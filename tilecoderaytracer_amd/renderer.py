@@ -57,25 +57,25 @@ def denoise(rgb, hits, iterations=2, sigma_color=1.0, normal_squarings=3, device
 class Renderer:
     """Owns an ``rt_scene`` (device tables for one HostScene on one GPU)."""
 
+    _CREATE = ("rt_scene_create", "rt_scene_create_textured", "rt_scene_create_refractive", "rt_scene_create_soft")
+
     def __init__(self, host_scene, device=0):
-        self._lib = capi.load_library()
         self._host = host_scene          # keeps the desc arrays alive
+        # the scene's Texture_Image objects (include/rt_capi_texture.h), its refractive materials (include/rt_capi_refract.h)
+        # and its area lights (include/rt_capi_soft.h): the plainest entry point that carries what it has
+        images, refr, soft = host_scene.images, host_scene.refractions, host_scene.area_lights
+        self._create(host_scene.desc, device, images, refr, soft, 3 if soft[0] else 2 if refr[0] else 1 if images[0] else 0)
+        self._cam = host_scene.camera
+
+    def _create(self, desc, device, images, refractive, area_lights, entry):
+        """The scene of the description at pointer desc by entry point _CREATE[entry], which takes the first `entry` of the
+        three (count, array or None) pairs.  (A plain scene must call rt_scene_create: TCRT_LIBRARY may name an older build
+        that has nothing else, capi.py.)"""
+        self._lib = capi.load_library()
         self._scene = C.c_void_p()
         self._device = device
-        n_images, images = host_scene.images        # the scene's Texture_Image objects (include/rt_capi_texture.h)
-        n_refr, refr = host_scene.refractions       # its refractive materials (include/rt_capi_refract.h)
-        n_soft, soft = host_scene.area_lights       # its area lights (include/rt_capi_soft.h)
-        if n_soft:
-            capi.check(self._lib.rt_scene_create_soft(host_scene.desc, n_images, images, n_refr, refr, n_soft, soft, device,
-                                                      C.byref(self._scene)))
-        elif n_refr:
-            capi.check(self._lib.rt_scene_create_refractive(host_scene.desc, n_images, images, n_refr, refr, device,
-                                                            C.byref(self._scene)))
-        elif n_images:
-            capi.check(self._lib.rt_scene_create_textured(host_scene.desc, n_images, images, device, C.byref(self._scene)))
-        else:
-            capi.check(self._lib.rt_scene_create(host_scene.desc, device, C.byref(self._scene)))
-        self._cam = host_scene.camera
+        lists = (*images, *refractive, *area_lights)[:2 * entry]
+        capi.check(getattr(self._lib, self._CREATE[entry])(desc, *lists, device, C.byref(self._scene)))
 
     @classmethod
     def from_desc(cls, desc, camera, device=0, keepalive=None, images=None, refractive=None, area_lights=None):
@@ -88,33 +88,14 @@ class Renderer:
         samples, radius); with it (even an empty list) the scene is made by rt_scene_create_soft, with the images and the
         refractive objects if any."""
         self = cls.__new__(cls)
-        self._lib = capi.load_library()
         self._host = keepalive
-        self._scene = C.c_void_p()
-        self._device = device
-        if area_lights is not None:
-            arrays, descs = image_descs(images or [])
-            rdescs = refraction_descs(refractive or [])
-            adescs = area_light_descs(area_lights)
-            self._images = (arrays, descs, rdescs, adescs)
-            capi.check(self._lib.rt_scene_create_soft(
-                C.byref(desc), len(images or []), descs if images else None, len(refractive or []),
-                rdescs if refractive else None, len(area_lights), adescs if len(area_lights) else None, device,
-                C.byref(self._scene)))
-        elif refractive is not None:
-            arrays, descs = image_descs(images or [])
-            rdescs = refraction_descs(refractive)
-            self._images = (arrays, descs, rdescs)
-            capi.check(self._lib.rt_scene_create_refractive(
-                C.byref(desc), len(images or []), descs if images else None, len(refractive),
-                rdescs if len(refractive) else None, device, C.byref(self._scene)))
-        elif images is None:
-            capi.check(self._lib.rt_scene_create(C.byref(desc), device, C.byref(self._scene)))
-        else:
-            arrays, descs = image_descs(images)
-            self._images = (arrays, descs)         # the texels stay alive with the scene (the library copies them too)
-            ptr = descs if len(images) else None
-            capi.check(self._lib.rt_scene_create_textured(C.byref(desc), len(images), ptr, device, C.byref(self._scene)))
+        given = (images, refractive, area_lights)
+        arrays, descs = image_descs(images or [])
+        made = (descs, refraction_descs(refractive or []), area_light_descs(area_lights or []))
+        self._images = (arrays,) + made            # the texels stay alive with the scene (the library copies them too)
+        pairs = [(len(g or []), m if g else None) for g, m in zip(given, made)]       # (an empty list: count 0, no array)
+        entry = max(k + 1 if g is not None else 0 for k, g in enumerate(given))      # the last list that is given, even empty
+        self._create(C.byref(desc), device, *pairs, entry)
         self._cam = C.pointer(camera)
         return self
 
@@ -214,15 +195,10 @@ class Renderer:
         """Trace a batch of primary rays (include/rt_capi_rays.h).  rays: C-contiguous float32, (n, 6) -- rows defaults to n --
         or (X, Z, 6), ray [x, z] = cell (x, z) of the grid, rows = Z; each ray {E.xyz, T.xyz} starts at E towards T.
         -> float32 (n, 3) or (X, Z, 3).  rows only shapes the launch; the results do not depend on it."""
-        if not isinstance(rays, np.ndarray) or rays.dtype != np.float32 or not rays.flags.c_contiguous:
-            raise TypeError("rays must be a C-contiguous float32 numpy array")
-        if rays.ndim not in (2, 3) or rays.shape[-1] != 6:
-            raise ValueError(f"rays must have shape (n, 6) or (X, Z, 6), not {rays.shape}")
-        n = rays.size // 6
-        if rows is None:
-            rows = max(rays.shape[1] if rays.ndim == 3 else n, 1)       # (an empty batch: any rows)
+        n, default_rows = self._batch(rays, "rays")
         out = np.empty(rays.shape[:-1] + (3,), dtype=np.float32)
-        capi.check(self._lib.rt_trace_rays(self._scene, n, int(rows), rays.ctypes.data, max_depth, out.ctypes.data))
+        capi.check(self._lib.rt_trace_rays(self._scene, n, int(default_rows if rows is None else rows), rays.ctypes.data, max_depth,
+                                           out.ctypes.data))
         return out
 
     def trace_rays_device(self, n, rows, rays_ptr, max_depth, out_ptr, stream=0):
@@ -237,7 +213,7 @@ class Renderer:
         if rays.ndim not in (2, 3) or rays.shape[-1] != 6:
             raise ValueError(f"{what} must have shape (n, 6) or (X, Z, 6), not {rays.shape}")
         n = rays.size // 6
-        return n, max(rays.shape[1] if rays.ndim == 3 else n, 1)
+        return n, max(rays.shape[1] if rays.ndim == 3 else n, 1)       # (an empty batch: any rows)
 
     def intersect_rays(self, rays, rows=None):
         """What each ray hits (include/rt_capi_query.h, rt_intersect_rays).  rays: C-contiguous float32, (n, 6) -- rows defaults
