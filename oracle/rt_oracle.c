@@ -3,8 +3,8 @@
  * path of ccelio/TileCodeRayTracer (float mode, x86, PARTIONING_STRATEGY 0).
  *
  * TEST INFRASTRUCTURE ONLY -- see rt_oracle.h for who may use this and for
- * the parity status ("parity unpinned" by the strict definition; checked
- * against the digests recorded in SURVEY.md Appendix D).
+ * the parity status (pinned to a build of the reference itself:
+ * tests/test_reference_pins_cpu.py, tests/golden/ref/).
  *
  * Build:  gcc -O2 -ffp-contract=off -fno-fast-math (oracle/Makefile).
  * The arithmetic is IEEE-754 binary32 in exactly the reference's operation

@@ -6,14 +6,21 @@
  * or call this.  Only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg use it, and only as the checker / the timed CPU baseline.
  *
- * PARITY STATUS (read DESIGN.md "Oracle"): the reference ships no tests, no
- * golden vectors and no fixtures, and it does not compile as shipped (it
- * includes fixed_class.h / fixed_func.h, which are not in the tree).  Writing
- * stand-ins for those headers is not allowed in this build, so no oracle/_ref
- * binary exists and, by the strict definition, this oracle is
- * "parity unpinned".  What it IS checked against: the SHA-256 digests and
- * spot pixel values that SURVEY.md Appendix D recorded from the survey's own
- * scratch build of the reference (tests/test_oracle_pins.py).
+ * PARITY STATUS (read DESIGN.md "Oracle"): pinned to a build of the reference
+ * itself.  The reference ships no tests, no golden vectors and no fixtures,
+ * and it does not compile as shipped (it includes fixed_class.h /
+ * fixed_func.h, which are not in the tree); `make -C oracle ref` compiles its
+ * own sources with two stand-in headers (oracle/ref/) into
+ * oracle/_ref/ref_harness, and tests/golden/ref/ holds what that binary wrote:
+ * frames, getCollision records, calculatePixel colours,
+ * inShadeCollisionDetection verdicts and the digests of a 268-case sweep.
+ * tests/test_reference_pins_cpu.py holds this oracle to all of it, always, and
+ * to the binary itself on fresh seeds where the binary exists;
+ * tests/test_oracle_pins.py keeps the seven digests SURVEY.md Appendix D
+ * recorded.  NOT pinned by the reference, because it has no such thing: the
+ * families the product adds (supersampling, image textures, refraction, soft
+ * shadows, the denoiser -- their references are tests/*_ref.py), the
+ * fixed-point mode and the Tilera partitioning strategies.
  *
  * Every function cites the reference file:line it restates
  * (paths relative to /root/reference/).

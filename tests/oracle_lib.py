@@ -205,6 +205,9 @@ def write_screen_txt(path, rgb, run_time_s=0.0, us_per_pixel=0.0):
 # SHA-256 digests of packed fp32 framebuffers recorded in SURVEY.md Appendix D
 # from the survey's scratch build of the reference.  The grid scenes there were
 # assembled with addObject() alone, i.e. shadow scan range [0, 0) ("-noshadow").
+# The three 64 x 64 ones are reproduced by oracle/_ref/ref_harness, the
+# repeatable build of the reference (golden/make_ref_pins.py rewrites their
+# .f32 files from it, byte for byte); the wider pins are in golden/ref/.
 SURVEY_PINS = {
     "b64d4":    ("builtin",          64,  64, 4, "8112d69522905d6d09c7d35704e5d9cfe880d4b4dd89c84a6c7c46d7290567cf"),
     "g32_64d4": ("grid32-noshadow",  64,  64, 4, "c3f0ba632a02d04176bc3024d713078d4c8b769f4543c7ac0135c38ee6146939"),

@@ -2,9 +2,9 @@
 pixel values recorded in SURVEY.md Appendix D from the survey's scratch build
 of the reference, and the committed golden fixtures must be those same images.
 
-The reference ships no tests and no fixtures of its own and is unbuildable
-here, so these recorded digests are the only external pin there is (see
-DESIGN.md "Oracle": strictly, "parity unpinned").
+The reference ships no tests and no fixtures of its own.  These recorded
+digests were the first external pin; test_reference_pins_cpu.py holds the
+oracle to a repeatable build of the reference itself (DESIGN.md "Oracle").
 """
 import hashlib
 import os

@@ -66,7 +66,7 @@ def test_survey_digests_on_gpu(oracle, key):
 
 def test_extra_digests():
     extra = json.load(open(os.path.join(GOLDEN, "extra.json")))
-    assert "grid32_256x256_d4" in extra and "grid16_256x256_d8" in extra       # the shadowed grids at 256 x 256 (oracle-only pins: "_about")
+    assert "grid32_256x256_d4" in extra and "grid16_256x256_d8" in extra       # the shadowed grids at 256 x 256 (also in ref/digests.json, from the reference)
     for key, digest in extra.items():
         if key.startswith("_"):
             continue

@@ -1,5 +1,6 @@
 """Build every native piece: the HIP library, the host library/executable and
-(test infrastructure) the oracle.  Used by __graft_entry__.build()."""
+(test infrastructure) the oracle and, where its sources exist, the reference
+harness.  Used by __graft_entry__.build()."""
 import os
 import subprocess
 
@@ -21,6 +22,15 @@ def build_product():
 
 def build_oracle():
     return _make(os.path.join(_ROOT, "oracle"))
+
+
+def build_reference_harness():
+    """oracle/_ref/ref_harness from the reference's own sources (oracle/Makefile, target `ref`) if they are on this machine;
+    None, and nothing built, if they are not.  Test infrastructure, like the oracle."""
+    reference = os.environ.get("REFERENCE", "/root/reference")
+    if not os.path.isdir(os.path.join(reference, "src")):
+        return None
+    return _make(os.path.join(_ROOT, "oracle"), "ref", f"REFERENCE={reference}")
 
 
 def build_all():
