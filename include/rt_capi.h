@@ -121,7 +121,9 @@ int rt_scene_destroy(rt_scene *scene);
  * memory, packed fp32: out_rgb[((x-x0)*H + z)*3 + c] -- the pixels[x][z]
  * order of src/RayTracer.h:44.  dx = (float)x / W, dz = (float)z / H use the
  * global W, H, so a strip is bit-identical to the same columns of a full
- * render.  Synchronous. */
+ * render.  Synchronous.  A strip may hold at most 8e9 floats (32 GB):
+ * 3 (x1 - x0) H beyond that is RT_ERR_INVALID, "strip too large", like
+ * every bad argument before any device work. */
 int rt_render(rt_scene *scene, const rt_camera_desc *cam, int W, int H,
               int x0, int x1, int max_depth, float *out_rgb);
 

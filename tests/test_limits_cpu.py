@@ -1,0 +1,269 @@
+"""Every documented size refusal at its exact boundary, without a GPU: the last admitted value passes its check -- the call then
+fails a LATER check, whose text it reports, or reaches the device question (RT_ERR_NO_DEVICE on a machine without one) -- and
+the first refused value is RT_ERR_INVALID with the limit's text.  The handle is test_gbuffer_cpu.py's stand-in (zeroed memory,
+never a scene): every check comes before the handle's contents are used.  Then the two facts test_large_extents_gpu.py leans on:
+large_extents.column_rays is rays_ref.camera_rays, and denoise_ref is local within m = 2 (2^iterations - 1) pixels on BOTH axes.
+
+The limits, in integers (the checks compare in double, exactly at these sizes):
+  rt_render*            3 (x1 - x0) H <= 8e9 floats.  8e9 is not a multiple of 3: the last admitted strip has 2 666 666 666 pixels
+                        (7 999 999 998 floats), the first refused one 2 666 666 667 (8 000 000 001).
+  rt_render_gbuffer*    60 (x1 - x0) H <= 3.2e10 bytes: 533 333 333 pixels pass, 533 333 334 do not.
+  ray batches           n_cols x rows <= 2^31 - 65 cells.  The other limit, 3 n <= 8e9, cannot be reached: n is an int.
+  rt_render_ssaa*       W << kl and H << kl <= 2^31 - 1: W = 2^30 - 1 (k = 2) and 2^29 - 1 (k = 4) pass, 2^30 and 2^29 do not;
+                        the virtual strip 3 k^2 (x1 - x0) H <= 8e9: k = 2, 666 666 666 pixels pass, 666 666 667 do not.
+The HBM bounce stack's 8e9 bytes (RT_ERR_CAPACITY) depend on the device's occupancy and are not reachable without one."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import denoise_ref
+import large_extents as le
+from rays_ref import camera_rays
+from test_denoise_cpu import random_frame
+from tilecoderaytracer_amd import HostScene, capi
+
+INT_MAX = (1 << 31) - 1
+LAST_STRIP, FIRST_REFUSED_STRIP = (1333333333, 2), (888888889, 3)          # (columns, H): 2 666 666 666 and 2 666 666 667 pixels
+assert LAST_STRIP[0] * LAST_STRIP[1] * 3 == 8 * 10 ** 9 - 2 and FIRST_REFUSED_STRIP[0] * FIRST_REFUSED_STRIP[1] * 3 == 8 * 10 ** 9 + 1
+LAST_GBUFFER, FIRST_REFUSED_GBUFFER = 533333333, 533333334
+assert LAST_GBUFFER * 60 <= 32 * 10 ** 9 < FIRST_REFUSED_GBUFFER * 60
+LAST_CELLS = (1 << 31) - 65
+A, B = 0x10000, 0x40000                  # fake addresses, never dereferenced: every call below returns before it would
+
+
+@pytest.fixture()
+def lib():
+    return capi.load_library()
+
+
+@pytest.fixture()
+def cam():
+    return HostScene.builtin().camera
+
+
+@pytest.fixture()
+def stand_in():
+    buf = C.create_string_buffer(1 << 20)
+    yield buf
+    assert not any(buf.raw)              # no refused call wrote into the handle
+
+
+def launched():
+    """a stand-in of its own for the calls that pass every check and reach the device question: a launch notes its shape in the
+    handle before it asks for the device"""
+    return C.create_string_buffer(1 << 20)
+
+
+def text(lib):
+    return lib.rt_last_error().decode()
+
+
+# ---- rt_render, rt_render_device ------------------------------------------------------------------------------------------------
+
+def test_render_strip_limit_first_refused_value(lib, cam, stand_in):
+    """8 000 000 001 floats: "strip too large", from the host call BEFORE any device work (no framebuffer of 32 GB is allocated
+    first) and from the device call"""
+    cols, H = FIRST_REFUSED_STRIP
+    assert lib.rt_render(stand_in, cam, cols, H, 0, cols, 2, A) == capi.RT_ERR_INVALID
+    assert "strip too large" in text(lib)
+    assert lib.rt_render_device(stand_in, cam, cols, H, 0, cols, 2, A, None) == capi.RT_ERR_INVALID
+    assert "strip too large" in text(lib)
+    # the strip counts, not the frame: the same columns of a wider frame, and one column more of the last admitted strip
+    assert lib.rt_render(stand_in, cam, INT_MAX, H, 5, 5 + cols, 2, A) == capi.RT_ERR_INVALID and "strip too large" in text(lib)
+    cols, H = LAST_STRIP
+    assert lib.rt_render_device(stand_in, cam, cols + 1, H, 0, cols + 1, 2, A, None) == capi.RT_ERR_INVALID
+    assert "strip too large" in text(lib)
+    # the counting call renders into the handle's framebuffer as rt_render does: refused before that is allocated, too
+    cols, H = FIRST_REFUSED_STRIP
+    counters = (C.c_uint64 * 64)()
+    assert lib.rt_render_stats(stand_in, cam, cols, H, 0, cols, 2, None, counters, 64, None, 0) == capi.RT_ERR_INVALID
+    assert "strip too large" in text(lib)
+    # the earlier checks still come first, in rt_render's order
+    assert lib.rt_render(stand_in, cam, cols, H, 0, cols, 2, None) == capi.RT_ERR_INVALID and "out_rgb" in text(lib)
+    assert lib.rt_render(stand_in, None, cols, H, 0, cols, 2, A) == capi.RT_ERR_INVALID and "camera" in text(lib)
+    assert lib.rt_render(stand_in, cam, cols, H, 0, cols, -1, A) == capi.RT_ERR_INVALID and "max_depth" in text(lib)
+
+
+def test_render_strip_limit_last_admitted_value(lib, cam, stand_in, have_gpu):
+    """7 999 999 998 floats pass the check.  Shown by a later check's text: rt_render_ssaa* checks the output strip as rt_render
+    does, then the virtual size -- W << 1 = 2 666 666 666 is "samples * W ...", which a refused strip never reaches.  Without a
+    device the plain calls reach the device question."""
+    cols, H = LAST_STRIP
+    for k in (2, 4):
+        assert lib.rt_render_ssaa(stand_in, cam, cols, H, 0, cols, 2, k, A) == capi.RT_ERR_INVALID
+        assert "samples * W" in text(lib)
+        assert lib.rt_render_ssaa_device(stand_in, cam, cols, H, 0, cols, 2, k, A, None) == capi.RT_ERR_INVALID
+        assert "samples * W" in text(lib)
+    cols3, H3 = FIRST_REFUSED_STRIP                                          # (the pair: here the strip's check is the one)
+    assert lib.rt_render_ssaa(stand_in, cam, cols3, H3, 0, cols3, 2, 4, A) == capi.RT_ERR_INVALID
+    assert "strip too large" in text(lib)
+    if have_gpu:
+        return                           # (with a device the admitted call would go on to use the stand-in as a scene)
+    assert lib.rt_render(launched(), cam, cols, H, 0, cols, 2, A) == capi.RT_ERR_NO_DEVICE
+    assert lib.rt_render_device(launched(), cam, cols, H, 0, cols, 2, A, None) == capi.RT_ERR_NO_DEVICE
+
+
+# ---- rt_render_gbuffer* ---------------------------------------------------------------------------------------------------------
+
+def test_gbuffer_limit_at_60_bytes_a_pixel(lib, cam, stand_in, have_gpu):
+    """533 333 334 pixels: the records' refusal (their colours are far below rt_render's limit).  533 333 333 pixels pass it: the
+    device call goes on to its next check, the records' alignment."""
+    for W, H in ((FIRST_REFUSED_GBUFFER, 1), (FIRST_REFUSED_GBUFFER // 2, 2), (2, FIRST_REFUSED_GBUFFER // 2)):
+        assert lib.rt_render_gbuffer(stand_in, cam, W, H, 0, W, 2, A, B) == capi.RT_ERR_INVALID
+        assert "strip too large for its colours and records" in text(lib)
+        assert lib.rt_render_gbuffer_device(stand_in, cam, W, H, 0, W, 2, A, B, None) == capi.RT_ERR_INVALID
+        assert "strip too large for its colours and records" in text(lib)
+    for W, H in ((LAST_GBUFFER, 1), (1, LAST_GBUFFER)):
+        assert lib.rt_render_gbuffer_device(stand_in, cam, W, H, 0, W, 2, A, B + 4, None) == capi.RT_ERR_INVALID
+        assert "16-byte aligned" in text(lib)
+        assert lib.rt_render_gbuffer(stand_in, cam, W, H, 0, W, 2, A, None) == capi.RT_ERR_INVALID     # (the check before it)
+        assert "out_hits" in text(lib)
+    if have_gpu:
+        return
+    assert lib.rt_render_gbuffer(launched(), cam, LAST_GBUFFER, 1, 0, LAST_GBUFFER, 2, A, B) == capi.RT_ERR_NO_DEVICE
+    assert lib.rt_render_gbuffer_device(launched(), cam, LAST_GBUFFER, 1, 0, LAST_GBUFFER, 2, A, B, None) == capi.RT_ERR_NO_DEVICE
+
+
+# ---- rt_trace_rays*, rt_intersect_rays*, rt_occluded_rays* -----------------------------------------------------------------------
+
+def _batch_calls(lib, stand_in, n, rows):
+    """every batch entry point with n rays in `rows` rows -> [(name, rc, text)]"""
+    out = []
+    for name, args in (("rt_trace_rays", (n, rows, A, 2, B)), ("rt_trace_rays_device", (n, rows, A, 2, B, None)),
+                       ("rt_intersect_rays", (n, rows, A, B)), ("rt_intersect_rays_device", (n, rows, A, B, None)),
+                       ("rt_occluded_rays", (n, rows, A, B)), ("rt_occluded_rays_device", (n, rows, A, B, None))):
+        rc = getattr(lib, name)(stand_in, *args)
+        out.append((name, rc, text(lib)))
+    return out
+
+
+# (n, rows) -> n_cols x rows cells: rows > n is read as n; the cells are ceil(n / rows) * rows
+REFUSED_GRIDS = [(LAST_CELLS + 1, LAST_CELLS + 1), (LAST_CELLS + 1, INT_MAX), (LAST_CELLS + 1, 1), (LAST_CELLS + 1, 1 << 16),
+                 (LAST_CELLS, 1 << 16),             # 2^31 - 65 rays in rows of 2^16: 32 768 columns, 2^31 cells
+                 (INT_MAX, 1), (INT_MAX, INT_MAX)]   # the largest n there is: 3 n = 6.4e9 floats is below 8e9, the grid is not
+ADMITTED_GRIDS = [(LAST_CELLS, LAST_CELLS), (LAST_CELLS, INT_MAX), (LAST_CELLS, 1), (LAST_CELLS, 63),
+                  (LAST_CELLS - (1 << 16) + 65, 1 << 16)]     # 2^31 - 2^16 rays: 32 767 full columns, the last grid below the limit
+
+
+def _cells(n, rows):
+    rows = min(rows, n)
+    return (n + rows - 1) // rows * rows
+
+
+def test_ray_batch_grid_limit(lib, stand_in, have_gpu):
+    for n, rows in REFUSED_GRIDS:
+        assert _cells(n, rows) > LAST_CELLS
+        for name, rc, msg in _batch_calls(lib, stand_in, n, rows):
+            assert rc == capi.RT_ERR_INVALID and "ray batch too large for its rows" in msg, (name, n, rows, rc, msg)
+    for n, rows in ADMITTED_GRIDS:
+        assert _cells(n, rows) <= LAST_CELLS
+    assert _cells(*ADMITTED_GRIDS[0]) == LAST_CELLS and _cells(*REFUSED_GRIDS[0]) == LAST_CELLS + 1
+    # the grid's check is the last one: an admitted grid with an earlier fault reports that fault, a refused one too
+    assert lib.rt_trace_rays_device(stand_in, LAST_CELLS, LAST_CELLS, A, -1, B, None) == capi.RT_ERR_INVALID
+    assert "max_depth" in text(lib)
+    assert lib.rt_trace_rays_device(stand_in, LAST_CELLS + 1, LAST_CELLS + 1, A, 2, None, None) == capi.RT_ERR_INVALID
+    assert "output pointer" in text(lib)
+    if have_gpu:
+        return                           # (with a device an admitted batch would be uploaded from the fake address)
+    for n, rows in ADMITTED_GRIDS:
+        for name, rc, msg in _batch_calls(lib, launched(), n, rows):
+            assert rc == capi.RT_ERR_NO_DEVICE, (name, n, rows, rc, msg)
+
+
+# ---- rt_render_ssaa* ------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("k", [2, 4])
+def test_ssaa_virtual_size_limit(lib, cam, stand_in, k, have_gpu):
+    """W << kl and H << kl must stay below 2^31.  They are multiples of k, so the largest admitted is 2^31 - k (W = 2^31 / k - 1)
+    and the first refused 2^31 itself.  The admitted size goes on to the next check, the virtual strip's: a strip of 2^28 x 3 output
+    pixels is within rt_render's limit (2.4e9 floats) and its k x k samples are not."""
+    last = (1 << 31) // k - 1
+    for W, H, x1 in ((last + 1, 1, 1), (1, last + 1, 1), (last + 1, last + 1, 1), (INT_MAX, 1, 0)):
+        assert lib.rt_render_ssaa(stand_in, cam, W, H, 0, x1, 2, k, A) == capi.RT_ERR_INVALID
+        assert "samples * W and samples * H must stay below 2^31" in text(lib), (W, H)
+        assert lib.rt_render_ssaa_device(stand_in, cam, W, H, 0, x1, 2, k, A, None) == capi.RT_ERR_INVALID
+        assert "samples * W and samples * H must stay below 2^31" in text(lib), (W, H)
+    assert lib.rt_render_ssaa_device(stand_in, cam, last, 3, 0, 1 << 28, 2, k, A, None) == capi.RT_ERR_INVALID
+    assert "strip too large" in text(lib)
+    if have_gpu:
+        return
+    assert lib.rt_render_ssaa(launched(), cam, last, 1, 0, 1, 2, k, A) == capi.RT_ERR_NO_DEVICE
+    # H at its limit passes the size check too: one column's k x k samples (3 k^2 H floats) then exceed the virtual strip's limit
+    assert lib.rt_render_ssaa_device(launched(), cam, 1, last, 0, 1, 2, k, A, None) == capi.RT_ERR_INVALID
+    assert "strip too large" in text(lib)
+    # ... and an empty strip of that frame passes every check: nothing to launch, RT_OK
+    assert lib.rt_render_ssaa_device(launched(), cam, 1, last, 1, 1, 2, k, A, None) == capi.RT_OK
+
+
+def test_ssaa_virtual_strip_at_the_float_limit(lib, cam, stand_in, have_gpu):
+    """k = 2: 12 floats an output pixel.  666 666 667 pixels (8 000 000 004 virtual floats) are refused by the virtual strip's check
+    -- the output strip's, 2.0e9 floats, passed; 666 666 666 (7 999 999 992) pass both.  k = 4: 166 666 666 and 166 666 667."""
+    for k, last in ((2, 666666666), (4, 166666666)):
+        assert 3 * k * k * last <= 8 * 10 ** 9 < 3 * k * k * (last + 1)
+        for W, H in ((last + 1, 1), (1, last + 1)):
+            assert lib.rt_render_ssaa(stand_in, cam, W, H, 0, W, 2, k, A) == capi.RT_ERR_INVALID
+            assert "strip too large" in text(lib)
+            assert lib.rt_render_ssaa_device(stand_in, cam, W, H, 0, W, 2, k, A, None) == capi.RT_ERR_INVALID
+            assert "strip too large" in text(lib)
+        if have_gpu:
+            continue
+        assert lib.rt_render_ssaa(launched(), cam, last, 1, 0, last, 2, k, A) == capi.RT_ERR_NO_DEVICE
+        assert lib.rt_render_ssaa_device(launched(), cam, 2, last // 2, 0, 2, 2, k, A, None) == capi.RT_ERR_NO_DEVICE
+
+
+# ---- what the large GPU tests lean on ----------------------------------------------------------------------------------------------
+
+def test_column_rays_are_the_frames_rays():
+    cam = HostScene.builtin().camera
+    for W, H in ((37, 29), (1, 5), (300, 2)):
+        whole = camera_rays(cam, W, H)
+        for x0, x1 in ((0, W), (W // 2, W // 2 + 1), (W - 1, W), (W // 3, W)):
+            assert le.column_rays(cam, W, H, x0, x1).tobytes() == whole[x0:x1].tobytes()
+    # above 2^24 the column number is rounded to fp32 as (float)x does it: to even
+    big = le.column_rays(cam, (1 << 24) + 4096, 4, (1 << 24) - 2, (1 << 24) + 6)
+    assert big[3].tobytes() == big[2].tobytes() and big[3].tobytes() != big[4].tobytes()     # 2^24 + 1 -> 2^24
+    assert big[5].tobytes() == big[6].tobytes()                                                 # 2^24 + 3 -> 2^24 + 4
+    assert le.column_keys(5, 2, 4).tolist() == [[10, 11, 12, 13, 14], [15, 16, 17, 18, 19]]
+    assert le.column_keys(1 << 16, (1 << 16) + 1, (1 << 16) + 2)[0, 3] == (1 << 16) + 3          # modulo 2^32
+
+
+def test_boundary_columns():
+    H = 18000
+    cols = le.boundary_columns([1 << 31, 1 << 32], 12 * H, 20000)
+    c31, c32 = (1 << 31) // (12 * H), (1 << 32) // (12 * H)
+    assert cols == [0, c31 - 1, c31, c31 + 1, c32 - 1, c32, c32 + 1, 19999]
+    assert c31 * 12 * H < (1 << 31) < (c31 + 1) * 12 * H
+    assert le.runs(cols) == [(0, 1), (c31 - 1, c31 + 2), (c32 - 1, c32 + 2), (19999, 20000)]
+    with pytest.raises(AssertionError):
+        le.boundary_columns([1 << 31], 1 << 20, 20000)          # falls between two columns
+    with pytest.raises(AssertionError):
+        le.boundary_columns([1 << 32], 12 * H, 1000)            # not inside the buffer
+
+
+@pytest.mark.parametrize("iterations, sigma, squarings", [(1, 0.0, 0), (2, 1.0, 3), (3, 1.0, 3), (3, 0.0, 0)])
+def test_denoise_ref_is_local_on_both_axes(iterations, sigma, squarings):
+    """The header's strip statement, on x AND on z: an output pixel depends on nothing farther than m = 2 (2^iterations - 1)
+    pixels away on either axis (iteration i reaches 2 * 2^i; the sum over i is m).  So denoise_ref of a crop that holds a window
+    and a margin of m around it -- clipped where the frame itself ends, so that a tap outside the frame stays a tap that does not
+    exist -- equals the whole frame's result on the window, bit for bit.  And m is tight: one pixel less of margin changes it."""
+    Wn, H = 90, 83
+    m = 2 * (2 ** iterations - 1)
+    rgb, hits = random_frame(40 + iterations, Wn, H, n_objects=1, palette=1)
+    hits["flags"] &= 1                                        # (few pass-throughs: almost every pixel filters)
+    hits["object"] = 0
+    hits["object"][::7, ::5] = -1
+    full = denoise_ref.denoise(rgb, hits, iterations, sigma, squarings)
+    for x0, x1, z0, z1 in ((0, 20, 0, 20), (70, 90, 63, 83), (0, 20, 63, 83), (70, 90, 0, 20), (30, 55, 28, 50), (0, 90, 30, 40),
+                           (40, 47, 0, 83)):
+        cx0, cx1, cz0, cz1 = max(x0 - m, 0), min(x1 + m, Wn), max(z0 - m, 0), min(z1 + m, H)
+        crop = denoise_ref.denoise(rgb[cx0:cx1, cz0:cz1], hits[cx0:cx1, cz0:cz1], iterations, sigma, squarings)
+        window = crop[x0 - cx0:x1 - cx0, z0 - cz0:z1 - cz0]
+        assert denoise_ref.same_bits(window, full[x0:x1, z0:z1]), (x0, x1, z0, z1)
+    # tightness, on z alone and on x alone: a margin of m - 1 is not enough
+    x0, x1, z0, z1 = 30, 55, 28, 50
+    short_z = denoise_ref.denoise(rgb[x0 - m:x1 + m, z0 - m + 1:z1 + m - 1], hits[x0 - m:x1 + m, z0 - m + 1:z1 + m - 1], iterations,
+                                  sigma, squarings)[m:-m, m - 1:-(m - 1)]
+    short_x = denoise_ref.denoise(rgb[x0 - m + 1:x1 + m - 1, z0 - m:z1 + m], hits[x0 - m + 1:x1 + m - 1, z0 - m:z1 + m], iterations,
+                                  sigma, squarings)[m - 1:-(m - 1), m:-m]
+    assert not denoise_ref.same_bits(short_z, full[x0:x1, z0:z1]) and not denoise_ref.same_bits(short_x, full[x0:x1, z0:z1])

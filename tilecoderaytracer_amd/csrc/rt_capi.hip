@@ -1733,10 +1733,14 @@ int check_strip(int W, int H, int x0, int x1, const void *out_rgb, bool out_requ
     return RT_OK;
 }
 
-/* rt_render and rt_render_stats, under the handle's lock: the strip's checks, the device, and the framebuffer the frame is
- * rendered into (*bytes of it) */
-int frame_preamble(rt_scene *s, int W, int H, int x0, int x1, const float *out_rgb, bool out_required, size_t *bytes) {
+/* rt_render, rt_render_ssaa and rt_render_stats, under the handle's lock: the strip's checks and the launch's (in the order a
+ * launch finds them, so that a strip beyond the limit is refused before a framebuffer of its size is allocated -- the launch
+ * renders into the handle's framebuffer, which is what check_launch_args() is told), then the device and that framebuffer
+ * (*bytes of it) */
+int frame_preamble(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const float *out_rgb,
+                   bool out_required, size_t *bytes) {
     int rc = check_strip(W, H, x0, x1, out_rgb, out_required);
+    if (rc == RT_OK) rc = check_launch_args(cam, W, H, x0, x1, max_depth, &s->d_fb);
     if (rc) return rc;
     *bytes = (size_t)(x1 - x0) * (size_t)H * 3 * sizeof(float);
     HIP_TRY(hipSetDevice(s->device));
@@ -2070,7 +2074,7 @@ int rt_render(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int 
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
     std::lock_guard<std::mutex> lock(s->mu);
     size_t bytes = 0;
-    int rc = frame_preamble(s, W, H, x0, x1, out_rgb, true, &bytes);
+    int rc = frame_preamble(s, cam, W, H, x0, x1, max_depth, out_rgb, true, &bytes);
     if (rc) return rc;
     return render_to_host(s, {.call = kCallFrame, .cam = cam, .W = W, .H = H, .x0 = x0, .x1 = x1, .max_depth = max_depth, .d_out = s->d_fb},
                           {{out_rgb, s->d_fb, bytes}});
@@ -2089,7 +2093,7 @@ int rt_render_ssaa(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0,
     if (kl == 0) return rt_render(s, cam, W, H, x0, x1, max_depth, out_rgb);
     std::lock_guard<std::mutex> lock(s->mu);
     size_t bytes = 0;
-    rc = frame_preamble(s, W, H, x0, x1, out_rgb, true, &bytes);
+    rc = frame_preamble(s, cam, W, H, x0, x1, max_depth, out_rgb, true, &bytes);
     if (rc) return rc;
     return render_to_host(s, {.call = kCallSsaa, .cam = cam, .W = W << kl, .H = H << kl, .x0 = x0 << kl, .x1 = x1 << kl,
                               .max_depth = max_depth, .ssaa_log2 = kl, .d_out = s->d_fb},
@@ -2177,7 +2181,7 @@ int rt_render_stats(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
     size_t bytes = 0;
-    rc = frame_preamble(s, W, H, x0, x1, out_rgb, false, &bytes);
+    rc = frame_preamble(s, cam, W, H, x0, x1, max_depth, out_rgb, false, &bytes);
     if (rc) return rc;
     LaunchRequest rq{.call = kCallFrame, .cam = cam, .W = W, .H = H, .x0 = x0, .x1 = x1, .max_depth = max_depth, .d_out = s->d_fb};
     /* counters, then one cycle count per wavefront tile */
