@@ -58,6 +58,16 @@ class RtDenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("sigma_color", C.c_float)]
 
 
+RT_TRANSFER_SRGB, RT_TRANSFER_LINEAR, RT_TRANSFER_CUSTOM = 0, 1, 2
+
+
+class RtImageParams(C.Structure):
+    """include/rt_capi_image.h: channels (3 or 4), bottom_up (0: row 0 is the top), transfer (RT_TRANSFER_*), exposure (finite,
+    > 0), thresholds (RT_TRANSFER_CUSTOM: 255 floats T[1..255])."""
+    _fields_ = [("channels", C.c_int32), ("bottom_up", C.c_int32), ("transfer", C.c_int32), ("exposure", C.c_float),
+                ("thresholds", C.POINTER(C.c_float))]
+
+
 class RtSceneDesc(C.Structure):
     _fields_ = [
         ("n_objects", C.c_int32), ("objects", C.POINTER(RtObjectDesc)),
@@ -220,6 +230,13 @@ def load_library():
         lib.rt_denoise.restype = lib.rt_denoise_device.restype = i
         lib.rt_denoise_scratch_bytes.argtypes = [C.POINTER(RtDenoiseParams), i, i]
         lib.rt_denoise_scratch_bytes.restype = C.c_uint64
+    # include/rt_capi_image.h (likewise absent from older builds)
+    if hasattr(lib, "rt_encode_image"):
+        lib.rt_capi_image_version.restype = i
+        lib.rt_image_transfer_table.argtypes = [i, C.POINTER(C.c_float)]
+        lib.rt_encode_image.argtypes = [i, C.POINTER(RtImageParams), i, i, vp, vp, C.c_uint64, C.POINTER(C.c_double)]
+        lib.rt_encode_image_device.argtypes = [i, C.POINTER(RtImageParams), i, i, vp, vp, C.c_uint64, vp]
+        lib.rt_image_transfer_table.restype = lib.rt_encode_image.restype = lib.rt_encode_image_device.restype = i
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):
         lib.rt_capi_launch_version.restype = i

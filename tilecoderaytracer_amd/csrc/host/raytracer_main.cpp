@@ -19,6 +19,9 @@
  *   --denoise IT[:SIGMA[:K]]  filter the frame by its hit records before it is written (rt_render_gbuffer, then rt_denoise:
  *                       IT iterations 1..5, colour sigma SIGMA >= 0 (default 1.0), K normal squarings 0..6 (default 3)); one
  *                       GPU, no supersampling (a supersampled frame has no records)
+ *   --ppm FILE          also the frame as a binary PPM, whatever made it (plain, --ssaa, --denoise, --gpus): rt_encode_image with
+ *                       the sRGB table, 3 channels, the top row first (include/rt_capi_image.h)
+ *   --exposure E        the colours are multiplied by E (finite, > 0; default 1) before they are encoded; needs --ppm
  */
 #include <chrono>
 #include <cmath>
@@ -32,8 +35,10 @@
 #include "../../../include/rt_capi.h"
 #include "../../../include/rt_capi_denoise.h"
 #include "../../../include/rt_capi_gbuffer.h"
+#include "../../../include/rt_capi_image.h"
 #include "../../../include/rt_capi_ssaa.h"
 #include "celio_model.hpp"
+#include "screen_ppm.hpp"
 #include "screen_txt.hpp"
 
 using namespace CelioRayTracer;
@@ -47,14 +52,14 @@ static int usage(const char *argv0) {
     std::fprintf(stderr,
                  "usage: %s [--width W] [--height H] [--depth D] [--scene 1|2|grid:N[:noshadow]]\n"
                  "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE] [--glass I:TF:IOR ...]\n"
-                 "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]]\n", argv0);
+                 "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n", argv0);
     return 1;
 }
 
 int main(int argc, char **argv) {
     int W = 500, H = 504, depth = 50, gpus = 1, ssaa = 1;
-    bool write_txt = true;
-    std::string scene_name = "1", out_path = "raytracer_screen.txt", hits_path;
+    bool write_txt = true, has_exposure = false;
+    std::string scene_name = "1", out_path = "raytracer_screen.txt", hits_path, ppm_path, exposure_arg;
     std::vector<std::string> glass;              /* --glass I:TF:IOR: object I refractive (include/rt_capi_refract.h) */
     std::string denoise;                         /* --denoise IT[:SIGMA[:K]] (include/rt_capi_denoise.h) */
     std::vector<std::string> soft;               /* --soft I:N[:R]: light I an area light, N x N samples, radius R (include/rt_capi_soft.h) */
@@ -72,6 +77,8 @@ int main(int argc, char **argv) {
         else if (a == "--glass" && i + 1 < argc) glass.push_back(argv[++i]);
         else if (a == "--soft" && i + 1 < argc) soft.push_back(argv[++i]);
         else if (a == "--denoise" && i + 1 < argc) denoise = argv[++i];
+        else if (a == "--ppm" && i + 1 < argc) ppm_path = argv[++i];
+        else if (a == "--exposure" && i + 1 < argc) exposure_arg = argv[++i], has_exposure = true;
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
@@ -87,6 +94,13 @@ int main(int argc, char **argv) {
             !(dn.sigma_color >= 0.0f) || std::isinf(dn.sigma_color))
             return usage(argv[0]);
         if (gpus > 1 || ssaa > 1) return usage(argv[0]);       /* (one GPU; a supersampled frame has no records) */
+    }
+    rt_image_params im = {3, 0, RT_TRANSFER_SRGB, 1.0f, nullptr};
+    if (has_exposure) {
+        char *end = nullptr;
+        im.exposure = std::strtof(exposure_arg.c_str(), &end);
+        if (ppm_path.empty() || end == exposure_arg.c_str() || *end || !(im.exposure > 0.0f) || std::isinf(im.exposure))
+            return usage(argv[0]);             /* (what rt_encode_image would refuse) */
     }
     verbose() = true;                          /* console output like the reference's */
 
@@ -223,6 +237,19 @@ int main(int argc, char **argv) {
         }
         if (!ok) {
             std::fprintf(stderr, "cannot write %s\n", hits_path.c_str());
+            return 1;
+        }
+    }
+    if (!ppm_path.empty()) {
+        std::vector<uint8_t> image((size_t)W * (size_t)H * 3);
+        double encode_ms = 0.0;
+        if (rt_encode_image(0, &im, W, H, pixels.data(), image.data(), (uint64_t)W * 3u, &encode_ms) != RT_OK) {
+            std::fprintf(stderr, "encode failed: %s\n", rt_last_error());
+            return 1;
+        }
+        std::printf("Encode kernel (ms)         : %f  (sRGB, exposure %g)\n", encode_ms, (double)im.exposure);
+        if (celio_write_screen_ppm(ppm_path.c_str(), W, H, image.data(), (uint64_t)W * 3u)) {
+            std::fprintf(stderr, "cannot write %s\n", ppm_path.c_str());
             return 1;
         }
     }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "celio_model.hpp"
+#include "screen_ppm.hpp"
 #include "screen_txt.hpp"
 
 using namespace CelioRayTracer;
@@ -220,6 +221,10 @@ int rth_write_screen_txt(const char *path, int W, int H, const float *rgb, doubl
 int rth_write_screen_txt_cores(const char *path, int W, int H, const float *rgb, double run_time_s,
                                double us_per_pixel, int n_cores) {
     return celio_write_screen_txt(path, W, H, rgb, run_time_s, us_per_pixel, n_cores);
+}
+
+int rth_write_screen_ppm(const char *path, int W, int H, const uint8_t *rows, uint64_t pitch_bytes) {
+    return celio_write_screen_ppm(path, W, H, rows, pitch_bytes);
 }
 
 } // extern "C"

@@ -69,6 +69,8 @@ int rth_write_screen_txt(const char *path, int W, int H, const float *rgb,
  * partition's label, src/RayTracer.cpp:2037-2058) */
 int rth_write_screen_txt_cores(const char *path, int W, int H, const float *rgb,
                                double run_time_s, double us_per_pixel, int n_cores);
+/* screen_ppm.hpp: a binary PPM of H rows of 3 W bytes, pitch_bytes apart in memory (0 ok / 1 error) */
+int rth_write_screen_ppm(const char *path, int W, int H, const uint8_t *rows, uint64_t pitch_bytes);
 
 #ifdef __cplusplus
 }

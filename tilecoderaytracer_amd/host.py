@@ -66,6 +66,7 @@ def load_host_library():
     lib.rth_camera_desc.restype = C.POINTER(RtCameraDesc)
     lib.rth_write_screen_txt.argtypes = [C.c_char_p, i, i, vp, C.c_double, C.c_double]
     lib.rth_write_screen_txt_cores.argtypes = [C.c_char_p, i, i, vp, C.c_double, C.c_double, i]
+    lib.rth_write_screen_ppm.argtypes = [C.c_char_p, i, i, vp, C.c_uint64]
     _hlib = lib
     return lib
 
@@ -228,4 +229,16 @@ def write_screen_txt(path, rgb, run_time_s=0.0, us_per_pixel=0.0, n_cores=1):
     rc = load_host_library().rth_write_screen_txt_cores(os.fsencode(path), W, H, a.ctypes.data,
                                                         run_time_s, us_per_pixel, int(n_cores))
     if rc != 0:
+        raise OSError(f"could not write {path}")
+
+
+def write_ppm(path, image):
+    """Write a binary PPM (P6) of a uint8 (H, W, 3) array, row 0 first: encode_image()'s result with 3 channels.  The rows may be
+    a view with a pitch (image.strides[0] >= 3 W), e.g. three columns' worth cut out of a wider image."""
+    a = np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"image must be uint8 (H, W, 3), not {a.dtype} {a.shape}")
+    if a.strides[1:] != (3, 1) or a.strides[0] < 3 * a.shape[1]:
+        a = np.ascontiguousarray(a)
+    if load_host_library().rth_write_screen_ppm(os.fsencode(path), a.shape[1], a.shape[0], a.ctypes.data, a.strides[0]) != 0:
         raise OSError(f"could not write {path}")

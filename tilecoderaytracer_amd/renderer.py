@@ -54,6 +54,41 @@ def denoise(rgb, hits, iterations=2, sigma_color=1.0, normal_squarings=3, device
     return out
 
 
+_TRANSFERS = {"srgb": capi.RT_TRANSFER_SRGB, "linear": capi.RT_TRANSFER_LINEAR, "custom": capi.RT_TRANSFER_CUSTOM}
+
+
+def image_params(channels=3, exposure=1.0, transfer="srgb", bottom_up=False, thresholds=None):
+    """encode_image's keywords -> (an RtImageParams, the float32 array its thresholds point into or None: keep it alive with the
+    struct).  thresholds (255 floats T[1..255]) selects RT_TRANSFER_CUSTOM whatever transfer says."""
+    table = None
+    if thresholds is not None:
+        table = np.ascontiguousarray(thresholds, dtype=np.float32)
+        if table.shape != (255,):
+            raise ValueError(f"thresholds must be 255 floats, not {table.shape}")
+        transfer = "custom"
+    if transfer not in _TRANSFERS:
+        raise ValueError(f"transfer must be one of {sorted(_TRANSFERS)}, not {transfer!r}")
+    params = capi.RtImageParams(int(channels), int(bool(bottom_up)), _TRANSFERS[transfer], float(exposure),
+                                table.ctypes.data_as(C.POINTER(C.c_float)) if table is not None else None)
+    return params, table
+
+
+def encode_image(rgb, channels=3, exposure=1.0, transfer="srgb", bottom_up=False, thresholds=None, device=0):
+    """A frame's colours as 8-bit scanlines (include/rt_capi_image.h, rt_encode_image): rgb float32 (Wn, H, 3) as render() returns
+    it, a whole frame or a strip -> uint8 (H, Wn, channels), row 0 the top of the picture (z = H - 1) unless bottom_up; channel 3,
+    if any, is 255.  transfer "srgb" or "linear", or thresholds: 255 floats T[1..255], code = the number of T[k] <= rgb * exposure.
+    Runs on GPU `device`; there is no CPU path."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"rgb must be (Wn, H, 3), not {rgb.shape}")
+    params, table = image_params(channels, exposure, transfer, bottom_up, thresholds)
+    Wn, H = rgb.shape[:2]
+    out = np.empty((H, Wn, params.channels if params.channels in (3, 4) else 3), dtype=np.uint8)
+    capi.check(capi.load_library().rt_encode_image(int(device), C.byref(params), Wn, H, rgb.ctypes.data, out.ctypes.data,
+                                                   Wn * out.shape[2], None))
+    return out
+
+
 class Renderer:
     """Owns an ``rt_scene`` (device tables for one HostScene on one GPU)."""
 
@@ -190,6 +225,29 @@ class Renderer:
         rgb = host[:W * H * 3].view(np.float32).reshape(W, H, 3)
         hits = host[W * H * 3:].view(HIT_DTYPE).reshape(W, H)
         return rgb, hits, kernel_ms
+
+    def render_image(self, W, H, max_depth, samples=1, channels=3, exposure=1.0, transfer="srgb", bottom_up=False,
+                     thresholds=None):
+        """A W x H frame as 8-bit scanlines, encoded on the GPU where it was rendered (include/rt_capi_image.h): rt_render_device
+        -- rt_render_ssaa_device for samples 2 or 4 -- and rt_encode_image_device enqueued on one stream with no host wait between
+        them, then a download of the bytes alone -> uint8 (H, W, channels).  The result is encode_image(render(W, H, max_depth),
+        ...) bit for bit.  The device buffers and the stream are torch's, so the process must have imported torch before the
+        library was loaded."""
+        import torch
+        device = int(self._device)
+        params, table = image_params(channels, exposure, transfer, bottom_up, thresholds)
+        C_ = params.channels if params.channels in (3, 4) else 3        # (a bad count is refused by the call below)
+        with torch.cuda.device(device):
+            frame = torch.empty((W, H, 3), dtype=torch.float32, device="cuda")
+            image = torch.empty((H, W, C_), dtype=torch.uint8, device="cuda")
+            stream = torch.cuda.current_stream()
+            if samples == 1:
+                self.render_device(W, H, max_depth, 0, W, frame.data_ptr(), stream.cuda_stream)
+            else:
+                self.render_ssaa_device(W, H, max_depth, samples, 0, W, frame.data_ptr(), stream.cuda_stream)
+            capi.check(self._lib.rt_encode_image_device(device, C.byref(params), W, H, frame.data_ptr(), image.data_ptr(),
+                                                        W * C_, stream.cuda_stream))
+            return image.cpu().numpy()                            # the one download
 
     def trace_rays(self, rays, max_depth, rows=None):
         """Trace a batch of primary rays (include/rt_capi_rays.h).  rays: C-contiguous float32, (n, 6) -- rows defaults to n --
