@@ -23,7 +23,9 @@ typedef struct rt_launch_info {
     int32_t lds_bytes;          /* dynamic LDS per workgroup (scene tables + bounce stack)      */
     int32_t scene_lds_bytes;    /* of which scene tables                                        */
     int32_t grid_blocks;        /* workgroups of the last launch                                */
-    int32_t tile_x, tile_z;     /* pixels per wavefront tile (tile_x * tile_z == 64)            */
+    int32_t tile_x, tile_z;     /* pixels per wavefront tile (tile_x * tile_z == 64); always ONE tile's: rt_render_kernel
+                                 * renders tiles in vertical pairs, a wavefront taking tile rows 2j and 2j + 1 of a column of
+                                 * tiles at once (two pixels per lane), every other kernel one tile per wavefront */
     char    kernel[48];         /* name of the __global__ function the last launch ran (its first pass), cut to 47 characters;
                                  * rt_get_launch_kernel() (rt_capi_launch.h) gives the whole name */
 } rt_launch_info;
@@ -89,7 +91,11 @@ int rt_get_launch_info(const rt_scene *scene, rt_launch_info *out);
  *                   is refused by that launch)
  *   "wide"          scenes with clustered sphere runs: which kernel (-1 automatic: the 96-register one when
  *                   LDS admits fewer than six wavefronts per SIMD anyway; 0 the 80-register one; 1 the other)
- *   "stack"         bounce stack: 0 auto, 1 LDS, 2 HBM
+ *   "stack"         bounce stack: 0 auto, 1 LDS, 2 HBM.  The option sizes the stack's LDS rows, one per level
+ *                   (1: max_depth rows, refused where they do not fit).  rt_render_kernel, which renders two
+ *                   tiles per wavefront, has two rows per level and the same LDS rows: with 1 the lower half
+ *                   of its levels are in LDS and the upper half in HBM (all in LDS only at depth 0); 2 is all
+ *                   in HBM for every kernel
  *   "pairs"         scenes with clustered sphere runs: 0 = every needed leaf is tested for
  *                   the whole wavefront (round 1's route); 1 (default) = the (ray, leaf)
  *                   pairs that the per-lane box tests leave are compacted into full

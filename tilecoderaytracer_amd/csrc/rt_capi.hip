@@ -1553,6 +1553,7 @@ struct LaunchPlan {
     TileShape tiles{};
     long long n_tiles = 0;
     bool help = false;            /* the launch carries HELP areas (p.help_rays_quads != 0) */
+    bool twin = false;            /* the kernel renders tiles in vertical pairs (rt_tables.h, TWIN TILES): a queue entry is a twin */
 };
 
 /* Host-only: the checks and every decision of a launch, in this order.  An empty strip is planned up to its tile count. */
@@ -1601,6 +1602,7 @@ int plan_launch(const rt_scene *s, const LaunchRequest &rq, LaunchPlan *plan) {
     if (!counting && !batch) learned_start_row(s, rq.W, rq.H, rq.x0, rq.x1, rq.max_depth, t, p);
     plan->kernel = choose_kernel(s, rq, bc.global_tables, bc.block, plan->lds_bytes);
     plan->help = p.help_rays_quads != 0;
+    plan->twin = RT_TWIN_TILES != 0 && plan->kernel.fn == (const void *)rt_render_kernel;
     return RT_OK;
 }
 
@@ -1680,15 +1682,19 @@ int launch(rt_scene *s, LaunchRequest rq, hipStream_t stream) {
     int per_cu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, (size_t)plan.lds_bytes));
     if (per_cu < 1) per_cu = 1;
-    const long long blocks_all = (plan.n_tiles + block / 64 - 1) / (block / 64);
+    /* (queue entries: the tiles, or the twins -- pairs of tile rows, the last one single when their number is odd) */
+    const long long n_entries = plan.twin ? ((plan.tiles.tiles_z + 1) / 2) * plan.tiles.tiles_x : plan.n_tiles;
+    const long long blocks_all = (n_entries + block / 64 - 1) / (block / 64);
     const long long blocks = s->grid_mult > 0
         ? std::min(blocks_all, (long long)per_cu * (long long)s->n_cus * (long long)s->grid_mult)
         : blocks_all;
     s->launch.grid_blocks = (int)blocks;
     HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, plan.lds_bytes));
-    /* bounce stack: one slice per workgroup of the persistent grid */
-    const double stack_bytes = plan.stack_lds_levels >= rq.max_depth ? 16.0
-                             : (double)blocks * (double)block * (double)(rq.max_depth + 1) * RT_STACK_ENTRY_BYTES * stack_entry_quads(s);
+    /* bounce stack: one slice per workgroup of the persistent grid.  A twin kernel's stack has two rows per level -- row
+     * 2 level + ray, the planned LDS rows first -- so half as many levels fit LDS and the slice is twice as long */
+    const int stack_rays = plan.twin ? 2 : 1;
+    const double stack_bytes = (long long)plan.stack_lds_levels >= (long long)stack_rays * rq.max_depth ? 16.0
+                             : (double)blocks * (double)block * (double)(rq.max_depth + 1) * RT_STACK_ENTRY_BYTES * stack_entry_quads(s) * stack_rays;
     if (stack_bytes > 8.0e9)
         return fail(RT_ERR_CAPACITY, "max_depth too large: the bounce stack would exceed 8 GB of HBM");
     /* the stack (and nothing else) is shared by successive launches of this handle:

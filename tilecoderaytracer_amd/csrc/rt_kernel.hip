@@ -1690,6 +1690,267 @@ __device__ __forceinline__ bool in_shade_fast(const RtParams &p, const float4 *l
     return nearest_block < dist_to_light;
 }
 
+/* ---- TWIN TILES (rt_tables.h, RT_TWIN_TILES): the FAST scans for two rays per lane ------------------------------------------
+ * rt_render_kernel gives every lane two pixels, one of each of two vertically adjacent wavefront tiles (render_tile_twin()).
+ * What a scan does for the wavefront as a whole -- the bundle's bounds, the cull, the candidates' order, the dispatch on a
+ * candidate's kind, the loads of its control word and record -- then runs once for 128 rays; only the exact tests run per
+ * ray, the two side by side.  The bundle is the one around both tiles' rays: a superset of either tile's own, so the culls only
+ * widen, which is exact by nearest_hit_items()'s argument (a candidate more is tested and found no nearer, or not blocking),
+ * and every ray sees the arithmetic of nearest_hit_fast() / in_shade_fast() on its own operands. */
+
+/* wave_bounds3() of a per-lane range [vlo, vhi] (a lane without a value: [+inf, -inf]) */
+__device__ __forceinline__ void wave_bounds3_range(const V3 vlo, const V3 vhi, V3 *lo, V3 *hi) {
+    float a = vlo.x, b = vlo.y, c = vlo.z, d = vhi.x, e = vhi.y, f = vhi.z;
+#define RT_DPP_STEP(ctrl)                                                                              \
+    "v_min_f32_dpp %0, %0, %0 " ctrl "\n v_min_f32_dpp %1, %1, %1 " ctrl "\n v_min_f32_dpp %2, %2, %2 " ctrl "\n" \
+    "v_max_f32_dpp %3, %3, %3 " ctrl "\n v_max_f32_dpp %4, %4, %4 " ctrl "\n v_max_f32_dpp %5, %5, %5 " ctrl "\n"
+    asm volatile("s_nop 1\n"
+                 RT_DPP_STEP("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
+                 RT_DPP_STEP("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
+                 RT_DPP_STEP("row_half_mirror row_mask:0xf bank_mask:0xf")
+                 RT_DPP_STEP("row_mirror row_mask:0xf bank_mask:0xf")
+                 RT_DPP_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf")
+                 RT_DPP_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf")
+                 "s_nop 1\n"
+                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
+#undef RT_DPP_STEP
+    *lo = mk(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 63)),
+             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b), 63)),
+             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), 63)));
+    *hi = mk(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(d), 63)),
+             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), 63)),
+             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f), 63)));
+}
+
+/* the box of two per-lane points over the lanes' rays in use: each lane's own minimum and maximum first (v_min / v_max skip a
+ * NaN, as the reduction does), then ONE reduction */
+__device__ __forceinline__ void wave_bounds3_twin(const V3 v0, const bool use0, const V3 v1, const bool use1, V3 *lo, V3 *hi) {
+    const float inf = __builtin_huge_valf();
+    const V3 vlo = mk(fminf(use0 ? v0.x : inf, use1 ? v1.x : inf), fminf(use0 ? v0.y : inf, use1 ? v1.y : inf),
+                      fminf(use0 ? v0.z : inf, use1 ? v1.z : inf));
+    const V3 vhi = mk(fmaxf(use0 ? v0.x : -inf, use1 ? v1.x : -inf), fmaxf(use0 ? v0.y : -inf, use1 ? v1.y : -inf),
+                      fmaxf(use0 ? v0.z : -inf, use1 ? v1.z : -inf));
+    wave_bounds3_range(vlo, vhi, lo, hi);
+}
+
+/* The exact tests of one candidate for both rays: sphere_hit_distance(), infinite_plane_hit_distance() and
+ * aa_rectangle_hit_distance() written for two rays, with ONE wavefront-wide question "is this worth computing" for the pair.
+ * A lane that is no candidate gets +infinity from the routine either way (its own margin is negative), and the plain and the
+ * short forms agree wherever the short one is allowed: the answer of each ray is the single routine's. */
+__device__ __forceinline__ void sphere_hit_distance_twin(const float4 s, const V3 o0, const V3 d0, const V3 o1, const V3 d1,
+                                                         float *t0, float *t1) {
+    const V3 OE0 = mk(s.x - o0.x, s.y - o0.y, s.z - o0.z), OE1 = mk(s.x - o1.x, s.y - o1.y, s.z - o1.z);
+    const float v0 = dot3(OE0, d0), v1 = dot3(OE1, d1);
+    const float q0 = s.w - (dot3(OE0, OE0) - v0 * v0), q1 = s.w - (dot3(OE1, OE1) - v1 * v1);
+    const float m0 = sphere_margin(v0, q0), m1 = sphere_margin(v1, q1);
+    *t0 = __builtin_huge_valf(); *t1 = __builtin_huge_valf();
+    if (wave_any(m0 >= 0.0f || m1 >= 0.0f)) {
+        if (wave_any(!sphere_operands_plain(fabsf(q0) + fabsf(q1)))) {
+            *t0 = sphere_hit_or_inf_exact(v0, q0); *t1 = sphere_hit_or_inf_exact(v1, q1);
+        } else {
+            const float r0 = sqrt_in_range(q0), r1 = sqrt_in_range(q1);
+            *t0 = sphere_hit_or_inf(v0, r0, m0); *t1 = sphere_hit_or_inf(v1, r1, m1);
+        }
+    }
+}
+
+__device__ __forceinline__ void infinite_plane_hit_distance_twin(const float4 q0, const V3 o0, const V3 d0, const float bound0,
+                                                                 const V3 o1, const V3 d1, const float bound1, float *t0, float *t1) {
+    const V3 n = xyz(q0);
+    const float num0 = -q0.w - dot3(o0, n), num1 = -q0.w - dot3(o1, n);
+    const float den0 = dot3(d0, n), den1 = dot3(d1, n);
+    const float c0 = plane_candidate_margin(num0, den0, bound0), c1 = plane_candidate_margin(num1, den1, bound1);
+    *t0 = __builtin_huge_valf(); *t1 = __builtin_huge_valf();
+    if (wave_any(c0 >= 0.0f || c1 >= 0.0f)) {
+        const float ta = num0 / den0, tb = num1 / den1;
+        *t0 = (__builtin_fminf(c0, ta - (float)1E-10) >= 0.0f) ? ta : *t0;
+        *t1 = (__builtin_fminf(c1, tb - (float)1E-10) >= 0.0f) ? tb : *t1;
+    }
+}
+
+__device__ __forceinline__ void aa_rectangle_hit_distance_twin(const float4 r0, const float4 r1, const V3 op0, const V3 dp0, const float bound0,
+                                                               const V3 op1, const V3 dp1, const float bound1, float *t0, float *t1) {
+    const float num0 = -r0.x - op0.x * r0.y, num1 = -r0.x - op1.x * r0.y;
+    const float den0 = dp0.x * r0.y, den1 = dp1.x * r0.y;
+    const float c0 = plane_candidate_margin(num0, den0, bound0), c1 = plane_candidate_margin(num1, den1, bound1);
+    *t0 = __builtin_huge_valf(); *t1 = __builtin_huge_valf();
+    if (wave_any(c0 >= 0.0f || c1 >= 0.0f)) {
+        const float ta = num0 / den0, tb = num1 / den1;
+        const float pa0 = dp0.y * ta + op0.y, pa1 = dp1.y * tb + op1.y;
+        const float pb0 = dp0.z * ta + op0.z, pb1 = dp1.z * tb + op1.z;
+        const float x0 = (pa0 - r1.x) * r0.z, x1 = (pa1 - r1.x) * r0.z;
+        const float y0 = (pb0 - r1.y) * r0.w, y1 = (pb1 - r1.y) * r0.w;
+        const float in0 = __builtin_fminf(__builtin_fminf(__builtin_fminf(x0, r1.z - x0), __builtin_fminf(y0, r1.w - y0)), ta - 0x1.4f8b5ap-17f);
+        const float in1 = __builtin_fminf(__builtin_fminf(__builtin_fminf(x1, r1.z - x1), __builtin_fminf(y1, r1.w - y1)), tb - 0x1.4f8b5ap-17f);
+        *t0 = (__builtin_fminf(c0, in0) >= 0.0f) ? ta : *t0;
+        *t1 = (__builtin_fminf(c1, in1) >= 0.0f) ? tb : *t1;
+    }
+}
+
+/* fast_item_distance() for both rays: one dispatch on the (scalar) kind */
+__device__ __forceinline__ void fast_item_distance_twin(const RtParams &p, const float4 *lds, const uint32_t ctl,
+                                                        const float4 r0, const float4 r1, const V3 o0, const V3 d0, const float bound0,
+                                                        const V3 o1, const V3 d1, const float bound1, const bool finite_rays,
+                                                        float *t0, float *t1) {
+    const int kind = (int)(ctl & 15u);
+    if (kind >= RT_KIND_FINITE_AA && finite_rays) {
+        if (kind == RT_KIND_FINITE_AA)
+            aa_rectangle_hit_distance_twin(r0, r1, mk(o0.x, o0.y, o0.z), mk(d0.x, d0.y, d0.z), bound0, mk(o1.x, o1.y, o1.z), mk(d1.x, d1.y, d1.z), bound1, t0, t1);
+        else if (kind == RT_KIND_FINITE_AA + 1)
+            aa_rectangle_hit_distance_twin(r0, r1, mk(o0.y, o0.z, o0.x), mk(d0.y, d0.z, d0.x), bound0, mk(o1.y, o1.z, o1.x), mk(d1.y, d1.z, d1.x), bound1, t0, t1);
+        else
+            aa_rectangle_hit_distance_twin(r0, r1, mk(o0.z, o0.x, o0.y), mk(d0.z, d0.x, d0.y), bound0, mk(o1.z, o1.x, o1.y), mk(d1.z, d1.x, d1.y), bound1, t0, t1);
+    } else if (kind == RT_KIND_SPHERE) {
+        sphere_hit_distance_twin(r0, o0, d0, o1, d1, t0, t1);
+    } else if (kind == RT_KIND_INFINITE_PLANE) {
+        infinite_plane_hit_distance_twin(r0, o0, d0, bound0, o1, d1, bound1, t0, t1);
+    } else {
+        /* the general routine on the full record, as fast_item_distance() */
+        const uint32_t *lds_u32 = reinterpret_cast<const uint32_t *>(lds);
+        const uint32_t full = kind == RT_KIND_FINITE_PLANE ? __float_as_uint(r1.x) : (lds_u32[p.objinfo_off * 4 + (ctl >> 8)] & 0xFFFFu);
+        *t0 = finite_plane_hit_distance(lds + full, o0, d0, bound0);
+        *t1 = finite_plane_hit_distance(lds + full, o1, d1, bound1);
+    }
+}
+
+/* nearest_hit_fast() for the two rays of a twin: ray k of a lane is (ok, dk), in use where activek.  camera_rays: (tile_x0,
+ * tile_z0) is the corner of the twin's first tile; the PRIMARY rectangles are compared with the rectangle of both tiles. */
+__device__ __forceinline__ void nearest_hit_fast_twin(const RtParams &p, const float4 *lds, const uint32_t *__restrict__ ctl_words,
+                                                      const bool active0, const V3 o0, const V3 d0,
+                                                      const bool active1, const V3 o1, const V3 d1,
+                                                      const V3 origins_lo, const V3 origins_hi, const bool camera_rays,
+                                                      const int tile_x0, const int tile_z0,
+                                                      float *best0_out, int *idx0_out, float *best1_out, int *idx1_out) {
+    float best0 = 65535.0f, best1 = 65535.0f;
+    int best_idx0 = -1, best_idx1 = -1;
+    const int lane = (int)(threadIdx.x & 63u);
+    const int n_items = p.n_fast_items;
+    const float4 *boxes = lds + p.fast_box_off;
+    const float4 *recs = lds + p.fast_rec_off;
+
+    const bool by_pixels = camera_rays && p.n_primary > 0;
+    V3 dlo = d0, dhi = d0;
+    const V3 olo = origins_lo, ohi = origins_hi;
+    float lax = 0, hax = 0, lbx = 0, hbx = 0, lay = 0, hay = 0, lby = 0, hby = 0, laz = 0, haz = 0, lbz = 0, hbz = 0;
+    if (!by_pixels) {
+        wave_bounds3_twin(d0, active0, d1, active1, &dlo, &dhi);
+        bound_multipliers(dlo.x, dhi.x, &lax, &hax, &lbx, &hbx);
+        bound_multipliers(dlo.y, dhi.y, &lay, &hay, &lby, &hby);
+        bound_multipliers(dlo.z, dhi.z, &laz, &haz, &lbz, &hbz);
+    }
+    const bool finite_rays = !wave_any((active0 && !ray_is_finite(o0, d0)) || (active1 && !ray_is_finite(o1, d1)));
+
+    for (int base = 0; base < n_items; base += 64) {
+        uint32_t key;                      /* this lane's item: tolerant bundle entry distance (high bits) | lane */
+        if (by_pixels) {                   /* n_items <= 64: one round */
+            const uint4 rect = reinterpret_cast<const uint4 *>(lds)[p.primary_off + min(lane, n_items - 1)];
+            const int x_lo = (int)(short)(rect.x & 0xFFFFu), x_hi = (int)rect.x >> 16;
+            const int z_lo = (int)(short)(rect.y & 0xFFFFu), z_hi = (int)rect.y >> 16;
+            const int tile_x1 = tile_x0 + (64 >> p.tile_z_log2) - 1, tile_z1 = tile_z0 + (2 << p.tile_z_log2) - 1;
+            const bool candidate = lane < n_items && x_lo <= tile_x1 && x_hi >= tile_x0 && z_lo <= tile_z1 && z_hi >= tile_z0;
+            key = candidate ? ((rect.z & ~63u) | (uint32_t)lane) : 0xFFFFFFFFu;
+        } else {
+            const int mine = min(base + lane, n_items - 1);
+            const float4 b0 = boxes[2 * mine], b1 = boxes[2 * mine + 1];
+            float ax = (b0.x - b1.x) - ohi.x, bx = (b0.x + b1.x) - olo.x;
+            float ay = (b0.y - b1.y) - ohi.y, by = (b0.y + b1.y) - olo.y;
+            float az = (b0.z - b1.z) - ohi.z, bz = (b0.z + b1.z) - olo.z;
+            float ex, ey, ez;
+            RT_CULL_SLACK(__float_as_uint(b0.w), fmaxf(fabsf(ax), fabsf(bx)), fmaxf(fabsf(ay), fabsf(by)), fmaxf(fabsf(az), fabsf(bz)), ex, ey, ez);
+            ax -= ex; ay -= ey; az -= ez; bx += ex; by += ey; bz += ez;
+            const float t_lo = fmaxf(fmaxf(fmaxf(0.0f, fmaxf(bx * lax, ax * lbx)), fmaxf(by * lay, ay * lby)), fmaxf(bz * laz, az * lbz));
+            const float t_hi = fminf(fminf(fminf(65600.0f, fminf(bx * hax, ax * hbx)), fminf(by * hay, ay * hby)), fminf(bz * haz, az * hbz));
+            const float entry = fmaxf(t_lo - 1.0e-4f * t_lo - 1.0e-6f, 0.0f);
+            const bool empty = (entry > t_hi + 1.0e-4f * fabsf(t_hi)) || (t_hi < -1.0e-6f);
+            const bool candidate = base + lane < n_items && !empty;
+            key = candidate ? ((__float_as_uint(entry) & ~63u) | (uint32_t)lane) : 0xFFFFFFFFu;
+        }
+        for (;;) {
+            const uint32_t nearest_key = wave_min_u32(key);
+            if (nearest_key == 0xFFFFFFFFu) break;                       /* no candidate left */
+            const uint32_t entry_bits = nearest_key & ~63u;
+            /* every active ray of either tile already has a hit nearer than anything in that box (and in all the remaining ones) */
+            if (entry_bits != 0u && !wave_any((active0 && !(__uint_as_float(entry_bits) > best0)) ||
+                                              (active1 && !(__uint_as_float(entry_bits) > best1)))) break;
+            const int src = (int)(nearest_key & 63u);
+            if (lane == src) key = 0xFFFFFFFFu;
+            const int item = base + src;
+            const uint32_t ctl = ctl_words[item];
+            const float4 r0 = recs[2 * item], r1 = recs[2 * item + 1];
+            float t0, t1;
+            fast_item_distance_twin(p, lds, ctl, r0, r1, o0, d0, best0, o1, d1, best1, finite_rays, &t0, &t1);
+            take_nearer(t0, (int)(ctl >> 8), &best0, &best_idx0);
+            take_nearer(t1, (int)(ctl >> 8), &best1, &best_idx1);
+        }
+    }
+    *best0_out = best0; *best1_out = best1;
+    *idx0_out = active0 ? best_idx0 : -1;
+    *idx1_out = active1 ? best_idx1 : -1;
+}
+
+/* in_shade_fast() for the two rays of a twin (the cull around both tiles' shading points, from shading_point_bundle()) */
+__device__ __forceinline__ void in_shade_fast_twin(const RtParams &p, const float4 *lds, const uint32_t *__restrict__ ctl_words,
+                                                   const bool active0, const V3 o0, const V3 d0, const float dist0,
+                                                   const bool active1, const V3 o1, const V3 d1, const float dist1,
+                                                   const V3 light, const V3 origins_centre, const V3 origins_half,
+                                                   const bool culled_already, const unsigned long long culled,
+                                                   bool *blocked0, bool *blocked1) {
+    const int n_items = p.n_fast_shadow;
+    *blocked0 = false; *blocked1 = false;
+    if (n_items == 0) return;
+    const float4 *boxes = lds + p.fast_box_off;
+    const float4 *recs = lds + p.fast_rec_off;
+    const float inf = __builtin_huge_valf();
+    float nearest0 = active0 ? inf : -inf, nearest1 = active1 ? inf : -inf;
+    const int lane = (int)(threadIdx.x & 63u);
+    const bool finite_rays = !wave_any((active0 && !ray_is_finite(o0, d0)) || (active1 && !ray_is_finite(o1, d1)));
+    /* the candidates of one round of 64 items, in table order; true: every ray of both tiles is blocked */
+    auto test_candidates = [&](unsigned long long mask, const int base) {
+        while (mask != 0ull) {
+            if (!wave_any(!(nearest0 < dist0) || !(nearest1 < dist1))) return true;
+            const int item = base + (__ffsll((long long)mask) - 1);
+            mask &= mask - 1ull;
+            const uint32_t ctl = ctl_words[item];
+            const float4 r0 = recs[2 * item], r1 = recs[2 * item + 1];
+            float t0, t1;
+            fast_item_distance_twin(p, lds, ctl, r0, r1, o0, d0, dist0, o1, d1, dist1, finite_rays, &t0, &t1);
+            nearest0 = __builtin_fminf(nearest0, t0);
+            nearest1 = __builtin_fminf(nearest1, t1);
+        }
+        return false;
+    };
+    bool all_blocked = false;
+    if (culled_already) {                    /* BOTH LIGHTS' SHADOW CULLS IN ONE PASS: at most 32 items */
+        all_blocked = test_candidates(culled, 0);
+    } else {
+        const V3 c = origins_centre;
+        const V3 seg = sub3(light, c);
+        V3 sinv = approx_inverse(seg);
+        const float reach = (fabsf(seg.x) + fabsf(seg.y) + fabsf(seg.z)) + (origins_half.x + origins_half.y + origins_half.z);
+        const float grow_more = uniform_f((RT_SPHERE_SLACK - RT_PLANE_SLACK) * reach);
+        const float grow = RT_PLANE_SLACK * reach + 1.0e-4f;
+        const V3 e = mk(uniform_f(origins_half.x + grow), uniform_f(origins_half.y + grow), uniform_f(origins_half.z + grow));
+        sinv = mk(uniform_f(sinv.x), uniform_f(sinv.y), uniform_f(sinv.z));
+        for (int base = 0; base < n_items && !all_blocked; base += 64) {
+            const int mine = min(base + lane, n_items - 1);
+            const float4 b0 = boxes[2 * mine], b1 = boxes[2 * mine + 1];
+            const float more = (__float_as_uint(b0.w) & RT_ITEM_TIGHT) != 0u ? 0.0f : grow_more;
+            const float gx = e.x + more, gy = e.y + more, gz = e.z + more;
+            const float tcx = (b0.x - c.x) * sinv.x, tcy = (b0.y - c.y) * sinv.y, tcz = (b0.z - c.z) * sinv.z;
+            const float tgx = (b1.x + gx) * fabsf(sinv.x), tgy = (b1.y + gy) * fabsf(sinv.y), tgz = (b1.z + gz) * fabsf(sinv.z);
+            const float s_enter = fmaxf(fmaxf(tcx - tgx, tcy - tgy), tcz - tgz);
+            const float s_exit = fminf(fminf(tcx + tgx, tcy + tgy), tcz + tgz);
+            /* every comparison is false on a NaN, which then means "candidate" */
+            const bool apart = (s_exit < s_enter - 1.0e-4f * (fabsf(s_enter) + fabsf(s_exit)) - 1.0e-6f) ||
+                               (s_exit < -1.0e-4f) || (s_enter > 1.0001f);
+            all_blocked = test_candidates(__builtin_amdgcn_ballot_w64(base + lane < n_items && !apart), base);
+        }
+    }
+    /* (every ray blocked: both are below; a blocked ray's minimum stays below its distance whatever is tested after it) */
+    *blocked0 = nearest0 < dist0;
+    *blocked1 = nearest1 < dist1;
+}
+
 /* Texture_CheckerBoard::getTexturePixel, src/Texture_CheckerBoard.h:31-65.
  * Returns 1 for the light colour, 2 for the dark colour. */
 /* fmodf(x, y) for 0 <= x < 2^20 y, y a normal number well inside the exponent
@@ -2530,6 +2791,269 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
     }
 }
 
+/* ---- TWIN TILES: two vertically adjacent wavefront tiles rendered by one wavefront (rt_render_kernel only) ------------------
+ * A tile's time is mostly work the wavefront does as a whole, which does not shrink with the number of rays (DESIGN.md
+ * section 4): the bundle bounds, the culls, the candidate order, the scalar dispatch.  Here every lane carries two pixels --
+ * ray k of a lane belongs to tile k of the twin, tile rows 2j and 2j + 1 of one macro tile, the same lane position in each --
+ * and all of that runs once for 128 rays (the scans above).  Each ray has its own state and sees render_tile()'s arithmetic in
+ * render_tile()'s order; the level loop runs while a ray of either tile is alive.  A second tile that does not exist (an odd
+ * number of tile rows) or pixels outside the strip are rays with inside == false, as the lanes of a partial tile always were.
+ *
+ * Bounce stack: entry (level, ray) is row 2 level + ray -- in LDS while the row is below the launch's planned LDS rows
+ * (p.stack_lds_levels, unchanged: half as many levels stay there), else in this workgroup's HBM slice of 2 (max_depth + 1)
+ * rows (rt_capi.hip allocates it so). */
+struct TwinRay {
+    V3 o, d, P, N, C;
+    float t;
+    int idx, texsel, top;
+    bool inside, alive, shade;
+};
+
+__device__ __forceinline__ float4 *twin_stack_entry(const RtParams &p, float4 *wlds, float4 *bounce_stack, const int level, const int ray) {
+    const int row = 2 * level + ray;
+    if (row < p.stack_lds_levels) return wlds + here(p.stack_off) + row * here(p.stack_stride) + threadIdx.x;
+    const unsigned int r = (unsigned int)here((int)blockIdx.x) * (unsigned int)(2 * (p.max_depth + 1)) + (unsigned int)row;
+    return bounce_stack + (size_t)(r * (unsigned int)here(p.stack_stride) + threadIdx.x);
+}
+
+/* `wave_in`: the number of the twin's first tile (an even tile row of its macro tile) */
+__device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4 *lds, float4 *wlds,
+                                                 const uint32_t *__restrict__ ctl_words, float *__restrict__ out,
+                                                 float4 *__restrict__ bounce_stack, const int wave_in, int &next_pop) {
+    const int wave = __builtin_amdgcn_readfirstlane(wave_in);
+    const uint32_t *lds_u32 = reinterpret_cast<const uint32_t *>(lds);
+    const int lane = (int)(threadIdx.x & 63u);
+    const int tile_row = wave / p.tiles_x;                  /* of the first tile; the second is the row above it */
+    const int tile_col = wave - tile_row * p.tiles_x;
+    const V3 null_color = mk(p.null_color[0], p.null_color[1], p.null_color[2]);
+
+    TwinRay r[2];
+    {
+        const int tzl_a = here(p.tile_z_log2);
+        const int x = p.x0 + tile_col * (64 >> tzl_a) + (lane >> tzl_a);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int z = ((tile_row + k) << tzl_a) + (lane & ((1 << tzl_a) - 1));
+            r[k].inside = (x < p.x1) && (z < p.H);             /* (a tile row that does not exist starts at z >= H) */
+            /* Camera::createEyeRay, as render_tile() */
+            r[k].o = mk(p.eye[0], p.eye[1], p.eye[2]);
+            const float dx_percent = ((float)x) / (float)here(p.W);
+            const float dy_percent = ((float)z) / (float)here(p.H);
+            const float scalar_x = dx_percent * p.sw - p.shw;
+            const float scalar_y = dy_percent * p.sh - p.shh;
+            V3 pixel = add3(mk(p.so[0], p.so[1], p.so[2]), scale3(mk(p.ch[0], p.ch[1], p.ch[2]), scalar_x));
+            pixel = add3(pixel, scale3(mk(p.cv[0], p.cv[1], p.cv[2]), scalar_y));
+            r[k].d = normalize3(sub3(pixel, r[k].o));
+            r[k].C = null_color;
+            r[k].top = 0;
+            r[k].alive = r[k].inside;
+        }
+    }
+    int levels = 0;           /* wave-uniform: levels any ray entered */
+    V3 box_lo = r[0].o, box_hi = r[0].o;        /* the eye at level 0, afterwards the shading points of the level before */
+
+    for (int level = 0; level <= p.max_depth; ++level) {
+        if (!wave_any(r[0].alive || r[1].alive)) break;
+        levels = level + 1;
+        if (level >= 1 && level <= 3 && p.tile_prio != 0) {       /* OLD TILES FIRST: the deeper of the two decides */
+            if (level == 1) __builtin_amdgcn_s_setprio(1);
+            else if (level == 2) __builtin_amdgcn_s_setprio(2);
+            else __builtin_amdgcn_s_setprio(3);
+        }
+        /* ---- phase 1: nearest hit (one scan for both rays), then each ray's winner ---- */
+#pragma unroll
+        for (int k = 0; k < 2; ++k) { r[k].shade = false; r[k].P = r[k].o; r[k].N = r[k].d; r[k].idx = 0; r[k].texsel = 0; r[k].t = 0.0f; }
+        {
+            const int tzl_n = here(p.tile_z_log2);
+            nearest_hit_fast_twin(p, lds, ctl_words, r[0].alive, r[0].o, r[0].d, r[1].alive, r[1].o, r[1].d, box_lo, box_hi, level == 0,
+                                  p.x0 + here(tile_col) * (64 >> tzl_n), here(tile_row) << tzl_n, &r[0].t, &r[0].idx, &r[1].t, &r[1].idx);
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            TwinRay &q = r[k];
+            if (q.alive) {
+                if (q.idx < 0) {                                   /* :507-509 */
+                    q.C = null_color;
+                    q.alive = false;
+                    q.idx = 0;
+                } else {
+                    const uint32_t info = lds_u32[p.objinfo_off * 4 + q.idx];
+                    const float4 *g = lds + (info & 0xFFFFu);
+                    const int kind = (int)((info >> 16) & 3u);
+                    const int mat = (int)(info >> 20);
+                    const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
+                    const uint32_t mbits = __float_as_uint(m1.w);
+                    if (kind == RT_KIND_SPHERE) {                /* src/SceneSphere.cpp:118-149 */
+                        const float4 s = g[0];
+                        q.P = add3(scale3(q.d, q.t), q.o);
+                        q.N = normalize3(sub3(q.P, xyz(s)));
+                    } else {                                     /* src/SceneInfinitePlane.cpp:53-95, src/SceneFinitePlane.cpp:106-150 */
+                        const float4 q0 = g[0], q1 = g[1], q2 = g[2], q3 = g[3], q4 = g[4];
+                        const V3 ip = add3(scale3(q.d, q.t), q.o);
+                        if ((mbits >> 1) != 0u) {
+                            const V3 PO = sub3(ip, xyz(q1));
+                            const float tx = dot3(PO, xyz(q2));
+                            const float ty = dot3(PO, xyz(q3));
+                            const int tex = (int)(mbits >> 1) - 1;
+                            const float4 t0 = lds[p.tex_off + tex * RT_TEX_QUADS];
+                            const float4 t1 = lds[p.tex_off + tex * RT_TEX_QUADS + 1];
+                            q.texsel = checkerboard_select(t0.w, t1.w, tx, ty);
+                        }
+                        q.N = (dot3(xyz(q0), q.d) < 0) ? xyz(q0) : xyz(q4);
+                        q.P = add3(ip, scale3(q.N, (float)1E-3));
+                    }
+                    if (mbits & 1u) {                            /* hit a light: :520-527 */
+                        const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
+                        q.C = scale3(entry_colour<false>(p, lds, m0, mbits, q.texsel), m1.z);
+                        q.alive = false;
+                    } else {
+                        q.shade = true;
+                    }
+                }
+            }
+            if (q.shade) q.C = mk(0.0f, 0.0f, 0.0f);
+        }
+
+        /* ---- phase 2 (whole wavefront, converged): lights in Scene index order, :540-591; what does not depend on the ray
+         * -- the shading points' bundle, both lights' cull, a light's rows -- once for both tiles ---- */
+        if (wave_any(r[0].shade || r[1].shade)) {
+            V3 bundle_centre, bundle_half;
+            wave_bounds3_twin(r[0].P, r[0].shade, r[1].P, r[1].shade, &box_lo, &box_hi);
+            shading_point_bundle(box_lo, box_hi, &bundle_centre, &bundle_half);
+            /* (render_tile(): whether the re-normalisations are the identity; renormalize3() returns a unit normal unchanged
+             * either way, so asking both tiles at once changes no lane's result) */
+            const bool normals_are_unit = !wave_any((r[0].shade && (r[0].N.x * r[0].N.x + r[0].N.y * r[0].N.y + r[0].N.z * r[0].N.z) != 1.0f) ||
+                                                    (r[1].shade && (r[1].N.x * r[1].N.x + r[1].N.y * r[1].N.y + r[1].N.z * r[1].N.z) != 1.0f));
+            const bool both_culls = p.n_lights == 2 && p.n_fast_shadow > 0 && p.n_fast_shadow <= 32;
+            unsigned long long culled_both = 0ull;
+            if (both_culls)
+                culled_both = shadow_cull_two_lights(lds + p.fast_box_off, p.n_fast_shadow, bundle_centre, bundle_half,
+                                                     xyz(lds[p.lights_off]), xyz(lds[p.lights_off + RT_LIGHT_QUADS]));
+            for (int l = 0; l < p.n_lights; ++l) {
+                const float4 l0 = lds[p.lights_off + l * RT_LIGHT_QUADS];
+                const float4 l1 = lds[p.lights_off + l * RT_LIGHT_QUADS + 1];
+                const unsigned long long culled = l == 0 ? (culled_both & 0xFFFFFFFFull) : (culled_both >> 32);
+                /* inShade, :743-771 */
+                float dist0, dist1;
+                const V3 light_ray0 = normalize3(sub3(xyz(l0), r[0].P), &dist0);
+                const V3 light_ray1 = normalize3(sub3(xyz(l0), r[1].P), &dist1);
+                bool blocked[2];
+                in_shade_fast_twin(p, lds, ctl_words, r[0].shade, r[0].P, light_ray0, dist0, r[1].shade, r[1].P, light_ray1, dist1,
+                                   xyz(l0), bundle_centre, bundle_half, both_culls, culled, &blocked[0], &blocked[1]);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    TwinRay &q = r[k];
+                    const V3 light_ray = k == 0 ? light_ray0 : light_ray1;
+                    if (q.shade && !blocked[k]) {
+                        const int mat = (int)(lds_u32[p.objinfo_off * 4 + q.idx] >> 20);
+                        const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
+                        const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
+                        const V3 object_color = entry_colour<false>(p, lds, m0, __float_as_uint(m1.w), q.texsel);
+                        const float diffuse_factor = m0.w, specular_factor = m1.x;
+                        V3 normal_dir = q.N;                     /* CollisionObject ctor: Ray(point, normal) re-normalises */
+                        if (!normals_are_unit) normal_dir = renormalize3(not_speculated(q.N));
+                        const V3 light_color = xyz(l1);
+                        /* cosineShade, :654-701 */
+                        if (diffuse_factor > (float)0) {
+                            float cosine_dot_factor = dot3(normal_dir, light_ray);
+                            if (cosine_dot_factor > (float)0) {
+                                float factor = cosine_dot_factor * diffuse_factor * l0.w;
+                                q.C.x += factor * object_color.x * light_color.x;
+                                q.C.y += factor * object_color.y * light_color.y;
+                                q.C.z += factor * object_color.z * light_color.z;
+                            }
+                            q.C.x = (q.C.x > 1.0f) ? 1.0f : q.C.x;
+                            q.C.y = (q.C.y > 1.0f) ? 1.0f : q.C.y;
+                            q.C.z = (q.C.z > 1.0f) ? 1.0f : q.C.z;
+                        }
+                        /* specular, :561-588 */
+                        V3 Nn = normal_dir;                      /* third normalisation, :566-567 */
+                        if (!normals_are_unit) Nn = renormalize3(not_speculated(normal_dir));
+                        const V3 R = sub3(light_ray, scale3(Nn, 2.0f * dot3(light_ray, Nn)));
+                        const float dot = dot3(q.d, R);
+                        if (dot > (float)0) {
+                            float pow_factor = dot;
+#pragma unroll
+                            for (int j = 0; j < 19; ++j) pow_factor *= dot;
+                            const float spec_factor = pow_factor * specular_factor;
+                            q.C = add3(q.C, scale3(light_color, spec_factor));
+                        }
+                    }
+                }
+            }
+        }
+
+        /* ---- phase 3 (per ray): reflect or finish, :595-604 ---- */
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            TwinRay &q = r[k];
+            if (q.shade) {
+                const int mat = (int)(lds_u32[p.objinfo_off * 4 + q.idx] >> 20);
+                const float reflective_factor = lds[p.mat_off + mat * RT_MAT_QUADS + 1].y;
+                const float n_dot_incoming = dot3(q.N, q.d);     /* src/SceneObject.h:65 */
+                if (reflective_factor > (float)0 && level == p.max_depth) {
+                    /* the reflected ray of the LAST level is never traced: render_tile() */
+                    const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
+                    const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
+                    const V3 oc = entry_colour<false>(p, lds, m0, __float_as_uint(m1.w), q.texsel);
+                    const V3 refl = mk(null_color.x * m1.y * oc.x, null_color.y * m1.y * oc.y, null_color.z * m1.y * oc.z);
+                    q.C = add3(q.C, refl);
+                    q.alive = false;
+                } else if (reflective_factor > (float)0) {
+                    const V3 reflected = mk(-2 * q.N.x * n_dot_incoming + q.d.x,
+                                            -2 * q.N.y * n_dot_incoming + q.d.y,
+                                            -2 * q.N.z * n_dot_incoming + q.d.z);
+                    *twin_stack_entry(p, wlds, bounce_stack, level, k) =
+                        make_float4(q.C.x, q.C.y, q.C.z, __uint_as_float((uint32_t)q.idx | ((uint32_t)q.texsel << 16)));
+                    q.top = level + 1;
+                    q.o = q.P;
+                    q.d = normalize3(reflected);                 /* Ray(point, reflected) */
+                    q.C = null_color;                            /* if the loop ends now the call at max_depth+1 returns NULL_COLOR */
+                } else {
+                    q.alive = false;                             /* C already holds final_color */
+                }
+            }
+        }
+    }
+
+    if (p.tile_prio != 0) __builtin_amdgcn_s_setprio(0);
+    /* unwind: final_k = local_k + (rf_k * C_{k+1}) * oc_k, inside-out (:601), each ray up its own rows */
+    for (int j = levels - 1; j >= 0; --j) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            TwinRay &q = r[k];
+            if (j < q.top) {
+                const float4 e = *twin_stack_entry(p, wlds, bounce_stack, j, k);
+                const uint32_t bits = __float_as_uint(e.w);
+                const uint32_t info = lds_u32[p.objinfo_off * 4 + (bits & 0xFFFFu)];
+                const int mat = (int)(info >> 20);
+                const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
+                const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
+                const V3 oc = entry_colour<false>(p, lds, m0, __float_as_uint(m1.w), (int)(bits >> 16));
+                const V3 refl = mk(q.C.x * m1.y * oc.x, q.C.y * m1.y * oc.y, q.C.z * m1.y * oc.z);
+                q.C = add3(mk(e.x, e.y, e.z), refl);
+            }
+        }
+    }
+
+    /* the next entry, asked for ahead, becomes a scalar BEFORE the pixels are stored (render_tile()) */
+    next_pop = __builtin_amdgcn_readfirstlane(next_pop);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (r[k].inside) {
+            const int tzl_b = here(p.tile_z_log2);
+            const int sx = here(tile_col) * (64 >> tzl_b) + (lane >> tzl_b);   /* x - x0 */
+            const int sz = ((here(tile_row) + k) << tzl_b) + (lane & ((1 << tzl_b) - 1));
+            float *dst = out + ((size_t)sx * (size_t)p.H + (size_t)sz) * 3;
+#if RT_NT_STORES
+            __builtin_nontemporal_store(r[k].C.x, dst); __builtin_nontemporal_store(r[k].C.y, dst + 1); __builtin_nontemporal_store(r[k].C.z, dst + 2);
+#else
+            dst[0] = r[k].C.x; dst[1] = r[k].C.y; dst[2] = r[k].C.z;
+#endif
+        }
+    }
+}
+
 /* ---- RAY QUERIES (include/rt_capi_query.h): the tiles of the *_hits and *_occluded kernels --------------------------------
  * A ray-batch tile (render_tile(), kRays: cell (x, z) of the n_cols x rows grid is ray x * rows + z) that asks the scene one
  * question per lane and stores the answer: no shading, no bounce stack, no HELP. */
@@ -2688,6 +3212,27 @@ __device__ RT_SCAN_INLINE unsigned int queues_with_tiles(const unsigned int *til
     return (unsigned int)__builtin_amdgcn_ballot_w64(left > 0) & 0xFFu;
 }
 
+/* TWIN TILES: the same look for queues whose entries are twins, RT_MACRO_ROWS / 2 per macro tile.  Written queue by queue
+ * with wave-uniform values only: what the lane-per-queue form derives from the lane number -- a head's address, a queue's
+ * length -- is loop-invariant, gets computed at the kernel's start and kept in vector registers across every tile, and the
+ * twin kernel's registers are all taken (they were its only spilled ones).  Once per wavefront, when its own queue runs dry. */
+__device__ __forceinline__ unsigned int queues_with_twins(const unsigned int *tile_counter, const int n_macros) {
+    unsigned int taken[RT_TILE_QUEUES];
+#pragma unroll
+    for (int q = 0; q < RT_TILE_QUEUES; ++q)
+        taken[q] = __hip_atomic_load(tile_counter + q * RT_QUEUE_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned int nonempty = 0u;
+#pragma unroll
+    for (int q = 0; q < RT_TILE_QUEUES; ++q) {
+        const int len_q = q < n_macros ? ((n_macros - q + RT_TILE_QUEUES - 1) / RT_TILE_QUEUES) * (RT_MACRO_ROWS / 2) : 0;
+        const int blocks = (int)gridDim.x;
+        const int first_q = q < blocks ? ((blocks - q + RT_TILE_QUEUES - 1) / RT_TILE_QUEUES) * (int)(blockDim.x >> 6) : 0;      /* first_entries(q, 0), written out: a call with a constant argument changes how the shared helper is optimised before it is inlined, and with it the other kernels of this unit */
+        const int left = len_q - first_q - (int)min((unsigned int)__builtin_amdgcn_readfirstlane((int)taken[q]), 0x3fffffffu);
+        nonempty |= left > 0 ? 1u << q : 0u;
+    }
+    return nonempty;
+}
+
 template <bool kStats, bool kGlobalTables = false, bool kClusters = false, bool kRoomy = false, bool kFast = false, bool kSsaa = false,
           bool kRays = false, int kQuery = RT_QUERY_NONE, bool kGbuffer = false, bool kImages = false, bool kRefract = false,
           bool kSoft = false>
@@ -2792,6 +3337,13 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
     }
     const int macro_rows = (p.tiles_z + RT_MACRO_ROWS - 1) / RT_MACRO_ROWS;
     const int n_macros = macro_rows * p.tiles_x;
+    /* TWIN TILES (render_tile_twin()): an entry of rt_render_kernel's queues is a twin -- tile rows 2j and 2j + 1 of a macro tile,
+     * still one macro tile per queue turn, so the XCD and the sector merging above are what they were -- and a macro tile is
+     * RT_MACRO_ROWS / 2 entries.  Every other kernel: an entry is a tile. */
+    constexpr bool kTwin = !kStats && RT_KERNEL_IS_TWIN(kGlobalTables, kClusters, kFast, kSsaa, kRays, kQuery, kGbuffer, kImages, kRefract, kSoft);
+    constexpr int kEntryRows = kTwin ? 2 : 1;                       /* tile rows per queue entry */
+    constexpr int kMacroEntries = RT_MACRO_ROWS / kEntryRows;       /* queue entries per macro tile */
+    static_assert(RT_MACRO_ROWS % kEntryRows == 0, "a macro tile is a whole number of twins");
     /* ask for the following tile while this one is rendered; the answer is only needed afterwards.  Not so in scenes
      * with clustered sphere runs, whose tiles take from tens of microseconds to milliseconds: a tile asked for
      * ahead of a long one waits for it while other wavefronts idle (a strip's timeline showed tiles STARTING a
@@ -2838,7 +3390,7 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
             const int queue = (my_xcc + steal) & (RT_TILE_QUEUES - 1);
             unsigned int *const head = tile_counter + queue * RT_QUEUE_STRIDE;
             /* macro tiles queue, queue + 8, queue + 16, ... */
-            const int queue_len = queue < n_macros ? ((n_macros - queue + RT_TILE_QUEUES - 1) / RT_TILE_QUEUES) * RT_MACRO_ROWS : 0;
+            const int queue_len = queue < n_macros ? ((n_macros - queue + RT_TILE_QUEUES - 1) / RT_TILE_QUEUES) * kMacroEntries : 0;
             if (fresh) {
                 if (lane == 0) next_pop = (int)atomicAdd(head, 1u);
                 fresh = false;
@@ -2857,7 +3409,8 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
                     ++steal;
                 } else {
                     if (candidates == ~0u) {
-                        const unsigned int nonempty = queues_with_tiles(tile_counter, n_macros, heavy_blocks);                   /* bit q: queue q */
+                        const unsigned int nonempty = kTwin ? queues_with_twins(tile_counter, n_macros)
+                                                            : queues_with_tiles(tile_counter, n_macros, heavy_blocks);    /* bit q: queue q */
                         candidates = ((nonempty >> my_xcc) | (nonempty << (RT_TILE_QUEUES - my_xcc))) & 0xFFu & ~(1u << (steal & 7));     /* bit k: queue my_xcc + k; not the one just found empty */
                     }
                     if (candidates == 0u) break;
@@ -2868,13 +3421,13 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
                 continue;
             }
             if (ask_ahead && lane == 0) next_pop = (int)atomicAdd(head, 1u);
-            const int macro = (pop / RT_MACRO_ROWS) * RT_TILE_QUEUES + queue;
+            const int macro = (pop / kMacroEntries) * RT_TILE_QUEUES + queue;
             const int queued_row = macro / p.tiles_x;
             const int tile_col = macro - queued_row * p.tiles_x;
             /* from first_macro_row (< macro_rows) upwards, or (rows_downwards) downwards; both wrap around */
             const int shifted_row = p.rows_downwards ? p.first_macro_row - queued_row : p.first_macro_row + queued_row;
             const int macro_row = shifted_row >= macro_rows ? shifted_row - macro_rows : (shifted_row < 0 ? shifted_row + macro_rows : shifted_row);
-            const int tile_row = macro_row * RT_MACRO_ROWS + (pop % RT_MACRO_ROWS);
+            const int tile_row = macro_row * RT_MACRO_ROWS + (pop % kMacroEntries) * kEntryRows;    /* (a twin: its first row) */
             bool skip = tile_row >= p.tiles_z;                      /* ragged top macro row */
             if constexpr (kHelp) {                                  /* a HEAVY tile: rendered by a workgroup, above */
                 if (p.help_rays_quads != 0 && p.heavy_half >= 0) {
@@ -2894,6 +3447,10 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
         if (p.timeline != 0ull && lane == 0)
             reinterpret_cast<unsigned long long *>(p.timeline)[(size_t)wave * RT_TIMELINE_WORDS] = __builtin_amdgcn_s_memrealtime();
         const int tile_number = here(wave);
+        /* (a twin: both tiles get the twin's record, the second where its row exists) */
+        const bool second_tile = kTwin && tile_number + p.tiles_x < p.n_tiles;
+        if (second_tile && p.timeline != 0ull && lane == 0)
+            reinterpret_cast<unsigned long long *>(p.timeline)[(size_t)(tile_number + p.tiles_x) * RT_TIMELINE_WORDS] = __builtin_amdgcn_s_memrealtime();
 #endif
         /* (the kernels that do not ask ahead ask inside, when the tile's rays are through -- not for a HEAVY tile, whose
          * successor comes from the HEAVY tiles' own head) */
@@ -2902,6 +3459,7 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
         constexpr int kMode = kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0);
         if constexpr (kQuery == RT_QUERY_HITS) hits_tile<kMode, kImages>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
         else if constexpr (kQuery == RT_QUERY_OCCLUDED) occluded_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
+        else if constexpr (kTwin) render_tile_twin(p, lds, wlds, ctl_words, out, bounce_stack, wave, next_pop);
         else render_tile<kStats, kMode, kSsaa, kRays, kGbuffer, kImages, kRefract, kSoft>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
                                                                 my_xcc, steal, next_pop, ask_head, shadow_seed);
 #ifdef RT_TIMELINE
@@ -2910,6 +3468,10 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
             rec[1] = __builtin_amdgcn_s_memrealtime();
             rec[2] = (unsigned long long)blockIdx.x * 16ull + (threadIdx.x >> 6);
             rec[3] = (kHelp && heavy_phase != 0) ? 1ull : 0ull;
+            if (second_tile) {
+                unsigned long long *rec2 = rec + (size_t)p.tiles_x * RT_TIMELINE_WORDS;
+                rec2[1] = rec[1]; rec2[2] = rec[2]; rec2[3] = rec[3];
+            }
         }
 #endif
     }
@@ -2948,6 +3510,11 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
 #ifndef RT_WAVES_PER_SIMD
 #define RT_WAVES_PER_SIMD 7
 #endif
+/* rt_render_kernel with TWIN TILES: two ray states per lane do not fit the 72 registers of seven wavefronts (A/B of 4, 5 and 6:
+ * profiles/twin_tiles_ab.txt) */
+#ifndef RT_WAVES_PER_SIMD_TWIN
+#define RT_WAVES_PER_SIMD_TWIN 5
+#endif
 #ifndef RT_WAVES_PER_SIMD_CLUSTERS
 #define RT_WAVES_PER_SIMD_CLUSTERS 6
 #endif
@@ -2964,7 +3531,9 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
 #define RT_SEED_ARG_true shadow_seed
 #define RT_DEFINE_KERNEL(mode, global_tables, clusters, roomy, fast, block_bound, waves, waves_soft,                           \
                          family, ssaa, rays, query, gbuffer, images, refract, soft, seeded)                                    \
-    extern "C" __global__ void __launch_bounds__(block_bound, (soft ? waves_soft : waves))                                     \
+    extern "C" __global__ void __launch_bounds__(block_bound,                                                                  \
+        (RT_KERNEL_IS_TWIN(global_tables, clusters, fast, ssaa, rays, query, gbuffer, images, refract, soft)                   \
+             ? RT_WAVES_PER_SIMD_TWIN : (soft ? waves_soft : waves)))                                                          \
     rt_render_kernel##mode##family(RT_KERNEL_ARGS RT_SEED_PARAM_##seeded) {                                                    \
         RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);                                                                               \
         render_body<false, global_tables, clusters, roomy, fast, ssaa, rays, query, gbuffer, images, refract, soft>(            \

@@ -288,7 +288,8 @@ enum { RT_QUERY_NONE = 0, RT_QUERY_HITS = 1, RT_QUERY_OCCLUDED = 2 };
  * wavefronts per SIMD of the soft families, family...) -- the launch bounds' names are rt_kernel.hip's.
  *   ""              FAST tables (scenes without clustered sphere runs; the built-in scene, the bench headline): 72 VGPRs, seven
  *                   wavefronts per SIMD where LDS allows (the bounce stack keeps its LDS place up to seven workgroups per CU,
- *                   RT_STACK_LDS_SHARE)
+ *                   RT_STACK_LDS_SHARE).  The base family's kernel of this mode, rt_render_kernel, is the TWIN TILES kernel
+ *                   (below): 96 VGPRs, five wavefronts per SIMD, its own bound RT_WAVES_PER_SIMD_TWIN
  *   _items          the same over the two item tables: option "fast" = 0, and option "cull" = 0 (the plain in-order scans)
  *   _large          scenes whose tables are large (or do not fit LDS at all): the tables stay in global memory.  These need
  *                   52-62 VGPRs and so run 8 wavefronts per SIMD although their bound asks for RT_WAVES_PER_SIMD only; the
@@ -306,6 +307,20 @@ enum { RT_QUERY_NONE = 0, RT_QUERY_HITS = 1, RT_QUERY_OCCLUDED = 2 };
     X(_large,         true,  false, false, false, RT_BLOCK_BOUND,          RT_WAVES_PER_SIMD,          8,                          __VA_ARGS__) \
     X(_clusters,      false, true,  false, false, RT_BLOCK_BOUND_CLUSTERS, RT_WAVES_PER_SIMD_CLUSTERS, RT_WAVES_PER_SIMD_CLUSTERS, __VA_ARGS__) \
     X(_clusters_wide, false, true,  true,  false, RT_BLOCK_BOUND_CLUSTERS, RT_WAVES_PER_SIMD_WIDE,     RT_WAVES_PER_SIMD_WIDE,     __VA_ARGS__)
+
+/* TWIN TILES.  rt_render_kernel -- the FAST tables' kernel of the camera's plain frame, the bench headline -- renders wavefront
+ * tiles in vertical pairs: every lane carries two pixels, one of each of tile rows 2j and 2j + 1 of a macro tile, and what a
+ * wavefront does as a whole (bundle bounds, culls, candidate order, scalar dispatch) runs once for both (rt_kernel.hip,
+ * render_tile_twin()).  A queue entry of that kernel is a twin, its bounce stack has two rows per level, and its launch bound
+ * is RT_WAVES_PER_SIMD_TWIN instead of the mode's.  Every other kernel renders one tile per wavefront, and so does this one
+ * with -DRT_TWIN_TILES=0 (a build switch, not an option: both bodies in one kernel would cost both their registers).
+ * RT_KERNEL_IS_TWIN: the rule, from a kernel's catalogue columns, for rt_kernel.hip and rt_capi.hip alike. */
+#ifndef RT_TWIN_TILES
+#define RT_TWIN_TILES 1
+#endif
+#define RT_KERNEL_IS_TWIN(global_tables, clusters, fast, ssaa, rays, query, gbuffer, images, refract, soft)                    \
+    (RT_TWIN_TILES != 0 && (fast) && !(global_tables) && !(clusters) && !(ssaa) && !(rays) && (query) == RT_QUERY_NONE &&      \
+     !(gbuffer) && !(images) && !(refract) && !(soft))
 
 /* The families, one list per translation unit of kernels: rt_kernel.hip is compiled once per unit (-DRT_KERNEL_TU=<unit>,
  * rt_kernel_<unit>.o; the base unit is rt_kernel.o), each unit's kernels in this order.  The split is part of the speed
