@@ -58,6 +58,13 @@ class RtDenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("sigma_color", C.c_float)]
 
 
+class RtAoParams(C.Structure):
+    """include/rt_capi_ao.h: n (n x n directions per record, 1..8), the radius a direction is followed for, the seed, the first
+    record's key, channels (1, or 3 equal ones)."""
+    _fields_ = [("samples", C.c_int32), ("radius", C.c_float), ("seed", C.c_uint32), ("key0", C.c_uint32),
+                ("channels", C.c_int32)]
+
+
 RT_TRANSFER_SRGB, RT_TRANSFER_LINEAR, RT_TRANSFER_CUSTOM = 0, 1, 2
 
 
@@ -237,6 +244,12 @@ def load_library():
         lib.rt_encode_image.argtypes = [i, C.POINTER(RtImageParams), i, i, vp, vp, C.c_uint64, C.POINTER(C.c_double)]
         lib.rt_encode_image_device.argtypes = [i, C.POINTER(RtImageParams), i, i, vp, vp, C.c_uint64, vp]
         lib.rt_image_transfer_table.restype = lib.rt_encode_image.restype = lib.rt_encode_image_device.restype = i
+    # include/rt_capi_ao.h (likewise absent from older builds)
+    if hasattr(lib, "rt_ambient_occlusion"):
+        lib.rt_capi_ao_version.restype = i
+        lib.rt_ambient_occlusion.argtypes = [vp, C.POINTER(RtAoParams), i, i, vp, vp]
+        lib.rt_ambient_occlusion_device.argtypes = [vp, C.POINTER(RtAoParams), i, i, vp, vp, vp]
+        lib.rt_ambient_occlusion.restype = lib.rt_ambient_occlusion_device.restype = i
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):
         lib.rt_capi_launch_version.restype = i

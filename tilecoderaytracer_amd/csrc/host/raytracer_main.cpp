@@ -22,6 +22,10 @@
  *   --ppm FILE          also the frame as a binary PPM, whatever made it (plain, --ssaa, --denoise, --gpus): rt_encode_image with
  *                       the sRGB table, 3 channels, the top row first (include/rt_capi_image.h)
  *   --exposure E        the colours are multiplied by E (finite, > 0; default 1) before they are encoded; needs --ppm
+ *   --ao N[:RADIUS] --ao-ppm FILE   also the frame's ambient-occlusion plane as a binary PPM (include/rt_capi_ao.h): the camera
+ *                       rays' records (rt_render_gbuffer), N x N directions per pixel (1..8) followed for RADIUS (default 1.0),
+ *                       seed 0, three equal channels, encoded by rt_encode_image with the LINEAR table, the top row first; one
+ *                       GPU, no supersampling.  The two options come together; the frame itself is the one rendered without them
  */
 #include <chrono>
 #include <cmath>
@@ -33,6 +37,7 @@
 #include <vector>
 
 #include "../../../include/rt_capi.h"
+#include "../../../include/rt_capi_ao.h"
 #include "../../../include/rt_capi_denoise.h"
 #include "../../../include/rt_capi_gbuffer.h"
 #include "../../../include/rt_capi_image.h"
@@ -52,14 +57,15 @@ static int usage(const char *argv0) {
     std::fprintf(stderr,
                  "usage: %s [--width W] [--height H] [--depth D] [--scene 1|2|grid:N[:noshadow]]\n"
                  "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE] [--glass I:TF:IOR ...]\n"
-                 "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n", argv0);
+                 "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n"
+                 "          [--ao N[:RADIUS] --ao-ppm FILE]\n", argv0);
     return 1;
 }
 
 int main(int argc, char **argv) {
     int W = 500, H = 504, depth = 50, gpus = 1, ssaa = 1;
     bool write_txt = true, has_exposure = false;
-    std::string scene_name = "1", out_path = "raytracer_screen.txt", hits_path, ppm_path, exposure_arg;
+    std::string scene_name = "1", out_path = "raytracer_screen.txt", hits_path, ppm_path, exposure_arg, ao_arg, ao_ppm_path;
     std::vector<std::string> glass;              /* --glass I:TF:IOR: object I refractive (include/rt_capi_refract.h) */
     std::string denoise;                         /* --denoise IT[:SIGMA[:K]] (include/rt_capi_denoise.h) */
     std::vector<std::string> soft;               /* --soft I:N[:R]: light I an area light, N x N samples, radius R (include/rt_capi_soft.h) */
@@ -79,6 +85,8 @@ int main(int argc, char **argv) {
         else if (a == "--denoise" && i + 1 < argc) denoise = argv[++i];
         else if (a == "--ppm" && i + 1 < argc) ppm_path = argv[++i];
         else if (a == "--exposure" && i + 1 < argc) exposure_arg = argv[++i], has_exposure = true;
+        else if (a == "--ao" && i + 1 < argc) ao_arg = argv[++i];
+        else if (a == "--ao-ppm" && i + 1 < argc) ao_ppm_path = argv[++i];
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
@@ -101,6 +109,22 @@ int main(int argc, char **argv) {
         im.exposure = std::strtof(exposure_arg.c_str(), &end);
         if (ppm_path.empty() || end == exposure_arg.c_str() || *end || !(im.exposure > 0.0f) || std::isinf(im.exposure))
             return usage(argv[0]);             /* (what rt_encode_image would refuse) */
+    }
+    rt_ao_params ao = {0, 1.0f, 0u, 0u, 3};
+    if (ao_arg.empty() != ao_ppm_path.empty()) return usage(argv[0]);
+    if (!ao_arg.empty()) {
+        /* N, or N:RADIUS, and nothing else */
+        char *end = nullptr;
+        const long n = std::strtol(ao_arg.c_str(), &end, 10);
+        if (end == ao_arg.c_str() || (*end != '\0' && *end != ':') || n < 1 || n > RT_AO_MAX_SAMPLES) return usage(argv[0]);
+        ao.samples = (int)n;
+        if (*end == ':') {
+            const char *r = end + 1;
+            ao.radius = std::strtof(r, &end);
+            if (end == r || *end != '\0') return usage(argv[0]);
+        }
+        if (ao.samples < 1 || ao.samples > RT_AO_MAX_SAMPLES || !(ao.radius > 0.0f) || std::isinf(ao.radius)) return usage(argv[0]);
+        if (gpus > 1 || ssaa > 1) return usage(argv[0]);       /* (one GPU; a supersampled frame has no records) */
     }
     verbose() = true;                          /* console output like the reference's */
 
@@ -163,7 +187,8 @@ int main(int argc, char **argv) {
         return 1;
     }
     pixels.assign((size_t)W * (size_t)H * 3, 0.0f);
-    std::vector<rt_hit> hits(hits_path.empty() && denoise.empty() ? 0 : (size_t)W * (size_t)H);
+    std::vector<rt_hit> hits(hits_path.empty() && denoise.empty() && ao_arg.empty() ? 0 : (size_t)W * (size_t)H);
+    std::vector<float> ao_plane(ao_arg.empty() ? 0 : (size_t)W * (size_t)H * 3);
 
     std::printf("****** Start Ray Tracing. *******\n");
     const auto t0 = std::chrono::steady_clock::now();
@@ -178,6 +203,18 @@ int main(int argc, char **argv) {
         if (rc == RT_OK) {
             rt_timing tm;
             if (rt_get_timing(scene, &tm) == RT_OK) kernel_ms = tm.last_kernel_ms;
+        }
+        if (rc == RT_OK && !ao_arg.empty()) {           /* (before the filter: it reads the records, not the colours) */
+            if ((double)W * (double)H > 533333333.0) {           /* (rt_ambient_occlusion's record limit; W * H must fit its int) */
+                std::fprintf(stderr, "--ao: the frame has more than 533333333 pixels\n");
+                rt_scene_destroy(scene);
+                return 1;
+            }
+            rc = rt_ambient_occlusion(scene, &ao, W * H, H, hits.data(), ao_plane.data());
+            rt_timing tm;
+            if (rc == RT_OK && rt_get_timing(scene, &tm) == RT_OK)
+                std::printf("Ambient occlusion (ms)     : %f  (%d x %d directions, radius %g)\n", tm.last_kernel_ms, ao.samples,
+                            ao.samples, (double)ao.radius);
         }
         if (rc == RT_OK && !denoise.empty()) {
             double denoise_ms = 0.0;
@@ -250,6 +287,18 @@ int main(int argc, char **argv) {
         std::printf("Encode kernel (ms)         : %f  (sRGB, exposure %g)\n", encode_ms, (double)im.exposure);
         if (celio_write_screen_ppm(ppm_path.c_str(), W, H, image.data(), (uint64_t)W * 3u)) {
             std::fprintf(stderr, "cannot write %s\n", ppm_path.c_str());
+            return 1;
+        }
+    }
+    if (!ao_ppm_path.empty()) {
+        const rt_image_params linear = {3, 0, RT_TRANSFER_LINEAR, 1.0f, nullptr};
+        std::vector<uint8_t> image((size_t)W * (size_t)H * 3);
+        if (rt_encode_image(0, &linear, W, H, ao_plane.data(), image.data(), (uint64_t)W * 3u, nullptr) != RT_OK) {
+            std::fprintf(stderr, "encode failed: %s\n", rt_last_error());
+            return 1;
+        }
+        if (celio_write_screen_ppm(ao_ppm_path.c_str(), W, H, image.data(), (uint64_t)W * 3u)) {
+            std::fprintf(stderr, "cannot write %s\n", ao_ppm_path.c_str());
             return 1;
         }
     }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cstddef>
 #include <cmath>
 #include <cstdio>
@@ -17,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/rt_capi_ao.h"
 #include "../../include/rt_capi_gbuffer.h"
 #include "../../include/rt_capi_launch.h"
 #include "../../include/rt_capi_query.h"
@@ -34,6 +36,12 @@
     extern "C" __global__ void rt_render_kernel##mode##family(RT_KERNEL_ARGS RT_SEED_PARAM_##seeded);
 #define RT_DECLARE_FAMILY(...) RT_TABLE_MODES(RT_DECLARE_KERNEL, __VA_ARGS__)
 RT_RENDER_FAMILIES(RT_DECLARE_FAMILY)
+/* the auxiliary kernels (rt_tables.h, AUXILIARY KERNELS): rt_ao_kernel<mode>, include/rt_capi_ao.h */
+#define RT_DECLARE_AO_KERNEL(mode, global_tables, clusters, roomy, fast, block_bound, waves, waves_soft,                       \
+                             family, ssaa, rays, query, gbuffer, images, refract, soft, seeded)                                \
+    extern "C" __global__ void rt_ao_kernel##mode##family(RT_KERNEL_ARGS RT_SEED_PARAM_##seeded RT_AO_PARAMS);
+#define RT_DECLARE_AO_FAMILY(...) RT_TABLE_MODES(RT_DECLARE_AO_KERNEL, __VA_ARGS__)
+RT_AUX_UNIT_ao(RT_DECLARE_AO_FAMILY)
 extern "C" __global__ void rt_render_kernel_stats(RT_KERNEL_ARGS_STATS);        /* the counting builds */
 extern "C" __global__ void rt_render_kernel_fast_stats(RT_KERNEL_ARGS_STATS);
 
@@ -43,6 +51,7 @@ static_assert(offsetof(RtParams, ssaa_log2) == 1336 && offsetof(RtParams, n_rays
                   sizeof(RtParams) == 1352,
               "RtParams layout");
 static_assert(offsetof(RtParams, gbuffer_hits) == offsetof(RtParams, rays), "RtParams: the G-buffer's records share the rays' place");
+static_assert(sizeof(rt_ao_params) == 20 && sizeof(RtAoArgs) == 16, "rt_ao_params layout");
 static_assert(sizeof(rt_hit) == RT_HIT_BYTES && offsetof(rt_hit, normal) == 20 && offsetof(rt_hit, flags) == 44, "rt_hit layout");
 
 namespace {
@@ -1320,9 +1329,10 @@ void camera_params(const rt_camera_desc *cam, RtParams &p) {
 
 /* The calls: a camera's frame (rt_render*), its supersampled frame (rt_render_ssaa*, k > 1), its frame with hit records
  * (rt_render_gbuffer*); a ray batch shaded (rt_trace_rays*) or queried (include/rt_capi_query.h: the *_hits or *_occluded
- * kernels instead of shading).  With the scene's shading the call names the family of kernels (family()). */
-enum Call { kCallFrame, kCallSsaa, kCallGbuffer, kCallRays, kCallHits, kCallOccluded, kCalls };
-bool is_query(Call c) { return c == kCallHits || c == kCallOccluded; }
+ * kernels instead of shading; include/rt_capi_ao.h: a batch of hit RECORDS through the rt_ao_kernel* kernels, a query in every
+ * other respect).  With the scene's shading the call names the family of kernels (family()). */
+enum Call { kCallFrame, kCallSsaa, kCallGbuffer, kCallRays, kCallHits, kCallOccluded, kCallAo, kCalls };
+bool is_query(Call c) { return c == kCallHits || c == kCallOccluded || c == kCallAo; }
 bool is_batch(Call c) { return c == kCallRays || is_query(c); }
 
 /* One launch as its entry point asks for it: built there once, read by plan_launch(), launch() and the policy below them. */
@@ -1342,6 +1352,8 @@ struct LaunchRequest {
      * the *_gbuffer sibling of rt_render's, and p.gbuffer_hits = d_hits */
     void *d_hits = nullptr;
     unsigned long long *d_stats = nullptr;    /* the counting build's counters (rt_render_stats); NULL: not counting */
+    /* kCallAo: n_rays records of 48 bytes at d_rays; the sampling's parameters travel as kernel arguments (launch()) */
+    const rt_ao_params *ao = nullptr;
 };
 
 /* Wavefront tile shape (speed only).  4 x 16 (x by z) makes every lane-row's
@@ -1473,7 +1485,8 @@ void learned_start_row(const rt_scene *s, int W, int H, int x0, int x1, int max_
     }
 }
 
-struct Kernel { const void *fn; const char *name; bool seeded = false; };    /* seeded: takes the sampling seed (SOFT SHADOWS) */
+/* seeded: takes the sampling seed (SOFT SHADOWS); ao: an rt_ao_kernel*, which takes the seed and RT_AO_PARAMS */
+struct Kernel { const void *fn; const char *name; bool seeded = false; bool ao = false; };
 #define RT_KERNEL(k, seeded) Kernel{(const void *)k, #k, seeded}
 
 /* the catalogue's table modes and families (rt_tables.h, RENDER KERNELS): kMode is the FAST tables' mode, kFamily the camera's
@@ -1503,6 +1516,13 @@ constexpr bool kernel_names_fit(size_t i = 0) {
            (kKernelNameBytes[i] <= RT_KERNEL_NAME_BYTES && kernel_names_fit(i + 1));
 }
 static_assert(kernel_names_fit(), "a render kernel's name does not fit RT_KERNEL_NAME_BYTES");
+/* AMBIENT OCCLUSION: rt_ao_kernel<mode>, [mode] */
+#define RT_AO_KERNEL_ENTRY(mode, global_tables, clusters, roomy, fast, block_bound, waves, waves_soft,                         \
+                           family, ssaa, rays, query, gbuffer, images, refract, soft, seeded)                                  \
+    Kernel{(const void *)rt_ao_kernel##mode##family, "rt_ao_kernel" #mode #family, seeded, true},
+#define RT_AO_KERNEL_ROW(...) RT_TABLE_MODES(RT_AO_KERNEL_ENTRY, __VA_ARGS__)
+const Kernel kAoKernels[kModes] = {RT_AUX_UNIT_ao(RT_AO_KERNEL_ROW)};
+static_assert(sizeof("rt_ao_kernel_clusters_wide") <= RT_KERNEL_NAME_BYTES, "an AO kernel's name does not fit RT_KERNEL_NAME_BYTES");
 
 /* the clustered-scene kernels (PAIRS, HELP): for scenes with clustered sphere runs whose tables are in LDS */
 bool clusters_mode(const rt_scene *s, bool global_tables) { return !global_tables && s->n_clusters > 0 && s->pairs_opt; }
@@ -1527,7 +1547,7 @@ Family family(const rt_scene *s, Call call) {
     enum { kNone, kImage, kRefract, kSoft, kRefractSoft };
     const int shading = s->soft_used ? (s->refract_used ? kRefractSoft : kSoft)
                                      : (s->refract_used ? kRefract : (s->images_used ? kImage : kNone));
-    static const Family kByShading[kCalls][5] = {
+    static const Family kByShading[kCallAo][5] = {      /* (kCallAo, the last call, has no render family: choose_kernel()) */
         /* kCallFrame */ {kFamily, kFamily_image, kFamily_refract, kFamily_soft, kFamily_refract_soft},
         /* kCallSsaa */ {kFamily_ssaa, kFamily_ssaa_image, kFamily_ssaa_refract, kFamily_ssaa_soft, kFamily_ssaa_refract_soft},
         /* kCallGbuffer */ {kFamily_gbuffer, kFamily_gbuffer_image, kFamily_gbuffer_refract, kFamily_gbuffer_soft, kFamily_gbuffer_refract_soft},
@@ -1535,13 +1555,16 @@ Family family(const rt_scene *s, Call call) {
         /* kCallHits */ {kFamily_hits, kFamily_hits_image, kFamily_hits_image, kFamily_hits_image, kFamily_hits_image},
         /* kCallOccluded */ {kFamily_occluded, kFamily_occluded, kFamily_occluded, kFamily_occluded, kFamily_occluded},
     };
+    assert(call < kCallAo);
     return kByShading[call][shading];
 }
 
-/* the kernel of a launch: the counting build's, or the family's kernel in the table mode */
+/* the kernel of a launch: the counting build's, or the family's kernel in the table mode (AMBIENT OCCLUSION: geometry alone, so
+ * with any shading the one rt_ao_kernel of the table mode, as the occlusion query) */
 Kernel choose_kernel(const rt_scene *s, const LaunchRequest &rq, bool global_tables, int block, int lds_bytes) {
     if (rq.d_stats)
         return s->base.n_fast_items > 0 ? RT_KERNEL(rt_render_kernel_fast_stats, false) : RT_KERNEL(rt_render_kernel_stats, false);
+    if (rq.call == kCallAo) return kAoKernels[table_mode(s, global_tables, block, lds_bytes)];
     return kKernels[family(s, rq.call)][table_mode(s, global_tables, block, lds_bytes)];
 }
 
@@ -1720,10 +1743,15 @@ int launch(rt_scene *s, LaunchRequest rq, hipStream_t stream) {
     unsigned int *list_arg = reinterpret_cast<unsigned int *>(s->d_help);      /* the clustered-scene kernels' HELP areas (unused by the others) */
     void *args6[] = {&p, &image_arg, &rq.d_out, &counter, &stack_arg, &list_arg};
     void *args7[] = {&p, &image_arg, &rq.d_out, &counter, &stack_arg, &rq.d_stats, &list_arg};
-    uint32_t seed = s->shadow_seed;       /* SOFT SHADOWS: copied into the launch's arguments here, so it is this launch's */
+    /* SOFT SHADOWS: the scene's seed, copied into the launch's arguments here, so it is this launch's; AMBIENT OCCLUSION: the
+     * call's own seed, and its other parameters behind it */
+    uint32_t seed = rq.ao ? rq.ao->seed : s->shadow_seed;
     void *args_seeded[] = {&p, &image_arg, &rq.d_out, &counter, &stack_arg, &list_arg, &seed};
+    rt_ao_params ao = rq.ao ? *rq.ao : rt_ao_params{};
+    void *args_ao[] = {&p, &image_arg, &rq.d_out, &counter, &stack_arg, &list_arg, &seed, &ao.samples, &ao.radius, &ao.key0, &ao.channels};
     HIP_TRY(hipLaunchKernel(kernel, dim3((unsigned)blocks), dim3((unsigned)block),
-                            plan.kernel.seeded ? args_seeded : (rq.d_stats ? args7 : args6), (size_t)plan.lds_bytes, stream));
+                            plan.kernel.ao ? args_ao : plan.kernel.seeded ? args_seeded : (rq.d_stats ? args7 : args6),
+                            (size_t)plan.lds_bytes, stream));
     HIP_TRY(hipGetLastError());
     s->ev_next = next_slot;               /* (only now: a launch that did not happen has zeroed nothing) */
     HIP_TRY(hipEventRecord(s->ev[slot].stop, stream));
@@ -1815,33 +1843,56 @@ int rays_args(const rt_scene *s, int n, int *rows, const void *rays, int max_dep
     return RT_OK;
 }
 
-/* a host batch (kCallRays at the caller's depth, 12 bytes out per ray; a query at depth 0, an rt_hit or a byte per ray): into the
- * handle's buffers, the launch of its grid, out_bytes_per_ray * n bytes back */
-int batch_to_host(rt_scene *s, Call call, int n, int rows, const float *in, int max_depth, void *out, size_t out_bytes_per_ray) {
+/* a host batch (kCallRays at the caller's depth, 24 bytes in and 12 bytes out per ray; a query at depth 0, an rt_hit or a byte
+ * per ray; kCallAo, 48 bytes in and 4 x channels out per record): into the handle's buffers, the launch of its grid,
+ * out_bytes_per_ray * n bytes back.  ao: kCallAo's parameters, its arguments checked by ao_args() already */
+int batch_to_host(rt_scene *s, Call call, int n, int rows, const void *in, int max_depth, void *out, size_t out_bytes_per_ray,
+                  size_t in_bytes_per_ray = 6 * sizeof(float), const rt_ao_params *ao = nullptr) {
     int n_cols = 0;
     int rc = rays_args(s, n, &rows, in, max_depth, out, &n_cols);
     if (rc || n == 0) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
-    const size_t in_bytes = (size_t)n * 6 * sizeof(float), bytes = (size_t)n * out_bytes_per_ray;
+    const size_t in_bytes = (size_t)n * in_bytes_per_ray, bytes = (size_t)n * out_bytes_per_ray;
     HIP_TRY(hipSetDevice(s->device));
     rc = grow_device_buffer(&s->d_rays, &s->d_rays_bytes, in_bytes);
     if (rc == RT_OK) rc = grow_device_buffer(&s->d_fb, &s->d_fb_bytes, bytes);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(s->d_rays, in, in_bytes, hipMemcpyHostToDevice));
     return render_to_host(s, {.call = call, .n_rays = n, .d_rays = s->d_rays, .W = n_cols, .H = rows, .x0 = 0, .x1 = n_cols,
-                              .max_depth = max_depth, .d_out = s->d_fb},
+                              .max_depth = max_depth, .d_out = s->d_fb, .ao = ao},
                           {{out, s->d_fb, bytes}});
 }
 
 /* a device batch, enqueued on the caller's stream */
-int batch_on_device(rt_scene *s, Call call, int n, int rows, const void *d_in, int max_depth, void *d_out, void *hip_stream) {
+int batch_on_device(rt_scene *s, Call call, int n, int rows, const void *d_in, int max_depth, void *d_out, void *hip_stream,
+                    const rt_ao_params *ao = nullptr) {
     int n_cols = 0;
     int rc = rays_args(s, n, &rows, d_in, max_depth, d_out, &n_cols);
     if (rc || n == 0) return rc;
     std::lock_guard<std::mutex> lock(s->mu);
     return launch(s, {.call = call, .n_rays = n, .d_rays = d_in, .W = n_cols, .H = rows, .x0 = 0, .x1 = n_cols, .max_depth = max_depth,
-                      .d_out = d_out},
+                      .d_out = d_out, .ao = ao},
                   static_cast<hipStream_t>(hip_stream));
+}
+
+/* rt_ambient_occlusion*: the checks of include/rt_capi_ao.h in its order, all before the device is touched (device: the two
+ * alignments of the device call as well).  What passes here passes rays_args(): 2 n cells stay below 2^31 - 64. */
+constexpr int kMaxAoRecords = 533333333;          /* rt_render_gbuffer's record limit */
+int ao_args(const rt_scene *s, const rt_ao_params *a, int n, int rows, const void *hits, const void *out, bool device) {
+    if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
+    if (!a) return fail(RT_ERR_INVALID, "params is NULL");
+    if (a->samples < 1 || a->samples > RT_AO_MAX_SAMPLES)
+        return fail(RT_ERR_INVALID, "samples must be 1.." + std::to_string(RT_AO_MAX_SAMPLES) + " (got " + std::to_string(a->samples) + ")");
+    if (!(std::isfinite(a->radius) && a->radius > 0.0f)) return fail(RT_ERR_INVALID, "radius must be finite and > 0");
+    if (a->channels != 1 && a->channels != 3) return fail(RT_ERR_INVALID, "channels must be 1 or 3 (got " + std::to_string(a->channels) + ")");
+    if (n < 0) return fail(RT_ERR_INVALID, "n < 0");
+    if (rows < 1) return fail(RT_ERR_INVALID, "rows must be positive");
+    if (n > 0 && !hits) return fail(RT_ERR_INVALID, "hits pointer is NULL");
+    if (n > 0 && !out) return fail(RT_ERR_INVALID, "output pointer is NULL");
+    if (n > kMaxAoRecords) return fail(RT_ERR_INVALID, "more than " + std::to_string(kMaxAoRecords) + " records");
+    if (device && ((uintptr_t)hits & 15u) != 0) return fail(RT_ERR_INVALID, "d_hits must be 16-byte aligned");
+    if (device && ((uintptr_t)out & 3u) != 0) return fail(RT_ERR_INVALID, "d_out_ao must be 4-byte aligned");
+    return RT_OK;
 }
 
 /* rt_render_gbuffer*: the checks of include/rt_capi_gbuffer.h in its order, all before the device is touched -- rt_render's in
@@ -2147,6 +2198,24 @@ int rt_occluded_rays(rt_scene *s, int n, int rows, const float *segs, uint8_t *o
 
 int rt_occluded_rays_device(rt_scene *s, int n, int rows, const void *d_segs, void *d_out_blocked, void *hip_stream) {
     return batch_on_device(s, kCallOccluded, n, rows, d_segs, 0, d_out_blocked, hip_stream);
+}
+
+int rt_capi_ao_version(void) { return RT_CAPI_AO_VERSION; }
+
+/* AMBIENT OCCLUSION (include/rt_capi_ao.h): a batch of hit records at depth 0 through the rt_ao_kernel* kernels */
+int rt_ambient_occlusion(rt_scene *s, const rt_ao_params *params, int n, int rows, const rt_hit *hits, float *out_ao) {
+    const int rc = ao_args(s, params, n, rows, hits, out_ao, false);
+    if (rc) return rc;
+    const rt_ao_params a = *params;
+    return batch_to_host(s, kCallAo, n, rows, hits, 0, out_ao, (size_t)a.channels * sizeof(float), sizeof(rt_hit), &a);
+}
+
+int rt_ambient_occlusion_device(rt_scene *s, const rt_ao_params *params, int n, int rows, const void *d_hits, void *d_out_ao,
+                                void *hip_stream) {
+    const int rc = ao_args(s, params, n, rows, d_hits, d_out_ao, true);
+    if (rc) return rc;
+    const rt_ao_params a = *params;
+    return batch_on_device(s, kCallAo, n, rows, d_hits, 0, d_out_ao, hip_stream, &a);
 }
 
 int rt_capi_gbuffer_version(void) { return RT_CAPI_GBUFFER_VERSION; }

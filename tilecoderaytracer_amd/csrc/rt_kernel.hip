@@ -3182,6 +3182,82 @@ __device__ __forceinline__ void occluded_tile(const RtParams &p, const float4 *l
     }
 }
 
+/* AMBIENT OCCLUSION (include/rt_capi_ao.h; rt_tables.h, AUXILIARY KERNELS): the tile of the rt_ao_kernel* kernels.  Cell i of the
+ * grid is RECORD i of p.rays -- an rt_hit, read as three 16-byte loads, consecutive lanes reading consecutive records -- and the
+ * lane follows n x n directions of the hemisphere around the record's normal for the distance R: sample s is the segment {P, Q_s}
+ * of the header's definition, its verdict the occlusion query's (occluded_tile(): the same normalize3(), the same scan).  The
+ * sample loop is wave-uniform; every pass is one in_shade() / in_shade_fast() over the wavefront's 64 segments.
+ *
+ * The bundle cull is occluded_tile()'s argument as it stands: the box of the origins once per tile, the box of the ends per
+ * sample, e = e_o + e_e rounded up.  A record that is a miss or a light is not live: it is in no box, takes part in no scan
+ * and stores 1.0f; a tile without a live lane scans nothing.  A live lane whose point or end has a NaN is not in the boxes and
+ * needs nothing, an infinity makes the slabs NaN, i.e. "candidate": as there.
+ *
+ * U and V are not kept across the scans: they are recomputed per sample from N, so what a lane carries through a scan is P, N,
+ * its hash and its count (the *_occluded kernels' registers plus those). */
+template <int kMode>
+__device__ __forceinline__ void ao_tile(const RtParams &p, const float4 *lds, float4 *wlds, const uint32_t *__restrict__ ctl_words,
+                                        float *__restrict__ out, const int wave_in, int &next_pop, unsigned int *const ask_head,
+                                        const uint32_t seed, const RtAoArgs ao) {
+    Stats<false> st;
+    const int wave = __builtin_amdgcn_readfirstlane(wave_in);
+    bool inside;
+    const unsigned int rec = query_cell(p, wave, &inside);
+    const float4 *src = reinterpret_cast<const float4 *>(p.rays) + (size_t)min(rec, (unsigned int)p.n_rays - 1u) * 3;
+    const float4 q0 = src[0], q1 = src[1], q2 = src[2];
+    const bool live = inside && __float_as_int(q0.x) >= 0 && (__float_as_int(q2.w) & 2) == 0;
+    const bool flip = (__float_as_int(q2.w) & 1) != 0;
+    /* (a lane that is not live: a harmless segment, as batch_ray()'s) */
+    const V3 P = live ? mk(q0.z, q0.w, q1.x) : mk(0.0f, 0.0f, 0.0f);
+    const V3 N = live ? (flip ? mk(-q1.y, -q1.z, -q1.w) : mk(q1.y, q1.z, q1.w)) : mk(0.0f, 0.0f, 1.0f);
+    const int n = __builtin_amdgcn_readfirstlane(ao.samples);
+    int open = 0;
+    if (wave_any(live)) {
+        V3 lo, hi, c_o, e_o;
+        wave_bounds3(P, live, &lo, &hi);
+        shading_point_bundle(lo, hi, &c_o, &e_o);
+        const uint32_t g = lowbias32(lowbias32(seed ^ 0x9e3779b9u) ^ (ao.key0 + rec));
+        const float step = 2.0f / (float)n;
+        for (int i = 0; i < n; ++i) {
+            for (int j = 0; j < n; ++j) {
+                const uint32_t hs = lowbias32(g ^ (uint32_t)(i * n + j));
+                const float xi1 = (float)(hs >> 8) * 0x1p-24f;
+                const float xi2 = (float)(lowbias32(hs ^ 0x9e3779b9u) >> 8) * 0x1p-24f;
+                const float a = ((float)i + xi1) * step - 1.0f, b = ((float)j + xi2) * step - 1.0f;
+                const float dx = a * sqrtf(1.0f - (b * b) * 0.5f), dy = b * sqrtf(1.0f - (a * a) * 0.5f);
+                const float w = (1.0f - dx * dx) - dy * dy;
+                const float dz = w > 0.0f ? sqrtf(w) : 0.0f;
+                const V3 A = fabsf(N.x) < 0.5f ? mk(1.0f, 0.0f, 0.0f) : mk(0.0f, 1.0f, 0.0f);
+                const V3 U = normalize3(cross3(A, N));
+                const V3 V = cross3(N, U);
+                const V3 D = add3(add3(scale3(U, dx), scale3(V, dy)), scale3(N, dz));
+                const V3 Q = add3(P, scale3(D, ao.radius));
+                float dist;                                          /* |Q - P| */
+                const V3 d = normalize3(sub3(Q, P), &dist);
+                V3 c_e, e_e;
+                wave_bounds3(Q, live, &lo, &hi);
+                shading_point_bundle(lo, hi, &c_e, &e_e);
+                const V3 e = mk(uniform_f((e_o.x + e_e.x) * 1.000001f), uniform_f((e_o.y + e_e.y) * 1.000001f),
+                                uniform_f((e_o.z + e_e.z) * 1.000001f));
+                bool blocked;
+                if constexpr (kMode == 6) blocked = in_shade_fast<false>(p, lds, ctl_words, live, P, d, dist, c_e, c_o, e, false, 0ull, st);
+                else blocked = in_shade<false, kMode>(p, lds, wlds, nullptr, live, P, d, dist, c_e, c_o, e, ~0ull, st);
+                open += blocked ? 0 : 1;
+            }
+        }
+    }
+    query_next_tile(next_pop, ask_head);
+    if (inside) {
+        const float value = live ? (float)open / (float)(n * n) : 1.0f;
+        if (ao.channels == 3) {
+            float *dst = out + (size_t)rec * 3;
+            dst[0] = value; dst[1] = value; dst[2] = value;
+        } else {
+            out[rec] = value;
+        }
+    }
+}
+
 /* which of the tile queues still have tiles to hand out (bit q: queue q).  Its own function, called once per exhausted
  * queue */
 #ifndef RT_SCAN_INLINE
@@ -3240,7 +3316,8 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
                                             float *__restrict__ out, unsigned int *__restrict__ tile_counter,
                                             float4 *__restrict__ bounce_stack,
                                             unsigned long long *__restrict__ stats_out,
-                                            unsigned int *__restrict__ help_area, const uint32_t shadow_seed = 0u) {
+                                            unsigned int *__restrict__ help_area, const uint32_t shadow_seed = 0u,
+                                            const RtAoArgs ao = RtAoArgs{}) {
     extern __shared__ float4 wlds[];                          /* LDS: the tables, the low levels of the bounce stack, the HELP desk */
     Stats<kStats> st;
     if constexpr (kStats) {
@@ -3459,6 +3536,7 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
         constexpr int kMode = kFast ? 6 : (kClusters ? (kRoomy ? 5 : 4) : 0);
         if constexpr (kQuery == RT_QUERY_HITS) hits_tile<kMode, kImages>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
         else if constexpr (kQuery == RT_QUERY_OCCLUDED) occluded_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head);
+        else if constexpr (kQuery == RT_QUERY_AO) ao_tile<kMode>(p, lds, wlds, ctl_words, out, wave, next_pop, ask_head, shadow_seed, ao);
         else if constexpr (kTwin) render_tile_twin(p, lds, wlds, ctl_words, out, bounce_stack, wave, next_pop);
         else render_tile<kStats, kMode, kSsaa, kRays, kGbuffer, kImages, kRefract, kSoft>(p, lds, wlds, help_rays, ctl_words, out, bounce_stack, stats_out, st, wave,
                                                                 my_xcc, steal, next_pop, ask_head, shadow_seed);
@@ -3543,7 +3621,22 @@ __device__ __forceinline__ void render_body(const RtParams &p, const float4 *__r
 #define RT_UNIT(unit) RT_UNIT_OF(unit)
 #define RT_UNIT_OF(unit) RT_UNIT_##unit
 
-#ifdef RT_KERNEL_TU
+/* AMBIENT OCCLUSION (rt_tables.h, AUXILIARY KERNELS): with -DRT_KERNEL_AUX_TU=ao this file is the unit rt_kernel_ao.o -- the
+ * same definition named rt_ao_kernel<mode>, with RT_AO_PARAMS behind the seed */
+#define RT_DEFINE_AO_KERNEL(mode, global_tables, clusters, roomy, fast, block_bound, waves, waves_soft,                        \
+                            family, ssaa, rays, query, gbuffer, images, refract, soft, seeded)                                 \
+    extern "C" __global__ void __launch_bounds__(block_bound, waves)                                                           \
+    rt_ao_kernel##mode##family(RT_KERNEL_ARGS RT_SEED_PARAM_##seeded RT_AO_PARAMS) {                                           \
+        RT_PARAMS_FROM_KERNARG(p, p_in_kernarg);                                                                               \
+        render_body<false, global_tables, clusters, roomy, fast, ssaa, rays, query, gbuffer, images, refract, soft>(            \
+            p, image, out, tile_counter, bounce_stack, nullptr, help_area, RT_SEED_ARG_##seeded,                               \
+            RtAoArgs{ao_samples, ao_radius, ao_key0, ao_channels});                                                            \
+    }
+#define RT_DEFINE_AO_FAMILY(...) RT_TABLE_MODES(RT_DEFINE_AO_KERNEL, __VA_ARGS__)
+
+#if defined(RT_KERNEL_AUX_TU)
+RT_AUX_UNIT_ao(RT_DEFINE_AO_FAMILY)
+#elif defined(RT_KERNEL_TU)
 RT_UNIT(RT_KERNEL_TU)(RT_DEFINE_FAMILY)
 #else
 RT_UNIT_base(RT_DEFINE_FAMILY)

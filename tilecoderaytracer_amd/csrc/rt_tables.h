@@ -259,7 +259,7 @@ typedef struct RtParams {
 /* RAY QUERIES (include/rt_capi_query.h): what a ray-batch launch computes -- colours (rt_trace_rays), the *_hits kernels'
  * 48-byte records or the *_occluded kernels' one-byte verdicts.  A template argument of the kernels and the host's choice of
  * sibling, not an RtParams field. */
-enum { RT_QUERY_NONE = 0, RT_QUERY_HITS = 1, RT_QUERY_OCCLUDED = 2 };
+enum { RT_QUERY_NONE = 0, RT_QUERY_HITS = 1, RT_QUERY_OCCLUDED = 2, RT_QUERY_AO = 3 };
 #define RT_HIT_BYTES 48
 
 /* FAST tables.  Scenes without clustered sphere runs (the reference's built-in Scene: 32 objects) are walked
@@ -376,5 +376,16 @@ enum { RT_QUERY_NONE = 0, RT_QUERY_HITS = 1, RT_QUERY_OCCLUDED = 2 };
     unsigned long long *__restrict__ stats_out, unsigned int *__restrict__ help_area
 #define RT_SEED_PARAM_false
 #define RT_SEED_PARAM_true , const uint32_t shadow_seed
+
+/* AUXILIARY KERNELS: kernels that are the same body over the same tables in the five table modes, but no render kernels -- they
+ * are not rt_render_kernel<mode><family>, not in RT_RENDER_FAMILIES, and their list is RT_AUX_UNIT_<unit> (the render families'
+ * columns): rt_kernel_<unit>.o is built with -DRT_KERNEL_AUX_TU=<unit>.  There is one:
+ *   ao   include/rt_capi_ao.h: AMBIENT OCCLUSION, rt_ao_kernel<mode> -- a query over a batch of rt_hit RECORDS instead of rays
+ *        (RtParams::rays is the records' address, n_rays their number): n x n hemisphere segments of length R per record, each
+ *        one the occlusion query's scan.  n, R, key0 and the output's channels are kernel arguments of these kernels only
+ *        (RT_AO_PARAMS, handed to render_body() as an RtAoArgs); the seed travels as RT_SEED_PARAM_true does. */
+typedef struct RtAoArgs { int32_t samples; float radius; uint32_t key0; int32_t channels; } RtAoArgs;
+#define RT_AUX_UNIT_ao(X)   X(,                      false, true,  RT_QUERY_AO,       false, false, false, false, true)
+#define RT_AO_PARAMS , const int32_t ao_samples, const float ao_radius, const uint32_t ao_key0, const int32_t ao_channels
 
 #endif /* RT_TABLES_H_ */

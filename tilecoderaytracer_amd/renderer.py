@@ -304,6 +304,56 @@ class Renderer:
         capi.check(self._lib.rt_occluded_rays_device(self._scene, n, rows, C.c_void_p(segs_ptr), C.c_void_p(out_ptr),
                                                      C.c_void_p(stream)))
 
+    @staticmethod
+    def _ao_params(samples, radius, seed, key0, channels):
+        return capi.RtAoParams(int(samples), float(radius), int(seed) & 0xFFFFFFFF, int(key0) & 0xFFFFFFFF, int(channels))
+
+    def ambient_occlusion(self, hits, samples=4, radius=1.0, seed=0, key0=0, channels=1, rows=None):
+        """The open fraction of samples x samples hemisphere directions of length radius around each hit record
+        (include/rt_capi_ao.h, rt_ambient_occlusion).  hits: C-contiguous HIT_DTYPE, (n,) -- rows defaults to n -- or (X, Z),
+        rows = Z, as render_gbuffer() and intersect_rays() return them; record i samples with key0 + i (a strip of a W x H
+        frame from column x0: key0 = x0 * H).  -> float32 of hits' shape, or with channels = 3 of that shape + (3,), the
+        three equal.  rows only shapes the launch; the results do not depend on it."""
+        if not isinstance(hits, np.ndarray) or hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous:
+            raise TypeError("hits must be a C-contiguous numpy array of HIT_DTYPE")
+        if hits.ndim not in (1, 2):
+            raise ValueError(f"hits must have shape (n,) or (X, Z), not {hits.shape}")
+        n = hits.size
+        default_rows = max(hits.shape[1] if hits.ndim == 2 else n, 1)
+        params = self._ao_params(samples, radius, seed, key0, channels)
+        out = np.empty(hits.shape + ((3,) if params.channels == 3 else ()), dtype=np.float32)
+        capi.check(self._lib.rt_ambient_occlusion(self._scene, C.byref(params), n, int(default_rows if rows is None else rows),
+                                                  hits.ctypes.data, out.ctypes.data))
+        return out
+
+    def ambient_occlusion_device(self, n, rows, hits_ptr, out_ptr, samples=4, radius=1.0, seed=0, key0=0, channels=1, stream=0):
+        """Enqueue the ambient occlusion of n records (48 bytes each, hits_ptr 16-byte aligned) into n * channels float32 at
+        out_ptr on a HIP stream (no sync; hits_ptr must stay valid until the stream has drained)."""
+        params = self._ao_params(samples, radius, seed, key0, channels)
+        capi.check(self._lib.rt_ambient_occlusion_device(self._scene, C.byref(params), n, rows, C.c_void_p(hits_ptr),
+                                                         C.c_void_p(out_ptr), C.c_void_p(stream)))
+
+    def render_ao(self, W, H, samples=4, radius=1.0, seed=0, channels=1):
+        """The ambient-occlusion plane of a W x H frame, computed on the GPU where its records were made: a depth-0
+        rt_render_gbuffer_device and rt_ambient_occlusion_device (rows = H) enqueued on one stream with no host wait between
+        them, then a download of the plane alone -> float32 (W, H), or (W, H, 3) with channels = 3 (a grey frame for denoise()
+        and encode_image()).  The result is ambient_occlusion(render_gbuffer(W, H, 0)[1], ...) bit for bit.  The device buffers
+        and the stream are torch's, so the process must have imported torch before the library was loaded (INTEGRATION.md
+        section 3)."""
+        import torch
+        params = self._ao_params(samples, radius, seed, 0, channels)
+        C_ = 3 if params.channels == 3 else 1                        # (a bad count is refused by the call below)
+        with torch.cuda.device(int(self._device)):
+            colours = torch.empty((W, H, 3), dtype=torch.float32, device="cuda")
+            records = torch.empty((W * H * 12,), dtype=torch.int32, device="cuda")
+            plane = torch.empty((W, H, C_), dtype=torch.float32, device="cuda")
+            stream = torch.cuda.current_stream()
+            self.render_gbuffer_device(W, H, 0, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
+            capi.check(self._lib.rt_ambient_occlusion_device(self._scene, C.byref(params), W * H, H, records.data_ptr(),
+                                                             plane.data_ptr(), stream.cuda_stream))
+            out = plane.cpu().numpy()                                 # the one download
+        return out if C_ == 3 else out.reshape(W, H)
+
     STAT_NAMES = ("nearest_rays", "shadow_rays", "wave_nearest_scans", "wave_shadow_scans",
                   "wave_sphere_tests", "wave_plane_tests", "wave_box_tests", "lane_sphere_tests",
                   "cycles_nearest", "cycles_shadow", "cycles_tile",
