@@ -615,15 +615,13 @@ __device__ __forceinline__ V3 approx_inverse(const V3 d) {
 }
 
 /* Wavefront-wide reductions with DPP (no LDS traffic).
- * Box of a per-lane point over the lanes with `use` set: three minima and three
- * maxima reduced side by side (the six chains fill each other's DPP wait
+ * Box of per-lane ranges [vlo, vhi] (a lane without a value: [+inf, -inf]): three minima
+ * and three maxima reduced side by side (the six chains fill each other's DPP wait
  * states): four butterfly steps inside each row of 16 lanes, then row_bcast
  * 15 / 31 fold the rows so that lane 63 holds the result.  All 64 lanes must be
  * active.  v_min/v_max ignore a NaN operand, like fminf/fmaxf. */
-__device__ __forceinline__ void wave_bounds3(const V3 v, const bool use, V3 *lo, V3 *hi) {
-    const float inf = __builtin_huge_valf();
-    float a = use ? v.x : inf, b = use ? v.y : inf, c = use ? v.z : inf;
-    float d = use ? v.x : -inf, e = use ? v.y : -inf, f = use ? v.z : -inf;
+__device__ __forceinline__ void wave_bounds3_range(const V3 vlo, const V3 vhi, V3 *lo, V3 *hi) {
+    float a = vlo.x, b = vlo.y, c = vlo.z, d = vhi.x, e = vhi.y, f = vhi.z;
 #define RT_DPP_STEP(ctrl)                                                                              \
     "v_min_f32_dpp %0, %0, %0 " ctrl "\n v_min_f32_dpp %1, %1, %1 " ctrl "\n v_min_f32_dpp %2, %2, %2 " ctrl "\n" \
     "v_max_f32_dpp %3, %3, %3 " ctrl "\n v_max_f32_dpp %4, %4, %4 " ctrl "\n v_max_f32_dpp %5, %5, %5 " ctrl "\n"
@@ -643,6 +641,12 @@ __device__ __forceinline__ void wave_bounds3(const V3 v, const bool use, V3 *lo,
     *hi = mk(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(d), 63)),
              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), 63)),
              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f), 63)));
+}
+
+/* ... of a per-lane point over the lanes with `use` set */
+__device__ __forceinline__ void wave_bounds3(const V3 v, const bool use, V3 *lo, V3 *hi) {
+    const float inf = __builtin_huge_valf();
+    wave_bounds3_range(mk(use ? v.x : inf, use ? v.y : inf, use ? v.z : inf), mk(use ? v.x : -inf, use ? v.y : -inf, use ? v.z : -inf), lo, hi);
 }
 
 /* Wavefront-wide minimum of an unsigned key (all 64 lanes active), same DPP
@@ -1543,6 +1547,57 @@ __device__ __forceinline__ float fast_item_distance(const RtParams &p, const flo
     }
 }
 
+/* The candidate key of a FAST nearest-hit scan, this lane's item against the PRIMARY table (rt_tables.h): the host has
+ * projected every item's box to the rectangle of pixels whose ray can reach it, with the distance it is at least away; the lane
+ * compares its item's rectangle with that of `tile_rows` (1; a twin: 2) vertically adjacent tiles from (tile_x0, tile_z0). */
+__device__ __forceinline__ uint32_t fast_primary_key(const RtParams &p, const float4 *lds, const int lane, const int n_items,
+                                                     const int tile_x0, const int tile_z0, const int tile_rows) {
+    const uint4 rect = reinterpret_cast<const uint4 *>(lds)[p.primary_off + min(lane, n_items - 1)];
+    const int x_lo = (int)(short)(rect.x & 0xFFFFu), x_hi = (int)rect.x >> 16;
+    const int z_lo = (int)(short)(rect.y & 0xFFFFu), z_hi = (int)rect.y >> 16;
+    const int tile_x1 = tile_x0 + (64 >> p.tile_z_log2) - 1, tile_z1 = tile_z0 + (tile_rows << p.tile_z_log2) - 1;
+    const bool candidate = lane < n_items && x_lo <= tile_x1 && x_hi >= tile_x0 && z_lo <= tile_z1 && z_hi >= tile_z0;
+    return candidate ? ((rect.z & ~63u) | (uint32_t)lane) : 0xFFFFFFFFu;
+}
+
+/* The same key from the bundle cull, for item base + lane of n_items: the item's box (b0: its centre, b1: its half-extent)
+ * against the box [olo, ohi] of the rays' origins and the multipliers of their directions' bounds, per axis (bound_multipliers()) */
+struct AxisBounds { float la, ha, lb, hb; };
+__device__ __forceinline__ uint32_t fast_bundle_key(const float4 b0, const float4 b1, const V3 olo, const V3 ohi,
+                                                    const AxisBounds mx, const AxisBounds my, const AxisBounds mz,
+                                                    const int lane, const int base, const int n_items) {
+    float ax = (b0.x - b1.x) - ohi.x, bx = (b0.x + b1.x) - olo.x;
+    float ay = (b0.y - b1.y) - ohi.y, by = (b0.y + b1.y) - olo.y;
+    float az = (b0.z - b1.z) - ohi.z, bz = (b0.z + b1.z) - olo.z;
+    float ex, ey, ez;
+    RT_CULL_SLACK(__float_as_uint(b0.w), fmaxf(fabsf(ax), fabsf(bx)), fmaxf(fabsf(ay), fabsf(by)), fmaxf(fabsf(az), fabsf(bz)), ex, ey, ez);
+    ax -= ex; ay -= ey; az -= ez; bx += ex; by += ey; bz += ez;
+    const float t_lo = fmaxf(fmaxf(fmaxf(0.0f, fmaxf(bx * mx.la, ax * mx.lb)), fmaxf(by * my.la, ay * my.lb)), fmaxf(bz * mz.la, az * mz.lb));
+    const float t_hi = fminf(fminf(fminf(65600.0f, fminf(bx * mx.ha, ax * mx.hb)), fminf(by * my.ha, ay * my.hb)), fminf(bz * mz.ha, az * mz.hb));
+    /* the entry distance less the tolerance of this arithmetic: what `best` is compared with in the scan.
+     * 0 (also: anything that rounds to it) = the origin box meets the item's box: always tested, see nearest_hit_items() */
+    const float entry = fmaxf(t_lo - 1.0e-4f * t_lo - 1.0e-6f, 0.0f);
+    const bool empty = (entry > t_hi + 1.0e-4f * fabsf(t_hi)) || (t_hi < -1.0e-6f);
+    const bool candidate = base + lane < n_items && !empty;
+    return candidate ? ((__float_as_uint(entry) & ~63u) | (uint32_t)lane) : 0xFFFFFFFFu;
+}
+
+/* The slab test of a FAST shadow scan: true where the item's box (b0: its centre, b1: its half-extent), grown by `e` -- the
+ * bundle's half-extent with the slack of a plane item (RT_ITEM_TIGHT); sphere-like items add grow_more -- lies apart from the
+ * segment from the bundle's centre c towards the light (sinv: the reciprocals of its components): the slab of axis k is
+ * (centre - c) / seg -+ (half + grown) / |seg| */
+__device__ __forceinline__ bool fast_shadow_apart(const float4 b0, const float4 b1, const V3 c, const V3 sinv, const V3 e,
+                                                  const float grow_more) {
+    const float more = (__float_as_uint(b0.w) & RT_ITEM_TIGHT) != 0u ? 0.0f : grow_more;
+    const float gx = e.x + more, gy = e.y + more, gz = e.z + more;
+    const float tcx = (b0.x - c.x) * sinv.x, tcy = (b0.y - c.y) * sinv.y, tcz = (b0.z - c.z) * sinv.z;
+    const float tgx = (b1.x + gx) * fabsf(sinv.x), tgy = (b1.y + gy) * fabsf(sinv.y), tgz = (b1.z + gz) * fabsf(sinv.z);
+    const float s_enter = fmaxf(fmaxf(tcx - tgx, tcy - tgy), tcz - tgz);
+    const float s_exit = fminf(fminf(tcx + tgx, tcy + tgy), tcz + tgz);
+    /* every comparison is false on a NaN, which then means "candidate" */
+    return (s_exit < s_enter - 1.0e-4f * (fabsf(s_enter) + fabsf(s_exit)) - 1.0e-6f) || (s_exit < -1.0e-4f) || (s_enter > 1.0001f);
+}
+
 /* getCollision (src/RayTracer.cpp:50-89) over the FAST item list; the cull and the nearest-first order are
  * nearest_hit_items()'s (see there for why they are exact), written for few instructions per scan: the cull always
  * runs (a bundle whose directions point everywhere gets no bound from it: every item a candidate with entry
@@ -1564,48 +1619,27 @@ __device__ __forceinline__ void nearest_hit_fast(const RtParams &p, const float4
     const float4 *recs = lds + p.fast_rec_off;
     const unsigned long long active_mask = __builtin_amdgcn_ballot_w64(active);
 
-    /* The camera rays of a tile (level 0) with a PRIMARY table (rt_tables.h): the host has projected every item's box to the
-     * rectangle of pixels whose ray can reach it, with the distance it is at least away; lane i compares item i's rectangle
-     * with the tile's -- no bundle, no reciprocals, no box arithmetic.  Every other scan: the bundle cull. */
+    /* The camera rays of a tile (level 0) with a PRIMARY table: lane i compares item i's rectangle with the tile's -- no bundle,
+     * no reciprocals, no box arithmetic.  Every other scan: the bundle cull. */
     const bool by_pixels = camera_rays && p.n_primary > 0;
     V3 dlo = d, dhi = d, olo = origins_lo, ohi = origins_hi;
-    float lax = 0, hax = 0, lbx = 0, hbx = 0, lay = 0, hay = 0, lby = 0, hby = 0, laz = 0, haz = 0, lbz = 0, hbz = 0;
+    AxisBounds mx = {0, 0, 0, 0}, my = {0, 0, 0, 0}, mz = {0, 0, 0, 0};
     if (!by_pixels) {
         wave_bounds3(d, active, &dlo, &dhi);
         if (!have_origin_box) wave_bounds3(o, active, &olo, &ohi);      /* the eye for primary rays, else the previous level's shading points */
-        bound_multipliers(dlo.x, dhi.x, &lax, &hax, &lbx, &hbx);
-        bound_multipliers(dlo.y, dhi.y, &lay, &hay, &lby, &hby);
-        bound_multipliers(dlo.z, dhi.z, &laz, &haz, &lbz, &hbz);
+        bound_multipliers(dlo.x, dhi.x, &mx.la, &mx.ha, &mx.lb, &mx.hb);
+        bound_multipliers(dlo.y, dhi.y, &my.la, &my.ha, &my.lb, &my.hb);
+        bound_multipliers(dlo.z, dhi.z, &mz.la, &mz.ha, &mz.lb, &mz.hb);
     }
     const bool finite_rays = (__builtin_amdgcn_ballot_w64(!ray_is_finite(o, d)) & active_mask) == 0ull;
 
     for (int base = 0; base < n_items; base += 64) {
         uint32_t key;                      /* this lane's item: tolerant bundle entry distance (high bits) | lane */
         if (by_pixels) {                   /* n_items <= 64: one round */
-            const uint4 rect = reinterpret_cast<const uint4 *>(lds)[p.primary_off + min(lane, n_items - 1)];
-            const int x_lo = (int)(short)(rect.x & 0xFFFFu), x_hi = (int)rect.x >> 16;
-            const int z_lo = (int)(short)(rect.y & 0xFFFFu), z_hi = (int)rect.y >> 16;
-            const int tile_x1 = tile_x0 + (64 >> p.tile_z_log2) - 1, tile_z1 = tile_z0 + (1 << p.tile_z_log2) - 1;
-            const bool candidate = lane < n_items && x_lo <= tile_x1 && x_hi >= tile_x0 && z_lo <= tile_z1 && z_hi >= tile_z0;
-            key = candidate ? ((rect.z & ~63u) | (uint32_t)lane) : 0xFFFFFFFFu;
+            key = fast_primary_key(p, lds, lane, n_items, tile_x0, tile_z0, 1);
         } else {
             const int mine = min(base + lane, n_items - 1);
-            const float4 b0 = boxes[2 * mine], b1 = boxes[2 * mine + 1];
-            /* (b0: the box's centre, b1: its half-extent) */
-            float ax = (b0.x - b1.x) - ohi.x, bx = (b0.x + b1.x) - olo.x;
-            float ay = (b0.y - b1.y) - ohi.y, by = (b0.y + b1.y) - olo.y;
-            float az = (b0.z - b1.z) - ohi.z, bz = (b0.z + b1.z) - olo.z;
-            float ex, ey, ez;
-            RT_CULL_SLACK(__float_as_uint(b0.w), fmaxf(fabsf(ax), fabsf(bx)), fmaxf(fabsf(ay), fabsf(by)), fmaxf(fabsf(az), fabsf(bz)), ex, ey, ez);
-            ax -= ex; ay -= ey; az -= ez; bx += ex; by += ey; bz += ez;
-            const float t_lo = fmaxf(fmaxf(fmaxf(0.0f, fmaxf(bx * lax, ax * lbx)), fmaxf(by * lay, ay * lby)), fmaxf(bz * laz, az * lbz));
-            const float t_hi = fminf(fminf(fminf(65600.0f, fminf(bx * hax, ax * hbx)), fminf(by * hay, ay * hby)), fminf(bz * haz, az * hbz));
-            /* the entry distance less the tolerance of this arithmetic: what `best` is compared with below.
-             * 0 (also: anything that rounds to it) = the origin box meets the item's box: always tested, see nearest_hit_items() */
-            const float entry = fmaxf(t_lo - 1.0e-4f * t_lo - 1.0e-6f, 0.0f);
-            const bool empty = (entry > t_hi + 1.0e-4f * fabsf(t_hi)) || (t_hi < -1.0e-6f);
-            const bool candidate = base + lane < n_items && !empty;
-            key = candidate ? ((__float_as_uint(entry) & ~63u) | (uint32_t)lane) : 0xFFFFFFFFu;
+            key = fast_bundle_key(boxes[2 * mine], boxes[2 * mine + 1], olo, ohi, mx, my, mz, lane, base, n_items);
         }
         for (;;) {
             const uint32_t nearest_key = wave_min_u32(key);
@@ -1666,25 +1700,14 @@ __device__ __forceinline__ bool in_shade_fast(const RtParams &p, const float4 *l
     const V3 seg = sub3(light, c);
     V3 sinv = approx_inverse(seg);
     const float reach = (fabsf(seg.x) + fabsf(seg.y) + fabsf(seg.z)) + (origins_half.x + origins_half.y + origins_half.z);
-    /* the same in every lane: keep them in scalar registers.  `e` carries the slack of a plane item
-     * (RT_ITEM_TIGHT); sphere-like items add `grow_more` */
+    /* the same in every lane: keep them in scalar registers (fast_shadow_apart()'s e and grow_more) */
     const float grow_more = uniform_f((RT_SPHERE_SLACK - RT_PLANE_SLACK) * reach);
     const float grow = RT_PLANE_SLACK * reach + 1.0e-4f;
     const V3 e = mk(uniform_f(origins_half.x + grow), uniform_f(origins_half.y + grow), uniform_f(origins_half.z + grow));
     sinv = mk(uniform_f(sinv.x), uniform_f(sinv.y), uniform_f(sinv.z));
     for (int base = 0; base < n_items; base += 64) {
         const int mine = min(base + lane, n_items - 1);
-        const float4 b0 = boxes[2 * mine], b1 = boxes[2 * mine + 1];
-        const float more = (__float_as_uint(b0.w) & RT_ITEM_TIGHT) != 0u ? 0.0f : grow_more;
-        const float gx = e.x + more, gy = e.y + more, gz = e.z + more;
-        /* b0: the item box's centre, b1: its half-extent: the slab of axis k is (centre - c) / seg -+ (half + grown) / |seg| */
-        const float tcx = (b0.x - c.x) * sinv.x, tcy = (b0.y - c.y) * sinv.y, tcz = (b0.z - c.z) * sinv.z;
-        const float tgx = (b1.x + gx) * fabsf(sinv.x), tgy = (b1.y + gy) * fabsf(sinv.y), tgz = (b1.z + gz) * fabsf(sinv.z);
-        const float s_enter = fmaxf(fmaxf(tcx - tgx, tcy - tgy), tcz - tgz);
-        const float s_exit = fminf(fminf(tcx + tgx, tcy + tgy), tcz + tgz);
-        /* every comparison is false on a NaN, which then means "candidate" */
-        const bool apart = (s_exit < s_enter - 1.0e-4f * (fabsf(s_enter) + fabsf(s_exit)) - 1.0e-6f) ||
-                           (s_exit < -1.0e-4f) || (s_enter > 1.0001f);
+        const bool apart = fast_shadow_apart(boxes[2 * mine], boxes[2 * mine + 1], c, sinv, e, grow_more);
         if (test_candidates(__builtin_amdgcn_ballot_w64(base + lane < n_items && !apart), base)) return true;
     }
     return nearest_block < dist_to_light;
@@ -1697,30 +1720,6 @@ __device__ __forceinline__ bool in_shade_fast(const RtParams &p, const float4 *l
  * ray, the two side by side.  The bundle is the one around both tiles' rays: a superset of either tile's own, so the culls only
  * widen, which is exact by nearest_hit_items()'s argument (a candidate more is tested and found no nearer, or not blocking),
  * and every ray sees the arithmetic of nearest_hit_fast() / in_shade_fast() on its own operands. */
-
-/* wave_bounds3() of a per-lane range [vlo, vhi] (a lane without a value: [+inf, -inf]) */
-__device__ __forceinline__ void wave_bounds3_range(const V3 vlo, const V3 vhi, V3 *lo, V3 *hi) {
-    float a = vlo.x, b = vlo.y, c = vlo.z, d = vhi.x, e = vhi.y, f = vhi.z;
-#define RT_DPP_STEP(ctrl)                                                                              \
-    "v_min_f32_dpp %0, %0, %0 " ctrl "\n v_min_f32_dpp %1, %1, %1 " ctrl "\n v_min_f32_dpp %2, %2, %2 " ctrl "\n" \
-    "v_max_f32_dpp %3, %3, %3 " ctrl "\n v_max_f32_dpp %4, %4, %4 " ctrl "\n v_max_f32_dpp %5, %5, %5 " ctrl "\n"
-    asm volatile("s_nop 1\n"
-                 RT_DPP_STEP("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
-                 RT_DPP_STEP("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
-                 RT_DPP_STEP("row_half_mirror row_mask:0xf bank_mask:0xf")
-                 RT_DPP_STEP("row_mirror row_mask:0xf bank_mask:0xf")
-                 RT_DPP_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf")
-                 RT_DPP_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf")
-                 "s_nop 1\n"
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
-#undef RT_DPP_STEP
-    *lo = mk(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 63)),
-             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b), 63)),
-             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), 63)));
-    *hi = mk(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(d), 63)),
-             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), 63)),
-             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f), 63)));
-}
 
 /* the box of two per-lane points over the lanes' rays in use: each lane's own minimum and maximum first (v_min / v_max skip a
  * NaN, as the reduction does), then ONE reduction */
@@ -1831,39 +1830,22 @@ __device__ __forceinline__ void nearest_hit_fast_twin(const RtParams &p, const f
     const bool by_pixels = camera_rays && p.n_primary > 0;
     V3 dlo = d0, dhi = d0;
     const V3 olo = origins_lo, ohi = origins_hi;
-    float lax = 0, hax = 0, lbx = 0, hbx = 0, lay = 0, hay = 0, lby = 0, hby = 0, laz = 0, haz = 0, lbz = 0, hbz = 0;
+    AxisBounds mx = {0, 0, 0, 0}, my = {0, 0, 0, 0}, mz = {0, 0, 0, 0};
     if (!by_pixels) {
         wave_bounds3_twin(d0, active0, d1, active1, &dlo, &dhi);
-        bound_multipliers(dlo.x, dhi.x, &lax, &hax, &lbx, &hbx);
-        bound_multipliers(dlo.y, dhi.y, &lay, &hay, &lby, &hby);
-        bound_multipliers(dlo.z, dhi.z, &laz, &haz, &lbz, &hbz);
+        bound_multipliers(dlo.x, dhi.x, &mx.la, &mx.ha, &mx.lb, &mx.hb);
+        bound_multipliers(dlo.y, dhi.y, &my.la, &my.ha, &my.lb, &my.hb);
+        bound_multipliers(dlo.z, dhi.z, &mz.la, &mz.ha, &mz.lb, &mz.hb);
     }
     const bool finite_rays = !wave_any((active0 && !ray_is_finite(o0, d0)) || (active1 && !ray_is_finite(o1, d1)));
 
     for (int base = 0; base < n_items; base += 64) {
         uint32_t key;                      /* this lane's item: tolerant bundle entry distance (high bits) | lane */
         if (by_pixels) {                   /* n_items <= 64: one round */
-            const uint4 rect = reinterpret_cast<const uint4 *>(lds)[p.primary_off + min(lane, n_items - 1)];
-            const int x_lo = (int)(short)(rect.x & 0xFFFFu), x_hi = (int)rect.x >> 16;
-            const int z_lo = (int)(short)(rect.y & 0xFFFFu), z_hi = (int)rect.y >> 16;
-            const int tile_x1 = tile_x0 + (64 >> p.tile_z_log2) - 1, tile_z1 = tile_z0 + (2 << p.tile_z_log2) - 1;
-            const bool candidate = lane < n_items && x_lo <= tile_x1 && x_hi >= tile_x0 && z_lo <= tile_z1 && z_hi >= tile_z0;
-            key = candidate ? ((rect.z & ~63u) | (uint32_t)lane) : 0xFFFFFFFFu;
+            key = fast_primary_key(p, lds, lane, n_items, tile_x0, tile_z0, 2);
         } else {
             const int mine = min(base + lane, n_items - 1);
-            const float4 b0 = boxes[2 * mine], b1 = boxes[2 * mine + 1];
-            float ax = (b0.x - b1.x) - ohi.x, bx = (b0.x + b1.x) - olo.x;
-            float ay = (b0.y - b1.y) - ohi.y, by = (b0.y + b1.y) - olo.y;
-            float az = (b0.z - b1.z) - ohi.z, bz = (b0.z + b1.z) - olo.z;
-            float ex, ey, ez;
-            RT_CULL_SLACK(__float_as_uint(b0.w), fmaxf(fabsf(ax), fabsf(bx)), fmaxf(fabsf(ay), fabsf(by)), fmaxf(fabsf(az), fabsf(bz)), ex, ey, ez);
-            ax -= ex; ay -= ey; az -= ez; bx += ex; by += ey; bz += ez;
-            const float t_lo = fmaxf(fmaxf(fmaxf(0.0f, fmaxf(bx * lax, ax * lbx)), fmaxf(by * lay, ay * lby)), fmaxf(bz * laz, az * lbz));
-            const float t_hi = fminf(fminf(fminf(65600.0f, fminf(bx * hax, ax * hbx)), fminf(by * hay, ay * hby)), fminf(bz * haz, az * hbz));
-            const float entry = fmaxf(t_lo - 1.0e-4f * t_lo - 1.0e-6f, 0.0f);
-            const bool empty = (entry > t_hi + 1.0e-4f * fabsf(t_hi)) || (t_hi < -1.0e-6f);
-            const bool candidate = base + lane < n_items && !empty;
-            key = candidate ? ((__float_as_uint(entry) & ~63u) | (uint32_t)lane) : 0xFFFFFFFFu;
+            key = fast_bundle_key(boxes[2 * mine], boxes[2 * mine + 1], olo, ohi, mx, my, mz, lane, base, n_items);
         }
         for (;;) {
             const uint32_t nearest_key = wave_min_u32(key);
@@ -1933,16 +1915,7 @@ __device__ __forceinline__ void in_shade_fast_twin(const RtParams &p, const floa
         sinv = mk(uniform_f(sinv.x), uniform_f(sinv.y), uniform_f(sinv.z));
         for (int base = 0; base < n_items && !all_blocked; base += 64) {
             const int mine = min(base + lane, n_items - 1);
-            const float4 b0 = boxes[2 * mine], b1 = boxes[2 * mine + 1];
-            const float more = (__float_as_uint(b0.w) & RT_ITEM_TIGHT) != 0u ? 0.0f : grow_more;
-            const float gx = e.x + more, gy = e.y + more, gz = e.z + more;
-            const float tcx = (b0.x - c.x) * sinv.x, tcy = (b0.y - c.y) * sinv.y, tcz = (b0.z - c.z) * sinv.z;
-            const float tgx = (b1.x + gx) * fabsf(sinv.x), tgy = (b1.y + gy) * fabsf(sinv.y), tgz = (b1.z + gz) * fabsf(sinv.z);
-            const float s_enter = fmaxf(fmaxf(tcx - tgx, tcy - tgy), tcz - tgz);
-            const float s_exit = fminf(fminf(tcx + tgx, tcy + tgy), tcz + tgz);
-            /* every comparison is false on a NaN, which then means "candidate" */
-            const bool apart = (s_exit < s_enter - 1.0e-4f * (fabsf(s_enter) + fabsf(s_exit)) - 1.0e-6f) ||
-                               (s_exit < -1.0e-4f) || (s_enter > 1.0001f);
+            const bool apart = fast_shadow_apart(boxes[2 * mine], boxes[2 * mine + 1], c, sinv, e, grow_more);
             all_blocked = test_candidates(__builtin_amdgcn_ballot_w64(base + lane < n_items && !apart), base);
         }
     }
@@ -2065,14 +2038,18 @@ __device__ __forceinline__ V3 entry_colour(const RtParams &p, const float4 *lds,
 
 } // namespace
 
-/* The winner's CollisionObject for the record of a *_hits kernel -- render_tile()'s phase 1 written as a function (render_tile()
- * keeps its own copy: taking this function there moved the register allocation of the existing kernels and added scratch
- * stores): Scene index idx at distance t along
- * the ray (o, d) gives the intersection point P, the normal N (before the CollisionObject ctor re-normalises it) and the texture
- * selector (0: the material's colour); returns the material's second quad (m1.w: its bits), with its number and the kind. */
+/* The winner's CollisionObject -- phase 1 of a tile, for render_tile_twin() and the *_hits kernels: Scene index idx at distance t
+ * along the ray (o, d) gives the intersection point P, the normal N (before the CollisionObject ctor re-normalises it) and the
+ * texture selector (0: the material's colour), with the material's number, its second quad (m1.w: its bits) and the kind.
+ * render_tile() keeps these lines by hand, measured against the parent's listings (scripts/isa_same.py):
+ * called there, this function returning the struct left every register, spill and scratch figure alone but changed the code of
+ * the kernels that use it (base unit: five of seven, 3 to 6 instructions fewer, rt_render_kernel 6 860 -> 6 854) -- different code
+ * in every family for no measured gain; taking P, N and the selector by reference put them in scratch (rt_render_kernel 0 -> 176
+ * bytes, 186 instructions more).  In render_tile_twin() and hits_tile() it compiles to the instructions of the copy. */
+struct Winner { V3 P, N; int texsel, mat, kind; float4 m1; };
 template <bool kImages = false>
-__device__ __forceinline__ float4 winner_geometry(const RtParams &p, const float4 *lds, const int idx, const float t, const V3 o,
-                                                  const V3 d, V3 *P_out, V3 *N_out, int *texsel_out, int *mat_out, int *kind_out) {
+__device__ __forceinline__ Winner winner_geometry(const RtParams &p, const float4 *lds, const int idx, const float t, const V3 o,
+                                                  const V3 d) {
     const uint32_t *lds_u32 = reinterpret_cast<const uint32_t *>(lds);
     const uint32_t info = lds_u32[p.objinfo_off * 4 + idx];
     const float4 *g = lds + (info & 0xFFFFu);
@@ -2080,7 +2057,7 @@ __device__ __forceinline__ float4 winner_geometry(const RtParams &p, const float
     const int mat = (int)(info >> 20);
     const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
     const uint32_t mbits = __float_as_uint(m1.w);
-    V3 P, N;                                     /* (locals, stored once at the end: through the pointers they went to scratch) */
+    V3 P, N;
     int texsel = 0;
     if (kind == RT_KIND_SPHERE) {                /* src/SceneSphere.cpp:118-149 */
         const float4 s = g[0];
@@ -2105,12 +2082,7 @@ __device__ __forceinline__ float4 winner_geometry(const RtParams &p, const float
         N = (dot3(xyz(q0), d) < 0) ? xyz(q0) : xyz(q4);
         P = add3(ip, scale3(N, (float)1E-3));
     }
-    *P_out = P;
-    *N_out = N;
-    *texsel_out = texsel;
-    *mat_out = mat;
-    *kind_out = kind;
-    return m1;
+    return Winner{P, N, texsel, mat, kind, m1};
 }
 
 /* RAY BATCH: ray `ray` = {E, T} of p.rays, 24 bytes, consecutive lanes read consecutive records, as render_tile() reads them
@@ -2129,14 +2101,21 @@ __device__ __forceinline__ size_t hbm_stack_entry(const RtParams &p, const int l
     return (size_t)(row * (unsigned int)here(p.stack_stride) + threadIdx.x);
 }
 
-/* REFRACTION (include/rt_capi_refract.h; the *_refract kernels only).  A level's stack entry is three quads (rt_tables.h,
- * RT_REFRACT_ENTRY_QUADS): quad q of level j is row 3 j + q, in LDS below p.stack_lds_levels levels, else in this workgroup's
- * HBM slice of 3 (max_depth + 1) rows. */
-__device__ __forceinline__ float4 *refract_entry(const RtParams &p, float4 *wlds, float4 *bounce_stack, const int level, const int q) {
-    const int row = level * RT_REFRACT_ENTRY_QUADS + q;
-    if (level < p.stack_lds_levels) return wlds + here(p.stack_off) + row * here(p.stack_stride) + threadIdx.x;
-    const unsigned int r = (unsigned int)here((int)blockIdx.x) * (unsigned int)((p.max_depth + 1) * RT_REFRACT_ENTRY_QUADS) + (unsigned int)row;
+/* This lane's entry of row `row` of the workgroup's bounce stack: in LDS (in_lds), else in the workgroup's HBM slice of
+ * rows_per_level (max_depth + 1) rows, addressed like hbm_stack_entry().  The twin tiles keep two rows per level (row 2 level +
+ * ray; in LDS while the row is below p.stack_lds_levels), REFRACTION three (rt_tables.h, RT_REFRACT_ENTRY_QUADS: quad q of level j
+ * is row 3 j + q; in LDS while the level is below p.stack_lds_levels): the option `stack` counts rows for the one, levels for the
+ * other, so each layout's one-line wrapper states its rule.  render_tile() keeps its two-armed wlds[...] / bounce_stack[...] form:
+ * a pointer chosen between LDS and HBM is a flat access (through this routine: VGPRs 81 -> 86 in rt_render_kernel_fast_stats, two
+ * spilled registers more in rt_render_kernel_clusters). */
+__device__ __forceinline__ float4 *stack_entry(const RtParams &p, float4 *wlds, float4 *bounce_stack, const int row, const bool in_lds,
+                                               const int rows_per_level) {
+    if (in_lds) return wlds + here(p.stack_off) + row * here(p.stack_stride) + threadIdx.x;
+    const unsigned int r = (unsigned int)here((int)blockIdx.x) * (unsigned int)(rows_per_level * (p.max_depth + 1)) + (unsigned int)row;
     return bounce_stack + (size_t)(r * (unsigned int)here(p.stack_stride) + threadIdx.x);
+}
+__device__ __forceinline__ float4 *refract_entry(const RtParams &p, float4 *wlds, float4 *bounce_stack, const int level, const int q) {
+    return stack_entry(p, wlds, bounce_stack, level * RT_REFRACT_ENTRY_QUADS + q, level < p.stack_lds_levels, RT_REFRACT_ENTRY_QUADS);
 }
 
 /* The transmitted child of a shaded hit on a refractive object (include/rt_capi_refract.h, with the oracle's v_* operations in
@@ -2212,6 +2191,93 @@ __device__ __forceinline__ void gbuffer_store(const RtParams &p, const int sx, c
 #define RT_GBUFFER_STORE_LATE 0
 #endif
 
+/* ---- THE PER-RAY STEPS OF A TILE, shared by render_tile() and render_tile_twin(): the parity contract's arithmetic, every
+ * operation in the reference's order, written once.  Values in, a value out (out-pointers went to scratch). */
+
+/* Lane `lane`'s cell of wavefront tile (tile_col, tile_row), its column and its row: a tile is (64 >> tzl) columns by
+ * (1 << tzl) rows (tzl: p.tile_z_log2); consecutive lanes walk z, the contiguous axis of pixels[x][z].  Columns count from x0
+ * (p.x0: the image's; 0: the strip's).  Lane 0's cell is the tile's corner. */
+__device__ __forceinline__ int cell_x(const int tzl, const int x0, const int tile_col, const int lane) {
+    return x0 + tile_col * (64 >> tzl) + (lane >> tzl);
+}
+__device__ __forceinline__ int cell_z(const int tzl, const int tile_row, const int lane) {
+    return (tile_row << tzl) + (lane & ((1 << tzl) - 1));
+}
+
+/* Camera::createEyeRay, src/Camera.cpp:71-84, with dx = (float)x / W, dz = (float)z / H from the pixel loop,
+ * src/RayTracer.cpp:916-918: the direction of pixel (x, z)'s ray from the eye o */
+__device__ __forceinline__ V3 eye_ray_direction(const RtParams &p, const V3 o, const int x, const int z) {
+    const float dx_percent = ((float)x) / (float)here(p.W);
+    const float dy_percent = ((float)z) / (float)here(p.H);
+    const float scalar_x = dx_percent * p.sw - p.shw;
+    const float scalar_y = dy_percent * p.sh - p.shh;
+    V3 pixel = add3(mk(p.so[0], p.so[1], p.so[2]), scale3(mk(p.ch[0], p.ch[1], p.ch[2]), scalar_x));
+    pixel = add3(pixel, scale3(mk(p.cv[0], p.cv[1], p.cv[2]), scalar_y));
+    return normalize3(sub3(pixel, o));
+}
+
+/* What one light that is not blocked adds to a shading ray's colour C, in place: cosineShade, src/RayTracer.cpp:654-701, then
+ * the specular term, :561-588.  N: the hit's normal, d: the ray's direction, light_ray: normalize(light - P); the material's
+ * colour and factors, the light's colour and intensity; normals_are_unit: render_tile(); soft, visible: SOFT SHADOWS, f = m / S.
+ * A macro, as RT_FOUR_SPHERES_VQ: as a function -- colour by value, by reference, the condition inside -- it compiled 22 to 65 of
+ * the G-buffer, refraction and soft-shadow kernels to other code, some to more instructions (scripts/isa_same.py).
+ * normal_dir: the CollisionObject ctor, Ray(point, normal), re-normalises, src/SceneObject.h:62.  (The rare path goes through an
+ * opaque copy: left to itself the compiler computes the square root and the three divides before the light loop, on every
+ * bounce level of every tile, speculatively -- 55 instructions and two spilled registers.) */
+#define RT_LIGHT_TERMS(soft, C, N, d, light_ray, normals_are_unit, object_color, diffuse_factor, specular_factor, light_color,   \
+                       intensity, visible)                                                                                      \
+    do {                                                                                                                        \
+        V3 normal_dir = N;                                                                                                      \
+        if (!normals_are_unit) normal_dir = renormalize3(not_speculated(N));                                                    \
+        if (diffuse_factor > (float)0) {                           /* cosineShade, :654-701 */                                  \
+            float cosine_dot_factor = dot3(normal_dir, light_ray);                                                              \
+            if (cosine_dot_factor > (float)0) {                                                                                 \
+                float factor = cosine_dot_factor * diffuse_factor * intensity;                                                  \
+                if constexpr (soft) factor = factor * visible;                                                                  \
+                C.x += factor * object_color.x * light_color.x;                                                                 \
+                C.y += factor * object_color.y * light_color.y;                                                                 \
+                C.z += factor * object_color.z * light_color.z;                                                                 \
+            }                                                                                                                   \
+            C.x = (C.x > 1.0f) ? 1.0f : C.x;                                                                                    \
+            C.y = (C.y > 1.0f) ? 1.0f : C.y;                                                                                    \
+            C.z = (C.z > 1.0f) ? 1.0f : C.z;                                                                                    \
+        }                                                                                                                       \
+        V3 Nn = normal_dir;                                        /* specular, :561-588; third normalisation, :566-567 */      \
+        if (!normals_are_unit) Nn = renormalize3(not_speculated(normal_dir));                                                   \
+        const V3 R = sub3(light_ray, scale3(Nn, 2.0f * dot3(light_ray, Nn)));                                                   \
+        const float dot = dot3(d, R);                                                                                           \
+        if (dot > (float)0) {                                                                                                   \
+            float pow_factor = dot;                                                                                             \
+            _Pragma("unroll")                                                                                                   \
+            for (int j = 0; j < 19; ++j) pow_factor *= dot;                                                                     \
+            float spec_factor = pow_factor * specular_factor;                                                                   \
+            if constexpr (soft) spec_factor = spec_factor * visible;                                                            \
+            C = add3(C, scale3(light_color, spec_factor));                                                                      \
+        }                                                                                                                       \
+    } while (0)
+
+/* final = local + (f * C_next) * colour, src/RayTracer.cpp:601, in the formula's order: a level's own colour `local` with what
+ * its child returned, C_next; f: the child's factor, oc: the colour of the level's winner */
+__device__ __forceinline__ V3 fold_child(const V3 local, const V3 C_next, const float f, const V3 oc) {
+    return add3(local, mk(C_next.x * f * oc.x, C_next.y * f * oc.y, C_next.z * f * oc.z));
+}
+
+/* the ray d mirrored at the normal N, src/SceneObject.h:65 (Ray(point, reflected) normalises it) */
+__device__ __forceinline__ V3 reflected_ray(const V3 N, const V3 d) {
+    const float n_dot_incoming = dot3(N, d);
+    return mk(-2 * N.x * n_dot_incoming + d.x, -2 * N.y * n_dot_incoming + d.y, -2 * N.z * n_dot_incoming + d.z);
+}
+
+/* A pixel's colour, three floats at dst.  Written once, never read here: streaming stores leave the L2 to the bounce stack and
+ * the scratch lines (RT_NT_STORES) */
+__device__ __forceinline__ void store_pixel(float *dst, const V3 c) {
+#if RT_NT_STORES
+    __builtin_nontemporal_store(c.x, dst); __builtin_nontemporal_store(c.y, dst + 1); __builtin_nontemporal_store(c.z, dst + 2);
+#else
+    dst[0] = c.x; dst[1] = c.y; dst[2] = c.z;
+#endif
+}
+
 /* One wavefront tile: camera rays, the bounce loop, the unwind, the store.  kSsaa: the tile is a rectangle of SAMPLES of a
  * virtual kW x kH image (k = 1 << p.ssaa_log2, both tile sides multiples of k: rt_capi.hip, tile_shape()); the store box-filters
  * them into the W x H output (below).  kRays: the tile is a rectangle of cells of the n_cols x rows grid of a caller's ray batch
@@ -2246,11 +2312,8 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
         t_start_real = __builtin_amdgcn_s_memrealtime();
     }
 
-    /* pixel of this lane: wavefront tiles are tile_x columns by tile_z rows;
-     * consecutive lanes walk z, the contiguous axis of pixels[x][z] */
     const int tzl_a = here(p.tile_z_log2);
-    const int x = p.x0 + tile_col * (64 >> tzl_a) + (lane >> tzl_a);
-    const int z = (tile_row << tzl_a) + (lane & ((1 << tzl_a) - 1));
+    const int x = cell_x(tzl_a, p.x0, tile_col, lane), z = cell_z(tzl_a, tile_row, lane);      /* pixel of this lane */
     /* RAY BATCH: this cell's ray; below 2^31 for cells of the grid (rt_capi.hip, rays_args()), wrapped for the others */
     const unsigned int ray = kRays ? (unsigned int)x * (unsigned int)here(p.H) + (unsigned int)z : 0u;
     const bool inside = (x < p.x1) && (z < p.H) && (!kRays || ray < (unsigned int)p.n_rays);   /* (the batch may end inside a tile) */
@@ -2267,16 +2330,8 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
         o = inside ? e : mk(0.0f, 0.0f, 0.0f);
         d = normalize3(sub3(inside ? tgt : mk(1.0f, 1.0f, 1.0f), o));
     } else {
-        /* Camera::createEyeRay, src/Camera.cpp:71-84, with dx = (float)x / W,
-         * dz = (float)z / H from the pixel loop, src/RayTracer.cpp:916-918 */
         o = mk(p.eye[0], p.eye[1], p.eye[2]);
-        const float dx_percent = ((float)x) / (float)here(p.W);
-        const float dy_percent = ((float)z) / (float)here(p.H);
-        const float scalar_x = dx_percent * p.sw - p.shw;
-        const float scalar_y = dy_percent * p.sh - p.shh;
-        V3 pixel = add3(mk(p.so[0], p.so[1], p.so[2]), scale3(mk(p.ch[0], p.ch[1], p.ch[2]), scalar_x));
-        pixel = add3(pixel, scale3(mk(p.cv[0], p.cv[1], p.cv[2]), scalar_y));
-        d = normalize3(sub3(pixel, o));
+        d = eye_ray_direction(p, o, x, z);
     }
 
     const V3 null_color = mk(p.null_color[0], p.null_color[1], p.null_color[2]);
@@ -2337,7 +2392,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
         if constexpr (kMode == 6) {
             const int tzl_n = here(p.tile_z_log2);
             nearest_hit_fast<kStats>(p, lds, ctl_words, alive, o, d, have_box, box_lo, box_hi, !kRays && level == 0,
-                                     p.x0 + here(tile_col) * (64 >> tzl_n), here(tile_row) << tzl_n, &t, &idx, st);
+                                     cell_x(tzl_n, p.x0, here(tile_col), 0), cell_z(tzl_n, here(tile_row), 0), &t, &idx, st);
         }
         else nearest_hit_items<kStats, kMode>(p, lds, wlds, alive, o, d, have_box, box_lo, box_hi, &t, &idx, st);   /* whole wavefront, converged */
         st_cycles(st, ST_CYCLES_NEAREST, t_scan);
@@ -2398,8 +2453,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
 #else
                 if (inside) {
                     const int tzl_g = here(p.tile_z_log2);
-                    gbuffer_store(p, here(tile_col) * (64 >> tzl_g) + (lane >> tzl_g),
-                                  (here(tile_row) << tzl_g) + (lane & ((1 << tzl_g) - 1)), record);
+                    gbuffer_store(p, cell_x(tzl_g, 0, here(tile_col), lane), cell_z(tzl_g, here(tile_row), lane), record);
                 }
 #endif
             }
@@ -2545,40 +2599,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                     const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
                     const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
                     const V3 object_color = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), texsel);
-                    const float diffuse_factor = m0.w, specular_factor = m1.x;
-                    /* CollisionObject ctor: Ray(point, normal) re-normalises, src/SceneObject.h:62.  (The rare path goes through an
-                     * opaque copy: left to itself the compiler computes the square root and the three divides before the light
-                     * loop, on every bounce level of every tile, speculatively -- 55 instructions and two spilled registers.) */
-                    V3 normal_dir = N;
-                    if (!normals_are_unit) normal_dir = renormalize3(not_speculated(N));
-                    const V3 light_color = xyz(l1);
-                    /* cosineShade, :654-701 */
-                    if (diffuse_factor > (float)0) {
-                        float cosine_dot_factor = dot3(normal_dir, light_ray);
-                        if (cosine_dot_factor > (float)0) {
-                            float factor = cosine_dot_factor * diffuse_factor * l0.w;
-                            if constexpr (kSoft) factor = factor * visible;
-                            C.x += factor * object_color.x * light_color.x;
-                            C.y += factor * object_color.y * light_color.y;
-                            C.z += factor * object_color.z * light_color.z;
-                        }
-                        C.x = (C.x > 1.0f) ? 1.0f : C.x;
-                        C.y = (C.y > 1.0f) ? 1.0f : C.y;
-                        C.z = (C.z > 1.0f) ? 1.0f : C.z;
-                    }
-                    /* specular, :561-588 */
-                    V3 Nn = normal_dir;                                                       /* third normalisation, :566-567 */
-                    if (!normals_are_unit) Nn = renormalize3(not_speculated(normal_dir));
-                    const V3 R = sub3(light_ray, scale3(Nn, 2.0f * dot3(light_ray, Nn)));
-                    const float dot = dot3(d, R);
-                    if (dot > (float)0) {
-                        float pow_factor = dot;
-#pragma unroll
-                        for (int j = 0; j < 19; ++j) pow_factor *= dot;
-                        float spec_factor = pow_factor * specular_factor;
-                        if constexpr (kSoft) spec_factor = spec_factor * visible;
-                        C = add3(C, scale3(light_color, spec_factor));
-                    }
+                    RT_LIGHT_TERMS(kSoft, C, N, d, light_ray, normals_are_unit, object_color, m0.w, m1.x, xyz(l1), l0.w, visible);
                 }
             }
         }
@@ -2601,8 +2622,8 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                 if (lvl == p.max_depth) {
                     /* the last level's children are never traced: C_{k+1} = NULL_COLOR, folded in here in the formula's order */
                     const V3 oc = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), texsel);
-                    if (has_r) C = add3(C, mk(null_color.x * m1.y * oc.x, null_color.y * m1.y * oc.y, null_color.z * m1.y * oc.z));
-                    if (has_t) C = add3(C, mk(null_color.x * r.x * oc.x, null_color.y * r.x * oc.y, null_color.z * r.x * oc.z));
+                    if (has_r) C = fold_child(C, null_color, m1.y, oc);
+                    if (has_t) C = fold_child(C, null_color, r.x, oc);
                     alive = false;
                 } else if (has_r || has_t) {
                     /* entry: {local.rgb, bits}, {transmitted origin, state}, {transmitted direction, -}; state 0: the reflected
@@ -2617,12 +2638,8 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                         refract_entry(p, wlds, bounce_stack, lvl, 1)->w = __int_as_float(0);
                     }
                     if (has_r) {
-                        const float n_dot_incoming = dot3(N, d);         /* src/SceneObject.h:65 */
-                        const V3 reflected = mk(-2 * N.x * n_dot_incoming + d.x,
-                                                -2 * N.y * n_dot_incoming + d.y,
-                                                -2 * N.z * n_dot_incoming + d.z);
                         o = P;
-                        d = normalize3(reflected);
+                        d = normalize3(reflected_ray(N, d));
                     } else {
                         o = to;
                         d = td;
@@ -2646,7 +2663,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                     const int state = __float_as_int(e1.w);
                     const float f = state == 1 ? lds[refr_off + mat].x : m1.y;
                     const V3 oc = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), (int)(bits >> kSelShift));
-                    C = add3(mk(e.x, e.y, e.z), mk(C.x * f * oc.x, C.y * f * oc.y, C.z * f * oc.z));
+                    C = fold_child(mk(e.x, e.y, e.z), C, f, oc);
                     if (state == 2) {
                         /* the reflected subtree is done: the partial sum stays, the transmitted child is walked next */
                         *refract_entry(p, wlds, bounce_stack, lvl, 0) = make_float4(C.x, C.y, C.z, e.w);
@@ -2663,7 +2680,6 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
         if (shade) {
             const int mat = (int)(lds_u32[p.objinfo_off * 4 + idx] >> 20);
             const float reflective_factor = lds[p.mat_off + mat * RT_MAT_QUADS + 1].y;
-            const float n_dot_incoming = dot3(N, d);         /* src/SceneObject.h:65 */
             if (reflective_factor > (float)0 && level == p.max_depth) {
                 /* The reflected ray of the LAST level is never traced: the call at max_depth + 1 returns NULL_COLOR at once
                  * (:454-455), so this level's sum can be formed here, with the operations the unwind below would apply to its
@@ -2673,14 +2689,10 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                 const int mat_last = (int)(info >> 20);
                 const float4 m0 = lds[p.mat_off + mat_last * RT_MAT_QUADS];
                 const float4 m1 = lds[p.mat_off + mat_last * RT_MAT_QUADS + 1];
-                const V3 oc = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), texsel);
-                const V3 refl = mk(null_color.x * m1.y * oc.x, null_color.y * m1.y * oc.y, null_color.z * m1.y * oc.z);
-                C = add3(C, refl);
+                C = fold_child(C, null_color, m1.y, entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), texsel));
                 alive = false;
             } else if (reflective_factor > (float)0) {
-                const V3 reflected = mk(-2 * N.x * n_dot_incoming + d.x,
-                                        -2 * N.y * n_dot_incoming + d.y,
-                                        -2 * N.z * n_dot_incoming + d.z);
+                const V3 reflected = reflected_ray(N, d);
                 float4 e;
                 e.x = C.x; e.y = C.y; e.z = C.z;
                 e.w = __uint_as_float((uint32_t)idx | ((uint32_t)texsel << kSelShift));
@@ -2714,9 +2726,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
             const int mat = (int)(info >> 20);
             const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
             const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
-            const V3 oc = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), (int)(bits >> kSelShift));
-            const V3 refl = mk(C.x * m1.y * oc.x, C.y * m1.y * oc.y, C.z * m1.y * oc.z);
-            C = add3(mk(e.x, e.y, e.z), refl);
+            C = fold_child(mk(e.x, e.y, e.z), C, m1.y, entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), (int)(bits >> kSelShift)));
         }
     }
 
@@ -2747,27 +2757,15 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
         const float inv = kl == 1 ? 0.25f : 0.0625f;                 /* 1 / k^2, k in {2, 4} */
         const bool base = ((lane >> tzl_s) & (k - 1)) == 0 && (lane & (k - 1)) == 0;
         if (inside && base) {
-            const int sx = (here(tile_col) * (64 >> tzl_s) + (lane >> tzl_s)) >> kl;   /* output column - output x0 */
-            const int sz = ((here(tile_row) << tzl_s) + (lane & ((1 << tzl_s) - 1))) >> kl;
-            float *dst = out + ((size_t)sx * (size_t)(here(p.H) >> kl) + (size_t)sz) * 3;
-            const float r = acc.x * inv, g = acc.y * inv, b = acc.z * inv;
-#if RT_NT_STORES
-            __builtin_nontemporal_store(r, dst); __builtin_nontemporal_store(g, dst + 1); __builtin_nontemporal_store(b, dst + 2);
-#else
-            dst[0] = r; dst[1] = g; dst[2] = b;
-#endif
+            const int sx = cell_x(tzl_s, 0, here(tile_col), lane) >> kl;       /* output column - output x0 */
+            const int sz = cell_z(tzl_s, here(tile_row), lane) >> kl;
+            store_pixel(out + ((size_t)sx * (size_t)(here(p.H) >> kl) + (size_t)sz) * 3, scale3(acc, inv));
         }
     } else if (inside) {
         const int tzl_b = here(p.tile_z_log2);
-        const int sx = here(tile_col) * (64 >> tzl_b) + (lane >> tzl_b);   /* x - x0 */
-        const int sz = (here(tile_row) << tzl_b) + (lane & ((1 << tzl_b) - 1));
-        float *dst = out + ((size_t)sx * (size_t)p.H + (size_t)sz) * 3;
-#if RT_NT_STORES
-        /* written once, never read here: streaming stores leave the L2 to the bounce stack and the scratch lines */
-        __builtin_nontemporal_store(C.x, dst); __builtin_nontemporal_store(C.y, dst + 1); __builtin_nontemporal_store(C.z, dst + 2);
-#else
-        dst[0] = C.x; dst[1] = C.y; dst[2] = C.z;
-#endif
+        const int sx = cell_x(tzl_b, 0, here(tile_col), lane);             /* x - x0 */
+        const int sz = cell_z(tzl_b, here(tile_row), lane);
+        store_pixel(out + ((size_t)sx * (size_t)p.H + (size_t)sz) * 3, C);
 #if RT_GBUFFER_STORE_LATE
         if constexpr (kGbuffer) gbuffer_store(p, sx, sz, late_record);
 #endif
@@ -2810,10 +2808,7 @@ struct TwinRay {
 };
 
 __device__ __forceinline__ float4 *twin_stack_entry(const RtParams &p, float4 *wlds, float4 *bounce_stack, const int level, const int ray) {
-    const int row = 2 * level + ray;
-    if (row < p.stack_lds_levels) return wlds + here(p.stack_off) + row * here(p.stack_stride) + threadIdx.x;
-    const unsigned int r = (unsigned int)here((int)blockIdx.x) * (unsigned int)(2 * (p.max_depth + 1)) + (unsigned int)row;
-    return bounce_stack + (size_t)(r * (unsigned int)here(p.stack_stride) + threadIdx.x);
+    return stack_entry(p, wlds, bounce_stack, 2 * level + ray, 2 * level + ray < p.stack_lds_levels, 2);
 }
 
 /* `wave_in`: the number of the twin's first tile (an even tile row of its macro tile) */
@@ -2830,20 +2825,13 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
     TwinRay r[2];
     {
         const int tzl_a = here(p.tile_z_log2);
-        const int x = p.x0 + tile_col * (64 >> tzl_a) + (lane >> tzl_a);
+        const int x = cell_x(tzl_a, p.x0, tile_col, lane);
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const int z = ((tile_row + k) << tzl_a) + (lane & ((1 << tzl_a) - 1));
+            const int z = cell_z(tzl_a, tile_row + k, lane);
             r[k].inside = (x < p.x1) && (z < p.H);             /* (a tile row that does not exist starts at z >= H) */
-            /* Camera::createEyeRay, as render_tile() */
             r[k].o = mk(p.eye[0], p.eye[1], p.eye[2]);
-            const float dx_percent = ((float)x) / (float)here(p.W);
-            const float dy_percent = ((float)z) / (float)here(p.H);
-            const float scalar_x = dx_percent * p.sw - p.shw;
-            const float scalar_y = dy_percent * p.sh - p.shh;
-            V3 pixel = add3(mk(p.so[0], p.so[1], p.so[2]), scale3(mk(p.ch[0], p.ch[1], p.ch[2]), scalar_x));
-            pixel = add3(pixel, scale3(mk(p.cv[0], p.cv[1], p.cv[2]), scalar_y));
-            r[k].d = normalize3(sub3(pixel, r[k].o));
+            r[k].d = eye_ray_direction(p, r[k].o, x, z);
             r[k].C = null_color;
             r[k].top = 0;
             r[k].alive = r[k].inside;
@@ -2866,7 +2854,7 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
         {
             const int tzl_n = here(p.tile_z_log2);
             nearest_hit_fast_twin(p, lds, ctl_words, r[0].alive, r[0].o, r[0].d, r[1].alive, r[1].o, r[1].d, box_lo, box_hi, level == 0,
-                                  p.x0 + here(tile_col) * (64 >> tzl_n), here(tile_row) << tzl_n, &r[0].t, &r[0].idx, &r[1].t, &r[1].idx);
+                                  cell_x(tzl_n, p.x0, here(tile_col), 0), cell_z(tzl_n, here(tile_row), 0), &r[0].t, &r[0].idx, &r[1].t, &r[1].idx);
         }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -2877,31 +2865,11 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
                     q.alive = false;
                     q.idx = 0;
                 } else {
-                    const uint32_t info = lds_u32[p.objinfo_off * 4 + q.idx];
-                    const float4 *g = lds + (info & 0xFFFFu);
-                    const int kind = (int)((info >> 16) & 3u);
-                    const int mat = (int)(info >> 20);
-                    const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
+                    const Winner w = winner_geometry<false>(p, lds, q.idx, q.t, q.o, q.d);
+                    q.P = w.P; q.N = w.N; q.texsel = w.texsel;
+                    const int mat = w.mat;
+                    const float4 m1 = w.m1;
                     const uint32_t mbits = __float_as_uint(m1.w);
-                    if (kind == RT_KIND_SPHERE) {                /* src/SceneSphere.cpp:118-149 */
-                        const float4 s = g[0];
-                        q.P = add3(scale3(q.d, q.t), q.o);
-                        q.N = normalize3(sub3(q.P, xyz(s)));
-                    } else {                                     /* src/SceneInfinitePlane.cpp:53-95, src/SceneFinitePlane.cpp:106-150 */
-                        const float4 q0 = g[0], q1 = g[1], q2 = g[2], q3 = g[3], q4 = g[4];
-                        const V3 ip = add3(scale3(q.d, q.t), q.o);
-                        if ((mbits >> 1) != 0u) {
-                            const V3 PO = sub3(ip, xyz(q1));
-                            const float tx = dot3(PO, xyz(q2));
-                            const float ty = dot3(PO, xyz(q3));
-                            const int tex = (int)(mbits >> 1) - 1;
-                            const float4 t0 = lds[p.tex_off + tex * RT_TEX_QUADS];
-                            const float4 t1 = lds[p.tex_off + tex * RT_TEX_QUADS + 1];
-                            q.texsel = checkerboard_select(t0.w, t1.w, tx, ty);
-                        }
-                        q.N = (dot3(xyz(q0), q.d) < 0) ? xyz(q0) : xyz(q4);
-                        q.P = add3(ip, scale3(q.N, (float)1E-3));
-                    }
                     if (mbits & 1u) {                            /* hit a light: :520-527 */
                         const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
                         q.C = scale3(entry_colour<false>(p, lds, m0, mbits, q.texsel), m1.z);
@@ -2949,35 +2917,7 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
                         const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
                         const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
                         const V3 object_color = entry_colour<false>(p, lds, m0, __float_as_uint(m1.w), q.texsel);
-                        const float diffuse_factor = m0.w, specular_factor = m1.x;
-                        V3 normal_dir = q.N;                     /* CollisionObject ctor: Ray(point, normal) re-normalises */
-                        if (!normals_are_unit) normal_dir = renormalize3(not_speculated(q.N));
-                        const V3 light_color = xyz(l1);
-                        /* cosineShade, :654-701 */
-                        if (diffuse_factor > (float)0) {
-                            float cosine_dot_factor = dot3(normal_dir, light_ray);
-                            if (cosine_dot_factor > (float)0) {
-                                float factor = cosine_dot_factor * diffuse_factor * l0.w;
-                                q.C.x += factor * object_color.x * light_color.x;
-                                q.C.y += factor * object_color.y * light_color.y;
-                                q.C.z += factor * object_color.z * light_color.z;
-                            }
-                            q.C.x = (q.C.x > 1.0f) ? 1.0f : q.C.x;
-                            q.C.y = (q.C.y > 1.0f) ? 1.0f : q.C.y;
-                            q.C.z = (q.C.z > 1.0f) ? 1.0f : q.C.z;
-                        }
-                        /* specular, :561-588 */
-                        V3 Nn = normal_dir;                      /* third normalisation, :566-567 */
-                        if (!normals_are_unit) Nn = renormalize3(not_speculated(normal_dir));
-                        const V3 R = sub3(light_ray, scale3(Nn, 2.0f * dot3(light_ray, Nn)));
-                        const float dot = dot3(q.d, R);
-                        if (dot > (float)0) {
-                            float pow_factor = dot;
-#pragma unroll
-                            for (int j = 0; j < 19; ++j) pow_factor *= dot;
-                            const float spec_factor = pow_factor * specular_factor;
-                            q.C = add3(q.C, scale3(light_color, spec_factor));
-                        }
+                        RT_LIGHT_TERMS(false, q.C, q.N, q.d, light_ray, normals_are_unit, object_color, m0.w, m1.x, xyz(l1), l0.w, 1.0f);
                     }
                 }
             }
@@ -2990,19 +2930,14 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
             if (q.shade) {
                 const int mat = (int)(lds_u32[p.objinfo_off * 4 + q.idx] >> 20);
                 const float reflective_factor = lds[p.mat_off + mat * RT_MAT_QUADS + 1].y;
-                const float n_dot_incoming = dot3(q.N, q.d);     /* src/SceneObject.h:65 */
                 if (reflective_factor > (float)0 && level == p.max_depth) {
                     /* the reflected ray of the LAST level is never traced: render_tile() */
                     const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
                     const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
-                    const V3 oc = entry_colour<false>(p, lds, m0, __float_as_uint(m1.w), q.texsel);
-                    const V3 refl = mk(null_color.x * m1.y * oc.x, null_color.y * m1.y * oc.y, null_color.z * m1.y * oc.z);
-                    q.C = add3(q.C, refl);
+                    q.C = fold_child(q.C, null_color, m1.y, entry_colour<false>(p, lds, m0, __float_as_uint(m1.w), q.texsel));
                     q.alive = false;
                 } else if (reflective_factor > (float)0) {
-                    const V3 reflected = mk(-2 * q.N.x * n_dot_incoming + q.d.x,
-                                            -2 * q.N.y * n_dot_incoming + q.d.y,
-                                            -2 * q.N.z * n_dot_incoming + q.d.z);
+                    const V3 reflected = reflected_ray(q.N, q.d);
                     *twin_stack_entry(p, wlds, bounce_stack, level, k) =
                         make_float4(q.C.x, q.C.y, q.C.z, __uint_as_float((uint32_t)q.idx | ((uint32_t)q.texsel << 16)));
                     q.top = level + 1;
@@ -3029,9 +2964,7 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
                 const int mat = (int)(info >> 20);
                 const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
                 const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
-                const V3 oc = entry_colour<false>(p, lds, m0, __float_as_uint(m1.w), (int)(bits >> 16));
-                const V3 refl = mk(q.C.x * m1.y * oc.x, q.C.y * m1.y * oc.y, q.C.z * m1.y * oc.z);
-                q.C = add3(mk(e.x, e.y, e.z), refl);
+                q.C = fold_child(mk(e.x, e.y, e.z), q.C, m1.y, entry_colour<false>(p, lds, m0, __float_as_uint(m1.w), (int)(bits >> 16)));
             }
         }
     }
@@ -3042,14 +2975,9 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
     for (int k = 0; k < 2; ++k) {
         if (r[k].inside) {
             const int tzl_b = here(p.tile_z_log2);
-            const int sx = here(tile_col) * (64 >> tzl_b) + (lane >> tzl_b);   /* x - x0 */
-            const int sz = ((here(tile_row) + k) << tzl_b) + (lane & ((1 << tzl_b) - 1));
-            float *dst = out + ((size_t)sx * (size_t)p.H + (size_t)sz) * 3;
-#if RT_NT_STORES
-            __builtin_nontemporal_store(r[k].C.x, dst); __builtin_nontemporal_store(r[k].C.y, dst + 1); __builtin_nontemporal_store(r[k].C.z, dst + 2);
-#else
-            dst[0] = r[k].C.x; dst[1] = r[k].C.y; dst[2] = r[k].C.z;
-#endif
+            const int sx = cell_x(tzl_b, 0, here(tile_col), lane);             /* x - x0 */
+            const int sz = cell_z(tzl_b, here(tile_row) + k, lane);
+            store_pixel(out + ((size_t)sx * (size_t)p.H + (size_t)sz) * 3, r[k].C);
         }
     }
 }
@@ -3064,8 +2992,7 @@ __device__ __forceinline__ unsigned int query_cell(const RtParams &p, const int 
     const int tile_row = wave / p.tiles_x;
     const int tile_col = wave - tile_row * p.tiles_x;
     const int tzl = here(p.tile_z_log2);
-    const int x = tile_col * (64 >> tzl) + (lane >> tzl);
-    const int z = (tile_row << tzl) + (lane & ((1 << tzl) - 1));
+    const int x = cell_x(tzl, 0, tile_col, lane), z = cell_z(tzl, tile_row, lane);
     const unsigned int ray = (unsigned int)x * (unsigned int)here(p.H) + (unsigned int)z;
     *inside = (x < p.x1) && (z < p.H) && ray < (unsigned int)p.n_rays;
     return ray;
@@ -3104,10 +3031,11 @@ __device__ __forceinline__ void hits_tile(const RtParams &p, const float4 *lds, 
     query_next_tile(next_pop, ask_head);
     float4 q0 = make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f), q1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q2 = q1;
     if (inside && idx >= 0) {
-        V3 P, N;
-        int texsel = 0, mat, kind;
-        const float4 m1 = winner_geometry<kImages>(p, lds, idx, t, o, d, &P, &N, &texsel, &mat, &kind);
-        const uint32_t mbits = __float_as_uint(m1.w);
+        const Winner w = winner_geometry<kImages>(p, lds, idx, t, o, d);
+        const V3 P = w.P;
+        V3 N = w.N;
+        const int texsel = w.texsel, mat = w.mat, kind = w.kind;
+        const uint32_t mbits = __float_as_uint(w.m1.w);
         const float nn = N.x * N.x + N.y * N.y + N.z * N.z;
         if (nn != 1.0f) {
             const float length = sqrtf(nn);

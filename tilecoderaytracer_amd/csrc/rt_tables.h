@@ -311,7 +311,7 @@ enum { RT_QUERY_NONE = 0, RT_QUERY_HITS = 1, RT_QUERY_OCCLUDED = 2, RT_QUERY_AO 
 /* TWIN TILES.  rt_render_kernel -- the FAST tables' kernel of the camera's plain frame, the bench headline -- renders wavefront
  * tiles in vertical pairs: every lane carries two pixels, one of each of tile rows 2j and 2j + 1 of a macro tile, and what a
  * wavefront does as a whole (bundle bounds, culls, candidate order, scalar dispatch) runs once for both (rt_kernel.hip,
- * render_tile_twin()).  A queue entry of that kernel is a twin, its bounce stack has two rows per level, and its launch bound
+ * render_tile_twin(), on render_tile()'s per-ray routines).  A queue entry is a twin, its bounce stack has two rows per level, and its launch bound
  * is RT_WAVES_PER_SIMD_TWIN instead of the mode's.  Every other kernel renders one tile per wavefront, and so does this one
  * with -DRT_TWIN_TILES=0 (a build switch, not an option: both bodies in one kernel would cost both their registers).
  * RT_KERNEL_IS_TWIN: the rule, from a kernel's catalogue columns, for rt_kernel.hip and rt_capi.hip alike. */
