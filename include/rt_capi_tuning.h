@@ -82,6 +82,26 @@ int rt_get_timeline(rt_scene *scene, uint64_t *out, int n_words);
 
 int rt_get_launch_info(const rt_scene *scene, rt_launch_info *out);
 
+/* The PRIMARY table a launch would get (option "primary"), without a device: pure host arithmetic, like rt_strip_bounds.  The
+ * description is checked and packed as rt_scene_create does it, with every option at its default, and the table is made by the
+ * function every launch of a W x H frame under `camera` calls.  Per item of the FAST list, in the list's order: the Scene index of
+ * its object, the rectangle of frame pixels [x_lo, x_hi] x [z_lo, z_hi] outside which the camera rays' scan skips the item, as the
+ * kernel decodes it (signed 16-bit bounds that may lie outside the image; x_lo > x_hi: no pixel), and the entry distance (0: the
+ * item is tested whatever has been found).  A k x k supersampled launch (rt_capi_ssaa.h) of a W x H frame gets the table of the
+ * kW x kH frame of its samples.  *n_items receives the table's number of items, whatever `cap` is, and out[] the first `cap` of
+ * them (RT_PRIMARY_ITEMS_MAX always suffice; cap 0 with out NULL asks for the count alone).  The count is 0 when a launch would
+ * get no table and cull by the bundle of rays instead -- a scene without FAST tables or with more items than the table holds, a
+ * camera or a frame size the table cannot be made for.  An added call: RT_CAPI_TUNING_VERSION stays, as for every call added
+ * to this header. */
+#define RT_PRIMARY_ITEMS_MAX 64
+typedef struct rt_primary_item {
+    int32_t object;
+    int32_t x_lo, x_hi, z_lo, z_hi;
+    float   entry;
+} rt_primary_item;
+int rt_primary_rectangles(const rt_scene_desc *desc, const rt_camera_desc *camera, int W, int H,
+                          rt_primary_item *out, int cap, int *n_items);
+
 /* Tuning knobs (speed only, never results).  key:
  *   "tile_z"        wavefront tile height, 1,2,4,...,64 (width = 64 / height)
  *   "block_threads" 0 = auto (256; 512 for scenes with clustered sphere runs whose tables are so large that

@@ -24,7 +24,7 @@ DROP_IN = ["rt_balance_strips", "rt_capi_version", "rt_chunk_bounds", "rt_device
            "rt_shared_image_close", "rt_shared_image_create", "rt_shared_image_destroy", "rt_shared_image_open",
            "rt_strip_bounds", "rt_suggest_chunks"]
 TUNING = ["rt_capi_tuning_version", "rt_get_launch_info", "rt_get_timeline", "rt_learn_tile_order", "rt_multi_set_option",
-          "rt_render_stats", "rt_set_option"]
+          "rt_primary_rectangles", "rt_render_stats", "rt_set_option"]
 
 
 def test_header_declares_the_expected_entry_points():

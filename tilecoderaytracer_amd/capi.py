@@ -109,6 +109,13 @@ class RtLaunchInfo(C.Structure):
     ]
 
 
+class RtPrimaryItem(C.Structure):
+    """include/rt_capi_tuning.h: one item of the PRIMARY table -- its object's Scene index, its pixel rectangle, its entry distance"""
+    _fields_ = [("object", C.c_int32), ("x_lo", C.c_int32), ("x_hi", C.c_int32), ("z_lo", C.c_int32), ("z_hi", C.c_int32),
+                ("entry", C.c_float)]
+
+
+RT_PRIMARY_ITEMS_MAX = 64
 RT_MULTI_MAX_GPUS = 16
 RT_KERNEL_NAME_BYTES = 64                 # include/rt_capi_launch.h
 
@@ -185,6 +192,11 @@ def load_library():
     lib.rt_reset_timing.argtypes = [vp]
     lib.rt_get_launch_info.argtypes = [vp, C.POINTER(RtLaunchInfo)]
     lib.rt_set_option.argtypes = [vp, C.c_char_p, i]
+    # (absent from builds older than it, which TCRT_LIBRARY may name for A/B timing)
+    if hasattr(lib, "rt_primary_rectangles"):
+        lib.rt_primary_rectangles.argtypes = [C.POINTER(RtSceneDesc), C.POINTER(RtCameraDesc), i, i, C.POINTER(RtPrimaryItem), i,
+                                              C.POINTER(i)]
+        lib.rt_primary_rectangles.restype = i
     # include/rt_capi_ssaa.h (absent from builds older than it, which TCRT_LIBRARY may name for A/B timing)
     if hasattr(lib, "rt_render_ssaa"):
         lib.rt_capi_ssaa_version.restype = i
@@ -264,6 +276,15 @@ def load_library():
         getattr(lib, name).restype = i
     _lib = lib
     return lib
+
+
+def primary_rectangles(desc, camera, W, H):
+    """rt_primary_rectangles (include/rt_capi_tuning.h, no device needed): the PRIMARY table a W x H launch of the scene
+    description under the camera would get, as a list of RtPrimaryItem; empty when the launch would get none"""
+    items = (RtPrimaryItem * RT_PRIMARY_ITEMS_MAX)()
+    n = C.c_int(0)
+    check(load_library().rt_primary_rectangles(desc, camera, W, H, items, RT_PRIMARY_ITEMS_MAX, C.byref(n)))
+    return list(items[:n.value])
 
 
 def check(rc):

@@ -2523,4 +2523,31 @@ int rt_set_option(rt_scene *s, const char *key, int value) {
     return fail(RT_ERR_INVALID, std::string("unknown option: ") + key);
 }
 
+/* the PRIMARY table of plan_launch() for a handle that never sees a device: the same adopt_desc, pack_scene, primary_quads and
+ * primary_table, and the kernel's decoding of the two rectangle words (rt_kernel.hip: fast_primary_key()) */
+int rt_primary_rectangles(const rt_scene_desc *desc, const rt_camera_desc *camera, int W, int H,
+                          rt_primary_item *out, int cap, int *n_items) {
+    static_assert(RT_PRIMARY_ITEMS_MAX == RT_PRIMARY_ITEMS, "include/rt_capi_tuning.h and rt_tables.h disagree");
+    if (!desc || !camera || !n_items || cap < 0 || (cap > 0 && !out)) return fail(RT_ERR_INVALID, "rt_primary_rectangles: NULL argument");
+    *n_items = 0;
+    if (W < 1 || H < 1) return fail(RT_ERR_INVALID, "rt_primary_rectangles: W and H must be at least 1");
+    rt_scene s;
+    int rc = adopt_desc(desc, &s, 0);
+    if (rc == RT_OK) rc = pack_scene(&s);
+    if (rc) return rc;
+    const int n = primary_quads(&s);
+    uint32_t table[RT_PRIMARY_ITEMS * 4];
+    if (n <= 0 || !primary_table(&s, camera, W, H, table)) return RT_OK;
+    const uint32_t *ctl = reinterpret_cast<const uint32_t *>(s.image.data()) + s.base.fast_ctl_off;
+    for (int i = 0; i < std::min(n, cap); ++i) {
+        const uint32_t *q = table + 4 * i;
+        out[i].object = (int32_t)(ctl[i] >> 8);
+        out[i].x_lo = (int)(short)(q[0] & 0xFFFFu); out[i].x_hi = (int)q[0] >> 16;
+        out[i].z_lo = (int)(short)(q[1] & 0xFFFFu); out[i].z_hi = (int)q[1] >> 16;
+        std::memcpy(&out[i].entry, &q[2], 4);
+    }
+    *n_items = n;
+    return RT_OK;
+}
+
 } // extern "C"
