@@ -1,6 +1,7 @@
 """Randomised parity sweep, GPU kernel vs CPU oracle (development aid; the permanent cases live in tests/).
 
-usage: fuzz_gpu.py [first_seed=1000] [count=200] [only=0..3] [far=1] [bigfields=1] [multi=1] [option=value ...]
+usage: fuzz_gpu.py [first_seed=1000] [count=200] [only=0..3] [far=1] [bigfields=1] [multi=1] [place=1] [option=value ...]
+place=1: every scene under a placement drawn from tests/placement.py's catalogue (scaled, shifted, turned onto other axes); off by default
 multi=1: every scene through rt_render_multi with 2 ... 7 strips on this one device (TCRT_MULTI_ONE_DEVICE=1: measured cut, direct stores)
 far=1: every scene is a far-origin grazing scene (scene_gen.build_far_grazing) in a strip 8 columns wide and 4 096 ... 32 768 rows
 tall, whose rows around the middle hit the ground 1e4 ... 6e4 units away"""
@@ -10,6 +11,7 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
 sys.path.insert(0, os.path.join(R, "tests"))
 import oracle_lib                                   # noqa: E402
+import placement                                    # noqa: E402
 from scene_gen import build_far_grazing, build_random, build_room, build_sphere_field   # noqa: E402
 from tilecoderaytracer_amd import HostScene, Renderer    # noqa: E402
 
@@ -35,10 +37,17 @@ for seed in range(first, first + count):
                   n_lights=int(rng.randint(1, 4)), shadows=bool(rng.rand() < 0.8))
         mk = lambda s: build_random(s, seed, **kw)
         W, H, depth = int(rng.randint(1, 90)), int(rng.randint(1, 90)), int(rng.randint(0, 9))
+    where = "identity"
+    if kv.get("place") == "1":            # a room carries a scale of its own and far=1 a wall 6e4 away: "large" would pass the rays' reach
+        where = str(rng.choice([n for n in placement.NAMES if n != "large" or (seed % 4 != 1 and kv.get("far") != "1")]))
     state = rng.get_state()
-    host = mk(HostScene.empty())
+    host = placement.Placed.named(HostScene.empty(), where)
+    mk(host)
+    host = host.put().scene
     rng.set_state(state)
-    orc = mk(oracle_lib.OracleScene())
+    orc = placement.Placed.named(oracle_lib.OracleScene(), where)
+    mk(orc)
+    orc = orc.put().scene
     if kv.get("multi") in ("1", "2"):           # 2: LOOPBACK -- the strip-buffer transport and the trial too
         import ctypes as C
         from tilecoderaytracer_amd import capi
@@ -49,14 +58,14 @@ for seed in range(first, first + count):
         want = orc.render(W, H, depth)
         if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
             d = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-            bad.append((seed, W, H, depth, len(d), d[0].tolist(), ngpu))
+            bad.append((seed, W, H, depth, len(d), d[0].tolist(), ngpu, where))
             print("MISMATCH", bad[-1], flush=True)
         if (seed - first) % 250 == 249:
             print(f"... {seed - first + 1} scenes, {len(bad)} mismatching, {time.time() - t0:.0f} s", flush=True)
         continue
     r = Renderer(host)
     for k, v in kv.items():                             # any other key=value: an rt_set_option for every scene (help=2 heavy=1 ...)
-        if k not in ("first_seed", "count", "only", "learn", "far", "bigfields", "multi"):
+        if k not in ("first_seed", "count", "only", "learn", "far", "bigfields", "multi", "place"):
             r.set_option(k, int(v))
     if seed % 3 == 0:
         r.set_option("tile_z", int(2 ** rng.randint(0, 7)))
@@ -65,7 +74,7 @@ for seed in range(first, first + count):
     got, want = r.render(W, H, depth), orc.render(W, H, depth)
     if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
         d = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        bad.append((seed, W, H, depth, len(d), d[0].tolist()))
+        bad.append((seed, W, H, depth, len(d), d[0].tolist(), where))
         print("MISMATCH", bad[-1], flush=True)
     if (seed - first) % 250 == 249:                  # a sign of life (a silent GPU job is taken for hung)
         print(f"... {seed - first + 1} scenes, {len(bad)} mismatching, {time.time() - t0:.0f} s", flush=True)

@@ -94,21 +94,31 @@ def build_sphere_field(scene, seed, n_spheres=120, spread=60.0):
     return scene
 
 
+ROOM_SCALES = [0.01, 0.3, 1.0, 1.0, 7.0, 1000.0]
+
+
+def room_scale(seed):
+    """the scale build_room(seed) gives its room (its first draw)"""
+    return f32(np.random.RandomState(seed).choice(ROOM_SCALES))
+
+
 def build_room(scene, seed):
     """Axis-aligned rooms: what round 3's culls changed.  Boxes of three-corner rectangles (the reference's makeSceneBox),
     nested and touching; axis-aligned INFINITE planes on any axis and side (slabs in the culls), lights that hug a surface
     (1e-3 ... 1e-1 in front of it) or sit exactly in a wall's plane, shading points that start on the surfaces (plane hits
-    are offset 1e-3), a few spheres, everything scaled from 1e-2 to 1e3 and shifted away from the origin -- the culls' slack
-    is relative to distance and magnitude -- seen by the horizontal two-mirrors camera (eye (0,-1,2.5), looking along +y)."""
+    are offset 1e-3), a few spheres, everything scaled from 1e-2 to 1e3 about the eye only -- the culls' slack is relative to
+    distance and magnitude -- seen by the horizontal two-mirrors camera (eye (0,-1,2.5), looking along +y).  Rooms are never
+    shifted here: moving, scaling about another point and turning a scene is placement.py's business."""
     rng = np.random.RandomState(seed)
-    scale = f32(rng.choice([0.01, 0.3, 1.0, 1.0, 7.0, 1000.0]))
-    shift = np.float32(rng.choice([0.0, 0.0, 3.0, 250.0]) * rng.uniform(-1, 1, 3)) if scale <= 7.0 else np.zeros(3, np.float32)
+    scale = f32(rng.choice(ROOM_SCALES))
+    if scale <= 7.0:                    # two draws that once fed a shift which was never applied: kept, so that every later draw
+        rng.choice([0.0, 0.0, 3.0, 250.0]), rng.uniform(-1, 1, 3)          # (and so every seed's room) stays what it is
 
     def pt(x, y, z):                    # a point of the unit-scale layout in front of the camera, scaled about the eye
         v = np.float32([x, y, z])
         eye = np.float32([0.0, -1.0, 2.5])
         w = eye + (v - eye) * np.float32(scale)
-        return tuple(f32(c) for c in (w if scale > 7.0 else w + shift * 0))
+        return tuple(f32(c) for c in w)
 
     def box(o, dims, **mat):
         o, dims = np.float32(o), np.float32(dims)
@@ -229,6 +239,33 @@ def build_far_grazing(scene, seed):
     for k in range(int(rng.randint(0, 4))):
         i = scene.add_sphere((f32(rng.uniform(-4, 4)), f32(rng.uniform(3, 12)), f32(rng.uniform(0.5, 3))), f32(rng.uniform(0.3, 1.2)))
         scene.set_color(i, PALETTE[rng.randint(len(PALETTE))])
+    scene.set_object_indices(0, 1)
+    scene.camera_two_mirrors()
+    return scene
+
+
+def build_lattice(scene, n, spacing=2.5, radius=0.8):
+    """An n x n lattice of equal spheres (one consecutive run, clustered by the kernel) standing on a checkered, half-mirror
+    ground plane under two lights, seen by the horizontal two-mirrors camera: the centres tie on every axis, n times each, so the
+    k-d split of the run (csrc/rt_capi.hip: split_leaves()) is decided by its tie order.  n = 12 and 23 are either side of its
+    16 / 20-per-leaf rule.  Through the verbs alone, so that placement.Placed can place it (the oracle's own grid scene cannot be)."""
+    for o, intensity in (((-20.0, 10.0, 10.0), 0.75), ((0.0, 40.0, 11.0), 1.0)):
+        i = scene.add_sphere(o, f32(0.15))
+        scene.set_light(i)
+        scene.set_intensity(i, f32(intensity))
+    g = scene.add_infinite_plane((0.0, 0.0, 0.0), (0.0, 0.0, 1.0), (1.0, 0.0, 0.0))
+    scene.set_reflective(g, 0.5)
+    scene.set_diffuse(g, 0.5)
+    scene.set_checkerboard(g, (1, 1, 1), (0, 0, 0), 3.0, 3.0)
+    for a in range(n):
+        for b in range(n):
+            i = scene.add_sphere((f32((a - (n - 1) * 0.5) * spacing), f32(6.0 + b * spacing), f32(radius)), f32(radius))
+            scene.set_color(i, PALETTE[(a * n + b) % 6])
+            if (a + b) % 2 == 0:
+                scene.set_reflective(i, 1.0)
+                scene.set_diffuse(i, 0.0)
+            elif (a + b) % 3 == 0:
+                scene.set_specular(i, 0.5)
     scene.set_object_indices(0, 1)
     scene.camera_two_mirrors()
     return scene

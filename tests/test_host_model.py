@@ -18,7 +18,9 @@ def same3(a, b):
     return [bits(v) for v in a] == [bits(v) for v in b]
 
 
-def compare(host, orc):
+def compare(host, orc, eye_rays=True):
+    """eye_rays=False: a camera copied onto the flattened description (cameras.put()), which the model's own Camera -- the one
+    that makes eye rays -- does not know"""
     d = host.desc.contents
     assert d.n_objects == orc.object_count == host.object_count
     assert (d.shadow_begin, d.shadow_end) == orc.shadow_range()
@@ -54,7 +56,7 @@ def compare(host, orc):
     assert same3(c.vector_horizontal, oc.vector_horizontal.tuple())
     assert same3(c.vector_vertical, oc.vector_vertical.tuple())
     assert same3(c.eye_origin, oc.eye_origin.tuple())
-    for dx, dy in ((0.0, 0.0), (0.5, 0.5), (0.123, 0.987), (1.0, 0.0)):
+    for dx, dy in () if not eye_rays else ((0.0, 0.0), (0.5, 0.5), (0.123, 0.987), (1.0, 0.0)):
         ho, hd = host.eye_ray(dx, dy)
         oo, od = orc.eye_ray(dx, dy)
         assert same3(ho, oo) and same3(hd, od)

@@ -73,12 +73,20 @@ def build(name, shading, host):
 class World:
     """one scene with one shading: the description the renderers are made from and the references' scene"""
 
-    def __init__(self, name, shading):
+    def __init__(self, name, shading, builder=None, area=None):
+        """builder(scene) -> the scene it has built on a fresh HostScene / OracleScene, in place of the scene `name` (without
+        glass or images); area: (samples, radius) of the area lights -- every light of a builder's scene -- in place of AREA[name]"""
         self.name, self.shading = name, shading
-        host, self.glass = build(name, shading, True)
-        self.orc, _ = build(name, shading, False)
-        n, r = AREA[name]
-        self.area = [(k, n, r) for k in (0, 1)] if "_soft" in shading else []
+        if builder is None:
+            host, self.glass = build(name, shading, True)
+            self.orc, _ = build(name, shading, False)
+            lights = (0, 1)
+        else:
+            host, self.glass = builder(HostScene.empty()), []
+            self.orc = builder(oracle.OracleScene())
+            lights = [k for k in range(self.orc.object_count) if self.orc.get_object(k).is_light]
+        n, r = area or AREA[name]
+        self.area = [(k, n, r) for k in lights] if "_soft" in shading else []
         self.seed = 5 if shading == "_refract_soft" else 0
         self.desc = Desc(host)
         self.images, self.image_of = None, {}

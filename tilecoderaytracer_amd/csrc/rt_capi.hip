@@ -1116,9 +1116,12 @@ bool primary_table(const rt_scene *s, const rt_camera_desc *cam, int W, int H, u
     const double m[3][3] = {{w0[0], ch[0], cv[0]}, {w0[1], ch[1], cv[1]}, {w0[2], ch[2], cv[2]}};
     const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
                        m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-    double scale = 0.0;
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) scale = std::max(scale, std::fabs(m[r][c]));
-    if (!std::isfinite(det) || !(std::fabs(det) > 1e-9 * scale * scale * scale) || scale == 0.0) return false;
+    /* degenerate: |det| against the product of the columns' magnitudes, each column on its own -- w0 is a length and ch, cv are
+     * directions, so one magnitude for all three refused every camera whose screen is more than 3e4 before the eye (a room of
+     * 1e5 under tests/placement.py's "large"), whatever its shape */
+    double scale = 1.0;
+    for (int c = 0; c < 3; ++c) scale *= std::max(std::max(std::fabs(m[0][c]), std::fabs(m[1][c])), std::fabs(m[2][c]));
+    if (!std::isfinite(det) || !(std::fabs(det) > 1e-9 * scale) || scale == 0.0) return false;
     double inv[3][3];
     inv[0][0] = (m[1][1] * m[2][2] - m[1][2] * m[2][1]) / det; inv[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det; inv[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det;
     inv[1][0] = (m[1][2] * m[2][0] - m[1][0] * m[2][2]) / det; inv[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det; inv[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det;
