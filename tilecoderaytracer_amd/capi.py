@@ -65,6 +65,20 @@ class RtAoParams(C.Structure):
                 ("channels", C.c_int32)]
 
 
+class RtAdaptiveParams(C.Structure):
+    """include/rt_capi_adaptive.h: k (1, 2 or 4), flag_all (0 / 1), the most flagged pixels a launch traces (0: the default),
+    the colour threshold (finite, >= 0) and the normals' cosine (-1..1) of the flag test."""
+    _fields_ = [("samples", C.c_int32), ("flag_all", C.c_int32), ("chunk_pixels", C.c_int32), ("color_threshold", C.c_float),
+                ("normal_cos", C.c_float)]
+
+
+class RtAdaptiveInfo(C.Structure):
+    """include/rt_capi_adaptive.h: the scene's last rt_render_adaptive* call -- strip pixels, of them refined, rays traced in the
+    second pass, its launches, and the four stages' HIP-event times."""
+    _fields_ = [("pixels", C.c_int64), ("flagged", C.c_int64), ("rays", C.c_int64), ("chunks", C.c_int32),
+                ("first_pass_ms", C.c_double), ("flag_ms", C.c_double), ("trace_ms", C.c_double), ("resolve_ms", C.c_double)]
+
+
 RT_TRANSFER_SRGB, RT_TRANSFER_LINEAR, RT_TRANSFER_CUSTOM = 0, 1, 2
 
 
@@ -262,6 +276,18 @@ def load_library():
         lib.rt_ambient_occlusion.argtypes = [vp, C.POINTER(RtAoParams), i, i, vp, vp]
         lib.rt_ambient_occlusion_device.argtypes = [vp, C.POINTER(RtAoParams), i, i, vp, vp, vp]
         lib.rt_ambient_occlusion.restype = lib.rt_ambient_occlusion_device.restype = i
+    # include/rt_capi_adaptive.h (likewise absent from older builds)
+    if hasattr(lib, "rt_render_adaptive"):
+        lib.rt_capi_adaptive_version.restype = i
+        lib.rt_adaptive_flags.argtypes = [i, C.POINTER(RtAdaptiveParams), i, i, vp, vp, vp]
+        lib.rt_adaptive_flags_device.argtypes = [i, C.POINTER(RtAdaptiveParams), i, i, vp, vp, vp, vp]
+        lib.rt_render_adaptive.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, C.POINTER(RtAdaptiveParams), vp, vp]
+        lib.rt_render_adaptive_device.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, C.POINTER(RtAdaptiveParams), vp, vp,
+                                                  vp]
+        lib.rt_get_adaptive_info.argtypes = [vp, C.POINTER(RtAdaptiveInfo)]
+        for name in ("rt_adaptive_flags", "rt_adaptive_flags_device", "rt_render_adaptive", "rt_render_adaptive_device",
+                     "rt_get_adaptive_info"):
+            getattr(lib, name).restype = i
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):
         lib.rt_capi_launch_version.restype = i

@@ -26,6 +26,11 @@
  *                       rays' records (rt_render_gbuffer), N x N directions per pixel (1..8) followed for RADIUS (default 1.0),
  *                       seed 0, three equal channels, encoded by rt_encode_image with the LINEAR table, the top row first; one
  *                       GPU, no supersampling.  The two options come together; the frame itself is the one rendered without them
+ *   --adaptive K[:COLOR[:COS]]  K x K samples only for the pixels an edge passes through (rt_render_adaptive: K = 1, 2, 4; a pixel
+ *                       is refined when it differs from another corner of its footprint in object, by a normal cosine below COS
+ *                       (default 0.9, -1..1) or by more than COLOR in a colour channel (default 1/32, >= 0)); one GPU, instead
+ *                       of --ssaa, without --hits, --denoise or --ao.  Composes with --ppm as --ssaa does
+ *   --adaptive-mask FILE  also the refined pixels as a binary PGM (255: refined), the top row first; needs --adaptive
  */
 #include <chrono>
 #include <cmath>
@@ -37,6 +42,7 @@
 #include <vector>
 
 #include "../../../include/rt_capi.h"
+#include "../../../include/rt_capi_adaptive.h"
 #include "../../../include/rt_capi_ao.h"
 #include "../../../include/rt_capi_denoise.h"
 #include "../../../include/rt_capi_gbuffer.h"
@@ -58,7 +64,7 @@ static int usage(const char *argv0) {
                  "usage: %s [--width W] [--height H] [--depth D] [--scene 1|2|grid:N[:noshadow]]\n"
                  "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE] [--glass I:TF:IOR ...]\n"
                  "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n"
-                 "          [--ao N[:RADIUS] --ao-ppm FILE]\n", argv0);
+                 "          [--ao N[:RADIUS] --ao-ppm FILE] [--adaptive 1|2|4[:COLOR[:COS]] [--adaptive-mask FILE]]\n", argv0);
     return 1;
 }
 
@@ -67,6 +73,7 @@ int main(int argc, char **argv) {
     bool write_txt = true, has_exposure = false;
     std::string scene_name = "1", out_path = "raytracer_screen.txt", hits_path, ppm_path, exposure_arg, ao_arg, ao_ppm_path;
     std::vector<std::string> glass;              /* --glass I:TF:IOR: object I refractive (include/rt_capi_refract.h) */
+    std::string adaptive_arg, mask_path;         /* --adaptive K[:COLOR[:COS]], --adaptive-mask FILE (include/rt_capi_adaptive.h) */
     std::string denoise;                         /* --denoise IT[:SIGMA[:K]] (include/rt_capi_denoise.h) */
     std::vector<std::string> soft;               /* --soft I:N[:R]: light I an area light, N x N samples, radius R (include/rt_capi_soft.h) */
     for (int i = 1; i < argc; ++i) {
@@ -87,6 +94,8 @@ int main(int argc, char **argv) {
         else if (a == "--exposure" && i + 1 < argc) exposure_arg = argv[++i], has_exposure = true;
         else if (a == "--ao" && i + 1 < argc) ao_arg = argv[++i];
         else if (a == "--ao-ppm" && i + 1 < argc) ao_ppm_path = argv[++i];
+        else if (a == "--adaptive" && i + 1 < argc) adaptive_arg = argv[++i];
+        else if (a == "--adaptive-mask" && i + 1 < argc) mask_path = argv[++i];
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
@@ -126,6 +135,27 @@ int main(int argc, char **argv) {
         if (ao.samples < 1 || ao.samples > RT_AO_MAX_SAMPLES || !(ao.radius > 0.0f) || std::isinf(ao.radius)) return usage(argv[0]);
         if (gpus > 1 || ssaa > 1) return usage(argv[0]);       /* (one GPU; a supersampled frame has no records) */
     }
+    rt_adaptive_params ad = {0, 0, 0, 1.0f / 32.0f, 0.9f};
+    if (adaptive_arg.empty() && !mask_path.empty()) return usage(argv[0]);
+    if (!adaptive_arg.empty()) {
+        /* K, K:COLOR or K:COLOR:COS, and nothing else: what rt_render_adaptive would refuse is refused here */
+        char *end = nullptr;
+        const long k = std::strtol(adaptive_arg.c_str(), &end, 10);
+        if (end == adaptive_arg.c_str() || (*end != '\0' && *end != ':') || (k != 1 && k != 2 && k != 4)) return usage(argv[0]);
+        ad.samples = (int)k;
+        float *fields[2] = {&ad.color_threshold, &ad.normal_cos};
+        for (int f = 0; f < 2 && *end == ':'; ++f) {
+            const char *v = end + 1;
+            *fields[f] = std::strtof(v, &end);
+            if (end == v || (*end != '\0' && (*end != ':' || f == 1))) return usage(argv[0]);
+        }
+        if (*end != '\0') return usage(argv[0]);
+        if (!(ad.color_threshold >= 0.0f) || std::isinf(ad.color_threshold) || !(ad.normal_cos >= -1.0f && ad.normal_cos <= 1.0f))
+            return usage(argv[0]);
+        /* (one GPU; instead of --ssaa; the records stay inside the call) */
+        if (gpus > 1 || ssaa > 1 || !hits_path.empty() || !denoise.empty() || !ao_arg.empty()) return usage(argv[0]);
+    }
+    std::vector<uint8_t> mask;
     verbose() = true;                          /* console output like the reference's */
 
     if (gpus == 1) std::cout << "Single-Core RayTracing!" << std::endl << std::endl;
@@ -194,12 +224,26 @@ int main(int argc, char **argv) {
     const auto t0 = std::chrono::steady_clock::now();
     int rc;
     double kernel_ms = 0.0;
+    double camera_rays = (double)ssaa * (double)ssaa * (double)W * (double)H;       /* for the Mrays/s line */
     if (gpus == 1) {
         rt_scene *scene = nullptr;
         rc = flat.create(0, &scene);                /* with the scene's bitmap textures, refractions and area lights, if any */
-        if (rc == RT_OK) rc = ssaa > 1 ? rt_render_ssaa(scene, &cam, W, H, 0, W, depth, ssaa, pixels.data())
-                            : !hits.empty() ? rt_render_gbuffer(scene, &cam, W, H, 0, W, depth, pixels.data(), hits.data())
-                                            : rt_render(scene, &cam, W, H, 0, W, depth, pixels.data());
+        if (rc == RT_OK && ad.samples > 0) {
+            if (!mask_path.empty()) mask.assign((size_t)W * (size_t)H, 0);
+            rc = rt_render_adaptive(scene, &cam, W, H, 0, W, depth, &ad, pixels.data(), mask.empty() ? nullptr : mask.data());
+            rt_adaptive_info info;
+            if (rc == RT_OK && rt_get_adaptive_info(scene, &info) == RT_OK) {
+                camera_rays += (double)info.rays;
+                std::printf("Adaptive supersampling     : %lld of %lld pixels refined (%.1f %%), %lld rays in %d launch(es); first pass "
+                            "%f ms, flags %f ms, trace %f ms, resolve %f ms\n", (long long)info.flagged, (long long)info.pixels,
+                            100.0 * (double)info.flagged / (double)info.pixels, (long long)info.rays, info.chunks, info.first_pass_ms,
+                            info.flag_ms, info.trace_ms, info.resolve_ms);
+            }
+        } else if (rc == RT_OK) {
+            rc = ssaa > 1 ? rt_render_ssaa(scene, &cam, W, H, 0, W, depth, ssaa, pixels.data())
+               : !hits.empty() ? rt_render_gbuffer(scene, &cam, W, H, 0, W, depth, pixels.data(), hits.data())
+                               : rt_render(scene, &cam, W, H, 0, W, depth, pixels.data());
+        }
         if (rc == RT_OK) {
             rt_timing tm;
             if (rt_get_timing(scene, &tm) == RT_OK) kernel_ms = tm.last_kernel_ms;
@@ -262,7 +306,7 @@ int main(int argc, char **argv) {
     std::printf("Render call (s)            : %f\n", render_s);
     if (kernel_ms > 0.0)
         std::printf("Render kernel (ms)         : %f  (%.1f Mrays/s)%s\n", kernel_ms,
-                    (double)ssaa * (double)ssaa * (double)W * (double)H / (kernel_ms * 1e3), gpus > 1 ? "  [the GPU whose kernels took longest]" : "");
+                    camera_rays / (kernel_ms * 1e3), gpus > 1 ? "  [the GPU whose kernels took longest]" : "");
     std::printf("AverageRoundTime (us/pixel): %f\n", run_time_us / ((double)W * (double)H));
 
     if (!hits_path.empty()) {
@@ -287,6 +331,24 @@ int main(int argc, char **argv) {
         std::printf("Encode kernel (ms)         : %f  (sRGB, exposure %g)\n", encode_ms, (double)im.exposure);
         if (celio_write_screen_ppm(ppm_path.c_str(), W, H, image.data(), (uint64_t)W * 3u)) {
             std::fprintf(stderr, "cannot write %s\n", ppm_path.c_str());
+            return 1;
+        }
+    }
+    if (!mask_path.empty()) {
+        /* the flags as a binary PGM, the top row (z = H - 1) first, like the PPM writers' scanlines */
+        FILE *f = std::fopen(mask_path.c_str(), "wb");
+        bool ok = f != nullptr;
+        if (f) {
+            std::vector<uint8_t> row((size_t)W);
+            ok = std::fprintf(f, "P5\n%d %d\n255\n", W, H) > 0;
+            for (int z = H - 1; ok && z >= 0; --z) {
+                for (int x = 0; x < W; ++x) row[(size_t)x] = mask[(size_t)x * (size_t)H + (size_t)z] ? 255 : 0;
+                ok = std::fwrite(row.data(), 1, row.size(), f) == row.size();
+            }
+            ok = std::fclose(f) == 0 && ok;
+        }
+        if (!ok) {
+            std::fprintf(stderr, "cannot write %s\n", mask_path.c_str());
             return 1;
         }
     }

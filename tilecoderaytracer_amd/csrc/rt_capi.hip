@@ -28,6 +28,7 @@
 #include "../../include/rt_capi_refract.h"
 #include "../../include/rt_capi_soft.h"
 #include "../../include/rt_capi_tuning.h"
+#include "rt_internal.h"
 #include "rt_tables.h"
 
 /* the render kernels (rt_tables.h, RENDER KERNELS), as rt_kernel.hip defines them */
@@ -165,6 +166,9 @@ struct rt_scene {
     bool ev_ready = false;
     rt_timing timing{};
     rt_launch_info launch{};
+    uint64_t launch_seq = 0;                         /* render-kernel launches made (launch()) */
+    /* ADAPTIVE SUPERSAMPLING (include/rt_capi_adaptive.h): rt_adaptive.hip's scratch and its last call's bookkeeping */
+    RtAdaptiveState *adaptive = nullptr;
     char launch_kernel[RT_KERNEL_NAME_BYTES] = {};   /* the whole name; launch.kernel is its first 47 characters */
     std::mutex mu;
 };
@@ -1757,6 +1761,7 @@ int launch(rt_scene *s, LaunchRequest rq, hipStream_t stream) {
                             (size_t)plan.lds_bytes, stream));
     HIP_TRY(hipGetLastError());
     s->ev_next = next_slot;               /* (only now: a launch that did not happen has zeroed nothing) */
+    s->launch_seq += 1;
     HIP_TRY(hipEventRecord(s->ev[slot].stop, stream));
     s->ev[slot].pending = true;
     return RT_OK;
@@ -1866,13 +1871,14 @@ int batch_to_host(rt_scene *s, Call call, int n, int rows, const void *in, int m
                           {{out, s->d_fb, bytes}});
 }
 
-/* a device batch, enqueued on the caller's stream */
+/* a device batch, enqueued on the caller's stream; locked: the caller holds the handle's lock */
 int batch_on_device(rt_scene *s, Call call, int n, int rows, const void *d_in, int max_depth, void *d_out, void *hip_stream,
-                    const rt_ao_params *ao = nullptr) {
+                    const rt_ao_params *ao = nullptr, bool locked = false) {
     int n_cols = 0;
     int rc = rays_args(s, n, &rows, d_in, max_depth, d_out, &n_cols);
     if (rc || n == 0) return rc;
-    std::lock_guard<std::mutex> lock(s->mu);
+    std::unique_lock<std::mutex> lock(s->mu, std::defer_lock);
+    if (!locked) lock.lock();
     return launch(s, {.call = call, .n_rays = n, .d_rays = d_in, .W = n_cols, .H = rows, .x0 = 0, .x1 = n_cols, .max_depth = max_depth,
                       .d_out = d_out, .ao = ao},
                   static_cast<hipStream_t>(hip_stream));
@@ -1898,6 +1904,13 @@ int ao_args(const rt_scene *s, const rt_ao_params *a, int n, int rows, const voi
     return RT_OK;
 }
 
+/* columns x H pixels of colours and records together within the bytes of kMaxStripFloats floats */
+int gbuffer_size(long long columns, int H) {
+    if ((double)columns * (double)H * (double)(3 * sizeof(float) + sizeof(rt_hit)) > kMaxStripFloats * sizeof(float))
+        return fail(RT_ERR_INVALID, "strip too large for its colours and records");
+    return RT_OK;
+}
+
 /* rt_render_gbuffer*: the checks of include/rt_capi_gbuffer.h in its order, all before the device is touched -- rt_render's in
  * rt_render's order (the scene, check_strip()'s, check_launch_args()'s), then the records': out_hits, and the strip's
  * colours and records together within the bytes of kMaxStripFloats floats */
@@ -1908,9 +1921,7 @@ int gbuffer_args(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int
     if (rc == RT_OK) rc = check_launch_args(cam, W, H, x0, x1, max_depth, out_rgb);
     if (rc) return rc;
     if (x1 > x0 && !out_hits) return fail(RT_ERR_INVALID, "out_hits is NULL");
-    if ((double)(x1 - x0) * (double)H * (double)(3 * sizeof(float) + sizeof(rt_hit)) > kMaxStripFloats * sizeof(float))
-        return fail(RT_ERR_INVALID, "strip too large for its colours and records");
-    return RT_OK;
+    return gbuffer_size(x1 - x0, H);
 }
 
 /* rt_render_stats and rt_learn_tile_order (so: what the refusal means for the latter's caller): the counting build shades nothing */
@@ -1928,6 +1939,42 @@ extern "C" {
 
 /* used by rt_multi.hip to report through rt_last_error() */
 int rt_internal_set_error(int code, const char *msg) { return fail(code, msg ? msg : ""); }
+
+/* ---- rt_internal.h: the handle, the argument rules and the launches, for rt_adaptive.hip ---- */
+int rt_internal_check_frame(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
+                            const void *out_rgb) {
+    if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
+    const int rc = check_strip(W, H, x0, x1, out_rgb, true);
+    return rc ? rc : check_launch_args(cam, W, H, x0, x1, max_depth, out_rgb);
+}
+
+int rt_internal_check_virtual(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, int samples,
+                              const void *out_rgb) {
+    int kl = 0;
+    return ssaa_args(cam, W, H, x0, x1, max_depth, samples, out_rgb, &kl);
+}
+
+int rt_internal_check_gbuffer_size(long long columns, int H) { return gbuffer_size(columns, H); }
+
+void rt_internal_lock(rt_scene *s) { s->mu.lock(); }
+void rt_internal_unlock(rt_scene *s) { s->mu.unlock(); }
+int rt_internal_scene_device(const rt_scene *s) { return s->device; }
+int rt_internal_scene_soft(const rt_scene *s) { return s->soft_used ? 1 : 0; }
+RtAdaptiveState **rt_internal_adaptive_slot(rt_scene *s) { return &s->adaptive; }
+uint64_t rt_internal_launch_seq(const rt_scene *s) { return s->launch_seq; }
+
+int rt_internal_launch_gbuffer(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
+                               void *d_rgb, void *d_hits, void *hip_stream) {
+    return launch(s, {.call = kCallGbuffer, .cam = cam, .W = W, .H = H, .x0 = x0, .x1 = x1, .max_depth = max_depth, .d_out = d_rgb,
+                      .d_hits = d_hits},
+                  static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_internal_launch_rays(rt_scene *s, int n, int rows, const void *d_rays, int max_depth, void *d_out_rgb, void *hip_stream) {
+    return batch_on_device(s, kCallRays, n, rows, d_rays, max_depth, d_out_rgb, hip_stream, nullptr, true);
+}
+
+int rt_internal_grow(void **buf, size_t *bytes, size_t need) { return grow_device_buffer(buf, bytes, need); }
 
 int rt_capi_version(void) { return RT_CAPI_VERSION; }
 
@@ -2117,6 +2164,7 @@ int rt_scene_destroy(rt_scene *s) {
     if (s->d_stack) (void)hipFree(s->d_stack);
     if (s->h_error) (void)hipHostFree(s->h_error);
     if (s->d_timeline) (void)hipFree(s->d_timeline);
+    if (s->adaptive) rt_internal_adaptive_free(s->adaptive);
     delete s;
     return RT_OK;
 }
@@ -2374,6 +2422,9 @@ int rt_get_timing(const rt_scene *cs, rt_timing *out) {
             if (rc) return rc;
         }
     }
+    /* ADAPTIVE SUPERSAMPLING: while its call is the handle's last launch, the call's four stages (include/rt_capi_adaptive.h) */
+    const double adaptive_ms = s->adaptive ? rt_internal_adaptive_ms(s->adaptive, s->launch_seq) : -1.0;
+    if (adaptive_ms >= 0.0) s->timing.last_kernel_ms = adaptive_ms;
     *out = s->timing;
     return device_report(s);
 }

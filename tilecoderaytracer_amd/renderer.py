@@ -54,6 +54,27 @@ def denoise(rgb, hits, iterations=2, sigma_color=1.0, normal_squarings=3, device
     return out
 
 
+def adaptive_params(samples=2, color_threshold=1 / 32, normal_cos=0.9, flag_all=False, chunk_pixels=0):
+    """render_adaptive's keywords -> an RtAdaptiveParams (include/rt_capi_adaptive.h); the library checks the values."""
+    return capi.RtAdaptiveParams(int(samples), int(flag_all), int(chunk_pixels), float(color_threshold), float(normal_cos))
+
+
+def adaptive_flags(rgb, hits, color_threshold=1 / 32, normal_cos=0.9, flag_all=False, device=0):
+    """Which pixels of a rectangle an edge passes through (include/rt_capi_adaptive.h, rt_adaptive_flags): rgb float32 (Wn, H, 3)
+    and hits HIT_DTYPE (Wn, H), as render_gbuffer() returns them -> bool (Wn, H): the pixel differs from one of the three other
+    corners of its footprint, (x+1, z), (x, z+1), (x+1, z+1), in object, in normal (cosine below normal_cos) or in a colour
+    channel (by more than color_threshold; a NaN flags).  Runs on GPU `device`; there is no CPU path."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or hits.shape != rgb.shape[:2]:
+        raise ValueError(f"rgb must be (Wn, H, 3) and hits (Wn, H), not {rgb.shape} and {hits.shape}")
+    params = adaptive_params(1, color_threshold, normal_cos, flag_all)
+    out = np.empty(rgb.shape[:2], dtype=np.uint8)
+    capi.check(capi.load_library().rt_adaptive_flags(int(device), C.byref(params), rgb.shape[0], rgb.shape[1], rgb.ctypes.data,
+                                                     hits.ctypes.data, out.ctypes.data))
+    return out.view(np.bool_)
+
+
 _TRANSFERS = {"srgb": capi.RT_TRANSFER_SRGB, "linear": capi.RT_TRANSFER_LINEAR, "custom": capi.RT_TRANSFER_CUSTOM}
 
 
@@ -195,6 +216,37 @@ class Renderer:
         HIP stream (no sync)."""
         capi.check(self._lib.rt_render_gbuffer_device(self._scene, self._cam, W, H, x0, x1, max_depth, C.c_void_p(rgb_ptr),
                                                       C.c_void_p(hits_ptr), C.c_void_p(stream)))
+
+    def render_adaptive(self, W, H, max_depth, samples=2, color_threshold=1 / 32, normal_cos=0.9, flag_all=False, chunk_pixels=0,
+                        x0=0, x1=None, return_flags=False):
+        """Columns [x0, x1) of a W x H image, supersampled only where an edge passes (include/rt_capi_adaptive.h): one sample a
+        pixel with its hit record first, then samples x samples samples for the pixels adaptive_flags() marks -> float32
+        (x1-x0, H, 3), and with return_flags also bool (x1-x0, H).  The frame is where(flags, render_ssaa(..., samples),
+        render(...)) bit for bit; chunk_pixels (the most flagged pixels traced per launch, 0: the default) never changes it.
+        adaptive_info() tells how many pixels were refined and what each stage cost."""
+        x1 = W if x1 is None else x1
+        params = adaptive_params(samples, color_threshold, normal_cos, flag_all, chunk_pixels)
+        out = np.empty((max(x1 - x0, 0), H, 3), dtype=np.float32)
+        flags = np.zeros((max(x1 - x0, 0), H), dtype=np.uint8) if return_flags else None
+        capi.check(self._lib.rt_render_adaptive(self._scene, self._cam, W, H, x0, x1, max_depth, C.byref(params), out.ctypes.data,
+                                                flags.ctypes.data if return_flags else None))
+        return (out, flags.view(np.bool_)) if return_flags else out
+
+    def render_adaptive_device(self, W, H, max_depth, x0, x1, device_ptr, flags_ptr=0, stream=0, samples=2, color_threshold=1 / 32,
+                               normal_cos=0.9, flag_all=False, chunk_pixels=0):
+        """An adaptive render into device memory on a HIP stream: colours (12 bytes a pixel) at device_ptr, the flags (a byte a
+        pixel) at flags_ptr unless that is 0.  The stream is synchronised once, after the flag pass (the host must know how many
+        pixels the second pass has), so the call cannot be captured into a graph; the second pass is only enqueued."""
+        params = adaptive_params(samples, color_threshold, normal_cos, flag_all, chunk_pixels)
+        capi.check(self._lib.rt_render_adaptive_device(self._scene, self._cam, W, H, x0, x1, max_depth, C.byref(params),
+                                                       C.c_void_p(device_ptr), C.c_void_p(flags_ptr or None), C.c_void_p(stream)))
+
+    def adaptive_info(self):
+        """The last render_adaptive*() of this scene (include/rt_capi_adaptive.h, rt_adaptive_info): pixels, flagged, rays,
+        chunks and the four stage times."""
+        info = capi.RtAdaptiveInfo()
+        capi.check(self._lib.rt_get_adaptive_info(self._scene, C.byref(info)))
+        return info
 
     def render_denoised(self, W, H, max_depth, iterations=2, sigma_color=1.0, normal_squarings=3):
         """A W x H G-buffer frame filtered on the GPU where it was rendered (include/rt_capi_denoise.h): rt_render_gbuffer_device
