@@ -79,6 +79,20 @@ class RtAdaptiveInfo(C.Structure):
                 ("first_pass_ms", C.c_double), ("flag_ms", C.c_double), ("trace_ms", C.c_double), ("resolve_ms", C.c_double)]
 
 
+class RtLensParams(C.Structure):
+    """include/rt_capi_lens.h: n (n x n samples per pixel, 1..8), the most columns a launch traces (0: the default), the seed,
+    the lens radius (finite, >= 0) and the focal plane's distance as a multiple of the screen's (finite, > 0)."""
+    _fields_ = [("samples", C.c_int32), ("chunk_columns", C.c_int32), ("seed", C.c_uint32), ("aperture", C.c_float),
+                ("focus", C.c_float)]
+
+
+class RtLensInfo(C.Structure):
+    """include/rt_capi_lens.h: the scene's last rt_render_lens* call -- strip pixels, rays traced, chunks of columns, and the
+    three stages' HIP-event times."""
+    _fields_ = [("pixels", C.c_int64), ("rays", C.c_int64), ("chunks", C.c_int32), ("raygen_ms", C.c_double),
+                ("trace_ms", C.c_double), ("resolve_ms", C.c_double)]
+
+
 RT_TRANSFER_SRGB, RT_TRANSFER_LINEAR, RT_TRANSFER_CUSTOM = 0, 1, 2
 
 
@@ -287,6 +301,16 @@ def load_library():
         lib.rt_get_adaptive_info.argtypes = [vp, C.POINTER(RtAdaptiveInfo)]
         for name in ("rt_adaptive_flags", "rt_adaptive_flags_device", "rt_render_adaptive", "rt_render_adaptive_device",
                      "rt_get_adaptive_info"):
+            getattr(lib, name).restype = i
+    # include/rt_capi_lens.h (likewise absent from older builds)
+    if hasattr(lib, "rt_render_lens"):
+        lib.rt_capi_lens_version.restype = i
+        lib.rt_lens_rays.argtypes = [C.POINTER(RtCameraDesc), i, i, i, i, C.POINTER(RtLensParams), i, vp]
+        lib.rt_lens_rays_device.argtypes = [C.POINTER(RtCameraDesc), i, i, i, i, C.POINTER(RtLensParams), i, vp, vp]
+        lib.rt_render_lens.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, C.POINTER(RtLensParams), vp]
+        lib.rt_render_lens_device.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, C.POINTER(RtLensParams), vp, vp]
+        lib.rt_get_lens_info.argtypes = [vp, C.POINTER(RtLensInfo)]
+        for name in ("rt_lens_rays", "rt_lens_rays_device", "rt_render_lens", "rt_render_lens_device", "rt_get_lens_info"):
             getattr(lib, name).restype = i
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):

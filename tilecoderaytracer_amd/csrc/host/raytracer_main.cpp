@@ -31,6 +31,10 @@
  *                       (default 0.9, -1..1) or by more than COLOR in a colour channel (default 1/32, >= 0)); one GPU, instead
  *                       of --ssaa, without --hits, --denoise or --ao.  Composes with --ppm as --ssaa does
  *   --adaptive-mask FILE  also the refined pixels as a binary PGM (255: refined), the top row first; needs --adaptive
+ *   --lens N[:APERTURE[:FOCUS[:SEED]]]  depth of field (rt_render_lens): N x N samples per pixel (1..8), each from its own point of a
+ *                       lens of radius APERTURE (>= 0, default 0) through the focal plane at FOCUS times the screen's distance
+ *                       (> 0, default 1), lens points hashed with SEED (default 0); one GPU, instead of --ssaa and --adaptive,
+ *                       without --hits, --denoise or --ao.  Composes with --ppm and --out as --ssaa does
  */
 #include <chrono>
 #include <cmath>
@@ -47,6 +51,7 @@
 #include "../../../include/rt_capi_denoise.h"
 #include "../../../include/rt_capi_gbuffer.h"
 #include "../../../include/rt_capi_image.h"
+#include "../../../include/rt_capi_lens.h"
 #include "../../../include/rt_capi_ssaa.h"
 #include "celio_model.hpp"
 #include "screen_ppm.hpp"
@@ -64,7 +69,8 @@ static int usage(const char *argv0) {
                  "usage: %s [--width W] [--height H] [--depth D] [--scene 1|2|grid:N[:noshadow]]\n"
                  "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE] [--glass I:TF:IOR ...]\n"
                  "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n"
-                 "          [--ao N[:RADIUS] --ao-ppm FILE] [--adaptive 1|2|4[:COLOR[:COS]] [--adaptive-mask FILE]]\n", argv0);
+                 "          [--ao N[:RADIUS] --ao-ppm FILE] [--adaptive 1|2|4[:COLOR[:COS]] [--adaptive-mask FILE]]\n"
+                 "          [--lens N[:APERTURE[:FOCUS[:SEED]]]]\n", argv0);
     return 1;
 }
 
@@ -74,6 +80,7 @@ int main(int argc, char **argv) {
     std::string scene_name = "1", out_path = "raytracer_screen.txt", hits_path, ppm_path, exposure_arg, ao_arg, ao_ppm_path;
     std::vector<std::string> glass;              /* --glass I:TF:IOR: object I refractive (include/rt_capi_refract.h) */
     std::string adaptive_arg, mask_path;         /* --adaptive K[:COLOR[:COS]], --adaptive-mask FILE (include/rt_capi_adaptive.h) */
+    std::string lens_arg;                        /* --lens N[:APERTURE[:FOCUS[:SEED]]] (include/rt_capi_lens.h) */
     std::string denoise;                         /* --denoise IT[:SIGMA[:K]] (include/rt_capi_denoise.h) */
     std::vector<std::string> soft;               /* --soft I:N[:R]: light I an area light, N x N samples, radius R (include/rt_capi_soft.h) */
     for (int i = 1; i < argc; ++i) {
@@ -96,6 +103,7 @@ int main(int argc, char **argv) {
         else if (a == "--ao-ppm" && i + 1 < argc) ao_ppm_path = argv[++i];
         else if (a == "--adaptive" && i + 1 < argc) adaptive_arg = argv[++i];
         else if (a == "--adaptive-mask" && i + 1 < argc) mask_path = argv[++i];
+        else if (a == "--lens" && i + 1 < argc) lens_arg = argv[++i];
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
@@ -154,6 +162,34 @@ int main(int argc, char **argv) {
             return usage(argv[0]);
         /* (one GPU; instead of --ssaa; the records stay inside the call) */
         if (gpus > 1 || ssaa > 1 || !hits_path.empty() || !denoise.empty() || !ao_arg.empty()) return usage(argv[0]);
+    }
+    rt_lens_params lens = {0, 0, 0u, 0.0f, 1.0f};
+    if (!lens_arg.empty()) {
+        /* N, N:APERTURE, N:APERTURE:FOCUS or N:APERTURE:FOCUS:SEED, and nothing else: what rt_render_lens would refuse is
+         * refused here */
+        char *end = nullptr;
+        const long n = std::strtol(lens_arg.c_str(), &end, 10);
+        if (end == lens_arg.c_str() || (*end != '\0' && *end != ':') || n < 1 || n > 8) return usage(argv[0]);
+        lens.samples = (int)n;
+        float *fields[2] = {&lens.aperture, &lens.focus};
+        for (int f = 0; f < 2 && *end == ':'; ++f) {
+            const char *v = end + 1;
+            *fields[f] = std::strtof(v, &end);
+            if (end == v || (*end != '\0' && *end != ':')) return usage(argv[0]);
+        }
+        if (*end == ':') {
+            const char *v = end + 1;
+            if (*v < '0' || *v > '9') return usage(argv[0]);                 /* (no sign, no blank) */
+            const unsigned long long seed = std::strtoull(v, &end, 10);
+            if (end == v || *end != '\0' || seed > 0xffffffffull) return usage(argv[0]);
+            lens.seed = (uint32_t)seed;
+        }
+        if (*end != '\0') return usage(argv[0]);
+        if (!(lens.aperture >= 0.0f) || std::isinf(lens.aperture) || !(lens.focus > 0.0f) || std::isinf(lens.focus))
+            return usage(argv[0]);
+        /* (one GPU; instead of --ssaa and --adaptive; a lens frame has no records) */
+        if (gpus > 1 || ssaa > 1 || !adaptive_arg.empty() || !hits_path.empty() || !denoise.empty() || !ao_arg.empty())
+            return usage(argv[0]);
     }
     std::vector<uint8_t> mask;
     verbose() = true;                          /* console output like the reference's */
@@ -238,6 +274,16 @@ int main(int argc, char **argv) {
                             "%f ms, flags %f ms, trace %f ms, resolve %f ms\n", (long long)info.flagged, (long long)info.pixels,
                             100.0 * (double)info.flagged / (double)info.pixels, (long long)info.rays, info.chunks, info.first_pass_ms,
                             info.flag_ms, info.trace_ms, info.resolve_ms);
+            }
+        } else if (rc == RT_OK && lens.samples > 0) {
+            rc = rt_render_lens(scene, &cam, W, H, 0, W, depth, &lens, pixels.data());
+            rt_lens_info info;
+            if (rc == RT_OK && rt_get_lens_info(scene, &info) == RT_OK) {
+                camera_rays = (double)info.rays;
+                std::printf("Lens camera                : %d x %d samples, aperture %g, focus %g, seed %u: %lld rays in %d chunk(s); "
+                            "ray generation %f ms, trace %f ms, resolve %f ms\n", lens.samples, lens.samples, (double)lens.aperture,
+                            (double)lens.focus, lens.seed, (long long)info.rays, info.chunks, info.raygen_ms, info.trace_ms,
+                            info.resolve_ms);
             }
         } else if (rc == RT_OK) {
             rc = ssaa > 1 ? rt_render_ssaa(scene, &cam, W, H, 0, W, depth, ssaa, pixels.data())

@@ -286,6 +286,10 @@ struct RtAdaptiveState {
     rt_adaptive_info info{};
 };
 
+/* the unit's place in the handle (rt_internal.h): how its state is freed, and its last call's stage times */
+extern "C" void rt_internal_adaptive_free(RtAdaptiveState *a);
+extern "C" double rt_internal_adaptive_ms(RtAdaptiveState *a, uint64_t seq);
+
 namespace {
 
 int grow(RtAdaptiveState::Buffer &b, size_t need) { return rt_internal_grow(&b.p, &b.bytes, need); }
@@ -346,9 +350,13 @@ long long chunk_size(const rt_adaptive_params &pr) {
 }
 
 RtAdaptiveState *state_of(rt_scene *s) {
-    RtAdaptiveState **slot = rt_internal_adaptive_slot(s);
-    if (!*slot) *slot = new RtAdaptiveState();
-    return *slot;
+    rt_internal_unit *slot = rt_internal_unit_slot(s, RT_INTERNAL_UNIT_ADAPTIVE);
+    if (!slot->state) {
+        slot->state = new RtAdaptiveState();
+        slot->free_state = [](void *a) { rt_internal_adaptive_free(static_cast<RtAdaptiveState *>(a)); };
+        slot->stage_ms = [](void *a, uint64_t seq) { return rt_internal_adaptive_ms(static_cast<RtAdaptiveState *>(a), seq); };
+    }
+    return static_cast<RtAdaptiveState *>(slot->state);
 }
 
 /* event number i of the call, recorded on stream */
@@ -580,7 +588,7 @@ int rt_get_adaptive_info(const rt_scene *cs, rt_adaptive_info *out) {
     rt_scene *s = const_cast<rt_scene *>(cs);
     rt_internal_lock(s);
     Unlock unlock{s};
-    RtAdaptiveState *a = *rt_internal_adaptive_slot(s);
+    RtAdaptiveState *a = static_cast<RtAdaptiveState *>(rt_internal_unit_slot(s, RT_INTERNAL_UNIT_ADAPTIVE)->state);
     if (!a) {
         *out = rt_adaptive_info{};
         return RT_OK;

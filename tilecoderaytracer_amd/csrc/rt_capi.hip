@@ -167,8 +167,9 @@ struct rt_scene {
     rt_timing timing{};
     rt_launch_info launch{};
     uint64_t launch_seq = 0;                         /* render-kernel launches made (launch()) */
-    /* ADAPTIVE SUPERSAMPLING (include/rt_capi_adaptive.h): rt_adaptive.hip's scratch and its last call's bookkeeping */
-    RtAdaptiveState *adaptive = nullptr;
+    /* COMPOSED CALLS (rt_internal.h: include/rt_capi_adaptive.h, include/rt_capi_lens.h): each unit's scratch and its last
+     * call's bookkeeping, with the unit's way of freeing it and of telling its last call's stage times */
+    rt_internal_unit units[RT_INTERNAL_UNITS] = {};
     char launch_kernel[RT_KERNEL_NAME_BYTES] = {};   /* the whole name; launch.kernel is its first 47 characters */
     std::mutex mu;
 };
@@ -1940,12 +1941,16 @@ extern "C" {
 /* used by rt_multi.hip to report through rt_last_error() */
 int rt_internal_set_error(int code, const char *msg) { return fail(code, msg ? msg : ""); }
 
-/* ---- rt_internal.h: the handle, the argument rules and the launches, for rt_adaptive.hip ---- */
+/* ---- rt_internal.h: the handle, the argument rules and the launches, for rt_adaptive.hip and rt_lens.hip ---- */
+int rt_internal_check_strip(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *out_rgb) {
+    const int rc = check_strip(W, H, x0, x1, out_rgb, true);
+    return rc ? rc : check_launch_args(cam, W, H, x0, x1, max_depth, out_rgb);
+}
+
 int rt_internal_check_frame(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
                             const void *out_rgb) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
-    const int rc = check_strip(W, H, x0, x1, out_rgb, true);
-    return rc ? rc : check_launch_args(cam, W, H, x0, x1, max_depth, out_rgb);
+    return rt_internal_check_strip(cam, W, H, x0, x1, max_depth, out_rgb);
 }
 
 int rt_internal_check_virtual(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, int samples,
@@ -1960,7 +1965,7 @@ void rt_internal_lock(rt_scene *s) { s->mu.lock(); }
 void rt_internal_unlock(rt_scene *s) { s->mu.unlock(); }
 int rt_internal_scene_device(const rt_scene *s) { return s->device; }
 int rt_internal_scene_soft(const rt_scene *s) { return s->soft_used ? 1 : 0; }
-RtAdaptiveState **rt_internal_adaptive_slot(rt_scene *s) { return &s->adaptive; }
+rt_internal_unit *rt_internal_unit_slot(rt_scene *s, int unit) { return &s->units[unit]; }
 uint64_t rt_internal_launch_seq(const rt_scene *s) { return s->launch_seq; }
 
 int rt_internal_launch_gbuffer(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
@@ -2164,7 +2169,8 @@ int rt_scene_destroy(rt_scene *s) {
     if (s->d_stack) (void)hipFree(s->d_stack);
     if (s->h_error) (void)hipHostFree(s->h_error);
     if (s->d_timeline) (void)hipFree(s->d_timeline);
-    if (s->adaptive) rt_internal_adaptive_free(s->adaptive);
+    for (rt_internal_unit &u : s->units)
+        if (u.state) u.free_state(u.state);
     delete s;
     return RT_OK;
 }
@@ -2422,9 +2428,12 @@ int rt_get_timing(const rt_scene *cs, rt_timing *out) {
             if (rc) return rc;
         }
     }
-    /* ADAPTIVE SUPERSAMPLING: while its call is the handle's last launch, the call's four stages (include/rt_capi_adaptive.h) */
-    const double adaptive_ms = s->adaptive ? rt_internal_adaptive_ms(s->adaptive, s->launch_seq) : -1.0;
-    if (adaptive_ms >= 0.0) s->timing.last_kernel_ms = adaptive_ms;
+    /* COMPOSED CALLS: while one's call is the handle's last launch, the sum of that call's stages (include/rt_capi_adaptive.h,
+     * include/rt_capi_lens.h) */
+    for (rt_internal_unit &u : s->units) {
+        const double stages_ms = u.state ? u.stage_ms(u.state, s->launch_seq) : -1.0;
+        if (stages_ms >= 0.0) s->timing.last_kernel_ms = stages_ms;
+    }
     *out = s->timing;
     return device_report(s);
 }

@@ -1,7 +1,7 @@
 /*
  * rt_internal.h -- what the library's units ask of one another across their object files; nothing here is part of the ABI.
  * rt_capi.hip owns the handle (struct rt_scene), the argument rules and the launch policy -- one copy per rule -- and
- * rt_adaptive.hip (include/rt_capi_adaptive.h) composes them through the calls below.
+ * rt_adaptive.hip (include/rt_capi_adaptive.h) and rt_lens.hip (include/rt_capi_lens.h) compose them through the calls below.
  */
 #ifndef RT_INTERNAL_H_
 #define RT_INTERNAL_H_
@@ -11,30 +11,40 @@
 
 #include "../../include/rt_capi.h"
 
-struct RtAdaptiveState;               /* rt_adaptive.hip: the handle's scratch and the last call's bookkeeping */
-
 extern "C" {
+
+/* A composing unit's place in the handle: its state (the handle's scratch for it and its last call's bookkeeping), made by
+ * the unit on its first call; how rt_scene_destroy frees it; and the sum of its last call's stage times if that call made the
+ * handle's launch number seq, else < 0 -- what rt_get_timing() reports as last_kernel_ms while the unit's call is the
+ * handle's last launch. */
+typedef struct rt_internal_unit {
+    void *state;
+    void (*free_state)(void *state);
+    double (*stage_ms)(void *state, uint64_t seq);
+} rt_internal_unit;
+enum { RT_INTERNAL_UNIT_ADAPTIVE, RT_INTERNAL_UNIT_LENS, RT_INTERNAL_UNITS };
 
 /* rt_capi.hip: the text behind rt_last_error(); returns code */
 int rt_internal_set_error(int code, const char *msg);
 
-/* ---- rt_capi.hip, for rt_adaptive.hip ---- */
-/* rt_render's checks in rt_render's order (the scene, the strip, the camera, the depth, the strip's size), no device work */
+/* ---- rt_capi.hip, for rt_adaptive.hip and rt_lens.hip ---- */
+/* rt_render's checks in rt_render's order (the scene, the strip, the camera, the depth, the strip's size), no device work;
+ * rt_internal_check_strip: the same without the scene */
 int rt_internal_check_frame(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
                             const void *out_rgb);
+int rt_internal_check_strip(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *out_rgb);
 /* rt_render_ssaa's rule for the virtual size (samples 2 or 4: samples already checked) */
 int rt_internal_check_virtual(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, int samples,
                               const void *out_rgb);
 /* rt_render_gbuffer's size limit for columns x H pixels of colours and records */
 int rt_internal_check_gbuffer_size(long long columns, int H);
 /* the handle: its lock (held by the caller of everything below), its device, whether it has area lights, the place where it
- * keeps rt_adaptive.hip's state (freed by rt_scene_destroy through rt_internal_adaptive_free()), and the number of
- * render-kernel launches it has made */
+ * keeps a unit's state (RT_INTERNAL_UNIT_*), and the number of render-kernel launches it has made */
 void rt_internal_lock(rt_scene *s);
 void rt_internal_unlock(rt_scene *s);
 int rt_internal_scene_device(const rt_scene *s);
 int rt_internal_scene_soft(const rt_scene *s);
-RtAdaptiveState **rt_internal_adaptive_slot(rt_scene *s);
+rt_internal_unit *rt_internal_unit_slot(rt_scene *s, int unit);
 uint64_t rt_internal_launch_seq(const rt_scene *s);
 /* launch() of a G-buffer strip and of a ray batch (rt_render_gbuffer_device's and rt_trace_rays_device's, arguments checked by
  * the caller for the former and by the batch's own rules for the latter), under the caller's lock */
@@ -43,11 +53,6 @@ int rt_internal_launch_gbuffer(rt_scene *s, const rt_camera_desc *cam, int W, in
 int rt_internal_launch_rays(rt_scene *s, int n, int rows, const void *d_rays, int max_depth, void *d_out_rgb, void *hip_stream);
 /* a device buffer that only grows (the device is synchronised before the old one is freed) */
 int rt_internal_grow(void **buf, size_t *bytes, size_t need);
-
-/* ---- rt_adaptive.hip, for rt_capi.hip ---- */
-void rt_internal_adaptive_free(RtAdaptiveState *a);
-/* the sum of the last adaptive call's four stage times if that call made the handle's launch number seq, else < 0 */
-double rt_internal_adaptive_ms(RtAdaptiveState *a, uint64_t seq);
 
 }
 

@@ -75,6 +75,24 @@ def adaptive_flags(rgb, hits, color_threshold=1 / 32, normal_cos=0.9, flag_all=F
     return out.view(np.bool_)
 
 
+def lens_params(samples=4, aperture=0.0, focus=1.0, seed=0, chunk_columns=0):
+    """render_lens's keywords -> an RtLensParams (include/rt_capi_lens.h); the library checks the values."""
+    return capi.RtLensParams(int(samples), int(chunk_columns), int(seed) & 0xFFFFFFFF, float(aperture), float(focus))
+
+
+def lens_rays(camera, W, H, samples=4, aperture=0.0, focus=1.0, seed=0, x0=0, x1=None, device=0):
+    """The rays of a thin-lens camera (include/rt_capi_lens.h, rt_lens_rays): columns [x0, x1) of a W x H frame of camera (an
+    RtCameraDesc), samples x samples rays a pixel -> float32 (x1-x0, H, samples^2, 6), ray [x - x0, z, s] = {O.xyz, T.xyz}: from
+    its point of the lens through its target on the focal plane.  What render_lens() traces; trace_rays() takes them as they
+    are.  Runs on GPU `device`; there is no CPU path."""
+    x1 = W if x1 is None else x1
+    params = lens_params(samples, aperture, focus, seed)
+    S = params.samples ** 2 if 1 <= params.samples <= 8 else 1        # (a bad count is refused by the call below)
+    out = np.empty((max(x1 - x0, 0), max(H, 0), S, 6), dtype=np.float32)
+    capi.check(capi.load_library().rt_lens_rays(C.byref(camera), W, H, x0, x1, C.byref(params), int(device), out.ctypes.data))
+    return out
+
+
 _TRANSFERS = {"srgb": capi.RT_TRANSFER_SRGB, "linear": capi.RT_TRANSFER_LINEAR, "custom": capi.RT_TRANSFER_CUSTOM}
 
 
@@ -248,6 +266,33 @@ class Renderer:
         capi.check(self._lib.rt_get_adaptive_info(self._scene, C.byref(info)))
         return info
 
+    def render_lens(self, W, H, max_depth, samples=4, aperture=0.0, focus=1.0, seed=0, chunk_columns=0, x0=0, x1=None):
+        """Columns [x0, x1) of a W x H image through a thin lens (include/rt_capi_lens.h): samples x samples rays a pixel, each
+        from its own point of a lens of radius aperture through the focal plane at focus times the screen's distance, generated,
+        traced and averaged on the GPU -> float32 (x1-x0, H, 3).  aperture 0, focus 1 is render_ssaa(..., samples) bit for bit;
+        chunk_columns (the most columns traced per launch, 0: the default) never changes the frame.  lens_info() tells what
+        each stage cost."""
+        x1 = W if x1 is None else x1
+        params = lens_params(samples, aperture, focus, seed, chunk_columns)
+        out = np.empty((max(x1 - x0, 0), H, 3), dtype=np.float32)
+        capi.check(self._lib.rt_render_lens(self._scene, self._cam, W, H, x0, x1, max_depth, C.byref(params), out.ctypes.data))
+        return out
+
+    def render_lens_device(self, W, H, max_depth, x0, x1, device_ptr, stream=0, samples=4, aperture=0.0, focus=1.0, seed=0,
+                           chunk_columns=0):
+        """Enqueue a thin-lens render into device memory (12 bytes a pixel at device_ptr) on a HIP stream (no sync: nothing is
+        read back)."""
+        params = lens_params(samples, aperture, focus, seed, chunk_columns)
+        capi.check(self._lib.rt_render_lens_device(self._scene, self._cam, W, H, x0, x1, max_depth, C.byref(params),
+                                                   C.c_void_p(device_ptr), C.c_void_p(stream)))
+
+    def lens_info(self):
+        """The last render_lens*() of this scene (include/rt_capi_lens.h, rt_lens_info): pixels, rays, chunks and the three
+        stage times."""
+        info = capi.RtLensInfo()
+        capi.check(self._lib.rt_get_lens_info(self._scene, C.byref(info)))
+        return info
+
     def render_denoised(self, W, H, max_depth, iterations=2, sigma_color=1.0, normal_squarings=3):
         """A W x H G-buffer frame filtered on the GPU where it was rendered (include/rt_capi_denoise.h): rt_render_gbuffer_device
         and rt_denoise_device enqueued on one stream with no host wait between them, then one download -> (rgb float32
@@ -279,12 +324,14 @@ class Renderer:
         return rgb, hits, kernel_ms
 
     def render_image(self, W, H, max_depth, samples=1, channels=3, exposure=1.0, transfer="srgb", bottom_up=False,
-                     thresholds=None):
+                     thresholds=None, lens=None):
         """A W x H frame as 8-bit scanlines, encoded on the GPU where it was rendered (include/rt_capi_image.h): rt_render_device
         -- rt_render_ssaa_device for samples 2 or 4 -- and rt_encode_image_device enqueued on one stream with no host wait between
         them, then a download of the bytes alone -> uint8 (H, W, channels).  The result is encode_image(render(W, H, max_depth),
-        ...) bit for bit.  The device buffers and the stream are torch's, so the process must have imported torch before the
-        library was loaded."""
+        ...) bit for bit.  lens: None, or a dict of render_lens_device's keywords (aperture, focus, seed, chunk_columns; samples
+        if it names none is this call's): the frame is then rt_render_lens_device's (include/rt_capi_lens.h).  The device
+        buffers and the stream are torch's, so the process must have imported torch before the library was loaded
+        (INTEGRATION.md section 3)."""
         import torch
         device = int(self._device)
         params, table = image_params(channels, exposure, transfer, bottom_up, thresholds)
@@ -293,7 +340,9 @@ class Renderer:
             frame = torch.empty((W, H, 3), dtype=torch.float32, device="cuda")
             image = torch.empty((H, W, C_), dtype=torch.uint8, device="cuda")
             stream = torch.cuda.current_stream()
-            if samples == 1:
+            if lens is not None:
+                self.render_lens_device(W, H, max_depth, 0, W, frame.data_ptr(), stream.cuda_stream, **{"samples": samples, **lens})
+            elif samples == 1:
                 self.render_device(W, H, max_depth, 0, W, frame.data_ptr(), stream.cuda_stream)
             else:
                 self.render_ssaa_device(W, H, max_depth, samples, 0, W, frame.data_ptr(), stream.cuda_stream)
