@@ -1,0 +1,323 @@
+"""One diffuse bounce from hit records (include/rt_capi_indirect.h) on the GPU against its definition: rt_indirect_rays against
+indirect_ref.rays word for word, rt_indirect_diffuse against indirect_ref.resolve of the CPU oracle's colours and first hits of
+those rays where the oracle covers the scene, else of the GPU's own rt_trace_rays / rt_intersect_rays (pinned by their own
+tests).  Bar: BIT-EXACT."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import adaptive_frames
+import ao_ref
+import indirect_ref
+import poisoned
+from tilecoderaytracer_amd import HostScene, Renderer, RtError, capi, denoise, indirect_rays
+from tilecoderaytracer_amd.renderer import HIT_DTYPE
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+W61, H37 = 61, 37                       # partial tiles on both axes, an odd record count for the chunker
+STRIPS = ((0, 20), (20, 21), (21, 61))
+BUILTIN = indirect_ref.FRAMES[0]
+RAY_FIELDS = ("P.x", "P.y", "P.z", "T.x", "T.y", "T.z")
+
+
+def assert_same(got, want, what):
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    same = np.ascontiguousarray(got).view(np.uint32) == np.ascontiguousarray(want).view(np.uint32)
+    if not same.all():
+        bad = np.argwhere(~same.all(axis=-1))
+        raise AssertionError(f"{what}: {len(bad)} cells differ, first at {bad[0].tolist()}: gpu={got[tuple(bad[0])]} "
+                             f"ref={want[tuple(bad[0])]}")
+
+
+def records(frame=BUILTIN):
+    """the oracle's records of a frame, writable and C-contiguous"""
+    return np.array(indirect_ref.oracle_gather(*frame)[1], dtype=HIT_DTYPE, order="C")
+
+
+def own_reference(r, hits, kd, n, gather_depth, seed, emitters, gain=1.0, base=None):
+    """indirect_ref.resolve of the handle's own rt_trace_rays and rt_intersect_rays of indirect_ref's rays"""
+    rays, _ = indirect_ref.rays(hits, n, seed, 0)
+    flat = np.ascontiguousarray(rays.reshape(-1, 6))
+    colours = r.trace_rays(flat, gather_depth).reshape(hits.shape + (n * n, 3))
+    light = ((r.intersect_rays(flat)["flags"] & indirect_ref.HIT_LIGHT) != 0).reshape(hits.shape + (n * n,))
+    return indirect_ref.resolve(colours, light, kd, hits, gain, base, emitters)
+
+
+# ---- 1. ray generation ---------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n", [1, 2, 3, 8])
+def test_rays_are_the_definitions_word_for_word(n):
+    for name, hits, seed, key0 in (("frame", records(), 0, 0), ("handmade", indirect_ref.handmade_records(), 0xC0FFEE, 0xFFFFFFF0)):
+        want, live = indirect_ref.rays(hits, n, seed, key0)
+        assert 0 < live.sum() < live.size                                  # dead records present
+        assert_same(indirect_rays(hits, n, seed=seed, key0=key0), want, f"rays {name} n{n}")
+    hits = records()
+    whole = indirect_ref.rays(hits, n, 5, 0)[0]
+    for x0, x1 in STRIPS:                                                  # a strip with key0 = x0 * H: the frame's columns
+        assert_same(indirect_rays(np.ascontiguousarray(hits[x0:x1]), n, seed=5, key0=x0 * H37), whole[x0:x1], f"rays strip {x0}:{x1}")
+
+
+@pytest.mark.parametrize("n", [3, 8])
+def test_rays_device_entry_into_poisoned_words(n):
+    hits = indirect_ref.handmade_records()                                 # 130 records: no multiple of 256 / S
+    assert (len(hits) * n * n) % 256 != 0 and len(hits) % max(256 // (n * n), 1) != 0
+    want = indirect_ref.rays(hits, n, 5, 0xFFFFFFF0)[0]
+    what = f"rt_indirect_rays_device 130 records n{n}"
+    poisoned.assert_reference_has_no_sentinel(want, what)
+    d_hits = poisoned._on_device(hits.view(np.int32))
+    o = poisoned._Outputs([(want.size, 6, RAY_FIELDS, False)])
+    params = capi.RtIndirectParams(n, 1, 0, 0, 5, 0xFFFFFFF0, 1.0)
+    capi.check(capi.load_library().rt_indirect_rays_device(C.byref(params), len(hits), d_hits.data_ptr(), 0, o.ptrs()[0],
+                                                           poisoned._stream()))
+    got, = o.checked(Renderer(HostScene.builtin()), n * n, 0, 1, what)
+    assert_same(got.view(F).reshape(want.shape), want, what)
+
+
+# ---- 2. the term against the CPU oracle ----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("with_base", [False, True])
+@pytest.mark.parametrize("emitters", [False, True])
+@pytest.mark.parametrize("frame", indirect_ref.FRAMES + [indirect_ref.EMITTER_FRAME], ids=lambda f: f"{f[0]}{f[1]}x{f[2]}")
+def test_against_the_oracle(frame, emitters, with_base):
+    key, W, H, depth, n, seed, gather_depth = frame
+    rgb = indirect_ref.oracle_gather(*frame)[0]
+    want = indirect_ref.oracle_term(frame, emitters, with_base)
+    r = Renderer(adaptive_frames.host_scene(key))
+    got = r.indirect_diffuse(records(frame), n, gather_depth, seed=seed, emitters=emitters, base=rgb if with_base else None)
+    assert_same(got, want, f"{key} {W}x{H} n{n} emitters {emitters} base {with_base}")
+    info = r.indirect_info()
+    assert (info.records, info.rays, info.chunks) == (W * H, W * H * n * n, 1)
+    assert (info.query_ms > 0) == (not emitters)
+    assert r.launch_info().kernel.decode().endswith("_rays" if emitters else "_hits")
+
+
+# ---- 3. the conditions, on the reference: a test above must not pass on an empty term -------------------------------------------
+
+@pytest.mark.parametrize("frame", indirect_ref.CONDITION_FRAMES, ids=lambda f: f"{f[0]}{f[1]}x{f[2]}")
+def test_the_compared_terms_are_not_empty(frame):
+    indirect_ref.check_conditions(frame)
+
+
+def test_the_emitters_flag_changes_at_least_a_hundred_records():
+    indirect_ref.check_emitter_frame()
+
+
+# ---- 4. scenes the oracle does not cover: the handle's own ray batches and queries -----------------------------------------------
+
+def test_an_image_textured_scene_against_its_own_ray_batches():
+    import texture_ref
+    from test_texture_gpu import Desc, image_planes
+    host, floor, wall = image_planes(HostScene.empty())
+    texels = np.random.RandomState(5).uniform(0, 1, (16, 16, 3)).astype(F)
+    d = Desc(host)
+    d.objs[floor].texture = 0
+    d.objs[wall].texture = 0
+    r = d.make(images=[(texels, F(5.0), F(3.5), texture_ref.REPEAT)])
+    kd = np.array([d.objs[i].diffuse for i in range(d.n)], dtype=F)
+    W, H, depth, n = 45, 34, 3, 3
+    rgb, hits = r.render_gbuffer(W, H, depth)
+    for emitters in (False, True):
+        want = own_reference(r, hits, kd, n, 2, 3, emitters, 1.25, rgb)
+        got = r.indirect_diffuse(hits, n, 2, 1.25, seed=3, emitters=emitters, base=rgb)
+        assert_same(got, want, f"image planes emitters {emitters}")
+    assert r.kernel_name() == "rt_render_kernel_rays_image"
+    term = r.indirect_diffuse(hits, n, 2, 1.25, seed=3)
+    assert (term != 0).any() and indirect_ref.distinct_colours(term) >= 50
+    assert len(np.unique(hits["color"][hits["object"] == floor], axis=0)) > 10        # the weights are texels
+
+
+def test_a_refractive_scene_against_its_own_ray_batches():
+    from test_refract_gpu import glass_builtin, make
+    from test_texture_gpu import Desc
+    host = HostScene.builtin()
+    refr = glass_builtin(host)
+    d = Desc(host)
+    r = make(d, refractive=refr)
+    kd = np.array([d.objs[i].diffuse for i in range(d.n)], dtype=F)
+    W, H, depth, n = 48, 36, 4, 2
+    rgb, hits = r.render_gbuffer(W, H, depth)
+    for emitters in (False, True):
+        want = own_reference(r, hits, kd, n, 3, 0, emitters, 1.0, rgb)
+        got = r.indirect_diffuse(hits, n, 3, seed=0, emitters=emitters, base=rgb)
+        assert_same(got, want, f"glass emitters {emitters}")
+    assert r.kernel_name() == "rt_render_kernel_rays_refract"
+    term = r.indirect_diffuse(hits, n, 3, seed=0)
+    assert (term != 0).any() and indirect_ref.distinct_colours(term) >= 50
+
+
+# ---- 5. chunks and strips -------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n,emitters", [(3, False), (2, True)])
+def test_chunks_and_strips_never_change_a_bit(n, emitters):
+    r = Renderer(HostScene.builtin())
+    hits = records()
+    N, S = hits.size, n * n
+    kw = dict(samples=n, gather_depth=2, seed=11, emitters=emitters)
+    want = r.indirect_diffuse(hits, **kw)
+    assert r.indirect_info().chunks == 1
+    group = 1024 // S                                                      # the resolve kernel's records a workgroup
+    # a column; chunks that are no multiple of the group; a last chunk of one record; the default
+    for chunk in (H37, 7, 1013, (N - 1) // 2, 0):
+        assert chunk == 0 or chunk % group != 0
+        got = r.indirect_diffuse(hits, chunk_records=chunk, **kw)
+        assert_same(got, want, f"n{n} chunk_records {chunk}")
+        info = r.indirect_info()
+        assert info.chunks == (-(-N // chunk) if chunk else 1), (chunk, info.chunks)
+        assert (info.records, info.rays) == (N, N * S)
+    assert N % ((N - 1) // 2) == 1
+    parts = [r.indirect_diffuse(np.ascontiguousarray(hits[x0:x1]), key0=x0 * H37, chunk_records=13 * H37, **kw) for x0, x1 in STRIPS]
+    assert r.indirect_info().records == 40 * H37 and r.indirect_info().chunks == 4
+    assert_same(np.concatenate(parts), want, f"n{n} strips")
+    assert r.indirect_diffuse(hits[:0], **kw).shape == (0, H37, 3)             # an empty batch launches nothing
+
+
+# ---- 6. the base, in place and out of place, on a stream into poisoned outputs ---------------------------------------------------
+
+@pytest.mark.parametrize("n,emitters,chunk", [(3, False, 0), (2, True, 7 * H37), (4, False, 1013)])
+def test_the_base_in_place_and_out_of_place(n, emitters, chunk):
+    import torch
+    r = Renderer(HostScene.builtin())
+    rgb, hits = np.array(indirect_ref.oracle_gather(*BUILTIN)[0]), records()
+    hits["object"][5, 7] = -1                                              # more dead records than the frame's three
+    hits["flags"][40, 2] |= indirect_ref.HIT_LIGHT
+    N = hits.size
+    live = ao_ref.live_records(hits).reshape(hits.shape)
+    kw = dict(samples=n, gather_depth=1, gain=0.75, seed=4, emitters=emitters, chunk_records=chunk)
+    term = r.indirect_diffuse(hits, **kw)
+    assert not term[~live].view(np.uint32).any() and (term[live] != 0).any()           # a dead record, no base: +0.0
+    want = rgb + term                                                      # numpy fp32: one add a word
+    assert_same(r.indirect_diffuse(hits, base=rgb, **kw), want, "host, with a base")
+    assert_same(want[~live], rgb[~live], "dead records return the base")
+    d_hits = poisoned._on_device(hits.view(np.int32))
+    d_base = poisoned._on_device(rgb.view(np.int32))
+    for with_base in (True, False):
+        what = f"rt_indirect_diffuse_device 61x37 n={n} base {with_base}"
+        ref = want if with_base else term
+        poisoned.assert_reference_has_no_sentinel(ref, what)
+        o = poisoned._Outputs([(N * 3, 3, poisoned.RGB, False)])
+        r.indirect_diffuse_device(N, d_hits.data_ptr(), d_base.data_ptr() if with_base else 0, o.ptrs()[0], poisoned._stream(), **kw)
+        out, = o.checked(r, H37, 0, 1, what)                                # every word written, none beside
+        assert_same(out.view(F).reshape(ref.shape), ref, what)
+    assert np.array_equal(d_base.cpu().numpy().view(F).reshape(rgb.shape).view(np.uint32), rgb.view(np.uint32))   # the base unchanged
+    in_place = d_base.clone()
+    r.indirect_diffuse_device(N, d_hits.data_ptr(), in_place.data_ptr(), in_place.data_ptr(), poisoned._stream(), **kw)
+    torch.cuda.synchronize()
+    assert_same(in_place.cpu().numpy().view(F).reshape(rgb.shape), want, "in place")
+    info = r.indirect_info()
+    stages = (info.raygen_ms, info.trace_ms, info.query_ms, info.resolve_ms)
+    assert all(t > 0 for t in stages) if not emitters else (info.query_ms == 0 and info.raygen_ms > 0 and info.trace_ms > 0 and info.resolve_ms > 0)
+    assert r.timing().last_kernel_ms == pytest.approx(sum(stages), rel=1e-12)
+    r.render(W61, H37, 2)                                                  # another launch: the timing is that launch's again
+    assert r.timing().last_kernel_ms != pytest.approx(sum(stages), rel=1e-12)
+
+
+# ---- 7. refusals and quiet paths -------------------------------------------------------------------------------------------------
+
+def test_a_soft_shadow_scene_is_refused_and_the_handle_renders_on():
+    import oracle_lib
+    from test_soft_gpu import lights_of, make
+    from test_texture_gpu import Desc
+    area = [(i, 2, 0.6) for i in lights_of(oracle_lib.OracleScene.builtin())]
+    r = make(Desc(HostScene.builtin()), area)
+    W, H, depth = 40, 32, 2
+    before, hits = r.render_gbuffer(W, H, depth)
+    for kw in (dict(samples=2), dict(samples=1, emitters=True)):
+        with pytest.raises(RtError) as e:
+            r.indirect_diffuse(hits, **kw)
+        assert e.value.code == capi.RT_ERR_INVALID and "area lights" in e.value.message and "chunk_records" in e.value.message
+        assert "area lights" in capi.load_library().rt_last_error().decode()
+    with pytest.raises(RtError) as e:                                     # the last check: a misaligned base is reported before it
+        r.indirect_diffuse_device(hits.size, 0x10000, 0x10002, 0x10000)
+    assert e.value.code == capi.RT_ERR_INVALID and "d_base_rgb" in e.value.message
+    with pytest.raises(RtError) as e:
+        r.indirect_diffuse_device(hits.size, 0x10000, 0x10000, 0x10000)
+    assert e.value.code == capi.RT_ERR_INVALID and "area lights" in e.value.message
+    assert_same(r.render(W, H, depth), before, "the handle after the refusal")
+    hard = make(Desc(HostScene.builtin()), [])                            # rt_scene_create_soft without an area light: accepted
+    plain = Renderer(HostScene.builtin())
+    assert_same(hard.indirect_diffuse(hits, 2), plain.indirect_diffuse(hits, 2), "no area light")
+
+
+def test_an_empty_batch_launches_nothing_and_argument_errors_leave_the_handle_usable():
+    r = Renderer(HostScene.builtin())
+    hits = records()
+    want = r.indirect_diffuse(hits, 2)
+    launches = r.timing().launches
+    assert launches >= 2                                                   # a ray batch and a hit query
+    assert r.indirect_diffuse(hits[:0], 2).shape == (0, H37, 3)
+    r.indirect_diffuse_device(0, 0, 0, 0)                                   # n = 0 needs no pointers
+    assert r.timing().launches == launches
+    assert r.indirect_info().records == hits.size                           # still the last call that launched
+    for kw, word in ((dict(samples=9, gather_depth=-1), "samples"), (dict(gather_depth=-1, chunk_records=-1), "gather_depth"),
+                     (dict(chunk_records=-1, gain=float("nan")), "chunk_records"), (dict(gain=float("inf")), "gain")):
+        with pytest.raises(RtError) as e:
+            r.indirect_diffuse(hits, **kw)
+        assert e.value.code == capi.RT_ERR_INVALID and word in e.value.message, (kw, e.value.message)
+    with pytest.raises(RtError) as e:
+        r.indirect_diffuse_device(hits.size, 0x10008, 0, 0x10000)
+    assert e.value.code == capi.RT_ERR_INVALID and "16-byte" in e.value.message
+    assert r.timing().launches == launches
+    assert_same(r.indirect_diffuse(hits, 2), want, "after the refusals")
+    with pytest.raises(RtError) as e:
+        indirect_rays(hits, 2, device=99)
+    assert e.value.code == capi.RT_ERR_INVALID and "device index" in e.value.message
+
+
+# ---- 8. composition ---------------------------------------------------------------------------------------------------------------
+
+def test_render_indirect_is_the_composition_of_the_public_calls():
+    r = Renderer(HostScene.builtin())
+    W, H, depth = 40, 36, 3
+    kw = dict(samples=2, gather_depth=1, gain=1.0, seed=0)
+    rgb, hits = r.render_gbuffer(W, H, depth)
+    want = r.indirect_diffuse(hits, base=rgb, **kw)
+    assert_same(r.render_indirect(W, H, depth, **kw), want, "render_indirect")
+    assert indirect_ref.nonzero_share(want - rgb, hits) >= 0.5
+    emit = r.render_indirect(W, H, depth, samples=3, gather_depth=2, gain=0.5, seed=9, emitters=True)
+    assert_same(emit, r.indirect_diffuse(hits, 3, 2, 0.5, seed=9, emitters=True, base=rgb), "render_indirect, other keywords")
+    dn = dict(iterations=2, sigma_color=0.5, normal_squarings=3)
+    filtered = rgb + denoise(r.indirect_diffuse(hits, **kw), hits, **dn)
+    got = r.render_indirect(W, H, depth, denoise=dn, **kw)
+    assert_same(got, filtered, "render_indirect, denoised")
+    assert not np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def test_the_executable_writes_that_frame(tmp_path):
+    from tilecoderaytracer_amd.host import write_screen_txt
+    exe = os.path.join(ROOT, "tilecoderaytracer_amd", "bin", "tcrt_raytracer")
+    W, H, depth = 40, 36, 3
+    out_txt, plain_txt, want_txt = (tmp_path / name for name in ("out.txt", "plain.txt", "want.txt"))
+    common = [exe, "--width", str(W), "--height", str(H), "--depth", str(depth)]
+    p = subprocess.run(common + ["--indirect", "2", "--out", str(out_txt)], cwd=tmp_path, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "Indirect diffuse" in p.stdout, (p.returncode, p.stdout[-500:], p.stderr[-500:])
+    p = subprocess.run(common + ["--out", str(plain_txt)], cwd=tmp_path, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, (p.returncode, p.stdout[-500:], p.stderr[-500:])
+    write_screen_txt(str(want_txt), Renderer(HostScene.builtin()).render_indirect(W, H, depth, samples=2))
+    got_lines, want_lines = out_txt.read_text().splitlines()[10:], want_txt.read_text().splitlines()[10:]
+    assert len(got_lines) == W * H and got_lines == want_lines
+    assert got_lines != plain_txt.read_text().splitlines()[10:]
+
+
+# ---- 9. speed-only options ----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("options", [{"cull": 0}, {"fast": 0}, {"tables": 2}])
+@pytest.mark.parametrize("emitters", [False, True])
+def test_speed_only_options_never_change_a_bit(options, emitters):
+    key, W, H, depth, n, seed, gather_depth = BUILTIN
+    rgb = indirect_ref.oracle_gather(*BUILTIN)[0]
+    want = indirect_ref.oracle_term(BUILTIN, emitters, True)
+    r = Renderer(HostScene.builtin())
+    r.indirect_diffuse(records(), n, gather_depth, seed=seed, emitters=emitters, base=rgb)
+    default = r.kernel_name()
+    for name, value in options.items():
+        r.set_option(name, value)
+    got = r.indirect_diffuse(records(), n, gather_depth, seed=seed, emitters=emitters, base=rgb)
+    if emitters and "fast" not in options:                              # (the ray batch's kernel, as test_lens_gpu.py names them)
+        assert r.kernel_name() != default and r.kernel_name().endswith("_rays")
+    assert_same(got, want, f"{options} emitters {emitters}")

@@ -93,6 +93,21 @@ class RtLensInfo(C.Structure):
                 ("trace_ms", C.c_double), ("resolve_ms", C.c_double)]
 
 
+class RtIndirectParams(C.Structure):
+    """include/rt_capi_indirect.h: n (n x n gather rays per record, 1..8), the gather rays' max_depth, the most records a launch
+    gathers for (0: the default), emitters (0: a gather ray whose first hit is a light counts black; 1: as traced), the seed,
+    the first record's key and the term's gain (finite)."""
+    _fields_ = [("samples", C.c_int32), ("gather_depth", C.c_int32), ("chunk_records", C.c_int32), ("emitters", C.c_int32),
+                ("seed", C.c_uint32), ("key0", C.c_uint32), ("gain", C.c_float)]
+
+
+class RtIndirectInfo(C.Structure):
+    """include/rt_capi_indirect.h: the scene's last rt_indirect_diffuse* call -- its records, gather rays traced, chunks of
+    records, and the four stages' HIP-event times (query_ms 0 with emitters 1)."""
+    _fields_ = [("records", C.c_int64), ("rays", C.c_int64), ("chunks", C.c_int32), ("raygen_ms", C.c_double),
+                ("trace_ms", C.c_double), ("query_ms", C.c_double), ("resolve_ms", C.c_double)]
+
+
 RT_TRANSFER_SRGB, RT_TRANSFER_LINEAR, RT_TRANSFER_CUSTOM = 0, 1, 2
 
 
@@ -311,6 +326,17 @@ def load_library():
         lib.rt_render_lens_device.argtypes = [vp, C.POINTER(RtCameraDesc), i, i, i, i, i, C.POINTER(RtLensParams), vp, vp]
         lib.rt_get_lens_info.argtypes = [vp, C.POINTER(RtLensInfo)]
         for name in ("rt_lens_rays", "rt_lens_rays_device", "rt_render_lens", "rt_render_lens_device", "rt_get_lens_info"):
+            getattr(lib, name).restype = i
+    # include/rt_capi_indirect.h (likewise absent from older builds)
+    if hasattr(lib, "rt_indirect_diffuse"):
+        lib.rt_capi_indirect_version.restype = i
+        lib.rt_indirect_rays.argtypes = [C.POINTER(RtIndirectParams), i, vp, i, vp]
+        lib.rt_indirect_rays_device.argtypes = [C.POINTER(RtIndirectParams), i, vp, i, vp, vp]
+        lib.rt_indirect_diffuse.argtypes = [vp, C.POINTER(RtIndirectParams), i, vp, vp, vp]
+        lib.rt_indirect_diffuse_device.argtypes = [vp, C.POINTER(RtIndirectParams), i, vp, vp, vp, vp]
+        lib.rt_get_indirect_info.argtypes = [vp, C.POINTER(RtIndirectInfo)]
+        for name in ("rt_indirect_rays", "rt_indirect_rays_device", "rt_indirect_diffuse", "rt_indirect_diffuse_device",
+                     "rt_get_indirect_info"):
             getattr(lib, name).restype = i
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):

@@ -35,6 +35,11 @@
  *                       lens of radius APERTURE (>= 0, default 0) through the focal plane at FOCUS times the screen's distance
  *                       (> 0, default 1), lens points hashed with SEED (default 0); one GPU, instead of --ssaa and --adaptive,
  *                       without --hits, --denoise or --ao.  Composes with --ppm and --out as --ssaa does
+ *   --indirect N[:DEPTH[:GAIN[:SEED]]]  one diffuse bounce added to the frame (rt_render_gbuffer, then rt_indirect_diffuse on its
+ *                       records with the frame as the base): N x N gather rays per pixel (1..8) traced at depth DEPTH (>= 0,
+ *                       default 1), the term scaled by GAIN (finite, default 1), directions hashed with SEED (default 0); gather
+ *                       rays that meet a light first count black (emitters 0).  One GPU, instead of --ssaa, --adaptive and
+ *                       --lens, without --ao or --denoise.  Composes with --ppm and --out as --lens does
  */
 #include <chrono>
 #include <cmath>
@@ -51,6 +56,7 @@
 #include "../../../include/rt_capi_denoise.h"
 #include "../../../include/rt_capi_gbuffer.h"
 #include "../../../include/rt_capi_image.h"
+#include "../../../include/rt_capi_indirect.h"
 #include "../../../include/rt_capi_lens.h"
 #include "../../../include/rt_capi_ssaa.h"
 #include "celio_model.hpp"
@@ -70,7 +76,7 @@ static int usage(const char *argv0) {
                  "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE] [--glass I:TF:IOR ...]\n"
                  "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n"
                  "          [--ao N[:RADIUS] --ao-ppm FILE] [--adaptive 1|2|4[:COLOR[:COS]] [--adaptive-mask FILE]]\n"
-                 "          [--lens N[:APERTURE[:FOCUS[:SEED]]]]\n", argv0);
+                 "          [--lens N[:APERTURE[:FOCUS[:SEED]]]] [--indirect N[:DEPTH[:GAIN[:SEED]]]]\n", argv0);
     return 1;
 }
 
@@ -81,6 +87,7 @@ int main(int argc, char **argv) {
     std::vector<std::string> glass;              /* --glass I:TF:IOR: object I refractive (include/rt_capi_refract.h) */
     std::string adaptive_arg, mask_path;         /* --adaptive K[:COLOR[:COS]], --adaptive-mask FILE (include/rt_capi_adaptive.h) */
     std::string lens_arg;                        /* --lens N[:APERTURE[:FOCUS[:SEED]]] (include/rt_capi_lens.h) */
+    std::string indirect_arg;                    /* --indirect N[:DEPTH[:GAIN[:SEED]]] (include/rt_capi_indirect.h) */
     std::string denoise;                         /* --denoise IT[:SIGMA[:K]] (include/rt_capi_denoise.h) */
     std::vector<std::string> soft;               /* --soft I:N[:R]: light I an area light, N x N samples, radius R (include/rt_capi_soft.h) */
     for (int i = 1; i < argc; ++i) {
@@ -104,6 +111,7 @@ int main(int argc, char **argv) {
         else if (a == "--adaptive" && i + 1 < argc) adaptive_arg = argv[++i];
         else if (a == "--adaptive-mask" && i + 1 < argc) mask_path = argv[++i];
         else if (a == "--lens" && i + 1 < argc) lens_arg = argv[++i];
+        else if (a == "--indirect" && i + 1 < argc) indirect_arg = argv[++i];
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
@@ -191,6 +199,38 @@ int main(int argc, char **argv) {
         if (gpus > 1 || ssaa > 1 || !adaptive_arg.empty() || !hits_path.empty() || !denoise.empty() || !ao_arg.empty())
             return usage(argv[0]);
     }
+    rt_indirect_params ind = {0, 1, 0, 0, 0u, 0u, 1.0f};
+    if (!indirect_arg.empty()) {
+        /* N, N:DEPTH, N:DEPTH:GAIN or N:DEPTH:GAIN:SEED, and nothing else: what rt_indirect_diffuse would refuse is refused
+         * here */
+        char *end = nullptr;
+        const long n = std::strtol(indirect_arg.c_str(), &end, 10);
+        if (end == indirect_arg.c_str() || (*end != '\0' && *end != ':') || n < 1 || n > RT_INDIRECT_MAX_SAMPLES) return usage(argv[0]);
+        ind.samples = (int)n;
+        if (*end == ':') {
+            const char *v = end + 1;
+            if (*v < '0' || *v > '9') return usage(argv[0]);                 /* (no sign, no blank) */
+            const long d = std::strtol(v, &end, 10);
+            if (end == v || (*end != '\0' && *end != ':') || d > 0x7fffffffL) return usage(argv[0]);
+            ind.gather_depth = (int)d;
+        }
+        if (*end == ':') {
+            const char *v = end + 1;
+            ind.gain = std::strtof(v, &end);
+            if (end == v || (*end != '\0' && *end != ':')) return usage(argv[0]);
+        }
+        if (*end == ':') {
+            const char *v = end + 1;
+            if (*v < '0' || *v > '9') return usage(argv[0]);
+            const unsigned long long seed = std::strtoull(v, &end, 10);
+            if (end == v || *end != '\0' || seed > 0xffffffffull) return usage(argv[0]);
+            ind.seed = (uint32_t)seed;
+        }
+        if (*end != '\0' || !std::isfinite(ind.gain)) return usage(argv[0]);
+        /* (one GPU; instead of --ssaa, --adaptive and --lens; its records are the plain frame's) */
+        if (gpus > 1 || ssaa > 1 || !adaptive_arg.empty() || !lens_arg.empty() || !denoise.empty() || !ao_arg.empty())
+            return usage(argv[0]);
+    }
     std::vector<uint8_t> mask;
     verbose() = true;                          /* console output like the reference's */
 
@@ -253,7 +293,7 @@ int main(int argc, char **argv) {
         return 1;
     }
     pixels.assign((size_t)W * (size_t)H * 3, 0.0f);
-    std::vector<rt_hit> hits(hits_path.empty() && denoise.empty() && ao_arg.empty() ? 0 : (size_t)W * (size_t)H);
+    std::vector<rt_hit> hits(hits_path.empty() && denoise.empty() && ao_arg.empty() && indirect_arg.empty() ? 0 : (size_t)W * (size_t)H);
     std::vector<float> ao_plane(ao_arg.empty() ? 0 : (size_t)W * (size_t)H * 3);
 
     std::printf("****** Start Ray Tracing. *******\n");
@@ -305,6 +345,20 @@ int main(int argc, char **argv) {
             if (rc == RT_OK && rt_get_timing(scene, &tm) == RT_OK)
                 std::printf("Ambient occlusion (ms)     : %f  (%d x %d directions, radius %g)\n", tm.last_kernel_ms, ao.samples,
                             ao.samples, (double)ao.radius);
+        }
+        if (rc == RT_OK && ind.samples > 0) {
+            if ((double)W * (double)H > 533333333.0) {           /* (rt_indirect_diffuse's record limit; W * H must fit its int) */
+                std::fprintf(stderr, "--indirect: the frame has more than 533333333 pixels\n");
+                rt_scene_destroy(scene);
+                return 1;
+            }
+            rc = rt_indirect_diffuse(scene, &ind, W * H, hits.data(), pixels.data(), pixels.data());
+            rt_indirect_info info;
+            if (rc == RT_OK && rt_get_indirect_info(scene, &info) == RT_OK)
+                std::printf("Indirect diffuse           : %d x %d gather rays at depth %d, gain %g, seed %u: %lld rays in %d chunk(s); "
+                            "ray generation %f ms, trace %f ms, query %f ms, resolve %f ms\n", ind.samples, ind.samples,
+                            ind.gather_depth, (double)ind.gain, ind.seed, (long long)info.rays, info.chunks, info.raygen_ms,
+                            info.trace_ms, info.query_ms, info.resolve_ms);
         }
         if (rc == RT_OK && !denoise.empty()) {
             double denoise_ms = 0.0;

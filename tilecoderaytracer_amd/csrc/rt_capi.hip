@@ -167,9 +167,10 @@ struct rt_scene {
     rt_timing timing{};
     rt_launch_info launch{};
     uint64_t launch_seq = 0;                         /* render-kernel launches made (launch()) */
-    /* COMPOSED CALLS (rt_internal.h: include/rt_capi_adaptive.h, include/rt_capi_lens.h): each unit's scratch and its last
+    /* COMPOSED CALLS (rt_internal.h: include/rt_capi_adaptive.h, include/rt_capi_lens.h, include/rt_capi_indirect.h): each unit's scratch and its last
      * call's bookkeeping, with the unit's way of freeing it and of telling its last call's stage times */
     rt_internal_unit units[RT_INTERNAL_UNITS] = {};
+    void *d_object_diffuse = nullptr;                /* rt_internal_object_diffuse(): a float per Scene object, made on first use */
     char launch_kernel[RT_KERNEL_NAME_BYTES] = {};   /* the whole name; launch.kernel is its first 47 characters */
     std::mutex mu;
 };
@@ -1979,6 +1980,24 @@ int rt_internal_launch_rays(rt_scene *s, int n, int rows, const void *d_rays, in
     return batch_on_device(s, kCallRays, n, rows, d_rays, max_depth, d_out_rgb, hip_stream, nullptr, true);
 }
 
+int rt_internal_launch_hits(rt_scene *s, int n, int rows, const void *d_rays, void *d_out_hits, void *hip_stream) {
+    return batch_on_device(s, kCallHits, n, rows, d_rays, 0, d_out_hits, hip_stream, nullptr, true);
+}
+
+int rt_internal_object_diffuse(rt_scene *s, const float **d_kd, int *n_objects) {
+    const size_t n = s->objects.size();
+    if (!s->d_object_diffuse && n > 0) {
+        std::vector<float> kd(n);
+        for (size_t i = 0; i < n; ++i) kd[i] = s->objects[i].diffuse;
+        HIP_TRY(hipSetDevice(s->device));
+        HIP_TRY(hipMalloc(&s->d_object_diffuse, n * sizeof(float)));
+        HIP_TRY(hipMemcpy(s->d_object_diffuse, kd.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    }
+    *d_kd = static_cast<const float *>(s->d_object_diffuse);
+    *n_objects = (int)n;
+    return RT_OK;
+}
+
 int rt_internal_grow(void **buf, size_t *bytes, size_t need) { return grow_device_buffer(buf, bytes, need); }
 
 int rt_capi_version(void) { return RT_CAPI_VERSION; }
@@ -2169,6 +2188,7 @@ int rt_scene_destroy(rt_scene *s) {
     if (s->d_stack) (void)hipFree(s->d_stack);
     if (s->h_error) (void)hipHostFree(s->h_error);
     if (s->d_timeline) (void)hipFree(s->d_timeline);
+    if (s->d_object_diffuse) (void)hipFree(s->d_object_diffuse);
     for (rt_internal_unit &u : s->units)
         if (u.state) u.free_state(u.state);
     delete s;
@@ -2429,7 +2449,7 @@ int rt_get_timing(const rt_scene *cs, rt_timing *out) {
         }
     }
     /* COMPOSED CALLS: while one's call is the handle's last launch, the sum of that call's stages (include/rt_capi_adaptive.h,
-     * include/rt_capi_lens.h) */
+     * include/rt_capi_lens.h, include/rt_capi_indirect.h) */
     for (rt_internal_unit &u : s->units) {
         const double stages_ms = u.state ? u.stage_ms(u.state, s->launch_seq) : -1.0;
         if (stages_ms >= 0.0) s->timing.last_kernel_ms = stages_ms;

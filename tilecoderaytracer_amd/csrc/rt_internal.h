@@ -1,7 +1,8 @@
 /*
  * rt_internal.h -- what the library's units ask of one another across their object files; nothing here is part of the ABI.
  * rt_capi.hip owns the handle (struct rt_scene), the argument rules and the launch policy -- one copy per rule -- and
- * rt_adaptive.hip (include/rt_capi_adaptive.h) and rt_lens.hip (include/rt_capi_lens.h) compose them through the calls below.
+ * rt_adaptive.hip (include/rt_capi_adaptive.h), rt_lens.hip (include/rt_capi_lens.h) and rt_indirect.hip
+ * (include/rt_capi_indirect.h) compose them through the calls below.
  */
 #ifndef RT_INTERNAL_H_
 #define RT_INTERNAL_H_
@@ -22,12 +23,12 @@ typedef struct rt_internal_unit {
     void (*free_state)(void *state);
     double (*stage_ms)(void *state, uint64_t seq);
 } rt_internal_unit;
-enum { RT_INTERNAL_UNIT_ADAPTIVE, RT_INTERNAL_UNIT_LENS, RT_INTERNAL_UNITS };
+enum { RT_INTERNAL_UNIT_ADAPTIVE, RT_INTERNAL_UNIT_LENS, RT_INTERNAL_UNIT_INDIRECT, RT_INTERNAL_UNITS };
 
 /* rt_capi.hip: the text behind rt_last_error(); returns code */
 int rt_internal_set_error(int code, const char *msg);
 
-/* ---- rt_capi.hip, for rt_adaptive.hip and rt_lens.hip ---- */
+/* ---- rt_capi.hip, for rt_adaptive.hip, rt_lens.hip and rt_indirect.hip ---- */
 /* rt_render's checks in rt_render's order (the scene, the strip, the camera, the depth, the strip's size), no device work;
  * rt_internal_check_strip: the same without the scene */
 int rt_internal_check_frame(const rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
@@ -51,6 +52,11 @@ uint64_t rt_internal_launch_seq(const rt_scene *s);
 int rt_internal_launch_gbuffer(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
                                void *d_rgb, void *d_hits, void *hip_stream);
 int rt_internal_launch_rays(rt_scene *s, int n, int rows, const void *d_rays, int max_depth, void *d_out_rgb, void *hip_stream);
+/* launch() of a hit query of a ray batch (rt_intersect_rays_device's), likewise under the caller's lock */
+int rt_internal_launch_hits(rt_scene *s, int n, int rows, const void *d_rays, void *d_out_hits, void *hip_stream);
+/* the `diffuse` of every Scene object as given to rt_scene_create*, one float each, on the scene's device (uploaded on first
+ * use, freed with the handle), and how many there are; under the caller's lock */
+int rt_internal_object_diffuse(rt_scene *s, const float **d_kd, int *n_objects);
 /* a device buffer that only grows (the device is synchronised before the old one is freed) */
 int rt_internal_grow(void **buf, size_t *bytes, size_t need);
 

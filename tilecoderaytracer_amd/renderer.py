@@ -93,6 +93,32 @@ def lens_rays(camera, W, H, samples=4, aperture=0.0, focus=1.0, seed=0, x0=0, x1
     return out
 
 
+def indirect_params(samples=4, gather_depth=1, gain=1.0, seed=0, key0=0, emitters=False, chunk_records=0):
+    """indirect_diffuse's keywords -> an RtIndirectParams (include/rt_capi_indirect.h); the library checks the values."""
+    return capi.RtIndirectParams(int(samples), int(gather_depth), int(chunk_records), int(emitters), int(seed) & 0xFFFFFFFF,
+                                 int(key0) & 0xFFFFFFFF, float(gain))
+
+
+def _records(hits):
+    if not isinstance(hits, np.ndarray) or hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous:
+        raise TypeError("hits must be a C-contiguous numpy array of HIT_DTYPE")
+    return hits
+
+
+def indirect_rays(hits, samples, seed=0, key0=0, device=0):
+    """The gather rays of one diffuse bounce (include/rt_capi_indirect.h, rt_indirect_rays): for every record of hits (HIT_DTYPE,
+    any shape) samples x samples rays from the record's point into the hemisphere around its normal, in ambient_occlusion()'s
+    directions -> float32 hits.shape + (samples^2, 6), ray [..., s] = {P.xyz, T.xyz}; a miss's or a light's rays are zeros.
+    Record i samples with key0 + i.  What indirect_diffuse() traces; trace_rays() takes them as they are.  Runs on GPU
+    `device`; there is no CPU path."""
+    hits = _records(hits)
+    params = indirect_params(samples, seed=seed, key0=key0)
+    S = params.samples ** 2 if 1 <= params.samples <= 8 else 1        # (a bad count is refused by the call below)
+    out = np.empty(hits.shape + (S, 6), dtype=np.float32)
+    capi.check(capi.load_library().rt_indirect_rays(C.byref(params), hits.size, hits.ctypes.data, int(device), out.ctypes.data))
+    return out
+
+
 _TRANSFERS = {"srgb": capi.RT_TRANSFER_SRGB, "linear": capi.RT_TRANSFER_LINEAR, "custom": capi.RT_TRANSFER_CUSTOM}
 
 
@@ -454,6 +480,78 @@ class Renderer:
                                                              plane.data_ptr(), stream.cuda_stream))
             out = plane.cpu().numpy()                                 # the one download
         return out if C_ == 3 else out.reshape(W, H)
+
+    def indirect_diffuse(self, hits, samples=4, gather_depth=1, gain=1.0, seed=0, key0=0, emitters=False, chunk_records=0,
+                         base=None):
+        """One diffuse bounce for every hit record (include/rt_capi_indirect.h, rt_indirect_diffuse): samples x samples gather
+        rays per record in ambient_occlusion()'s directions, traced at gather_depth, averaged and weighted by the record's
+        colour, its object's diffuse coefficient and gain.  hits: C-contiguous HIT_DTYPE of any shape, as render_gbuffer() and
+        intersect_rays() return them; record i samples with key0 + i (a strip of a W x H frame from column x0: key0 = x0 * H).
+        base: None, or float32 hits.shape + (3,) that the term is added to (a frame's direct colours).  emitters False: a
+        gather ray whose first hit is a light counts black, since the record's direct shading has that light already.
+        -> float32 hits.shape + (3,).  chunk_records (the most records gathered per launch, 0: the default) never changes the
+        result; indirect_info() tells what each stage cost."""
+        hits = _records(hits)
+        params = indirect_params(samples, gather_depth, gain, seed, key0, emitters, chunk_records)
+        if base is not None:
+            base = np.ascontiguousarray(base, dtype=np.float32)
+            if base.shape != hits.shape + (3,):
+                raise ValueError(f"base must have shape {hits.shape + (3,)}, not {base.shape}")
+        out = np.empty(hits.shape + (3,), dtype=np.float32)
+        capi.check(self._lib.rt_indirect_diffuse(self._scene, C.byref(params), hits.size, hits.ctypes.data,
+                                                 base.ctypes.data if base is not None else None, out.ctypes.data))
+        return out
+
+    def indirect_diffuse_device(self, n, hits_ptr, base_ptr, out_ptr, stream=0, samples=4, gather_depth=1, gain=1.0, seed=0, key0=0,
+                                emitters=False, chunk_records=0):
+        """Enqueue the indirect term of n records (48 bytes each, hits_ptr 16-byte aligned) into 3 n float32 at out_ptr, added to
+        the 3 n float32 at base_ptr unless that is 0 (base_ptr == out_ptr: in place), on a HIP stream (no sync: nothing is read
+        back)."""
+        params = indirect_params(samples, gather_depth, gain, seed, key0, emitters, chunk_records)
+        capi.check(self._lib.rt_indirect_diffuse_device(self._scene, C.byref(params), n, C.c_void_p(hits_ptr),
+                                                        C.c_void_p(base_ptr or None), C.c_void_p(out_ptr), C.c_void_p(stream)))
+
+    def indirect_info(self):
+        """The last indirect_diffuse*() of this scene (include/rt_capi_indirect.h, rt_indirect_info): records, rays, chunks and
+        the four stage times."""
+        info = capi.RtIndirectInfo()
+        capi.check(self._lib.rt_get_indirect_info(self._scene, C.byref(info)))
+        return info
+
+    def render_indirect(self, W, H, max_depth, samples=4, gather_depth=1, gain=1.0, seed=0, emitters=False, denoise=None):
+        """A W x H frame with one diffuse bounce added, computed on the GPU where its records were made
+        (include/rt_capi_indirect.h): rt_render_gbuffer_device and rt_indirect_diffuse_device -- the frame's colours the base,
+        in place -- enqueued on one stream with no host wait between them, then one download -> float32 (W, H, 3).  The result
+        is indirect_diffuse(hits, ..., base=rgb) of rgb, hits = render_gbuffer(W, H, max_depth) bit for bit.  denoise: None, or
+        a dict of denoise()'s keywords (iterations, sigma_color, normal_squarings): the indirect term alone is then computed
+        without a base, filtered by rt_denoise_device with the frame's records and added to the direct colours by one fp32
+        add -- rgb + denoise(indirect_diffuse(hits, ...), hits, ...) bit for bit.  The device buffers and the stream are
+        torch's, so the process must have imported torch before the library was loaded."""
+        import torch
+        device = int(self._device)
+        kw = dict(samples=samples, gather_depth=gather_depth, gain=gain, seed=seed, emitters=emitters)
+        if denoise is not None:
+            dn = capi.RtDenoiseParams(int(denoise.get("iterations", 2)), int(denoise.get("normal_squarings", 3)),
+                                      float(denoise.get("sigma_color", 1.0)))
+            scratch_bytes = self._lib.rt_denoise_scratch_bytes(C.byref(dn), W, H)
+            if not scratch_bytes:                                     # (bad parameters: refused by the call itself)
+                capi.check(self._lib.rt_denoise_device(device, C.byref(dn), W, H, None, None, None, None, None))
+        with torch.cuda.device(device):
+            colours = torch.empty((W, H, 3), dtype=torch.float32, device="cuda")
+            records = torch.empty((W * H * 12,), dtype=torch.int32, device="cuda")
+            stream = torch.cuda.current_stream()
+            self.render_gbuffer_device(W, H, max_depth, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
+            if denoise is None:
+                self.indirect_diffuse_device(W * H, records.data_ptr(), colours.data_ptr(), colours.data_ptr(), stream.cuda_stream,
+                                             **kw)
+                return colours.cpu().numpy()                          # the one download
+            term = torch.empty((W, H, 3), dtype=torch.float32, device="cuda")
+            clean = torch.empty((W, H, 3), dtype=torch.float32, device="cuda")
+            scratch = torch.empty(((scratch_bytes + 15) // 16 * 4,), dtype=torch.int32, device="cuda")
+            self.indirect_diffuse_device(W * H, records.data_ptr(), 0, term.data_ptr(), stream.cuda_stream, **kw)
+            capi.check(self._lib.rt_denoise_device(device, C.byref(dn), W, H, term.data_ptr(), records.data_ptr(), clean.data_ptr(),
+                                                   scratch.data_ptr(), stream.cuda_stream))
+            return torch.add(colours, clean).cpu().numpy()            # the one download
 
     STAT_NAMES = ("nearest_rays", "shadow_rays", "wave_nearest_scans", "wave_shadow_scans",
                   "wave_sphere_tests", "wave_plane_tests", "wave_box_tests", "lane_sphere_tests",
