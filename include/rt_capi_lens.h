@@ -37,7 +37,8 @@
  *
  * WHAT FOLLOWS.
  *   - The sampling key is the pixel's number in the whole frame: a strip equals the same columns of the frame bit for bit,
- *     and chunk_columns never changes a bit.
+ *     and chunk_columns never changes a bit.  The key x*H + z is taken modulo 2^32: on a frame of more than 2^32 pixels the
+ *     pixels 2^32 apart share their lens points (their targets still differ).
  *   - aperture = 0 and focus = 1: every ray is {E, P}, so the frame is rt_render_ssaa's for n = 1, 2, 4 and rt_render's for
  *     n = 1 -- for every camera whose screen_origin has no -0.0 component (rt_trace_rays reads a -0.0 of its target as +0.0,
  *     rt_capi_rays.h; the caveat rt_capi_adaptive.h carries).

@@ -122,6 +122,26 @@ def test_flag_all_is_rt_render_ssaa_on_every_pixel(camera, k):
     assert (info.pixels, info.flagged, info.rays) == (W * H, W * H, W * H * k * k)
 
 
+@pytest.mark.parametrize("halo", [False, True], ids=["last-columns", "halo"])
+@pytest.mark.parametrize("k", [2, 4])
+def test_flag_all_is_rt_render_ssaa_where_k_x_exceeds_2_24(k, halo):
+    """the last 8 columns of a frame as wide as rt_render_ssaa admits (k W = 2^31 - k): (float)((x << kl) + i) rounds far above
+    2^24 and must round as the supersampling kernels' own pixel numbers do (those are held to the oracle by
+    test_large_extents_gpu.py); and the 8 columns before them, which bring a halo column and the scratch copy"""
+    W, H, depth = (1 << 31) // k - 1, 37, 3
+    x1 = W - 8 if halo else W
+    x0 = x1 - 8
+    assert k * x0 > 1 << 24 and k * W <= 0x7fffffff < k * (W + 1)
+    r = Renderer(HostScene.builtin())
+    want = r.render_ssaa(W, H, depth, k, x0=x0, x1=x1)
+    got, flags = r.render_adaptive(W, H, depth, samples=k, flag_all=True, x0=x0, x1=x1, return_flags=True)
+    assert flags.all()
+    assert_same(got, want, f"flag_all W={W} k{k} columns {x0}:{x1}")
+    info = r.adaptive_info()
+    assert (info.pixels, info.flagged, info.rays) == (8 * H, 8 * H, 8 * H * k * k)
+    assert len(np.unique(np.ascontiguousarray(want).view(np.uint32).reshape(-1, 3), axis=0)) >= 2       # (not one flat colour)
+
+
 @pytest.mark.parametrize("key,W,H,depth", [("builtin", 61, 37, 4), ("grid16", 50, 44, 5)])
 def test_one_sample_is_rt_render_with_the_flags_still_reported(key, W, H, depth):
     r = Renderer(adaptive_frames.host_scene(key))

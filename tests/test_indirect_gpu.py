@@ -40,9 +40,9 @@ def records(frame=BUILTIN):
     return np.array(indirect_ref.oracle_gather(*frame)[1], dtype=HIT_DTYPE, order="C")
 
 
-def own_reference(r, hits, kd, n, gather_depth, seed, emitters, gain=1.0, base=None):
+def own_reference(r, hits, kd, n, gather_depth, seed, emitters, gain=1.0, base=None, key0=0):
     """indirect_ref.resolve of the handle's own rt_trace_rays and rt_intersect_rays of indirect_ref's rays"""
-    rays, _ = indirect_ref.rays(hits, n, seed, 0)
+    rays, _ = indirect_ref.rays(hits, n, seed, key0)
     flat = np.ascontiguousarray(rays.reshape(-1, 6))
     colours = r.trace_rays(flat, gather_depth).reshape(hits.shape + (n * n, 3))
     light = ((r.intersect_rays(flat)["flags"] & indirect_ref.HIT_LIGHT) != 0).reshape(hits.shape + (n * n,))
@@ -51,7 +51,7 @@ def own_reference(r, hits, kd, n, gather_depth, seed, emitters, gain=1.0, base=N
 
 # ---- 1. ray generation ---------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("n", [1, 2, 3, 8])
+@pytest.mark.parametrize("n", [1, 2, 3, 5, 6, 7, 8])
 def test_rays_are_the_definitions_word_for_word(n):
     for name, hits, seed, key0 in (("frame", records(), 0, 0), ("handmade", indirect_ref.handmade_records(), 0xC0FFEE, 0xFFFFFFF0)):
         want, live = indirect_ref.rays(hits, n, seed, key0)
@@ -63,7 +63,7 @@ def test_rays_are_the_definitions_word_for_word(n):
         assert_same(indirect_rays(np.ascontiguousarray(hits[x0:x1]), n, seed=5, key0=x0 * H37), whole[x0:x1], f"rays strip {x0}:{x1}")
 
 
-@pytest.mark.parametrize("n", [3, 8])
+@pytest.mark.parametrize("n", [3, 6, 8])
 def test_rays_device_entry_into_poisoned_words(n):
     hits = indirect_ref.handmade_records()                                 # 130 records: no multiple of 256 / S
     assert (len(hits) * n * n) % 256 != 0 and len(hits) % max(256 // (n * n), 1) != 0
@@ -95,6 +95,47 @@ def test_against_the_oracle(frame, emitters, with_base):
     assert (info.records, info.rays, info.chunks) == (W * H, W * H * n * n, 1)
     assert (info.query_ms > 0) == (not emitters)
     assert r.launch_info().kernel.decode().endswith("_rays" if emitters else "_hits")
+
+
+def test_against_the_oracle_at_five_by_five():
+    """S = 25 is no power of two and no divisor of 1024: a record's lanes straddle wavefronts and workgroups in the ray generation
+    (the workgroup's record window and its LDS frames), and the resolve's workgroups take 40 records and leave 24 sample slots
+    over.  The smallest frame of indirect_ref.FRAMES, both `emitters` settings, onto a base."""
+    key, W, H, depth, _, seed, gather_depth = min(indirect_ref.FRAMES, key=lambda f: f[1] * f[2])
+    frame = (key, W, H, depth, 5, seed, gather_depth)
+    rgb = indirect_ref.oracle_gather(*frame)[0]
+    r = Renderer(adaptive_frames.host_scene(key))
+    assert (W * H) % (1024 // 25) != 0
+    for emitters in (False, True):
+        got = r.indirect_diffuse(records(frame), 5, gather_depth, seed=seed, emitters=emitters, base=rgb)
+        assert_same(got, indirect_ref.oracle_term(frame, emitters, True), f"{key} {W}x{H} n5 emitters {emitters}")
+        info = r.indirect_info()
+        assert (info.records, info.rays, info.chunks) == (W * H, W * H * 25, 1)
+    assert indirect_ref.nonzero_share(indirect_ref.oracle_term(frame, False, False), indirect_ref.oracle_gather(*frame)[1]) >= 0.5
+
+
+@pytest.mark.parametrize("n", [6, 7])
+def test_handmade_records_whose_lanes_straddle_workgroups(n):
+    """the hand-made records -- misses, lights, inside hits, an unknown object -- at S = 36 and 49 with key0 = 0xFFFFFFF0: dead
+    and inside-flagged records fall on the seams of the ray generation's workgroups (256 rays: 7.1 and 5.2 records) and of the
+    resolve's (28 and 20 records), and the keys wrap inside the batch.  Against the handle's own ray batches and queries."""
+    import oracle_lib
+    r = Renderer(HostScene.builtin())
+    kd = indirect_ref.object_diffuse(oracle_lib.OracleScene.builtin())
+    hits = indirect_ref.handmade_records()
+    S, key0 = n * n, 0xFFFFFFF0
+    seams = {(256 * b) // S for b in range(1, len(hits) * S // 256 + 1)}      # the records a workgroup of rays ends in
+    live = ao_ref.live_records(hits)
+    special = set(np.flatnonzero(~live)) | set(np.flatnonzero(hits["flags"] & ao_ref.HIT_INSIDE))
+    assert seams & special, (sorted(seams), sorted(special))              # (record 64, a miss, at n = 6; record 10, inside, at n = 7)
+    assert len(hits) % (1024 // S) != 0 and len(hits) > 1024 // S
+    base = np.random.RandomState(n).uniform(0, 1, (len(hits), 3)).astype(F)
+    for emitters in (False, True):
+        want = own_reference(r, hits, kd, n, 1, 0xC0FFEE, emitters, 0.75, base, key0)
+        got = r.indirect_diffuse(hits, n, 1, 0.75, seed=0xC0FFEE, key0=key0, emitters=emitters, base=base)
+        assert_same(got, want, f"handmade n{n} emitters {emitters}")
+        assert_same(got[~live], base[~live], "dead records return the base")
+    assert (got[live] != base[live]).any()
 
 
 # ---- 3. the conditions, on the reference: a test above must not pass on an empty term -------------------------------------------
@@ -153,7 +194,7 @@ def test_a_refractive_scene_against_its_own_ray_batches():
 
 # ---- 5. chunks and strips -------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("n,emitters", [(3, False), (2, True)])
+@pytest.mark.parametrize("n,emitters", [(3, False), (2, True), (5, False), (7, True)])
 def test_chunks_and_strips_never_change_a_bit(n, emitters):
     r = Renderer(HostScene.builtin())
     hits = records()

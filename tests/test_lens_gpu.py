@@ -44,7 +44,7 @@ def own_reference(r, cam, W, H, depth, n, seed, aperture, focus):
 
 # ---- 1. ray generation ---------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("n", [1, 2, 3, 4, 8])
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 6, 7, 8])
 @pytest.mark.parametrize("camera,seed", [(None, 0), ("pitched_down", 0), ("rolled_1p45", 0xC0FFEE), ("left_handed", 0)])
 def test_rays_are_the_definitions_word_for_word(camera, seed, n):
     cam = lens_ref.camera_copy(camera_of(camera))
@@ -74,6 +74,28 @@ def test_rays_device_entry_into_poisoned_words():
     assert_same(got.view(F).reshape(want.shape), want, what)
 
 
+W24 = (1 << 24) + 43
+W28 = (1 << 28) + 5
+WRAP = (1 << 32) // H37                   # the first column whose pixel keys x * H + z pass 2^32
+
+
+@pytest.mark.parametrize("W,n,x0,x1", [(W24, 3, 0, 8), (W24, 3, W24 - 8, W24), (W28, 2, WRAP - 8, WRAP + 8)],
+                         ids=["first-columns", "3x-above-2^24", "key-wraps-2^32"])
+def test_rays_of_strips_of_very_wide_frames(W, n, x0, x1):
+    """W = 2^24 + 43, n = 3: in the last columns n x + i is above 2^24, where (float) rounds, and must round as lens_ref's
+    int -> float32 does.  W = 2^28 + 5, H = 37: around column 2^32 // 37 the pixel key x H + z passes 2^32 and is taken modulo 2^32
+    (include/rt_capi_lens.h); the lens is open, so a key computed otherwise moves every origin."""
+    cam = lens_ref.camera_copy(camera_of("pitched_down"))
+    if W == W24 and x0 > 0:
+        assert n * x0 > 1 << 24 and len(np.unique((n * np.arange(x0, x1)[:, None] + np.arange(n)).astype(F))) < n * (x1 - x0)
+    if W == W28:
+        assert x0 * H37 < 1 << 32 < (x1 - 1) * H37
+    want = lens_ref.rays(cam, W, H37, x0, x1, n, 0xC0FFEE, APERTURE, FOCUS)
+    got = lens_rays(cam, W, H37, samples=n, aperture=APERTURE, focus=FOCUS, seed=0xC0FFEE, x0=x0, x1=x1)
+    assert_same(got, want, f"rays W={W} n{n} columns {x0}:{x1}")
+    assert len(np.unique(got[..., :3].reshape(-1, 3), axis=0)) > (x1 - x0) * H37 * n * n // 2       # the lens is open
+
+
 # ---- 2. frames against the CPU oracle ------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("key,W,H,depth,n,seed,point", lens_ref.FRAMES)
@@ -86,6 +108,21 @@ def test_against_the_oracle(key, W, H, depth, n, seed, point):
     info = r.lens_info()
     assert (info.pixels, info.rays, info.chunks) == (W * H, W * H * n * n, 1)
     assert r.launch_info().kernel.decode().endswith("_rays")
+
+
+def test_against_the_oracle_at_five_by_five():
+    """S = 25 is no power of two and no divisor of 1024: a pixel's lanes straddle wavefronts and workgroups in the ray generation,
+    and the resolve's workgroups take 40 pixels and leave 24 sample slots over.  The smallest frame of lens_ref.FRAMES."""
+    key, W, H, depth, _, seed, point = min(lens_ref.FRAMES, key=lambda f: f[1] * f[2])
+    n = 5
+    aperture, focus = lens_ref.lens_of(key, point)
+    want = lens_ref.oracle_frame(key, W, H, depth, n, seed, aperture, focus)
+    r = Renderer(adaptive_frames.host_scene(key))
+    got = r.render_lens(W, H, depth, samples=n, aperture=aperture, focus=focus, seed=seed)
+    assert_same(got, want, f"{key} {W}x{H} d{depth} n{n}")
+    assert (W * H) % (1024 // (n * n)) != 0
+    info = r.lens_info()
+    assert (info.pixels, info.rays, info.chunks) == (W * H, W * H * n * n, 1)
 
 
 def test_an_image_textured_scene_against_its_own_ray_batches():
@@ -137,7 +174,7 @@ def test_a_pinhole_focused_on_the_screen_is_rt_render_ssaa(camera, n):
 
 # ---- 4. chunks and strips -------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("n", [2, 3])
+@pytest.mark.parametrize("n", [2, 3, 5, 7])
 def test_chunks_and_strips_never_change_a_bit(n):
     r = Renderer(HostScene.builtin())
     depth = 3
@@ -145,6 +182,7 @@ def test_chunks_and_strips_never_change_a_bit(n):
     want = r.render_lens(W61, H37, depth, **kw)
     assert r.lens_info().chunks == 1
     for chunk in (1, 7, 61, 0):
+        assert (chunk * H37) % (1024 // (n * n)) != 0 or chunk == 0      # no chunk ends on a seam of the resolve's workgroups
         got = r.render_lens(W61, H37, depth, chunk_columns=chunk, **kw)
         assert_same(got, want, f"n{n} chunk_columns {chunk}")
         info = r.lens_info()
