@@ -58,6 +58,13 @@ class RtDenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("sigma_color", C.c_float)]
 
 
+class RtUpsampleParams(C.Structure):
+    """include/rt_capi_upsample.h: the scale s (2..8), channels (1 or 3), normal squarings (0..6), match_color and modulate
+    (0 / 1), the plane term's sigma (0: none) and the value of a pixel with no surface."""
+    _fields_ = [("scale", C.c_int32), ("channels", C.c_int32), ("normal_squarings", C.c_int32), ("match_color", C.c_int32),
+                ("modulate", C.c_int32), ("sigma_plane", C.c_float), ("dead_value", C.c_float)]
+
+
 class RtAoParams(C.Structure):
     """include/rt_capi_ao.h: n (n x n directions per record, 1..8), the radius a direction is followed for, the seed, the first
     record's key, channels (1, or 3 equal ones)."""
@@ -337,6 +344,15 @@ def load_library():
         lib.rt_get_indirect_info.argtypes = [vp, C.POINTER(RtIndirectInfo)]
         for name in ("rt_indirect_rays", "rt_indirect_rays_device", "rt_indirect_diffuse", "rt_indirect_diffuse_device",
                      "rt_get_indirect_info"):
+            getattr(lib, name).restype = i
+    # include/rt_capi_upsample.h (likewise absent from older builds)
+    if hasattr(lib, "rt_upsample_guided"):
+        lib.rt_capi_upsample_version.restype = i
+        lib.rt_subsample_hits.argtypes = [i, i, i, i, i, vp, vp]
+        lib.rt_subsample_hits_device.argtypes = [i, i, i, i, i, vp, vp, vp]
+        lib.rt_upsample_guided.argtypes = [i, C.POINTER(RtUpsampleParams), i, i, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
+        lib.rt_upsample_guided_device.argtypes = [i, C.POINTER(RtUpsampleParams), i, i, vp, vp, vp, vp, vp, vp]
+        for name in ("rt_subsample_hits", "rt_subsample_hits_device", "rt_upsample_guided", "rt_upsample_guided_device"):
             getattr(lib, name).restype = i
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):

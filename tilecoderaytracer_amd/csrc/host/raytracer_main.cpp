@@ -40,6 +40,10 @@
  *                       default 1), the term scaled by GAIN (finite, default 1), directions hashed with SEED (default 0); gather
  *                       rays that meet a light first count black (emitters 0).  One GPU, instead of --ssaa, --adaptive and
  *                       --lens, without --ao or --denoise.  Composes with --ppm and --out as --lens does
+ *   --gather-scale S[:SIGMA_PLANE[:refine]]  with --indirect or --ao: gather for every S-th pixel in both directions only (2..8)
+ *                       and carry the term to every pixel by rt_upsample_guided (include/rt_capi_upsample.h: 3 normal squarings,
+ *                       plane sigma SIGMA_PLANE >= 0, default 0: none); `refine`: the holes it reports are gathered at full
+ *                       resolution afterwards, as one more batch with key0 0x80000000
  */
 #include <chrono>
 #include <cmath>
@@ -59,6 +63,7 @@
 #include "../../../include/rt_capi_indirect.h"
 #include "../../../include/rt_capi_lens.h"
 #include "../../../include/rt_capi_ssaa.h"
+#include "../../../include/rt_capi_upsample.h"
 #include "celio_model.hpp"
 #include "screen_ppm.hpp"
 #include "screen_txt.hpp"
@@ -76,7 +81,8 @@ static int usage(const char *argv0) {
                  "          [--gpus G] [--out FILE] [--no-txt] [--ssaa 1|2|4] [--hits FILE] [--glass I:TF:IOR ...]\n"
                  "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n"
                  "          [--ao N[:RADIUS] --ao-ppm FILE] [--adaptive 1|2|4[:COLOR[:COS]] [--adaptive-mask FILE]]\n"
-                 "          [--lens N[:APERTURE[:FOCUS[:SEED]]]] [--indirect N[:DEPTH[:GAIN[:SEED]]]]\n", argv0);
+                 "          [--lens N[:APERTURE[:FOCUS[:SEED]]]] [--indirect N[:DEPTH[:GAIN[:SEED]]]]\n"
+                 "          [--gather-scale S[:SIGMA_PLANE[:refine]]]\n", argv0);
     return 1;
 }
 
@@ -88,6 +94,8 @@ int main(int argc, char **argv) {
     std::string adaptive_arg, mask_path;         /* --adaptive K[:COLOR[:COS]], --adaptive-mask FILE (include/rt_capi_adaptive.h) */
     std::string lens_arg;                        /* --lens N[:APERTURE[:FOCUS[:SEED]]] (include/rt_capi_lens.h) */
     std::string indirect_arg;                    /* --indirect N[:DEPTH[:GAIN[:SEED]]] (include/rt_capi_indirect.h) */
+    std::string gather_arg;                      /* --gather-scale S[:SIGMA_PLANE[:refine]] (include/rt_capi_upsample.h) */
+    bool has_gather = false;
     std::string denoise;                         /* --denoise IT[:SIGMA[:K]] (include/rt_capi_denoise.h) */
     std::vector<std::string> soft;               /* --soft I:N[:R]: light I an area light, N x N samples, radius R (include/rt_capi_soft.h) */
     for (int i = 1; i < argc; ++i) {
@@ -112,6 +120,7 @@ int main(int argc, char **argv) {
         else if (a == "--adaptive-mask" && i + 1 < argc) mask_path = argv[++i];
         else if (a == "--lens" && i + 1 < argc) lens_arg = argv[++i];
         else if (a == "--indirect" && i + 1 < argc) indirect_arg = argv[++i];
+        else if (a == "--gather-scale" && i + 1 < argc) gather_arg = argv[++i], has_gather = true;
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
@@ -231,6 +240,60 @@ int main(int argc, char **argv) {
         if (gpus > 1 || ssaa > 1 || !adaptive_arg.empty() || !lens_arg.empty() || !denoise.empty() || !ao_arg.empty())
             return usage(argv[0]);
     }
+    rt_upsample_params up = {0, 3, 3, 0, 0, 0.0f, 0.0f};
+    bool refine = false;
+    if (has_gather) {
+        /* S, S:SIGMA_PLANE or S:SIGMA_PLANE:refine, and nothing else; with --indirect or --ao */
+        char *end = nullptr;
+        const long sc = std::strtol(gather_arg.c_str(), &end, 10);
+        if (end == gather_arg.c_str() || (*end != '\0' && *end != ':') || sc < 2 || sc > 8) return usage(argv[0]);
+        up.scale = (int)sc;
+        if (*end == ':') {
+            const char *v = end + 1;
+            up.sigma_plane = std::strtof(v, &end);
+            if (end == v || (*end != '\0' && *end != ':') || !(up.sigma_plane >= 0.0f) || std::isinf(up.sigma_plane))
+                return usage(argv[0]);
+            if (*end == ':') {
+                if (std::strcmp(end + 1, "refine") != 0) return usage(argv[0]);
+                refine = true;
+            }
+        }
+        if (ao_arg.empty() && indirect_arg.empty()) return usage(argv[0]);
+    }
+    /* a term gathered for the cells of the frame's records and upsampled onto `base` (or alone) into out, 3 channels: gather(n,
+     * rows, records, key0, values) is the full-resolution call */
+    auto gather_scaled = [&](const std::vector<rt_hit> &records, auto gather, int modulate, float dead_value, const float *base,
+                             float *out, const char *what) -> int {
+        const int Wl = (W + up.scale - 1) / up.scale, Hl = (H + up.scale - 1) / up.scale;
+        std::vector<rt_hit> cells((size_t)Wl * (size_t)Hl);
+        std::vector<float> lo(cells.size() * 3);
+        std::vector<uint8_t> holes((size_t)W * (size_t)H);
+        rt_upsample_params p = up;
+        p.modulate = modulate, p.dead_value = dead_value;
+        double up_ms = 0.0;
+        int r = rt_subsample_hits(0, up.scale, 1, W, H, records.data(), cells.data());
+        if (r == RT_OK) r = gather(Wl * Hl, Hl, cells.data(), 0u, lo.data());
+        std::vector<float> kept;                     /* the base, where out overwrites it and the holes' add needs it */
+        if (r == RT_OK && refine && base && base == out) kept.assign(base, base + records.size() * 3), base = kept.data();
+        if (r == RT_OK) r = rt_upsample_guided(0, &p, W, H, records.data(), lo.data(), base, out, holes.data(), &up_ms);
+        size_t n_holes = 0;
+        for (uint8_t f : holes) n_holes += f;
+        if (r == RT_OK)
+            std::printf("%s at 1/%d density  : %d x %d cells, upsample kernel %f ms (plane sigma %g), %zu hole(s)%s\n", what,
+                        up.scale * up.scale, Wl, Hl, up_ms, (double)up.sigma_plane, n_holes, refine ? ", refined" : "");
+        if (r == RT_OK && refine && n_holes > 0) {
+            std::vector<rt_hit> own;
+            std::vector<size_t> where;
+            for (size_t k = 0; k < holes.size(); ++k)
+                if (holes[k]) own.push_back(records[k]), where.push_back(k);
+            std::vector<float> term(own.size() * 3);
+            r = gather((int)own.size(), (int)own.size(), own.data(), 0x80000000u, term.data());
+            for (size_t k = 0; r == RT_OK && k < where.size(); ++k)
+                for (int c = 0; c < 3; ++c)
+                    out[where[k] * 3 + c] = base ? base[where[k] * 3 + c] + term[k * 3 + c] : term[k * 3 + c];
+        }
+        return r;
+    };
     std::vector<uint8_t> mask;
     verbose() = true;                          /* console output like the reference's */
 
@@ -340,7 +403,14 @@ int main(int argc, char **argv) {
                 rt_scene_destroy(scene);
                 return 1;
             }
-            rc = rt_ambient_occlusion(scene, &ao, W * H, H, hits.data(), ao_plane.data());
+            if (has_gather)
+                rc = gather_scaled(hits, [&](int n, int rows, const rt_hit *records, uint32_t key0, float *values) {
+                         rt_ao_params a = ao;
+                         a.key0 = key0;
+                         return rt_ambient_occlusion(scene, &a, n, rows, records, values);
+                     }, 0, 1.0f, nullptr, ao_plane.data(), "Ambient occlusion");
+            else
+                rc = rt_ambient_occlusion(scene, &ao, W * H, H, hits.data(), ao_plane.data());
             rt_timing tm;
             if (rc == RT_OK && rt_get_timing(scene, &tm) == RT_OK)
                 std::printf("Ambient occlusion (ms)     : %f  (%d x %d directions, radius %g)\n", tm.last_kernel_ms, ao.samples,
@@ -352,7 +422,14 @@ int main(int argc, char **argv) {
                 rt_scene_destroy(scene);
                 return 1;
             }
-            rc = rt_indirect_diffuse(scene, &ind, W * H, hits.data(), pixels.data(), pixels.data());
+            if (has_gather)
+                rc = gather_scaled(hits, [&](int n, int, const rt_hit *records, uint32_t key0, float *values) {
+                         rt_indirect_params g = ind;
+                         g.key0 = key0;
+                         return rt_indirect_diffuse(scene, &g, n, records, nullptr, values);
+                     }, 1, 0.0f, pixels.data(), pixels.data(), "Indirect diffuse ");
+            else
+                rc = rt_indirect_diffuse(scene, &ind, W * H, hits.data(), pixels.data(), pixels.data());
             rt_indirect_info info;
             if (rc == RT_OK && rt_get_indirect_info(scene, &info) == RT_OK)
                 std::printf("Indirect diffuse           : %d x %d gather rays at depth %d, gain %g, seed %u: %lld rays in %d chunk(s); "

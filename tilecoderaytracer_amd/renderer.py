@@ -119,6 +119,63 @@ def indirect_rays(hits, samples, seed=0, key0=0, device=0):
     return out
 
 
+def _frame_records(hits):
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    if hits.ndim != 2:
+        raise ValueError(f"hits must be (Wn, H), not {hits.shape}")
+    return hits
+
+
+def subsample_hits(hits, scale, white=False, device=0):
+    """The records of every scale-th pixel in both directions (include/rt_capi_upsample.h, rt_subsample_hits): hits HIT_DTYPE
+    (Wn, H) as render_gbuffer() returns them -> HIT_DTYPE (ceil(Wn / scale), ceil(H / scale)), cell [i, j] = hits[i * scale,
+    j * scale] word for word; white: a live record's colour becomes (1, 1, 1), so that indirect_diffuse() of the cells is
+    irradiance without albedo.  Runs on GPU `device`; there is no CPU path."""
+    hits = _frame_records(hits)
+    s = int(scale)
+    out = np.empty((-(-hits.shape[0] // s), -(-hits.shape[1] // s)) if 2 <= s <= 8 else (0, 0), dtype=HIT_DTYPE)
+    capi.check(capi.load_library().rt_subsample_hits(int(device), s, int(white), hits.shape[0], hits.shape[1], hits.ctypes.data,
+                                                     out.ctypes.data if out.size else None))
+    return out
+
+
+def upsample_params(scale, channels=3, normal_squarings=3, match_color=False, modulate=False, sigma_plane=0.0, dead_value=0.0):
+    """upsample_guided's keywords -> an RtUpsampleParams (include/rt_capi_upsample.h); the library checks the values."""
+    return capi.RtUpsampleParams(int(scale), int(channels), int(normal_squarings), int(match_color), int(modulate),
+                                 float(sigma_plane), float(dead_value))
+
+
+def upsample_guided(hits, lo, scale, normal_squarings=3, match_color=False, modulate=False, sigma_plane=0.0, dead_value=0.0,
+                    base=None, return_flags=False, device=0):
+    """Values gathered for the cells subsample_hits() picks, carried to every pixel by a tent filter guided by the
+    full-resolution records (include/rt_capi_upsample.h, rt_upsample_guided): hits HIT_DTYPE (Wn, H); lo float32 (Wl, Hl) -- one
+    channel, AO's plane -- or (Wl, Hl, 3); base None or float32 of the result's shape that the result is added to -> float32
+    (Wn, H) or (Wn, H, 3), and with return_flags also bool (Wn, H): the holes, pixels none of whose four cells lies on their
+    surface, filled by the unguided tent.  A tap counts only from the pixel's own object (with match_color: its own albedo
+    bits), weighted by max(n_p . n_q, 0) ^ (2 ^ normal_squarings) and, with sigma_plane > 0, by the tap's distance from the
+    pixel's tangent plane; modulate multiplies by the pixel's own colour; dead_value is the value of a pixel with no surface.
+    Runs on GPU `device`; there is no CPU path."""
+    hits = _frame_records(hits)
+    lo = np.ascontiguousarray(lo, dtype=np.float32)
+    s = int(scale)
+    channels = 3 if lo.ndim == 3 else 1
+    cells = (-(-hits.shape[0] // s), -(-hits.shape[1] // s)) if 2 <= s <= 8 else lo.shape[:2]
+    if lo.shape != cells + ((3,) if channels == 3 else ()):
+        raise ValueError(f"lo must be {cells} or {cells + (3,)} for hits {hits.shape} at scale {s}, not {lo.shape}")
+    shape = hits.shape + ((3,) if channels == 3 else ())
+    if base is not None:
+        base = np.ascontiguousarray(base, dtype=np.float32)
+        if base.shape != shape:
+            raise ValueError(f"base must have shape {shape}, not {base.shape}")
+    params = upsample_params(s, channels, normal_squarings, match_color, modulate, sigma_plane, dead_value)
+    out = np.empty(shape, dtype=np.float32)
+    flags = np.zeros(hits.shape, dtype=np.uint8) if return_flags else None
+    capi.check(capi.load_library().rt_upsample_guided(int(device), C.byref(params), hits.shape[0], hits.shape[1], hits.ctypes.data,
+                                                      lo.ctypes.data, base.ctypes.data if base is not None else None,
+                                                      out.ctypes.data, flags.ctypes.data if return_flags else None, None))
+    return (out, flags.view(np.bool_)) if return_flags else out
+
+
 _TRANSFERS = {"srgb": capi.RT_TRANSFER_SRGB, "linear": capi.RT_TRANSFER_LINEAR, "custom": capi.RT_TRANSFER_CUSTOM}
 
 
@@ -460,14 +517,21 @@ class Renderer:
         capi.check(self._lib.rt_ambient_occlusion_device(self._scene, C.byref(params), n, rows, C.c_void_p(hits_ptr),
                                                          C.c_void_p(out_ptr), C.c_void_p(stream)))
 
-    def render_ao(self, W, H, samples=4, radius=1.0, seed=0, channels=1):
+    def render_ao(self, W, H, samples=4, radius=1.0, seed=0, channels=1, scale=1, normal_squarings=3, sigma_plane=0.0,
+                  refine=False, key0_refine=0x80000000):
         """The ambient-occlusion plane of a W x H frame, computed on the GPU where its records were made: a depth-0
         rt_render_gbuffer_device and rt_ambient_occlusion_device (rows = H) enqueued on one stream with no host wait between
         them, then a download of the plane alone -> float32 (W, H), or (W, H, 3) with channels = 3 (a grey frame for denoise()
         and encode_image()).  The result is ambient_occlusion(render_gbuffer(W, H, 0)[1], ...) bit for bit.  The device buffers
         and the stream are torch's, so the process must have imported torch before the library was loaded (INTEGRATION.md
-        section 3)."""
+        section 3).  scale 2..8 (include/rt_capi_upsample.h): the plane is gathered for every scale-th pixel in both directions
+        and upsampled, rt_subsample_hits_device, rt_ambient_occlusion_device and rt_upsample_guided_device on that one stream
+        with no host wait -- ambient_occlusion_scaled(render_gbuffer(W, H, 0)[1], scale, ...) bit for bit; refine costs exactly
+        one read-back of the flags before the holes' batch is enqueued."""
         import torch
+        if scale != 1:
+            return self._render_ao_scaled(W, H, samples, radius, seed, channels, scale, normal_squarings, sigma_plane, refine,
+                                          key0_refine)
         params = self._ao_params(samples, radius, seed, 0, channels)
         C_ = 3 if params.channels == 3 else 1                        # (a bad count is refused by the call below)
         with torch.cuda.device(int(self._device)):
@@ -480,6 +544,68 @@ class Renderer:
                                                              plane.data_ptr(), stream.cuda_stream))
             out = plane.cpu().numpy()                                 # the one download
         return out if C_ == 3 else out.reshape(W, H)
+
+    def ambient_occlusion_scaled(self, hits, scale, samples=4, radius=1.0, seed=0, key0=0, channels=1, normal_squarings=3,
+                                 sigma_plane=0.0, refine=False, key0_refine=0x80000000, return_flags=False):
+        """ambient_occlusion() gathered for every scale-th pixel in both directions only and carried to every pixel of the
+        frame hits (HIT_DTYPE (Wn, H)) by upsample_guided() (include/rt_capi_upsample.h) -> float32 (Wn, H), or (Wn, H, 3) with
+        channels = 3, and with return_flags also the holes, bool (Wn, H).  DEFINITION: cells = subsample_hits(hits, scale,
+        white=True); lo = ambient_occlusion(cells, samples, radius, seed, key0, channels); the result is upsample_guided(hits,
+        lo, scale, normal_squarings, sigma_plane=sigma_plane, dead_value=1.0, return_flags=True) bit for bit.  refine: the holes,
+        in ascending pixel order (np.flatnonzero(flags)), are then gathered as one more batch of their own full-resolution
+        records with key0 = key0_refine, and written over the fallback."""
+        hits = _frame_records(hits)
+        cells = subsample_hits(hits, scale, True, self._device)
+        lo = self.ambient_occlusion(cells, samples, radius, seed, key0, channels)
+        out, flags = upsample_guided(hits, lo, scale, normal_squarings, False, False, sigma_plane, 1.0, None, True, self._device)
+        if refine and flags.any():
+            idx = np.flatnonzero(flags)
+            holes = np.ascontiguousarray(hits.reshape(-1)[idx])
+            out.reshape((hits.size,) + out.shape[2:])[idx] = self.ambient_occlusion(holes, samples, radius, seed, key0_refine, channels)
+        return (out, flags) if return_flags else out
+
+    def indirect_diffuse_scaled(self, hits, scale, samples=4, gather_depth=1, gain=1.0, seed=0, key0=0, emitters=False,
+                                chunk_records=0, base=None, normal_squarings=3, sigma_plane=0.0, refine=False,
+                                key0_refine=0x80000000, return_flags=False):
+        """indirect_diffuse() gathered for every scale-th pixel in both directions only and carried to every pixel of the frame
+        hits (HIT_DTYPE (Wn, H)) by upsample_guided() (include/rt_capi_upsample.h) -> float32 (Wn, H, 3), and with return_flags
+        also the holes, bool (Wn, H).  DEFINITION: cells = subsample_hits(hits, scale, white=True); lo = indirect_diffuse(cells,
+        samples, gather_depth, gain, seed, key0, emitters) -- no base: irradiance without albedo, (kd gain) mean; the result is
+        upsample_guided(hits, lo, scale, normal_squarings, match_color=False, modulate=True, sigma_plane=sigma_plane,
+        dead_value=0.0, base=base, return_flags=True) bit for bit: the filter runs across a surface's checker tiles and texels,
+        and each pixel multiplies by its own albedo.  refine: the holes, in ascending pixel order (np.flatnonzero(flags)), are
+        then gathered as one more batch of their own full-colour, full-resolution records with key0 = key0_refine and no base,
+        and base + term (term, without a base: one fp32 add a word) is written over the fallback.  chunk_records never changes
+        the result."""
+        hits = _frame_records(hits)
+        kw = dict(samples=samples, gather_depth=gather_depth, gain=gain, seed=seed, emitters=emitters, chunk_records=chunk_records)
+        cells = subsample_hits(hits, scale, True, self._device)
+        lo = self.indirect_diffuse(cells, key0=key0, **kw)
+        out, flags = upsample_guided(hits, lo, scale, normal_squarings, False, True, sigma_plane, 0.0, base, True, self._device)
+        if refine and flags.any():
+            idx = np.flatnonzero(flags)
+            term = self.indirect_diffuse(np.ascontiguousarray(hits.reshape(-1)[idx]), key0=key0_refine, **kw)
+            if base is not None:
+                term = np.ascontiguousarray(base, dtype=np.float32).reshape(-1, 3)[idx] + term
+            out.reshape(-1, 3)[idx] = term
+        return (out, flags) if return_flags else out
+
+    def _upsample_device(self, params, W, H, records, lo, base, out, flags, stream):
+        capi.check(self._lib.rt_upsample_guided_device(int(self._device), C.byref(params), W, H, records.data_ptr(), lo.data_ptr(),
+                                                       base.data_ptr() if base is not None else None, out.data_ptr(),
+                                                       flags.data_ptr() if flags is not None else None, stream.cuda_stream))
+
+    def _subsample_device(self, scale, W, H, records, stream):
+        """-> (the white cells of a frame's records as an int32 tensor, Wl, Hl), enqueued"""
+        import torch
+        s = int(scale)
+        if not 2 <= s <= 8:                                           # (refused by the call itself)
+            capi.check(self._lib.rt_subsample_hits_device(int(self._device), s, 1, W, H, None, None, None))
+        Wl, Hl = -(-W // s), -(-H // s)
+        cells = torch.empty((Wl * Hl * 12,), dtype=torch.int32, device="cuda")
+        capi.check(self._lib.rt_subsample_hits_device(int(self._device), s, 1, W, H, records.data_ptr(), cells.data_ptr(),
+                                                      stream.cuda_stream))
+        return cells, Wl, Hl
 
     def indirect_diffuse(self, hits, samples=4, gather_depth=1, gain=1.0, seed=0, key0=0, emitters=False, chunk_records=0,
                          base=None):
@@ -518,7 +644,75 @@ class Renderer:
         capi.check(self._lib.rt_get_indirect_info(self._scene, C.byref(info)))
         return info
 
-    def render_indirect(self, W, H, max_depth, samples=4, gather_depth=1, gain=1.0, seed=0, emitters=False, denoise=None):
+    def _render_ao_scaled(self, W, H, samples, radius, seed, channels, scale, normal_squarings, sigma_plane, refine, key0_refine):
+        import torch
+        C_ = 3 if int(channels) == 3 else 1                          # (a bad count is refused by the calls below)
+        up = upsample_params(scale, channels, normal_squarings, False, False, sigma_plane, 1.0)
+        kw = dict(samples=samples, radius=radius, seed=seed, channels=channels)
+        with torch.cuda.device(int(self._device)):
+            colours = torch.empty((W, H, 3), dtype=torch.float32, device="cuda")
+            records = torch.empty((W * H * 12,), dtype=torch.int32, device="cuda")
+            plane = torch.empty((W * H, C_), dtype=torch.float32, device="cuda")
+            flags = torch.empty((W * H,), dtype=torch.uint8, device="cuda") if refine else None
+            stream = torch.cuda.current_stream()
+            self.render_gbuffer_device(W, H, 0, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
+            cells, Wl, Hl = self._subsample_device(scale, W, H, records, stream)
+            lo = torch.empty((Wl * Hl, C_), dtype=torch.float32, device="cuda")
+            self.ambient_occlusion_device(Wl * Hl, Hl, cells.data_ptr(), lo.data_ptr(), key0=0, stream=stream.cuda_stream, **kw)
+            self._upsample_device(up, W, H, records, lo, None, plane, flags, stream)
+            if refine:
+                idx = torch.nonzero(flags).reshape(-1)                 # the one read-back: how many holes there are
+                if idx.numel():
+                    holes = records.view(W * H, 12)[idx].contiguous()
+                    term = torch.empty((idx.numel(), C_), dtype=torch.float32, device="cuda")
+                    self.ambient_occlusion_device(idx.numel(), idx.numel(), holes.data_ptr(), term.data_ptr(), key0=key0_refine,
+                                                  stream=stream.cuda_stream, **kw)
+                    plane[idx] = term
+            out = plane.cpu().numpy()                                 # the one download
+        return out.reshape(W, H, 3) if C_ == 3 else out.reshape(W, H)
+
+    def _render_indirect_scaled(self, W, H, max_depth, kw, denoise, scale, normal_squarings, sigma_plane, refine, key0_refine):
+        import torch
+        device = int(self._device)
+        up = upsample_params(scale, 3, normal_squarings, False, True, sigma_plane, 0.0)
+        if denoise is not None:
+            dn = capi.RtDenoiseParams(int(denoise.get("iterations", 2)), int(denoise.get("normal_squarings", 3)),
+                                      float(denoise.get("sigma_color", 1.0)))
+            scratch_bytes = self._lib.rt_denoise_scratch_bytes(C.byref(dn), W, H)
+            if not scratch_bytes:                                     # (bad parameters: refused by the call itself)
+                capi.check(self._lib.rt_denoise_device(device, C.byref(dn), W, H, None, None, None, None, None))
+        with torch.cuda.device(device):
+            colours = torch.empty((W * H, 3), dtype=torch.float32, device="cuda")
+            records = torch.empty((W * H * 12,), dtype=torch.int32, device="cuda")
+            flags = torch.empty((W * H,), dtype=torch.uint8, device="cuda") if refine else None
+            stream = torch.cuda.current_stream()
+            self.render_gbuffer_device(W, H, max_depth, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
+            cells, Wl, Hl = self._subsample_device(scale, W, H, records, stream)
+            lo = torch.empty((Wl * Hl, 3), dtype=torch.float32, device="cuda")
+            self.indirect_diffuse_device(Wl * Hl, cells.data_ptr(), 0, lo.data_ptr(), stream.cuda_stream, **kw)
+            # the upsampled term: onto the colours in place, or alone where a filter or the holes' batch comes before the add
+            alone = denoise is not None or refine
+            term = torch.empty((W * H, 3), dtype=torch.float32, device="cuda") if alone else colours
+            self._upsample_device(up, W, H, records, lo, None if alone else colours, term, flags, stream)
+            if refine:
+                idx = torch.nonzero(flags).reshape(-1)                 # the one read-back: how many holes there are
+                if idx.numel():
+                    holes = records.view(W * H, 12)[idx].contiguous()
+                    fine = torch.empty((idx.numel(), 3), dtype=torch.float32, device="cuda")
+                    self.indirect_diffuse_device(idx.numel(), holes.data_ptr(), 0, fine.data_ptr(), stream.cuda_stream,
+                                                 **dict(kw, key0=key0_refine))
+                    term[idx] = fine
+            if denoise is not None:
+                clean = torch.empty((W * H, 3), dtype=torch.float32, device="cuda")
+                scratch = torch.empty(((scratch_bytes + 15) // 16 * 4,), dtype=torch.int32, device="cuda")
+                capi.check(self._lib.rt_denoise_device(device, C.byref(dn), W, H, term.data_ptr(), records.data_ptr(),
+                                                       clean.data_ptr(), scratch.data_ptr(), stream.cuda_stream))
+                term = clean
+            out = torch.add(colours, term) if alone else colours
+            return out.cpu().numpy().reshape(W, H, 3)                 # the one download
+
+    def render_indirect(self, W, H, max_depth, samples=4, gather_depth=1, gain=1.0, seed=0, emitters=False, denoise=None, scale=1,
+                        normal_squarings=3, sigma_plane=0.0, refine=False, key0_refine=0x80000000):
         """A W x H frame with one diffuse bounce added, computed on the GPU where its records were made
         (include/rt_capi_indirect.h): rt_render_gbuffer_device and rt_indirect_diffuse_device -- the frame's colours the base,
         in place -- enqueued on one stream with no host wait between them, then one download -> float32 (W, H, 3).  The result
@@ -526,10 +720,18 @@ class Renderer:
         a dict of denoise()'s keywords (iterations, sigma_color, normal_squarings): the indirect term alone is then computed
         without a base, filtered by rt_denoise_device with the frame's records and added to the direct colours by one fp32
         add -- rgb + denoise(indirect_diffuse(hits, ...), hits, ...) bit for bit.  The device buffers and the stream are
-        torch's, so the process must have imported torch before the library was loaded."""
+        torch's, so the process must have imported torch before the library was loaded.  scale 2..8
+        (include/rt_capi_upsample.h): the term is gathered for every scale-th pixel in both directions and upsampled --
+        rt_subsample_hits_device, rt_indirect_diffuse_device and rt_upsample_guided_device on that one stream with no host wait
+        -- indirect_diffuse_scaled(hits, scale, ..., base=rgb) bit for bit, and with denoise rgb + denoise(
+        indirect_diffuse_scaled(hits, scale, ...), hits, ...); refine costs exactly one read-back of the flags before the holes'
+        batch is enqueued.  With scale 1 nothing of this runs and normal_squarings, sigma_plane and refine are not read."""
         import torch
         device = int(self._device)
         kw = dict(samples=samples, gather_depth=gather_depth, gain=gain, seed=seed, emitters=emitters)
+        if scale != 1:
+            return self._render_indirect_scaled(W, H, max_depth, kw, denoise, scale, normal_squarings, sigma_plane, refine,
+                                                key0_refine)
         if denoise is not None:
             dn = capi.RtDenoiseParams(int(denoise.get("iterations", 2)), int(denoise.get("normal_squarings", 3)),
                                       float(denoise.get("sigma_color", 1.0)))
