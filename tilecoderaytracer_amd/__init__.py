@@ -13,6 +13,8 @@ missing or no GPU is present, rendering raises.
 from .capi import RtError, load_library, library_path  # noqa: F401
 from .host import HostScene  # noqa: F401
 from .renderer import Renderer, adaptive_flags, denoise, encode_image, indirect_rays, lens_rays, subsample_hits, upsample_guided  # noqa: F401
+from .renderer import TemporalHistory, temporal_accumulate, temporal_params  # noqa: F401
 
 __all__ = ["RtError", "load_library", "library_path", "HostScene", "Renderer", "adaptive_flags", "denoise", "encode_image",
-           "indirect_rays", "lens_rays", "subsample_hits", "upsample_guided"]
+           "indirect_rays", "lens_rays", "subsample_hits", "upsample_guided", "TemporalHistory", "temporal_accumulate",
+           "temporal_params"]

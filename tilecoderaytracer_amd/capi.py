@@ -65,6 +65,13 @@ class RtUpsampleParams(C.Structure):
                 ("modulate", C.c_int32), ("sigma_plane", C.c_float), ("dead_value", C.c_float)]
 
 
+class RtTemporalParams(C.Structure):
+    """include/rt_temporal.h: channels (1 or 3), match_color (0 / 1), the cap of the history length (1..65535), the normals'
+    cosine (-1..1) and the tangent-plane distance (0: no test) a tap must keep, and the floors of the two blend weights (0..1)."""
+    _fields_ = [("channels", C.c_int32), ("match_color", C.c_int32), ("max_history", C.c_int32), ("normal_cos", C.c_float),
+                ("plane_eps", C.c_float), ("alpha", C.c_float), ("alpha_moments", C.c_float)]
+
+
 class RtAoParams(C.Structure):
     """include/rt_capi_ao.h: n (n x n directions per record, 1..8), the radius a direction is followed for, the seed, the first
     record's key, channels (1, or 3 equal ones)."""
@@ -354,6 +361,13 @@ def load_library():
         lib.rt_upsample_guided_device.argtypes = [i, C.POINTER(RtUpsampleParams), i, i, vp, vp, vp, vp, vp, vp]
         for name in ("rt_subsample_hits", "rt_subsample_hits_device", "rt_upsample_guided", "rt_upsample_guided_device"):
             getattr(lib, name).restype = i
+    # include/rt_temporal.h (likewise absent from older builds)
+    if hasattr(lib, "rt_temporal_accumulate"):
+        lib.rt_capi_temporal_version.restype = i
+        head = [i, C.POINTER(RtTemporalParams), C.POINTER(RtCameraDesc), C.POINTER(RtCameraDesc), i, i, i, i] + [vp] * 11
+        lib.rt_temporal_accumulate.argtypes = head + [C.POINTER(C.c_double)]
+        lib.rt_temporal_accumulate_device.argtypes = head + [vp]
+        lib.rt_temporal_accumulate.restype = lib.rt_temporal_accumulate_device.restype = i
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):
         lib.rt_capi_launch_version.restype = i

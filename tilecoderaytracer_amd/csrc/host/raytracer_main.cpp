@@ -44,6 +44,12 @@
  *                       and carry the term to every pixel by rt_upsample_guided (include/rt_capi_upsample.h: 3 normal squarings,
  *                       plane sigma SIGMA_PLANE >= 0, default 0: none); `refine`: the holes it reports are gathered at full
  *                       resolution afterwards, as one more batch with key0 0x80000000
+ *   --accumulate K[:ALPHA]  K frames (1..65535) of the frame's own camera, the sampled term of the run -- --soft (through
+ *                       rt_scene_set_shadow_seed), --ao or --indirect -- drawn with seeds 0..K-1, accumulated by
+ *                       rt_temporal_accumulate (include/rt_temporal.h: normal cosine 0.9, plane distance 0.05, max_history K,
+ *                       both blend weights at least ALPHA, 0..1, default 0: the running mean); the last accumulated frame (and
+ *                       occlusion plane) is what the writers get.  One GPU, with at least one of those terms, without --ssaa,
+ *                       --adaptive or --lens
  */
 #include <chrono>
 #include <cmath>
@@ -62,7 +68,9 @@
 #include "../../../include/rt_capi_image.h"
 #include "../../../include/rt_capi_indirect.h"
 #include "../../../include/rt_capi_lens.h"
+#include "../../../include/rt_capi_soft.h"
 #include "../../../include/rt_capi_ssaa.h"
+#include "../../../include/rt_temporal.h"
 #include "../../../include/rt_capi_upsample.h"
 #include "celio_model.hpp"
 #include "screen_ppm.hpp"
@@ -82,7 +90,7 @@ static int usage(const char *argv0) {
                  "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n"
                  "          [--ao N[:RADIUS] --ao-ppm FILE] [--adaptive 1|2|4[:COLOR[:COS]] [--adaptive-mask FILE]]\n"
                  "          [--lens N[:APERTURE[:FOCUS[:SEED]]]] [--indirect N[:DEPTH[:GAIN[:SEED]]]]\n"
-                 "          [--gather-scale S[:SIGMA_PLANE[:refine]]]\n", argv0);
+                 "          [--gather-scale S[:SIGMA_PLANE[:refine]]] [--accumulate K[:ALPHA]]\n", argv0);
     return 1;
 }
 
@@ -96,6 +104,8 @@ int main(int argc, char **argv) {
     std::string indirect_arg;                    /* --indirect N[:DEPTH[:GAIN[:SEED]]] (include/rt_capi_indirect.h) */
     std::string gather_arg;                      /* --gather-scale S[:SIGMA_PLANE[:refine]] (include/rt_capi_upsample.h) */
     bool has_gather = false;
+    std::string accumulate_arg;                  /* --accumulate K[:ALPHA] (include/rt_temporal.h) */
+    bool has_accumulate = false;
     std::string denoise;                         /* --denoise IT[:SIGMA[:K]] (include/rt_capi_denoise.h) */
     std::vector<std::string> soft;               /* --soft I:N[:R]: light I an area light, N x N samples, radius R (include/rt_capi_soft.h) */
     for (int i = 1; i < argc; ++i) {
@@ -121,6 +131,7 @@ int main(int argc, char **argv) {
         else if (a == "--lens" && i + 1 < argc) lens_arg = argv[++i];
         else if (a == "--indirect" && i + 1 < argc) indirect_arg = argv[++i];
         else if (a == "--gather-scale" && i + 1 < argc) gather_arg = argv[++i], has_gather = true;
+        else if (a == "--accumulate" && i + 1 < argc) accumulate_arg = argv[++i], has_accumulate = true;
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
@@ -260,6 +271,23 @@ int main(int argc, char **argv) {
         }
         if (ao_arg.empty() && indirect_arg.empty()) return usage(argv[0]);
     }
+    rt_temporal_params tp = {3, 0, 0, 0.9f, 0.05f, 0.0f, 0.0f};       /* max_history: K, 0 without --accumulate */
+    if (has_accumulate) {
+        /* K or K:ALPHA, and nothing else; one GPU, with a sampled term, the frame's records its own pixels' */
+        char *end = nullptr;
+        const long k = std::strtol(accumulate_arg.c_str(), &end, 10);
+        if (end == accumulate_arg.c_str() || (*end != '\0' && *end != ':') || k < 1 || k > 65535) return usage(argv[0]);
+        tp.max_history = (int)k;
+        if (*end == ':') {
+            const char *v = end + 1;
+            tp.alpha = std::strtof(v, &end);
+            if (end == v || *end != '\0' || !(tp.alpha >= 0.0f && tp.alpha <= 1.0f)) return usage(argv[0]);
+            tp.alpha_moments = tp.alpha;
+        }
+        if (soft.empty() && ao_arg.empty() && indirect_arg.empty()) return usage(argv[0]);
+        if (gpus > 1 || ssaa > 1 || !adaptive_arg.empty() || !lens_arg.empty()) return usage(argv[0]);
+    }
+    const int frames = has_accumulate ? tp.max_history : 1;
     /* a term gathered for the cells of the frame's records and upsampled onto `base` (or alone) into out, 3 channels: gather(n,
      * rows, records, key0, values) is the full-resolution call */
     auto gather_scaled = [&](const std::vector<rt_hit> &records, auto gather, int modulate, float dead_value, const float *base,
@@ -356,7 +384,8 @@ int main(int argc, char **argv) {
         return 1;
     }
     pixels.assign((size_t)W * (size_t)H * 3, 0.0f);
-    std::vector<rt_hit> hits(hits_path.empty() && denoise.empty() && ao_arg.empty() && indirect_arg.empty() ? 0 : (size_t)W * (size_t)H);
+    std::vector<rt_hit> hits(hits_path.empty() && denoise.empty() && ao_arg.empty() && indirect_arg.empty() && !has_accumulate
+                                 ? 0 : (size_t)W * (size_t)H);
     std::vector<float> ao_plane(ao_arg.empty() ? 0 : (size_t)W * (size_t)H * 3);
 
     std::printf("****** Start Ray Tracing. *******\n");
@@ -367,75 +396,110 @@ int main(int argc, char **argv) {
     if (gpus == 1) {
         rt_scene *scene = nullptr;
         rc = flat.create(0, &scene);                /* with the scene's bitmap textures, refractions and area lights, if any */
-        if (rc == RT_OK && ad.samples > 0) {
-            if (!mask_path.empty()) mask.assign((size_t)W * (size_t)H, 0);
-            rc = rt_render_adaptive(scene, &cam, W, H, 0, W, depth, &ad, pixels.data(), mask.empty() ? nullptr : mask.data());
-            rt_adaptive_info info;
-            if (rc == RT_OK && rt_get_adaptive_info(scene, &info) == RT_OK) {
-                camera_rays += (double)info.rays;
-                std::printf("Adaptive supersampling     : %lld of %lld pixels refined (%.1f %%), %lld rays in %d launch(es); first pass "
-                            "%f ms, flags %f ms, trace %f ms, resolve %f ms\n", (long long)info.flagged, (long long)info.pixels,
-                            100.0 * (double)info.flagged / (double)info.pixels, (long long)info.rays, info.chunks, info.first_pass_ms,
-                            info.flag_ms, info.trace_ms, info.resolve_ms);
+        /* --accumulate: the history of the frame and of the occlusion plane, two sets each that take turns */
+        struct History {
+            std::vector<float> value[2], moments[2], length[2], variance;
+        } frame_history, ao_history;
+        double accumulate_ms = 0.0;
+        auto accumulate = [&](History &h, std::vector<float> &cur, int k) -> int {
+            const size_t n = (size_t)W * (size_t)H;
+            const int to = k & 1, from = to ^ 1;
+            h.value[to].resize(n * 3), h.moments[to].resize(n * 2), h.length[to].resize(n), h.variance.resize(n);
+            double ms = 0.0;
+            /* the camera does not move and the scene does not change: the previous frame's records are this frame's */
+            const int r = rt_temporal_accumulate(0, &tp, k ? &cam : nullptr, &cam, W, H, 0, W, cur.data(), hits.data(),
+                                                 k ? hits.data() : nullptr, k ? h.value[from].data() : nullptr,
+                                                 k ? h.moments[from].data() : nullptr, k ? h.length[from].data() : nullptr,
+                                                 h.value[to].data(), h.moments[to].data(), h.length[to].data(), h.variance.data(),
+                                                 nullptr, &ms);
+            accumulate_ms += ms;
+            if (r == RT_OK) cur = h.value[to];
+            return r;
+        };
+        for (int frame = 0; rc == RT_OK && frame < frames; ++frame) {
+            if (has_accumulate) {
+                ao.seed = ind.seed = (uint32_t)frame;
+                if (!soft.empty()) rc = rt_scene_set_shadow_seed(scene, (uint32_t)frame);
             }
-        } else if (rc == RT_OK && lens.samples > 0) {
-            rc = rt_render_lens(scene, &cam, W, H, 0, W, depth, &lens, pixels.data());
-            rt_lens_info info;
-            if (rc == RT_OK && rt_get_lens_info(scene, &info) == RT_OK) {
-                camera_rays = (double)info.rays;
-                std::printf("Lens camera                : %d x %d samples, aperture %g, focus %g, seed %u: %lld rays in %d chunk(s); "
-                            "ray generation %f ms, trace %f ms, resolve %f ms\n", lens.samples, lens.samples, (double)lens.aperture,
-                            (double)lens.focus, lens.seed, (long long)info.rays, info.chunks, info.raygen_ms, info.trace_ms,
-                            info.resolve_ms);
+            if (rc != RT_OK) break;
+            if (ad.samples > 0) {
+                if (!mask_path.empty()) mask.assign((size_t)W * (size_t)H, 0);
+                rc = rt_render_adaptive(scene, &cam, W, H, 0, W, depth, &ad, pixels.data(), mask.empty() ? nullptr : mask.data());
+                rt_adaptive_info info;
+                if (rc == RT_OK && rt_get_adaptive_info(scene, &info) == RT_OK) {
+                    camera_rays += (double)info.rays;
+                    std::printf("Adaptive supersampling     : %lld of %lld pixels refined (%.1f %%), %lld rays in %d launch(es); first pass "
+                                "%f ms, flags %f ms, trace %f ms, resolve %f ms\n", (long long)info.flagged, (long long)info.pixels,
+                                100.0 * (double)info.flagged / (double)info.pixels, (long long)info.rays, info.chunks, info.first_pass_ms,
+                                info.flag_ms, info.trace_ms, info.resolve_ms);
+                }
+            } else if (lens.samples > 0) {
+                rc = rt_render_lens(scene, &cam, W, H, 0, W, depth, &lens, pixels.data());
+                rt_lens_info info;
+                if (rc == RT_OK && rt_get_lens_info(scene, &info) == RT_OK) {
+                    camera_rays = (double)info.rays;
+                    std::printf("Lens camera                : %d x %d samples, aperture %g, focus %g, seed %u: %lld rays in %d chunk(s); "
+                                "ray generation %f ms, trace %f ms, resolve %f ms\n", lens.samples, lens.samples, (double)lens.aperture,
+                                (double)lens.focus, lens.seed, (long long)info.rays, info.chunks, info.raygen_ms, info.trace_ms,
+                                info.resolve_ms);
+                }
+            } else {
+                rc = ssaa > 1 ? rt_render_ssaa(scene, &cam, W, H, 0, W, depth, ssaa, pixels.data())
+                   : !hits.empty() ? rt_render_gbuffer(scene, &cam, W, H, 0, W, depth, pixels.data(), hits.data())
+                                   : rt_render(scene, &cam, W, H, 0, W, depth, pixels.data());
             }
-        } else if (rc == RT_OK) {
-            rc = ssaa > 1 ? rt_render_ssaa(scene, &cam, W, H, 0, W, depth, ssaa, pixels.data())
-               : !hits.empty() ? rt_render_gbuffer(scene, &cam, W, H, 0, W, depth, pixels.data(), hits.data())
-                               : rt_render(scene, &cam, W, H, 0, W, depth, pixels.data());
+            if (rc == RT_OK) {
+                rt_timing tm;
+                if (rt_get_timing(scene, &tm) == RT_OK) kernel_ms = tm.last_kernel_ms;
+            }
+            if (rc == RT_OK && !ao_arg.empty()) {           /* (before the filter: it reads the records, not the colours) */
+                if ((double)W * (double)H > 533333333.0) {           /* (rt_ambient_occlusion's record limit; W * H must fit its int) */
+                    std::fprintf(stderr, "--ao: the frame has more than 533333333 pixels\n");
+                    rt_scene_destroy(scene);
+                    return 1;
+                }
+                if (has_gather)
+                    rc = gather_scaled(hits, [&](int n, int rows, const rt_hit *records, uint32_t key0, float *values) {
+                             rt_ao_params a = ao;
+                             a.key0 = key0;
+                             return rt_ambient_occlusion(scene, &a, n, rows, records, values);
+                         }, 0, 1.0f, nullptr, ao_plane.data(), "Ambient occlusion");
+                else
+                    rc = rt_ambient_occlusion(scene, &ao, W * H, H, hits.data(), ao_plane.data());
+                rt_timing tm;
+                if (rc == RT_OK && rt_get_timing(scene, &tm) == RT_OK)
+                    std::printf("Ambient occlusion (ms)     : %f  (%d x %d directions, radius %g)\n", tm.last_kernel_ms, ao.samples,
+                                ao.samples, (double)ao.radius);
+            }
+            if (rc == RT_OK && ind.samples > 0) {
+                if ((double)W * (double)H > 533333333.0) {           /* (rt_indirect_diffuse's record limit; W * H must fit its int) */
+                    std::fprintf(stderr, "--indirect: the frame has more than 533333333 pixels\n");
+                    rt_scene_destroy(scene);
+                    return 1;
+                }
+                if (has_gather)
+                    rc = gather_scaled(hits, [&](int n, int, const rt_hit *records, uint32_t key0, float *values) {
+                             rt_indirect_params g = ind;
+                             g.key0 = key0;
+                             return rt_indirect_diffuse(scene, &g, n, records, nullptr, values);
+                         }, 1, 0.0f, pixels.data(), pixels.data(), "Indirect diffuse ");
+                else
+                    rc = rt_indirect_diffuse(scene, &ind, W * H, hits.data(), pixels.data(), pixels.data());
+                rt_indirect_info info;
+                if (rc == RT_OK && rt_get_indirect_info(scene, &info) == RT_OK)
+                    std::printf("Indirect diffuse           : %d x %d gather rays at depth %d, gain %g, seed %u: %lld rays in %d chunk(s); "
+                                "ray generation %f ms, trace %f ms, query %f ms, resolve %f ms\n", ind.samples, ind.samples,
+                                ind.gather_depth, (double)ind.gain, ind.seed, (long long)info.rays, info.chunks, info.raygen_ms,
+                                info.trace_ms, info.query_ms, info.resolve_ms);
+            }
+            if (rc == RT_OK && has_accumulate) rc = accumulate(frame_history, pixels, frame);
+            if (rc == RT_OK && has_accumulate && !ao_arg.empty()) rc = accumulate(ao_history, ao_plane, frame);
         }
-        if (rc == RT_OK) {
-            rt_timing tm;
-            if (rt_get_timing(scene, &tm) == RT_OK) kernel_ms = tm.last_kernel_ms;
-        }
-        if (rc == RT_OK && !ao_arg.empty()) {           /* (before the filter: it reads the records, not the colours) */
-            if ((double)W * (double)H > 533333333.0) {           /* (rt_ambient_occlusion's record limit; W * H must fit its int) */
-                std::fprintf(stderr, "--ao: the frame has more than 533333333 pixels\n");
-                rt_scene_destroy(scene);
-                return 1;
-            }
-            if (has_gather)
-                rc = gather_scaled(hits, [&](int n, int rows, const rt_hit *records, uint32_t key0, float *values) {
-                         rt_ao_params a = ao;
-                         a.key0 = key0;
-                         return rt_ambient_occlusion(scene, &a, n, rows, records, values);
-                     }, 0, 1.0f, nullptr, ao_plane.data(), "Ambient occlusion");
-            else
-                rc = rt_ambient_occlusion(scene, &ao, W * H, H, hits.data(), ao_plane.data());
-            rt_timing tm;
-            if (rc == RT_OK && rt_get_timing(scene, &tm) == RT_OK)
-                std::printf("Ambient occlusion (ms)     : %f  (%d x %d directions, radius %g)\n", tm.last_kernel_ms, ao.samples,
-                            ao.samples, (double)ao.radius);
-        }
-        if (rc == RT_OK && ind.samples > 0) {
-            if ((double)W * (double)H > 533333333.0) {           /* (rt_indirect_diffuse's record limit; W * H must fit its int) */
-                std::fprintf(stderr, "--indirect: the frame has more than 533333333 pixels\n");
-                rt_scene_destroy(scene);
-                return 1;
-            }
-            if (has_gather)
-                rc = gather_scaled(hits, [&](int n, int, const rt_hit *records, uint32_t key0, float *values) {
-                         rt_indirect_params g = ind;
-                         g.key0 = key0;
-                         return rt_indirect_diffuse(scene, &g, n, records, nullptr, values);
-                     }, 1, 0.0f, pixels.data(), pixels.data(), "Indirect diffuse ");
-            else
-                rc = rt_indirect_diffuse(scene, &ind, W * H, hits.data(), pixels.data(), pixels.data());
-            rt_indirect_info info;
-            if (rc == RT_OK && rt_get_indirect_info(scene, &info) == RT_OK)
-                std::printf("Indirect diffuse           : %d x %d gather rays at depth %d, gain %g, seed %u: %lld rays in %d chunk(s); "
-                            "ray generation %f ms, trace %f ms, query %f ms, resolve %f ms\n", ind.samples, ind.samples,
-                            ind.gather_depth, (double)ind.gain, ind.seed, (long long)info.rays, info.chunks, info.raygen_ms,
-                            info.trace_ms, info.query_ms, info.resolve_ms);
+        if (rc == RT_OK && has_accumulate) {
+            double mean = 0.0;
+            for (float v : frame_history.variance) mean += v;
+            std::printf("Temporal accumulation      : %d frame(s), seeds 0..%d, alpha %g: kernels %f ms, mean luminance variance %g\n", frames,
+                        frames - 1, (double)tp.alpha, accumulate_ms, mean / ((double)W * (double)H));
         }
         if (rc == RT_OK && !denoise.empty()) {
             double denoise_ms = 0.0;

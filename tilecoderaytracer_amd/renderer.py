@@ -176,6 +176,147 @@ def upsample_guided(hits, lo, scale, normal_squarings=3, match_color=False, modu
     return (out, flags.view(np.bool_)) if return_flags else out
 
 
+def temporal_params(channels=3, match_color=False, max_history=32, normal_cos=0.9, plane_eps=0.05, alpha=0.0, alpha_moments=0.0):
+    """temporal_accumulate's keywords -> an RtTemporalParams (include/rt_temporal.h); the library checks the values."""
+    return capi.RtTemporalParams(int(channels), int(match_color), int(max_history), float(normal_cos), float(plane_eps),
+                                 float(alpha), float(alpha_moments))
+
+
+def _camera_ptr(camera):
+    """None, an RtCameraDesc or a pointer to one -> what ctypes passes for a const rt_camera_desc *"""
+    return C.byref(camera) if isinstance(camera, capi.RtCameraDesc) else camera
+
+
+def temporal_accumulate(cur, hits, camera, prev=None, x0=0, W=None, device=0, **params):
+    """One frame blended into the accumulated history of the frame before (include/rt_temporal.h, rt_temporal_accumulate):
+    cur float32 (Wn, H) -- one channel -- or (Wn, H, 3) and hits HIT_DTYPE (Wn, H), columns [x0, x0 + Wn) of a W x H frame seen by
+    `camera` (an RtCameraDesc); prev None -- the first frame -- or (camera, hits, value, moments, length) of the WHOLE previous
+    frame: its camera, its records (W, H) and what this call returned for it.  -> (value of cur's shape, moments float32
+    (Wn, H, 2), length float32 (Wn, H), variance float32 (Wn, H), flags bool (Wn, H): the pixels without history).  params:
+    temporal_params()'s keywords but channels, which cur's shape gives.  Runs on GPU `device`; there is no CPU path."""
+    hits = _frame_records(hits)
+    cur = np.ascontiguousarray(cur, dtype=np.float32)
+    channels = 3 if cur.ndim == 3 else 1
+    Wn, H = hits.shape
+    if cur.shape != hits.shape + ((3,) if channels == 3 else ()):
+        raise ValueError(f"cur must be {hits.shape} or {hits.shape + (3,)}, not {cur.shape}")
+    pr = temporal_params(channels, **params)
+    ptr = [None] * 4
+    cam_prev = None
+    if prev is not None:
+        cam_prev, prev_hits, value, moments, length = prev
+        prev_hits = _frame_records(prev_hits)
+        W = prev_hits.shape[0] if W is None else int(W)
+        shapes = ((W, H), (W, H) + ((3,) if channels == 3 else ()), (W, H, 2), (W, H))
+        kept = [prev_hits] + [np.ascontiguousarray(a, dtype=np.float32) for a in (value, moments, length)]
+        for a, shape, name in zip(kept, shapes, ("hits", "value", "moments", "length")):
+            if a.shape != shape:
+                raise ValueError(f"the previous frame's {name} must have shape {shape}, not {a.shape}")
+        ptr = [a.ctypes.data for a in kept]
+    W = int(x0) + Wn if W is None else int(W)
+    out = np.empty(cur.shape, dtype=np.float32)
+    out_moments, out_len = np.empty((Wn, H, 2), dtype=np.float32), np.empty((Wn, H), dtype=np.float32)
+    variance, flags = np.empty((Wn, H), dtype=np.float32), np.empty((Wn, H), dtype=np.uint8)
+    capi.check(capi.load_library().rt_temporal_accumulate(int(device), C.byref(pr), _camera_ptr(cam_prev), _camera_ptr(camera), W, H,
+                                                          int(x0), int(x0) + Wn, cur.ctypes.data, hits.ctypes.data, *ptr,
+                                                          out.ctypes.data, out_moments.ctypes.data, out_len.ctypes.data,
+                                                          variance.ctypes.data, flags.ctypes.data, None))
+    return out, out_moments, out_len, variance, flags.view(np.bool_)
+
+
+class TemporalHistory:
+    """The accumulated history of a W x H frame sequence on GPU `device` (include/rt_temporal.h): two ping-pong sets of device
+    buffers (records, value, moments, length) owned through torch, the previous frame's camera, and rt_temporal_accumulate_device
+    between them.  params: temporal_params()'s keywords but channels.  The process must have imported torch before the library
+    was loaded."""
+
+    def __init__(self, W, H, channels=3, device=0, **params):
+        import torch
+        self.W, self.H, self.channels, self._device = int(W), int(H), int(channels), int(device)
+        self._params = temporal_params(channels, **params)
+        self._lib = capi.load_library()
+        if self.channels not in (1, 3) or self.W <= 0 or self.H <= 0:    # (refused by the call itself, before any allocation)
+            capi.check(self._lib.rt_temporal_accumulate_device(self._device, C.byref(self._params), None, None, self.W, self.H, 0,
+                                                               self.W, *([None] * 12)))
+            raise ValueError("channels must be 1 or 3")
+        n = self.W * self.H
+        with torch.cuda.device(self._device):
+            new = lambda words, dtype: torch.empty((words,), dtype=dtype, device="cuda")
+            self._sets = [dict(hits=new(n * 12, torch.int32), value=new(n * self.channels, torch.float32),
+                               moments=new(n * 2, torch.float32), length=new(n, torch.float32)) for _ in range(2)]
+            self._variance, self._flags = new(n, torch.float32), new(n, torch.uint8)
+        self.reset()
+
+    def reset(self):
+        """forget the history: the next frame is a first frame"""
+        self.frames, self._next_column, self._cam_prev, self._cam = 0, 0, None, None
+
+    def _copy_camera(self, camera):
+        cam = capi.RtCameraDesc()
+        C.memmove(C.byref(cam), _camera_ptr(camera), C.sizeof(cam))
+        return cam
+
+    def push_device(self, value, hits, camera, x0=0, x1=None, stream=None):
+        """push() of torch tensors on the device (float32 value, the records as 12 int32 words each), enqueued on `stream` (the
+        current one by default) without a host wait -> the strip's (value, variance, flags) as views of this history's buffers,
+        valid until the next frame's push."""
+        import torch
+        W, H, ch = self.W, self.H, self.channels
+        x0, x1 = int(x0), W if x1 is None else int(x1)
+        if x0 != self._next_column or not x0 < x1 <= W:
+            raise ValueError(f"a frame's strips are pushed in ascending order: expected a strip from column {self._next_column}")
+        n = (x1 - x0) * H
+        if value.numel() != n * ch or hits.numel() * hits.element_size() != n * 48:
+            raise ValueError(f"columns {x0}:{x1} need {n * ch} values and {n} records")
+        if x0 == 0:
+            self._cam = self._copy_camera(camera)
+        old, new = self._sets[self.frames % 2], self._sets[(self.frames + 1) % 2]
+        first = self.frames == 0
+        prev = [None] * 4 if first else [old[k].data_ptr() for k in ("hits", "value", "moments", "length")]
+        with torch.cuda.device(self._device):
+            stream = torch.cuda.current_stream() if stream is None else stream
+            part = lambda t, words: t[x0 * H * words:x1 * H * words]
+            with torch.cuda.stream(stream):
+                part(new["hits"], 12).copy_(hits.reshape(-1).view(torch.int32))      # next frame's previous records
+            out = [part(new["value"], ch), part(new["moments"], 2), part(new["length"], 1), part(self._variance, 1),
+                   part(self._flags, 1)]
+            capi.check(self._lib.rt_temporal_accumulate_device(
+                self._device, C.byref(self._params), None if first else C.byref(self._cam_prev), C.byref(self._cam), W, H, x0, x1,
+                value.data_ptr(), part(new["hits"], 12).data_ptr(), *prev, *[t.data_ptr() for t in out], stream.cuda_stream))
+        self._next_column = x1
+        if x1 == W:                                                     # the frame is whole: swap the sets
+            self.frames, self._next_column, self._cam_prev = self.frames + 1, 0, self._cam
+        return out[0], out[3], out[4]
+
+    def push(self, rgb, hits, camera, x0=0, x1=None):
+        """Columns [x0, x1) of the next frame, seen by `camera`: rgb float32 (Wn, H) or (Wn, H, 3) by this history's channels,
+        hits HIT_DTYPE (Wn, H) -> (value of rgb's shape, variance float32 (Wn, H), flags bool (Wn, H)), temporal_accumulate()'s
+        bit for bit.  A frame's strips are pushed in ascending order from column 0; the strip that ends at W completes the
+        frame and swaps the two sets."""
+        import torch
+        hits = _frame_records(hits)
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        shape = hits.shape + ((3,) if self.channels == 3 else ())
+        if rgb.shape != shape:
+            raise ValueError(f"rgb must have shape {shape}, not {rgb.shape}")
+        with torch.cuda.device(self._device):
+            d_rgb = torch.tensor(rgb.reshape(-1), device="cuda")
+            d_hits = torch.tensor(hits.reshape(-1).view(np.int32), device="cuda")      # (a copy: the caller's may be read-only)
+            value, variance, flags = self.push_device(d_rgb, d_hits, camera, x0, x1)
+            return (value.cpu().numpy().reshape(shape), variance.cpu().numpy().reshape(hits.shape),
+                    flags.cpu().numpy().reshape(hits.shape).view(np.bool_))
+
+    def state(self):
+        """-> (camera, hits, value, moments, length) of the last whole frame on the host, what temporal_accumulate() takes as prev;
+        None before the first"""
+        if self.frames == 0:
+            return None
+        s, W, H = self._sets[self.frames % 2], self.W, self.H
+        return (self._cam_prev, s["hits"].cpu().numpy().view(HIT_DTYPE).reshape(W, H),
+                s["value"].cpu().numpy().reshape((W, H, 3) if self.channels == 3 else (W, H)),
+                s["moments"].cpu().numpy().reshape(W, H, 2), s["length"].cpu().numpy().reshape(W, H))
+
+
 _TRANSFERS = {"srgb": capi.RT_TRANSFER_SRGB, "linear": capi.RT_TRANSFER_LINEAR, "custom": capi.RT_TRANSFER_CUSTOM}
 
 
@@ -754,6 +895,47 @@ class Renderer:
             capi.check(self._lib.rt_denoise_device(device, C.byref(dn), W, H, term.data_ptr(), records.data_ptr(), clean.data_ptr(),
                                                    scratch.data_ptr(), stream.cuda_stream))
             return torch.add(colours, clean).cpu().numpy()            # the one download
+
+    def render_accumulated(self, cameras, W, H, max_depth, term="indirect", samples=1, **kw):
+        """A sequence of W x H frames, one per camera of `cameras` (RtCameraDesc), accumulated on the GPU where they were made
+        (include/rt_temporal.h): frame k is the G-buffer at max_depth and its term sampled with seed k -- "indirect": the
+        colours plus indirect_diffuse(hits, samples, seed=k, base=rgb); "ao": ambient_occlusion(hits, samples, seed=k), one
+        channel; "direct": the colours themselves after set_shadow_seed(k), for scenes with area lights (the scene's seed is
+        left at the last k) -- pushed into one TemporalHistory with no host wait and no download between the frames.  kw:
+        temporal_params()'s keywords (but channels) for the history, every other one for the term.  -> the last frame's (value,
+        variance, flags), what temporal_accumulate() over the public calls' frames gives bit for bit."""
+        import torch
+        if term not in ("indirect", "ao", "direct"):
+            raise ValueError(f'term must be "indirect", "ao" or "direct", not {term!r}')
+        names = ("match_color", "max_history", "normal_cos", "plane_eps", "alpha", "alpha_moments")
+        history = TemporalHistory(W, H, 1 if term == "ao" else 3, self._device, **{k: kw.pop(k) for k in names if k in kw})
+        cameras = list(cameras)
+        if not cameras:
+            raise ValueError("no cameras")
+        own = self._cam
+        try:
+            with torch.cuda.device(int(self._device)):
+                colours = torch.empty((W * H * 3,), dtype=torch.float32, device="cuda")
+                records = torch.empty((W * H * 12,), dtype=torch.int32, device="cuda")
+                plane = torch.empty((W * H,), dtype=torch.float32, device="cuda") if term == "ao" else None
+                stream = torch.cuda.current_stream()
+                for k, camera in enumerate(cameras):
+                    self._cam = C.pointer(camera)
+                    if term == "direct":
+                        self.set_shadow_seed(k)
+                    self.render_gbuffer_device(W, H, max_depth, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
+                    if term == "indirect":
+                        self.indirect_diffuse_device(W * H, records.data_ptr(), colours.data_ptr(), colours.data_ptr(),
+                                                     stream.cuda_stream, samples=samples, seed=k, **kw)
+                    elif term == "ao":
+                        self.ambient_occlusion_device(W * H, H, records.data_ptr(), plane.data_ptr(), samples=samples, seed=k,
+                                                      stream=stream.cuda_stream, **kw)
+                    value, variance, flags = history.push_device(plane if term == "ao" else colours, records, camera, stream=stream)
+                shape = (W, H) if term == "ao" else (W, H, 3)
+                return (value.cpu().numpy().reshape(shape), variance.cpu().numpy().reshape(W, H),
+                        flags.cpu().numpy().reshape(W, H).view(np.bool_))
+        finally:
+            self._cam = own
 
     STAT_NAMES = ("nearest_rays", "shadow_rays", "wave_nearest_scans", "wave_shadow_scans",
                   "wave_sphere_tests", "wave_plane_tests", "wave_box_tests", "lane_sphere_tests",
