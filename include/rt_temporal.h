@@ -57,8 +57,8 @@
  * the luminance samples the history has seen, not of their mean; it is 0 while len is 1.
  *
  * Not provided: moving objects (records carry no motion), history behind mirrors or glass (the record is the mirror's),
- * supersampled frames (they have no records), several GPUs, the counting build, a spatial variance estimate for short histories,
- * a variance-steered rt_denoise.
+ * supersampled frames (they have no records), several GPUs, the counting build.  The spatial variance estimate for short
+ * histories and the variance-steered filter are include/rt_svgf.h.
  *
  * ERRORS.  Int codes and rt_last_error() as everywhere.  All argument checks come before any device work, RT_ERR_INVALID in this
  * order: params is NULL; channels not 1 or 3; match_color not 0 or 1; max_history outside 1..65535; normal_cos NaN or outside

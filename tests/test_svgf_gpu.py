@@ -1,0 +1,363 @@
+"""The variance-steered filter (include/rt_svgf.h) on the GPU against its definition: rt_svgf_filter and rt_svgf_filter_device
+against svgf_ref bit for bit -- out_value, out_variance and out_estimate -- over rendered sequences accumulated by
+rt_temporal_accumulate, the fixture whose conditions test_svgf_cpu.py counts, rectangles smaller than a tile and than the
+footprint, a frame of more than 1024 x 1024, strips, synthetic records with special values in every input, the device entry point
+behind the G-buffer render and the accumulation on one stream, and the composed calls.  Bar: BIT-EXACT."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import poisoned
+import svgf_ref
+import temporal_ref
+from large_extents import Guarded
+from test_denoise_gpu import soft_renderer
+from test_svgf_cpu import GPU_FIXTURE, GPU_FIXTURE_KW, assert_conditions, counts, fixture
+from test_temporal_cpu import camera_pair
+from test_upsample_gpu import assert_same, random_frame
+from tilecoderaytracer_amd import HostScene, Renderer, TemporalHistory, capi, svgf_filter, temporal_accumulate
+from tilecoderaytracer_amd.host import write_screen_txt
+from tilecoderaytracer_amd.renderer import svgf_params
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("value", "variance", "estimate")
+
+
+def assert_all_same(got, want, what):
+    for g, w, name in zip(got, want, NAMES):
+        if g is not None:
+            assert_same(g, w, f"{what}: {name}")
+
+
+def device_filter(value, hits, moments, length, want, optional=True, **kw):
+    """rt_svgf_filter_device into sentinel-filled outputs and scratch -> the three outputs (variance and estimate None without
+    `optional`); every word of the outputs written, none beside them or the scratch, and no input changed"""
+    import torch
+    channels = 3 if value.ndim == 3 else 1
+    Wn, H = hits.shape
+    params = svgf_params(channels, **kw)
+    what = f"rt_svgf_filter_device {Wn}x{H} channels {channels} {kw}"
+    poisoned.assert_reference_has_no_sentinel(list(want[:3]), what)
+    d_in = [poisoned._on_device(np.ascontiguousarray(a).reshape(-1).view(np.int32)) for a in (value, hits, moments, length)]
+    before = [t.clone() for t in d_in]
+    n = Wn * H
+    specs = [(n * channels, channels), (n, 1), (n, 1)]
+    bufs = [Guarded(words + poisoned.SLACK_CELLS * per) for words, per in specs]
+    lib = capi.load_library()
+    scratch_bytes = int(lib.rt_svgf_scratch_bytes(C.byref(params), Wn, H))
+    assert scratch_bytes > 0 and scratch_bytes % 16 == 0
+    scratch = Guarded(scratch_bytes // 4)
+    out_ptrs = [g.ptr for g in bufs] if optional else [bufs[0].ptr, None, None]
+    capi.check(lib.rt_svgf_filter_device(0, C.byref(params), Wn, H, *[t.data_ptr() for t in d_in], *out_ptrs, scratch.ptr,
+                                         poisoned._stream()))
+    torch.cuda.synchronize()
+    for t, b in zip(d_in, before):
+        assert torch.equal(t, b), f"{what}: an input was written"
+    assert scratch.guards_untouched(), f"{what}: a word beside the scratch was written"
+    out = []
+    for k, (g, (words, per)) in enumerate(zip(bufs, specs)):
+        host = g.all.cpu().numpy()
+        if k >= 1 and not optional:
+            assert g.sentinels_left() == g.n and g.guards_untouched()
+            out.append(None)
+            continue
+        body = poisoned.check_output(host[:g.guard], host[g.guard:g.guard + g.n], host[g.guard + g.n:], words,
+                                     poisoned.layout(per, H), f"{what}, {NAMES[k]}")
+        out.append(body.copy().view(F).reshape((Wn, H, 3) if per == 3 else (Wn, H)))
+    return tuple(out)
+
+
+def both_ways(value, hits, moments, length, what, device=True, **kw):
+    """the host call and (device) the device entry point against the reference -> the reference's outputs"""
+    want = svgf_ref.svgf(value, hits, moments, length, **kw)
+    assert_all_same(svgf_filter(value, hits, moments, length, **kw), want, f"{what} {kw}")
+    if device:
+        assert_all_same(device_filter(value, hits, moments, length, want, **kw), want, f"{what} {kw}, device")
+    return want
+
+
+def made_up_inputs(seed, Wn, H, channels, max_len=6.0):
+    """values, moments and lengths as an accumulation leaves them: positive, m2 >= m1^2 mostly, lengths 1..max_len"""
+    rng = np.random.default_rng(seed)
+    value = rng.random((Wn, H, 3) if channels == 3 else (Wn, H), dtype=F) + F(0.01)
+    m1 = rng.random((Wn, H), dtype=F) + F(0.01)
+    moments = np.stack([m1, m1 * m1 + (rng.random((Wn, H), dtype=F) - F(0.2)) * F(0.05)], axis=-1).astype(F)
+    length = np.floor(F(1.0) + rng.random((Wn, H), dtype=F) * F(max_len)).astype(F)
+    return value, moments, length
+
+
+# every value of every parameter, and every iteration count
+COMBOS = [dict(iterations=1, match_color=True, sigma_l=2.0, sigma_plane=0.0, min_history=1, spatial_radius=1, normal_squarings=3),
+          dict(iterations=2, match_color=False, sigma_l=0.0, sigma_plane=0.05, min_history=2, spatial_radius=2, normal_squarings=0),
+          dict(iterations=3, match_color=True, sigma_l=2.0, sigma_plane=0.05, min_history=4, spatial_radius=3, normal_squarings=3),
+          dict(iterations=4, match_color=False, sigma_l=2.0, sigma_plane=0.0, min_history=2, spatial_radius=3, normal_squarings=0),
+          dict(iterations=5, match_color=True, sigma_l=0.0, sigma_plane=0.0, min_history=4, spatial_radius=1, normal_squarings=0),
+          dict(iterations=5, match_color=False, sigma_l=2.0, sigma_plane=0.05, min_history=1, spatial_radius=2, normal_squarings=3)]
+
+
+# ---- 1. rendered sequences -----------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def rendered_sequence(name, W, H, frames, pair):
+    """`frames` one-sample soft-shadow frames of the scene, shadow seeds 0.., accumulated by rt_temporal_accumulate; pair "truck":
+    the first frame from the pair's previous camera (the built-in scene) -> {channels: (value, hits, moments, length)}"""
+    r = soft_renderer(name)
+    own = r._cam
+    cams = [own] * frames
+    if pair == "truck":
+        cam_prev, cam = camera_pair("truck")
+        cams = [C.pointer(cam_prev)] + [C.pointer(cam)] * (frames - 1)
+    state = {1: None, 3: None}
+    try:
+        for k, cam in enumerate(cams):
+            r._cam = cam
+            r.set_shadow_seed(k)
+            rgb, hits = r.render_gbuffer(W, H, 3)
+            for channels in (1, 3):
+                cur = rgb if channels == 3 else np.ascontiguousarray(temporal_ref.lum(rgb))
+                value, moments, length, _, _ = temporal_accumulate(cur, hits, cam, state[channels], max_history=32)
+                state[channels] = (cam, hits, value, moments, length)
+    finally:
+        r._cam = own
+    return {c: (s[2], s[1], s[3], s[4]) for c, s in state.items()}
+
+
+@pytest.mark.parametrize("size", [(61, 37), (96, 80)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("name, frames, pair", [("builtin", 2, "truck"), ("builtin", 4, "equal"), ("field", 3, "equal"),
+                                                ("image", 2, "equal")])
+def test_rendered_sequences_are_the_reference_bit_for_bit(name, frames, pair, size):
+    W, H = size
+    seq = rendered_sequence(name, W, H, frames, pair)
+    changed = spatial = 0
+    for k, kw in enumerate(COMBOS):
+        for channels in (1, 3):
+            value, hits, moments, length = seq[channels]
+            want = both_ways(value, hits, moments, length, f"{name} {W}x{H} {frames} frames", device=(k + channels) % 3 == 0, **kw)
+            changed += int((want[0] != value).any())
+            spatial += int((length < kw["min_history"]).any())
+    assert changed == 2 * len(COMBOS) and (length.max() == frames) and spatial >= (4 if pair == "truck" or frames < 4 else 0)
+    assert (hits["object"] >= 0).mean() > 0.3
+
+
+@pytest.mark.parametrize("channels", [3, 1])
+def test_the_counted_fixture_is_the_reference_bit_for_bit(channels):
+    """the fixture whose conditions test_svgf_cpu.py counts: both estimate paths, taps a key rejects, taps the luminance term
+    drops, dead pixels"""
+    name, W, H, frames = GPU_FIXTURE
+    value, hits, moments, length = fixture(name, W, H, frames, channels)
+    assert_conditions(counts(value, hits, moments, length, **dict(GPU_FIXTURE_KW, iterations=1)), "the fixture")
+    for iterations in range(1, 6):
+        both_ways(value, hits, moments, length, "fixture", **dict(GPU_FIXTURE_KW, iterations=iterations))
+    both_ways(value, hits, moments, length, "fixture", **dict(GPU_FIXTURE_KW, sigma_plane=0.05, match_color=False, spatial_radius=3))
+
+
+# ---- 2. small and awkward rectangles ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("W, H", [(1, 1), (1, 300), (300, 1), (5, 5), (2, 67), (67, 3), (65, 129)])
+def test_sizes_smaller_than_a_tile_and_the_footprint(W, H):
+    hits = random_frame(W * 1000 + H, W, H)
+    for iterations in range(1, 6):
+        for sigma_l in (0.0, 2.0):
+            channels = 3 if (iterations + (sigma_l > 0)) % 2 else 1
+            value, moments, length = made_up_inputs(iterations, W, H, channels)
+            both_ways(value, hits, moments, length, f"{W}x{H}", device=iterations in (1, 5), iterations=iterations, sigma_l=sigma_l,
+                      min_history=4, spatial_radius=1 + iterations % 3, sigma_plane=0.4 * (iterations % 2), match_color=False,
+                      normal_squarings=1)
+
+
+# ---- 3. one larger frame -----------------------------------------------------------------------------------------------------------------
+
+def test_a_frame_of_more_than_1024_squared():
+    W, H = 1100, 1030
+    hits = random_frame(21, W, H)
+    value, moments, length = made_up_inputs(22, W, H, 3)
+    want = both_ways(value, hits, moments, length, "1100x1030", device=False, iterations=2, sigma_l=2.0, min_history=3,
+                     spatial_radius=1, match_color=False, normal_squarings=1)
+    assert (want[0] != value).mean() > 0.3 and (length < 3).mean() > 0.2
+
+
+# ---- 4. strips ---------------------------------------------------------------------------------------------------------------------------
+
+def test_a_strip_differs_from_the_frame_only_within_its_reach():
+    """the header: within spatial_radius + 2 * (2^iterations - 1) columns of the strip's edges, and nowhere else"""
+    value, hits, moments, length = rendered_sequence("builtin", 96, 80, 2, "truck")[3]
+    x0, x1 = 20, 80
+    part = lambda a: np.ascontiguousarray(a[x0:x1])
+    for iterations, radius in ((1, 3), (3, 1)):
+        kw = dict(iterations=iterations, sigma_l=2.0, min_history=4, spatial_radius=radius)
+        full = svgf_filter(value, hits, moments, length, **kw)
+        strip = both_ways(part(value), part(hits), part(moments), part(length), "strip", device=False, **kw)
+        m = radius + 2 * (2 ** iterations - 1)
+        for s, f, what in zip(strip, full, NAMES):
+            assert_same(s[m:x1 - x0 - m], f[x0 + m:x1 - m], f"strip, {iterations} iterations: {what}")
+        assert not svgf_ref.same_bits(strip[0][:m], full[0][x0:x0 + m])
+        assert not svgf_ref.same_bits(strip[0][-m:], full[0][x1 - m:x1])
+
+
+# ---- 5. synthetic records and special values ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("seed", range(20))
+def test_synthetic_records_and_special_values(seed):
+    rng = np.random.default_rng(2000 + seed)
+    Wn, H = int(rng.integers(1, 100)), int(rng.integers(1, 100))
+    channels = 3 if seed % 2 else 1
+    special = np.array([np.nan, np.inf, -np.inf, 1e-40, -1e-45, -0.0, 0.0, 3e38, -3e38, 1e-38], dtype=F)
+    hits = random_frame(3000 + seed, Wn, H)
+    value, moments, length = made_up_inputs(4000 + seed, Wn, H, channels)
+
+    def sprinkle(a, share, values=special):
+        flat = a.reshape(-1)
+        pick = rng.random(flat.shape) < share
+        flat[pick] = rng.choice(values, int(pick.sum()))
+
+    sprinkle(value, 0.03)
+    sprinkle(moments, 0.03)
+    sprinkle(length, 0.06, np.array([0.0, 0.25, 0.999, np.nan, np.inf, -1.0, -0.0, 1e-40], dtype=F))
+    for field in ("normal", "point", "color"):
+        a = hits[field].copy()
+        sprinkle(a, 0.01)
+        hits[field] = a
+    if Wn > 8 and H > 8:
+        hits["object"][2:6, 3:8] = -1                              # dead blocks
+        hits["flags"][Wn - 4:, H - 3:] |= 2
+    kw = dict(iterations=1 + seed % 5, sigma_l=(0.0, 2.0, 0.5)[seed % 3], sigma_plane=(0.0, 0.3)[seed % 2], min_history=1 + seed % 4,
+              spatial_radius=1 + seed % 3, match_color=bool(seed % 4 < 2), normal_squarings=seed % 7, epsilon=(1e-8, 1e-3)[seed % 2])
+    want = both_ways(value, hits, moments, length, f"seed {seed} {Wn}x{H}", **kw)
+    dead = svgf_ref.dead_records(hits)
+    assert_same(want[0][dead], value[dead], "dead pixels pass through")
+
+
+# ---- 6. the device path on one stream ------------------------------------------------------------------------------------------------------
+
+def test_device_entry_follows_the_render_and_the_accumulation_on_one_stream():
+    """rt_render_gbuffer_device, rt_temporal_accumulate_device and rt_svgf_filter_device enqueued back to back, no host wait
+    between them; outputs and scratch between sentinel-filled guards; the optional outputs NULL in a second call"""
+    import torch
+    W, H, depth = 70, 45, 3
+    r = soft_renderer("builtin")
+    n = W * H
+    lib = capi.load_library()
+    kw = dict(iterations=3, sigma_l=2.0, min_history=4, spatial_radius=2)
+    params = svgf_params(3, **kw)
+    history = TemporalHistory(W, H, 3, max_history=8)
+    colours = torch.empty((n * 3,), dtype=torch.float32, device="cuda")
+    records = torch.empty((n * 12,), dtype=torch.int32, device="cuda")
+    outs = [Guarded(n * 3 + poisoned.SLACK_CELLS * 3), Guarded(n + poisoned.SLACK_CELLS), Guarded(n + poisoned.SLACK_CELLS)]
+    scratch = Guarded(int(lib.rt_svgf_scratch_bytes(C.byref(params), W, H)) // 4)
+    plain = Guarded(n * 3)
+    stream = torch.cuda.current_stream()
+    for k in range(3):
+        r.set_shadow_seed(k)
+        r.render_gbuffer_device(W, H, depth, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
+        history.push_device(colours, records, r._cam, stream=stream)
+    s = history._sets[history.frames % 2]
+    ptrs = [s[k].data_ptr() for k in ("value", "hits", "moments", "length")]
+    capi.check(lib.rt_svgf_filter_device(0, C.byref(params), W, H, *ptrs, outs[0].ptr, outs[1].ptr, outs[2].ptr, scratch.ptr,
+                                         stream.cuda_stream))
+    kept = [s[k].clone() for k in ("value", "hits", "moments", "length")]
+    capi.check(lib.rt_svgf_filter_device(0, C.byref(params), W, H, *ptrs, plain.ptr, None, None, scratch.ptr, stream.cuda_stream))
+    torch.cuda.synchronize()
+    cam, hits, value, moments, length = history.state()
+    for t, name in zip(kept, ("value", "hits", "moments", "length")):
+        assert torch.equal(t, s[name]), f"the history's {name} was written"
+    want = svgf_ref.svgf(value, hits, moments, length, **kw)
+    poisoned.assert_reference_has_no_sentinel(list(want), "the device path")
+    got = []
+    for g, per, name in zip(outs, (3, 1, 1), NAMES):
+        host = g.all.cpu().numpy()
+        body = poisoned.check_output(host[:g.guard], host[g.guard:g.guard + g.n], host[g.guard + g.n:], n * per,
+                                     poisoned.layout(per, H), f"device path, {name}")
+        got.append(body.copy().view(F).reshape((W, H, 3) if per == 3 else (W, H)))
+    assert_all_same(got, want, "device path")
+    assert scratch.guards_untouched() and plain.guards_untouched() and plain.sentinels_left() == 0
+    assert_same(plain.body.cpu().numpy().view(F).reshape(W, H, 3), want[0], "device path without the optional outputs")
+    assert (want[0] != value).mean() > 0.2 and (want[1] > 0).sum() > 100
+    # refusals launch nothing
+    for bad_ptrs, word in (((ptrs[0], ptrs[1] + 8, ptrs[2], ptrs[3], outs[0].ptr), "16-byte"),
+                           ((ptrs[0] + 2, ptrs[1], ptrs[2], ptrs[3], outs[0].ptr), "4-byte"),
+                           ((ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[0]), "overlap")):
+        rc = lib.rt_svgf_filter_device(0, C.byref(params), W, H, *bad_ptrs, None, None, scratch.ptr, stream.cuda_stream)
+        assert rc == capi.RT_ERR_INVALID and word in lib.rt_last_error().decode(), word
+    rc = lib.rt_svgf_filter_device(99, C.byref(params), W, H, *ptrs, outs[0].ptr, None, None, scratch.ptr, stream.cuda_stream)
+    assert rc == capi.RT_ERR_INVALID and "device index" in lib.rt_last_error().decode()
+
+
+# ---- 7. the composed calls ---------------------------------------------------------------------------------------------------------------
+
+def test_history_filter_device_and_render_accumulated_equal_the_public_calls():
+    W, H, depth = 45, 38, 3
+    r = Renderer(HostScene.builtin())
+    cam_prev, cam = camera_pair("truck")
+    cams = [cam_prev, cam, cam]
+    tkw = dict(max_history=3, plane_eps=0.02)
+    fkw = dict(iterations=3, sigma_l=2.0, min_history=3, spatial_radius=2)
+    for term, term_kw in (("indirect", dict(gather_depth=1, gain=1.25)), ("ao", dict(radius=2.0))):
+        state, own = None, r._cam
+        history = TemporalHistory(W, H, 1 if term == "ao" else 3, **tkw)
+        with pytest.raises(ValueError):
+            history.filter_device(**fkw)                        # no frame yet
+        for k, c in enumerate(cams):
+            r._cam = C.pointer(c)
+            rgb, hits = r.render_gbuffer(W, H, depth)
+            cur = r.indirect_diffuse(hits, 1, seed=k, base=rgb, **term_kw) if term == "indirect" else \
+                r.ambient_occlusion(hits, 1, seed=k, **term_kw)
+            value, moments, length, variance, flags = temporal_accumulate(cur, hits, c, state, **tkw)
+            state = (c, hits, value, moments, length)
+            history.push(cur, hits, c)
+        r._cam = own
+        want = svgf_filter(value, hits, moments, length, **fkw)
+        assert_all_same(want, svgf_ref.svgf(value, hits, moments, length, **fkw), f"{term}: svgf_filter")
+        got = history.filter_device(**fkw)
+        shape = (W, H) if term == "ao" else (W, H, 3)
+        assert_same(got[0].cpu().numpy().reshape(shape), want[0], f"{term}: filter_device value")
+        assert_same(got[1].cpu().numpy().reshape(W, H), want[1], f"{term}: filter_device variance")
+        kept = history.state()
+        assert_same(kept[2], value, "the history is untouched")
+        assert_same(kept[3], moments, "the history is untouched")
+        got = r.render_accumulated(cams, W, H, depth, term=term, samples=1, filter=fkw, **tkw, **term_kw)
+        assert_same(got[0], want[0], f"{term}: render_accumulated value")
+        assert_same(got[1], want[1], f"{term}: render_accumulated variance")
+        assert_same(got[2], flags, f"{term}: render_accumulated flags")
+        unfiltered = r.render_accumulated(cams, W, H, depth, term=term, samples=1, **tkw, **term_kw)
+        assert_same(unfiltered[0], value, f"{term}: filter=None is the accumulated frame")
+        assert (want[0] != value).mean() > 0.2
+    with pytest.raises(capi.RtError):
+        history.filter_device(iterations=9)
+    r.close()
+
+
+def test_raytracer_svgf_writes_the_filter_of_its_own_accumulated_frame(tmp_path):
+    exe = os.path.join(ROOT, "tilecoderaytracer_amd", "bin", "tcrt_raytracer")
+    W, H, depth, K = 64, 48, 3, 3
+    common = [exe, "--width", str(W), "--height", str(H), "--depth", str(depth), "--soft", "0:1:1.0", "--accumulate", str(K)]
+    plain_txt, out_txt, want_txt = (tmp_path / n for n in ("plain.txt", "out.txt", "want.txt"))
+    p = subprocess.run(common + ["--out", str(plain_txt)], cwd=tmp_path, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, (p.returncode, p.stdout[-500:], p.stderr[-500:])
+    p = subprocess.run(common + ["--out", str(out_txt), "--svgf", "2:1.5:4"], cwd=tmp_path, capture_output=True, text=True,
+                       timeout=120)
+    assert p.returncode == 0 and "Variance-steered filter" in p.stdout, (p.returncode, p.stdout[-500:], p.stderr[-500:])
+    # the same frames through the library (the .txt rounds the colours, so they are made here and checked against the .txt)
+    host = HostScene.builtin()
+    host.set_area_light(0, 1, 1.0)
+    r = Renderer(host)
+    state = None
+    for k in range(K):
+        r.set_shadow_seed(k)
+        rgb, hits = r.render_gbuffer(W, H, depth)
+        value, moments, length, _, _ = temporal_accumulate(rgb, hits, r._cam, state, max_history=K, normal_cos=0.9, plane_eps=0.05)
+        state = (r._cam, hits, value, moments, length)
+    lines = lambda path: path.read_text().splitlines()[10:]
+    write_screen_txt(str(want_txt), value)
+    assert lines(plain_txt) == lines(want_txt)
+    want = svgf_filter(value, hits, moments, length, iterations=2, sigma_l=1.5, min_history=4, spatial_radius=3, normal_squarings=3,
+                       match_color=True, sigma_plane=0.0, epsilon=1e-8)[0]
+    write_screen_txt(str(want_txt), want)
+    assert len(lines(out_txt)) == W * H and lines(out_txt) == lines(want_txt) and lines(out_txt) != lines(plain_txt)
+    r.close()

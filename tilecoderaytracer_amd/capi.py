@@ -72,6 +72,15 @@ class RtTemporalParams(C.Structure):
                 ("plane_eps", C.c_float), ("alpha", C.c_float), ("alpha_moments", C.c_float)]
 
 
+class RtSvgfParams(C.Structure):
+    """include/rt_svgf.h: channels (1 or 3), iterations (1..5), normal squarings (0..6), match_color (0 / 1), the history length
+    below which the variance is estimated spatially (1..65535), that estimate's radius (1..3), the luminance term's sigma (0:
+    none), the plane term's (0: none) and the epsilon added to sigma_l^2 * variance (> 0)."""
+    _fields_ = [("channels", C.c_int32), ("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("match_color", C.c_int32),
+                ("min_history", C.c_int32), ("spatial_radius", C.c_int32), ("sigma_l", C.c_float), ("sigma_plane", C.c_float),
+                ("epsilon", C.c_float)]
+
+
 class RtAoParams(C.Structure):
     """include/rt_capi_ao.h: n (n x n directions per record, 1..8), the radius a direction is followed for, the seed, the first
     record's key, channels (1, or 3 equal ones)."""
@@ -368,6 +377,14 @@ def load_library():
         lib.rt_temporal_accumulate.argtypes = head + [C.POINTER(C.c_double)]
         lib.rt_temporal_accumulate_device.argtypes = head + [vp]
         lib.rt_temporal_accumulate.restype = lib.rt_temporal_accumulate_device.restype = i
+    # include/rt_svgf.h (likewise absent from older builds)
+    if hasattr(lib, "rt_svgf_filter"):
+        lib.rt_capi_svgf_version.restype = i
+        lib.rt_svgf_filter.argtypes = [i, C.POINTER(RtSvgfParams), i, i] + [vp] * 7 + [C.POINTER(C.c_double)]
+        lib.rt_svgf_filter_device.argtypes = [i, C.POINTER(RtSvgfParams), i, i] + [vp] * 9
+        lib.rt_svgf_filter.restype = lib.rt_svgf_filter_device.restype = i
+        lib.rt_svgf_scratch_bytes.argtypes = [C.POINTER(RtSvgfParams), i, i]
+        lib.rt_svgf_scratch_bytes.restype = C.c_uint64
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):
         lib.rt_capi_launch_version.restype = i

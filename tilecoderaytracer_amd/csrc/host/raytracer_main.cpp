@@ -50,6 +50,11 @@
  *                       both blend weights at least ALPHA, 0..1, default 0: the running mean); the last accumulated frame (and
  *                       occlusion plane) is what the writers get.  One GPU, with at least one of those terms, without --ssaa,
  *                       --adaptive or --lens
+ *   --svgf IT[:SIGMA_L[:MIN_HISTORY]]  with --accumulate: the last accumulated frame (and occlusion plane) goes through the
+ *                       variance-steered filter before it is written (rt_svgf_filter, include/rt_svgf.h): IT iterations (1..5),
+ *                       luminance sigma SIGMA_L (>= 0, default 2), spatial variance estimate below MIN_HISTORY frames (1..65535,
+ *                       default 4) over a radius of 3; 3 normal squarings, the albedo matched, no plane term, epsilon 1e-8.  One
+ *                       GPU, no supersampling
  */
 #include <chrono>
 #include <cmath>
@@ -70,6 +75,7 @@
 #include "../../../include/rt_capi_lens.h"
 #include "../../../include/rt_capi_soft.h"
 #include "../../../include/rt_capi_ssaa.h"
+#include "../../../include/rt_svgf.h"
 #include "../../../include/rt_temporal.h"
 #include "../../../include/rt_capi_upsample.h"
 #include "celio_model.hpp"
@@ -90,7 +96,8 @@ static int usage(const char *argv0) {
                  "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n"
                  "          [--ao N[:RADIUS] --ao-ppm FILE] [--adaptive 1|2|4[:COLOR[:COS]] [--adaptive-mask FILE]]\n"
                  "          [--lens N[:APERTURE[:FOCUS[:SEED]]]] [--indirect N[:DEPTH[:GAIN[:SEED]]]]\n"
-                 "          [--gather-scale S[:SIGMA_PLANE[:refine]]] [--accumulate K[:ALPHA]]\n", argv0);
+                 "          [--gather-scale S[:SIGMA_PLANE[:refine]]] [--accumulate K[:ALPHA]]\n"
+                 "          [--svgf IT[:SIGMA_L[:MIN_HISTORY]]]\n", argv0);
     return 1;
 }
 
@@ -106,6 +113,8 @@ int main(int argc, char **argv) {
     bool has_gather = false;
     std::string accumulate_arg;                  /* --accumulate K[:ALPHA] (include/rt_temporal.h) */
     bool has_accumulate = false;
+    std::string svgf_arg;                        /* --svgf IT[:SIGMA_L[:MIN_HISTORY]] (include/rt_svgf.h) */
+    bool has_svgf = false;
     std::string denoise;                         /* --denoise IT[:SIGMA[:K]] (include/rt_capi_denoise.h) */
     std::vector<std::string> soft;               /* --soft I:N[:R]: light I an area light, N x N samples, radius R (include/rt_capi_soft.h) */
     for (int i = 1; i < argc; ++i) {
@@ -132,6 +141,7 @@ int main(int argc, char **argv) {
         else if (a == "--indirect" && i + 1 < argc) indirect_arg = argv[++i];
         else if (a == "--gather-scale" && i + 1 < argc) gather_arg = argv[++i], has_gather = true;
         else if (a == "--accumulate" && i + 1 < argc) accumulate_arg = argv[++i], has_accumulate = true;
+        else if (a == "--svgf" && i + 1 < argc) svgf_arg = argv[++i], has_svgf = true;
         else if (a == "--no-txt") write_txt = false;
         else return usage(argv[0]);
     }
@@ -286,6 +296,17 @@ int main(int argc, char **argv) {
         }
         if (soft.empty() && ao_arg.empty() && indirect_arg.empty()) return usage(argv[0]);
         if (gpus > 1 || ssaa > 1 || !adaptive_arg.empty() || !lens_arg.empty()) return usage(argv[0]);
+    }
+    rt_svgf_params sv = {3, 0, 3, 1, 4, 3, 2.0f, 0.0f, 1e-8f};       /* iterations: IT, 0 without --svgf */
+    if (has_svgf) {
+        /* IT, IT:SIGMA_L or IT:SIGMA_L:MIN_HISTORY, and nothing else, refused as --denoise refuses its string */
+        char tail = 0;
+        const int got = std::sscanf(svgf_arg.c_str(), "%d:%f:%d%c", &sv.iterations, &sv.sigma_l, &sv.min_history, &tail);
+        if (got < 1 || got > 3 || (got == 1 && svgf_arg.find(':') != std::string::npos)) return usage(argv[0]);
+        if (sv.iterations < 1 || sv.iterations > 5 || sv.min_history < 1 || sv.min_history > 65535 || !(sv.sigma_l >= 0.0f) ||
+            std::isinf(sv.sigma_l))
+            return usage(argv[0]);
+        if (!has_accumulate || gpus > 1 || ssaa > 1) return usage(argv[0]);   /* (it filters a history; one GPU, records needed) */
     }
     const int frames = has_accumulate ? tp.max_history : 1;
     /* a term gathered for the cells of the frame's records and upsampled onto `base` (or alone) into out, 3 channels: gather(n,
@@ -500,6 +521,21 @@ int main(int argc, char **argv) {
             for (float v : frame_history.variance) mean += v;
             std::printf("Temporal accumulation      : %d frame(s), seeds 0..%d, alpha %g: kernels %f ms, mean luminance variance %g\n", frames,
                         frames - 1, (double)tp.alpha, accumulate_ms, mean / ((double)W * (double)H));
+        }
+        if (rc == RT_OK && sv.iterations > 0) {
+            /* the last accumulated frame, and the occlusion plane's, through the variance-steered filter */
+            const int to = (frames - 1) & 1;
+            double svgf_ms = 0.0, ms = 0.0;
+            rc = rt_svgf_filter(0, &sv, W, H, pixels.data(), hits.data(), frame_history.moments[to].data(),
+                                frame_history.length[to].data(), pixels.data(), nullptr, nullptr, &svgf_ms);
+            if (rc == RT_OK && !ao_arg.empty()) {
+                rc = rt_svgf_filter(0, &sv, W, H, ao_plane.data(), hits.data(), ao_history.moments[to].data(),
+                                    ao_history.length[to].data(), ao_plane.data(), nullptr, nullptr, &ms);
+                svgf_ms += ms;
+            }
+            if (rc == RT_OK)
+                std::printf("Variance-steered filter    : %f ms  (%d iteration(s), sigma_l %g, spatial estimate below %d frame(s))\n",
+                            svgf_ms, sv.iterations, (double)sv.sigma_l, sv.min_history);
         }
         if (rc == RT_OK && !denoise.empty()) {
             double denoise_ms = 0.0;

@@ -245,6 +245,7 @@ class TemporalHistory:
             self._sets = [dict(hits=new(n * 12, torch.int32), value=new(n * self.channels, torch.float32),
                                moments=new(n * 2, torch.float32), length=new(n, torch.float32)) for _ in range(2)]
             self._variance, self._flags = new(n, torch.float32), new(n, torch.uint8)
+        self._filtered = self._scratch = None                          # filter_device()'s outputs and scratch, made on first use
         self.reset()
 
     def reset(self):
@@ -306,6 +307,32 @@ class TemporalHistory:
             return (value.cpu().numpy().reshape(shape), variance.cpu().numpy().reshape(hits.shape),
                     flags.cpu().numpy().reshape(hits.shape).view(np.bool_))
 
+    def filter_device(self, stream=None, **params):
+        """The last completed frame through the variance-steered filter (include/rt_svgf.h, rt_svgf_filter_device), read from
+        this history's own buffers and enqueued on `stream` (the current one by default) without a host wait -> the filtered
+        (value, variance) as tensors this history owns, valid until the next filter_device().  params: svgf_params()'s keywords
+        but channels.  The history itself is left untouched: the next push blends into the unfiltered frame."""
+        import torch
+        if self.frames == 0:
+            raise ValueError("no completed frame to filter")
+        pr = svgf_params(self.channels, **params)
+        W, H, n = self.W, self.H, self.W * self.H
+        need = int(self._lib.rt_svgf_scratch_bytes(C.byref(pr), W, H))
+        s = self._sets[self.frames % 2]
+        with torch.cuda.device(self._device):
+            stream = torch.cuda.current_stream() if stream is None else stream
+            if self._filtered is None:
+                self._filtered = (torch.empty((n * self.channels,), dtype=torch.float32, device="cuda"),
+                                  torch.empty((n,), dtype=torch.float32, device="cuda"))
+            if need and (self._scratch is None or self._scratch.numel() < need):
+                self._scratch = torch.empty((need,), dtype=torch.uint8, device="cuda")
+            scratch = self._scratch.data_ptr() if need else None       # (refused arguments: the call itself says why)
+            capi.check(self._lib.rt_svgf_filter_device(self._device, C.byref(pr), W, H, s["value"].data_ptr(), s["hits"].data_ptr(),
+                                                       s["moments"].data_ptr(), s["length"].data_ptr(),
+                                                       self._filtered[0].data_ptr(), self._filtered[1].data_ptr(), None, scratch,
+                                                       stream.cuda_stream))
+        return self._filtered
+
     def state(self):
         """-> (camera, hits, value, moments, length) of the last whole frame on the host, what temporal_accumulate() takes as prev;
         None before the first"""
@@ -315,6 +342,38 @@ class TemporalHistory:
         return (self._cam_prev, s["hits"].cpu().numpy().view(HIT_DTYPE).reshape(W, H),
                 s["value"].cpu().numpy().reshape((W, H, 3) if self.channels == 3 else (W, H)),
                 s["moments"].cpu().numpy().reshape(W, H, 2), s["length"].cpu().numpy().reshape(W, H))
+
+
+def svgf_params(channels=3, iterations=4, sigma_l=2.0, min_history=4, spatial_radius=3, normal_squarings=3, match_color=True,
+                sigma_plane=0.0, epsilon=1e-8):
+    """svgf_filter's keywords -> an RtSvgfParams (include/rt_svgf.h); the library checks the values."""
+    return capi.RtSvgfParams(int(channels), int(iterations), int(normal_squarings), int(match_color), int(min_history),
+                             int(spatial_radius), float(sigma_l), float(sigma_plane), float(epsilon))
+
+
+def svgf_filter(value, hits, moments, length, device=0, **params):
+    """The variance-steered filter over an accumulated frame (include/rt_svgf.h, rt_svgf_filter): value float32 (Wn, H) -- one
+    channel -- or (Wn, H, 3), hits HIT_DTYPE (Wn, H), moments float32 (Wn, H, 2) and length float32 (Wn, H), as
+    temporal_accumulate() returns them (a whole frame or a strip) -> (the filtered value of value's shape, its variance float32
+    (Wn, H), the variance estimate the first iteration read, float32 (Wn, H)).  params: svgf_params()'s keywords but channels,
+    which value's shape gives.  Runs on GPU `device`; there is no CPU path."""
+    hits = _frame_records(hits)
+    value = np.ascontiguousarray(value, dtype=np.float32)
+    moments = np.ascontiguousarray(moments, dtype=np.float32)
+    length = np.ascontiguousarray(length, dtype=np.float32)
+    channels = 3 if value.ndim == 3 else 1
+    Wn, H = hits.shape
+    if value.shape != hits.shape + ((3,) if channels == 3 else ()):
+        raise ValueError(f"value must be {hits.shape} or {hits.shape + (3,)}, not {value.shape}")
+    if moments.shape != (Wn, H, 2) or length.shape != (Wn, H):
+        raise ValueError(f"moments must be {(Wn, H, 2)} and length {(Wn, H)}, not {moments.shape} and {length.shape}")
+    pr = svgf_params(channels, **params)
+    out = np.empty(value.shape, dtype=np.float32)
+    variance, estimate = np.empty((Wn, H), dtype=np.float32), np.empty((Wn, H), dtype=np.float32)
+    capi.check(capi.load_library().rt_svgf_filter(int(device), C.byref(pr), Wn, H, value.ctypes.data, hits.ctypes.data,
+                                                  moments.ctypes.data, length.ctypes.data, out.ctypes.data, variance.ctypes.data,
+                                                  estimate.ctypes.data, None))
+    return out, variance, estimate
 
 
 _TRANSFERS = {"srgb": capi.RT_TRANSFER_SRGB, "linear": capi.RT_TRANSFER_LINEAR, "custom": capi.RT_TRANSFER_CUSTOM}
@@ -896,14 +955,16 @@ class Renderer:
                                                    scratch.data_ptr(), stream.cuda_stream))
             return torch.add(colours, clean).cpu().numpy()            # the one download
 
-    def render_accumulated(self, cameras, W, H, max_depth, term="indirect", samples=1, **kw):
+    def render_accumulated(self, cameras, W, H, max_depth, term="indirect", samples=1, filter=None, **kw):
         """A sequence of W x H frames, one per camera of `cameras` (RtCameraDesc), accumulated on the GPU where they were made
         (include/rt_temporal.h): frame k is the G-buffer at max_depth and its term sampled with seed k -- "indirect": the
         colours plus indirect_diffuse(hits, samples, seed=k, base=rgb); "ao": ambient_occlusion(hits, samples, seed=k), one
         channel; "direct": the colours themselves after set_shadow_seed(k), for scenes with area lights (the scene's seed is
         left at the last k) -- pushed into one TemporalHistory with no host wait and no download between the frames.  kw:
         temporal_params()'s keywords (but channels) for the history, every other one for the term.  -> the last frame's (value,
-        variance, flags), what temporal_accumulate() over the public calls' frames gives bit for bit."""
+        variance, flags), what temporal_accumulate() over the public calls' frames gives bit for bit.  filter: None, or a dict of
+        svgf_params()'s keywords (but channels): the last frame goes through the variance-steered filter on the same stream
+        (include/rt_svgf.h) and value and variance are the filtered ones, svgf_filter()'s of that frame bit for bit."""
         import torch
         if term not in ("indirect", "ao", "direct"):
             raise ValueError(f'term must be "indirect", "ao" or "direct", not {term!r}')
@@ -931,6 +992,8 @@ class Renderer:
                         self.ambient_occlusion_device(W * H, H, records.data_ptr(), plane.data_ptr(), samples=samples, seed=k,
                                                       stream=stream.cuda_stream, **kw)
                     value, variance, flags = history.push_device(plane if term == "ao" else colours, records, camera, stream=stream)
+                if filter is not None:
+                    value, variance = history.filter_device(stream=stream, **filter)
                 shape = (W, H) if term == "ao" else (W, H, 3)
                 return (value.cpu().numpy().reshape(shape), variance.cpu().numpy().reshape(W, H),
                         flags.cpu().numpy().reshape(W, H).view(np.bool_))
