@@ -286,6 +286,23 @@ def test_product_does_not_reference_the_oracle():
         assert b"orc_render" not in blob and b"liboracle" not in blob
 
 
+def test_the_units_share_one_copy_of_their_host_plumbing():
+    """One copy per rule (csrc/rt_host.h): the device question is asked by rt_capi.hip (rt_internal_check_device) and, for its own
+    handles, by rt_multi.hip, and by nobody else; HIP_TRY is defined by the shared header and by rt_capi.hip, which owns the error
+    text; and no unit but rt_capi.hip declares rt_internal_set_error itself instead of including the header.  A new unit that
+    starts as a copy of another fails here."""
+    csrc = os.path.join(ROOT, "tilecoderaytracer_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    assert {"rt_capi.hip", "rt_multi.hip", "rt_host.h", "rt_internal.h"} <= set(texts)
+    asks = [f for f, t in texts.items() if "no HIP device (this library has no CPU path)" in t]
+    assert asks == ["rt_capi.hip", "rt_multi.hip"], asks
+    defines = [f for f, t in texts.items() if re.search(r"#\s*define\s+HIP_TRY\b", t)]
+    assert defines == ["rt_capi.hip", "rt_host.h"], defines
+    declares = [f for f, t in texts.items() if f.endswith(".hip") and f != "rt_capi.hip"
+                and re.search(r"\bint\s+rt_internal_set_error\s*\(", t)]
+    assert not declares, declares
+
+
 def test_build_keeps_the_arithmetic_contract_flags():
     """Parity depends on how the kernel is compiled: no FMA
     contraction, correctly rounded fp32 divide/sqrt, denormals kept, never fast-math."""

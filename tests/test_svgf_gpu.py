@@ -172,6 +172,24 @@ def test_sizes_smaller_than_a_tile_and_the_footprint(W, H):
                       normal_squarings=1)
 
 
+def test_the_host_call_without_its_optional_outputs():
+    """rt_svgf_filter with out_variance and out_estimate NULL and kernel_ms given: out_value is the reference's bit for bit.
+    5 x 67: one whole 64-lane tile and 3 lanes of the next along z, and columns that fill neither a workgroup's four wavefronts
+    nor a column group."""
+    Wn, H = 5, 67
+    hits = random_frame(5067, Wn, H)
+    value, moments, length = made_up_inputs(67, Wn, H, 3)
+    kw = dict(iterations=2, sigma_l=2.0, min_history=4, spatial_radius=2, sigma_plane=0.4, match_color=False, normal_squarings=1)
+    want = svgf_ref.svgf(value, hits, moments, length, **kw)
+    assert (want[0] != value).mean() > 0.3 and (length < 4).any()  # filtered pixels, and pixels that take the spatial estimate
+    params = svgf_params(3, **kw)
+    out, ms = np.empty(value.shape, dtype=F), C.c_double(-1.0)
+    capi.check(capi.load_library().rt_svgf_filter(0, C.byref(params), Wn, H, value.ctypes.data, hits.ctypes.data,
+                                                  moments.ctypes.data, length.ctypes.data, out.ctypes.data, None, None, C.byref(ms)))
+    assert_same(out, want[0], "host call without variance and estimate")
+    assert ms.value > 0.0
+
+
 # ---- 3. one larger frame -----------------------------------------------------------------------------------------------------------------
 
 def test_a_frame_of_more_than_1024_squared():

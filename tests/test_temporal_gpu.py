@@ -215,6 +215,32 @@ def test_made_up_records_under_a_moved_camera():
         assert (~want[4]).sum() >= 300 and want[4][live].sum() >= 300, (kw, int((~want[4]).sum()), int(want[4][live].sum()))
 
 
+def test_the_host_call_without_variance_and_flags():
+    """rt_temporal_accumulate with out_variance and out_flags NULL and kernel_ms given: the three outputs it has left are the
+    reference's word for word.  5 x 67: one whole 64-lane tile and 3 lanes of the next along z, and columns that fill neither a
+    workgroup's four wavefronts nor a column group."""
+    Wn, H = 5, 67
+    hits, prev_hits = random_frame(21, Wn, H), random_frame(21, Wn, H)
+    changed = np.random.default_rng(22).random((Wn, H)) < 0.3
+    prev_hits[changed] = random_frame(23, Wn, H)[changed]
+    centre = np.array([Wn * 0.125, 0.0, H * 0.125])
+    cam = cameras.camera(centre + [0.0, -12.0, 0.0], centre, up=(0.0, 0.0, 1.0), screen=(1.5, 1.5))
+    cam_prev = cameras.camera(centre + [0.4, -12.0, -0.3], centre + [0.2, 0.0, 0.1], up=(0.0, 0.0, 1.0), screen=(1.5, 1.5), roll=0.05)
+    cur = np.random.default_rng(24).random((Wn, H, 3), dtype=F)
+    value, moments, length = made_up_history(25, Wn, H, 3)
+    kw = dict(normal_cos=0.3, plane_eps=0.5)
+    want = temporal_ref.accumulate(cur, hits, cam, (cam_prev, prev_hits, value, moments, length), **kw)
+    assert (~want[4]).sum() >= 20 and want[4].sum() >= 20           # pixels with a history and pixels without
+    params = temporal_params(3, **kw)
+    got = [np.empty((Wn, H, 3), dtype=F), np.empty((Wn, H, 2), dtype=F), np.empty((Wn, H), dtype=F)]
+    ms = C.c_double(-1.0)
+    capi.check(capi.load_library().rt_temporal_accumulate(
+        0, C.byref(params), C.byref(cam_prev), C.byref(cam), Wn, H, 0, Wn, cur.ctypes.data, hits.ctypes.data, prev_hits.ctypes.data,
+        value.ctypes.data, moments.ctypes.data, length.ctypes.data, *[a.ctypes.data for a in got], None, None, C.byref(ms)))
+    assert_all_same(got, want[:3], "host call without variance and flags")
+    assert ms.value > 0.0
+
+
 # ---- 2. the history object and the accumulated render ------------------------------------------------------------------------------
 
 def test_temporal_history_push_over_four_frames_equals_four_host_calls():

@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "../../include/rt_capi_adaptive.h"
-#include "rt_internal.h"
+#include "rt_host.h"
 
 #pragma clang fp contract(off)
 
@@ -56,16 +56,6 @@ static_assert((kResolveSamples / 16) * (3 * 16 + 1) <= (kResolveSamples / 4) * (
 constexpr long long kMaxRectPixels = 533333333;        /* rt_render_gbuffer's limit: 3.2e10 bytes of colours and records */
 constexpr size_t kChunkBytes = (size_t)256 << 20;      /* the default chunk: its rays and sample colours within 256 MiB */
 constexpr int kMaxChunk = 1 << 26;                     /* pixels a launch at most: 2^30 rays with k = 4 */
-
-int fail(int code, const std::string &msg) { return rt_internal_set_error(code, msg.c_str()); }
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorNoDevice ? RT_ERR_NO_DEVICE : RT_ERR_HIP,               \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
 
 /* the camera as createEyeRay reads it */
 struct Cam { float so[3], ch[3], cv[3], eye[3], sw, sh, shw, shh; };
@@ -273,26 +263,26 @@ __global__ __launch_bounds__(kBlock) void rt_adaptive_resolve_kernel(const uint3
     }
 }
 
-/* the handle's scratch, which only grows, and the last call's bookkeeping */
-struct RtAdaptiveState {
-    struct Buffer { void *p = nullptr; size_t bytes = 0; };
-    Buffer first_rgb, first_hits, flags, counts, list, rays, samples, out_rgb, out_flags;   /* (out_*: the host variant's outputs) */
-    uint32_t *d_total = nullptr, *h_total = nullptr;     /* the number of flagged pixels: on the device, and pinned */
-    /* events of the last call: start, first pass done, flags and list done; second pass begun, then per chunk traced, resolved */
-    std::vector<hipEvent_t> events;
-    int n_events = 0;
-    bool collected = true;
-    uint64_t seq = 0;                                     /* the handle's launch number at the call's end */
-    rt_adaptive_info info{};
-};
-
-/* the unit's place in the handle (rt_internal.h): how its state is freed, and its last call's stage times */
-extern "C" void rt_internal_adaptive_free(RtAdaptiveState *a);
-extern "C" double rt_internal_adaptive_ms(RtAdaptiveState *a, uint64_t seq);
+/* the unit's place in the handle (rt_internal.h): how its state is freed, and its last call's stage times (named symbols: the
+ * host-side program scripts/asan_adaptive_host.hip calls them) */
+extern "C" void rt_internal_adaptive_free(void *state);
+extern "C" double rt_internal_adaptive_ms(void *state, uint64_t seq);
 
 namespace {
 
-int grow(RtAdaptiveState::Buffer &b, size_t need) { return rt_internal_grow(&b.p, &b.bytes, need); }
+/* the handle's scratch, which only grows, and the last call's bookkeeping */
+struct RtAdaptiveState {
+    Buffer first_rgb, first_hits, flags, counts, list, rays, samples, out_rgb, out_flags;   /* (out_*: the host variant's outputs) */
+    uint32_t *d_total = nullptr, *h_total = nullptr;     /* the number of flagged pixels: on the device, and pinned */
+    /* the last call's start, first pass done, flags and list done; second pass begun, then per chunk traced, resolved */
+    StageClock clock;
+    rt_adaptive_info info{};
+    ~RtAdaptiveState() {
+        clock.release();
+        if (d_total) (void)hipFree(d_total);
+        if (h_total) (void)hipHostFree(h_total);
+    }
+};
 
 /* the header's checks of the params, in its order */
 int check_params(const rt_adaptive_params *pr) {
@@ -304,14 +294,6 @@ int check_params(const rt_adaptive_params *pr) {
     if (!(pr->color_threshold >= 0.0f) || std::isinf(pr->color_threshold))
         return fail(RT_ERR_INVALID, "color_threshold must be finite and >= 0");
     if (!(pr->normal_cos >= -1.0f && pr->normal_cos <= 1.0f)) return fail(RT_ERR_INVALID, "normal_cos must be in [-1, 1]");
-    return RT_OK;
-}
-
-int check_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "device index out of range");
     return RT_OK;
 }
 
@@ -350,40 +332,21 @@ long long chunk_size(const rt_adaptive_params &pr) {
 }
 
 RtAdaptiveState *state_of(rt_scene *s) {
-    rt_internal_unit *slot = rt_internal_unit_slot(s, RT_INTERNAL_UNIT_ADAPTIVE);
-    if (!slot->state) {
-        slot->state = new RtAdaptiveState();
-        slot->free_state = [](void *a) { rt_internal_adaptive_free(static_cast<RtAdaptiveState *>(a)); };
-        slot->stage_ms = [](void *a, uint64_t seq) { return rt_internal_adaptive_ms(static_cast<RtAdaptiveState *>(a), seq); };
-    }
-    return static_cast<RtAdaptiveState *>(slot->state);
-}
-
-/* event number i of the call, recorded on stream */
-int mark(RtAdaptiveState *a, hipStream_t stream) {
-    if ((size_t)a->n_events == a->events.size()) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        a->events.push_back(e);
-    }
-    HIP_TRY(hipEventRecord(a->events[a->n_events], stream));
-    a->n_events += 1;
-    return RT_OK;
+    return unit_state<RtAdaptiveState>(s, RT_INTERNAL_UNIT_ADAPTIVE, rt_internal_adaptive_free, rt_internal_adaptive_ms);
 }
 
 /* the last call's stage times from its events, once */
 int collect(RtAdaptiveState *a) {
-    if (a->collected) return RT_OK;
-    if (a->n_events > 0) HIP_TRY(hipEventSynchronize(a->events[a->n_events - 1]));
+    if (a->clock.collected) return RT_OK;
+    std::vector<float> t;
+    const int rc = a->clock.intervals(&t);
+    if (rc) return rc;
     double ms[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = 0; i + 1 < a->n_events; ++i) {
+    for (size_t i = 0; i < t.size(); ++i) {
         if (i == 2) continue;                           /* (flags done -> second pass begun: the host's wait) */
-        float t = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&t, a->events[i], a->events[i + 1]));
-        ms[i < 2 ? i : 2 + ((i - 3) & 1)] += t;
+        ms[i < 2 ? i : 2 + ((i - 3) & 1)] += t[i];
     }
     a->info.first_pass_ms = ms[0], a->info.flag_ms = ms[1], a->info.trace_ms = ms[2], a->info.resolve_ms = ms[3];
-    a->collected = true;
     return RT_OK;
 }
 
@@ -415,25 +378,25 @@ int run(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, in
     HIP_TRY(hipSetDevice(rt_internal_scene_device(s)));
     const bool direct = RT_ADAPTIVE_DIRECT_FIRST != 0 && Wh == Wn;        /* no halo: the first pass's colours go where they stay */
     int rc = collect(a);                                  /* (the events are about to be recorded again) */
-    if (rc == RT_OK && !direct) rc = grow(a->first_rgb, nh * 12);
-    if (rc == RT_OK) rc = grow(a->first_hits, nh * sizeof(rt_hit));
-    if (rc == RT_OK) rc = grow(a->flags, n);
+    if (rc == RT_OK && !direct) rc = a->first_rgb.grow(nh * 12);
+    if (rc == RT_OK) rc = a->first_hits.grow(nh * sizeof(rt_hit));
+    if (rc == RT_OK) rc = a->flags.grow(n);
     const unsigned n_groups = (n_blocks + kScanBlock - 1) / kScanBlock;
-    if (rc == RT_OK) rc = grow(a->counts, ((size_t)n_blocks + n_groups) * 8);      /* counts, offsets, the groups' sums and bases */
-    if (rc == RT_OK) rc = grow(a->list, n * 4);
+    if (rc == RT_OK) rc = a->counts.grow(((size_t)n_blocks + n_groups) * 8);      /* counts, offsets, the groups' sums and bases */
+    if (rc == RT_OK) rc = a->list.grow(n * 4);
     if (rc) return rc;
     if (!a->d_total) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a->d_total), 4));
     if (!a->h_total) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&a->h_total), 4, hipHostMallocDefault));
-    a->n_events = 0;
+    a->clock.n_events = 0;
     a->info = rt_adaptive_info{};
     a->info.pixels = (int64_t)n;
 
     /* the first pass: into scratch, from where the flag kernel, which reads the colours anyway, copies the strip's to the
      * output -- or, without a halo column, straight into the output */
     void *first_rgb = direct ? d_out_rgb : a->first_rgb.p;
-    if ((rc = mark(a, stream))) return rc;
+    if ((rc = a->clock.mark(stream))) return rc;
     rc = rt_internal_launch_gbuffer(s, cam, W, H, x0, x1h, max_depth, first_rgb, a->first_hits.p, stream);
-    if (rc == RT_OK) rc = mark(a, stream);
+    if (rc == RT_OK) rc = a->clock.mark(stream);
     if (rc) return rc;
     uint32_t *counts = static_cast<uint32_t *>(a->counts.p), *offsets = counts + n_blocks;
     uint32_t *group_sums = offsets + n_blocks, *group_base = group_sums + n_groups;
@@ -453,16 +416,16 @@ int run(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, in
                            static_cast<const uint8_t *>(a->flags.p), offsets, group_base, list, (uint32_t)n);
         HIP_TRY(hipGetLastError());
     }
-    if ((rc = mark(a, stream))) return rc;
+    if ((rc = a->clock.mark(stream))) return rc;
     HIP_TRY(hipStreamSynchronize(stream));                /* THE call's one synchronisation: how many pixels the second pass has */
     const uint32_t flagged = *a->h_total;
     a->info.flagged = (int64_t)flagged;
     if (pr.samples > 1 && flagged > 0) {
         const long long chunk = chunk_size(pr);
         const size_t most = (size_t)std::min<long long>(chunk, flagged);
-        rc = grow(a->rays, most * (size_t)kk * 24);
-        if (rc == RT_OK) rc = grow(a->samples, most * (size_t)kk * 12);
-        if (rc == RT_OK) rc = mark(a, stream);
+        rc = a->rays.grow(most * (size_t)kk * 24);
+        if (rc == RT_OK) rc = a->samples.grow(most * (size_t)kk * 12);
+        if (rc == RT_OK) rc = a->clock.mark(stream);
         if (rc) return rc;
         Cam c;
         for (int k = 0; k < 3; ++k) {
@@ -478,49 +441,31 @@ int run(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, in
             HIP_TRY(hipGetLastError());
             rc = rt_internal_launch_rays(s, n_rays, RT_ADAPTIVE_ROWS > 0 ? RT_ADAPTIVE_ROWS : n_rays, a->rays.p, max_depth,
                                          a->samples.p, stream);
-            if (rc == RT_OK) rc = mark(a, stream);
+            if (rc == RT_OK) rc = a->clock.mark(stream);
             if (rc) return rc;
             hipLaunchKernelGGL(rt_adaptive_resolve_kernel, dim3((m + kResolveSamples / kk - 1) / (kResolveSamples / kk)), dim3(kBlock), 0, stream,
                                list + g0, m, kk,
                                static_cast<const float *>(a->samples.p), static_cast<float *>(d_out_rgb));
             HIP_TRY(hipGetLastError());
-            if ((rc = mark(a, stream))) return rc;
+            if ((rc = a->clock.mark(stream))) return rc;
             a->info.chunks += 1;
             a->info.rays += (int64_t)n_rays;
         }
     }
-    a->collected = false;
-    a->seq = rt_internal_launch_seq(s);
+    a->clock.collected = false;
+    a->clock.seq = rt_internal_launch_seq(s);
     return RT_OK;
 }
-
-struct Unlock {
-    rt_scene *s;
-    ~Unlock() { rt_internal_unlock(s); }
-};
-
-struct DeviceBuffers {       /* rt_adaptive_flags' allocations, freed on every way out */
-    void *rgb = nullptr, *hits = nullptr, *flags = nullptr;
-    ~DeviceBuffers() { (void)hipFree(rgb), (void)hipFree(hits), (void)hipFree(flags); }
-};
 
 } // namespace
 
 extern "C" {
 
-void rt_internal_adaptive_free(RtAdaptiveState *a) {
-    if (!a) return;
-    for (hipEvent_t e : a->events) (void)hipEventDestroy(e);
-    for (RtAdaptiveState::Buffer *b : {&a->first_rgb, &a->first_hits, &a->flags, &a->counts, &a->list, &a->rays, &a->samples,
-                                       &a->out_rgb, &a->out_flags})
-        if (b->p) (void)hipFree(b->p);
-    if (a->d_total) (void)hipFree(a->d_total);
-    if (a->h_total) (void)hipHostFree(a->h_total);
-    delete a;
-}
+void rt_internal_adaptive_free(void *state) { delete static_cast<RtAdaptiveState *>(state); }
 
-double rt_internal_adaptive_ms(RtAdaptiveState *a, uint64_t seq) {
-    if (!a || a->seq != seq || a->n_events == 0 || collect(a) != RT_OK) return -1.0;
+double rt_internal_adaptive_ms(void *state, uint64_t seq) {
+    RtAdaptiveState *a = static_cast<RtAdaptiveState *>(state);
+    if (!a || a->clock.seq != seq || a->clock.n_events == 0 || collect(a) != RT_OK) return -1.0;
     return a->info.first_pass_ms + a->info.flag_ms + a->info.trace_ms + a->info.resolve_ms;
 }
 
@@ -529,25 +474,20 @@ int rt_capi_adaptive_version(void) { return RT_CAPI_ADAPTIVE_VERSION; }
 int rt_adaptive_flags(int device, const rt_adaptive_params *pr, int Wn, int H, const float *rgb, const rt_hit *hits,
                       uint8_t *out_flags) {
     int rc = check_flags_args(pr, Wn, H, rgb, hits, out_flags, false);
-    if (rc == RT_OK) rc = check_device(device);
+    if (rc == RT_OK) rc = rt_internal_check_device(device);
     if (rc) return rc;
     const size_t pixels = (size_t)Wn * (size_t)H;
-    DeviceBuffers d;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(&d.rgb, pixels * 12));
-    HIP_TRY(hipMalloc(&d.hits, pixels * sizeof(rt_hit)));
-    HIP_TRY(hipMalloc(&d.flags, pixels));
-    HIP_TRY(hipMemcpy(d.rgb, rgb, pixels * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.hits, hits, pixels * sizeof(rt_hit), hipMemcpyHostToDevice));
-    if ((rc = enqueue_flags(*pr, Wn, Wn, H, d.rgb, d.hits, d.flags, nullptr, nullptr, nullptr, nullptr))) return rc;
-    HIP_TRY(hipMemcpy(out_flags, d.flags, pixels, hipMemcpyDeviceToHost));
-    return RT_OK;
+    const HostIn in[2] = {{rgb, pixels * 12}, {hits, pixels * sizeof(rt_hit)}};
+    const HostOut out[1] = {{out_flags, pixels}};
+    return staged_call(device, in, 2, out, 1, 0, nullptr, [&](void *const *d_in, void *const *d_out, void *) {
+        return enqueue_flags(*pr, Wn, Wn, H, d_in[0], d_in[1], d_out[0], nullptr, nullptr, nullptr, nullptr);
+    });
 }
 
 int rt_adaptive_flags_device(int device, const rt_adaptive_params *pr, int Wn, int H, const void *d_rgb, const void *d_hits,
                              void *d_out_flags, void *hip_stream) {
     int rc = check_flags_args(pr, Wn, H, d_rgb, d_hits, d_out_flags, true);
-    if (rc == RT_OK) rc = check_device(device);
+    if (rc == RT_OK) rc = rt_internal_check_device(device);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(device));
     return enqueue_flags(*pr, Wn, Wn, H, d_rgb, d_hits, d_out_flags, nullptr, nullptr, nullptr, static_cast<hipStream_t>(hip_stream));
@@ -573,8 +513,8 @@ int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, int W, int H, int
     RtAdaptiveState *a = state_of(s);
     const size_t n = (size_t)(x1 - x0) * (size_t)H;
     HIP_TRY(hipSetDevice(rt_internal_scene_device(s)));
-    rc = grow(a->out_rgb, n * 12);
-    if (rc == RT_OK && out_flags) rc = grow(a->out_flags, n);
+    rc = a->out_rgb.grow(n * 12);
+    if (rc == RT_OK && out_flags) rc = a->out_flags.grow(n);
     if (rc == RT_OK) rc = run(s, cam, W, H, x0, x1, max_depth, p, a->out_rgb.p, out_flags ? a->out_flags.p : nullptr, nullptr);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(out_rgb, a->out_rgb.p, n * 12, hipMemcpyDeviceToHost));

@@ -1003,13 +1003,9 @@ int upload_texels(rt_scene *s) {
  * tables packed again with its address), the tables' upload, the error word */
 int finish_create(rt_scene *s, int device, rt_scene **out) {
     s->device = device;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        delete s;
-        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-    }
-    if (device < 0 || device >= ndev) { delete s; return fail(RT_ERR_INVALID, "device index out of range"); }
-    int rc = s->images_used ? upload_texels(s) : RT_OK;
+    int rc = rt_internal_check_device(device);
+    if (rc) { delete s; return rc; }                     /* (the handle owns nothing on a device yet) */
+    rc = s->images_used ? upload_texels(s) : RT_OK;
     if (rc == RT_OK && s->images_used) rc = pack_scene(s);
     if (rc == RT_OK) rc = upload_scene(s);
     if (rc) { rt_scene_destroy(s); return rc; }
@@ -1939,8 +1935,16 @@ int check_counting(const rt_scene *s, const char *so) {
 
 extern "C" {
 
-/* used by rt_multi.hip to report through rt_last_error() */
+/* how every other unit reports through rt_last_error() */
 int rt_internal_set_error(int code, const char *msg) { return fail(code, msg ? msg : ""); }
+
+int rt_internal_check_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "device index out of range");
+    return RT_OK;
+}
 
 /* ---- rt_internal.h: the handle, the argument rules and the launches, for rt_adaptive.hip and rt_lens.hip ---- */
 int rt_internal_check_strip(const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth, const void *out_rgb) {

@@ -18,8 +18,7 @@
 #include <string>
 
 #include "../../include/rt_capi_denoise.h"
-
-extern "C" int rt_internal_set_error(int code, const char *msg);      /* rt_capi.hip: the text behind rt_last_error() */
+#include "rt_host.h"
 
 static_assert(sizeof(rt_hit) == 48, "rt_hit layout");
 static_assert(sizeof(rt_denoise_params) == 12, "rt_denoise_params layout");
@@ -29,16 +28,6 @@ namespace {
 constexpr int kTileZ = 64, kTileX = 4;                 /* a workgroup: 4 wavefronts, each 64 consecutive z */
 constexpr int kPixels = 8;                             /* the columns, one step apart, a wavefront filters together */
 constexpr double kMaxPixels = 2.0e9 * 4.0 * 4.0 / 60.0; /* rt_render_gbuffer's limit: 3.2e10 bytes of colours and records */
-
-int fail(int code, const std::string &msg) { return rt_internal_set_error(code, msg.c_str()); }
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorNoDevice ? RT_ERR_NO_DEVICE : RT_ERR_HIP,               \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
 
 } // namespace
 
@@ -162,8 +151,6 @@ __global__ __launch_bounds__(kTileZ *kTileX) void rt_denoise_atrous_kernel(const
 
 namespace {
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 /* the header's checks up to the buffers, in its order */
 int check_shape(const rt_denoise_params *pr, int Wn, int H) {
     if (!pr) return fail(RT_ERR_INVALID, "params is NULL");
@@ -173,14 +160,6 @@ int check_shape(const rt_denoise_params *pr, int Wn, int H) {
         return fail(RT_ERR_INVALID, "sigma_color must be finite and >= 0");
     if (Wn <= 0 || H <= 0) return fail(RT_ERR_INVALID, "need Wn, H > 0");
     if ((double)Wn * (double)H > kMaxPixels) return fail(RT_ERR_INVALID, "rectangle too large for its colours and records");
-    return RT_OK;
-}
-
-int check_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "device index out of range");
     return RT_OK;
 }
 
@@ -234,16 +213,6 @@ int enqueue(const rt_denoise_params *pr, int Wn, int H, const void *d_rgb, const
     return RT_OK;
 }
 
-struct DeviceBuffers {       /* rt_denoise's allocations, freed on every way out */
-    void *rgb = nullptr, *hits = nullptr, *out = nullptr, *scratch = nullptr;
-    hipEvent_t start = nullptr, stop = nullptr;
-    ~DeviceBuffers() {
-        if (start) (void)hipEventDestroy(start);
-        if (stop) (void)hipEventDestroy(stop);
-        (void)hipFree(rgb), (void)hipFree(hits), (void)hipFree(out), (void)hipFree(scratch);
-    }
-};
-
 } // namespace
 
 extern "C" {
@@ -260,29 +229,14 @@ int rt_denoise(int device, const rt_denoise_params *pr, int Wn, int H, const flo
     int rc = check_shape(pr, Wn, H);
     if (rc) return rc;
     if (!rgb || !hits || !out_rgb) return fail(RT_ERR_INVALID, "rgb / hits / out_rgb is NULL");
-    if ((rc = check_device(device))) return rc;
+    if ((rc = rt_internal_check_device(device))) return rc;
     const size_t pixels = (size_t)Wn * (size_t)H;
-    DeviceBuffers d;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(&d.rgb, pixels * 12));
-    HIP_TRY(hipMalloc(&d.hits, pixels * sizeof(rt_hit)));
-    HIP_TRY(hipMalloc(&d.out, pixels * 12));
-    HIP_TRY(hipMalloc(&d.scratch, scratch_bytes(pr, pixels)));
-    HIP_TRY(hipEventCreate(&d.start));
-    HIP_TRY(hipEventCreate(&d.stop));
-    HIP_TRY(hipMemcpy(d.rgb, rgb, pixels * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.hits, hits, pixels * sizeof(rt_hit), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventRecord(d.start, nullptr));
-    if ((rc = enqueue(pr, Wn, H, d.rgb, d.hits, d.out, d.scratch, nullptr))) return rc;
-    HIP_TRY(hipEventRecord(d.stop, nullptr));
-    HIP_TRY(hipEventSynchronize(d.stop));
-    HIP_TRY(hipMemcpy(out_rgb, d.out, pixels * 12, hipMemcpyDeviceToHost));
-    if (kernel_ms) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, d.start, d.stop));
-        *kernel_ms = ms;
-    }
-    return RT_OK;
+    const HostIn in[2] = {{rgb, pixels * 12}, {hits, pixels * sizeof(rt_hit)}};
+    const HostOut out[1] = {{out_rgb, pixels * 12}};
+    return staged_call(device, in, 2, out, 1, scratch_bytes(pr, pixels), kernel_ms,
+                       [&](void *const *d_in, void *const *d_out, void *d_scratch) {
+                           return enqueue(pr, Wn, H, d_in[0], d_in[1], d_out[0], d_scratch, nullptr);
+                       });
 }
 
 int rt_denoise_device(int device, const rt_denoise_params *pr, int Wn, int H, const void *d_rgb, const void *d_hits,
@@ -296,9 +250,8 @@ int rt_denoise_device(int device, const rt_denoise_params *pr, int Wn, int H, co
     if (((uintptr_t)d_rgb & 3u) != 0 || ((uintptr_t)d_out_rgb & 3u) != 0)
         return fail(RT_ERR_INVALID, "d_rgb and d_out_rgb must be 4-byte aligned");
     const size_t bytes = (size_t)Wn * (size_t)H * 12;
-    const uintptr_t a = (uintptr_t)d_rgb, b = (uintptr_t)d_out_rgb;
-    if (a < b + bytes && b < a + bytes) return fail(RT_ERR_INVALID, "d_out_rgb overlaps d_rgb");
-    if ((rc = check_device(device))) return rc;
+    if (overlap(d_rgb, bytes, d_out_rgb, bytes)) return fail(RT_ERR_INVALID, "d_out_rgb overlaps d_rgb");
+    if ((rc = rt_internal_check_device(device))) return rc;
     HIP_TRY(hipSetDevice(device));
     return enqueue(pr, Wn, H, d_rgb, d_hits, d_out_rgb, d_scratch, static_cast<hipStream_t>(hip_stream));
 }

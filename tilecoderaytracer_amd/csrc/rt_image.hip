@@ -21,8 +21,7 @@
 
 #include "../../include/rt_capi.h"
 #include "../../include/rt_capi_image.h"
-
-extern "C" int rt_internal_set_error(int code, const char *msg);      /* rt_capi.hip: the text behind rt_last_error() */
+#include "rt_host.h"
 
 static_assert(sizeof(rt_image_params) == 24, "rt_image_params layout");
 static_assert(offsetof(rt_image_params, exposure) == 12 && offsetof(rt_image_params, thresholds) == 16, "rt_image_params layout");
@@ -79,16 +78,6 @@ const float kSrgb[255] = {
     0x1.c0401ap-1f, 0x1.c47d1ep-1f, 0x1.c8c018p-1f, 0x1.cd090ap-1f, 0x1.d157f6p-1f, 0x1.d5ace0p-1f, 0x1.da07c8p-1f, 0x1.de68b4p-1f,
     0x1.e2cfa2p-1f, 0x1.e73c98p-1f, 0x1.ebaf98p-1f, 0x1.f028a2p-1f, 0x1.f4a7bap-1f, 0x1.f92ce2p-1f, 0x1.fdb81cp-1f
 };
-
-int fail(int code, const std::string &msg) { return rt_internal_set_error(code, msg.c_str()); }
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorNoDevice ? RT_ERR_NO_DEVICE : RT_ERR_HIP,               \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
 
 } // namespace
 
@@ -208,14 +197,6 @@ int check_shape(const rt_image_params *p, int Wn, int H, uint64_t pitch, SearchT
     return RT_OK;
 }
 
-int check_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "device index out of range");
-    return RT_OK;
-}
-
 /* the one launch, enqueued on stream; every argument already checked, the device current */
 int enqueue(const rt_image_params *p, const SearchTree &tab, int Wn, int H, const void *d_rgb, void *d_out, uint64_t pitch,
             hipStream_t stream) {
@@ -231,16 +212,6 @@ int enqueue(const rt_image_params *p, const SearchTree &tab, int Wn, int H, cons
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
-
-struct DeviceBuffers {       /* rt_encode_image's allocations, freed on every way out */
-    void *rgb = nullptr, *out = nullptr;
-    hipEvent_t start = nullptr, stop = nullptr;
-    ~DeviceBuffers() {
-        if (start) (void)hipEventDestroy(start);
-        if (stop) (void)hipEventDestroy(stop);
-        (void)hipFree(rgb), (void)hipFree(out);
-    }
-};
 
 } // namespace
 
@@ -263,32 +234,15 @@ int rt_encode_image(int device, const rt_image_params *p, int Wn, int H, const f
     int rc = check_shape(p, Wn, H, pitch_bytes, &tab);
     if (rc) return rc;
     if (!rgb || !out) return fail(RT_ERR_INVALID, "rgb / out is NULL");
-    if ((rc = check_device(device))) return rc;
+    if ((rc = rt_internal_check_device(device))) return rc;
     /* on the device the rows are dense; the caller's pitch is applied by the copy back, row by row, so that the bytes between
      * its rows are never written */
-    const size_t in_bytes = (size_t)Wn * (size_t)H * 12, row_bytes = (size_t)Wn * (size_t)p->channels;
-    DeviceBuffers d;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(&d.rgb, in_bytes));
-    HIP_TRY(hipMalloc(&d.out, row_bytes * (size_t)H));
-    HIP_TRY(hipEventCreate(&d.start));
-    HIP_TRY(hipEventCreate(&d.stop));
-    HIP_TRY(hipMemcpy(d.rgb, rgb, in_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipEventRecord(d.start, nullptr));
-    if ((rc = enqueue(p, tab, Wn, H, d.rgb, d.out, row_bytes, nullptr))) return rc;
-    HIP_TRY(hipEventRecord(d.stop, nullptr));
-    HIP_TRY(hipEventSynchronize(d.stop));
-    if (pitch_bytes == row_bytes) {
-        HIP_TRY(hipMemcpy(out, d.out, row_bytes * (size_t)H, hipMemcpyDeviceToHost));
-    } else {
-        HIP_TRY(hipMemcpy2D(out, pitch_bytes, d.out, row_bytes, row_bytes, (size_t)H, hipMemcpyDeviceToHost));
-    }
-    if (kernel_ms) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, d.start, d.stop));
-        *kernel_ms = ms;
-    }
-    return RT_OK;
+    const size_t row_bytes = (size_t)Wn * (size_t)p->channels;
+    const HostIn in[1] = {{rgb, (size_t)Wn * (size_t)H * 12}};
+    const HostOut outs[1] = {{out, row_bytes * (size_t)H, row_bytes, (size_t)pitch_bytes}};
+    return staged_call(device, in, 1, outs, 1, 0, kernel_ms, [&](void *const *d_in, void *const *d_out, void *) {
+        return enqueue(p, tab, Wn, H, d_in[0], d_out[0], row_bytes, nullptr);
+    });
 }
 
 int rt_encode_image_device(int device, const rt_image_params *p, int Wn, int H, const void *d_rgb, void *d_out,
@@ -301,9 +255,8 @@ int rt_encode_image_device(int device, const rt_image_params *p, int Wn, int H, 
     if (p->channels == 4 && ((uintptr_t)d_out & 3u) != 0) return fail(RT_ERR_INVALID, "d_out must be 4-byte aligned with 4 channels");
     const uint64_t in_bytes = (uint64_t)Wn * (uint64_t)H * 12;
     const uint64_t out_bytes = (uint64_t)(H - 1) * pitch_bytes + (uint64_t)Wn * (uint64_t)p->channels;
-    const uintptr_t a = (uintptr_t)d_rgb, b = (uintptr_t)d_out;
-    if (a < b + out_bytes && b < a + in_bytes) return fail(RT_ERR_INVALID, "d_out overlaps d_rgb");
-    if ((rc = check_device(device))) return rc;
+    if (overlap(d_rgb, in_bytes, d_out, out_bytes)) return fail(RT_ERR_INVALID, "d_out overlaps d_rgb");
+    if ((rc = rt_internal_check_device(device))) return rc;
     HIP_TRY(hipSetDevice(device));
     return enqueue(p, tab, Wn, H, d_rgb, d_out, pitch_bytes, static_cast<hipStream_t>(hip_stream));
 }

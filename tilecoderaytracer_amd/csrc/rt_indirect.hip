@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "../../include/rt_capi_indirect.h"
-#include "rt_internal.h"
+#include "rt_host.h"
 
 #pragma clang fp contract(off)
 
@@ -51,16 +51,6 @@ constexpr int lds_floats() {
     return most;
 }
 static_assert(lds_floats() * 4 <= 16384, "resolve: LDS");
-
-int fail(int code, const std::string &msg) { return rt_internal_set_error(code, msg.c_str()); }
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorNoDevice ? RT_ERR_NO_DEVICE : RT_ERR_HIP,               \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
 
 } // namespace
 
@@ -185,22 +175,18 @@ __global__ __launch_bounds__(kBlock) void rt_indirect_resolve_kernel(uint32_t m,
     }
 }
 
-/* the handle's scratch, which only grows, and the last call's bookkeeping */
-struct RtIndirectState {
-    struct Buffer { void *p = nullptr; size_t bytes = 0; };
-    Buffer rays, samples, gather;                          /* a chunk's rays, their colours, their records (emitters == 0) */
-    Buffer hits, out_rgb;                                  /* the host variant's records and its base / output */
-    /* events of the last call: its start, then per chunk rays generated, traced, (emitters == 0: queried,) resolved */
-    std::vector<hipEvent_t> events;
-    int n_events = 0, stages = 3;
-    bool collected = true;
-    uint64_t seq = 0;                                     /* the handle's launch number at the call's end */
-    rt_indirect_info info{};
-};
-
 namespace {
 
-int grow(RtIndirectState::Buffer &b, size_t need) { return rt_internal_grow(&b.p, &b.bytes, need); }
+/* the handle's scratch, which only grows, and the last call's bookkeeping */
+struct RtIndirectState {
+    Buffer rays, samples, gather;                          /* a chunk's rays, their colours, their records (emitters == 0) */
+    Buffer hits, out_rgb;                                  /* the host variant's records and its base / output */
+    /* the last call's start, then per chunk rays generated, traced, (emitters == 0: queried,) resolved */
+    StageClock clock;
+    int stages = 3;
+    rt_indirect_info info{};
+    ~RtIndirectState() { clock.release(); }
+};
 
 unsigned blocks_of(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
@@ -217,14 +203,6 @@ int check_params(const rt_indirect_params *pr, int n, const void *hits, const vo
     if (n < 0) return fail(RT_ERR_INVALID, "n < 0");
     if (n > 0 && !hits) return fail(RT_ERR_INVALID, "hits pointer is NULL");
     if (n > 0 && !out) return fail(RT_ERR_INVALID, "output pointer is NULL");
-    return RT_OK;
-}
-
-int check_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "device index out of range");
     return RT_OK;
 }
 
@@ -269,62 +247,31 @@ int chunk_records(const rt_indirect_params &pr, int n) {
     return (int)std::min<long long>(c, n);
 }
 
-void indirect_free(void *state);
-double indirect_ms(void *state, uint64_t seq);
-
-RtIndirectState *state_of(rt_scene *s) {
-    rt_internal_unit *slot = rt_internal_unit_slot(s, RT_INTERNAL_UNIT_INDIRECT);
-    if (!slot->state) {
-        slot->state = new RtIndirectState();
-        slot->free_state = indirect_free;
-        slot->stage_ms = indirect_ms;
-    }
-    return static_cast<RtIndirectState *>(slot->state);
-}
-
-/* the call's next event, recorded on stream */
-int mark(RtIndirectState *a, hipStream_t stream) {
-    if ((size_t)a->n_events == a->events.size()) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        a->events.push_back(e);
-    }
-    HIP_TRY(hipEventRecord(a->events[a->n_events], stream));
-    a->n_events += 1;
-    return RT_OK;
-}
-
 /* the last call's stage times from its events, once: interval i is stage i % stages of chunk i / stages, the stages being
  * raygen, trace, (stages == 4: query,) resolve */
 int collect(RtIndirectState *a) {
-    if (a->collected) return RT_OK;
-    if (a->n_events > 0) HIP_TRY(hipEventSynchronize(a->events[a->n_events - 1]));
+    if (a->clock.collected) return RT_OK;
+    std::vector<float> t;
+    const int rc = a->clock.intervals(&t);
+    if (rc) return rc;
     double ms[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = 0; i + 1 < a->n_events; ++i) {
-        float t = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&t, a->events[i], a->events[i + 1]));
-        ms[i % a->stages] += t;
-    }
+    for (size_t i = 0; i < t.size(); ++i) ms[i % (size_t)a->stages] += t[i];
     a->info.raygen_ms = ms[0], a->info.trace_ms = ms[1];
     a->info.query_ms = a->stages == 4 ? ms[2] : 0.0;
     a->info.resolve_ms = ms[a->stages - 1];
-    a->collected = true;
     return RT_OK;
 }
 
-void indirect_free(void *state) {
-    RtIndirectState *a = static_cast<RtIndirectState *>(state);
-    if (!a) return;
-    for (hipEvent_t e : a->events) (void)hipEventDestroy(e);
-    for (RtIndirectState::Buffer *b : {&a->rays, &a->samples, &a->gather, &a->hits, &a->out_rgb})
-        if (b->p) (void)hipFree(b->p);
-    delete a;
-}
+void indirect_free(void *state) { delete static_cast<RtIndirectState *>(state); }
 
 double indirect_ms(void *state, uint64_t seq) {
     RtIndirectState *a = static_cast<RtIndirectState *>(state);
-    if (!a || a->seq != seq || a->n_events == 0 || collect(a) != RT_OK) return -1.0;
+    if (!a || a->clock.seq != seq || a->clock.n_events == 0 || collect(a) != RT_OK) return -1.0;
     return a->info.raygen_ms + a->info.trace_ms + a->info.query_ms + a->info.resolve_ms;
+}
+
+RtIndirectState *state_of(rt_scene *s) {
+    return unit_state<RtIndirectState>(s, RT_INTERNAL_UNIT_INDIRECT, indirect_free, indirect_ms);
 }
 
 /* the rays of m records at d_hits, the first of which samples with key, into d_rays, on stream */
@@ -360,28 +307,28 @@ int run(rt_scene *s, const rt_indirect_params &pr, int n, const void *d_hits, co
     int n_objects = 0;
     HIP_TRY(hipSetDevice(rt_internal_scene_device(s)));
     int rc = rt_internal_object_diffuse(s, &d_kd, &n_objects);
-    if (rc == RT_OK) rc = grow(a->rays, most * 24);
-    if (rc == RT_OK) rc = grow(a->samples, most * 12);
-    if (rc == RT_OK && !pr.emitters) rc = grow(a->gather, most * 48);
+    if (rc == RT_OK) rc = a->rays.grow(most * 24);
+    if (rc == RT_OK) rc = a->samples.grow(most * 12);
+    if (rc == RT_OK && !pr.emitters) rc = a->gather.grow(most * 48);
     if (rc) return rc;
-    a->n_events = 0;
+    a->clock.n_events = 0;
     a->stages = pr.emitters ? 3 : 4;
-    a->collected = true;
+    a->clock.collected = true;
     a->info = rt_indirect_info{};
     a->info.records = n;
-    if ((rc = mark(a, stream))) return rc;
+    if ((rc = a->clock.mark(stream))) return rc;
     const unsigned group = (unsigned)(kResolveSamples / S);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const uint32_t m = (uint32_t)std::min(chunk, n - i0);
         const int n_rays = (int)(m * (uint32_t)S);                        /* <= kMaxBatchRays */
         const char *hits = static_cast<const char *>(d_hits) + (size_t)i0 * 48;
         rc = enqueue_raygen(pr, pr.key0 + (uint32_t)i0, m, hits, a->rays.p, stream);
-        if (rc == RT_OK) rc = mark(a, stream);
+        if (rc == RT_OK) rc = a->clock.mark(stream);
         if (rc == RT_OK) rc = rt_internal_launch_rays(s, n_rays, n_rays, a->rays.p, pr.gather_depth, a->samples.p, stream);
-        if (rc == RT_OK) rc = mark(a, stream);
+        if (rc == RT_OK) rc = a->clock.mark(stream);
         if (rc == RT_OK && !pr.emitters) {
             rc = rt_internal_launch_hits(s, n_rays, n_rays, a->rays.p, a->gather.p, stream);
-            if (rc == RT_OK) rc = mark(a, stream);
+            if (rc == RT_OK) rc = a->clock.mark(stream);
         }
         if (rc) return rc;
         hipLaunchKernelGGL(rt_indirect_resolve_kernel, dim3((m + group - 1) / group), dim3(kBlock), 0, stream, m, S, pr.gain,
@@ -390,24 +337,14 @@ int run(rt_scene *s, const rt_indirect_params &pr, int n, const void *d_hits, co
                            d_base ? static_cast<const float *>(d_base) + 3 * (size_t)i0 : nullptr,
                            static_cast<float *>(d_out) + 3 * (size_t)i0);
         HIP_TRY(hipGetLastError());
-        if ((rc = mark(a, stream))) return rc;
+        if ((rc = a->clock.mark(stream))) return rc;
         a->info.chunks += 1;
         a->info.rays += (int64_t)n_rays;
     }
-    a->collected = false;
-    a->seq = rt_internal_launch_seq(s);
+    a->clock.collected = false;
+    a->clock.seq = rt_internal_launch_seq(s);
     return RT_OK;
 }
-
-struct Unlock {
-    rt_scene *s;
-    ~Unlock() { rt_internal_unlock(s); }
-};
-
-struct DeviceBuffer {        /* rt_indirect_rays' allocations, freed on every way out */
-    void *p = nullptr;
-    ~DeviceBuffer() { (void)hipFree(p); }
-};
 
 } // namespace
 
@@ -417,7 +354,7 @@ int rt_capi_indirect_version(void) { return RT_CAPI_INDIRECT_VERSION; }
 
 int rt_indirect_rays_device(const rt_indirect_params *pr, int n, const void *d_hits, int device, void *d_out_rays, void *hip_stream) {
     int rc = check_rays_args(pr, n, d_hits, d_out_rays, true);
-    if (rc == RT_OK) rc = check_device(device);
+    if (rc == RT_OK) rc = rt_internal_check_device(device);
     if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(device));
     return enqueue_all_rays(*pr, n, d_hits, d_out_rays, static_cast<hipStream_t>(hip_stream));
@@ -425,17 +362,13 @@ int rt_indirect_rays_device(const rt_indirect_params *pr, int n, const void *d_h
 
 int rt_indirect_rays(const rt_indirect_params *pr, int n, const rt_hit *hits, int device, float *out_rays) {
     int rc = check_rays_args(pr, n, hits, out_rays, false);
-    if (rc == RT_OK) rc = check_device(device);
+    if (rc == RT_OK) rc = rt_internal_check_device(device);
     if (rc || n == 0) return rc;
-    const size_t bytes = (size_t)n * (size_t)(pr->samples * pr->samples) * 24;
-    DeviceBuffer d_hits, d_rays;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(&d_hits.p, (size_t)n * 48));
-    HIP_TRY(hipMalloc(&d_rays.p, bytes));
-    HIP_TRY(hipMemcpy(d_hits.p, hits, (size_t)n * 48, hipMemcpyHostToDevice));
-    if ((rc = enqueue_all_rays(*pr, n, d_hits.p, d_rays.p, nullptr))) return rc;
-    HIP_TRY(hipMemcpy(out_rays, d_rays.p, bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
+    const HostIn in[1] = {{hits, (size_t)n * 48}};
+    const HostOut out[1] = {{out_rays, (size_t)n * (size_t)(pr->samples * pr->samples) * 24}};
+    return staged_call(device, in, 1, out, 1, 0, nullptr, [&](void *const *d_in, void *const *d_out, void *) {
+        return enqueue_all_rays(*pr, n, d_in[0], d_out[0], nullptr);
+    });
 }
 
 int rt_indirect_diffuse_device(rt_scene *s, const rt_indirect_params *pr, int n, const void *d_hits, const void *d_base_rgb,
@@ -456,8 +389,8 @@ int rt_indirect_diffuse(rt_scene *s, const rt_indirect_params *pr, int n, const 
     Unlock unlock{s};
     RtIndirectState *a = state_of(s);
     HIP_TRY(hipSetDevice(rt_internal_scene_device(s)));
-    rc = grow(a->hits, (size_t)n * 48);
-    if (rc == RT_OK) rc = grow(a->out_rgb, (size_t)n * 12);
+    rc = a->hits.grow((size_t)n * 48);
+    if (rc == RT_OK) rc = a->out_rgb.grow((size_t)n * 12);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(a->hits.p, hits, (size_t)n * 48, hipMemcpyHostToDevice));
     if (base_rgb) HIP_TRY(hipMemcpy(a->out_rgb.p, base_rgb, (size_t)n * 12, hipMemcpyHostToDevice));

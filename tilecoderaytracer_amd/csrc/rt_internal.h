@@ -1,8 +1,11 @@
 /*
  * rt_internal.h -- what the library's units ask of one another across their object files; nothing here is part of the ABI.
- * rt_capi.hip owns the handle (struct rt_scene), the argument rules and the launch policy -- one copy per rule -- and
- * rt_adaptive.hip (include/rt_capi_adaptive.h), rt_lens.hip (include/rt_capi_lens.h) and rt_indirect.hip
- * (include/rt_capi_indirect.h) compose them through the calls below.
+ * rt_capi.hip owns the handle (struct rt_scene), the error text, the argument rules and the launch policy -- one copy per rule.
+ * Every other unit reports its errors through rt_internal_set_error and asks the device question through
+ * rt_internal_check_device: rt_denoise.hip, rt_image.hip, rt_upsample.hip, rt_temporal.hip and rt_svgf.hip, which launch
+ * kernels of their own and nothing else, and rt_adaptive.hip (include/rt_capi_adaptive.h), rt_lens.hip (include/rt_capi_lens.h)
+ * and rt_indirect.hip (include/rt_capi_indirect.h), which compose rt_capi.hip's launches through the calls below.  The host
+ * code those eight share among themselves is rt_host.h, which includes this file.
  */
 #ifndef RT_INTERNAL_H_
 #define RT_INTERNAL_H_
@@ -27,6 +30,9 @@ enum { RT_INTERNAL_UNIT_ADAPTIVE, RT_INTERNAL_UNIT_LENS, RT_INTERNAL_UNIT_INDIRE
 
 /* rt_capi.hip: the text behind rt_last_error(); returns code */
 int rt_internal_set_error(int code, const char *msg);
+/* rt_capi.hip: the device question every entry point asks last -- RT_ERR_NO_DEVICE without a HIP device, RT_ERR_INVALID for an
+ * index out of range */
+int rt_internal_check_device(int device);
 
 /* ---- rt_capi.hip, for rt_adaptive.hip, rt_lens.hip and rt_indirect.hip ---- */
 /* rt_render's checks in rt_render's order (the scene, the strip, the camera, the depth, the strip's size), no device work;

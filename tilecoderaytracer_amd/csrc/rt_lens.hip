@@ -30,7 +30,7 @@
 #include <vector>
 
 #include "../../include/rt_capi_lens.h"
-#include "rt_internal.h"
+#include "rt_host.h"
 
 #pragma clang fp contract(off)
 
@@ -60,16 +60,6 @@ constexpr int lds_floats() {
     return most;
 }
 static_assert(lds_floats() * 4 <= 16384, "resolve: LDS");
-
-int fail(int code, const std::string &msg) { return rt_internal_set_error(code, msg.c_str()); }
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorNoDevice ? RT_ERR_NO_DEVICE : RT_ERR_HIP,               \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
 
 RtLensCam cam_of(const rt_camera_desc *cam) {
     RtLensCam c;
@@ -167,21 +157,15 @@ __global__ __launch_bounds__(kBlock) void rt_lens_resolve_kernel(uint32_t m, int
     }
 }
 
-/* the handle's scratch, which only grows, and the last call's bookkeeping */
-struct RtLensState {
-    struct Buffer { void *p = nullptr; size_t bytes = 0; };
-    Buffer rays, samples, out_rgb;                         /* (out_rgb: the host variant's output) */
-    /* events of the last call: its start, then per chunk rays generated, traced, resolved */
-    std::vector<hipEvent_t> events;
-    int n_events = 0;
-    bool collected = true;
-    uint64_t seq = 0;                                     /* the handle's launch number at the call's end */
-    rt_lens_info info{};
-};
-
 namespace {
 
-int grow(RtLensState::Buffer &b, size_t need) { return rt_internal_grow(&b.p, &b.bytes, need); }
+/* the handle's scratch, which only grows, and the last call's bookkeeping */
+struct RtLensState {
+    Buffer rays, samples, out_rgb;                         /* (out_rgb: the host variant's output) */
+    StageClock clock;                                      /* the last call's start, then per chunk rays generated, traced, resolved */
+    rt_lens_info info{};
+    ~RtLensState() { clock.release(); }
+};
 
 unsigned blocks_of(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
@@ -195,14 +179,6 @@ int check_params(const rt_lens_params *pr, int W, int H) {
     if (!(pr->focus > 0.0f) || std::isinf(pr->focus)) return fail(RT_ERR_INVALID, "focus must be finite and > 0");
     if ((long long)pr->samples * W > 0x7fffffffLL || (long long)pr->samples * H > 0x7fffffffLL)
         return fail(RT_ERR_INVALID, "samples * W and samples * H must stay below 2^31");
-    return RT_OK;
-}
-
-int check_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "device index out of range");
     return RT_OK;
 }
 
@@ -241,60 +217,27 @@ int chunk_columns(const rt_lens_params &pr, int H, int columns) {
     return (int)std::min<long long>(c, columns);
 }
 
-void lens_free(void *state);
-double lens_ms(void *state, uint64_t seq);
-
-RtLensState *state_of(rt_scene *s) {
-    rt_internal_unit *slot = rt_internal_unit_slot(s, RT_INTERNAL_UNIT_LENS);
-    if (!slot->state) {
-        slot->state = new RtLensState();
-        slot->free_state = lens_free;
-        slot->stage_ms = lens_ms;
-    }
-    return static_cast<RtLensState *>(slot->state);
-}
-
-/* the call's next event, recorded on stream */
-int mark(RtLensState *a, hipStream_t stream) {
-    if ((size_t)a->n_events == a->events.size()) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        a->events.push_back(e);
-    }
-    HIP_TRY(hipEventRecord(a->events[a->n_events], stream));
-    a->n_events += 1;
-    return RT_OK;
-}
-
 /* the last call's stage times from its events, once: interval i is stage i % 3 of chunk i / 3 */
 int collect(RtLensState *a) {
-    if (a->collected) return RT_OK;
-    if (a->n_events > 0) HIP_TRY(hipEventSynchronize(a->events[a->n_events - 1]));
+    if (a->clock.collected) return RT_OK;
+    std::vector<float> t;
+    const int rc = a->clock.intervals(&t);
+    if (rc) return rc;
     double ms[3] = {0.0, 0.0, 0.0};
-    for (int i = 0; i + 1 < a->n_events; ++i) {
-        float t = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&t, a->events[i], a->events[i + 1]));
-        ms[i % 3] += t;
-    }
+    for (size_t i = 0; i < t.size(); ++i) ms[i % 3] += t[i];
     a->info.raygen_ms = ms[0], a->info.trace_ms = ms[1], a->info.resolve_ms = ms[2];
-    a->collected = true;
     return RT_OK;
 }
 
-void lens_free(void *state) {
-    RtLensState *a = static_cast<RtLensState *>(state);
-    if (!a) return;
-    for (hipEvent_t e : a->events) (void)hipEventDestroy(e);
-    for (RtLensState::Buffer *b : {&a->rays, &a->samples, &a->out_rgb})
-        if (b->p) (void)hipFree(b->p);
-    delete a;
-}
+void lens_free(void *state) { delete static_cast<RtLensState *>(state); }
 
 double lens_ms(void *state, uint64_t seq) {
     RtLensState *a = static_cast<RtLensState *>(state);
-    if (!a || a->seq != seq || a->n_events == 0 || collect(a) != RT_OK) return -1.0;
+    if (!a || a->clock.seq != seq || a->clock.n_events == 0 || collect(a) != RT_OK) return -1.0;
     return a->info.raygen_ms + a->info.trace_ms + a->info.resolve_ms;
 }
+
+RtLensState *state_of(rt_scene *s) { return unit_state<RtLensState>(s, RT_INTERNAL_UNIT_LENS, lens_free, lens_ms); }
 
 /* the rays of m pixels from frame column xc on, into d_rays, on stream */
 int enqueue_raygen(const rt_camera_desc *cam, int W, int H, const rt_lens_params &pr, int xc, uint32_t m, int planes, void *d_rays,
@@ -315,20 +258,20 @@ int run(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, in
     const int chunk = chunk_columns(pr, H, x1 - x0);
     const size_t most = (size_t)chunk * (size_t)H * (size_t)S;            /* rays of the largest chunk, the first */
     HIP_TRY(hipSetDevice(rt_internal_scene_device(s)));
-    int rc = grow(a->rays, most * 24);
-    if (rc == RT_OK) rc = grow(a->samples, most * 12);
+    int rc = a->rays.grow(most * 24);
+    if (rc == RT_OK) rc = a->samples.grow(most * 12);
     if (rc) return rc;
-    a->n_events = 0;
-    a->collected = true;
+    a->clock.n_events = 0;
+    a->clock.collected = true;
     a->info = rt_lens_info{};
     a->info.pixels = (int64_t)(x1 - x0) * H;
-    if ((rc = mark(a, stream))) return rc;
+    if ((rc = a->clock.mark(stream))) return rc;
     for (int xc = x0; xc < x1; xc += chunk) {
         const int columns = std::min(chunk, x1 - xc);
         const uint32_t m = (uint32_t)((size_t)columns * (size_t)H);
         const int n_rays = (int)(m * (uint32_t)S);                        /* <= kMaxBatchRays */
         rc = enqueue_raygen(cam, W, H, pr, xc, m, RT_LENS_PLANES, a->rays.p, stream);
-        if (rc == RT_OK) rc = mark(a, stream);
+        if (rc == RT_OK) rc = a->clock.mark(stream);
         if (rc) return rc;
 #if RT_LENS_PLANES
         for (int k = 0; k < S && rc == RT_OK; ++k)
@@ -339,30 +282,20 @@ int run(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, in
         rc = rt_internal_launch_rays(s, n_rays, n_rays, a->rays.p, max_depth, a->samples.p, stream);
         const unsigned resolve_blocks = (m + kResolveSamples / S - 1) / (kResolveSamples / S);
 #endif
-        if (rc == RT_OK) rc = mark(a, stream);
+        if (rc == RT_OK) rc = a->clock.mark(stream);
         if (rc) return rc;
         hipLaunchKernelGGL(rt_lens_resolve_kernel, dim3(resolve_blocks), dim3(kBlock), 0, stream, m, S, RT_LENS_PLANES,
                            static_cast<const float *>(a->samples.p),
                            static_cast<float *>(d_out_rgb) + 3 * (size_t)(xc - x0) * (size_t)H);
         HIP_TRY(hipGetLastError());
-        if ((rc = mark(a, stream))) return rc;
+        if ((rc = a->clock.mark(stream))) return rc;
         a->info.chunks += 1;
         a->info.rays += (int64_t)n_rays;
     }
-    a->collected = false;
-    a->seq = rt_internal_launch_seq(s);
+    a->clock.collected = false;
+    a->clock.seq = rt_internal_launch_seq(s);
     return RT_OK;
 }
-
-struct Unlock {
-    rt_scene *s;
-    ~Unlock() { rt_internal_unlock(s); }
-};
-
-struct DeviceBuffer {        /* rt_lens_rays' allocation, freed on every way out */
-    void *p = nullptr;
-    ~DeviceBuffer() { (void)hipFree(p); }
-};
 
 } // namespace
 
@@ -373,7 +306,7 @@ int rt_capi_lens_version(void) { return RT_CAPI_LENS_VERSION; }
 int rt_lens_rays_device(const rt_camera_desc *cam, int W, int H, int x0, int x1, const rt_lens_params *pr, int device,
                         void *d_out_rays, void *hip_stream) {
     int rc = check_rays_args(cam, W, H, x0, x1, pr, d_out_rays, true);
-    if (rc == RT_OK) rc = check_device(device);
+    if (rc == RT_OK) rc = rt_internal_check_device(device);
     if (rc || x0 == x1) return rc;
     HIP_TRY(hipSetDevice(device));
     return enqueue_raygen(cam, W, H, *pr, x0, (uint32_t)((size_t)(x1 - x0) * (size_t)H), 0, d_out_rays,
@@ -382,16 +315,13 @@ int rt_lens_rays_device(const rt_camera_desc *cam, int W, int H, int x0, int x1,
 
 int rt_lens_rays(const rt_camera_desc *cam, int W, int H, int x0, int x1, const rt_lens_params *pr, int device, float *out_rays) {
     int rc = check_rays_args(cam, W, H, x0, x1, pr, out_rays, false);
-    if (rc == RT_OK) rc = check_device(device);
+    if (rc == RT_OK) rc = rt_internal_check_device(device);
     if (rc || x0 == x1) return rc;
     const uint32_t m = (uint32_t)((size_t)(x1 - x0) * (size_t)H);
-    const size_t bytes = (size_t)m * (size_t)(pr->samples * pr->samples) * 24;
-    DeviceBuffer d;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(&d.p, bytes));
-    if ((rc = enqueue_raygen(cam, W, H, *pr, x0, m, 0, d.p, nullptr))) return rc;
-    HIP_TRY(hipMemcpy(out_rays, d.p, bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
+    const HostOut out[1] = {{out_rays, (size_t)m * (size_t)(pr->samples * pr->samples) * 24}};
+    return staged_call(device, nullptr, 0, out, 1, 0, nullptr, [&](void *const *, void *const *d_out, void *) {
+        return enqueue_raygen(cam, W, H, *pr, x0, m, 0, d_out[0], nullptr);
+    });
 }
 
 int rt_render_lens_device(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
@@ -414,7 +344,7 @@ int rt_render_lens(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0,
     RtLensState *a = state_of(s);
     const size_t n = (size_t)(x1 - x0) * (size_t)H;
     HIP_TRY(hipSetDevice(rt_internal_scene_device(s)));
-    rc = grow(a->out_rgb, n * 12);
+    rc = a->out_rgb.grow(n * 12);
     if (rc == RT_OK) rc = run(s, cam, W, H, x0, x1, max_depth, p, a->out_rgb.p, nullptr);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(out_rgb, a->out_rgb.p, n * 12, hipMemcpyDeviceToHost));

@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "../../include/rt_capi_tuning.h"
+#include "rt_internal.h"                /* rt_internal_set_error: the text behind rt_last_error() is rt_capi.hip's */
 
 namespace {
 
@@ -107,9 +108,6 @@ ncclResult_t loopback_recv(void *p, size_t n, int, int, ncclComm_t, hipStream_t)
 const char *loopback_error(ncclResult_t) { return "loopback transfer failed"; }
 
 } // namespace
-
-/* defined in rt_capi.hip: stores the message for rt_last_error() */
-extern "C" int rt_internal_set_error(int code, const char *msg);
 
 extern "C" int rt_strip_bounds(int W, int ngpu, int g, int *x0, int *x1) {
     if (W <= 0 || ngpu <= 0 || g < 0 || g >= ngpu) return 0;

@@ -34,8 +34,7 @@
 #include <string>
 
 #include "../../include/rt_svgf.h"
-
-extern "C" int rt_internal_set_error(int code, const char *msg);      /* rt_capi.hip: the text behind rt_last_error() */
+#include "rt_host.h"
 
 static_assert(sizeof(rt_hit) == 48, "rt_hit layout");
 static_assert(sizeof(rt_svgf_params) == 36, "rt_svgf_params layout");
@@ -64,16 +63,6 @@ constexpr bool fused_prefilter(int channels) {          /* the iteration kernel 
     return RT_SVGF_FUSED_PREFILTER == 1 || (RT_SVGF_FUSED_PREFILTER == 2 && channels == 3);
 }
 constexpr uint32_t kDead = 4u;                         /* aux.w: flags & 3, and this bit for a miss or a light */
-
-int fail(int code, const std::string &msg) { return rt_internal_set_error(code, msg.c_str()); }
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorNoDevice ? RT_ERR_NO_DEVICE : RT_ERR_HIP,               \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
 
 } // namespace
 
@@ -462,8 +451,6 @@ __global__ __launch_bounds__(kTileZ *kTileX) void rt_svgf_atrous_kernel(
 
 namespace {
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 /* the header's checks up to the buffers, in its order */
 int check_shape(const rt_svgf_params *pr, int Wn, int H) {
     if (!pr) return fail(RT_ERR_INVALID, "params is NULL");
@@ -478,14 +465,6 @@ int check_shape(const rt_svgf_params *pr, int Wn, int H) {
     if (!(pr->epsilon > 0.0f) || std::isinf(pr->epsilon)) return fail(RT_ERR_INVALID, "epsilon must be finite and > 0");
     if (Wn <= 0 || H <= 0) return fail(RT_ERR_INVALID, "need Wn, H > 0");
     if ((double)Wn * (double)H > kMaxPixels) return fail(RT_ERR_INVALID, "rectangle too large for its values and records");
-    return RT_OK;
-}
-
-int check_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "device index out of range");
     return RT_OK;
 }
 
@@ -608,21 +587,6 @@ int enqueue(const rt_svgf_params *pr, int Wn, int H, const Buffers &b, hipStream
     return RT_OK;
 }
 
-struct DeviceBuffers {       /* the host call's allocations, freed on every way out */
-    void *p[8] = {};
-    hipEvent_t start = nullptr, stop = nullptr;
-    ~DeviceBuffers() {
-        if (start) (void)hipEventDestroy(start);
-        if (stop) (void)hipEventDestroy(stop);
-        for (void *q : p) (void)hipFree(q);
-    }
-};
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
-}
-
 } // namespace
 
 extern "C" {
@@ -640,34 +604,15 @@ int rt_svgf_filter(int device, const rt_svgf_params *pr, int Wn, int H, const fl
     if (rc) return rc;
     if (!value || !hits || !moments || !len || !out_value)
         return fail(RT_ERR_INVALID, "value / hits / moments / len / out_value is NULL");
-    if ((rc = check_device(device))) return rc;
+    if ((rc = rt_internal_check_device(device))) return rc;
     const size_t pixels = (size_t)Wn * (size_t)H, cb = (size_t)pr->channels * sizeof(float);
-    const void *in[4] = {value, hits, moments, len};
-    const size_t in_bytes[4] = {pixels * cb, pixels * sizeof(rt_hit), pixels * 8, pixels * 4};
-    void *out[3] = {out_value, out_variance, out_estimate};
-    const size_t out_bytes[3] = {pixels * cb, pixels * 4, pixels * 4};
-    DeviceBuffers d;
-    HIP_TRY(hipSetDevice(device));
-    for (int k = 0; k < 4; ++k) HIP_TRY(hipMalloc(&d.p[k], in_bytes[k]));
-    for (int k = 0; k < 3; ++k)
-        if (out[k]) HIP_TRY(hipMalloc(&d.p[4 + k], out_bytes[k]));
-    HIP_TRY(hipMalloc(&d.p[7], scratch_layout(pr, pixels).bytes));
-    HIP_TRY(hipEventCreate(&d.start));
-    HIP_TRY(hipEventCreate(&d.stop));
-    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpy(d.p[k], in[k], in_bytes[k], hipMemcpyHostToDevice));
-    const Buffers b{d.p[0], d.p[1], d.p[2], d.p[3], d.p[4], d.p[5], d.p[6], d.p[7]};
-    HIP_TRY(hipEventRecord(d.start, nullptr));
-    if ((rc = enqueue(pr, Wn, H, b, nullptr))) return rc;
-    HIP_TRY(hipEventRecord(d.stop, nullptr));
-    HIP_TRY(hipEventSynchronize(d.stop));
-    for (int k = 0; k < 3; ++k)
-        if (out[k]) HIP_TRY(hipMemcpy(out[k], d.p[4 + k], out_bytes[k], hipMemcpyDeviceToHost));
-    if (kernel_ms) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, d.start, d.stop));
-        *kernel_ms = ms;
-    }
-    return RT_OK;
+    const HostIn in[4] = {{value, pixels * cb}, {hits, pixels * sizeof(rt_hit)}, {moments, pixels * 8}, {len, pixels * 4}};
+    const HostOut out[3] = {{out_value, pixels * cb}, {out_variance, pixels * 4}, {out_estimate, pixels * 4}};
+    return staged_call(device, in, 4, out, 3, scratch_layout(pr, pixels).bytes, kernel_ms,
+                       [&](void *const *d_in, void *const *d_out, void *d_scratch) {
+                           const Buffers b{d_in[0], d_in[1], d_in[2], d_in[3], d_out[0], d_out[1], d_out[2], d_scratch};
+                           return enqueue(pr, Wn, H, b, nullptr);
+                       });
 }
 
 int rt_svgf_filter_device(int device, const rt_svgf_params *pr, int Wn, int H, const void *d_value, const void *d_hits,
@@ -691,7 +636,7 @@ int rt_svgf_filter_device(int device, const rt_svgf_params *pr, int Wn, int H, c
         for (int q = o + 1; q < 8; ++q)
             if (overlap(bufs[o], bytes[o], bufs[q], bytes[q]))
                 return fail(RT_ERR_INVALID, "an output or the scratch overlaps another buffer");
-    if ((rc = check_device(device))) return rc;
+    if ((rc = rt_internal_check_device(device))) return rc;
     HIP_TRY(hipSetDevice(device));
     const Buffers b{d_value, d_hits, d_moments, d_len, d_out_value, d_out_variance, d_out_estimate, d_scratch};
     return enqueue(pr, Wn, H, b, static_cast<hipStream_t>(hip_stream));

@@ -26,8 +26,7 @@
 #include <string>
 
 #include "../../include/rt_temporal.h"
-
-extern "C" int rt_internal_set_error(int code, const char *msg);      /* rt_capi.hip: the text behind rt_last_error() */
+#include "rt_host.h"
 
 static_assert(sizeof(rt_hit) == 48, "rt_hit layout");
 static_assert(sizeof(rt_temporal_params) == 28, "rt_temporal_params layout");
@@ -42,16 +41,6 @@ namespace {
 constexpr int kTileZ = 64, kTileX = 4;                 /* a workgroup: 4 wavefronts, each 64 consecutive z of one column */
 constexpr uint64_t kMaxGroups = 1ull << 20;            /* workgroups of a launch; they stride over the tiles */
 constexpr double kMaxPixels = 2.0e9 * 4.0 * 4.0 / 60.0; /* rt_render_gbuffer's limit: 3.2e10 bytes of colours and records */
-
-int fail(int code, const std::string &msg) { return rt_internal_set_error(code, msg.c_str()); }
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorNoDevice ? RT_ERR_NO_DEVICE : RT_ERR_HIP,               \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
 
 struct V3 {
     float x, y, z;
@@ -244,14 +233,6 @@ int check_buffers(const rt_camera_desc *cam_prev, const rt_camera_desc *cam, con
     return RT_OK;
 }
 
-int check_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "device index out of range");
-    return RT_OK;
-}
-
 struct Buffers {             /* the call's buffers, in host or in device memory */
     const void *cur, *cur_hits, *prev_hits, *prev_value, *prev_moments, *prev_len;
     void *out_value, *out_moments, *out_len, *out_variance, *out_flags;
@@ -313,21 +294,6 @@ int enqueue(const rt_temporal_params *pr, const rt_camera_desc *cam_prev, const 
     return RT_OK;
 }
 
-struct DeviceBuffers {       /* the host call's allocations, freed on every way out */
-    void *p[11] = {};
-    hipEvent_t start = nullptr, stop = nullptr;
-    ~DeviceBuffers() {
-        if (start) (void)hipEventDestroy(start);
-        if (stop) (void)hipEventDestroy(stop);
-        for (void *q : p) (void)hipFree(q);
-    }
-};
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
-}
-
 /* rt_temporal_accumulate_device's checks and launch; staged: the variant (true in a build that has one) */
 int accumulate_device(int device, const rt_temporal_params *pr, const rt_camera_desc *cam_prev, const rt_camera_desc *cam, int W,
                       int H, int x0, int x1, const Buffers &b, void *hip_stream, bool staged) {
@@ -349,7 +315,7 @@ int accumulate_device(int device, const rt_temporal_params *pr, const rt_camera_
     for (int o = 0; o < 5; ++o)
         for (int q = 0; q < 4; ++q)
             if (overlap(outs[o], out_bytes[o], prevs[q], prev_bytes[q])) return fail(RT_ERR_INVALID, "an output overlaps a prev_* buffer");
-    if ((rc = check_device(device))) return rc;
+    if ((rc = rt_internal_check_device(device))) return rc;
     HIP_TRY(hipSetDevice(device));
     return enqueue(pr, cam_prev, cam, W, H, x0, x1, b, static_cast<hipStream_t>(hip_stream), staged);
 }
@@ -369,35 +335,16 @@ int rt_temporal_accumulate(int device, const rt_temporal_params *pr, const rt_ca
     if ((rc = check_buffers(cam_prev, cam, cur, cur_hits, prev_hits, prev_value, prev_moments, prev_len, out_value, out_moments,
                             out_len)))
         return rc;
-    if ((rc = check_device(device))) return rc;
+    if ((rc = rt_internal_check_device(device))) return rc;
     const size_t strip = (size_t)(x1 - x0) * (size_t)H, frame = (size_t)W * (size_t)H, cb = (size_t)pr->channels * sizeof(float);
-    const void *in[6] = {cur, cur_hits, prev_hits, prev_value, prev_moments, prev_len};
-    const size_t in_bytes[6] = {strip * cb, strip * sizeof(rt_hit), frame * sizeof(rt_hit), frame * cb, frame * 8, frame * 4};
-    void *out[5] = {out_value, out_moments, out_len, out_variance, out_flags};
-    const size_t out_bytes[5] = {strip * cb, strip * 8, strip * 4, strip * 4, strip};
-    DeviceBuffers d;
-    HIP_TRY(hipSetDevice(device));
-    for (int k = 0; k < 6; ++k)
-        if (in[k]) HIP_TRY(hipMalloc(&d.p[k], in_bytes[k]));
-    for (int k = 0; k < 5; ++k)
-        if (out[k]) HIP_TRY(hipMalloc(&d.p[6 + k], out_bytes[k]));
-    HIP_TRY(hipEventCreate(&d.start));
-    HIP_TRY(hipEventCreate(&d.stop));
-    for (int k = 0; k < 6; ++k)
-        if (in[k]) HIP_TRY(hipMemcpy(d.p[k], in[k], in_bytes[k], hipMemcpyHostToDevice));
-    const Buffers b{d.p[0], d.p[1], d.p[2], d.p[3], d.p[4], d.p[5], d.p[6], d.p[7], d.p[8], d.p[9], d.p[10]};
-    HIP_TRY(hipEventRecord(d.start, nullptr));
-    if ((rc = enqueue(pr, cam_prev, cam, W, H, x0, x1, b, nullptr, true))) return rc;
-    HIP_TRY(hipEventRecord(d.stop, nullptr));
-    HIP_TRY(hipEventSynchronize(d.stop));
-    for (int k = 0; k < 5; ++k)
-        if (out[k]) HIP_TRY(hipMemcpy(out[k], d.p[6 + k], out_bytes[k], hipMemcpyDeviceToHost));
-    if (kernel_ms) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, d.start, d.stop));
-        *kernel_ms = ms;
-    }
-    return RT_OK;
+    const HostIn in[6] = {{cur, strip * cb},        {cur_hits, strip * sizeof(rt_hit)}, {prev_hits, frame * sizeof(rt_hit)},
+                          {prev_value, frame * cb}, {prev_moments, frame * 8},          {prev_len, frame * 4}};
+    const HostOut out[5] = {{out_value, strip * cb}, {out_moments, strip * 8}, {out_len, strip * 4}, {out_variance, strip * 4},
+                            {out_flags, strip}};
+    return staged_call(device, in, 6, out, 5, 0, kernel_ms, [&](void *const *d_in, void *const *d_out, void *) {
+        const Buffers b{d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], d_in[5], d_out[0], d_out[1], d_out[2], d_out[3], d_out[4]};
+        return enqueue(pr, cam_prev, cam, W, H, x0, x1, b, nullptr, true);
+    });
 }
 
 int rt_temporal_accumulate_device(int device, const rt_temporal_params *pr, const rt_camera_desc *cam_prev, const rt_camera_desc *cam,

@@ -22,8 +22,7 @@
 #include <string>
 
 #include "../../include/rt_capi_upsample.h"
-
-extern "C" int rt_internal_set_error(int code, const char *msg);      /* rt_capi.hip: the text behind rt_last_error() */
+#include "rt_host.h"
 
 static_assert(sizeof(rt_hit) == 48, "rt_hit layout");
 static_assert(sizeof(rt_upsample_params) == 28, "rt_upsample_params layout");
@@ -37,16 +36,6 @@ namespace {
 constexpr int kTileZ = 64, kTileX = 4;                 /* a workgroup: 4 wavefronts, each 64 consecutive z of one column */
 constexpr int kCellsX = 3, kCellsZ = 33;               /* the most tap cells a tile touches, at s = 2: 4/2 + 1 and 64/2 + 1 */
 constexpr double kMaxPixels = 2.0e9 * 4.0 * 4.0 / 60.0; /* rt_render_gbuffer's limit: 3.2e10 bytes of colours and records */
-
-int fail(int code, const std::string &msg) { return rt_internal_set_error(code, msg.c_str()); }
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorNoDevice ? RT_ERR_NO_DEVICE : RT_ERR_HIP,               \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
 
 } // namespace
 
@@ -225,14 +214,6 @@ int check_params(const rt_upsample_params *pr, int Wn, int H) {
     return check_rectangle(Wn, H);
 }
 
-int check_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RT_ERR_NO_DEVICE, "no HIP device (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "device index out of range");
-    return RT_OK;
-}
-
 size_t cells_of(int n, int s) { return (size_t)((n + s - 1) / s); }
 
 dim3 grid_of(size_t columns, size_t rows, uint32_t *tiles_z) {
@@ -283,21 +264,6 @@ int enqueue_upsample(const rt_upsample_params *pr, int Wn, int H, const void *d_
     return RT_OK;
 }
 
-struct DeviceBuffers {       /* the host calls' allocations, freed on every way out */
-    void *hits = nullptr, *lo = nullptr, *base = nullptr, *out = nullptr, *flags = nullptr;
-    hipEvent_t start = nullptr, stop = nullptr;
-    ~DeviceBuffers() {
-        if (start) (void)hipEventDestroy(start);
-        if (stop) (void)hipEventDestroy(stop);
-        (void)hipFree(hits), (void)hipFree(lo), (void)hipFree(base), (void)hipFree(out), (void)hipFree(flags);
-    }
-};
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
 } // namespace
 
 extern "C" {
@@ -316,16 +282,13 @@ static int check_subsample(int scale, int white, int Wn, int H, const void *hits
 int rt_subsample_hits(int device, int scale, int white, int Wn, int H, const rt_hit *hits, rt_hit *out_lo) {
     int rc = check_subsample(scale, white, Wn, H, hits, out_lo);
     if (rc) return rc;
-    if ((rc = check_device(device))) return rc;
+    if ((rc = rt_internal_check_device(device))) return rc;
     const size_t pixels = (size_t)Wn * (size_t)H, cells = cells_of(Wn, scale) * cells_of(H, scale);
-    DeviceBuffers d;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(&d.hits, pixels * sizeof(rt_hit)));
-    HIP_TRY(hipMalloc(&d.out, cells * sizeof(rt_hit)));
-    HIP_TRY(hipMemcpy(d.hits, hits, pixels * sizeof(rt_hit), hipMemcpyHostToDevice));
-    if ((rc = enqueue_subsample(scale, white, Wn, H, d.hits, d.out, nullptr))) return rc;
-    HIP_TRY(hipMemcpy(out_lo, d.out, cells * sizeof(rt_hit), hipMemcpyDeviceToHost));
-    return RT_OK;
+    const HostIn in[1] = {{hits, pixels * sizeof(rt_hit)}};
+    const HostOut out[1] = {{out_lo, cells * sizeof(rt_hit)}};
+    return staged_call(device, in, 1, out, 1, 0, nullptr, [&](void *const *d_in, void *const *d_out, void *) {
+        return enqueue_subsample(scale, white, Wn, H, d_in[0], d_out[0], nullptr);
+    });
 }
 
 int rt_subsample_hits_device(int device, int scale, int white, int Wn, int H, const void *d_hits, void *d_out_lo,
@@ -334,7 +297,7 @@ int rt_subsample_hits_device(int device, int scale, int white, int Wn, int H, co
     if (rc) return rc;
     if (((uintptr_t)d_hits & 15u) != 0 || ((uintptr_t)d_out_lo & 15u) != 0)
         return fail(RT_ERR_INVALID, "d_hits and d_out_lo must be 16-byte aligned");
-    if ((rc = check_device(device))) return rc;
+    if ((rc = rt_internal_check_device(device))) return rc;
     HIP_TRY(hipSetDevice(device));
     return enqueue_subsample(scale, white, Wn, H, d_hits, d_out_lo, static_cast<hipStream_t>(hip_stream));
 }
@@ -344,33 +307,14 @@ int rt_upsample_guided(int device, const rt_upsample_params *pr, int Wn, int H, 
     int rc = check_params(pr, Wn, H);
     if (rc) return rc;
     if (!hits || !lo || !out) return fail(RT_ERR_INVALID, "hits / lo / out is NULL");
-    if ((rc = check_device(device))) return rc;
+    if ((rc = rt_internal_check_device(device))) return rc;
     const size_t pixels = (size_t)Wn * (size_t)H, cells = cells_of(Wn, pr->scale) * cells_of(H, pr->scale);
     const size_t cb = (size_t)pr->channels * sizeof(float);
-    DeviceBuffers d;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(&d.hits, pixels * sizeof(rt_hit)));
-    HIP_TRY(hipMalloc(&d.lo, cells * cb));
-    HIP_TRY(hipMalloc(&d.out, pixels * cb));
-    if (base) HIP_TRY(hipMalloc(&d.base, pixels * cb));
-    if (out_flags) HIP_TRY(hipMalloc(&d.flags, pixels));
-    HIP_TRY(hipEventCreate(&d.start));
-    HIP_TRY(hipEventCreate(&d.stop));
-    HIP_TRY(hipMemcpy(d.hits, hits, pixels * sizeof(rt_hit), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.lo, lo, cells * cb, hipMemcpyHostToDevice));
-    if (base) HIP_TRY(hipMemcpy(d.base, base, pixels * cb, hipMemcpyHostToDevice));
-    HIP_TRY(hipEventRecord(d.start, nullptr));
-    if ((rc = enqueue_upsample(pr, Wn, H, d.hits, d.lo, d.base, d.out, d.flags, nullptr, true))) return rc;
-    HIP_TRY(hipEventRecord(d.stop, nullptr));
-    HIP_TRY(hipEventSynchronize(d.stop));
-    HIP_TRY(hipMemcpy(out, d.out, pixels * cb, hipMemcpyDeviceToHost));
-    if (out_flags) HIP_TRY(hipMemcpy(out_flags, d.flags, pixels, hipMemcpyDeviceToHost));
-    if (kernel_ms) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, d.start, d.stop));
-        *kernel_ms = ms;
-    }
-    return RT_OK;
+    const HostIn in[3] = {{hits, pixels * sizeof(rt_hit)}, {lo, cells * cb}, {base, pixels * cb}};
+    const HostOut outs[2] = {{out, pixels * cb}, {out_flags, pixels}};
+    return staged_call(device, in, 3, outs, 2, 0, kernel_ms, [&](void *const *d_in, void *const *d_out, void *) {
+        return enqueue_upsample(pr, Wn, H, d_in[0], d_in[1], d_in[2], d_out[0], d_out[1], nullptr, true);
+    });
 }
 
 /* rt_upsample_guided_device's checks and launch; lds: the tap-loading variant (true in a build that has one) */
@@ -385,7 +329,7 @@ static int upsample_device(int device, const rt_upsample_params *pr, int Wn, int
     const size_t cb = (size_t)pr->channels * sizeof(float);
     if (overlap(d_out, (size_t)Wn * (size_t)H * cb, d_lo, cells_of(Wn, pr->scale) * cells_of(H, pr->scale) * cb))
         return fail(RT_ERR_INVALID, "d_out overlaps d_lo");
-    if ((rc = check_device(device))) return rc;
+    if ((rc = rt_internal_check_device(device))) return rc;
     HIP_TRY(hipSetDevice(device));
     return enqueue_upsample(pr, Wn, H, d_hits, d_lo, d_base, d_out, d_flags, static_cast<hipStream_t>(hip_stream), lds);
 }
