@@ -56,9 +56,10 @@
  * -0.0 becomes +0.0).  A strip equals the frame's columns, because the previous frame is always whole.  The variance is that of
  * the luminance samples the history has seen, not of their mean; it is 0 while len is 1.
  *
- * Not provided: moving objects (records carry no motion), history behind mirrors or glass (the record is the mirror's),
+ * Not provided: history behind mirrors or glass (the record is the mirror's),
  * supersampled frames (they have no records), several GPUs, the counting build.  The spatial variance estimate for short
- * histories and the variance-steered filter are include/rt_svgf.h.
+ * histories and the variance-steered filter are include/rt_svgf.h.  Objects that move between the frames (these records carry no
+ * motion) are include/rt_motion.h: the same calls with one rigid motion per object.
  *
  * ERRORS.  Int codes and rt_last_error() as everywhere.  All argument checks come before any device work, RT_ERR_INVALID in this
  * order: params is NULL; channels not 1 or 3; match_color not 0 or 1; max_history outside 1..65535; normal_cos NaN or outside

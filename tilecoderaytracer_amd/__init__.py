@@ -15,7 +15,8 @@ from .host import HostScene  # noqa: F401
 from .renderer import Renderer, adaptive_flags, denoise, encode_image, indirect_rays, lens_rays, subsample_hits, upsample_guided  # noqa: F401
 from .renderer import TemporalHistory, temporal_accumulate, temporal_params  # noqa: F401
 from .renderer import svgf_filter, svgf_params  # noqa: F401
+from .renderer import motion_accumulate, object_motions, render_animated  # noqa: F401
 
 __all__ = ["RtError", "load_library", "library_path", "HostScene", "Renderer", "adaptive_flags", "denoise", "encode_image",
            "indirect_rays", "lens_rays", "subsample_hits", "upsample_guided", "TemporalHistory", "temporal_accumulate",
-           "temporal_params", "svgf_filter", "svgf_params"]
+           "temporal_params", "svgf_filter", "svgf_params", "motion_accumulate", "object_motions", "render_animated"]

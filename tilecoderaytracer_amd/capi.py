@@ -72,6 +72,12 @@ class RtTemporalParams(C.Structure):
                 ("plane_eps", C.c_float), ("alpha", C.c_float), ("alpha_moments", C.c_float)]
 
 
+class RtObjectMotion(C.Structure):
+    """include/rt_motion.h: the rows {m0 m1 m2 | m3}, {m4 .. m7}, {m8 .. m11} of the rigid motion that carries a point of an
+    object in the current frame to where it was in the previous frame."""
+    _fields_ = [("m", C.c_float * 12)]
+
+
 class RtSvgfParams(C.Structure):
     """include/rt_svgf.h: channels (1 or 3), iterations (1..5), normal squarings (0..6), match_color (0 / 1), the history length
     below which the variance is estimated spatially (1..65535), that estimate's radius (1..3), the luminance term's sigma (0:
@@ -377,6 +383,13 @@ def load_library():
         lib.rt_temporal_accumulate.argtypes = head + [C.POINTER(C.c_double)]
         lib.rt_temporal_accumulate_device.argtypes = head + [vp]
         lib.rt_temporal_accumulate.restype = lib.rt_temporal_accumulate_device.restype = i
+    # include/rt_motion.h (likewise absent from older builds)
+    if hasattr(lib, "rt_motion_accumulate"):
+        lib.rt_capi_motion_version.restype = i
+        head = [i, C.POINTER(RtTemporalParams), C.POINTER(RtCameraDesc), C.POINTER(RtCameraDesc), i, i, i, i, vp, i] + [vp] * 11
+        lib.rt_motion_accumulate.argtypes = head + [C.POINTER(C.c_double)]
+        lib.rt_motion_accumulate_device.argtypes = head + [vp]
+        lib.rt_motion_accumulate.restype = lib.rt_motion_accumulate_device.restype = i
     # include/rt_svgf.h (likewise absent from older builds)
     if hasattr(lib, "rt_svgf_filter"):
         lib.rt_capi_svgf_version.restype = i

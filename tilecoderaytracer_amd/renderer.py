@@ -194,6 +194,30 @@ def temporal_accumulate(cur, hits, camera, prev=None, x0=0, W=None, device=0, **
     frame: its camera, its records (W, H) and what this call returned for it.  -> (value of cur's shape, moments float32
     (Wn, H, 2), length float32 (Wn, H), variance float32 (Wn, H), flags bool (Wn, H): the pixels without history).  params:
     temporal_params()'s keywords but channels, which cur's shape gives.  Runs on GPU `device`; there is no CPU path."""
+    return _accumulate(None, cur, hits, camera, prev, x0, W, device, params)
+
+
+def _motion_table(motions):
+    """None or a float32 (n, 12) array -> (the C-contiguous array or None, n)"""
+    if motions is None:
+        return None, 0
+    table = np.ascontiguousarray(motions, dtype=np.float32)
+    if table.ndim != 2 or table.shape[1] != 12:
+        raise ValueError(f"motions must be (n, 12), not {table.shape}")
+    return table, table.shape[0]
+
+
+def motion_accumulate(cur, hits, camera, prev=None, motions=None, x0=0, W=None, device=0, **params):
+    """temporal_accumulate() for a scene whose objects move (include/rt_motion.h, rt_motion_accumulate): motions None or float32
+    (n, 12), row o the rigid motion -- rows {m0 m1 m2 | m3}, {m4 .. m7}, {m8 .. m11} -- that carries a point of Scene object o in
+    this frame to where it was in the previous one (object_motions() makes the table from two poses).  A record whose object
+    has no row, or the identity's bits, is treated as temporal_accumulate() treats it.  Arguments, result and params are
+    temporal_accumulate()'s.  Runs on GPU `device`; there is no CPU path."""
+    return _accumulate(_motion_table(motions), cur, hits, camera, prev, x0, W, device, params)
+
+
+def _accumulate(table, cur, hits, camera, prev, x0, W, device, params):
+    """temporal_accumulate() (table None) and motion_accumulate() (table (array or None, n))"""
     hits = _frame_records(hits)
     cur = np.ascontiguousarray(cur, dtype=np.float32)
     channels = 3 if cur.ndim == 3 else 1
@@ -217,11 +241,53 @@ def temporal_accumulate(cur, hits, camera, prev=None, x0=0, W=None, device=0, **
     out = np.empty(cur.shape, dtype=np.float32)
     out_moments, out_len = np.empty((Wn, H, 2), dtype=np.float32), np.empty((Wn, H), dtype=np.float32)
     variance, flags = np.empty((Wn, H), dtype=np.float32), np.empty((Wn, H), dtype=np.uint8)
-    capi.check(capi.load_library().rt_temporal_accumulate(int(device), C.byref(pr), _camera_ptr(cam_prev), _camera_ptr(camera), W, H,
-                                                          int(x0), int(x0) + Wn, cur.ctypes.data, hits.ctypes.data, *ptr,
-                                                          out.ctypes.data, out_moments.ctypes.data, out_len.ctypes.data,
-                                                          variance.ctypes.data, flags.ctypes.data, None))
+    lib = capi.load_library()
+    head = (int(device), C.byref(pr), _camera_ptr(cam_prev), _camera_ptr(camera), W, H, int(x0), int(x0) + Wn)
+    tail = (cur.ctypes.data, hits.ctypes.data, *ptr, out.ctypes.data, out_moments.ctypes.data, out_len.ctypes.data,
+            variance.ctypes.data, flags.ctypes.data, None)
+    if table is None:
+        capi.check(lib.rt_temporal_accumulate(*head, *tail))
+    else:
+        capi.check(lib.rt_motion_accumulate(*head, table[0].ctypes.data if table[0] is not None else None, table[1], *tail))
     return out, out_moments, out_len, variance, flags.view(np.bool_)
+
+
+_IDENTITY_MOTION = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=np.float32)
+
+
+def object_motions(desc_prev, desc_cur):
+    """The motion table between two poses of the same object list (include/rt_motion.h), given as two HostScene.desc (pointers
+    to, or instances of, RtSceneDesc) -> float32 (n_objects, 12), what motion_accumulate() takes for a frame of desc_cur whose
+    previous frame was desc_prev's.  A sphere gets the identity matrix and t = origin_prev - origin_cur in fp32.  A plane gets
+    R = F_prev F_cur^T, F the columns (horizontal, vertical, normal), and t = o_prev - R o_cur with o the plane_origin of a
+    finite plane and the origin of an infinite one, computed in float64 and rounded once.  An object whose geometry words are
+    equal as bits in both poses gets the identity's bits, so it is static.  ValueError if the counts or kinds differ.  A
+    convenience: the table it makes is as exact as fp32 allows, and outside the bit-exact definition."""
+    prev = desc_prev.contents if hasattr(desc_prev, "contents") else desc_prev
+    cur = desc_cur.contents if hasattr(desc_cur, "contents") else desc_cur
+    n = int(cur.n_objects)
+    if int(prev.n_objects) != n:
+        raise ValueError(f"the poses have {int(prev.n_objects)} and {n} objects")
+    geometry = ("origin", "radius", "radius_squared", "plane_origin", "normal", "vertical", "horizontal", "reverse_normal",
+                "v_distance", "h_distance", "distance_to_origin")
+    words = lambda o: b"".join(bytes(memoryview(np.array(getattr(o, k), dtype=np.float32))) for k in geometry)
+    vec = lambda v: np.array(list(v), dtype=np.float32)
+    out = np.tile(_IDENTITY_MOTION, (n, 1))
+    for k in range(n):
+        a, b = prev.objects[k], cur.objects[k]
+        if a.kind != b.kind:
+            raise ValueError(f"object {k} is of kind {a.kind} in one pose and {b.kind} in the other")
+        if words(a) == words(b):
+            continue
+        if a.kind == 0:                                                 # a sphere: a translation
+            out[k, 3::4] = vec(a.origin) - vec(b.origin)
+            continue
+        frame = lambda o: np.stack([vec(o.horizontal), vec(o.vertical), vec(o.normal)], axis=1).astype(np.float64)
+        R = frame(a) @ frame(b).T
+        where = (lambda o: vec(o.plane_origin)) if a.kind == 2 else (lambda o: vec(o.origin))
+        t = where(a).astype(np.float64) - R @ where(b).astype(np.float64)
+        out[k] = np.concatenate([R, t[:, None]], axis=1).reshape(12).astype(np.float32)
+    return out
 
 
 class TemporalHistory:
@@ -250,17 +316,18 @@ class TemporalHistory:
 
     def reset(self):
         """forget the history: the next frame is a first frame"""
-        self.frames, self._next_column, self._cam_prev, self._cam = 0, 0, None, None
+        self.frames, self._next_column, self._cam_prev, self._cam, self._motions = 0, 0, None, None, None
 
     def _copy_camera(self, camera):
         cam = capi.RtCameraDesc()
         C.memmove(C.byref(cam), _camera_ptr(camera), C.sizeof(cam))
         return cam
 
-    def push_device(self, value, hits, camera, x0=0, x1=None, stream=None):
+    def push_device(self, value, hits, camera, x0=0, x1=None, stream=None, motions=None):
         """push() of torch tensors on the device (float32 value, the records as 12 int32 words each), enqueued on `stream` (the
         current one by default) without a host wait -> the strip's (value, variance, flags) as views of this history's buffers,
-        valid until the next frame's push."""
+        valid until the next frame's push.  motions: None, a float32 (n, 12) numpy table, which is uploaded, or a float32 device
+        tensor of 12 n words, used as it is and kept alive until the next push (include/rt_motion.h)."""
         import torch
         W, H, ch = self.W, self.H, self.channels
         x0, x1 = int(x0), W if x1 is None else int(x1)
@@ -281,19 +348,29 @@ class TemporalHistory:
                 part(new["hits"], 12).copy_(hits.reshape(-1).view(torch.int32))      # next frame's previous records
             out = [part(new["value"], ch), part(new["moments"], 2), part(new["length"], 1), part(self._variance, 1),
                    part(self._flags, 1)]
-            capi.check(self._lib.rt_temporal_accumulate_device(
-                self._device, C.byref(self._params), None if first else C.byref(self._cam_prev), C.byref(self._cam), W, H, x0, x1,
-                value.data_ptr(), part(new["hits"], 12).data_ptr(), *prev, *[t.data_ptr() for t in out], stream.cuda_stream))
+            head = (self._device, C.byref(self._params), None if first else C.byref(self._cam_prev), C.byref(self._cam), W, H, x0, x1)
+            tail = (value.data_ptr(), part(new["hits"], 12).data_ptr(), *prev, *[t.data_ptr() for t in out], stream.cuda_stream)
+            if motions is None:
+                capi.check(self._lib.rt_temporal_accumulate_device(*head, *tail))
+            else:
+                if not isinstance(motions, torch.Tensor):
+                    with torch.cuda.stream(stream):
+                        motions = torch.tensor(_motion_table(motions)[0].reshape(-1), device="cuda")
+                if motions.dtype != torch.float32 or motions.numel() % 12 or not motions.is_contiguous():
+                    raise ValueError("a device motion table is a contiguous float32 tensor of 12 n words")
+                self._motions = motions                                 # (alive while the launch may read it)
+                capi.check(self._lib.rt_motion_accumulate_device(*head, motions.data_ptr() if motions.numel() else None,
+                                                                 motions.numel() // 12, *tail))
         self._next_column = x1
         if x1 == W:                                                     # the frame is whole: swap the sets
             self.frames, self._next_column, self._cam_prev = self.frames + 1, 0, self._cam
         return out[0], out[3], out[4]
 
-    def push(self, rgb, hits, camera, x0=0, x1=None):
+    def push(self, rgb, hits, camera, x0=0, x1=None, motions=None):
         """Columns [x0, x1) of the next frame, seen by `camera`: rgb float32 (Wn, H) or (Wn, H, 3) by this history's channels,
         hits HIT_DTYPE (Wn, H) -> (value of rgb's shape, variance float32 (Wn, H), flags bool (Wn, H)), temporal_accumulate()'s
-        bit for bit.  A frame's strips are pushed in ascending order from column 0; the strip that ends at W completes the
-        frame and swaps the two sets."""
+        bit for bit -- with motions (push_device()'s), motion_accumulate()'s.  A frame's strips are pushed in ascending order
+        from column 0; the strip that ends at W completes the frame and swaps the two sets."""
         import torch
         hits = _frame_records(hits)
         rgb = np.ascontiguousarray(rgb, dtype=np.float32)
@@ -303,7 +380,7 @@ class TemporalHistory:
         with torch.cuda.device(self._device):
             d_rgb = torch.tensor(rgb.reshape(-1), device="cuda")
             d_hits = torch.tensor(hits.reshape(-1).view(np.int32), device="cuda")      # (a copy: the caller's may be read-only)
-            value, variance, flags = self.push_device(d_rgb, d_hits, camera, x0, x1)
+            value, variance, flags = self.push_device(d_rgb, d_hits, camera, x0, x1, motions=motions)
             return (value.cpu().numpy().reshape(shape), variance.cpu().numpy().reshape(hits.shape),
                     flags.cpu().numpy().reshape(hits.shape).view(np.bool_))
 
@@ -1057,3 +1134,52 @@ class Renderer:
         li = capi.RtLaunchInfo()
         capi.check(self._lib.rt_get_launch_info(self._scene, C.byref(li)))
         return li
+
+
+def render_animated(frames, W, H, max_depth, term="indirect", samples=1, filter=None, **kw):
+    """Renderer.render_accumulated() for a scene whose objects move (include/rt_motion.h): frames is a sequence of (Renderer,
+    camera, motions or None), one per W x H frame -- the Renderer of that frame's pose (all on one device), its camera (an
+    RtCameraDesc) and the motion table from that pose to the previous frame's (object_motions(); push_device()'s motions; the
+    first frame's is never read).  Frame k is its renderer's G-buffer at max_depth and its term sampled with seed k, as
+    render_accumulated() makes them, pushed into one TemporalHistory with the frame's table, with no host wait and no download
+    between the frames.  kw and filter are render_accumulated()'s.  -> the last frame's (value, variance, flags), what
+    motion_accumulate() over the public calls' frames gives bit for bit."""
+    import torch
+    if term not in ("indirect", "ao", "direct"):
+        raise ValueError(f'term must be "indirect", "ao" or "direct", not {term!r}')
+    frames = list(frames)
+    if not frames:
+        raise ValueError("no frames")
+    device = int(frames[0][0]._device)
+    if any(int(r._device) != device for r, _, _ in frames):
+        raise ValueError("the frames' renderers must be on one device")
+    names = ("match_color", "max_history", "normal_cos", "plane_eps", "alpha", "alpha_moments")
+    history = TemporalHistory(W, H, 1 if term == "ao" else 3, device, **{k: kw.pop(k) for k in names if k in kw})
+    own = [(r, r._cam) for r, _, _ in frames]
+    try:
+        with torch.cuda.device(device):
+            colours = torch.empty((W * H * 3,), dtype=torch.float32, device="cuda")
+            records = torch.empty((W * H * 12,), dtype=torch.int32, device="cuda")
+            plane = torch.empty((W * H,), dtype=torch.float32, device="cuda") if term == "ao" else None
+            stream = torch.cuda.current_stream()
+            for k, (r, camera, motions) in enumerate(frames):
+                r._cam = C.pointer(camera)
+                if term == "direct":
+                    r.set_shadow_seed(k)
+                r.render_gbuffer_device(W, H, max_depth, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
+                if term == "indirect":
+                    r.indirect_diffuse_device(W * H, records.data_ptr(), colours.data_ptr(), colours.data_ptr(), stream.cuda_stream,
+                                              samples=samples, seed=k, **kw)
+                elif term == "ao":
+                    r.ambient_occlusion_device(W * H, H, records.data_ptr(), plane.data_ptr(), samples=samples, seed=k,
+                                               stream=stream.cuda_stream, **kw)
+                value, variance, flags = history.push_device(plane if term == "ao" else colours, records, camera, stream=stream,
+                                                             motions=motions)
+            if filter is not None:
+                value, variance = history.filter_device(stream=stream, **filter)
+            shape = (W, H) if term == "ao" else (W, H, 3)
+            return (value.cpu().numpy().reshape(shape), variance.cpu().numpy().reshape(W, H),
+                    flags.cpu().numpy().reshape(W, H).view(np.bool_))
+    finally:
+        for r, cam in own:
+            r._cam = cam
