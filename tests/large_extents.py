@@ -121,6 +121,19 @@ class Guarded:
         self.all = self.body = None
 
 
+def hashed(n, salt, scale=1.0, offset=0.0):
+    """n floats in [offset, offset + scale) on the device, a hash of their index, made a chunk at a time (never the sentinel: it is
+    no finite number)"""
+    import torch
+    out = torch.empty((n,), dtype=torch.float32, device="cuda")
+    step = 1 << 26
+    for c0 in range(0, n, step):
+        k = torch.arange(c0, min(c0 + step, n), dtype=torch.int64, device="cuda")
+        out[c0:c0 + step] = ((((k + salt) * 2654435761) >> 7) & 0xFFFF).to(torch.float32) * (scale / 65536.0) + offset
+        del k
+    return out
+
+
 def count_equal(t, value):
     total = 0
     flat = t.reshape(-1)

@@ -48,11 +48,13 @@ def moved(hits, motions, moving):
 
 
 def accumulate(cur, hits, cam, prev=None, motions=None, x0=0, W=None, match_color=False, max_history=32, normal_cos=0.9,
-               plane_eps=0.05, alpha=0.0, alpha_moments=0.0, details=False):
+               plane_eps=0.05, alpha=0.0, alpha_moments=0.0, details=False, prev_x0=0):
     """rt_motion_accumulate: temporal_ref.accumulate's arguments and result, with motions None or float32 (n, 12); with details
     also a dict: "moving" bool (Wn, H), "outside" bool (Wn, H), live pixels that are reprojected and land outside the previous
     frame (or behind its eye), "identity" bool (Wn, H), the live pixels that take the identity tap, and "passing" int (Wn, H), for
-    the other live pixels how many of their cells inside the frame passed the tap tests (before the bw > 0 test)"""
+    the other live pixels how many of their cells inside the frame passed the tap tests (before the bw > 0 test).  prev_x0:
+    temporal_ref.accumulate's -- the previous frame's arrays hold its columns [prev_x0, prev_x0 + n) only, and a tap outside them
+    raises IndexError."""
     cur = np.asarray(cur, dtype=F)
     Wn, H = hits.shape
     one = cur.ndim == 2
@@ -69,9 +71,11 @@ def accumulate(cur, hits, cam, prev=None, motions=None, x0=0, W=None, match_colo
         if prev is not None:
             cam_prev, g_all, p_value, p_moments, p_len = prev
             W = g_all.shape[0] if W is None else W
-            assert g_all.shape == (W, H)
-            words = np.concatenate([np.asarray(p_value, dtype=F).reshape(W, H, Cn), np.asarray(p_moments, dtype=F).reshape(W, H, 2),
-                                    np.asarray(p_len, dtype=F).reshape(W, H, 1)], axis=-1)
+            n_prev = g_all.shape[0]                              # the previous frame's columns [prev_x0, prev_x0 + n_prev) are here
+            assert g_all.shape == (n_prev, H) and 0 <= prev_x0 and prev_x0 + n_prev <= W
+            words = np.concatenate([np.asarray(p_value, dtype=F).reshape(n_prev, H, Cn),
+                                    np.asarray(p_moments, dtype=F).reshape(n_prev, H, 2),
+                                    np.asarray(p_len, dtype=F).reshape(n_prev, H, 1)], axis=-1)
             live = ~dead_records(hits)
             moving = moving_records(hits, motions)
             pnt, nrm = moved(hits, motions, moving)              # Pp and Np: the tap tests and the reprojection read these
@@ -99,7 +103,12 @@ def accumulate(cur, hits, cam, prev=None, motions=None, x0=0, W=None, match_colo
                     inside = seen & (i >= 0) & (i < W) & (j >= 0) & (j < H)
                     if a or b:
                         inside = inside & ~identity              # the identity's only tap is its own cell
-                    cell = (np.clip(i, 0, W - 1), np.clip(j, 0, H - 1))           # (a cell that does not exist is never taken)
+                    held = (i >= prev_x0) & (i < prev_x0 + n_prev)
+                    if (inside & ~held).any():
+                        raise IndexError(f"{int((inside & ~held).sum())} taps fall on columns {int(i[inside & ~held].min())}.."
+                                         f"{int(i[inside & ~held].max())} of the previous frame, of which only "
+                                         f"{prev_x0}:{prev_x0 + n_prev} are given")
+                    cell = (np.clip(i - prev_x0, 0, n_prev - 1), np.clip(j, 0, H - 1))   # (a cell that does not exist is never taken)
                     g = g_all[cell]
                     take = (g["object"] == hits["object"]) & ((g["flags"] & 3) == (hits["flags"] & 3))
                     if match_color:

@@ -76,12 +76,27 @@ def project(cam_prev, point, W, H):
     return seen, px, pz
 
 
+def tap_columns(cam_prev, hits, W, H, points=None):
+    """the columns [lo, hi) of the previous W x H frame that hold every cell a reprojected tap of the live records `hits` can
+    fall on (what accumulate's prev_x0 window must hold); points: where the records' points were (motion_ref.moved), if not their
+    own.  None if no record is seen."""
+    with np.errstate(all="ignore"):
+        seen, px, _ = project(cam_prev, hits["point"] if points is None else points, W, H)
+        seen = seen & ~dead_records(hits)
+        if not seen.any():
+            return None
+        i0 = np.floor(px[seen]).astype(np.int64)
+    return max(int(i0.min()), 0), min(int(i0.max()) + 2, W)
+
+
 def accumulate(cur, hits, cam, prev=None, x0=0, W=None, match_color=False, max_history=32, normal_cos=0.9, plane_eps=0.05,
-               alpha=0.0, alpha_moments=0.0, details=False):
+               alpha=0.0, alpha_moments=0.0, details=False, prev_x0=0):
     """rt_temporal_accumulate: cur float32 (Wn, H[, 3]), hits HIT_DTYPE (Wn, H), prev None or (camera, hits, value, moments,
     length) of the whole W x H previous frame -> (value, moments (Wn, H, 2), length, variance, flags bool); with details also a
     dict: "outside" bool (Wn, H), live pixels that project outside the previous frame (or behind its eye), and "passing" int
-    (Wn, H), for the other live pixels how many of their cells inside the frame passed the tap tests (before the bw > 0 test)"""
+    (Wn, H), for the other live pixels how many of their cells inside the frame passed the tap tests (before the bw > 0 test).
+    With prev_x0 (and W) the previous frame's four arrays hold only its columns [prev_x0, prev_x0 + n): a frame too large to have on
+    the host.  A tap on a cell of the frame outside those columns raises IndexError; it never counts as a rejected tap."""
     cur = np.asarray(cur, dtype=F)
     Wn, H = hits.shape
     one = cur.ndim == 2
@@ -97,9 +112,11 @@ def accumulate(cur, hits, cam, prev=None, x0=0, W=None, match_color=False, max_h
         if prev is not None:
             cam_prev, g_all, p_value, p_moments, p_len = prev
             W = g_all.shape[0] if W is None else W
-            assert g_all.shape == (W, H)
-            words = np.concatenate([np.asarray(p_value, dtype=F).reshape(W, H, Cn), np.asarray(p_moments, dtype=F).reshape(W, H, 2),
-                                    np.asarray(p_len, dtype=F).reshape(W, H, 1)], axis=-1)
+            n_prev = g_all.shape[0]                              # the previous frame's columns [prev_x0, prev_x0 + n_prev) are here
+            assert g_all.shape == (n_prev, H) and 0 <= prev_x0 and prev_x0 + n_prev <= W
+            words = np.concatenate([np.asarray(p_value, dtype=F).reshape(n_prev, H, Cn),
+                                    np.asarray(p_moments, dtype=F).reshape(n_prev, H, 2),
+                                    np.asarray(p_len, dtype=F).reshape(n_prev, H, 1)], axis=-1)
             live = ~dead_records(hits)
             nrm, pnt = hits["normal"], hits["point"]
             col = np.ascontiguousarray(hits["color"]).view(np.uint32)
@@ -128,7 +145,12 @@ def accumulate(cur, hits, cam, prev=None, x0=0, W=None, match_color=False, max_h
                     wz = fz if b else F(1.0) - fz
                     bw = np.ones((Wn, H), dtype=F) if identity else wx * wz
                     inside = seen & (i >= 0) & (i < W) & (j >= 0) & (j < H)
-                    cell = (np.clip(i, 0, W - 1), np.clip(j, 0, H - 1))           # (a cell that does not exist is never taken)
+                    held = (i >= prev_x0) & (i < prev_x0 + n_prev)
+                    if (inside & ~held).any():
+                        raise IndexError(f"{int((inside & ~held).sum())} taps fall on columns {int(i[inside & ~held].min())}.."
+                                         f"{int(i[inside & ~held].max())} of the previous frame, of which only "
+                                         f"{prev_x0}:{prev_x0 + n_prev} are given")
+                    cell = (np.clip(i - prev_x0, 0, n_prev - 1), np.clip(j, 0, H - 1))   # (a cell that does not exist is never taken)
                     g = g_all[cell]
                     take = (g["object"] == hits["object"]) & ((g["flags"] & 3) == (hits["flags"] & 3))
                     if match_color:

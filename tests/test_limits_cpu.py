@@ -2,7 +2,8 @@
 fails a LATER check, whose text it reports, or reaches the device question (RT_ERR_NO_DEVICE on a machine without one) -- and
 the first refused value is RT_ERR_INVALID with the limit's text.  The handle is test_gbuffer_cpu.py's stand-in (zeroed memory,
 never a scene): every check comes before the handle's contents are used.  Then the two facts test_large_extents_gpu.py leans on:
-large_extents.column_rays is rays_ref.camera_rays, and denoise_ref is local within m = 2 (2^iterations - 1) pixels on BOTH axes.
+large_extents.column_rays is rays_ref.camera_rays, and denoise_ref is local within m = 2 (2^iterations - 1) pixels on BOTH axes;
+and the one test_svgf_large_gpu.py leans on: svgf_ref is local within spatial_radius + 2 (2^iterations - 1).
 
 The limits, in integers (the checks compare in double, exactly at these sizes):
   rt_render*            3 (x1 - x0) H <= 8e9 floats.  8e9 is not a multiple of 3: the last admitted strip has 2 666 666 666 pixels
@@ -23,6 +24,7 @@ from rays_ref import camera_rays
 from test_denoise_cpu import random_frame
 from tilecoderaytracer_amd import HostScene, capi
 
+F = np.float32
 INT_MAX = (1 << 31) - 1
 LAST_STRIP, FIRST_REFUSED_STRIP = (1333333333, 2), (888888889, 3)          # (columns, H): 2 666 666 666 and 2 666 666 667 pixels
 assert LAST_STRIP[0] * LAST_STRIP[1] * 3 == 8 * 10 ** 9 - 2 and FIRST_REFUSED_STRIP[0] * FIRST_REFUSED_STRIP[1] * 3 == 8 * 10 ** 9 + 1
@@ -267,3 +269,50 @@ def test_denoise_ref_is_local_on_both_axes(iterations, sigma, squarings):
     short_x = denoise_ref.denoise(rgb[x0 - m + 1:x1 + m - 1, z0 - m:z1 + m], hits[x0 - m + 1:x1 + m - 1, z0 - m:z1 + m], iterations,
                                   sigma, squarings)[m - 1:-(m - 1), m:-m]
     assert not denoise_ref.same_bits(short_z, full[x0:x1, z0:z1]) and not denoise_ref.same_bits(short_x, full[x0:x1, z0:z1])
+
+
+@pytest.mark.parametrize("radius", [1, 3])
+@pytest.mark.parametrize("iterations", [1, 2, 3])
+def test_svgf_ref_is_local_on_both_axes(iterations, radius):
+    """include/rt_svgf.h's strip statement, on x AND on z, which test_svgf_large_gpu.py's windows and strips rest on: an output
+    pixel depends on nothing farther than m = spatial_radius + 2 (2^iterations - 1) pixels away on either axis.  The estimate
+    reaches spatial_radius; iteration i reads values and variances 2 * 2^i away, and its own pixel's tolerance reads variances
+    one pixel away, which is never farther -- so the luminance term's 3 x 3 prefilter does not widen m.  svgf_ref of a crop that
+    holds a window and a margin of m, clipped where the frame ends, equals the whole 40 x 50 frame's three outputs on the window
+    bit for bit; with a margin of m - 1, on z alone and on x alone, it does not."""
+    import svgf_ref
+    Wn, H = 40, 50
+    m = radius + 2 * (2 ** iterations - 1)
+    _, hits = random_frame(60 + iterations, Wn, H, n_objects=1, palette=1)
+    hits["flags"] &= 1
+    hits["object"] = 0
+    hits["object"][::7, ::5] = -1
+    rng = np.random.default_rng(70 + iterations)
+    value = rng.random((Wn, H, 3), dtype=F) + F(0.01)
+    m1 = rng.random((Wn, H), dtype=F) + F(0.01)
+    moments = np.stack([m1, m1 * m1 + (rng.random((Wn, H), dtype=F) - F(0.2)) * F(0.05)], axis=-1).astype(F)
+    length = np.floor(F(1.0) + rng.random((Wn, H), dtype=F) * F(6.0)).astype(F)       # 1..6 against min_history 4: both estimates
+    kw = dict(iterations=iterations, sigma_l=2.0, min_history=4, spatial_radius=radius, normal_squarings=1, match_color=False,
+              sigma_plane=0.4)
+    full = svgf_ref.svgf(value, hits, moments, length, **kw)
+    assert (length < 4).mean() > 0.2 and (length >= 4).mean() > 0.2
+
+    def crop(cx0, cx1, cz0, cz1):
+        part = lambda a: np.ascontiguousarray(a[cx0:cx1, cz0:cz1])
+        return svgf_ref.svgf(part(value), part(hits), part(moments), part(length), **kw)
+
+    windows = [(0, 8, 0, 8), (32, 40, 42, 50), (0, 8, 42, 50), (32, 40, 0, 8), (0, 40, 22, 28), (18, 22, 0, 50)]
+    for x0, x1, z0, z1 in windows:
+        cx0, cx1, cz0, cz1 = max(x0 - m, 0), min(x1 + m, Wn), max(z0 - m, 0), min(z1 + m, H)
+        for got, want, name in zip(crop(cx0, cx1, cz0, cz1), full, ("value", "variance", "estimate")):
+            assert svgf_ref.same_bits(got[x0 - cx0:x1 - cx0, z0 - cz0:z1 - cz0], want[x0:x1, z0:z1]), (name, x0, x1, z0, z1)
+    # tightness: the frame without its first and last row, then without its first and last column -- a margin of m - 1 for the
+    # pixels m away from them -- changes those pixels
+    short_z = crop(0, Wn, 1, H - 1)
+    short_x = crop(1, Wn - 1, 0, H)
+    same_z = all(svgf_ref.same_bits(g[:, m - 1:H - m - 1], w[:, m:H - m]) for g, w in zip(short_z, full))
+    same_x = all(svgf_ref.same_bits(g[m - 1:Wn - m - 1], w[m:Wn - m]) for g, w in zip(short_x, full))
+    assert not same_z and not same_x
+    # ... and no pixel farther away
+    assert all(svgf_ref.same_bits(g[:, m:H - m - 2], w[:, m + 1:H - m - 1]) for g, w in zip(short_z, full))
+    assert all(svgf_ref.same_bits(g[m:Wn - m - 2], w[m + 1:Wn - m - 1]) for g, w in zip(short_x, full))

@@ -406,6 +406,41 @@ def test_ref_equals_the_definition_in_float32_scalars_on_made_up_records():
             assert flags[hits["object"] == o].all(), (o, word)
 
 
+def test_refs_given_a_window_of_the_previous_frame_equal_the_whole_frames_columns_and_refuse_a_narrow_one():
+    """prev_x0, which test_motion_large_gpu.py's reference rests on: temporal_ref and motion_ref given only the previous frame's
+    columns that the taps of a few current columns reach (temporal_ref.tap_columns) equal, word for word, what they give with the
+    whole 61 x 37 previous frame; a window one column narrower on either side raises, it is never a rejected tap"""
+    W, H = 61, 37
+    cases = [(temporal_ref.accumulate, pair_records("truck", W, H), None, 3)]
+    cases.append((motion_ref.accumulate, motion_scenes.records("spheres_truck", W, H), motion_scenes.table("spheres_truck"), 1))
+    windows = 0
+    for accumulate, (cam_prev, cam, prev_hits, hits), table, channels in cases:
+        rng = np.random.default_rng(channels)
+        cur = rng.random((W, H, 3) if channels == 3 else (W, H), dtype=F)
+        history = made_up_history(11, W, H, channels)
+        more = dict(normal_cos=-1.0, plane_eps=0.0, max_history=4) if table is None else dict(motions=table)
+        whole = accumulate(cur, hits, cam, (cam_prev, prev_hits) + history, **more)
+        assert 50 <= whole[4].sum() <= W * H - 200
+        for c0, c1 in ((0, 1), (20, 23), (31, 33), (60, 61), (0, 61)):
+            part = np.ascontiguousarray(hits[c0:c1])
+            before = part["point"] if table is None else motion_ref.moved(part, table, motion_ref.moving_records(part, table))[0]
+            span = temporal_ref.tap_columns(cam_prev, part, W, H, before)
+            lo, hi = span or (c0, c1)                             # (None: no point of the column is seen; any window does)
+            assert 0 <= lo < hi <= W
+
+            def windowed(a, b):
+                prev = (cam_prev, np.ascontiguousarray(prev_hits[a:b])) + tuple(np.ascontiguousarray(t[a:b]) for t in history)
+                return accumulate(np.ascontiguousarray(cur[c0:c1]), part, cam, prev, x0=c0, W=W, prev_x0=a, **more)
+
+            same_words(windowed(lo, hi), [np.ascontiguousarray(w[c0:c1]) for w in whole], f"columns {c0}:{c1} from {lo}:{hi}")
+            windows += int((lo, hi) != (0, W))
+            for a, b in ((lo + 1, hi), (lo, hi - 1)):
+                if a < b and span:
+                    with pytest.raises(IndexError):
+                        windowed(a, b)
+    assert windows >= 6                                          # (most windows are a few columns, not the frame)
+
+
 # ---- 4. the conditions on the pose pairs the GPU tests compare ----------------------------------------------------------------------
 
 def classes(name, W, H):

@@ -10,25 +10,13 @@ import pytest
 
 import large_extents as le
 import temporal_ref
-from large_extents import Guarded
+from large_extents import Guarded, hashed
 from tilecoderaytracer_amd import HostScene, Renderer, capi
 from tilecoderaytracer_amd.renderer import HIT_DTYPE, temporal_params
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 B32 = 1 << 32
-
-
-def hashed(n, salt, scale=1.0, offset=0.0):
-    """n floats in [offset, offset + scale) on the device, a hash of their index, made a chunk at a time"""
-    import torch
-    out = torch.empty((n,), dtype=torch.float32, device="cuda")
-    step = 1 << 26
-    for c0 in range(0, n, step):
-        k = torch.arange(c0, min(c0 + step, n), dtype=torch.int64, device="cuda")
-        out[c0:c0 + step] = ((((k + salt) * 2654435761) >> 7) & 0xFFFF).to(torch.float32) * (scale / 65536.0) + offset
-        del k
-    return out
 
 
 def test_accumulate_where_the_records_pass_2_32_bytes():
