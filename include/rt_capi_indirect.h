@@ -41,7 +41,8 @@
  *   - The directions are cosine-distributed (the disc lift), so mean estimates irradiance / pi and albedo * mean is the
  *     Lambertian bounce with no further weight.  A mirror (diffuse 0) gains nothing.
  *   - A gather ray that misses returns the scene's null_color: an open scene is lit by its sky.
- *   - Only the first hit gathers: what the camera ray sees in a mirror or through glass is not given a bounce of its own.
+ *   - Only the first hit gathers: what the camera ray sees in a mirror or through glass is not given a bounce of its own
+ *     (for mirrors, include/rt_mirror.h gives the records to gather at).
  *   - An inside hit (RT_HIT_INSIDE) gathers inside the sphere that contains it, as AO looks there.
  *
  * SOFT-SHADOW SCENES (rt_scene_create_soft with at least one area light) are refused with RT_ERR_INVALID, for the reason
@@ -77,8 +78,8 @@
  * rt_trace_rays and rt_intersect_rays.
  *
  * Not provided: several GPUs; the counting build; soft-shadow scenes; compaction of dead records (a sky pixel still traces its
- * S degenerate rays: a compacting variant needs a host read-back); gathers at mirrored or refracted hits; more than one
- * diffuse bounce beyond what gather_depth gives the gather rays' own direct shading; importance by BRDF.
+ * S degenerate rays: a compacting variant needs a host read-back); gathers at refracted hits (mirrors: include/rt_mirror.h);
+ * more than one diffuse bounce beyond what gather_depth gives the gather rays' own direct shading; importance by BRDF.
  *
  * rt_indirect_params is 28 bytes; rt_indirect_info is 56 bytes: records at 0, rays at 8, chunks at 16, raygen_ms at 24,
  * trace_ms at 32, query_ms at 40, resolve_ms at 48.

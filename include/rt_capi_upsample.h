@@ -53,8 +53,8 @@
  * reported, not hidden, so that a caller may gather for them at full resolution.
  *
  * Not provided: several GPUs, the counting build, supersampled frames (they have no records), scales above 8, filtering across
- * mirrored or refracted content (a mirror's record is the mirror's; what it shows is not guided), and hole refinement without a
- * host read-back of the flags.
+ * refracted content (a pane's record is the pane's; for mirrors, include/rt_mirror.h makes the guide records of what they
+ * show), and hole refinement without a host read-back of the flags.
  *
  * ERRORS.  Int codes and rt_last_error() as everywhere.  All argument checks come before any device work, RT_ERR_INVALID in this
  * order: params is NULL; scale outside 2..8; channels not 1 or 3; normal_squarings outside 0..6; match_color, modulate (for the

@@ -32,8 +32,8 @@
  * fails).  The motion table is never read on a first frame.
  *
  * Not provided: history is not invalidated where a mover's shadow or reflection passes over a surface that stayed (alpha is
- * the caller's tool for that); deforming or scaling objects; history behind mirrors or glass; supersampled frames; several
- * GPUs; the counting build; a command-line flag (the executable has no animated scene).
+ * the caller's tool for that); deforming or scaling objects; history behind glass (mirrors: include/rt_mirror.h);
+ * supersampled frames; several GPUs; the counting build; a command-line flag (the executable has no animated scene).
  *
  * ERRORS.  The checks are rt_temporal_accumulate's, in its order, each RT_ERR_INVALID and each before any device work.  The new
  * ones: after the first-frame rule, n_motions < 0 or n_motions > 4096 (the scene's object limit), then motions NULL while

@@ -63,8 +63,9 @@
  * spatial_radius + 2 * (2^iterations - 1) columns of its edges.  On a flat interior region with constant input variance v and
  * sigma_l = 0 one iteration gives v * (35/128)^2 up to rounding (the sum of the squared B3 weights is (35/128)^2).
  *
- * Not provided: feeding the first iteration's output back into the history, moving objects, mirrored or refracted content (the
- * record is the mirror's or the pane's), several GPUs, the counting build, supersampled frames (they have no records).
+ * Not provided: feeding the first iteration's output back into the history, moving objects, refracted content (the record is
+ * the pane's; for mirrors, include/rt_mirror.h makes the guide records), several GPUs, the counting build, supersampled frames
+ * (they have no records).
  *
  * ERRORS.  Int codes and rt_last_error() as everywhere.  All argument checks come before any device work, RT_ERR_INVALID in this
  * order: params is NULL; channels not 1 or 3; iterations outside 1..5; normal_squarings outside 0..6; match_color not 0 or 1;

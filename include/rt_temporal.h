@@ -56,7 +56,7 @@
  * -0.0 becomes +0.0).  A strip equals the frame's columns, because the previous frame is always whole.  The variance is that of
  * the luminance samples the history has seen, not of their mean; it is 0 while len is 1.
  *
- * Not provided: history behind mirrors or glass (the record is the mirror's),
+ * Not provided: history behind glass (the record is the pane's; for mirrors, include/rt_mirror.h makes the guide records),
  * supersampled frames (they have no records), several GPUs, the counting build.  The spatial variance estimate for short
  * histories and the variance-steered filter are include/rt_svgf.h.  Objects that move between the frames (these records carry no
  * motion) are include/rt_motion.h: the same calls with one rigid motion per object.

@@ -137,6 +137,22 @@ class RtIndirectInfo(C.Structure):
                 ("trace_ms", C.c_double), ("query_ms", C.c_double), ("resolve_ms", C.c_double)]
 
 
+RT_MIRROR_MAX_BOUNCES = 64
+
+
+class RtMirrorParams(C.Structure):
+    """include/rt_mirror.h: the most mirrors followed (0..64), the most rays walked per launch (0: the default) and the
+    `reflective` at or above which a hit is followed (not NaN)."""
+    _fields_ = [("max_bounces", C.c_int32), ("chunk_rays", C.c_int32), ("min_reflective", C.c_float)]
+
+
+class RtMirrorInfo(C.Structure):
+    """include/rt_mirror.h: the scene's last rt_mirror_records* call -- its rays, chunks of rays, hit queries launched, and the
+    two stages' HIP-event times."""
+    _fields_ = [("rays", C.c_int64), ("chunks", C.c_int32), ("queries", C.c_int32), ("query_ms", C.c_double),
+                ("step_ms", C.c_double)]
+
+
 RT_TRANSFER_SRGB, RT_TRANSFER_LINEAR, RT_TRANSFER_CUSTOM = 0, 1, 2
 
 
@@ -367,6 +383,13 @@ def load_library():
         for name in ("rt_indirect_rays", "rt_indirect_rays_device", "rt_indirect_diffuse", "rt_indirect_diffuse_device",
                      "rt_get_indirect_info"):
             getattr(lib, name).restype = i
+    # include/rt_mirror.h (likewise absent from older builds)
+    if hasattr(lib, "rt_mirror_records"):
+        lib.rt_mirror_version.restype = i
+        lib.rt_mirror_records.argtypes = [vp, C.POINTER(RtMirrorParams), i, i, vp, vp, vp, vp, vp]
+        lib.rt_mirror_records_device.argtypes = [vp, C.POINTER(RtMirrorParams), i, i, vp, vp, vp, vp, vp, vp]
+        lib.rt_get_mirror_info.argtypes = [vp, C.POINTER(RtMirrorInfo)]
+        lib.rt_mirror_records.restype = lib.rt_mirror_records_device.restype = lib.rt_get_mirror_info.restype = i
     # include/rt_capi_upsample.h (likewise absent from older builds)
     if hasattr(lib, "rt_upsample_guided"):
         lib.rt_capi_upsample_version.restype = i

@@ -171,6 +171,7 @@ struct rt_scene {
      * call's bookkeeping, with the unit's way of freeing it and of telling its last call's stage times */
     rt_internal_unit units[RT_INTERNAL_UNITS] = {};
     void *d_object_diffuse = nullptr;                /* rt_internal_object_diffuse(): a float per Scene object, made on first use */
+    void *d_object_reflective = nullptr;             /* rt_internal_object_reflective(): likewise */
     char launch_kernel[RT_KERNEL_NAME_BYTES] = {};   /* the whole name; launch.kernel is its first 47 characters */
     std::mutex mu;
 };
@@ -2002,6 +2003,20 @@ int rt_internal_object_diffuse(rt_scene *s, const float **d_kd, int *n_objects) 
     return RT_OK;
 }
 
+int rt_internal_object_reflective(rt_scene *s, const float **d_rf, int *n_objects) {
+    const size_t n = s->objects.size();
+    if (!s->d_object_reflective && n > 0) {
+        std::vector<float> rf(n);
+        for (size_t i = 0; i < n; ++i) rf[i] = s->objects[i].reflective;
+        HIP_TRY(hipSetDevice(s->device));
+        HIP_TRY(hipMalloc(&s->d_object_reflective, n * sizeof(float)));
+        HIP_TRY(hipMemcpy(s->d_object_reflective, rf.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    }
+    *d_rf = static_cast<const float *>(s->d_object_reflective);
+    *n_objects = (int)n;
+    return RT_OK;
+}
+
 int rt_internal_grow(void **buf, size_t *bytes, size_t need) { return grow_device_buffer(buf, bytes, need); }
 
 int rt_capi_version(void) { return RT_CAPI_VERSION; }
@@ -2193,6 +2208,7 @@ int rt_scene_destroy(rt_scene *s) {
     if (s->h_error) (void)hipHostFree(s->h_error);
     if (s->d_timeline) (void)hipFree(s->d_timeline);
     if (s->d_object_diffuse) (void)hipFree(s->d_object_diffuse);
+    if (s->d_object_reflective) (void)hipFree(s->d_object_reflective);
     for (rt_internal_unit &u : s->units)
         if (u.state) u.free_state(u.state);
     delete s;

@@ -103,7 +103,7 @@ int staged_call(int device, const HostIn *in, int n_in, const HostOut *out, int 
     return RT_OK;
 }
 
-/* ---- THE COMPOSING UNITS (rt_adaptive.hip, rt_lens.hip, rt_indirect.hip) ---- */
+/* ---- THE COMPOSING UNITS (rt_adaptive.hip, rt_lens.hip, rt_indirect.hip, rt_mirror.hip) ---- */
 
 struct Unlock {              /* the handle's lock, given back on every way out */
     rt_scene *s;

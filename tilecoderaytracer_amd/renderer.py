@@ -99,6 +99,11 @@ def indirect_params(samples=4, gather_depth=1, gain=1.0, seed=0, key0=0, emitter
                                  int(key0) & 0xFFFFFFFF, float(gain))
 
 
+def mirror_params(max_bounces=8, min_reflective=1.0, chunk_rays=0):
+    """mirror_records' keywords -> an RtMirrorParams (include/rt_mirror.h); the library checks the values."""
+    return capi.RtMirrorParams(int(max_bounces), int(chunk_rays), float(min_reflective))
+
+
 def _records(hits):
     if not isinstance(hits, np.ndarray) or hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous:
         raise TypeError("hits must be a C-contiguous numpy array of HIT_DTYPE")
@@ -795,7 +800,7 @@ class Renderer:
                                                          C.c_void_p(out_ptr), C.c_void_p(stream)))
 
     def render_ao(self, W, H, samples=4, radius=1.0, seed=0, channels=1, scale=1, normal_squarings=3, sigma_plane=0.0,
-                  refine=False, key0_refine=0x80000000):
+                  refine=False, key0_refine=0x80000000, mirrors=None):
         """The ambient-occlusion plane of a W x H frame, computed on the GPU where its records were made: a depth-0
         rt_render_gbuffer_device and rt_ambient_occlusion_device (rows = H) enqueued on one stream with no host wait between
         them, then a download of the plane alone -> float32 (W, H), or (W, H, 3) with channels = 3 (a grey frame for denoise()
@@ -804,8 +809,14 @@ class Renderer:
         section 3).  scale 2..8 (include/rt_capi_upsample.h): the plane is gathered for every scale-th pixel in both directions
         and upsampled, rt_subsample_hits_device, rt_ambient_occlusion_device and rt_upsample_guided_device on that one stream
         with no host wait -- ambient_occlusion_scaled(render_gbuffer(W, H, 0)[1], scale, ...) bit for bit; refine costs exactly
-        one read-back of the flags before the holes' batch is enqueued."""
+        one read-back of the flags before the holes' batch is enqueued.  mirrors: None, or a dict of max_bounces and
+        min_reflective (include/rt_mirror.h; scale 1 only): the plane is gathered at the terminal records of the pixel rays,
+        ambient_occlusion(render_gbuffer_mirrored(W, H, 0, ...)[1], ...) bit for bit -- an open fraction takes no weight."""
         import torch
+        if mirrors is not None:
+            if scale != 1:
+                raise ValueError("mirrors needs scale 1")
+            return self._render_ao_mirrored(W, H, self._ao_params(samples, radius, seed, 0, channels), mirrors)
         if scale != 1:
             return self._render_ao_scaled(W, H, samples, radius, seed, channels, scale, normal_squarings, sigma_plane, refine,
                                           key0_refine)
@@ -989,7 +1000,7 @@ class Renderer:
             return out.cpu().numpy().reshape(W, H, 3)                 # the one download
 
     def render_indirect(self, W, H, max_depth, samples=4, gather_depth=1, gain=1.0, seed=0, emitters=False, denoise=None, scale=1,
-                        normal_squarings=3, sigma_plane=0.0, refine=False, key0_refine=0x80000000):
+                        normal_squarings=3, sigma_plane=0.0, refine=False, key0_refine=0x80000000, mirrors=None):
         """A W x H frame with one diffuse bounce added, computed on the GPU where its records were made
         (include/rt_capi_indirect.h): rt_render_gbuffer_device and rt_indirect_diffuse_device -- the frame's colours the base,
         in place -- enqueued on one stream with no host wait between them, then one download -> float32 (W, H, 3).  The result
@@ -1002,10 +1013,18 @@ class Renderer:
         rt_subsample_hits_device, rt_indirect_diffuse_device and rt_upsample_guided_device on that one stream with no host wait
         -- indirect_diffuse_scaled(hits, scale, ..., base=rgb) bit for bit, and with denoise rgb + denoise(
         indirect_diffuse_scaled(hits, scale, ...), hits, ...); refine costs exactly one read-back of the flags before the holes'
-        batch is enqueued.  With scale 1 nothing of this runs and normal_squarings, sigma_plane and refine are not read."""
+        batch is enqueued.  With scale 1 nothing of this runs and normal_squarings, sigma_plane and refine are not read.
+        mirrors: None, or a dict of max_bounces and min_reflective (include/rt_mirror.h; scale 1 and no denoise only): the term
+        is gathered at the terminal records of the pixel rays and multiplied by the path's weight before it is added -- with
+        (_, hits, _, weight, _) = render_gbuffer_mirrored(W, H, max_depth, ...), rgb + weight * indirect_diffuse(hits, ...), one
+        fp32 multiply and one fp32 add, bit for bit."""
         import torch
         device = int(self._device)
         kw = dict(samples=samples, gather_depth=gather_depth, gain=gain, seed=seed, emitters=emitters)
+        if mirrors is not None:
+            if scale != 1 or denoise is not None:
+                raise ValueError("mirrors needs scale 1 and no denoise")
+            return self._render_indirect_mirrored(W, H, max_depth, kw, mirrors)
         if scale != 1:
             return self._render_indirect_scaled(W, H, max_depth, kw, denoise, scale, normal_squarings, sigma_plane, refine,
                                                 key0_refine)
@@ -1032,7 +1051,132 @@ class Renderer:
                                                    scratch.data_ptr(), stream.cuda_stream))
             return torch.add(colours, clean).cpu().numpy()            # the one download
 
-    def render_accumulated(self, cameras, W, H, max_depth, term="indirect", samples=1, filter=None, **kw):
+    MIRROR_OUTPUTS = ("guide", "weight", "path")
+
+    def mirror_records(self, rays, max_bounces=8, min_reflective=1.0, rows=None, chunk_rays=0, outputs=MIRROR_OUTPUTS):
+        """What each ray sees through the scene's mirrors (include/rt_mirror.h, rt_mirror_records).  rays as intersect_rays'
+        (float32 (n, 6) or (X, Z, 6)); a hit is followed while its object's `reflective` >= min_reflective, max_bounces times
+        at the most.  -> (hits, guide, weight, path): the terminal records and the guide records (HIT_DTYPE, rays' shape), the
+        path's throughput (float32, shape + (3,)) and the path word (uint32: k | cut << 8 | tag << 12).  hits is what
+        ambient_occlusion() and indirect_diffuse() gather at; guide is what the filters and the accumulation are steered by --
+        its object is a tagged id, never an index.  outputs: which of the three optional ones are asked for; the others are
+        None and what is returned does not depend on them.  rows and chunk_rays never change a result."""
+        n, default_rows = self._batch(rays, "rays")
+        shape = rays.shape[:-1]
+        hits = np.zeros(shape, dtype=HIT_DTYPE)
+        guide = np.zeros(shape, dtype=HIT_DTYPE) if "guide" in outputs else None
+        weight = np.zeros(shape + (3,), dtype=np.float32) if "weight" in outputs else None
+        path = np.zeros(shape, dtype=np.uint32) if "path" in outputs else None
+        params = mirror_params(max_bounces, min_reflective, chunk_rays)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        capi.check(self._lib.rt_mirror_records(self._scene, C.byref(params), n, int(default_rows if rows is None else rows),
+                                               rays.ctypes.data, hits.ctypes.data, ptr(guide), ptr(weight), ptr(path)))
+        return hits, guide, weight, path
+
+    def mirror_records_device(self, n, rows, rays_ptr, hits_ptr, guide_ptr=0, weight_ptr=0, path_ptr=0, stream=0, max_bounces=8,
+                              min_reflective=1.0, chunk_rays=0):
+        """Enqueue the mirror chains of n rays (6 float32 each) at device address rays_ptr on a HIP stream: the terminal
+        records at hits_ptr and, unless 0, the guide records at guide_ptr (48 bytes each, 16-byte aligned), 3 n float32 at
+        weight_ptr and n uint32 at path_ptr (no sync: nothing is read back; rays_ptr must stay valid until the stream has
+        drained)."""
+        params = mirror_params(max_bounces, min_reflective, chunk_rays)
+        capi.check(self._lib.rt_mirror_records_device(self._scene, C.byref(params), n, rows, C.c_void_p(rays_ptr),
+                                                      C.c_void_p(hits_ptr), C.c_void_p(guide_ptr or None),
+                                                      C.c_void_p(weight_ptr or None), C.c_void_p(path_ptr or None),
+                                                      C.c_void_p(stream)))
+
+    def mirror_info(self):
+        """The last mirror_records*() of this scene (include/rt_mirror.h, rt_mirror_info): rays, chunks, queries and the two
+        stage times."""
+        info = capi.RtMirrorInfo()
+        capi.check(self._lib.rt_get_mirror_info(self._scene, C.byref(info)))
+        return info
+
+    def _mirror_device(self, W, H, x0, x1, mirrors, stream):
+        """the four outputs of the pixel rays of columns [x0, x1) as torch tensors on the device (records as 12 int32 words),
+        enqueued on `stream`: rt_lens_rays_device at one sample, aperture 0, focus 1 -- rt_render's own pixel rays -- and
+        rt_mirror_records_device (rows = H); mirrors: a dict of max_bounces and min_reflective"""
+        import torch
+        unknown = set(mirrors) - {"max_bounces", "min_reflective"}
+        if unknown:
+            raise ValueError(f"mirrors takes max_bounces and min_reflective, not {sorted(unknown)}")
+        n = max(x1 - x0, 0) * H
+        lens = lens_params(1, 0.0, 1.0, 0)
+        rays = torch.empty((n * 6,), dtype=torch.float32, device="cuda")
+        hits = torch.empty((n * 12,), dtype=torch.int32, device="cuda")
+        guide = torch.empty((n * 12,), dtype=torch.int32, device="cuda")
+        weight = torch.empty((n, 3), dtype=torch.float32, device="cuda")
+        path = torch.empty((n,), dtype=torch.int32, device="cuda")
+        capi.check(self._lib.rt_lens_rays_device(self._cam, W, H, x0, x1, C.byref(lens), int(self._device), rays.data_ptr(),
+                                                 stream.cuda_stream))
+        self.mirror_records_device(n, max(H, 1), rays.data_ptr(), hits.data_ptr(), guide.data_ptr(), weight.data_ptr(),
+                                   path.data_ptr(), stream.cuda_stream, **mirrors)
+        return hits, guide, weight, path                               # (rays: torch frees them in the stream's order)
+
+    def render_gbuffer_mirrored(self, W, H, max_depth, max_bounces=8, min_reflective=1.0, x0=0, x1=None):
+        """Columns [x0, x1) of a W x H frame with what each pixel sees through the mirrors (include/rt_mirror.h):
+        render_gbuffer()'s colours, and mirror_records()'s four outputs for the pixel rays that lens_rays(camera, W, H,
+        samples=1, aperture=0, focus=1) makes, generated and walked on the device with no host wait between the calls ->
+        (rgb float32 (Wn, H, 3), hits HIT_DTYPE (Wn, H), guide HIT_DTYPE (Wn, H), weight float32 (Wn, H, 3), path uint32
+        (Wn, H)).  Where no mirror was followed (path & 0xff == 0) hits is render_gbuffer()'s record.  The device buffers and
+        the stream are torch's, so the process must have imported torch before the library was loaded."""
+        import torch
+        x1 = W if x1 is None else x1
+        Wn = max(x1 - x0, 0)
+        with torch.cuda.device(int(self._device)):
+            colours = torch.empty((Wn, H, 3), dtype=torch.float32, device="cuda")
+            records = torch.empty((Wn * H * 12,), dtype=torch.int32, device="cuda")
+            stream = torch.cuda.current_stream()
+            self.render_gbuffer_device(W, H, max_depth, x0, x1, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
+            hits, guide, weight, path = self._mirror_device(W, H, x0, x1, dict(max_bounces=max_bounces,
+                                                                              min_reflective=min_reflective), stream)
+            return (colours.cpu().numpy(), hits.cpu().numpy().view(HIT_DTYPE).reshape(Wn, H),
+                    guide.cpu().numpy().view(HIT_DTYPE).reshape(Wn, H), weight.cpu().numpy().reshape(Wn, H, 3),
+                    path.cpu().numpy().view(np.uint32).reshape(Wn, H))
+
+    def _render_indirect_mirrored(self, W, H, max_depth, kw, mirrors):
+        """render_indirect(mirrors=...): rgb + weight * indirect_diffuse(terminal records), one fp32 multiply and one fp32 add"""
+        import torch
+        with torch.cuda.device(int(self._device)):
+            colours = torch.empty((W * H, 3), dtype=torch.float32, device="cuda")
+            records = torch.empty((W * H * 12,), dtype=torch.int32, device="cuda")
+            term = torch.empty((W * H, 3), dtype=torch.float32, device="cuda")
+            stream = torch.cuda.current_stream()
+            self.render_gbuffer_device(W, H, max_depth, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
+            hits, _, weight, _ = self._mirror_device(W, H, 0, W, mirrors, stream)
+            self.indirect_diffuse_device(W * H, hits.data_ptr(), 0, term.data_ptr(), stream.cuda_stream, **kw)
+            return torch.add(colours, torch.mul(weight, term)).cpu().numpy().reshape(W, H, 3)       # the one download
+
+    def _render_ao_mirrored(self, W, H, params, mirrors):
+        """render_ao(mirrors=...): ambient_occlusion(terminal records); an open fraction is no radiance and takes no weight"""
+        import torch
+        C_ = 3 if params.channels == 3 else 1
+        with torch.cuda.device(int(self._device)):
+            plane = torch.empty((W, H, C_), dtype=torch.float32, device="cuda")
+            stream = torch.cuda.current_stream()
+            hits, _, _, _ = self._mirror_device(W, H, 0, W, mirrors, stream)
+            capi.check(self._lib.rt_ambient_occlusion_device(self._scene, C.byref(params), W * H, H, hits.data_ptr(),
+                                                             plane.data_ptr(), stream.cuda_stream))
+            out = plane.cpu().numpy()                                 # the one download
+        return out if C_ == 3 else out.reshape(W, H)
+
+    def _accumulated_term_mirrored(self, W, H, term, samples, k, kw, mirrors, colours, plane, stream):
+        """render_accumulated(mirrors=...): frame k's value from its colours, gathered at the terminal records -> (value, the
+        guide records)"""
+        import torch
+        hits, guide, weight, _ = self._mirror_device(W, H, 0, W, mirrors, stream)
+        if term == "indirect":
+            gathered = torch.empty((W * H, 3), dtype=torch.float32, device="cuda")
+            self.indirect_diffuse_device(W * H, hits.data_ptr(), 0, gathered.data_ptr(), stream.cuda_stream, samples=samples, seed=k,
+                                         **kw)
+            return torch.add(colours.view(W * H, 3), torch.mul(weight, gathered)).reshape(-1), guide
+        if term == "ao":
+            self.ambient_occlusion_device(W * H, H, hits.data_ptr(), plane.data_ptr(), samples=samples, seed=k,
+                                          stream=stream.cuda_stream, **kw)
+            return plane, guide
+        return colours, guide
+
+    def render_accumulated(self, cameras, W, H, max_depth, term="indirect", samples=1, filter=None, mirrors=None, **kw):
         """A sequence of W x H frames, one per camera of `cameras` (RtCameraDesc), accumulated on the GPU where they were made
         (include/rt_temporal.h): frame k is the G-buffer at max_depth and its term sampled with seed k -- "indirect": the
         colours plus indirect_diffuse(hits, samples, seed=k, base=rgb); "ao": ambient_occlusion(hits, samples, seed=k), one
@@ -1041,7 +1185,10 @@ class Renderer:
         temporal_params()'s keywords (but channels) for the history, every other one for the term.  -> the last frame's (value,
         variance, flags), what temporal_accumulate() over the public calls' frames gives bit for bit.  filter: None, or a dict of
         svgf_params()'s keywords (but channels): the last frame goes through the variance-steered filter on the same stream
-        (include/rt_svgf.h) and value and variance are the filtered ones, svgf_filter()'s of that frame bit for bit."""
+        (include/rt_svgf.h) and value and variance are the filtered ones, svgf_filter()'s of that frame bit for bit.
+        mirrors: None, or a dict of max_bounces and min_reflective (include/rt_mirror.h): the term is gathered at the terminal
+        records of the pixel rays ("indirect": weighted as render_indirect(mirrors=...) does) and the history and the filter
+        are given the guide records in place of the G-buffer's."""
         import torch
         if term not in ("indirect", "ao", "direct"):
             raise ValueError(f'term must be "indirect", "ao" or "direct", not {term!r}')
@@ -1062,6 +1209,10 @@ class Renderer:
                     if term == "direct":
                         self.set_shadow_seed(k)
                     self.render_gbuffer_device(W, H, max_depth, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
+                    if mirrors is not None:
+                        value, guide = self._accumulated_term_mirrored(W, H, term, samples, k, kw, mirrors, colours, plane, stream)
+                        value, variance, flags = history.push_device(value, guide, camera, stream=stream)
+                        continue
                     if term == "indirect":
                         self.indirect_diffuse_device(W * H, records.data_ptr(), colours.data_ptr(), colours.data_ptr(),
                                                      stream.cuda_stream, samples=samples, seed=k, **kw)
