@@ -82,7 +82,7 @@
  * rt_get_launch_info() describes the call's last one (a *_hits kernel).  The handle's lock is held for the whole call.
  * Speed-only options (rt_capi_tuning.h) apply as for rt_intersect_rays.
  *
- * Not provided: compaction of finished rays (it needs a read-back); glass; more than one terminal per pixel (a half-mirror is
+ * Not provided: compaction of finished rays (it needs a read-back: rt_mirror_compact.h has it, as calls of its own); glass; more than one terminal per pixel (a half-mirror is
  * either followed or not: that is min_reflective's job); several GPUs; the counting build; a command-line flag.  Buffers past
  * 2^32 bytes: untested.
  *

@@ -153,6 +153,15 @@ class RtMirrorInfo(C.Structure):
                 ("step_ms", C.c_double)]
 
 
+class RtMirrorCompactInfo(C.Structure):
+    """include/rt_mirror_compact.h: the scene's last rt_mirror_records_compact* call -- its rays, the rays its queries were
+    asked (the sum of alive), chunks, hit queries launched, stream waits made, the two stages' HIP-event times, and alive[b], the
+    rays whose chain reached query b."""
+    _fields_ = [("rays", C.c_int64), ("rays_queried", C.c_int64), ("chunks", C.c_int32), ("queries", C.c_int32),
+                ("syncs", C.c_int32), ("reserved", C.c_int32), ("query_ms", C.c_double), ("step_ms", C.c_double),
+                ("alive", C.c_int64 * (RT_MIRROR_MAX_BOUNCES + 1))]
+
+
 RT_TRANSFER_SRGB, RT_TRANSFER_LINEAR, RT_TRANSFER_CUSTOM = 0, 1, 2
 
 
@@ -390,6 +399,14 @@ def load_library():
         lib.rt_mirror_records_device.argtypes = [vp, C.POINTER(RtMirrorParams), i, i, vp, vp, vp, vp, vp, vp]
         lib.rt_get_mirror_info.argtypes = [vp, C.POINTER(RtMirrorInfo)]
         lib.rt_mirror_records.restype = lib.rt_mirror_records_device.restype = lib.rt_get_mirror_info.restype = i
+    # include/rt_mirror_compact.h (likewise)
+    if hasattr(lib, "rt_mirror_records_compact"):
+        lib.rt_mirror_compact_version.restype = i
+        lib.rt_mirror_records_compact.argtypes = [vp, C.POINTER(RtMirrorParams), i, i, vp, vp, vp, vp, vp]
+        lib.rt_mirror_records_compact_device.argtypes = [vp, C.POINTER(RtMirrorParams), i, i, vp, vp, vp, vp, vp, vp]
+        lib.rt_get_mirror_compact_info.argtypes = [vp, C.POINTER(RtMirrorCompactInfo)]
+        lib.rt_mirror_records_compact.restype = lib.rt_mirror_records_compact_device.restype = i
+        lib.rt_get_mirror_compact_info.restype = i
     # include/rt_capi_upsample.h (likewise absent from older builds)
     if hasattr(lib, "rt_upsample_guided"):
         lib.rt_capi_upsample_version.restype = i

@@ -25,6 +25,7 @@
 
 #include "../../include/rt_mirror.h"
 #include "rt_host.h"
+#include "rt_mirror_body.h"
 
 #pragma clang fp contract(off)
 
@@ -39,147 +40,18 @@ static_assert(sizeof(rt_hit) == 48, "rt_capi_query.h layout");
 
 namespace {
 
-constexpr int kBlock = 256;                            /* rays a workgroup */
+constexpr int kBlock = kMirrorBlock;                   /* rays a workgroup */
 constexpr size_t kChunkBytes = (size_t)256 << 20;      /* the default chunk: its scratch within 256 MiB */
-constexpr double kMaxRayFloats = 2.0e9 * 4.0;          /* rt_render's limit for one output, in floats */
-constexpr long long kMaxCells = 0x7fffffffLL - 64;     /* rt_trace_rays' grid limit (include/rt_capi_rays.h) */
 constexpr int kStateWords = 14;                        /* a ray's state: the word, w, L, A -- each a plane of the chunk */
 constexpr int kStateWordsNoGuide = 4;                  /* without a guide: the word and w */
 constexpr size_t kRayBytes = 48 + 24 + 4 * kStateWords;   /* a ray's scratch: its record, its next ray, its state */
-constexpr uint32_t kDone = 1u << 9;                    /* the state word is out_path's (k | cut << 8 | tag << 12) and this */
-constexpr int kLdsStride = 13;                         /* STAGE: a record's 12 words in LDS, odd stride */
-/* How the step kernel reads its 48-byte-strided records.  false: three 16-byte loads a lane.  true: the workgroup's records as
+/* How the step kernel (rt_mirror_body.h's, which rt_mirror_compact.hip instantiates as well; here in place, COMPACT false)
+ * reads its 48-byte-strided records.  false: three 16-byte loads a lane.  true: the workgroup's records as
  * the consecutive words they are through LDS (rt_accumulate_body.h's and rt_upsample.hip's way).  Both were measured
  * (profiles/mirror_experiments.txt); this is the one kept. */
 constexpr bool kStageLds = false;
 
 } // namespace
-
-/* the 32-bit integer hash "lowbias32" (include/rt_capi_ao.h) */
-__device__ __forceinline__ uint32_t rt_mirror_hash(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ float rt_mirror_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return (ax * bx + ay * by) + az * bz;
-}
-
-/* normalize(T - E) of the ray at r[0..5], createEyeRay's arithmetic */
-__device__ __forceinline__ void rt_mirror_direction(const float *r, float *dx, float *dy, float *dz) {
-    const float x = r[3] - r[0], y = r[4] - r[1], z = r[5] - r[2];
-    const float len = sqrtf((x * x + y * y) + z * z);
-    *dx = x / len, *dy = y / len, *dz = z / len;
-}
-
-/* Bounce s of the m rays of a chunk, one lane a ray (i < m < 2^31).  records[3 i ..] is the record of ray_s, rays_k[6 i ..] is
- * ray_s itself (FIRST: the caller's rays; later the chunk's scratch, which rays_next then is as well: a lane reads its own
- * ray before it writes it), rays0 the caller's rays, state the chunk's planes of `stride` words (kStateWords of them with
- * GUIDE, else kStateWordsNoGuide).  FIRST: s == 0, the starting state is the header's and no state is read.  last: s ==
- * max_bounces, every ray still alive ends here.  GUIDE: out_guide is given, so L and A are carried.  STAGE: kStageLds.  Every
- * address is i's own (STAGE: or one of the workgroup's records, below records[3 m]): nothing is read or written past ray m - 1. */
-template <bool FIRST, bool GUIDE, bool STAGE>
-__global__ __launch_bounds__(kBlock) void rt_mirror_step_kernel(uint32_t m, uint32_t stride, int last, float min_reflective,
-                                                                const float *__restrict__ rf, int n_objects,
-                                                                const float4 *__restrict__ records, const float *rays_k,
-                                                                const float *__restrict__ rays0, float *rays_next, uint32_t *state,
-                                                                float4 *__restrict__ out_hits, float4 *__restrict__ out_guide,
-                                                                float *__restrict__ out_weight, uint32_t *__restrict__ out_path) {
-    const uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
-    __shared__ float lds[STAGE ? kBlock * kLdsStride : 1];
-    if (STAGE) {
-        const uint32_t base = blockIdx.x * (uint32_t)kBlock;                 /* (base < m: the grid is ceil(m / kBlock)) */
-        const uint32_t words = min((uint32_t)kBlock, m - base) * 12u;
-        const float *src = reinterpret_cast<const float *>(records) + (size_t)base * 12;
-        for (uint32_t t = threadIdx.x; t < words; t += (uint32_t)kBlock) {
-            const uint32_t rec = t / 12u;
-            lds[rec * kLdsStride + (t - rec * 12u)] = src[t];
-        }
-        __syncthreads();
-    }
-    if (i >= m) return;
-    const uint32_t word = FIRST ? 0u : state[i];
-    if (word & kDone) return;
-    float4 q0, q1, q2;
-    if (STAGE) {
-        const float *q = lds + threadIdx.x * kLdsStride;
-        q0 = make_float4(q[0], q[1], q[2], q[3]), q1 = make_float4(q[4], q[5], q[6], q[7]), q2 = make_float4(q[8], q[9], q[10], q[11]);
-    } else {
-        q0 = records[3 * (size_t)i], q1 = records[3 * (size_t)i + 1], q2 = records[3 * (size_t)i + 2];
-    }
-    const int32_t object = __float_as_int(q0.x), flags = __float_as_int(q2.w);
-    const uint32_t k = word & 0xffu, tag = word >> 12;
-    float wx = 1.0f, wy = 1.0f, wz = 1.0f, L = 0.0f;
-    float A[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
-    if (!FIRST) {
-        wx = __uint_as_float(state[(size_t)stride + i]);
-        wy = __uint_as_float(state[2 * (size_t)stride + i]);
-        wz = __uint_as_float(state[3 * (size_t)stride + i]);
-        if (GUIDE) {
-            L = __uint_as_float(state[4 * (size_t)stride + i]);
-#pragma unroll
-            for (int c = 0; c < 9; ++c) A[c] = __uint_as_float(state[(size_t)(5 + c) * stride + i]);
-        }
-    }
-    if (GUIDE && object >= 0) L = L + q0.y;
-    const float refl = (object >= 0 && object < n_objects) ? rf[object] : 0.0f;
-    const bool mirror = object >= 0 && object < n_objects && (flags & RT_HIT_LIGHT) == 0 && refl >= min_reflective;
-    const float Px = q0.z, Py = q0.w, Pz = q1.x, nx = q1.y, ny = q1.z, nz = q1.w;
-
-    if (!mirror || last) {                                                    /* the terminal record */
-        out_hits[3 * (size_t)i] = q0, out_hits[3 * (size_t)i + 1] = q1, out_hits[3 * (size_t)i + 2] = q2;
-        if (out_weight) {
-            float *o = out_weight + 3 * (size_t)i;
-            o[0] = wx, o[1] = wy, o[2] = wz;
-        }
-        if (out_path) out_path[i] = k | (mirror ? 1u << 8 : 0u) | tag << 12;
-        if (GUIDE) {
-            float4 g0 = q0, g1 = q1;
-            if (!FIRST && object >= 0 && k != 0u) {
-                const float *e = rays0 + 6 * (size_t)i;
-                float dx, dy, dz;
-                rt_mirror_direction(e, &dx, &dy, &dz);
-                g0.x = __int_as_float((int32_t)(tag << 12 | (uint32_t)object));
-                g0.y = L;
-                g0.z = e[0] + dx * L, g0.w = e[1] + dy * L, g1.x = e[2] + dz * L;
-                g1.y = rt_mirror_dot(A[0], A[1], A[2], nx, ny, nz);
-                g1.z = rt_mirror_dot(A[3], A[4], A[5], nx, ny, nz);
-                g1.w = rt_mirror_dot(A[6], A[7], A[8], nx, ny, nz);
-            }
-            out_guide[3 * (size_t)i] = g0, out_guide[3 * (size_t)i + 1] = g1, out_guide[3 * (size_t)i + 2] = q2;
-        }
-        if (!last) {                                                          /* retired: a degenerate ray from here on */
-            float *o = rays_next + 6 * (size_t)i;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) o[c] = 0.0f;
-            state[i] = kDone;
-        }
-        return;
-    }
-
-    float dx, dy, dz;
-    rt_mirror_direction(rays_k + 6 * (size_t)i, &dx, &dy, &dz);
-    const float c = rt_mirror_dot(nx, ny, nz, dx, dy, dz);
-    const float rx = ((-2.0f * nx) * c) + dx, ry = ((-2.0f * ny) * c) + dy, rz = ((-2.0f * nz) * c) + dz;
-    float *o = rays_next + 6 * (size_t)i;
-    o[0] = Px, o[1] = Py, o[2] = Pz;
-    o[3] = Px + rx, o[4] = Py + ry, o[5] = Pz + rz;
-    state[i] = (k + 1u) | (1u + rt_mirror_hash(tag << 12 | (uint32_t)object) % 0x7fffeu) << 12;
-    state[(size_t)stride + i] = __float_as_uint(wx * (refl * q2.x));
-    state[2 * (size_t)stride + i] = __float_as_uint(wy * (refl * q2.y));
-    state[3 * (size_t)stride + i] = __float_as_uint(wz * (refl * q2.z));
-    if (GUIDE) {
-        state[4 * (size_t)stride + i] = __float_as_uint(L);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const float an = rt_mirror_dot(A[3 * r], A[3 * r + 1], A[3 * r + 2], nx, ny, nz);
-            const float two = 2.0f * an;
-            state[(size_t)(5 + 3 * r) * stride + i] = __float_as_uint(A[3 * r] - two * nx);
-            state[(size_t)(6 + 3 * r) * stride + i] = __float_as_uint(A[3 * r + 1] - two * ny);
-            state[(size_t)(7 + 3 * r) * stride + i] = __float_as_uint(A[3 * r + 2] - two * nz);
-        }
-    }
-}
 
 namespace {
 
@@ -191,31 +63,10 @@ struct RtMirrorState {
     ~RtMirrorState() { clock.release(); }
 };
 
-/* the header's checks (1) .. (10) */
+/* the header's checks (1) .. (10): rt_mirror_body.h's, which rt_mirror_compact.hip makes as well */
 int check_args(const rt_scene *s, const rt_mirror_params *pr, int n, int rows, const void *rays, const void *out_hits,
                const void *out_guide, const void *out_weight, const void *out_path, bool device) {
-    if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
-    if (!pr) return fail(RT_ERR_INVALID, "params is NULL");
-    if (pr->max_bounces < 0 || pr->max_bounces > RT_MIRROR_MAX_BOUNCES)
-        return fail(RT_ERR_INVALID, "max_bounces must be 0.." + std::to_string(RT_MIRROR_MAX_BOUNCES) + " (got " +
-                                        std::to_string(pr->max_bounces) + ")");
-    if (pr->chunk_rays < 0) return fail(RT_ERR_INVALID, "chunk_rays must not be negative");
-    if (std::isnan(pr->min_reflective)) return fail(RT_ERR_INVALID, "min_reflective must not be NaN");
-    if (n < 0) return fail(RT_ERR_INVALID, "n < 0");
-    if (rows < 1) return fail(RT_ERR_INVALID, "rows must be positive");
-    if (n > 0 && !rays) return fail(RT_ERR_INVALID, "rays pointer is NULL");
-    if (n > 0 && !out_hits) return fail(RT_ERR_INVALID, "out_hits pointer is NULL");
-    /* rt_trace_rays' limit (rays_args() of rt_capi.hip): the batch's floats, and the cells of its grid of rows */
-    const int r = std::min(rows, std::max(n, 1));
-    if ((double)n * 3.0 > kMaxRayFloats || (((long long)n + r - 1) / r) * r > kMaxCells)
-        return fail(RT_ERR_INVALID, "ray batch too large for its rows");
-    if (!device) return RT_OK;
-    if (((uintptr_t)rays & 3u) != 0) return fail(RT_ERR_INVALID, "d_rays must be 4-byte aligned");
-    if (((uintptr_t)out_hits & 15u) != 0) return fail(RT_ERR_INVALID, "d_out_hits must be 16-byte aligned");
-    if (((uintptr_t)out_guide & 15u) != 0) return fail(RT_ERR_INVALID, "d_out_guide must be 16-byte aligned");
-    if (((uintptr_t)out_weight & 3u) != 0) return fail(RT_ERR_INVALID, "d_out_weight must be 4-byte aligned");
-    if (((uintptr_t)out_path & 3u) != 0) return fail(RT_ERR_INVALID, "d_out_path must be 4-byte aligned");
-    return RT_OK;
+    return rt_mirror_check_args(s, pr, n, rows, rays, out_hits, out_guide, out_weight, out_path, device);
 }
 
 /* the rays a launch walks: the caller's chunk_rays, or the default -- as many as keep the scratch within kChunkBytes -- never
@@ -262,11 +113,11 @@ void launch_step(uint32_t m, uint32_t stride, int last, float min_reflective, co
         return launch_step<FIRST, GUIDE, !kStageLds>(m, stride, last, min_reflective, rf, n_objects, records, rays_k, rays0, rays_next,
                                                      state, out_hits, out_guide, out_weight, out_path, stream);
 #endif
-    hipLaunchKernelGGL((rt_mirror_step_kernel<FIRST, GUIDE, STAGE>), dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, m, stride,
+    hipLaunchKernelGGL((rt_mirror_step_kernel<FIRST, GUIDE, STAGE, false>), dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, m, stride,
                        last, min_reflective, rf, n_objects, static_cast<const float4 *>(records), static_cast<const float *>(rays_k),
                        static_cast<const float *>(rays0), static_cast<float *>(rays_next), static_cast<uint32_t *>(state),
                        static_cast<float4 *>(out_hits), static_cast<float4 *>(out_guide), static_cast<float *>(out_weight),
-                       static_cast<uint32_t *>(out_path));
+                       static_cast<uint32_t *>(out_path), nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 /* the call, every argument checked, the handle locked, n > 0: device memory, on stream.  The events of the call before are

@@ -809,8 +809,8 @@ class Renderer:
         section 3).  scale 2..8 (include/rt_capi_upsample.h): the plane is gathered for every scale-th pixel in both directions
         and upsampled, rt_subsample_hits_device, rt_ambient_occlusion_device and rt_upsample_guided_device on that one stream
         with no host wait -- ambient_occlusion_scaled(render_gbuffer(W, H, 0)[1], scale, ...) bit for bit; refine costs exactly
-        one read-back of the flags before the holes' batch is enqueued.  mirrors: None, or a dict of max_bounces and
-        min_reflective (include/rt_mirror.h; scale 1 only): the plane is gathered at the terminal records of the pixel rays,
+        one read-back of the flags before the holes' batch is enqueued.  mirrors: None, or a dict of max_bounces,
+        min_reflective and optionally compact (include/rt_mirror.h, rt_mirror_compact.h; scale 1 only): the plane is gathered at the terminal records of the pixel rays,
         ambient_occlusion(render_gbuffer_mirrored(W, H, 0, ...)[1], ...) bit for bit -- an open fraction takes no weight."""
         import torch
         if mirrors is not None:
@@ -1014,7 +1014,8 @@ class Renderer:
         -- indirect_diffuse_scaled(hits, scale, ..., base=rgb) bit for bit, and with denoise rgb + denoise(
         indirect_diffuse_scaled(hits, scale, ...), hits, ...); refine costs exactly one read-back of the flags before the holes'
         batch is enqueued.  With scale 1 nothing of this runs and normal_squarings, sigma_plane and refine are not read.
-        mirrors: None, or a dict of max_bounces and min_reflective (include/rt_mirror.h; scale 1 and no denoise only): the term
+        mirrors: None, or a dict of max_bounces, min_reflective and optionally compact (include/rt_mirror.h, rt_mirror_compact.h;
+        scale 1 and no denoise only): the term
         is gathered at the terminal records of the pixel rays and multiplied by the path's weight before it is added -- with
         (_, hits, _, weight, _) = render_gbuffer_mirrored(W, H, max_depth, ...), rgb + weight * indirect_diffuse(hits, ...), one
         fp32 multiply and one fp32 add, bit for bit."""
@@ -1053,14 +1054,17 @@ class Renderer:
 
     MIRROR_OUTPUTS = ("guide", "weight", "path")
 
-    def mirror_records(self, rays, max_bounces=8, min_reflective=1.0, rows=None, chunk_rays=0, outputs=MIRROR_OUTPUTS):
+    def mirror_records(self, rays, max_bounces=8, min_reflective=1.0, rows=None, chunk_rays=0, outputs=MIRROR_OUTPUTS,
+                       compact=False):
         """What each ray sees through the scene's mirrors (include/rt_mirror.h, rt_mirror_records).  rays as intersect_rays'
         (float32 (n, 6) or (X, Z, 6)); a hit is followed while its object's `reflective` >= min_reflective, max_bounces times
         at the most.  -> (hits, guide, weight, path): the terminal records and the guide records (HIT_DTYPE, rays' shape), the
         path's throughput (float32, shape + (3,)) and the path word (uint32: k | cut << 8 | tag << 12).  hits is what
         ambient_occlusion() and indirect_diffuse() gather at; guide is what the filters and the accumulation are steered by --
         its object is a tagged id, never an index.  outputs: which of the three optional ones are asked for; the others are
-        None and what is returned does not depend on them.  rows and chunk_rays never change a result."""
+        None and what is returned does not depend on them.  rows and chunk_rays never change a result.  compact: walk only
+        the rays still alive (include/rt_mirror_compact.h, rt_mirror_records_compact): the same words, fewer rays queried, one
+        host wait per bounce; mirror_compact_info() then describes the call, and mirror_info() does not."""
         n, default_rows = self._batch(rays, "rays")
         shape = rays.shape[:-1]
         hits = np.zeros(shape, dtype=HIT_DTYPE)
@@ -1069,21 +1073,24 @@ class Renderer:
         path = np.zeros(shape, dtype=np.uint32) if "path" in outputs else None
         params = mirror_params(max_bounces, min_reflective, chunk_rays)
         ptr = lambda a: a.ctypes.data if a is not None else None
-        capi.check(self._lib.rt_mirror_records(self._scene, C.byref(params), n, int(default_rows if rows is None else rows),
-                                               rays.ctypes.data, hits.ctypes.data, ptr(guide), ptr(weight), ptr(path)))
+        call = self._lib.rt_mirror_records_compact if compact else self._lib.rt_mirror_records
+        capi.check(call(self._scene, C.byref(params), n, int(default_rows if rows is None else rows), rays.ctypes.data,
+                        hits.ctypes.data, ptr(guide), ptr(weight), ptr(path)))
         return hits, guide, weight, path
 
     def mirror_records_device(self, n, rows, rays_ptr, hits_ptr, guide_ptr=0, weight_ptr=0, path_ptr=0, stream=0, max_bounces=8,
-                              min_reflective=1.0, chunk_rays=0):
+                              min_reflective=1.0, chunk_rays=0, compact=False):
         """Enqueue the mirror chains of n rays (6 float32 each) at device address rays_ptr on a HIP stream: the terminal
         records at hits_ptr and, unless 0, the guide records at guide_ptr (48 bytes each, 16-byte aligned), 3 n float32 at
         weight_ptr and n uint32 at path_ptr (no sync: nothing is read back; rays_ptr must stay valid until the stream has
-        drained)."""
+        drained).  compact: rt_mirror_records_compact_device (include/rt_mirror_compact.h) -- the same words over the rays still
+        alive; it WAITS for the stream once per bounce, so the stream must not be capturing, and returns with its last step
+        possibly still running."""
         params = mirror_params(max_bounces, min_reflective, chunk_rays)
-        capi.check(self._lib.rt_mirror_records_device(self._scene, C.byref(params), n, rows, C.c_void_p(rays_ptr),
-                                                      C.c_void_p(hits_ptr), C.c_void_p(guide_ptr or None),
-                                                      C.c_void_p(weight_ptr or None), C.c_void_p(path_ptr or None),
-                                                      C.c_void_p(stream)))
+        call = self._lib.rt_mirror_records_compact_device if compact else self._lib.rt_mirror_records_device
+        capi.check(call(self._scene, C.byref(params), n, rows, C.c_void_p(rays_ptr), C.c_void_p(hits_ptr),
+                        C.c_void_p(guide_ptr or None), C.c_void_p(weight_ptr or None), C.c_void_p(path_ptr or None),
+                        C.c_void_p(stream)))
 
     def mirror_info(self):
         """The last mirror_records*() of this scene (include/rt_mirror.h, rt_mirror_info): rays, chunks, queries and the two
@@ -1092,14 +1099,22 @@ class Renderer:
         capi.check(self._lib.rt_get_mirror_info(self._scene, C.byref(info)))
         return info
 
+    def mirror_compact_info(self):
+        """The last mirror_records*(compact=True) of this scene (include/rt_mirror_compact.h, rt_mirror_compact_info): rays,
+        rays_queried, chunks, queries, syncs, the two stage times and alive[b]."""
+        info = capi.RtMirrorCompactInfo()
+        capi.check(self._lib.rt_get_mirror_compact_info(self._scene, C.byref(info)))
+        return info
+
     def _mirror_device(self, W, H, x0, x1, mirrors, stream):
         """the four outputs of the pixel rays of columns [x0, x1) as torch tensors on the device (records as 12 int32 words),
         enqueued on `stream`: rt_lens_rays_device at one sample, aperture 0, focus 1 -- rt_render's own pixel rays -- and
-        rt_mirror_records_device (rows = H); mirrors: a dict of max_bounces and min_reflective"""
+        rt_mirror_records_device (rows = H); mirrors: a dict of max_bounces and min_reflective and, optionally, compact
+        (rt_mirror_records_compact_device in its place: the same words, with host waits)"""
         import torch
-        unknown = set(mirrors) - {"max_bounces", "min_reflective"}
+        unknown = set(mirrors) - {"max_bounces", "min_reflective", "compact"}
         if unknown:
-            raise ValueError(f"mirrors takes max_bounces and min_reflective, not {sorted(unknown)}")
+            raise ValueError(f"mirrors takes max_bounces, min_reflective and compact, not {sorted(unknown)}")
         n = max(x1 - x0, 0) * H
         lens = lens_params(1, 0.0, 1.0, 0)
         rays = torch.empty((n * 6,), dtype=torch.float32, device="cuda")
@@ -1113,13 +1128,15 @@ class Renderer:
                                    path.data_ptr(), stream.cuda_stream, **mirrors)
         return hits, guide, weight, path                               # (rays: torch frees them in the stream's order)
 
-    def render_gbuffer_mirrored(self, W, H, max_depth, max_bounces=8, min_reflective=1.0, x0=0, x1=None):
+    def render_gbuffer_mirrored(self, W, H, max_depth, max_bounces=8, min_reflective=1.0, x0=0, x1=None, compact=False):
         """Columns [x0, x1) of a W x H frame with what each pixel sees through the mirrors (include/rt_mirror.h):
         render_gbuffer()'s colours, and mirror_records()'s four outputs for the pixel rays that lens_rays(camera, W, H,
         samples=1, aperture=0, focus=1) makes, generated and walked on the device with no host wait between the calls ->
         (rgb float32 (Wn, H, 3), hits HIT_DTYPE (Wn, H), guide HIT_DTYPE (Wn, H), weight float32 (Wn, H, 3), path uint32
         (Wn, H)).  Where no mirror was followed (path & 0xff == 0) hits is render_gbuffer()'s record.  The device buffers and
-        the stream are torch's, so the process must have imported torch before the library was loaded."""
+        the stream are torch's, so the process must have imported torch before the library was loaded.  compact: the chains
+        are walked by rt_mirror_records_compact_device (include/rt_mirror_compact.h): the same words, with one host wait per
+        bounce between the calls."""
         import torch
         x1 = W if x1 is None else x1
         Wn = max(x1 - x0, 0)
@@ -1128,8 +1145,8 @@ class Renderer:
             records = torch.empty((Wn * H * 12,), dtype=torch.int32, device="cuda")
             stream = torch.cuda.current_stream()
             self.render_gbuffer_device(W, H, max_depth, x0, x1, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
-            hits, guide, weight, path = self._mirror_device(W, H, x0, x1, dict(max_bounces=max_bounces,
-                                                                              min_reflective=min_reflective), stream)
+            hits, guide, weight, path = self._mirror_device(W, H, x0, x1, dict(max_bounces=max_bounces, min_reflective=min_reflective,
+                                                                              compact=compact), stream)
             return (colours.cpu().numpy(), hits.cpu().numpy().view(HIT_DTYPE).reshape(Wn, H),
                     guide.cpu().numpy().view(HIT_DTYPE).reshape(Wn, H), weight.cpu().numpy().reshape(Wn, H, 3),
                     path.cpu().numpy().view(np.uint32).reshape(Wn, H))
@@ -1186,7 +1203,7 @@ class Renderer:
         variance, flags), what temporal_accumulate() over the public calls' frames gives bit for bit.  filter: None, or a dict of
         svgf_params()'s keywords (but channels): the last frame goes through the variance-steered filter on the same stream
         (include/rt_svgf.h) and value and variance are the filtered ones, svgf_filter()'s of that frame bit for bit.
-        mirrors: None, or a dict of max_bounces and min_reflective (include/rt_mirror.h): the term is gathered at the terminal
+        mirrors: None, or a dict of max_bounces, min_reflective and optionally compact (include/rt_mirror.h, rt_mirror_compact.h): the term is gathered at the terminal
         records of the pixel rays ("indirect": weighted as render_indirect(mirrors=...) does) and the history and the filter
         are given the guide records in place of the G-buffer's."""
         import torch
