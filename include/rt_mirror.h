@@ -83,8 +83,14 @@
  * Speed-only options (rt_capi_tuning.h) apply as for rt_intersect_rays.
  *
  * Not provided: compaction of finished rays (it needs a read-back: rt_mirror_compact.h has it, as calls of its own); glass; more than one terminal per pixel (a half-mirror is
- * either followed or not: that is min_reflective's job); several GPUs; the counting build; a command-line flag.  Buffers past
- * 2^32 bytes: untested.
+ * either followed or not: that is min_reflective's job); several GPUs; the counting build; a command-line flag.
+ *
+ * Buffers past 2^32 bytes: the device call is tested on 100 000 007 rays (tests/test_mirror_large_gpu.py) -- terminal and guide
+ * records of 4.8 GB each, every word compared; the default chunk, whose offsets into the outputs pass 2^32 bytes, and one
+ * chunk of 90 000 001 rays, whose records and state planes in the scratch pass 2^32 bytes.  Not tested, because no batch that
+ * fits a test's 48 GB of device memory reaches them: out_weight and out_path past 2^32 bytes (n > 357.9 million and n > 2^30);
+ * the element index 6 * ray of the rays past 2^32 (n > 715 827 882); the host variant past 2^32 bytes (it stages the batch and
+ * runs the device call's code).
  *
  * rt_mirror_params is 12 bytes; rt_mirror_info is 32 bytes: rays at 0, chunks at 8, queries at 12, query_ms at 16, step_ms
  * at 24.

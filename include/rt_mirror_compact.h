@@ -44,7 +44,16 @@
  * The handle's lock is held for the whole call.  Speed-only options (rt_capi_tuning.h) apply as for rt_intersect_rays.
  *
  * Not provided: a graph-capturable form; compaction across chunks; glass; several GPUs; the counting build; a command-line
- * flag.  Buffers past 2^32 bytes: untested.
+ * flag.
+ *
+ * Buffers past 2^32 bytes: the device call is tested on 100 000 007 rays (tests/test_mirror_large_gpu.py), every output word
+ * and the info's counts compared: with the default chunk, and with one chunk of 90 000 001 rays -- 19.5 GB of scratch, lists
+ * of 43.9 million entries whose ray indices address output bytes past 2^32 -- with and without out_guide and out_weight.  The
+ * scan is tested on its own up to 2^21 + 1537 counts, three trips of its second level (tests/test_mirror_compact_gpu.py).  Not
+ * tested, because no batch that fits a test's 48 GB of device memory reaches them: a list of more than 2^28 entries through
+ * the call (a chunk of 56 GB with its rays and records; the scan alone is covered); out_weight and out_path past 2^32 bytes
+ * (n > 357.9 million and n > 2^30); the element index 6 * ray of the rays past 2^32 (n > 715 827 882); the host variant past
+ * 2^32 bytes (it stages the batch and runs the device call's code).
  *
  * rt_mirror_compact_info is 568 bytes: rays at 0, rays_queried at 8, chunks at 16, queries at 20, syncs at 24, reserved at 28,
  * query_ms at 32, step_ms at 40, alive at 48.

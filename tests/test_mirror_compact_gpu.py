@@ -3,15 +3,19 @@ mirror_ref word for word AND against rt_mirror_records of the same handle -- the
 struct's counts (alive, rays_queried, queries, syncs, chunks) against the numbers the reference's path words give: over bounce
 limits up to 64, both reflectivity floors, lists whose sizes sit at the edges of a wavefront and a workgroup, more live rays than
 one step of the scan covers (kScanBlock * 256 = 262 144, the constants of csrc/rt_scan.h), chunks, rows, strips, absent
-outputs, a non-null stream into sentinel-filled guarded outputs, and the Renderer's composed calls.  Bar: BIT-EXACT."""
+outputs, a non-null stream into sentinel-filled guarded outputs, the Renderer's composed calls, the refusal of a batch too large
+for its rows, and the unit's scan on its own (rt_internal_mirror_compact_scan) up to three trips of its second level, which no
+batch that fits a device reaches through the call.  Bar: BIT-EXACT."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import large_extents as le
 import mirror_ref
 import mirror_scenes
 import poisoned
+from mirror_large import expected_info
 from tilecoderaytracer_amd import Renderer, capi
 from tilecoderaytracer_amd.renderer import HIT_DTYPE, mirror_params
 
@@ -50,21 +54,6 @@ def renderers():
 
 def rays_of(key, W, H):
     return np.array(mirror_scenes.pixel_rays(key, W, H), dtype=F, order="C")
-
-
-def expected_info(path, bounces, chunk=0):
-    """from the path words of a batch, in ray order: what rt_mirror_compact_info must say of a call that walks it in chunks of
-    `chunk` rays (0: one chunk) -> (rays, rays_queried, chunks, queries, syncs, alive[0 .. 64])"""
-    k = mirror_ref.unpack(np.asarray(path))[0].reshape(-1)
-    n = len(k)
-    chunk = chunk or n
-    alive, queries, syncs, chunks = [0] * 65, 0, 0, 0
-    for i0 in range(0, n, chunk):
-        mine = [int((k[i0:i0 + chunk] >= b).sum()) for b in range(bounces + 1)]
-        q = sum(1 for a in mine if a > 0)
-        queries, syncs, chunks = queries + q, syncs + q - (1 if q == bounces + 1 else 0), chunks + 1
-        alive = [a + m for a, m in zip(alive, mine + [0] * 65)]
-    return n, sum(alive), chunks, queries, syncs, alive
 
 
 def info_of(r):
@@ -318,3 +307,96 @@ def test_mirrors_compact_through_the_composed_renders(renderers):
     assert r.mirror_compact_info().rays == 45 * 38
     with pytest.raises(ValueError):
         r.render_indirect(W61, H37, 2, mirrors=dict(mirrors, compacted=True), **kw)
+
+
+# ---- 8. the size refusal ----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n", [2 ** 31 - 1, 2 ** 31 - 64])
+def test_a_batch_too_large_for_its_rows_is_refused_and_the_next_call_is_unharmed(renderers, n):
+    """rt_mirror.h's check (9)/(10) of the batch's size, "ray batch too large for its rows", with rows = 1: the largest int, and
+    2^31 - 64, one cell over rt_trace_rays' grid limit of 0x7fffffff - 64 cells.  The checks precede all device work, so aligned
+    dummy addresses are never read.  (The last admitted size, 2^31 - 65 rays, is 51 GB of rays alone and is not launched.)"""
+    r = renderers["room"]
+    rays = rays_of("room", W61, H37)
+    lib, p = capi.load_library(), mirror_params(3, 1.0)
+    dummy = 0x10000
+    assert n >= (0x7fffffff - 64) + 1 and n * 3.0 <= 8.0e9                    # the cells refuse it, not the floats
+    rc = lib.rt_mirror_records_compact_device(r._scene, C.byref(p), n, 1, C.c_void_p(dummy), C.c_void_p(dummy), None, None, None, None)
+    assert rc == capi.RT_ERR_INVALID and "ray batch too large for its rows" in lib.rt_last_error().decode()
+    rc = lib.rt_mirror_records_compact(r._scene, C.byref(p), n, 1, C.c_void_p(dummy), C.c_void_p(dummy), None, None, None)
+    assert rc == capi.RT_ERR_INVALID and "ray batch too large for its rows" in lib.rt_last_error().decode()
+    want = mirror_scenes.reference("room", W61, H37, 3, 1.0)[:4]
+    assert_all_same(r.mirror_records(rays, 3, 1.0, compact=True), want, "after a refusal")
+    assert info_of(r) == expected_info(want[3], 3)
+
+
+# ---- 9. the scan on its own, past what a batch that fits a device gives it -------------------------------------------------------
+
+SCAN_GROUP = 1024                                                             # kScanBlock of csrc/rt_scan.h
+SCAN_MOST = 256                                                               # kRankBlock: the most a workgroup can report
+SCAN_SIZES = [1, 63, 64, 1023, 1024, 1025, 1024 ** 2 - 1, 1024 ** 2, 1024 ** 2 + 1, 2 * 1024 ** 2 + 1537]
+
+
+def scan_counts(n, pattern):
+    if pattern == "all 256":
+        return np.full(n, SCAN_MOST, dtype=np.uint32)
+    if pattern == "a single 1 at the end":
+        c = np.zeros(n, dtype=np.uint32)
+        c[-1] = 1
+        return c
+    assert pattern == "random with runs"
+    rng = np.random.default_rng(n)
+    c = rng.integers(0, SCAN_MOST + 1, size=n).astype(np.uint32)
+    for value in (0, SCAN_MOST) * 6:                                          # runs longer than a group, so that whole groups sum
+        start = int(rng.integers(0, n))                                       # to 0 and to 1024 x 256, and shorter ones
+        c[start:start + int(rng.integers(1, 3 * SCAN_GROUP + 2))] = value
+    return c
+
+
+@pytest.mark.parametrize("pattern", ["all 256", "random with runs", "a single 1 at the end"])
+@pytest.mark.parametrize("n", SCAN_SIZES)
+def test_the_scan_on_its_own_up_to_three_trips_of_its_second_level(n, pattern):
+    """rt_internal_mirror_compact_scan (csrc/rt_internal.h) -- the function rt_mirror_records_compact enqueues its scan through --
+    against numpy in uint64.  More than 1024 groups (n > 1024^2 counts, more than 2^28 live rays of one chunk) take
+    rt_scan_total_kernel round its loop again: the carried base, the barrier that guards wave_sum between the trips, and
+    group_base past entry 1023, which no batch within a test's 48 GB reaches through the call.  Every output lies in a guarded,
+    sentinel-filled buffer of exactly its words; no sum here reaches the sentinel's value (the largest is 2^29 + 393 472)."""
+    import torch
+    lib = capi.load_library()
+    scan = lib.rt_internal_mirror_compact_scan
+    scan.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
+    scan.restype = C.c_int
+    groups = -(-n // SCAN_GROUP)
+    counts = scan_counts(n, pattern)
+    assert counts.max() <= SCAN_MOST and len(counts) == n
+    c64 = counts.astype(np.uint64)
+    assert int(c64.sum()) <= 2 ** 29 + 393472 < le.SENTINEL
+    padded = np.zeros(groups * SCAN_GROUP, dtype=np.uint64)
+    padded[:n] = c64
+    in_group = padded.reshape(groups, SCAN_GROUP)
+    want_offsets = (np.cumsum(in_group, axis=1) - in_group).reshape(-1)[:n]
+    want_sums = in_group.sum(axis=1)
+    want_base = np.cumsum(want_sums) - want_sums
+    before_all = np.cumsum(c64) - c64                                         # the global exclusive sum
+    d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
+    outs = [le.Guarded(n), le.Guarded(groups), le.Guarded(groups), le.Guarded(1)]
+    try:
+        stream = torch.cuda.Stream()
+        stream.wait_stream(torch.cuda.current_stream())
+        capi.check(scan(d_counts.data_ptr(), n, *[o.ptr for o in outs], stream.cuda_stream))
+        stream.synchronize()
+        what = f"the scan of {n} counts, {pattern}"
+        for o, name in zip(outs, ("offsets", "group_sums", "group_base", "total")):
+            o.assert_written(f"{what}: {name}")
+        offsets, sums, base, total = (o.body.cpu().numpy().view(np.uint32).astype(np.uint64) for o in outs)
+        assert np.array_equal(d_counts.cpu().numpy().view(np.uint32), counts), f"{what}: the counts changed"
+        for name, got, want in (("offsets", offsets, want_offsets), ("group_sums", sums, want_sums), ("group_base", base, want_base),
+                                ("total", total, c64.sum(keepdims=True))):
+            bad = np.flatnonzero(got != want)
+            assert len(bad) == 0, f"{what}: {len(bad)} of {name} differ, first at {bad[0]}: got {got[bad[0]]}, want {want[bad[0]]}"
+        place = base[np.arange(n) // SCAN_GROUP] + offsets                    # what the step kernel adds a lane's rank to
+        bad = np.flatnonzero(place != before_all)
+        assert len(bad) == 0, f"{what}: group_base[i // 1024] + offsets[i] is not the exclusive sum at {bad[0]}"
+    finally:
+        for o in outs:
+            o.free()

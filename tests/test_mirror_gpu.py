@@ -162,6 +162,25 @@ def test_device_entry_refuses_misaligned_outputs_and_the_next_call_is_unharmed(r
     assert_all_same(r.mirror_records(rays, 3, 1.0), mirror_scenes.reference("room", W61, H37, 3, 1.0)[:4], "after a refusal")
 
 
+@pytest.mark.parametrize("n", [2 ** 31 - 1, 2 ** 31 - 64])
+def test_a_batch_too_large_for_its_rows_is_refused_and_the_next_call_is_unharmed(renderers, n):
+    """the header's check of the batch's size, "ray batch too large for its rows", with rows = 1: the largest int, and 2^31 - 64,
+    one cell over rt_trace_rays' grid limit of 0x7fffffff - 64 cells.  The checks precede all device work, so aligned dummy
+    addresses are never read.  (The last admitted size, 2^31 - 65 rays, is 51 GB of rays alone and is not launched.)"""
+    r = renderers["room"]
+    lib, p = capi.load_library(), mirror_params(3, 1.0)
+    dummy = 0x10000
+    assert n >= (0x7fffffff - 64) + 1 and n * 3.0 <= 8.0e9                    # the cells refuse it, not the floats
+    before = r.mirror_info().rays
+    rc = lib.rt_mirror_records_device(r._scene, C.byref(p), n, 1, C.c_void_p(dummy), C.c_void_p(dummy), None, None, None, None)
+    assert rc == capi.RT_ERR_INVALID and "ray batch too large for its rows" in lib.rt_last_error().decode()
+    rc = lib.rt_mirror_records(r._scene, C.byref(p), n, 1, C.c_void_p(dummy), C.c_void_p(dummy), None, None, None)
+    assert rc == capi.RT_ERR_INVALID and "ray batch too large for its rows" in lib.rt_last_error().decode()
+    assert r.mirror_info().rays == before                                     # (a refused call is not the handle's last call)
+    assert_all_same(r.mirror_records(rays_of("room", W61, H37), 3, 1.0), mirror_scenes.reference("room", W61, H37, 3, 1.0)[:4],
+                    "after a refusal")
+
+
 # ---- 4. the composed calls ------------------------------------------------------------------------------------------------------
 
 def test_render_gbuffer_mirrored_is_the_gbuffer_where_no_mirror_is_followed(renderers):

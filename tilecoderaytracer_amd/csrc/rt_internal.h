@@ -70,6 +70,15 @@ int rt_internal_object_reflective(rt_scene *s, const float **d_rf, int *n_object
 /* a device buffer that only grows (the device is synchronised before the old one is freed) */
 int rt_internal_grow(void **buf, size_t *bytes, size_t need);
 
+/* ---- rt_mirror_compact.hip ---- */
+/* Its instantiation of rt_scan.h's two-level scan, enqueued on hip_stream exactly as the call enqueues it for a bounce's counts
+ * (the call itself goes through here), so that a test can give the scan more counts than any batch that fits a device would:
+ * of n_counts > 0 counts, d_offsets[i] = the sum of the counts before i in i's group of kScanBlock (n_counts words),
+ * d_group_sums[g] and d_group_base[g] = group g's sum and the sum of the groups before it (ceil(n_counts / kScanBlock) words
+ * each), *d_total = the sum of all.  Device pointers, nothing checked, no wait. */
+int rt_internal_mirror_compact_scan(const uint32_t *d_counts, uint32_t n_counts, uint32_t *d_offsets, uint32_t *d_group_sums,
+                                    uint32_t *d_group_base, uint32_t *d_total, void *hip_stream);
+
 }
 
 #endif /* RT_INTERNAL_H_ */

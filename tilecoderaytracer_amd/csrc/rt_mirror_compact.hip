@@ -212,16 +212,11 @@ int run(rt_scene *s, const rt_mirror_params &pr, int n, int rows, const void *d_
             a->info.alive[b] += (int64_t)cnt;
             a->info.rays_queried += (int64_t)cnt;
             if (!last) {
-                const unsigned n_blocks = blocks_of(cnt), n_groups = (n_blocks + kScanBlock - 1) / kScanBlock;
+                const unsigned n_blocks = blocks_of(cnt);
                 hipLaunchKernelGGL(rt_mirror_compact_count_kernel, dim3(n_blocks), dim3(kBlock), 0, stream, cnt, pr.min_reflective, d_rf,
                                    n_objects, static_cast<const uint32_t *>(a->records.p), counts);
                 HIP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(rt_scan_groups_kernel<RT_INTERNAL_UNIT_MIRROR_COMPACT>, dim3(n_groups), dim3(kScanBlock), 0, stream, counts, offsets,
-                                   (uint32_t)n_blocks, group_sums);
-                HIP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(rt_scan_total_kernel<RT_INTERNAL_UNIT_MIRROR_COMPACT>, dim3(1), dim3(kScanBlock), 0, stream, group_sums, group_base,
-                                   (uint32_t)n_groups, a->d_total);
-                HIP_TRY(hipGetLastError());
+                if ((rc = rt_internal_mirror_compact_scan(counts, n_blocks, offsets, group_sums, group_base, a->d_total, stream))) return rc;
                 HIP_TRY(hipMemcpyAsync(a->h_total, a->d_total, 4, hipMemcpyDeviceToHost, stream));
             }
             auto step = b == 0 ? (guide ? launch_step<true, true> : launch_step<true, false>)
@@ -249,6 +244,20 @@ int run(rt_scene *s, const rt_mirror_params &pr, int n, int rows, const void *d_
 extern "C" {
 
 int rt_mirror_compact_version(void) { return RT_MIRROR_COMPACT_VERSION; }
+
+/* rt_internal.h: the two levels of the scan, as run() enqueues them for a bounce's counts */
+int rt_internal_mirror_compact_scan(const uint32_t *d_counts, uint32_t n_counts, uint32_t *d_offsets, uint32_t *d_group_sums,
+                                    uint32_t *d_group_base, uint32_t *d_total, void *hip_stream) {
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const unsigned n_groups = (n_counts + kScanBlock - 1) / kScanBlock;
+    hipLaunchKernelGGL(rt_scan_groups_kernel<RT_INTERNAL_UNIT_MIRROR_COMPACT>, dim3(n_groups), dim3(kScanBlock), 0, stream, d_counts,
+                       d_offsets, n_counts, d_group_sums);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rt_scan_total_kernel<RT_INTERNAL_UNIT_MIRROR_COMPACT>, dim3(1), dim3(kScanBlock), 0, stream, d_group_sums,
+                       d_group_base, (uint32_t)n_groups, d_total);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
 
 #if RT_MIRROR_COMPACT_VARIANTS
 /* 0: a dense list is queried flat; 1: with the caller's rows scaled; returns what was set before */
