@@ -83,7 +83,8 @@
  * Speed-only options (rt_capi_tuning.h) apply as for rt_intersect_rays.
  *
  * Not provided: compaction of finished rays (it needs a read-back: rt_mirror_compact.h has it, as calls of its own); glass; more than one terminal per pixel (a half-mirror is
- * either followed or not: that is min_reflective's job); several GPUs; the counting build; a command-line flag.
+ * either followed or not: that is min_reflective's job); several GPUs; the counting build; a command-line flag.  (Glass has since got
+ * a header of its own: rt_glass.h, this chain with the transmitted child as one more way to go on.)
  *
  * Buffers past 2^32 bytes: the device call is tested on 100 000 007 rays (tests/test_mirror_large_gpu.py) -- terminal and guide
  * records of 4.8 GB each, every word compared; the default chunk, whose offsets into the outputs pass 2^32 bytes, and one

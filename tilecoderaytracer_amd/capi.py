@@ -162,6 +162,19 @@ class RtMirrorCompactInfo(C.Structure):
                 ("alive", C.c_int64 * (RT_MIRROR_MAX_BOUNCES + 1))]
 
 
+class RtGlassParams(C.Structure):
+    """include/rt_glass.h: RtMirrorParams and the transmission factor at or above which a hit is looked through (not NaN;
+    +inf: never)."""
+    _fields_ = [("max_bounces", C.c_int32), ("chunk_rays", C.c_int32), ("min_reflective", C.c_float),
+                ("min_transmissive", C.c_float)]
+
+
+class RtGlassInfo(C.Structure):
+    """include/rt_glass.h: the scene's last rt_glass_records* call, RtMirrorInfo's fields."""
+    _fields_ = [("rays", C.c_int64), ("chunks", C.c_int32), ("queries", C.c_int32), ("query_ms", C.c_double),
+                ("step_ms", C.c_double)]
+
+
 RT_TRANSFER_SRGB, RT_TRANSFER_LINEAR, RT_TRANSFER_CUSTOM = 0, 1, 2
 
 
@@ -399,6 +412,13 @@ def load_library():
         lib.rt_mirror_records_device.argtypes = [vp, C.POINTER(RtMirrorParams), i, i, vp, vp, vp, vp, vp, vp]
         lib.rt_get_mirror_info.argtypes = [vp, C.POINTER(RtMirrorInfo)]
         lib.rt_mirror_records.restype = lib.rt_mirror_records_device.restype = lib.rt_get_mirror_info.restype = i
+    # include/rt_glass.h (likewise)
+    if hasattr(lib, "rt_glass_records"):
+        lib.rt_glass_version.restype = i
+        lib.rt_glass_records.argtypes = [vp, C.POINTER(RtGlassParams), i, i, vp, vp, vp, vp, vp]
+        lib.rt_glass_records_device.argtypes = [vp, C.POINTER(RtGlassParams), i, i, vp, vp, vp, vp, vp, vp]
+        lib.rt_get_glass_info.argtypes = [vp, C.POINTER(RtGlassInfo)]
+        lib.rt_glass_records.restype = lib.rt_glass_records_device.restype = lib.rt_get_glass_info.restype = i
     # include/rt_mirror_compact.h (likewise)
     if hasattr(lib, "rt_mirror_records_compact"):
         lib.rt_mirror_compact_version.restype = i

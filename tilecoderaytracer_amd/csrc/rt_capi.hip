@@ -172,6 +172,7 @@ struct rt_scene {
     rt_internal_unit units[RT_INTERNAL_UNITS] = {};
     void *d_object_diffuse = nullptr;                /* rt_internal_object_diffuse(): a float per Scene object, made on first use */
     void *d_object_reflective = nullptr;             /* rt_internal_object_reflective(): likewise */
+    void *d_object_glass = nullptr;                  /* rt_internal_object_glass(): three float4 per Scene object, likewise */
     char launch_kernel[RT_KERNEL_NAME_BYTES] = {};   /* the whole name; launch.kernel is its first 47 characters */
     std::mutex mu;
 };
@@ -2017,6 +2018,30 @@ int rt_internal_object_reflective(rt_scene *s, const float **d_rf, int *n_object
     return RT_OK;
 }
 
+int rt_internal_object_glass(rt_scene *s, const float4 **d_table, int *n_objects) {
+    const size_t n = s->objects.size();
+    if (!s->d_object_glass && n > 0) {
+        std::vector<float> rows(12 * n, 0.0f);
+        for (size_t i = 0; i < n; ++i) {
+            const rt_object_desc &o = s->objects[i];
+            float *r = rows.data() + 12 * i;
+            r[0] = s->refract_used ? s->refr_tf[i] : 0.0f;
+            r[1] = s->refract_used ? s->refr_ior[i] : 1.0f;
+            r[2] = (float)o.kind;
+            const float *first = o.kind == RT_KIND_SPHERE ? o.origin : o.normal;
+            for (int c = 0; c < 3; ++c) r[4 + c] = first[c];
+            if (o.kind != RT_KIND_SPHERE)
+                for (int c = 0; c < 3; ++c) r[8 + c] = o.reverse_normal[c];
+        }
+        HIP_TRY(hipSetDevice(s->device));
+        HIP_TRY(hipMalloc(&s->d_object_glass, rows.size() * sizeof(float)));
+        HIP_TRY(hipMemcpy(s->d_object_glass, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    *d_table = static_cast<const float4 *>(s->d_object_glass);
+    *n_objects = (int)n;
+    return RT_OK;
+}
+
 int rt_internal_grow(void **buf, size_t *bytes, size_t need) { return grow_device_buffer(buf, bytes, need); }
 
 int rt_capi_version(void) { return RT_CAPI_VERSION; }
@@ -2209,6 +2234,7 @@ int rt_scene_destroy(rt_scene *s) {
     if (s->d_timeline) (void)hipFree(s->d_timeline);
     if (s->d_object_diffuse) (void)hipFree(s->d_object_diffuse);
     if (s->d_object_reflective) (void)hipFree(s->d_object_reflective);
+    if (s->d_object_glass) (void)hipFree(s->d_object_glass);
     for (rt_internal_unit &u : s->units)
         if (u.state) u.free_state(u.state);
     delete s;

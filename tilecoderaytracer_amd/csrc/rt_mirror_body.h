@@ -5,6 +5,8 @@
  * reads and writes, never what it computes: in place, entry = ray = place; compact, a dense list of the rays still alive whose
  * survivors go to the next list.  Both units compile this file under `#pragma clang fp contract(off)` and the library's
  * arithmetic flags.  (As rt_accumulate_body.h is for rt_temporal.hip and rt_motion.hip.)
+ * rt_glass.hip (include/rt_glass.h) shares the argument checks and, through rt_glass_body.h, the __device__ helpers; its step is a
+ * kernel of its own there, and the kernel below is as it was before that unit existed (DESIGN.md section 29 says why).
  */
 #ifndef RT_MIRROR_BODY_H_
 #define RT_MIRROR_BODY_H_
@@ -16,6 +18,7 @@
 #include <cstdint>
 #include <string>
 
+#include "../../include/rt_glass.h"
 #include "../../include/rt_mirror.h"
 #include "rt_host.h"
 #include "rt_scan.h"
@@ -199,8 +202,13 @@ namespace {
 constexpr double kMaxRayFloats = 2.0e9 * 4.0;          /* rt_render's limit for one output, in floats */
 constexpr long long kMaxCells = 0x7fffffffLL - 64;     /* rt_trace_rays' grid limit (include/rt_capi_rays.h) */
 
-/* rt_mirror.h's checks (1) .. (10), which rt_mirror_compact.h takes over word for word */
-inline int rt_mirror_check_args(const rt_scene *s, const rt_mirror_params *pr, int n, int rows, const void *rays, const void *out_hits,
+inline bool rt_mirror_transmissive_nan(const rt_mirror_params &) { return false; }
+inline bool rt_mirror_transmissive_nan(const rt_glass_params &pr) { return std::isnan(pr.min_transmissive); }
+
+/* rt_mirror.h's checks (1) .. (10), which rt_mirror_compact.h takes over word for word and rt_glass.h (Params = rt_glass_params)
+ * with one check more */
+template <class Params>
+inline int rt_mirror_check_args(const rt_scene *s, const Params *pr, int n, int rows, const void *rays, const void *out_hits,
                const void *out_guide, const void *out_weight, const void *out_path, bool device) {
     if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
     if (!pr) return fail(RT_ERR_INVALID, "params is NULL");
@@ -209,6 +217,7 @@ inline int rt_mirror_check_args(const rt_scene *s, const rt_mirror_params *pr, i
                                         std::to_string(pr->max_bounces) + ")");
     if (pr->chunk_rays < 0) return fail(RT_ERR_INVALID, "chunk_rays must not be negative");
     if (std::isnan(pr->min_reflective)) return fail(RT_ERR_INVALID, "min_reflective must not be NaN");
+    if (rt_mirror_transmissive_nan(*pr)) return fail(RT_ERR_INVALID, "min_transmissive must not be NaN");
     if (n < 0) return fail(RT_ERR_INVALID, "n < 0");
     if (rows < 1) return fail(RT_ERR_INVALID, "rows must be positive");
     if (n > 0 && !rays) return fail(RT_ERR_INVALID, "rays pointer is NULL");

@@ -99,6 +99,11 @@ def indirect_params(samples=4, gather_depth=1, gain=1.0, seed=0, key0=0, emitter
                                  int(key0) & 0xFFFFFFFF, float(gain))
 
 
+def glass_params(max_bounces=8, min_reflective=1.0, min_transmissive=0.5, chunk_rays=0):
+    """glass_records' keywords -> an RtGlassParams (include/rt_glass.h); the library checks the values."""
+    return capi.RtGlassParams(int(max_bounces), int(chunk_rays), float(min_reflective), float(min_transmissive))
+
+
 def mirror_params(max_bounces=8, min_reflective=1.0, chunk_rays=0):
     """mirror_records' keywords -> an RtMirrorParams (include/rt_mirror.h); the library checks the values."""
     return capi.RtMirrorParams(int(max_bounces), int(chunk_rays), float(min_reflective))
@@ -1092,6 +1097,42 @@ class Renderer:
                         C.c_void_p(guide_ptr or None), C.c_void_p(weight_ptr or None), C.c_void_p(path_ptr or None),
                         C.c_void_p(stream)))
 
+    def glass_records(self, rays, max_bounces=8, min_reflective=1.0, min_transmissive=0.5, rows=None, chunk_rays=0,
+                      outputs=MIRROR_OUTPUTS):
+        """What each ray sees through the scene's mirrors and its glass (include/rt_glass.h, rt_glass_records): mirror_records()
+        with one more way to go on -- a hit on an object whose transmission factor is > 0 and >= min_transmissive is looked
+        through along rt_capi_refract.h's transmitted child where that child exists.  max_bounces counts mirrors and glass
+        objects together.  -> mirror_records()'s (hits, guide, weight, path); the path word is k | cut << 8 | g << 10 |
+        tag << 12, g: some glass was looked through.  With min_transmissive = inf every word is mirror_records()'s."""
+        n, default_rows = self._batch(rays, "rays")
+        shape = rays.shape[:-1]
+        hits = np.zeros(shape, dtype=HIT_DTYPE)
+        guide = np.zeros(shape, dtype=HIT_DTYPE) if "guide" in outputs else None
+        weight = np.zeros(shape + (3,), dtype=np.float32) if "weight" in outputs else None
+        path = np.zeros(shape, dtype=np.uint32) if "path" in outputs else None
+        params = glass_params(max_bounces, min_reflective, min_transmissive, chunk_rays)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        capi.check(self._lib.rt_glass_records(self._scene, C.byref(params), n, int(default_rows if rows is None else rows),
+                                              rays.ctypes.data, hits.ctypes.data, ptr(guide), ptr(weight), ptr(path)))
+        return hits, guide, weight, path
+
+    def glass_records_device(self, n, rows, rays_ptr, hits_ptr, guide_ptr=0, weight_ptr=0, path_ptr=0, stream=0, max_bounces=8,
+                             min_reflective=1.0, min_transmissive=0.5, chunk_rays=0):
+        """mirror_records_device() through glass as well (include/rt_glass.h, rt_glass_records_device): enqueued on the HIP
+        stream with no sync, nothing read back, so the stream may be capturing once an eager call has grown the scratch."""
+        params = glass_params(max_bounces, min_reflective, min_transmissive, chunk_rays)
+        capi.check(self._lib.rt_glass_records_device(self._scene, C.byref(params), n, rows, C.c_void_p(rays_ptr),
+                                                     C.c_void_p(hits_ptr), C.c_void_p(guide_ptr or None),
+                                                     C.c_void_p(weight_ptr or None), C.c_void_p(path_ptr or None),
+                                                     C.c_void_p(stream)))
+
+    def glass_info(self):
+        """The last glass_records*() of this scene (include/rt_glass.h, rt_glass_info): rays, chunks, queries and the two
+        stage times."""
+        info = capi.RtGlassInfo()
+        capi.check(self._lib.rt_get_glass_info(self._scene, C.byref(info)))
+        return info
+
     def mirror_info(self):
         """The last mirror_records*() of this scene (include/rt_mirror.h, rt_mirror_info): rays, chunks, queries and the two
         stage times."""
@@ -1110,11 +1151,15 @@ class Renderer:
         """the four outputs of the pixel rays of columns [x0, x1) as torch tensors on the device (records as 12 int32 words),
         enqueued on `stream`: rt_lens_rays_device at one sample, aperture 0, focus 1 -- rt_render's own pixel rays -- and
         rt_mirror_records_device (rows = H); mirrors: a dict of max_bounces and min_reflective and, optionally, compact
-        (rt_mirror_records_compact_device in its place: the same words, with host waits)"""
+        (rt_mirror_records_compact_device in its place: the same words, with host waits) or min_transmissive
+        (rt_glass_records_device in its place, include/rt_glass.h: glass is looked through; it has no compact form)"""
         import torch
-        unknown = set(mirrors) - {"max_bounces", "min_reflective", "compact"}
+        unknown = set(mirrors) - {"max_bounces", "min_reflective", "compact", "min_transmissive"}
         if unknown:
-            raise ValueError(f"mirrors takes max_bounces, min_reflective and compact, not {sorted(unknown)}")
+            raise ValueError(f"mirrors takes max_bounces, min_reflective and compact, or min_transmissive, not {sorted(unknown)}")
+        glass = mirrors.get("min_transmissive") is not None
+        if glass and mirrors.get("compact"):
+            raise ValueError("mirrors: min_transmissive has no compact form (include/rt_glass.h)")
         n = max(x1 - x0, 0) * H
         lens = lens_params(1, 0.0, 1.0, 0)
         rays = torch.empty((n * 6,), dtype=torch.float32, device="cuda")
@@ -1124,11 +1169,18 @@ class Renderer:
         path = torch.empty((n,), dtype=torch.int32, device="cuda")
         capi.check(self._lib.rt_lens_rays_device(self._cam, W, H, x0, x1, C.byref(lens), int(self._device), rays.data_ptr(),
                                                  stream.cuda_stream))
+        if glass:
+            kw = {k: v for k, v in mirrors.items() if k != "compact"}
+            self.glass_records_device(n, max(H, 1), rays.data_ptr(), hits.data_ptr(), guide.data_ptr(), weight.data_ptr(),
+                                      path.data_ptr(), stream.cuda_stream, **kw)
+            return hits, guide, weight, path
+        kw = {k: v for k, v in mirrors.items() if k != "min_transmissive"}
         self.mirror_records_device(n, max(H, 1), rays.data_ptr(), hits.data_ptr(), guide.data_ptr(), weight.data_ptr(),
-                                   path.data_ptr(), stream.cuda_stream, **mirrors)
+                                   path.data_ptr(), stream.cuda_stream, **kw)
         return hits, guide, weight, path                               # (rays: torch frees them in the stream's order)
 
-    def render_gbuffer_mirrored(self, W, H, max_depth, max_bounces=8, min_reflective=1.0, x0=0, x1=None, compact=False):
+    def render_gbuffer_mirrored(self, W, H, max_depth, max_bounces=8, min_reflective=1.0, x0=0, x1=None, compact=False,
+                                min_transmissive=None):
         """Columns [x0, x1) of a W x H frame with what each pixel sees through the mirrors (include/rt_mirror.h):
         render_gbuffer()'s colours, and mirror_records()'s four outputs for the pixel rays that lens_rays(camera, W, H,
         samples=1, aperture=0, focus=1) makes, generated and walked on the device with no host wait between the calls ->
@@ -1136,7 +1188,8 @@ class Renderer:
         (Wn, H)).  Where no mirror was followed (path & 0xff == 0) hits is render_gbuffer()'s record.  The device buffers and
         the stream are torch's, so the process must have imported torch before the library was loaded.  compact: the chains
         are walked by rt_mirror_records_compact_device (include/rt_mirror_compact.h): the same words, with one host wait per
-        bounce between the calls."""
+        bounce between the calls.  min_transmissive: None, or the transmission factor from which glass is looked through
+        (include/rt_glass.h, rt_glass_records_device in the mirror call's place; not together with compact)."""
         import torch
         x1 = W if x1 is None else x1
         Wn = max(x1 - x0, 0)
@@ -1145,8 +1198,10 @@ class Renderer:
             records = torch.empty((Wn * H * 12,), dtype=torch.int32, device="cuda")
             stream = torch.cuda.current_stream()
             self.render_gbuffer_device(W, H, max_depth, x0, x1, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
-            hits, guide, weight, path = self._mirror_device(W, H, x0, x1, dict(max_bounces=max_bounces, min_reflective=min_reflective,
-                                                                              compact=compact), stream)
+            mirrors = dict(max_bounces=max_bounces, min_reflective=min_reflective, compact=compact)
+            if min_transmissive is not None:
+                mirrors["min_transmissive"] = min_transmissive
+            hits, guide, weight, path = self._mirror_device(W, H, x0, x1, mirrors, stream)
             return (colours.cpu().numpy(), hits.cpu().numpy().view(HIT_DTYPE).reshape(Wn, H),
                     guide.cpu().numpy().view(HIT_DTYPE).reshape(Wn, H), weight.cpu().numpy().reshape(Wn, H, 3),
                     path.cpu().numpy().view(np.uint32).reshape(Wn, H))
