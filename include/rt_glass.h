@@ -79,8 +79,12 @@
  * child's geometry (step 5's `exists`), so its rule does not carry over, and a count kernel that did the refraction arithmetic
  * a second time was not built.
  *
- * Buffers past 2^32 bytes: the addressing is the mirror unit's -- the same kernel body, every offset 64-bit -- which
- * tests/test_mirror_large_gpu.py holds to 100 000 007 rays.  This call itself is NOT tested at such sizes.
+ * Buffers past 2^32 bytes: every offset is 64-bit, and tests/test_glass_large_gpu.py holds the device call to it bit for bit
+ * on 100 000 007 rays of a refractive scene (4.8 GB of terminal records and of guide records, 2.4 GB of rays): the default
+ * chunk (48 chunks, the chunk loop's byte offsets past 2^32), one chunk of 90 000 001 rays whose records and guide state planes
+ * pass 2^32 bytes with a tail whose outputs begin past them, and that chunk again without guide and weight.  NOT tested: the
+ * weights and the path words past 2^32 bytes (n > 357.9 million, n > 2^30 rays), the rays' element index 6 * ray past 2^32
+ * (n > 715 827 882), and the host call rt_glass_records at such sizes (it stages the batch and runs the same chunk loop).
  *
  * rt_glass_params is 16 bytes; rt_glass_info is 32 bytes: rays at 0, chunks at 8, queries at 12, query_ms at 16, step_ms at 24.
  */

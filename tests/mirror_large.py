@@ -53,21 +53,25 @@ TILE_RAYS = ROOM_W * ROOM_H - 1                              # 7679: odd, so a t
 WORDS = dict(hits=12, guide=12, weight=3, path=1)            # 32-bit words a ray of each output
 
 
-def room_tile(bounces, floor):
+def room_tile(bounces, floor, reference=None):
     """the room's 96 x 80 pixel rays, flat, cut to TILE_RAYS -> (rays float32 (M, 6), {output: its reference as int32 words
-    (M, words a ray)}), of mirror_scenes.reference -- a ray's result depends on that ray alone (include/rt_mirror.h)"""
+    (M, words a ray)}), of mirror_scenes.reference -- a ray's result depends on that ray alone (include/rt_mirror.h).
+    reference: another call's, as (the (ROOM_W, ROOM_H, 6) pixel rays, its four outputs of them) -- test_glass_large_gpu.py's
+    is glass_scenes'; its path words keep k and cut where rt_mirror.h has them, which is all tile_preconditions reads of them"""
     M = TILE_RAYS
-    rays = np.array(mirror_scenes.pixel_rays("room", ROOM_W, ROOM_H), dtype=F, order="C").reshape(-1, 6)[:M]
-    want = mirror_scenes.reference("room", ROOM_W, ROOM_H, bounces, floor)[:4]
+    frame, want = reference or (mirror_scenes.pixel_rays("room", ROOM_W, ROOM_H),
+                                mirror_scenes.reference("room", ROOM_W, ROOM_H, bounces, floor))
+    rays = np.array(frame, dtype=F, order="C").reshape(-1, 6)[:M]
+    assert np.shape(frame) == (ROOM_W, ROOM_H, 6)
     words = {name: np.ascontiguousarray(a).reshape(ROOM_W * ROOM_H, -1)[:M].copy().view(np.int32).reshape(M, w)   # (a copy: the
-             for (name, w), a in zip(WORDS.items(), want)}                                    # reference itself is read-only)
+             for (name, w), a in zip(WORDS.items(), want[:4])}                                # reference itself is read-only)
     return rays, words
 
 
 def tile_preconditions(words, sentinel=0x7FC5A5A5):
     """what the large test needs of room_tile()'s reference, so that it cannot pass vacuously: no output holds the sentinel word
     (large_extents.SENTINEL) or a NaN, whose bits a kernel need not reproduce -> (the chains of length >= b for b = 0 .. 8, the
-    chains cut at the limit)"""
+    chains cut at the limit).  The words may be rt_glass.h's as well: k and cut lie where rt_mirror.h's do."""
     for name, w in words.items():
         assert not (w.view(np.uint32) == np.uint32(sentinel)).any(), f"the reference's {name} holds the sentinel"
     for name in ("hits", "guide"):

@@ -3,7 +3,9 @@ the header's order (none touches a device or the handle), and glass_ref -- the t
 what the header says follows from it, so that the GPU tests, which compare against it, cannot pass vacuously: it is mirror_ref
 where nothing is looked through, the room of glass_scenes.py has chains of every kind, the first child is refract_ref's, the
 guide through panes and planar mirrors is the float64 unfolding of its terminal within the bound DESIGN.md section 29 derives,
-and the guide records carry the history of what stands behind a window where the G-buffer's cannot."""
+and the guide records carry the history of what stands behind a window where the G-buffer's cannot.  Section 4 holds the
+reference to the scenes "edges" and "open" -- every category of ray that the GPU tests on them are there for is present, by
+count -- and pins the chains of the batch test_glass_large_gpu.py tiles."""
 import ctypes as C
 import os
 import re
@@ -15,6 +17,7 @@ import pytest
 
 import glass_ref
 import glass_scenes
+import mirror_large
 import mirror_ref
 import query_ref
 import refract_ref
@@ -294,6 +297,122 @@ def test_guide_records_carry_the_history_of_what_stands_behind_the_window():
     with_guide, with_plain = history_error([f[1] for f in frames]), history_error(plain)
     print(f"guide records {with_guide:.4f}, G-buffer records {with_plain:.4f}")
     assert with_plain > 0.1 and with_guide <= 0.5 * with_plain
+
+
+# ---- 4. the scenes that hold the step to the rule's edges: what test_glass_gpu.py's cases on them rely on ---------------------
+
+def words_of(out):
+    """every 32-bit word of a reference's four outputs, in one array"""
+    return np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint32) for a in out[:4]])
+
+
+def no_nan(out):
+    """no float of a reference's outputs is a NaN, whose bits a kernel need not give"""
+    floats = [out[0][f] for f in ("distance", "point", "normal", "color")] + [out[1][f] for f in ("distance", "point", "normal", "color")]
+    return not any(np.isnan(a).any() for a in floats + [out[2]])
+
+
+def edges(floor, look, bounces=BOUNCES):
+    return glass_scenes.reference("edges", W61, H37, bounces, floor, look)
+
+
+@pytest.mark.parametrize("floor", glass_scenes.EDGES_FLOORS)
+def test_edges_every_threshold_moves_words_one_ulp_above_it_and_none_at_equality(floor):
+    """tf >= min_transmissive: with min_transmissive ON a tf the words are those of the look below it, and one ulp above they
+    are not; tf > 0: nothing changes among -inf, -1, 0 and the smallest tf, although the red sphere is listed with tf 0"""
+    below = words_of(edges(floor, -INF))
+    for look in (-1.0, 0.0):
+        assert (words_of(edges(floor, look)) == below).all(), (floor, look)
+    assert glass_scenes.EDGES_LOOKS[:3] == (-INF, -1.0, 0.0) and len(glass_scenes.EDGES_LOOKS) == 14
+    for tf in glass_scenes.EDGES_TF:
+        assert glass_scenes.up(tf) in glass_scenes.EDGES_LOOKS and F(glass_scenes.up(tf)) > F(tf) == F(tf)
+        assert (words_of(edges(floor, tf)) == below).all(), (floor, tf)
+        above = edges(floor, glass_scenes.up(tf))
+        changed, paths = int((words_of(above) != below).sum()), int((above[3] != edges(floor, tf)[3]).sum())
+        print(f"floor {floor}: across tf {tf}, {changed} words change, {paths} of them path words")
+        assert changed >= 30 and paths >= 30, (floor, tf, changed, paths)
+        assert no_nan(above)
+        below = words_of(above)
+    assert (words_of(edges(floor, INF)) == below).all()
+    scene, rays = glass_scenes.ref_scene("edges"), glass_scenes.pixel_rays("edges", W61, H37)
+    assert (words_of(mirror_ref.records(scene, rays, BOUNCES, floor)) == below).all()
+
+
+def edge_kinds(scene, out, floor, look):
+    """masks over the rays of a reference on "edges": an object that qualifies as glass and as a mirror followed as glass; a
+    candidate without a child followed as a mirror (a candidate not followed as glass had no child); the chain ended, not cut,
+    on the sphere listed with tf 0; the infinite floor looked through; the ior-1 sphere looked through"""
+    hits, d = out[0], out[4]
+    rf, (tf, _) = mirror_ref.reflective(scene), glass_ref.transmissive(scene)
+    ch, gl = d["chain"], d["glass"]
+    o = np.clip(ch, 0, None)
+    candidate = (ch >= 0) & (tf[o] > 0) & (tf[o] >= F(look))
+    qualifies = (ch >= 0) & (rf[o] >= F(floor))
+    return dict(both=(candidate & qualifies & gl).any(-1), fell=(candidate & ~gl).any(-1),
+                tf0=(hits["object"] == glass_scenes.RED_SPHERE) & ~d["cut"],
+                floor=((ch == glass_scenes.FLOOR) & gl).any(-1), clear=((ch == glass_scenes.CLEAR_SPHERE) & gl).any(-1))
+
+
+@pytest.mark.parametrize("floor", glass_scenes.EDGES_FLOORS)
+def test_edges_has_rays_of_every_category(floor):
+    scene = glass_scenes.ref_scene("edges")
+    assert scene.objects[glass_scenes.FLOOR].kind == query_ref.INFINITE_PLANE
+    assert scene.refractive[glass_scenes.RED_SPHERE][0] == 0 and scene.refractive[glass_scenes.CLEAR_SPHERE][1] == 1.0
+    for look in (-INF, 0.2, 0.3):
+        out = edges(floor, look)
+        kinds = edge_kinds(scene, out, floor, look)
+        counts = {name: int(m.sum()) for name, m in kinds.items()}
+        print(f"floor {floor} look {look}:", counts)
+        assert counts["both"] >= 100 and counts["fell"] >= 20 and counts["clear"] >= 20, counts
+        assert counts["floor"] >= 50 or look > 0.2, counts                    # (the floor's tf is 0.2)
+        assert (out[4]["childless"][kinds["fell"]] >= 1).all() and glass_ref.unpack(out[3])[2][kinds["both"]].all()
+        if look == -INF:
+            assert counts["tf0"] >= 50, counts
+
+
+def test_through_the_ior_1_sphere_the_child_keeps_the_rays_direction():
+    """eta = 1: k1 = 1 - (1 - c1 c1) is c1 c1 up to roundings, T1 is d up to roundings, and so is T2.  The pixel rays whose first
+    hit is the ior-1 sphere, and the header's step 5 of them: D against d, in units of the float32 spacing at 1 (2^-23; the
+    components of a unit vector are no larger)"""
+    scene = glass_scenes.ref_scene("edges")
+    d = edges(0.5, 0.2)[4]
+    first = ((d["chain"][..., 0] == glass_scenes.CLEAR_SPHERE) & d["glass"][..., 0]).reshape(-1)
+    assert first.sum() >= 20
+    rays = np.ascontiguousarray(glass_scenes.pixel_rays("edges", W61, H37)).reshape(-1, 6)[first]
+    dirs = query_ref.directions(rays)
+    h = query_ref.intersect(scene, rays)
+    assert (h["object"] == glass_scenes.CLEAR_SPHERE).all()
+    exists, O, D, s = glass_ref.child(scene, h, rays[:, :3].copy(), dirs, glass_ref.transmissive(scene)[1])
+    assert exists.all() and same(O, d["first"].reshape(-1, 3)[first]) and (s > 0).all()
+    worst = float(np.abs(D.astype(np.float64) - dirs.astype(np.float64)).max() / 2.0 ** -23)
+    print(f"ior 1: {int(first.sum())} rays, D differs from d by at most {worst:.2f} ulp")
+    assert worst <= 4.0
+
+
+@pytest.mark.parametrize("bounces,missed,behind_glass,twice", [(1, 400, 300, None), (3, 700, 500, 200)])
+def test_open_has_followed_chains_that_end_in_a_miss(bounces, missed, behind_glass, twice):
+    """object < 0 with k >= 1: the guide is the record itself, and the weight and the tag are carried"""
+    hits, guide, weight, path, d = glass_scenes.reference("open", W61, H37, bounces, 1.0, 0.5)
+    k, cut, g, tag = glass_ref.unpack(path)
+    follow = k >= 1
+    miss = follow & (hits["object"] < 0)
+    counts = (int(follow.sum()), int(miss.sum()), int((miss & g).sum()), int((miss & (k >= 2)).sum()))
+    print(f"open, max_bounces {bounces}: follow something, end in a miss, after glass, with k >= 2:", counts)
+    assert counts[0] >= counts[1] >= missed and counts[2] >= behind_glass and (twice is None or counts[3] >= twice)
+    assert same(guide[miss], hits[miss]) and ((path[miss] & 0xff) >= 1).all() and (tag[miss] >= 1).all() and not cut[miss].any()
+    assert (weight[miss & g] != 1).any(-1).all()
+    assert no_nan((hits, guide, weight))
+
+
+def test_the_large_batchs_reference_is_what_the_large_test_relies_on():
+    """test_glass_large_gpu.py's preconditions, which it asserts again before its first launch"""
+    rays, words, details = glass_scenes.large_tile()
+    assert mirror_large.TILE_RAYS == len(rays) == 7679
+    assert [w.shape for w in words.values()] == [(7679, 12), (7679, 12), (7679, 3), (7679, 1)]
+    assert glass_scenes.large_tile_figures(words, details) == glass_scenes.LARGE_FIGURES
+    assert glass_scenes.LARGE_FIGURES == dict(alive=[7679, 5319, 2632, 1039, 577, 288, 148, 111, 64], cut=47, g=3495,
+                                              glass_steps=[3007, 288, 367, 177, 76, 55, 24, 23], glass_sphere=627, bubble=123,
+                                              childless=85)
 
 
 def test_the_stated_deviation_is_reported():

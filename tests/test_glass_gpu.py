@@ -3,7 +3,10 @@ glass_ref word for word -- terminal records, guide records, weights and path wor
 (whose chains test_glass_cpu.py counts) and on the room without glass, over bounce limits, both reflectivity floors, glass
 looked through and not, chunks, rows, strips, absent outputs, a non-null stream, sentinel-filled guarded outputs and a captured
 graph, against rt_mirror_records where nothing is looked through, and the Renderer's composed calls against the formulae
-composed from the separate calls.  Bar: BIT-EXACT."""
+composed from the separate calls; then (section 5) on the scenes "edges" and "open", which run what the glass room never
+does: min_transmissive on a tf and one ulp above it, a tf of 0 in the list, glass that is a mirror as well, a candidate without
+a child followed as a mirror, planes finite and infinite as glass, an ior of 1, a pane's ior, followed chains that end in a
+miss, and the size refusal from a real handle.  Bar: BIT-EXACT."""
 import ctypes as C
 import itertools
 
@@ -51,7 +54,7 @@ def renderer_of(key):
 
 @pytest.fixture(scope="module")
 def renderers():
-    made = {key: renderer_of(key) for key in ("glass", "room")}
+    made = {key: renderer_of(key) for key in ("glass", "room", "edges", "open")}
     yield made
     for r in made.values():
         r.close()
@@ -76,6 +79,27 @@ def device_records(r, rays, stream=None, **kw):
     h, g, w, p = (b.cpu().numpy() for b in bufs)
     return (h.view(HIT_DTYPE).reshape(shape), g.view(HIT_DTYPE).reshape(shape), w.view(F).reshape(shape + (3,)),
             p.view(np.uint32).reshape(shape))
+
+
+def poisoned_device_records(r, rays, want, what, **kw):
+    """rt_glass_records_device of a frame's rays (W, H, 6) on a stream of its own into sentinel-filled, guarded outputs: the
+    reference `want` holds no sentinel, the guards are untouched, every needed word was written and no slack word was -> the
+    four outputs, downloaded"""
+    import torch
+    W, H = rays.shape[:2]
+    n = W * H
+    poisoned.assert_reference_has_no_sentinel([np.ascontiguousarray(w) for w in want], what)
+    d_rays = poisoned._on_device(rays)
+    o = poisoned._Outputs([(n * 12, 12, poisoned.HIT_FIELDS, False), (n * 12, 12, poisoned.HIT_FIELDS, False),
+                           (n * 3, 3, poisoned.RGB, False), (n, 1, ("path",), False)])
+    stream = torch.cuda.Stream()
+    assert stream.cuda_stream != 0
+    stream.wait_stream(torch.cuda.current_stream())
+    r.glass_records_device(n, H, d_rays.data_ptr(), *o.ptrs(), stream=stream.cuda_stream, **kw)
+    stream.synchronize()
+    hits, guide, weight, path = o.checked(r, H, 0, 1, what)
+    return (hits.view(HIT_DTYPE).reshape(W, H), guide.view(HIT_DTYPE).reshape(W, H), weight.view(F).reshape(W, H, 3),
+            path.reshape(W, H))
 
 
 # ---- 1. every output word against the definition --------------------------------------------------------------------------------
@@ -202,25 +226,12 @@ def test_each_subset_of_the_optional_outputs_may_be_absent(renderers):
 @pytest.mark.parametrize("key,bounces,floor,look,chunk", [("glass", 3, 0.5, 0.5, 0), ("glass", 4, 1.0, 0.5, 300),
                                                           ("glass", 0, 1.0, 0.5, 0), ("room", 2, 1.0, 0.5, 0)])
 def test_device_entry_into_poisoned_words_on_a_stream_of_its_own(renderers, key, bounces, floor, look, chunk):
-    import torch
     r = renderers[key]
-    rays = rays_of(key, W61, H37)
     n = W61 * H37
     want = glass_scenes.reference(key, W61, H37, bounces, floor, look)[:4]
     what = f"rt_glass_records_device {key} bounces {bounces} chunk {chunk}"
-    poisoned.assert_reference_has_no_sentinel([np.ascontiguousarray(w) for w in want], what)
-    d_rays = poisoned._on_device(rays)
-    o = poisoned._Outputs([(n * 12, 12, poisoned.HIT_FIELDS, False), (n * 12, 12, poisoned.HIT_FIELDS, False),
-                           (n * 3, 3, poisoned.RGB, False), (n, 1, ("path",), False)])
-    stream = torch.cuda.Stream()
-    assert stream.cuda_stream != 0
-    stream.wait_stream(torch.cuda.current_stream())
-    r.glass_records_device(n, H37, d_rays.data_ptr(), *o.ptrs(), stream=stream.cuda_stream, max_bounces=bounces,
-                           min_reflective=floor, min_transmissive=look, chunk_rays=chunk)
-    stream.synchronize()
-    hits, guide, weight, path = o.checked(r, H37, 0, 1, what)
-    got = (hits.view(HIT_DTYPE).reshape(W61, H37), guide.view(HIT_DTYPE).reshape(W61, H37), weight.view(F).reshape(W61, H37, 3),
-           path.reshape(W61, H37))
+    got = poisoned_device_records(r, rays_of(key, W61, H37), want, what, max_bounces=bounces, min_reflective=floor,
+                                  min_transmissive=look, chunk_rays=chunk)
     assert_all_same(got, want, what)
     info = r.glass_info()
     chunks = -(-n // chunk) if chunk else 1
@@ -240,16 +251,14 @@ def test_device_entry_refuses_bad_arguments_and_the_next_call_is_unharmed(render
     assert_all_same(r.glass_records(rays, 3, 1.0, 0.5), glass_scenes.reference("glass", W61, H37, 3, 1.0, 0.5)[:4], "after a refusal")
 
 
-def test_the_device_call_captured_into_a_graph_and_replayed_once_gives_the_eager_words():
-    """The call enqueues only: captured on a side stream and replayed once, its words are the eager call's.  The eager call comes
-    first, on the same stream, and grows the scratch and uploads the object tables; the capture then allocates nothing.  (Once:
-    a captured hit query holds its launch's place in the handle's counter ring.)  The Renderer is this test's own."""
+def captured_and_replayed_once(key, want, **kw):
+    """the device call on scene `key`'s 61 x 37 pixel rays, eager and then captured on the same side stream and replayed once:
+    the replayed words are the eager call's and the definition's (`want`).  The Renderer is this call's own."""
     import torch
-    r = renderer_of("glass")
+    r = renderer_of(key)
     try:
-        rays = rays_of("glass", W61, H37)
+        rays = rays_of(key, W61, H37)
         n = W61 * H37
-        kw = dict(max_bounces=3, min_reflective=1.0, min_transmissive=0.5)
         d_rays = poisoned._on_device(rays)
         eager = [torch.zeros((n * w,), dtype=torch.int32, device="cuda") for w in (12, 12, 3, 1)]
         replayed = [torch.zeros((n * w,), dtype=torch.int32, device="cuda") for w in (12, 12, 3, 1)]
@@ -265,14 +274,23 @@ def test_the_device_call_captured_into_a_graph_and_replayed_once_gives_the_eager
         assert all(int(b.abs().max()) == 0 for b in replayed)                 # captured, not run
         graph.replay()
         torch.cuda.synchronize()
-        want = glass_scenes.reference("glass", W61, H37, 3, 1.0, 0.5)[:4]
         shapes = ((HIT_DTYPE, (W61, H37)), (HIT_DTYPE, (W61, H37)), (F, (W61, H37, 3)), (np.uint32, (W61, H37)))
         for name, e, g, w, (dtype, shape) in zip(NAMES, eager, replayed, want, shapes):
             assert_same(g.cpu().numpy(), e.cpu().numpy(), f"replayed against eager: {name}")
             assert_same(g.cpu().numpy().view(dtype).reshape(shape), w, f"replayed against the definition: {name}")
+        info = r.glass_info()
         del graph
+        return info
     finally:
         r.close()
+
+
+def test_the_device_call_captured_into_a_graph_and_replayed_once_gives_the_eager_words():
+    """The call enqueues only: captured on a side stream and replayed once, its words are the eager call's.  The eager call comes
+    first, on the same stream, and grows the scratch and uploads the object tables; the capture then allocates nothing.  (Once:
+    a captured hit query holds its launch's place in the handle's counter ring.)  The Renderer is this test's own."""
+    captured_and_replayed_once("glass", glass_scenes.reference("glass", W61, H37, 3, 1.0, 0.5)[:4], max_bounces=3,
+                               min_reflective=1.0, min_transmissive=0.5)
 
 
 # ---- 4. the composed calls ------------------------------------------------------------------------------------------------------
@@ -329,3 +347,143 @@ def test_render_accumulated_steers_the_history_by_the_guide_behind_the_glass(ren
     for name, g, w in zip(("value", "variance", "flags"), got, (out[0], out[3], out[4])):
         assert_same(g.view(np.uint8) if g.dtype == bool else g, w.view(np.uint8) if w.dtype == bool else w, f"mirrors: {name}")
     assert r._cam is own and (~out[4]).sum() > 100 and not temporal_ref.dead_records(guide).all()
+
+
+# ---- 5. the rule's edges: scenes "edges" and "open" of glass_scenes.py, whose categories test_glass_cpu.py counts ----------------
+
+def edges_both_ways(r, bounces, floor, look):
+    rays = rays_of("edges", W61, H37)
+    want = glass_scenes.reference("edges", W61, H37, bounces, floor, look)
+    what = f"edges bounces {bounces} floor {floor} look {look!r}"
+    assert_all_same(r.glass_records(rays, bounces, floor, look), want, what + " (host)")
+    assert_all_same(device_records(r, rays, max_bounces=bounces, min_reflective=floor, min_transmissive=look), want,
+                    what + " (device)")
+
+
+@pytest.mark.parametrize("floor", glass_scenes.EDGES_FLOORS)
+def test_edges_over_the_floors_and_min_transmissive_on_every_threshold_and_one_ulp_above(renderers, floor):
+    """tf >= min_transmissive at equality and one ulp above, tf > 0 under min_transmissive <= 0, several tf in one scene, glass
+    that is a mirror as well, a finite and an infinite plane as glass, an ior of 1: every word, host and device"""
+    for look in glass_scenes.EDGES_LOOKS:
+        edges_both_ways(renderers["edges"], 4, floor, look)
+
+
+@pytest.mark.parametrize("floor,look", [(0.05, 0.3), (1.0, -INF)])
+@pytest.mark.parametrize("bounces", [0, 8])
+def test_edges_at_no_bounce_and_at_eight(renderers, bounces, floor, look):
+    edges_both_ways(renderers["edges"], bounces, floor, look)
+
+
+def test_edges_the_rim_of_a_bubble_that_is_a_mirror_is_followed_and_so_are_inside_starts(renderers):
+    """handmade_rays() on "edges": a candidate without a child falls to the mirror rule, which now follows -- across the bubble's
+    rim (rf 1) and from inside the glass sphere (t < 0; rf 0.7 against a floor of 0.5) -- in the lane that ran the child"""
+    rays = handmade_rays()
+    scene = glass_scenes.ref_scene("edges")
+    want = glass_ref.records(scene, rays, 3, 0.5, 0.2, details=True)
+    d = want[4]
+    inside, rim = slice(140, 164), slice(164, 164 + 103)
+    fell = lambda o, part: ((d["chain"][part] == o) & ~d["glass"][part]).any(-1) & (d["childless"][part] >= 1)
+    counts = int(fell(glass_scenes.BUBBLE, rim).sum()), int(fell(glass_scenes.GLASS_SPHERE, inside).sum())
+    through = int(((d["chain"][rim] == glass_scenes.BUBBLE) & d["glass"][rim]).any(-1).sum())
+    assert counts[0] >= 20 and counts[1] >= 8 and through >= 10, (counts, through)
+    r = renderers["edges"]
+    assert_all_same(r.glass_records(rays, 3, 0.5, 0.2), want[:4], "edges, handmade")
+    assert_all_same(device_records(r, rays, max_bounces=3, min_reflective=0.5, min_transmissive=0.2), want[:4],
+                    "edges, handmade (device)")
+    got = r.glass_records(rays, 3, 0.5, 0.2, outputs=("path",))               # GUIDE = false on both branches
+    assert_same(got[0], want[0], "edges, handmade, hits and path only: hits")
+    assert_same(got[3], want[3], "edges, handmade, hits and path only: path")
+
+
+def test_edges_in_chunks_of_seven_rays_and_with_hits_and_path_only(renderers):
+    """a slice whose rays take the both-qualify branch and the fall-to-mirror branch, walked seven rays a launch, and the frame
+    with hits and path alone: the GUIDE = false instantiations of the step"""
+    r = renderers["edges"]
+    rays = rays_of("edges", W61, H37)
+    want = glass_scenes.reference("edges", W61, H37, 4, 0.5, 0.3)
+    d = want[4]
+    fell = ((d["chain"] >= 0) & ~d["glass"] & np.isin(d["chain"], (glass_scenes.BUBBLE, glass_scenes.GLASS_SPHERE))).any(-1)
+    fell &= d["childless"] >= 1
+    x = int(np.flatnonzero(fell.any(1))[0])
+    sub = slice(max(x - 1, 0), max(x - 1, 0) + 3)                             # three columns, 111 rays, 16 launches a bounce
+    both = (d["glass"] & np.isin(d["chain"], (glass_scenes.GLASS_SPHERE, glass_scenes.FAR_MIRROR, glass_scenes.FLOOR))).any(-1)
+    assert fell[sub].sum() >= 1 and both[sub].sum() >= 10
+    for asked in (Renderer.MIRROR_OUTPUTS, ("path",)):
+        got = r.glass_records(np.ascontiguousarray(rays[sub]), 4, 0.5, 0.3, chunk_rays=7, outputs=asked)
+        for name, g, w in zip(NAMES, got, want):
+            if name == "hits" or name in asked:
+                assert_same(g, w[sub], f"edges chunk_rays 7 asked {asked}: {name}")
+        m = 3 * H37
+        info = r.glass_info()
+        assert (info.rays, info.chunks, info.queries) == (m, -(-m // 7), -(-m // 7) * 5)
+    got = r.glass_records(rays, 4, 0.5, 0.3, outputs=("path",))
+    assert got[1] is None and got[2] is None
+    assert_same(got[0], want[0], "edges, hits and path only: hits")
+    assert_same(got[3], want[3], "edges, hits and path only: path")
+
+
+@pytest.mark.parametrize("ior", [2.0, 0.5])
+def test_a_panes_ior_is_never_read(renderers, ior):
+    """"ior is read for spheres only": the glass room with its pane's ior changed gives the words of ior 1"""
+    host, refr = glass_scenes.host_scene("glass")
+    refr = [(o, tf, ior if o == glass_scenes.PANE else i) for o, tf, i in refr]
+    assert sum(1 for o, _, i in refr if o == glass_scenes.PANE and i == ior) == 1
+    rays = rays_of("glass", W61, H37)
+    want = glass_scenes.reference("glass", W61, H37, 4, 1.0, 0.5)
+    assert ((want[4]["chain"] == glass_scenes.PANE) & want[4]["glass"]).any(-1).sum() >= 400
+    r = make(Desc(host), refractive=refr)
+    try:
+        got = r.glass_records(rays, 4, 1.0, 0.5)
+        assert_all_same(got, want, f"pane ior {ior}")
+        assert_all_same(got, renderers["glass"].glass_records(rays, 4, 1.0, 0.5), f"pane ior {ior} against ior 1 on the GPU")
+        assert_all_same(device_records(r, rays, max_bounces=4, min_reflective=1.0, min_transmissive=0.5), want,
+                        f"pane ior {ior} (device)")
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("bounces", [1, 3])
+def test_open_chains_that_followed_something_and_end_in_a_miss(renderers, bounces):
+    """object < 0 with k >= 1: the guide is the record itself, L is not advanced, the weight and the tag are carried"""
+    r = renderers["open"]
+    rays = rays_of("open", W61, H37)
+    want = glass_scenes.reference("open", W61, H37, bounces, 1.0, 0.5)
+    k, _, g, _ = glass_ref.unpack(want[3])
+    miss = (k >= 1) & (want[0]["object"] < 0)
+    assert miss.sum() >= 400 and (miss & g).sum() >= 300
+    what = f"open bounces {bounces}"
+    assert_all_same(r.glass_records(rays, bounces, 1.0, 0.5), want, what + " (host)")
+    assert_all_same(device_records(r, rays, max_bounces=bounces, min_reflective=1.0, min_transmissive=0.5), want, what + " (device)")
+    got = poisoned_device_records(r, rays, want[:4], what + " (device, poisoned)", max_bounces=bounces, min_reflective=1.0,
+                                  min_transmissive=0.5)
+    assert_all_same(got, want, what + " (device, poisoned)")
+    assert_all_same(r.glass_records(rays, bounces, 1.0, 0.5, chunk_rays=1000, outputs=("path",))[::3], want[:4:3], what + " (no guide)")
+
+
+def test_edges_captured_in_three_chunks_and_replayed_once_gives_the_eager_words():
+    """test_the_device_call_captured_into_a_graph_and_replayed_once_gives_the_eager_words on "edges", the chunk loop captured:
+    three chunks of 1000 rays, glass that is a mirror and the fall to the mirror rule among them.  Once, for that test's reason."""
+    want = glass_scenes.reference("edges", W61, H37, 4, 0.05, 0.3)[:4]
+    info = captured_and_replayed_once("edges", want, max_bounces=4, min_reflective=0.05, min_transmissive=0.3, chunk_rays=1000)
+    assert (info.rays, info.chunks, info.queries) == (W61 * H37, 3, 15)
+
+
+@pytest.mark.parametrize("n", [2 ** 31 - 1, 2 ** 31 - 64])
+def test_a_batch_too_large_for_its_rows_is_refused_and_the_next_call_is_unharmed(renderers, n):
+    """the header's check (9), "ray batch too large for its rows", with rows = 1, from a real handle: the largest int, and
+    2^31 - 64, one cell over rt_trace_rays' grid limit of 0x7fffffff - 64 cells.  The checks precede all device work, so aligned
+    dummy addresses are never read, and nothing is launched."""
+    r = renderers["glass"]
+    lib, p = capi.load_library(), glass_params(3, 1.0, 0.5)
+    dummy = 0x10000
+    assert n >= (0x7fffffff - 64) + 1 and n * 3.0 <= 8.0e9                    # the cells refuse it, not the floats
+    r.glass_records(np.ascontiguousarray(rays_of("glass", W61, H37)[:5]), 1, 1.0, 0.5)
+    before = r.glass_info().rays
+    assert before == 5 * H37
+    rc = lib.rt_glass_records_device(r._scene, C.byref(p), n, 1, C.c_void_p(dummy), C.c_void_p(dummy), None, None, None, None)
+    assert rc == capi.RT_ERR_INVALID and "ray batch too large for its rows" in lib.rt_last_error().decode()
+    rc = lib.rt_glass_records(r._scene, C.byref(p), n, 1, C.c_void_p(dummy), C.c_void_p(dummy), None, None, None)
+    assert rc == capi.RT_ERR_INVALID and "ray batch too large for its rows" in lib.rt_last_error().decode()
+    assert r.glass_info().rays == before                                      # (a refused call is not the handle's last call)
+    assert_all_same(r.glass_records(rays_of("glass", W61, H37), 3, 1.0, 0.5), glass_scenes.reference("glass", W61, H37, 3, 1.0, 0.5)[:4],
+                    "after a refusal")
