@@ -66,7 +66,9 @@
  * THE DEVICE VARIANT SYNCHRONISES hip_stream ONCE.  The number of flagged pixels decides the launches of the second pass,
  * and the host reads it, four bytes through pinned memory, after the flag pass.  rt_render_adaptive_device therefore cannot
  * be captured into a graph (hipGraph, torch.cuda.graph).  Everything else is enqueued: when the call returns, the second
- * pass may still be running on hip_stream.  rt_adaptive_flags_device is enqueued without synchronising.
+ * pass may still be running on hip_stream.  rt_adaptive_flags_device is enqueued without synchronising.  (Besides: scratch
+ * that has to grow is reallocated first, which waits for the device; and a call on another stream than the handle's previous
+ * call first waits on the host for that previous stream, as every call of a handle does: INTEGRATION.md section 4, "Streams".)
  *
  * SCRATCH lives in the scene handle and only grows: the first pass's colours and records (60 bytes a pixel of the strip and
  * its halo; a strip that ends at the frame's right edge has no halo and renders its colours straight into the output, 48

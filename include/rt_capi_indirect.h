@@ -63,7 +63,9 @@
  *
  * NO HOST SYNCHRONISATION.  rt_indirect_diffuse_device and rt_indirect_rays_device are enqueued on hip_stream and return;
  * nothing is read back, the launches depend on the arguments alone.  (Scratch that has to grow is reallocated first, which
- * waits for the device as any allocation does; a call that fits the handle's scratch waits for nothing.)
+ * waits for the device as any allocation does; a call that fits the handle's scratch, on the stream of the handle's previous
+ * call, waits for nothing.  On another stream it first waits on the host for that previous stream, as every call of a handle
+ * does: INTEGRATION.md section 4, "Streams".)
  *
  * SCRATCH lives in the scene handle and only grows: per record of a chunk the rays and their colours, 36 S bytes, and with
  * emitters == 0 the gather rays' records as well, 84 S bytes in all.  chunk_records = 0 is the library's default: the most

@@ -69,8 +69,9 @@
  *
  * NO HOST SYNCHRONISATION.  rt_render_lens_device and rt_lens_rays_device are enqueued on hip_stream and return; unlike
  * rt_render_adaptive_device nothing is read back, the launches depend on the arguments alone.  (Scratch that has to grow is
- * reallocated first, which waits for the device as any allocation does; a call that fits the handle's scratch waits for
- * nothing.)
+ * reallocated first, which waits for the device as any allocation does; a call that fits the handle's scratch, on the
+ * stream of the handle's previous call, waits for nothing.  On another stream it first waits on the host for that previous
+ * stream, as every call of a handle does: INTEGRATION.md section 4, "Streams".)
  *
  * SCRATCH lives in the scene handle and only grows: the rays and the sample colours of one chunk of columns, 36 S bytes a
  * pixel.  chunk_columns = 0 is the library's default: the most columns whose rays and sample colours stay within 256 MiB,

@@ -68,7 +68,9 @@
  * non-NULL weight or path not 4-byte aligned.  n == 0 is RT_OK and launches nothing.
  *
  * NO HOST SYNCHRONISATION in the device call, which can be captured into a graph once the scratch has been grown by an eager
- * call: each chunk enqueues max_bounces + 1 hit queries with a step kernel after each, exactly as rt_mirror_records_device does.
+ * call: each chunk enqueues max_bounces + 1 hit queries with a step kernel after each, exactly as rt_mirror_records_device does
+ * (and, like it, a call on another stream than the handle's previous call first waits on the host for that previous stream:
+ * INTEGRATION.md section 4, "Streams").
  * SCRATCH is rt_mirror_records' 128 bytes per ray of a chunk, kept in the scene handle apart from the mirror call's, and the
  * default chunk is the same.  The object table the step reads (48 bytes an object) is uploaded on the scene's first call.
  * Timing, lock and options are as rt_mirror.h says; rt_glass_info has rt_mirror_info's fields and layout.

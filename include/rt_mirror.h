@@ -70,7 +70,9 @@
  * NO HOST SYNCHRONISATION in the device call.  The host cannot know when every chain has ended, so each chunk enqueues
  * max_bounces + 1 hit queries with a step kernel after each; a ray whose chain has ended is given six +0.0f as its next ray, as
  * a dead record's rays are in rt_indirect_diffuse, and its later records are ignored.  Nothing is read back.  (Scratch that has
- * to grow is reallocated first, which waits for the device as any allocation does.)
+ * to grow is reallocated first, which waits for the device as any allocation does; and a call on another stream than the
+ * handle's previous call first waits on the host for that previous stream, as every call of a handle does: INTEGRATION.md
+ * section 4, "Streams".)
  *
  * SCRATCH lives in the scene handle and only grows: per ray of a chunk its record (48 bytes), its next ray (24) and its state
  * (56: w, L, A and a word).  chunk_rays = 0 is the library's default: the most rays whose scratch stays within 256 MiB.  The

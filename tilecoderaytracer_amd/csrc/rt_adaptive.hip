@@ -384,6 +384,7 @@ int run(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, in
     const unsigned n_groups = (n_blocks + kScanBlock - 1) / kScanBlock;
     if (rc == RT_OK) rc = a->counts.grow(((size_t)n_blocks + n_groups) * 8);      /* counts, offsets, the groups' sums and bases */
     if (rc == RT_OK) rc = a->list.grow(n * 4);
+    if (rc == RT_OK) rc = rt_internal_order_stream(s, stream);           /* (before anything is enqueued, whatever comes first) */
     if (rc) return rc;
     if (!a->d_total) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a->d_total), 4));
     if (!a->h_total) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&a->h_total), 4, hipHostMallocDefault));

@@ -1727,11 +1727,11 @@ int launch(rt_scene *s, LaunchRequest rq, hipStream_t stream) {
                              : (double)blocks * (double)block * (double)(rq.max_depth + 1) * RT_STACK_ENTRY_BYTES * stack_entry_quads(s) * stack_rays;
     if (stack_bytes > 8.0e9)
         return fail(RT_ERR_CAPACITY, "max_depth too large: the bounce stack would exceed 8 GB of HBM");
-    /* the stack (and nothing else) is shared by successive launches of this handle:
-     * launches must be stream-ordered, so fence when the caller switches streams */
-    if (s->has_last_stream && s->last_stream != stream) HIP_TRY(hipStreamSynchronize(s->last_stream));
-    s->last_stream = stream;
-    s->has_last_stream = true;
+    /* successive launches of this handle share the stack, the ring of counters below, the HELP areas and -- through the units
+     * that compose launches -- those units' scratch: launches must be stream-ordered, so fence when the caller switches
+     * streams (rt_internal.h, THE STREAM RULE; a unit's run() has been here already, and this call then waits for nothing) */
+    rc = rt_internal_order_stream(s, stream);
+    if (rc) return rc;
     rc = grow_device_buffer(&s->d_stack, &s->d_stack_bytes, (size_t)stack_bytes);
     if (rc == RT_OK && plan.help) rc = grow_device_buffer(&s->d_help, &s->d_help_bytes, (size_t)blocks * (size_t)p.help_rays_quads * 16);
     if (rc) return rc;
@@ -1974,6 +1974,14 @@ int rt_internal_scene_device(const rt_scene *s) { return s->device; }
 int rt_internal_scene_soft(const rt_scene *s) { return s->soft_used ? 1 : 0; }
 rt_internal_unit *rt_internal_unit_slot(rt_scene *s, int unit) { return &s->units[unit]; }
 uint64_t rt_internal_launch_seq(const rt_scene *s) { return s->launch_seq; }
+
+int rt_internal_order_stream(rt_scene *s, void *hip_stream) {
+    const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (s->has_last_stream && s->last_stream != stream) HIP_TRY(hipStreamSynchronize(s->last_stream));
+    s->last_stream = stream;
+    s->has_last_stream = true;
+    return RT_OK;
+}
 
 int rt_internal_launch_gbuffer(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,
                                void *d_rgb, void *d_hits, void *hip_stream) {

@@ -310,6 +310,8 @@ int run(rt_scene *s, const rt_indirect_params &pr, int n, const void *d_hits, co
     if (rc == RT_OK) rc = a->rays.grow(most * 24);
     if (rc == RT_OK) rc = a->samples.grow(most * 12);
     if (rc == RT_OK && !pr.emitters) rc = a->gather.grow(most * 48);
+    /* the ray generation below writes the rays that the call before, on another stream, may not have traced yet */
+    if (rc == RT_OK) rc = rt_internal_order_stream(s, stream);
     if (rc) return rc;
     a->clock.n_events = 0;
     a->stages = pr.emitters ? 3 : 4;

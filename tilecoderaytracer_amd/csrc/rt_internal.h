@@ -57,6 +57,13 @@ int rt_internal_scene_device(const rt_scene *s);
 int rt_internal_scene_soft(const rt_scene *s);
 rt_internal_unit *rt_internal_unit_slot(rt_scene *s, int unit);
 uint64_t rt_internal_launch_seq(const rt_scene *s);
+/* THE STREAM RULE, its one copy: what a call of this handle enqueues takes
+ * effect after everything its earlier calls enqueued, whatever their streams -- they share the bounce stack, the ring of
+ * tile-queue counters and every unit's scratch.  If hip_stream is not the stream of the handle's last call, the host waits here
+ * for that stream to drain; hip_stream is then the handle's stream.  A call on the same stream waits for nothing.  launch()
+ * calls it, and so does every composing unit's run(), after its grow()s and before the first thing it enqueues -- a unit's own
+ * kernels (ray generation, say) write its scratch before its first launch().  Under the caller's lock, the device set. */
+int rt_internal_order_stream(rt_scene *s, void *hip_stream);
 /* launch() of a G-buffer strip and of a ray batch (rt_render_gbuffer_device's and rt_trace_rays_device's, arguments checked by
  * the caller for the former and by the batch's own rules for the latter), under the caller's lock */
 int rt_internal_launch_gbuffer(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, int max_depth,

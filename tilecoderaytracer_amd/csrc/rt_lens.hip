@@ -260,6 +260,8 @@ int run(rt_scene *s, const rt_camera_desc *cam, int W, int H, int x0, int x1, in
     HIP_TRY(hipSetDevice(rt_internal_scene_device(s)));
     int rc = a->rays.grow(most * 24);
     if (rc == RT_OK) rc = a->samples.grow(most * 12);
+    /* the ray generation below writes the rays that the call before, on another stream, may not have traced yet */
+    if (rc == RT_OK) rc = rt_internal_order_stream(s, stream);
     if (rc) return rc;
     a->clock.n_events = 0;
     a->clock.collected = true;

@@ -134,6 +134,7 @@ int run(rt_scene *s, const rt_mirror_params &pr, int n, int rows, const void *d_
     if (rc == RT_OK) rc = a->records.grow((size_t)chunk * 48);
     if (rc == RT_OK) rc = a->rays.grow((size_t)chunk * 24);
     if (rc == RT_OK) rc = a->state.grow((size_t)chunk * 4 * (size_t)(guide ? kStateWords : kStateWordsNoGuide));
+    if (rc == RT_OK) rc = rt_internal_order_stream(s, stream);           /* (before anything is enqueued, whatever comes first) */
     if (rc) return rc;
     a->clock.n_events = 0;
     a->clock.collected = true;

@@ -183,6 +183,7 @@ int run(rt_scene *s, const rt_mirror_params &pr, int n, int rows, const void *d_
             if (rc == RT_OK) rc = a->idx[l].grow((size_t)chunk * 4);
         }
     if (rc == RT_OK) rc = a->counts.grow(((size_t)max_blocks + max_groups) * 8);      /* counts, offsets, the groups' sums and bases */
+    if (rc == RT_OK) rc = rt_internal_order_stream(s, stream);           /* (before anything is enqueued, whatever comes first) */
     if (rc) return rc;
     if (!a->d_total) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a->d_total), 4));
     if (!a->h_total) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&a->h_total), 4, hipHostMallocDefault));
