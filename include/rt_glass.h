@@ -76,10 +76,10 @@
  * Timing, lock and options are as rt_mirror.h says; rt_glass_info has rt_mirror_info's fields and layout.
  *
  * Not provided: more than one terminal per pixel (an object that both reflects and transmits is looked through, or followed as
- * a mirror, never both); Fresnel weighting; several GPUs; the counting build; a command-line flag; and a compacting form.
- * rt_mirror_compact.h's count kernel decides whether a chain goes on from two words of its record; here that depends on the
- * child's geometry (step 5's `exists`), so its rule does not carry over, and a count kernel that did the refraction arithmetic
- * a second time was not built.
+ * a mirror, never both); Fresnel weighting; several GPUs; the counting build; a command-line flag.  The compacting form --
+ * these chains over the rays still alive, as rt_mirror_compact.h is to rt_mirror.h -- is rt_glass_compact.h's
+ * rt_glass_records_compact: whether a chain goes on depends here on the child's geometry (step 5's `exists`), and that
+ * header's count pass evaluates steps 3 to 8 by the function its step uses.
  *
  * Buffers past 2^32 bytes: every offset is 64-bit, and tests/test_glass_large_gpu.py holds the device call to it bit for bit
  * on 100 000 007 rays of a refractive scene (4.8 GB of terminal records and of guide records, 2.4 GB of rays): the default

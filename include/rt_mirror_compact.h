@@ -43,8 +43,8 @@
  * neither.  rt_get_timing() and rt_get_launch_info() behave as rt_mirror.h says for rt_mirror_records, with these two times.
  * The handle's lock is held for the whole call.  Speed-only options (rt_capi_tuning.h) apply as for rt_intersect_rays.
  *
- * Not provided: a graph-capturable form; compaction across chunks; glass; several GPUs; the counting build; a command-line
- * flag.
+ * Not provided: a graph-capturable form; compaction across chunks; several GPUs; the counting build; a command-line flag.
+ * Glass is rt_glass_compact.h's rt_glass_records_compact, the same loop over rt_glass.h's chains.
  *
  * Buffers past 2^32 bytes: the device call is tested on 100 000 007 rays (tests/test_mirror_large_gpu.py), every output word
  * and the info's counts compared: with the default chunk, and with one chunk of 90 000 001 rays -- 19.5 GB of scratch, lists

@@ -175,6 +175,13 @@ class RtGlassInfo(C.Structure):
                 ("step_ms", C.c_double)]
 
 
+class RtGlassCompactInfo(C.Structure):
+    """include/rt_glass_compact.h: the scene's last rt_glass_records_compact* call, RtMirrorCompactInfo's fields."""
+    _fields_ = [("rays", C.c_int64), ("rays_queried", C.c_int64), ("chunks", C.c_int32), ("queries", C.c_int32),
+                ("syncs", C.c_int32), ("reserved", C.c_int32), ("query_ms", C.c_double), ("step_ms", C.c_double),
+                ("alive", C.c_int64 * (RT_MIRROR_MAX_BOUNCES + 1))]
+
+
 RT_TRANSFER_SRGB, RT_TRANSFER_LINEAR, RT_TRANSFER_CUSTOM = 0, 1, 2
 
 
@@ -427,6 +434,14 @@ def load_library():
         lib.rt_get_mirror_compact_info.argtypes = [vp, C.POINTER(RtMirrorCompactInfo)]
         lib.rt_mirror_records_compact.restype = lib.rt_mirror_records_compact_device.restype = i
         lib.rt_get_mirror_compact_info.restype = i
+    # include/rt_glass_compact.h (likewise)
+    if hasattr(lib, "rt_glass_records_compact"):
+        lib.rt_glass_compact_version.restype = i
+        lib.rt_glass_records_compact.argtypes = [vp, C.POINTER(RtGlassParams), i, i, vp, vp, vp, vp, vp]
+        lib.rt_glass_records_compact_device.argtypes = [vp, C.POINTER(RtGlassParams), i, i, vp, vp, vp, vp, vp, vp]
+        lib.rt_get_glass_compact_info.argtypes = [vp, C.POINTER(RtGlassCompactInfo)]
+        lib.rt_glass_records_compact.restype = lib.rt_glass_records_compact_device.restype = i
+        lib.rt_get_glass_compact_info.restype = i
     # include/rt_capi_upsample.h (likewise absent from older builds)
     if hasattr(lib, "rt_upsample_guided"):
         lib.rt_capi_upsample_version.restype = i

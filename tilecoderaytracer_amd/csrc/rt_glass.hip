@@ -7,7 +7,7 @@
  * query of the chunk's current rays through rt_internal_launch_hits and a step kernel after it.  The step is rt_glass_body.h's
  * (rt_glass_step_kernel), built from rt_mirror_body.h's helpers: a lane whose hit is a candidate
  * reads its object's three table rows (rt_internal_object_glass), computes the transmitted child and, if it exists, goes on
- * along it.  In place only; there is no compacting form (the header says why).  Nothing is read back, the launches depend on the
+ * along it.  In place only; the compacting form is rt_glass_compact.hip's (include/rt_glass_compact.h).  Nothing is read back, the launches depend on the
  * arguments alone, and the call never waits for the device.  The scratch is a unit slot's of its own, so that a mirror call and a
  * glass call of one handle keep their own bookkeeping (rt_get_mirror_info, rt_get_glass_info).
  */

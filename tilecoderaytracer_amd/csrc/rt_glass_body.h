@@ -6,6 +6,9 @@
  * profiles/glass_experiments.txt): as a template parameter of that kernel it adds four instantiations under a name the library
  * is held to have eight of, and as one __device__ function inlined into two kernels it moves the registers of two of the eight.
  * rt_mirror_body.h's kernel is therefore left as it is, and the mirror step of this file -- step 11 of the header -- restates it.
+ * rt_glass_child below is the library's one copy of the child's arithmetic: rt_glass_compact_body.h's decision function, which
+ * the compacting unit's count and step kernels call, is built on it (DESIGN.md section 31 says why the kernel here does not
+ * call that function).
  * Compiled under `#pragma clang fp contract(off)` and the library's arithmetic flags.
  */
 #ifndef RT_GLASS_BODY_H_

@@ -5,7 +5,8 @@
  * rt_internal_check_device: rt_denoise.hip, rt_image.hip, rt_upsample.hip, rt_temporal.hip and rt_svgf.hip, which launch
  * kernels of their own and nothing else, and rt_adaptive.hip (include/rt_capi_adaptive.h), rt_lens.hip (include/rt_capi_lens.h)
  * rt_indirect.hip (include/rt_capi_indirect.h), rt_mirror.hip (include/rt_mirror.h), rt_mirror_compact.hip
- * (include/rt_mirror_compact.h) and rt_glass.hip (include/rt_glass.h), which compose rt_capi.hip's launches
+ * (include/rt_mirror_compact.h), rt_glass.hip (include/rt_glass.h) and rt_glass_compact.hip (include/rt_glass_compact.h), which
+ * compose rt_capi.hip's launches
  * through the calls below.  The host code those units share among themselves is rt_host.h, which includes this file.
  */
 #ifndef RT_INTERNAL_H_
@@ -30,7 +31,7 @@ typedef struct rt_internal_unit {
     double (*stage_ms)(void *state, uint64_t seq);
 } rt_internal_unit;
 enum { RT_INTERNAL_UNIT_ADAPTIVE, RT_INTERNAL_UNIT_LENS, RT_INTERNAL_UNIT_INDIRECT, RT_INTERNAL_UNIT_MIRROR,
-       RT_INTERNAL_UNIT_MIRROR_COMPACT, RT_INTERNAL_UNIT_GLASS, RT_INTERNAL_UNITS };
+       RT_INTERNAL_UNIT_MIRROR_COMPACT, RT_INTERNAL_UNIT_GLASS, RT_INTERNAL_UNIT_GLASS_COMPACT, RT_INTERNAL_UNITS };
 
 /* rt_capi.hip: the text behind rt_last_error(); returns code */
 int rt_internal_set_error(int code, const char *msg);
@@ -76,7 +77,7 @@ int rt_internal_launch_hits(rt_scene *s, int n, int rows, const void *d_rays, vo
 int rt_internal_object_diffuse(rt_scene *s, const float **d_kd, int *n_objects);
 /* its twin for rt_mirror.hip and rt_mirror_compact.hip (include/rt_mirror.h): the `reflective` of every Scene object, likewise */
 int rt_internal_object_reflective(rt_scene *s, const float **d_rf, int *n_objects);
-/* its twin for rt_glass.hip (include/rt_glass.h): three float4 per Scene object -- {tf, ior, kind, 0} (tf and ior the object's
+/* its twin for rt_glass.hip and rt_glass_compact.hip (include/rt_glass.h): three float4 per Scene object -- {tf, ior, kind, 0} (tf and ior the object's
  * rt_refraction_desc, tf 0 where it has none; kind RT_KIND_* as a float), {a sphere's origin | a plane's normal}, {- | a plane's
  * reverse_normal} -- likewise */
 int rt_internal_object_glass(rt_scene *s, const float4 **d_table, int *n_objects);
@@ -85,7 +86,7 @@ int rt_internal_grow(void **buf, size_t *bytes, size_t need);
 
 /* ---- rt_mirror_compact.hip ---- */
 /* Its instantiation of rt_scan.h's two-level scan, enqueued on hip_stream exactly as the call enqueues it for a bounce's counts
- * (the call itself goes through here), so that a test can give the scan more counts than any batch that fits a device would:
+ * (the call itself goes through here, and so does rt_glass_compact.hip, which has no scan kernels of its own), so that a test can give the scan more counts than any batch that fits a device would:
  * of n_counts > 0 counts, d_offsets[i] = the sum of the counts before i in i's group of kScanBlock (n_counts words),
  * d_group_sums[g] and d_group_base[g] = group g's sum and the sum of the groups before it (ceil(n_counts / kScanBlock) words
  * each), *d_total = the sum of all.  Device pointers, nothing checked, no wait. */

@@ -815,7 +815,8 @@ class Renderer:
         and upsampled, rt_subsample_hits_device, rt_ambient_occlusion_device and rt_upsample_guided_device on that one stream
         with no host wait -- ambient_occlusion_scaled(render_gbuffer(W, H, 0)[1], scale, ...) bit for bit; refine costs exactly
         one read-back of the flags before the holes' batch is enqueued.  mirrors: None, or a dict of max_bounces,
-        min_reflective and optionally compact (include/rt_mirror.h, rt_mirror_compact.h; scale 1 only): the plane is gathered at the terminal records of the pixel rays,
+        min_reflective and optionally compact, or min_transmissive and glass_compact (include/rt_mirror.h, rt_mirror_compact.h,
+        rt_glass.h, rt_glass_compact.h; scale 1 only): the plane is gathered at the terminal records of the pixel rays,
         ambient_occlusion(render_gbuffer_mirrored(W, H, 0, ...)[1], ...) bit for bit -- an open fraction takes no weight."""
         import torch
         if mirrors is not None:
@@ -1019,7 +1020,8 @@ class Renderer:
         -- indirect_diffuse_scaled(hits, scale, ..., base=rgb) bit for bit, and with denoise rgb + denoise(
         indirect_diffuse_scaled(hits, scale, ...), hits, ...); refine costs exactly one read-back of the flags before the holes'
         batch is enqueued.  With scale 1 nothing of this runs and normal_squarings, sigma_plane and refine are not read.
-        mirrors: None, or a dict of max_bounces, min_reflective and optionally compact (include/rt_mirror.h, rt_mirror_compact.h;
+        mirrors: None, or a dict of max_bounces, min_reflective and optionally compact, or min_transmissive and glass_compact (include/rt_mirror.h, rt_mirror_compact.h,
+        rt_glass.h, rt_glass_compact.h;
         scale 1 and no denoise only): the term
         is gathered at the terminal records of the pixel rays and multiplied by the path's weight before it is added -- with
         (_, hits, _, weight, _) = render_gbuffer_mirrored(W, H, max_depth, ...), rgb + weight * indirect_diffuse(hits, ...), one
@@ -1098,12 +1100,14 @@ class Renderer:
                         C.c_void_p(stream)))
 
     def glass_records(self, rays, max_bounces=8, min_reflective=1.0, min_transmissive=0.5, rows=None, chunk_rays=0,
-                      outputs=MIRROR_OUTPUTS):
+                      outputs=MIRROR_OUTPUTS, compact=False):
         """What each ray sees through the scene's mirrors and its glass (include/rt_glass.h, rt_glass_records): mirror_records()
         with one more way to go on -- a hit on an object whose transmission factor is > 0 and >= min_transmissive is looked
         through along rt_capi_refract.h's transmitted child where that child exists.  max_bounces counts mirrors and glass
         objects together.  -> mirror_records()'s (hits, guide, weight, path); the path word is k | cut << 8 | g << 10 |
-        tag << 12, g: some glass was looked through.  With min_transmissive = inf every word is mirror_records()'s."""
+        tag << 12, g: some glass was looked through.  With min_transmissive = inf every word is mirror_records()'s.  compact:
+        walk only the rays still alive (include/rt_glass_compact.h, rt_glass_records_compact): the same words, fewer rays queried,
+        one host wait per bounce; glass_compact_info() then describes the call, and glass_info() does not."""
         n, default_rows = self._batch(rays, "rays")
         shape = rays.shape[:-1]
         hits = np.zeros(shape, dtype=HIT_DTYPE)
@@ -1112,25 +1116,36 @@ class Renderer:
         path = np.zeros(shape, dtype=np.uint32) if "path" in outputs else None
         params = glass_params(max_bounces, min_reflective, min_transmissive, chunk_rays)
         ptr = lambda a: a.ctypes.data if a is not None else None
-        capi.check(self._lib.rt_glass_records(self._scene, C.byref(params), n, int(default_rows if rows is None else rows),
-                                              rays.ctypes.data, hits.ctypes.data, ptr(guide), ptr(weight), ptr(path)))
+        call = self._lib.rt_glass_records_compact if compact else self._lib.rt_glass_records
+        capi.check(call(self._scene, C.byref(params), n, int(default_rows if rows is None else rows), rays.ctypes.data,
+                        hits.ctypes.data, ptr(guide), ptr(weight), ptr(path)))
         return hits, guide, weight, path
 
     def glass_records_device(self, n, rows, rays_ptr, hits_ptr, guide_ptr=0, weight_ptr=0, path_ptr=0, stream=0, max_bounces=8,
-                             min_reflective=1.0, min_transmissive=0.5, chunk_rays=0):
+                             min_reflective=1.0, min_transmissive=0.5, chunk_rays=0, compact=False):
         """mirror_records_device() through glass as well (include/rt_glass.h, rt_glass_records_device): enqueued on the HIP
-        stream with no sync, nothing read back, so the stream may be capturing once an eager call has grown the scratch."""
+        stream with no sync, nothing read back, so the stream may be capturing once an eager call has grown the scratch.
+        compact: rt_glass_records_compact_device (include/rt_glass_compact.h) -- the same words over the rays still alive; it
+        WAITS for the stream once per bounce, so the stream must not be capturing, and returns with its last step possibly
+        still running."""
         params = glass_params(max_bounces, min_reflective, min_transmissive, chunk_rays)
-        capi.check(self._lib.rt_glass_records_device(self._scene, C.byref(params), n, rows, C.c_void_p(rays_ptr),
-                                                     C.c_void_p(hits_ptr), C.c_void_p(guide_ptr or None),
-                                                     C.c_void_p(weight_ptr or None), C.c_void_p(path_ptr or None),
-                                                     C.c_void_p(stream)))
+        call = self._lib.rt_glass_records_compact_device if compact else self._lib.rt_glass_records_device
+        capi.check(call(self._scene, C.byref(params), n, rows, C.c_void_p(rays_ptr), C.c_void_p(hits_ptr),
+                        C.c_void_p(guide_ptr or None), C.c_void_p(weight_ptr or None), C.c_void_p(path_ptr or None),
+                        C.c_void_p(stream)))
 
     def glass_info(self):
         """The last glass_records*() of this scene (include/rt_glass.h, rt_glass_info): rays, chunks, queries and the two
         stage times."""
         info = capi.RtGlassInfo()
         capi.check(self._lib.rt_get_glass_info(self._scene, C.byref(info)))
+        return info
+
+    def glass_compact_info(self):
+        """The last glass_records*(compact=True) of this scene (include/rt_glass_compact.h, rt_glass_compact_info): rays,
+        rays_queried, chunks, queries, syncs, the two stage times and alive[b]."""
+        info = capi.RtGlassCompactInfo()
+        capi.check(self._lib.rt_get_glass_compact_info(self._scene, C.byref(info)))
         return info
 
     def mirror_info(self):
@@ -1152,14 +1167,19 @@ class Renderer:
         enqueued on `stream`: rt_lens_rays_device at one sample, aperture 0, focus 1 -- rt_render's own pixel rays -- and
         rt_mirror_records_device (rows = H); mirrors: a dict of max_bounces and min_reflective and, optionally, compact
         (rt_mirror_records_compact_device in its place: the same words, with host waits) or min_transmissive
-        (rt_glass_records_device in its place, include/rt_glass.h: glass is looked through; it has no compact form)"""
+        (rt_glass_records_device in its place, include/rt_glass.h: glass is looked through) and, with that, glass_compact
+        (rt_glass_records_compact_device, include/rt_glass_compact.h: the same words, with host waits)"""
         import torch
-        unknown = set(mirrors) - {"max_bounces", "min_reflective", "compact", "min_transmissive"}
+        unknown = set(mirrors) - {"max_bounces", "min_reflective", "compact", "min_transmissive", "glass_compact"}
         if unknown:
-            raise ValueError(f"mirrors takes max_bounces, min_reflective and compact, or min_transmissive, not {sorted(unknown)}")
+            raise ValueError(f"mirrors takes max_bounces, min_reflective and compact, or min_transmissive and glass_compact, "
+                             f"not {sorted(unknown)}")
         glass = mirrors.get("min_transmissive") is not None
         if glass and mirrors.get("compact"):
-            raise ValueError("mirrors: min_transmissive has no compact form (include/rt_glass.h)")
+            raise ValueError("mirrors: with min_transmissive the compact form is asked for by glass_compact, not compact "
+                             "(include/rt_glass_compact.h)")
+        if mirrors.get("glass_compact") and not glass:
+            raise ValueError("mirrors: glass_compact is valid only with min_transmissive (include/rt_glass_compact.h)")
         n = max(x1 - x0, 0) * H
         lens = lens_params(1, 0.0, 1.0, 0)
         rays = torch.empty((n * 6,), dtype=torch.float32, device="cuda")
@@ -1170,17 +1190,18 @@ class Renderer:
         capi.check(self._lib.rt_lens_rays_device(self._cam, W, H, x0, x1, C.byref(lens), int(self._device), rays.data_ptr(),
                                                  stream.cuda_stream))
         if glass:
-            kw = {k: v for k, v in mirrors.items() if k != "compact"}
+            kw = {k: v for k, v in mirrors.items() if k not in ("compact", "glass_compact")}
+            kw["compact"] = bool(mirrors.get("glass_compact"))
             self.glass_records_device(n, max(H, 1), rays.data_ptr(), hits.data_ptr(), guide.data_ptr(), weight.data_ptr(),
                                       path.data_ptr(), stream.cuda_stream, **kw)
             return hits, guide, weight, path
-        kw = {k: v for k, v in mirrors.items() if k != "min_transmissive"}
+        kw = {k: v for k, v in mirrors.items() if k not in ("min_transmissive", "glass_compact")}
         self.mirror_records_device(n, max(H, 1), rays.data_ptr(), hits.data_ptr(), guide.data_ptr(), weight.data_ptr(),
                                    path.data_ptr(), stream.cuda_stream, **kw)
         return hits, guide, weight, path                               # (rays: torch frees them in the stream's order)
 
     def render_gbuffer_mirrored(self, W, H, max_depth, max_bounces=8, min_reflective=1.0, x0=0, x1=None, compact=False,
-                                min_transmissive=None):
+                                min_transmissive=None, glass_compact=False):
         """Columns [x0, x1) of a W x H frame with what each pixel sees through the mirrors (include/rt_mirror.h):
         render_gbuffer()'s colours, and mirror_records()'s four outputs for the pixel rays that lens_rays(camera, W, H,
         samples=1, aperture=0, focus=1) makes, generated and walked on the device with no host wait between the calls ->
@@ -1189,7 +1210,9 @@ class Renderer:
         the stream are torch's, so the process must have imported torch before the library was loaded.  compact: the chains
         are walked by rt_mirror_records_compact_device (include/rt_mirror_compact.h): the same words, with one host wait per
         bounce between the calls.  min_transmissive: None, or the transmission factor from which glass is looked through
-        (include/rt_glass.h, rt_glass_records_device in the mirror call's place; not together with compact)."""
+        (include/rt_glass.h, rt_glass_records_device in the mirror call's place; not together with compact).  glass_compact:
+        valid only with min_transmissive -- rt_glass_records_compact_device (include/rt_glass_compact.h) in its place: the same
+        words, with one host wait per bounce."""
         import torch
         x1 = W if x1 is None else x1
         Wn = max(x1 - x0, 0)
@@ -1201,6 +1224,8 @@ class Renderer:
             mirrors = dict(max_bounces=max_bounces, min_reflective=min_reflective, compact=compact)
             if min_transmissive is not None:
                 mirrors["min_transmissive"] = min_transmissive
+            if glass_compact:
+                mirrors["glass_compact"] = True
             hits, guide, weight, path = self._mirror_device(W, H, x0, x1, mirrors, stream)
             return (colours.cpu().numpy(), hits.cpu().numpy().view(HIT_DTYPE).reshape(Wn, H),
                     guide.cpu().numpy().view(HIT_DTYPE).reshape(Wn, H), weight.cpu().numpy().reshape(Wn, H, 3),
@@ -1258,7 +1283,8 @@ class Renderer:
         variance, flags), what temporal_accumulate() over the public calls' frames gives bit for bit.  filter: None, or a dict of
         svgf_params()'s keywords (but channels): the last frame goes through the variance-steered filter on the same stream
         (include/rt_svgf.h) and value and variance are the filtered ones, svgf_filter()'s of that frame bit for bit.
-        mirrors: None, or a dict of max_bounces, min_reflective and optionally compact (include/rt_mirror.h, rt_mirror_compact.h): the term is gathered at the terminal
+        mirrors: None, or a dict of max_bounces, min_reflective and optionally compact, or min_transmissive and glass_compact (include/rt_mirror.h, rt_mirror_compact.h,
+        rt_glass.h, rt_glass_compact.h): the term is gathered at the terminal
         records of the pixel rays ("indirect": weighted as render_indirect(mirrors=...) does) and the history and the filter
         are given the guide records in place of the G-buffer's."""
         import torch
