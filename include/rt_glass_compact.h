@@ -53,10 +53,12 @@
  *
  * Not provided: a graph-capturable form; compaction across chunks; several GPUs; the counting build; a command-line flag.
  *
- * Buffers past 2^32 bytes: every offset is 64-bit.  NOT tested: any buffer of these calls past 2^32 bytes -- records and guide
- * records (n > 89.4 million), weights, path words, the rays' element index 6 * ray past 2^32, and lists of more than 2^28
- * entries.  (The in-place call and the mirror compact call are held to such sizes by tests/test_glass_large_gpu.py and
- * tests/test_mirror_large_gpu.py; this call's test of that kind is to follow.)
+ * Buffers past 2^32 bytes: every offset is 64-bit.  Tested (tests/test_glass_compact_large_gpu.py, the device call, 100 000 007
+ * rays): records and guide records past 2^32 bytes and rays past 2^31, with the default chunk and with one chunk of 90 000 001
+ * rays, whose records and state planes pass 2^32 bytes themselves; a dense list of 62.3 million entries; and a dense list of
+ * 90 000 001 entries, whose own records pass 2^32 bytes and whose rays 2^31.  NOT tested: weights past 2^32 bytes (n > 357.9
+ * million), path words past 2^32 bytes (n > 2^30), the rays' element index 6 * ray past 2^32, lists of more than 2^28 entries
+ * through the call, and the host variant at any of these sizes.
  *
  * rt_glass_compact_info is 568 bytes: rays at 0, rays_queried at 8, chunks at 16, queries at 20, syncs at 24, reserved at 28,
  * query_ms at 32, step_ms at 40, alive at 48 -- rt_mirror_compact_info's fields and layout.

@@ -296,6 +296,79 @@ def test_the_list_size_batches_are_cut_as_the_gpu_test_needs_them():
     assert steps.sum() >= 1000 and (~steps).sum() >= 1000                                 # both kinds of step in one list
 
 
+def test_the_all_alive_tile_is_what_the_large_run_d_relies_on():
+    """test_glass_compact_large_gpu.py's tile of run (d), which it asserts again before its first launch: the format is
+    mirror_large.room_tile's, the figures are pinned, no word is the sentinel and no float field holds a NaN
+    (mirror_large.tile_preconditions, inside all_alive_tile_figures)"""
+    import glass_compact_batches as B
+    import large_extents
+    import mirror_large
+    rays, words, details = B.all_alive_tile()
+    M = 5319
+    assert rays.shape == (M, 6) and rays.dtype == F and rays.flags["C_CONTIGUOUS"] and M % 2 == 1
+    assert [(name, w.shape, w.dtype) for name, w in words.items()] == [(name, (M, n), np.int32) for name, n in mirror_large.WORDS.items()]
+    ch, pick = B.chains(), B.all_alive_batch()
+    assert (rays == ch["rays"][pick]).all()
+    for w, a in zip(words.values(), ch["want"]):                             # the frame's reference at the batch's indices
+        assert (w.reshape(-1) == np.ascontiguousarray(a[pick]).view(np.int32).reshape(-1)).all()
+    for w in words.values():
+        assert not (w.view(np.uint32) == np.uint32(large_extents.SENTINEL)).any()
+    figures = B.all_alive_tile_figures(words, details)
+    assert figures == B.ALL_ALIVE_FIGURES
+    assert figures == dict(alive=[5319, 5319, 2632, 1039, 577, 288, 148, 111, 64], cut=47, g=3495,
+                           glass_steps=[3007, 288, 367, 177, 76, 55, 24, 23], mirror_steps=[2312, 2344, 672, 400, 212, 93, 87, 41],
+                           ended=[0, 2687, 1593, 462, 289, 140, 37, 47, 64], childless=15, ended_childless=15)
+    # every step is one or the other, and what does not go on ended: the three rows account for the tile
+    for b in range(8):
+        assert figures["glass_steps"][b] + figures["mirror_steps"][b] == figures["alive"][b + 1]
+        assert figures["alive"][b] - figures["alive"][b + 1] == figures["ended"][b]
+    # the standard tile's rows past query 0 are this tile's: it is that tile without the 2360 chains that end at once (and with
+    # ray 7679, which ends at once too)
+    assert figures["alive"][1:] == glass_scenes.LARGE_FIGURES["alive"][1:] and figures["glass_steps"] == glass_scenes.LARGE_FIGURES["glass_steps"]
+    assert glass_scenes.LARGE_FIGURES["childless"] - figures["childless"] == 70
+
+
+def test_the_large_runs_list_sizes_from_the_tiles():
+    """what test_glass_compact_large_gpu.py's runs (b) and (d) assert of their lists, from the closed form over the tile's path
+    words (mirror_large.tiled_expected_info, which test_mirror_compact_cpu.py proves equal to the count over tiled words)"""
+    import glass_compact_batches as B
+    import mirror_large
+    n, chunk, B31, B32 = 100000007, 90000001, 1 << 31, 1 << 32
+    path = B.all_alive_tile()[1]["path"].view(np.uint32).reshape(-1)
+    rays_, queried, chunks, queries, syncs, alive = mirror_large.tiled_expected_info(path, n, 8, chunk)
+    assert alive[0] == alive[1] == n and (rays_, chunks, queries, syncs) == (n, 2, 18, 16) and min(alive[:9]) > 0 and alive[9:] == [0] * 56
+    first = mirror_large.tiled_expected_info(path, chunk, 8)[5]
+    assert first[:3] == [chunk, chunk, 44534472] and 48 * first[1] > B32 and 24 * first[1] > B31 and min(first[:9]) > 0
+    assert first[1] > 89478485 == B32 // 48                                   # the fewest entries whose records pass 2^32 bytes
+    path = glass_scenes.large_tile()[1]["path"].view(np.uint32).reshape(-1)
+    first = mirror_large.tiled_expected_info(path, chunk, 8)[5]
+    assert first[0] == chunk and first[1] == 62340474 and 62.3e6 < first[1] < 62.4e6
+    assert 48 * first[1] < B32                                                # (why run (d) has a tile of its own)
+    assert 237 * 1024 < -(-first[1] // 256) <= 238 * 1024                     # 238 groups of the scan's first level
+    assert mirror_large.tiled_expected_info(path, n, 8, 0)[2] == 1 and mirror_large.tiled_expected_info(path, n, 8, 1237029)[2] == 81
+
+
+@pytest.mark.parametrize("floor", [1.0, 0.5])
+@pytest.mark.parametrize("bounces", [8, 3])
+def test_in_open_chunks_end_at_different_bounces_and_a_later_chunk_goes_further(bounces, floor):
+    """test_glass_compact_gpu.py's chunk test on "open": under each of its chunk sizes some chunk ends early and -- except in
+    chunks of 1000, which run 4, 4 and 3 queries -- a later chunk runs more queries than it"""
+    import glass_compact_batches as B
+    assert B.OPEN_CHUNKS == (7, 64, 300, 600, 1000) and B.OPEN_CHUNKS_NO_LATER_CHUNK_GOES_FURTHER == (1000,)
+    path = np.asarray(glass_scenes.reference("open", W61, H37, bounces, floor, 0.5)[3]).reshape(-1)
+    for chunk in B.OPEN_CHUNKS:
+        q = B.assert_chunks_end_at_different_bounces(path, bounces, chunk)
+        assert len(q) == -(-len(path) // chunk) and max(q) == 4 and sum(q) == mirror_large_info(path, bounces, chunk)[3]
+        assert (max(q) == bounces + 1) == (bounces == 3)                      # at 8 no chunk runs every query, at 3 some do
+    assert B.queries_per_chunk(path, bounces, 300) == [2, 3, 4, 4, 3, 3, 4, 1]
+    assert B.queries_per_chunk(path, bounces, 600) == [3, 4, 3, 4]
+
+
+def mirror_large_info(path, bounces, chunk):
+    import mirror_large
+    return mirror_large.expected_info(path, bounces, chunk)
+
+
 def test_the_default_chunk_is_the_mirror_compact_calls():
     unit = open(os.path.join(CSRC, "rt_glass_compact.hip")).read()
     assert "static_assert(kRayBytes == 217" in unit and "== 1237029" in unit and (256 << 20) // 217 == 1237029

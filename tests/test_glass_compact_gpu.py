@@ -301,6 +301,116 @@ def test_the_call_on_another_stream_than_a_held_glass_call_of_the_handle():
         h.r.close()
 
 
+# ---- 6b. between chunks, between calls, between handles -----------------------------------------------------------------------------
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("floor", [1.0, 0.5])
+@pytest.mark.parametrize("chunk", batches.OPEN_CHUNKS)
+def test_chunks_that_end_at_different_bounces(renderers, chunk, floor, device):
+    """"open" at max_bounces 8: chains end in misses and as one chunk the list is empty at query 4.  In chunks of 7, 64, 300 and
+    1000 rays some chunks end after one query and others after four, and a chunk that ended early is followed by one that goes
+    further (test_glass_compact_cpu.py holds that on the path words, and it is asserted here again): the next chunk starts at
+    bounce 0 with cnt = its rays and the lists' roles by b & 1, whatever the bounce the chunk before stopped at.  No chunk of
+    "open" runs all nine queries, so syncs == queries at max_bounces 8; at max_bounces 3 the chunks that run all four wait three
+    times and the others once per query -- expected_info reckons both, per chunk."""
+    r = renderers["open"]
+    rays = rays_of("open", W61, H37)
+    for bounces in (8, 3):
+        want = glass_scenes.reference("open", W61, H37, bounces, floor, 0.5)[:4]
+        q = batches.assert_chunks_end_at_different_bounces(np.asarray(want[3]).reshape(-1), bounces, chunk)
+        what = f"open in chunks of {chunk}, max_bounces {bounces}, floor {floor}, {'device' if device else 'host'}"
+        if device:
+            got = poisoned_device_records(r, rays, want, what, max_bounces=bounces, min_reflective=floor, min_transmissive=0.5,
+                                          chunk_rays=chunk, compact=True)
+        else:
+            got = r.glass_records(rays, bounces, floor, 0.5, chunk_rays=chunk, compact=True)
+        assert_all_same(got, want, what)
+        info = info_of(r)
+        assert info == expected_info(want[3], bounces, chunk), what
+        full = sum(1 for a in q if a == bounces + 1)
+        assert info[2:5] == (len(q), sum(q), sum(q) - full) and (full == 0) == (bounces == 8), (what, q)
+
+
+def test_one_handle_called_with_alternating_chunks_outputs_and_batches():
+    """A fresh handle, called in turn with chunks, outputs and batches that change under scratch which only grows: the state
+    buffer holds 4 or 14 planes of `stride = chunk` words, a stride that is not the one the buffer was grown for, and the batch
+    of the third call (test_glass_gpu.py's handmade rays, an odd number that is no frame's) has another length.  First of all a
+    call with max_bounces 0, which allocates no list.  Every call is bit-exact with its info."""
+    rays = rays_of("glass", W61, H37)
+    made = batches.handmade_rays()
+    frame = lambda bounces: glass_scenes.reference("glass", W61, H37, bounces, 0.5, 0.5)[:4]
+    made_want = glass_ref.records(glass_scenes.ref_scene("glass"), made, 3, 0.5, 0.5)[:4]
+    assert len(made) % 2 == 1 and 257 < len(made) < 2 * 257 + 257
+    #        rays, bounces, chunk_rays, outputs, reference
+    calls = [(rays, 0, 0, NAMES[1:], frame(0)),                               # no list is allocated yet
+             (rays, 8, 100, ("path",), frame(8)),
+             (rays, 8, 0, NAMES[1:], frame(8)),
+             (made, 3, 257, NAMES[1:], made_want),
+             (rays, 8, 1000, ("path",), frame(8)),
+             (rays, 8, 7, NAMES[1:], frame(8)),
+             (rays, 8, 0, NAMES[1:], frame(8))]
+    r = renderer_of("glass")
+    try:
+        for step, (batch, bounces, chunk, asked, want) in enumerate(calls):
+            what = f"call {step} of one handle: {len(batch.reshape(-1, 6))} rays, max_bounces {bounces}, chunk_rays {chunk}, {asked}"
+            got = r.glass_records(batch, bounces, 0.5, 0.5, chunk_rays=chunk, outputs=asked, compact=True)
+            for name, g, w in zip(NAMES, got, want):
+                if name == "hits" or name in asked:
+                    assert_same(g, w, f"{what}: {name}")
+                else:
+                    assert g is None
+            assert info_of(r) == expected_info(want[3], bounces, chunk), what
+    finally:
+        r.close()
+
+
+def test_two_handles_on_two_streams_from_two_threads_at_once():
+    """"glass" and "edges", a handle each, the compact device entry of each on a side stream of its own from a thread of its own,
+    both started together, three rounds: every word of both is its own reference and each handle's info its own.  The scan's
+    instantiation is shared code; its buffers, the device's total and the pinned word the host reads it through are a handle's."""
+    import threading
+    import torch
+    keys = ("glass", "edges")
+    n = W96 * H80
+    want = {key: glass_scenes.reference(key, W96, H80, 8, 0.5, 0.5)[:4] for key in keys}
+    assert expected_info(want["glass"][3], 8) != expected_info(want["edges"][3], 8)
+    made = {key: renderer_of(key) for key in keys}
+    try:
+        d_rays = {key: poisoned._on_device(rays_of(key, W96, H80)) for key in keys}
+        streams = {key: torch.cuda.Stream() for key in keys}
+        assert len({s.cuda_stream for s in streams.values()} | {0}) == 3
+        for rounds in range(3):
+            bufs = {key: [torch.full((n * w,), poisoned.SENTINEL, dtype=torch.int32, device="cuda") for w in (12, 12, 3, 1)]
+                    for key in keys}
+            torch.cuda.synchronize()
+            gate, errors = threading.Barrier(2), {}
+
+            def work(key):
+                try:
+                    gate.wait(timeout=60)
+                    made[key].glass_records_device(n, H80, d_rays[key].data_ptr(), *[b.data_ptr() for b in bufs[key]],
+                                                   stream=streams[key].cuda_stream, max_bounces=8, min_reflective=0.5,
+                                                   min_transmissive=0.5, compact=True)
+                    streams[key].synchronize()
+                except BaseException as e:                                    # (reported by the main thread)
+                    errors[key] = e
+            threads = [threading.Thread(target=work, args=(key,)) for key in keys]
+            for t in threads:
+                t.start()
+            for t in threads:
+                t.join()
+            assert not errors, errors
+            torch.cuda.synchronize()
+            for key in keys:
+                what = f"{key} beside {keys[1 - keys.index(key)]}, round {rounds}"
+                for name, b, w in zip(NAMES, bufs[key], want[key]):
+                    assert_same(b.cpu().numpy(), np.ascontiguousarray(w).reshape(-1).view(np.int32), f"{what}: {name}")
+                assert info_of(made[key]) == expected_info(want[key][3], 8), what
+    finally:
+        for r in made.values():
+            r.close()
+
+
 # ---- 7. the Renderer's composed calls -----------------------------------------------------------------------------------------------
 
 def test_render_gbuffer_mirrored_glass_compact_is_the_call_without_it_bit_for_bit(renderers):

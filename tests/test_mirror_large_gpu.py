@@ -141,6 +141,7 @@ def test_mirror_records_past_2_32_bytes(tile, run):
             i = r.mirror_info()
             assert (i.rays, i.chunks, i.queries) == (n, chunks, chunks * (BOUNCES + 1)), what
             assert i.query_ms > 0 and i.step_ms > 0
+        print(f"[mirror large] {run}: query {i.query_ms:.1f} ms, step {i.step_ms:.1f} ms")
     finally:
         for g in outs.values():
             g.free()

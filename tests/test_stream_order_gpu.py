@@ -15,9 +15,9 @@ call 2: its ray generation ran at once, the fence in its first launch waited for
 rays, and call 2 came out as call 1's reference word for word.)  The outputs are filled with poisoned.py's sentinel before the
 calls.
 
-Two calls cannot be held: rt_render_adaptive_device and rt_mirror_records_compact_device wait for their own stream inside the
-call (include/rt_capi_adaptive.h, include/rt_mirror_compact.h), so call 1 returns after the hold whatever the library does, and
-step 3 asserts that wait in place of the hold.  Their pairs still change streams with call 1's last stage in flight.
+Three calls cannot be held: rt_render_adaptive_device, rt_mirror_records_compact_device and rt_glass_records_compact_device wait
+for their own stream inside the call (include/rt_capi_adaptive.h, include/rt_mirror_compact.h, include/rt_glass_compact.h), so
+call 1 returns after the hold whatever the library does, and step 3 asserts that wait in place of the hold.  Their pairs still change streams with call 1's last stage in flight.
 
 The stream pairs (A, B) are (side, other side), (side, null) and (null, side).  Bar: BIT-EXACT."""
 import ctypes as C
@@ -132,7 +132,7 @@ def run_held(pair, a, b, what):
     pair.issue(0, a.cuda_stream)
     ended_early = held.query()
     if pair.waits:
-        # rt_render_adaptive_device and rt_mirror_records_compact_device wait for their own stream by their definition (how many
+        # rt_render_adaptive_device and rt_*_records_compact_device wait for their own stream by their definition (how many
         # pixels, how many rays the next stage has): the call returns after the hold, whatever the library does, and only its
         # last stage can still be in flight when call 2 is issued.  That wait is what is asserted of them.
         assert ended_early, f"{what}: call 1 is documented to wait for its stream and returned while that stream was held"
@@ -243,15 +243,17 @@ def mirror_pair(compact):
     return pair
 
 
-def glass_pair():
+def glass_pair(compact=(False, False)):
+    """compact[k]: call k is rt_glass_records_compact_device (include/rt_glass_compact.h), which waits for its own stream"""
     G = refs.GLASS
     h = Handle(glass_renderer(), G["key"])
     d_rays = [on_device(glass_scenes.pixel_rays(G["key"], W, H, c["camera"])) for c in G["calls"]]
 
     def call(k, ptrs, stream):
         h.r.glass_records_device(N, H, d_rays[k].data_ptr(), *ptrs, stream=stream, max_bounces=refs.BOUNCES,
-                                 min_reflective=G["min_reflective"], min_transmissive=G["calls"][k]["min_transmissive"])
-    pair = Pair("glass", h, call)
+                                 min_reflective=G["min_reflective"], min_transmissive=G["calls"][k]["min_transmissive"],
+                                 compact=compact[k])
+    pair = Pair("glass", h, call, waits=compact[0])
     pair.keep = d_rays
     return pair
 
@@ -337,6 +339,8 @@ DEVICE_PAIRS = {
     "mirror": lambda: mirror_pair(False),
     "mirror-compact": lambda: mirror_pair(True),
     "glass": glass_pair,
+    "glass-compact": lambda: glass_pair((True, True)),
+    "glass-compact-then-glass": lambda: glass_pair((True, False)),
     "mirror-then-glass": crossed_pair,
     "render-stack-in-hbm": stack_pair,
     "gbuffer": gbuffer_pair,
