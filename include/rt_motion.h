@@ -31,8 +31,9 @@
  * gives that object's pixels no history, by the way the comparisons are written (Pp.k and Np.k are NaN, so s or the normal test
  * fails).  The motion table is never read on a first frame.
  *
- * Not provided: history is not invalidated where a mover's shadow or reflection passes over a surface that stayed (alpha is
- * the caller's tool for that); deforming or scaling objects; history behind glass (mirrors: include/rt_mirror.h);
+ * Not provided: history is not invalidated here where a mover's shadow or reflection passes over a surface that stayed
+ * (include/rt_clamp.h clips such history to the frame's neighbourhood, as a call of its own after this one; alpha fades it
+ * everywhere); deforming or scaling objects; history behind glass (mirrors: include/rt_mirror.h);
  * supersampled frames; several GPUs; the counting build; a command-line flag (the executable has no animated scene).
  *
  * ERRORS.  The checks are rt_temporal_accumulate's, in its order, each RT_ERR_INVALID and each before any device work.  The new

@@ -59,7 +59,8 @@
  * Not provided: history behind glass (the record is the pane's; for mirrors, include/rt_mirror.h makes the guide records),
  * supersampled frames (they have no records), several GPUs, the counting build.  The spatial variance estimate for short
  * histories and the variance-steered filter are include/rt_svgf.h.  Objects that move between the frames (these records carry no
- * motion) are include/rt_motion.h: the same calls with one rigid motion per object.
+ * motion) are include/rt_motion.h: the same calls with one rigid motion per object.  History that went stale on a surface that
+ * stayed (a shadow moved, a light changed) is clipped by include/rt_clamp.h, a call of its own after this one.
  *
  * ERRORS.  Int codes and rt_last_error() as everywhere.  All argument checks come before any device work, RT_ERR_INVALID in this
  * order: params is NULL; channels not 1 or 3; match_color not 0 or 1; max_history outside 1..65535; normal_cos NaN or outside

@@ -1,0 +1,468 @@
+"""Neighbourhood clipping of an accumulated history (include/rt_clamp.h) without a GPU: the header, the exported symbols, every
+argument check in the header's order (none touches a device), clamp_ref -- the tests' restatement of the definition -- against a
+per-pixel restatement in np.float32 scalars, each line of the header's WHAT FOLLOWS on the reference, and the conditions on the
+ghost pixels of two pose pairs of the motion scene, counted with the reference on the oracle's colours and records."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import cameras
+import clamp_ref
+import temporal_ref
+from clamp_scenes import GHOST_KW, GHOST_PAIRS, ghost_error, ghost_setting
+from denoise_ref import same_bits
+from test_temporal_cpu import made_up_history
+from test_upsample_gpu import random_frame
+from tilecoderaytracer_amd import capi
+from tilecoderaytracer_amd.renderer import HIT_DTYPE
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INCLUDE = os.path.join(ROOT, "include")
+HEADER = os.path.join(INCLUDE, "rt_clamp.h")
+FUNCTIONS = ["rt_capi_clamp_version", "rt_history_clamp", "rt_history_clamp_device"]
+F = np.float32
+NAMES = clamp_ref.NAMES
+
+
+def same_words(got, want, what):
+    """bit for bit"""
+    for g, w, name in zip(got, want, NAMES):
+        g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
+        assert g.shape == w.shape and g.tobytes() == w.tobytes(), f"{what}: {name}"
+
+
+# ---- 1. the header ----------------------------------------------------------------------------------------------------------
+
+def test_header_declares_exactly_its_functions_and_the_library_exports_them():
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert sorted(set(re.findall(r"^\s*(?:int|uint64_t)\s+(rt_\w+)\s*\(", text, flags=re.M))) == FUNCTIONS
+    assert re.findall(r'#include\s+[<"]([^>"]+)[>"]', text) == ["rt_capi_query.h"]
+    lib = capi.load_library()
+    for name in FUNCTIONS:
+        assert getattr(lib, name) is not None, name
+    r = subprocess.run(["nm", "-D", "--defined-only", capi.library_path()], capture_output=True, text=True, check=True)
+    lines = [line.split() for line in r.stdout.splitlines() if line.split()]
+    exported = sorted(p[-1] for p in lines if p[-2] == "T" and re.fullmatch(r"rt_\w*clamp\w*", p[-1]))
+    assert exported == FUNCTIONS                              # and nothing else of this unit: the library has one kernel form
+    assert int(re.search(r"#define RT_CAPI_CLAMP_VERSION (\d+)", text).group(1)) == lib.rt_capi_clamp_version() == 1
+    assert C.sizeof(capi.RtClampParams) == 32
+    # no render kernel came with the unit
+    assert not [p[-1] for p in lines if p[-1].startswith("rt_render_kernel") and "clamp" in p[-1]]
+    # the accumulate headers point here for what they do not provide
+    for header in ("rt_motion.h", "rt_temporal.h"):
+        assert "rt_clamp.h" in open(os.path.join(INCLUDE, header)).read(), header
+
+
+def test_header_is_plain_c99_with_every_other_header_and_the_struct_is_32_bytes(tmp_path):
+    if not shutil.which("gcc"):
+        pytest.skip("no gcc")
+    others = sorted(f for f in os.listdir(INCLUDE) if f.endswith(".h"))
+    assert "rt_clamp.h" in others and len(others) >= 24
+    for first in ('#include "rt_clamp.h"\n', ""):                # on its own before every other header, and among them
+        src = tmp_path / "clamp.c"
+        src.write_text(first + "".join(f'#include "{h}"\n' for h in others) +
+                       "#include <stddef.h>\n"
+                       "int main(void) { rt_clamp_params p = {3, 0, 1, 1, 3, 4, 0.9f, 1.0f};\n"
+                       "  return (RT_CAPI_CLAMP_VERSION == 1 && sizeof p == 32 && offsetof(rt_clamp_params, clip_history) == 20\n"
+                       "          && offsetof(rt_clamp_params, normal_cos) == 24 && offsetof(rt_clamp_params, gamma) == 28\n"
+                       "          && p.gamma == 1.0f) ? 0 : 1; }\n")
+        exe = tmp_path / "clamp"
+        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", INCLUDE, str(src), "-o", str(exe)],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        assert subprocess.run([str(exe)]).returncode == 0
+
+
+# ---- 2. the argument checks, in the header's order, without a device ---------------------------------------------------------
+
+P = capi.RtClampParams
+GOOD = (3, 0, 1, 1, 3, 4, 0.9, 1.0)
+NAN, INF = float("nan"), float("inf")
+UP = float(np.nextafter(F(1), F(2)))                            # the first float above 1
+DOWN = float(np.nextafter(F(-1), F(-2)))
+TINY = float(np.nextafter(F(0), F(-1)))                         # the first float below 0
+# each bad value -- the first refused one on either side of its range -- with every later field bad too, and the word of the
+# message that names the first
+BAD_PARAMS = [((c, 2, 0, 2, 0, 0, NAN, -1.0), "channels") for c in (0, 2, 4)]
+BAD_PARAMS += [((3, b, 0, 2, 0, 0, NAN, -1.0), "box must") for b in (-1, 2)]
+BAD_PARAMS += [((1, 1, r, 2, 0, 0, NAN, -1.0), "radius") for r in (0, 4)]
+BAD_PARAMS += [((3, 0, 3, m, 0, 0, NAN, -1.0), "match_color") for m in (-1, 2)]
+BAD_PARAMS += [((3, 0, 1, 1, t, 0, NAN, -1.0), "min_taps") for t in (0, 50)]
+BAD_PARAMS += [((3, 0, 1, 0, 49, h, NAN, -1.0), "clip_history") for h in (0, 65536)]
+BAD_PARAMS += [((3, 0, 1, 0, 1, 65535, v, -1.0), "normal_cos") for v in (NAN, UP, DOWN, INF)]
+BAD_PARAMS += [((3, 0, 1, 0, 1, 1, 1.0, v), "gamma") for v in (TINY, NAN, INF)]
+# the last admitted values of every range
+EDGE_PARAMS = [(1, 1, 1, 0, 1, 1, -1.0, 0.0), (3, 0, 3, 1, 49, 65535, 1.0, 3e38), (3, 1, 2, 1, 9, 4, -0.0, 1e-45)]
+
+CUR, HITS, VALUE, MOMENTS, LEN = 0x100000, 0x200000, 0x300000, 0x400000, 0x500000
+OUT_VALUE, OUT_MOMENTS, OUT_LEN, OUT_VARIANCE, OUT_FLAGS = 0x700000, 0x800000, 0x900000, 0xA00000, 0xB00001
+ALL = (CUR, HITS, VALUE, MOMENTS, LEN, OUT_VALUE, OUT_MOMENTS, OUT_LEN, OUT_VARIANCE, OUT_FLAGS)   # fake: no check dereferences one
+WORDS = ALL[:9] + (0xB00000,)                                   # the flags on a word, so that a float output may stand there
+NONE = (None,) * 10
+
+
+def _call(params, Wn, H, pointers, device_call, device=0):
+    """pointers: (cur, hits, value, moments, len, the five outputs), addresses"""
+    lib = capi.load_library()
+    p = C.byref(params) if params is not None else None
+    fn = lib.rt_history_clamp_device if device_call else lib.rt_history_clamp
+    rc = fn(device, p, Wn, H, *pointers, None)
+    return rc, lib.rt_last_error().decode()
+
+
+def test_every_argument_check_comes_before_the_device_in_the_headers_order(have_gpu):
+    INV = capi.RT_ERR_INVALID
+    for device_call in (False, True):
+        rc, msg = _call(None, 0, 0, NONE, device_call)
+        assert rc == INV and "params" in msg
+        for bad, word in BAD_PARAMS:
+            rc, msg = _call(P(*bad), 0, 0, NONE, device_call)
+            assert rc == INV and word in msg, (bad, msg)
+        for Wn, H in ((0, 3), (4, 0), (-1, 3), (4, -2)):
+            rc, msg = _call(P(*GOOD), Wn, H, NONE, device_call)
+            assert rc == INV and "Wn, H" in msg, (Wn, H, msg)
+        for Wn, H in ((1 << 15, 1 << 15), (533333334, 1), (23095, 23094)):
+            assert "too large" in _call(P(*GOOD), Wn, H, NONE, device_call)[1]
+        for Wn, H in ((23094, 23094), (533333333, 1), (1, 533333333)):
+            rc, msg = _call(P(*GOOD), Wn, H, NONE, device_call)        # allowed: the next check speaks
+            assert rc == INV and "NULL" in msg
+        for edge in EDGE_PARAMS:
+            assert "is NULL" in _call(P(*edge), 8, 6, NONE, device_call)[1]
+        for missing in range(8):                                     # every required buffer, the records misaligned as well
+            args = list(ALL)
+            args[1] = HITS + 8
+            args[missing] = None
+            rc, msg = _call(P(*GOOD), 8, 6, args, device_call)
+            assert rc == INV and "is NULL" in msg, (missing, msg)
+    # the device variant: the records' alignment, then the floats', then the overlaps
+    for off in (4, 8, 12):
+        args = list(ALL)
+        args[1] += off
+        args[0] += 2                                                 # (a misaligned float too)
+        rc, msg = _call(P(*GOOD), 8, 6, args, True)
+        assert rc == INV and "16-byte" in msg, off
+    for slot in (0, 2, 3, 4, 5, 6, 7, 8):
+        args = list(ALL)
+        args[slot] += 2
+        args[9] = HITS                                               # (an overlapping output too)
+        rc, msg = _call(P(*GOOD), 8, 6, args, True)
+        assert rc == INV and "4-byte" in msg, slot
+    # a 4 x 6 rectangle of three channels: cur and value 288 bytes, records 1152, moments 192, length and variance 96, flags 24
+    size = {0: 288, 1: 1152, 2: 288, 3: 192, 4: 96, 5: 288, 6: 192, 7: 96, 8: 96, 9: 24}
+    cases = []
+    for o in range(5, 10):
+        step = 1 if o == 9 else 4
+        for q in list(range(5)) + [k for k in range(5, 10) if k != o]:
+            own = q == o - 3 and o < 8
+            word = "d_cur or d_hits" if q < 2 else "another output" if q >= 5 else "an input"
+            cases += [(o, WORDS[q], not own, word), (o, WORDS[q] + size[q] - step, True, word), (o, WORDS[q] - size[o] + step, True, word),
+                      (o, WORDS[q] + size[q], False, word), (o, WORDS[q] - size[o], False, word)]
+            if own:
+                cases += [(o, WORDS[q] + 4, True, "partially"), (o, WORDS[q] - 4, True, "partially")]
+    for o, address, refused, word in cases:
+        args = list(WORDS)
+        args[o] = address
+        rc, msg = _call(P(*GOOD), 4, 6, args, True, device=-1)
+        # (in place and adjacent are not overlapping: the call goes on to the device, whose index is bad or which there is none of)
+        assert rc != capi.RT_OK and ("overlaps" in msg) == refused and (not refused or (rc == INV and word in msg)), (o, hex(address), msg)
+    args = list(WORDS)
+    args[5:8] = args[2:5]                                            # the whole history in place
+    rc, msg = _call(P(*GOOD), 4, 6, args, True, device=-1)
+    assert rc != capi.RT_OK and "overlaps" not in msg
+    if have_gpu:
+        return
+    NODEV = capi.RT_ERR_NO_DEVICE                                    # every admitted edge reaches the device check
+    for edge in EDGE_PARAMS:
+        assert _call(P(*edge), 4, 6, args, True)[0] == NODEV
+        assert _call(P(*edge), 4, 6, ALL[:8] + (None, None), True)[0] == NODEV
+    host = [np.zeros(n, dtype=np.uint8) for n in (288, 1152, 288, 192, 96, 288, 192, 96, 96, 24)]
+    assert _call(P(*GOOD), 4, 6, [a.ctypes.data for a in host], False)[0] == NODEV
+    assert _call(P(*GOOD), 4, 6, [a.ctypes.data for a in host[:8]] + [None, None], False)[0] == NODEV
+
+
+def test_python_wrappers_refuse_without_a_device(have_gpu):
+    from tilecoderaytracer_amd import clamp_params, history_clamp
+    pr = clamp_params()
+    assert [getattr(pr, n) for n, _ in pr._fields_][:6] == [3, 0, 1, 1, 3, 4] and (pr.normal_cos, pr.gamma) == (float(F(0.9)), 1.0)
+    pr = clamp_params(1, 1, 3, False, 9, 2, 0.5, 2.0)
+    assert [getattr(pr, n) for n, _ in pr._fields_] == [1, 1, 3, 0, 9, 2, 0.5, 2.0]
+    hits = np.zeros((8, 6), dtype=HIT_DTYPE)
+    cur, moments, length = np.zeros((8, 6, 3), dtype=F), np.zeros((8, 6, 2), dtype=F), np.zeros((8, 6), dtype=F)
+    with pytest.raises(ValueError):
+        history_clamp(cur, hits, cur[..., 0], moments, length)
+    with pytest.raises(ValueError):
+        history_clamp(cur, hits, cur, moments[:7], length)
+    with pytest.raises(TypeError):
+        history_clamp(cur, hits, cur, moments, length, channels=3)
+    if have_gpu:
+        pytest.skip("a GPU is present")
+    from tilecoderaytracer_amd import RtError
+    with pytest.raises(RtError) as e:
+        history_clamp(cur, hits, cur, moments, length)
+    assert e.value.code == capi.RT_ERR_NO_DEVICE
+    with pytest.raises(RtError) as e:
+        history_clamp(cur[..., 0], hits, cur[..., 0], moments, length, radius=4)
+    assert e.value.code == capi.RT_ERR_INVALID and "radius" in e.value.message
+
+
+# ---- 3. clamp_ref: the definition ---------------------------------------------------------------------------------------------------
+
+SPECIAL = np.array([np.nan, np.inf, -np.inf, 1e-40, -1e-45, -0.0, 0.0, 3e38, -3e38, 1e-38], dtype=F)
+SPECIAL_LEN = np.array([0.0, 0.25, 1.0, 1.0000001, np.nan, np.inf, -1.0, -0.0, 1e-40, 70000.0], dtype=F)
+
+
+def made_up_inputs(seed, Wn, H, channels, special=True):
+    """records (test_upsample_gpu.random_frame: dead records, lights and inside hits among them), this frame's samples, and an
+    accumulated history around them -- a third of the values far from the samples, so that pixels are clipped and pixels are not
+    -> (cur, hits, value, moments, length); special: NaN, infinities, denormals and -0.0 sprinkled into cur, value, moments,
+    length and the records' normals and colours"""
+    rng = np.random.default_rng(seed)
+    hits = random_frame(seed, Wn, H)
+    shape = (Wn, H, 3) if channels == 3 else (Wn, H)
+    smooth = rng.random(shape, dtype=F) * F(0.2) + F(0.4)
+    cur = (smooth + np.where(rng.random(shape) < 0.1, F(0.4), F(0.0))).astype(F)
+    _, moments, length = made_up_history(seed + 1, Wn, H, channels)
+    value = np.where(rng.random(shape) < 0.35, rng.random(shape, dtype=F), cur + (rng.random(shape, dtype=F) - F(0.5)) * F(0.02)).astype(F)
+    length = length.copy()
+    length[rng.random((Wn, H)) < 0.1] = F(1.0)                   # pixels without history
+
+    def sprinkle(a, share, values=SPECIAL):
+        flat = a.reshape(-1)
+        pick = rng.random(flat.shape) < share
+        flat[pick] = rng.choice(values, int(pick.sum()))
+
+    if special:
+        sprinkle(cur, 0.03)
+        sprinkle(value, 0.03)
+        sprinkle(moments, 0.03)
+        sprinkle(length, 0.06, SPECIAL_LEN)
+        for field in ("normal", "color"):
+            a = hits[field].copy()
+            sprinkle(a, 0.01)
+            hits[field] = a
+    return cur, hits, value, moments, length
+
+
+def by_hand(cur, hits, value, moments, length, x, z, box, radius, match_color, min_taps, clip_history, normal_cos, gamma):
+    """pixel (x, z) by the header's definition, every operation on np.float32 scalars -> (value list, m1, m2, len, variance, flag)"""
+    Wn, H = hits.shape
+    zero, one = F(0.0), F(1.0)
+    h = hits[x, z]
+    c, v = [F(t) for t in np.atleast_1d(cur[x, z])], [F(t) for t in np.atleast_1d(value[x, z])]
+    n = len(c)
+    m1, m2, L = F(moments[x, z, 0]), F(moments[x, z, 1]), F(length[x, z])
+    lum = lambda w: (F(0.25) * w[0] + F(0.5) * w[1]) + F(0.25) * w[2] if n == 3 else w[0]
+    dead = lambda g: g["object"] < 0 or (g["flags"] & 2) != 0
+
+    def result(vo, m1o, m2o, Lo, flag):
+        t = m2o - m1o * m1o
+        return vo, m1o, m2o, Lo, (t if t > 0 else zero), flag
+
+    if dead(h) or not L > one:
+        return result(v, m1, m2, L, 0)
+    cnt, s1, s2, mn, mx = zero, [zero] * n, [zero] * n, list(c), list(c)
+    for a in range(-radius, radius + 1):
+        for b in range(-radius, radius + 1):
+            xq, zq = x + a, z + b
+            if not (0 <= xq < Wn and 0 <= zq < H):
+                continue
+            g = hits[xq, zq]
+            if (a, b) != (0, 0):
+                if dead(g) or g["object"] != h["object"] or (g["flags"] & 3) != (h["flags"] & 3):
+                    continue
+                if match_color and g["color"].tobytes() != h["color"].tobytes():
+                    continue
+                n_p, n_q = [F(t) for t in h["normal"]], [F(t) for t in g["normal"]]
+                if not (n_p[0] * n_q[0] + n_p[1] * n_q[1]) + n_p[2] * n_q[2] >= F(normal_cos):
+                    continue
+            cq = [F(t) for t in np.atleast_1d(cur[xq, zq])]
+            cnt = cnt + one
+            for k in range(n):
+                s1[k] = s1[k] + cq[k]
+                s2[k] = s2[k] + cq[k] * cq[k]
+                if cq[k] < mn[k]:
+                    mn[k] = cq[k]
+                if cq[k] > mx[k]:
+                    mx[k] = cq[k]
+    if cnt < F(min_taps):
+        return result(v, m1, m2, L, 2)
+    vo, clipped = list(v), False
+    for k in range(n):
+        lo, hi = mn[k], mx[k]
+        if box == 1:
+            mean, e2 = s1[k] / cnt, s2[k] / cnt
+            var = e2 - mean * mean
+            var = var if var > 0 else zero
+            w = F(gamma) * np.sqrt(var)
+            lo, hi = mean - w, mean + w
+        if v[k] < lo:
+            vo[k], clipped = lo, True
+        if vo[k] > hi:
+            vo[k], clipped = hi, True
+    if not clipped:
+        return result(v, m1, m2, L, 0)
+    Lo = L if L <= F(clip_history) else F(clip_history)
+    m1o = m1 + (lum(vo) - lum(v))
+    m2o = m2 + (m1o * m1o - m1 * m1)
+    return result(vo, m1o, m2o, Lo, 1)
+
+
+def assert_ref_is_by_hand(cur, hits, value, moments, length, what, **kw):
+    out = clamp_ref.clamp(cur, hits, value, moments, length, **kw)
+    Wn, H = hits.shape
+    with np.errstate(all="ignore"):
+        for x in range(Wn):
+            for z in range(H):
+                vo, m1, m2, Lo, var, flag = by_hand(cur, hits, value, moments, length, x, z, **kw)
+                got = [np.atleast_1d(out[0][x, z]), out[1][x, z], out[2][x, z], out[3][x, z]]
+                want = [np.array(vo, dtype=F), np.array([m1, m2], dtype=F), F(Lo), F(var)]
+                for g, w, name in zip(got, want, NAMES):
+                    assert same_bits(g, w), (what, kw, x, z, name, g, w)
+                assert int(out[4][x, z]) == flag, (what, kw, x, z)
+    return out
+
+
+@pytest.mark.parametrize("channels", [3, 1])
+@pytest.mark.parametrize("box", [0, 1])
+def test_ref_equals_the_definition_in_float32_scalars_on_made_up_records(box, channels):
+    seen = np.zeros(3, dtype=np.int64)
+    for Wn, H in ((7, 5), (23, 70)):
+        cur, hits, value, moments, length = made_up_inputs(Wn * 100 + H + channels, Wn, H, channels)
+        for radius in (1, 2, 3):
+            kw = dict(box=box, radius=radius, match_color=bool((radius + channels) % 2), min_taps=(1, 3, 6)[radius - 1],
+                      clip_history=(4, 1, 2)[radius - 1], normal_cos=(0.3, -1.0, 0.7)[radius - 1], gamma=(1.0, 0.5, 2.0)[radius - 1])
+            out = assert_ref_is_by_hand(cur, hits, value, moments, length, f"{Wn}x{H}", **kw)
+            seen += np.bincount(out[4].reshape(-1), minlength=3)[:3]
+    assert (seen >= 60).all(), seen                               # untouched, clipped and left for too few taps
+
+
+def test_ref_at_the_edges_of_its_parameters():
+    """normal_cos 1 (a tap's normal must be the pixel's own, to rounding), min_taps above the window's count (every walked pixel
+    is left, flag 2), min_taps 1 on records none of whose taps count but the pixel itself, and clip_history at its ends"""
+    Wn, H = 7, 5
+    cur, hits, value, moments, length = made_up_inputs(3, Wn, H, 3)
+    assert_ref_is_by_hand(cur, hits, value, moments, length, "normal_cos 1", box=0, radius=2, match_color=False, min_taps=1,
+                          clip_history=65535, normal_cos=1.0, gamma=1.0)
+    out = assert_ref_is_by_hand(cur, hits, value, moments, length, "min_taps 10 of 9", box=1, radius=1, match_color=True, min_taps=10,
+                                clip_history=1, normal_cos=-1.0, gamma=0.0)
+    walked = ~clamp_ref.dead_records(hits) & (length > F(1.0))
+    assert walked.sum() >= 10 and (out[4][walked] == 2).all() and (out[4][~walked] == 0).all()
+    same_words(out[:3], (value, moments, length), "nothing changes")
+    flat = hits.copy()
+    flat["normal"] = (0.0, 1.0, 0.0)
+    out = assert_ref_is_by_hand(cur, flat, value, moments, length, "gamma 0", box=1, radius=3, match_color=False, min_taps=49,
+                                clip_history=3, normal_cos=1.0, gamma=0.0)
+    assert (out[4] == 2).sum() >= 10                              # a 7 x 5 rectangle has no 49 taps
+
+
+# ---- 4. WHAT FOLLOWS, line by line -------------------------------------------------------------------------------------------------
+
+KWS = [dict(box=0, radius=1, match_color=True, min_taps=3, clip_history=4, normal_cos=0.3, gamma=1.0),
+       dict(box=1, radius=2, match_color=False, min_taps=1, clip_history=2, normal_cos=-1.0, gamma=1.0),
+       dict(box=1, radius=3, match_color=True, min_taps=5, clip_history=1, normal_cos=0.5, gamma=2.0),
+       dict(box=0, radius=3, match_color=False, min_taps=1, clip_history=65535, normal_cos=0.9, gamma=0.0)]
+
+
+@pytest.mark.parametrize("channels", [3, 1])
+def test_a_pixel_that_is_not_clipped_keeps_the_accumulate_calls_words_and_variance(channels):
+    """value, moments and length of a real accumulation (temporal_ref over made-up records, NaN and infinities in them), so
+    that the variance the accumulate call wrote exists: it is the clamp's wherever the pixel is not clipped -- +0.0 for a pixel
+    without history included"""
+    Wn, H = 23, 70
+    cur, hits, history, moments, length = made_up_inputs(40 + channels, Wn, H, channels)
+    cam = cameras.camera((0.0, -12.0, 0.0), (0.0, 0.0, 0.0), up=(0.0, 0.0, 1.0))
+    prev_hits = hits.copy()
+    prev_hits["object"][::5, ::3] = 2                            # pixels whose surface was another one: no history
+    acc = temporal_ref.accumulate(cur, hits, cam, (cam, prev_hits, history, moments, length), normal_cos=-1.0, plane_eps=0.0)
+    assert acc[4].sum() >= 100 and (~acc[4]).sum() >= 500
+    for kw in KWS:
+        out = clamp_ref.clamp(cur, hits, acc[0], acc[1], acc[2], **kw)
+        keep = out[4] != 1
+        assert keep.sum() >= 200 and (~keep).sum() >= 50, kw
+        same_words([o[keep] for o in out[:4]], [a[keep] for a in acc[:4]], f"not clipped {kw}")
+        none = acc[4] & ~clamp_ref.dead_records(hits)
+        assert (out[4][none] == 0).all() and (out[3][none].view(np.uint32) == 0).all()
+        clipped = out[4] == 1
+        assert (out[2][clipped] <= F(kw["clip_history"])).all() and (acc[2][clipped] > 1).all()
+
+
+@pytest.mark.parametrize("channels", [3, 1])
+def test_the_call_on_its_own_output_changes_nothing(channels):
+    for seed, (Wn, H) in enumerate(((7, 5), (23, 70))):
+        cur, hits, value, moments, length = made_up_inputs(60 + seed + channels, Wn, H, channels)
+        for kw in KWS:
+            once = clamp_ref.clamp(cur, hits, value, moments, length, **kw)
+            twice = clamp_ref.clamp(cur, hits, once[0], once[1], once[2], **kw)
+            same_words(twice[:4], once[:4], f"twice {kw}")
+            assert not (twice[4] == 1).any() and ((twice[4] == 2) == (once[4] == 2))[once[2] > 1].all()
+            assert Wn < 20 or (once[4] == 1).sum() >= 100
+
+
+def test_with_the_extremes_box_a_value_within_its_windows_samples_is_never_touched_and_an_isolated_pixel_takes_its_sample():
+    Wn, H = 23, 70
+    cur, hits, value, moments, length = made_up_inputs(81, Wn, H, 3, special=False)
+    rng = np.random.default_rng(82)
+    for radius in (1, 2, 3):
+        kw = dict(box=0, radius=radius, match_color=True, min_taps=1, clip_history=4, normal_cos=0.3)
+        info = clamp_ref.clamp(cur, hits, value, moments, length, details=True, **kw)[5]
+        # a value between the pixel's own sample and that of a tap that counts -- any tap: the left neighbour where it counts
+        inside = value.copy()
+        t = rng.random((Wn, H, 1), dtype=F)
+        inside[1:] = cur[1:] + t[1:] * (cur[:-1] - cur[1:])
+        inside[0] = cur[0]
+        out = clamp_ref.clamp(cur, hits, inside, moments, length, **kw)
+        alone = clamp_ref.clamp(cur, hits, inside, moments, length, **dict(kw, radius=1, normal_cos=-1.0, match_color=False))
+        left = np.zeros((Wn, H), dtype=bool)
+        left[1:] = (hits["object"][1:] == hits["object"][:-1]) & ((hits["flags"][1:] & 3) == (hits["flags"][:-1] & 3)) & \
+            ~clamp_ref.dead_records(hits)[:-1]
+        assert left.sum() >= 500 and (alone[4][left] == 0).all()
+        inside[~left] = cur[~left]                               # everywhere else the sample itself
+        out = clamp_ref.clamp(cur, hits, inside, moments, length, **dict(kw, normal_cos=-1.0, match_color=False))
+        assert (out[4] == 0).all()
+        same_words(out[:3], (inside, moments, length), f"within the window, radius {radius}")
+        # an isolated pixel -- one tap, itself -- takes its own sample at min_taps 1, and is left alone at min_taps 2
+        out = clamp_ref.clamp(cur, hits, value, moments, length, **kw)
+        isolated = info["walked"] & (info["taps"] == 1)
+        assert isolated.sum() >= 20, radius
+        differs = isolated & (value != cur).any(axis=-1)
+        assert (out[4][differs] == 1).all() and same_bits(out[0][isolated], cur[isolated])
+        out = clamp_ref.clamp(cur, hits, value, moments, length, **dict(kw, min_taps=2))
+        assert (out[4][isolated] == 2).all() and same_bits(out[0][isolated], value[isolated])
+
+
+def test_a_strip_differs_from_the_frames_columns_only_within_radius_columns_of_its_edges():
+    Wn, H = 23, 70
+    for channels in (3, 1):
+        cur, hits, value, moments, length = made_up_inputs(90 + channels, Wn, H, channels)
+        for kw in KWS:
+            full = clamp_ref.clamp(cur, hits, value, moments, length, **kw)
+            r, x0, x1 = kw["radius"], 5, 19
+            part = lambda a: np.ascontiguousarray(a[x0:x1])
+            strip = clamp_ref.clamp(part(cur), part(hits), part(value), part(moments), part(length), **kw)
+            same_words([s[r:x1 - x0 - r] for s in strip], [f[x0 + r:x1 - r] for f in full], f"strip {kw}")
+            assert any(s[:r].tobytes() != f[x0:x0 + r].tobytes() for s, f in zip(strip, full)), kw
+
+
+# ---- 5. the conditions on the ghost pixels ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", GHOST_PAIRS)
+def test_the_clamp_halves_the_ghost_and_touches_no_unchanged_pixel(name):
+    """Measured with the reference at 192 x 128, box 0, r = 1, the other parameters at their defaults (min_taps 3, clip_history 4,
+    normal_cos 0.9): spheres_equal 262 ghost pixels, error 0.378 without and 0.145 with the clamp (0.38 x), 17 373 unchanged
+    pixels, none clipped, 370 pixels clipped in all; sphere_leaves 364 ghost pixels, 0.374 and 0.143 (0.38 x), 17 254 unchanged
+    pixels, none clipped, 558 clipped in all."""
+    cur, hits, value, moments, length, ghost, unchanged = ghost_setting(name, 192, 128)
+    out = clamp_ref.clamp(cur, hits, value, moments, length, **GHOST_KW)
+    without, with_clamp = ghost_error(value, cur, ghost), ghost_error(out[0], cur, ghost)
+    clipped = out[4] == 1
+    print(name, "ghost pixels", int(ghost.sum()), "error without", without, "with", with_clamp, "ratio", with_clamp / without,
+          "unchanged", int(unchanged.sum()), "of them clipped", int((clipped & unchanged).sum()), "clipped", int(clipped.sum()))
+    assert ghost.sum() >= 200
+    assert with_clamp <= 0.5 * without
+    assert unchanged.sum() >= 10000 and not (clipped & unchanged).any()
+    assert clipped.any() and (out[2][clipped] <= F(4)).all()

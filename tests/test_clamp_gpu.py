@@ -1,0 +1,415 @@
+"""Neighbourhood clipping of an accumulated history (include/rt_clamp.h) on the GPU against its definition: rt_history_clamp and
+rt_history_clamp_device against clamp_ref bit for bit -- value, moments, length, variance and flags -- over rendered sequences of
+the motion scene's pose pairs pushed through rt_motion_accumulate, rectangles smaller than a tile and than the window, a frame of
+more than 1024 x 1024, synthetic records with special values in every input, in place against out of place, strips, the device
+entry point behind rt_motion_accumulate_device on one stream (eager, and captured in a graph and replayed once), and the composed
+calls.  The device entry point writes into sentinel-filled guarded outputs.  Bar: BIT-EXACT."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import clamp_ref
+import motion_ref
+import motion_scenes
+import poisoned
+import temporal_ref
+from large_extents import SENTINEL_BYTE, Guarded
+from test_clamp_cpu import KWS, made_up_inputs
+from test_temporal_cpu import made_up_history
+from test_upsample_gpu import assert_same
+from tilecoderaytracer_amd import (Renderer, TemporalHistory, capi, history_clamp, motion_accumulate, render_animated,
+                                   temporal_accumulate)
+from tilecoderaytracer_amd.renderer import clamp_params, temporal_params
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+NAMES = clamp_ref.NAMES
+# both boxes x every radius x both settings of match_color, and every value of the other parameters
+COMBOS = [dict(box=box, radius=radius, match_color=bool((box + radius) % 2), min_taps=(3, 1, 6)[radius - 1],
+               clip_history=(4, 1, 65535)[radius - 1], normal_cos=(0.9, -1.0, 0.5)[radius - 1], gamma=(1.0, 2.0, 0.0)[radius - 1])
+          for box in (0, 1) for radius in (1, 2, 3)]
+
+
+def assert_all_same(got, want, what):
+    for g, w, name in zip(got, want, NAMES):
+        if g is not None:
+            assert_same(g, w, f"{what}: {name}")
+
+
+def device_clamp(cur, hits, value, moments, length, want, in_place=False, optional=True, **kw):
+    """rt_history_clamp_device into sentinel-filled outputs -- in place: value, moments and length into (copies of) the inputs
+    themselves -> the five outputs (variance and flags None without `optional`); every word of the outputs written, none beside,
+    and no input changed but those written in place"""
+    import torch
+    channels = 3 if cur.ndim == 3 else 1
+    Wn, H = hits.shape
+    params = clamp_params(channels, **kw)
+    what = f"rt_history_clamp_device {Wn}x{H} channels {channels} in place {in_place} {kw}"
+    poisoned.assert_reference_has_no_sentinel(list(want[:4]), what)
+    poisoned.assert_reference_has_no_sentinel(want[4], what)
+    d_in = [poisoned._on_device(np.ascontiguousarray(a).reshape(-1).view(np.int32)) for a in (cur, hits, value, moments, length)]
+    before = [t.clone() for t in d_in]
+    n = Wn * H
+    specs = [(n * channels, channels, False), (n * 2, 2, False), (n, 1, False), (n, 1, False), (n, 1, True)]
+    bufs = [Guarded(words + poisoned.SLACK_CELLS * per, as_bytes=b) for words, per, b in specs]
+    out_ptrs = [t.data_ptr() for t in d_in[2:]] if in_place else [g.ptr for g in bufs[:3]]
+    out_ptrs += [g.ptr for g in bufs[3:]] if optional else [None, None]
+    capi.check(capi.load_library().rt_history_clamp_device(0, C.byref(params), Wn, H, *[t.data_ptr() for t in d_in], *out_ptrs,
+                                                           poisoned._stream()))
+    torch.cuda.synchronize()
+    for k, (t, b) in enumerate(zip(d_in, before)):
+        assert (in_place and k >= 2) or torch.equal(t, b), f"{what}: an input was written"
+    out = []
+    for k, (g, (words, per, as_bytes)) in enumerate(zip(bufs, specs)):
+        if (k < 3 and in_place) or (k >= 3 and not optional):
+            assert g.sentinels_left() == g.n and g.guards_untouched(), f"{what}: {NAMES[k]} was written"
+            out.append(d_in[k + 2].cpu().numpy() if k < 3 else None)
+            continue
+        host = g.all.cpu().numpy()
+        body = poisoned.check_output(host[:g.guard], host[g.guard:g.guard + g.n], host[g.guard + g.n:], words,
+                                     poisoned.layout(per, H), f"{what}, {NAMES[k]}", SENTINEL_BYTE if as_bytes else poisoned.SENTINEL)
+        out.append(body.copy())
+    for g in bufs:
+        g.free()
+    shape = (Wn, H)
+    return (out[0].view(F).reshape(shape + ((3,) if channels == 3 else ())), out[1].view(F).reshape(shape + (2,)),
+            out[2].view(F).reshape(shape), out[3].view(F).reshape(shape) if out[3] is not None else None,
+            out[4].reshape(shape) if out[4] is not None else None)
+
+
+def both_ways(cur, hits, value, moments, length, what, device=True, in_place=False, **kw):
+    """the host call and (device) the device entry point against the reference -> the reference's outputs"""
+    want = clamp_ref.clamp(cur, hits, value, moments, length, **kw)
+    assert_all_same(history_clamp(cur, hits, value, moments, length, **kw), want, f"{what} {kw}")
+    if device:
+        assert_all_same(device_clamp(cur, hits, value, moments, length, want, in_place=in_place, **kw), want, f"{what} {kw}, device")
+    return want
+
+
+# ---- 1. rendered sequences ---------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def rendered_pair(name, W, H, frames=3):
+    """`frames` frames of the pair's previous pose and one of its current pose, the G-buffer's colours at depth 3 as the term,
+    pushed through rt_motion_accumulate with the pair's table -> {channels: (cur, hits, value, moments, length) of the last frame}"""
+    cam_prev, cam = motion_scenes.camera_pair(motion_scenes.PAIRS[name][2])
+    table = motion_scenes.table(name)
+    out = {}
+    frames_of = []
+    for pose, c in zip(motion_scenes.PAIRS[name][:2], (cam_prev, cam)):
+        r = Renderer(motion_scenes.host(pose))
+        own, r._cam = r._cam, C.pointer(c)
+        frames_of.append(r.render_gbuffer(W, H, 3))
+        r._cam = own
+        r.close()
+    for channels in (1, 3):
+        state = None
+        term = lambda rgb: rgb if channels == 3 else np.ascontiguousarray(temporal_ref.lum(rgb))
+        for _ in range(frames):
+            rgb, hits = frames_of[0]
+            value, moments, length, _, _ = motion_accumulate(term(rgb), hits, cam_prev, state, None, match_color=True)
+            state = (cam_prev, hits, value, moments, length)
+        rgb, hits = frames_of[1]
+        value, moments, length, _, _ = motion_accumulate(term(rgb), hits, cam, state, table, match_color=True)
+        out[channels] = (term(rgb), hits, value, moments, length)
+    return out
+
+
+@pytest.mark.parametrize("size", [(61, 37), (96, 64)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("name", ["spheres_equal", "box_dolly", "sphere_leaves"])
+def test_rendered_sequences_are_the_reference_bit_for_bit(name, size):
+    W, H = size
+    seq = rendered_pair(name, W, H)
+    clipped = 0
+    for k, kw in enumerate(COMBOS):
+        for channels in (1, 3):
+            want = both_ways(*seq[channels], f"{name} {W}x{H}", device=(k + channels) % 2 == 0, in_place=k % 3 == 0, **kw)
+            clipped += int((want[4] == 1).sum())
+            assert (want[2][want[4] == 1] <= kw["clip_history"]).all()
+    length = seq[3][4]
+    assert 3.5 < length.max() < 4.5 and (length > 1).mean() > 0.5 and clipped >= 100       # histories, and stale ones among them
+
+
+# ---- 2. small and awkward rectangles ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("Wn, H", [(1, 1), (1, 9), (2, 3), (5, 70), (3, 129), (4, 64), (9, 65), (67, 130)])
+def test_sizes_smaller_than_a_tile_and_the_window(Wn, H):
+    """H on either side of a wavefront's 64 lanes and of two, Wn on either side of a workgroup's four columns"""
+    for k, kw in enumerate(COMBOS):
+        channels = 3 if k % 2 else 1
+        inputs = made_up_inputs(Wn * 1000 + H + k, Wn, H, channels, special=False)
+        want = both_ways(*inputs, f"{Wn}x{H}", in_place=k % 2 == 0, **kw)
+        assert Wn * H < 300 or ((want[4] == 1).sum() >= 3 and (want[4] == 0).sum() >= 20)
+
+
+def test_a_frame_of_more_than_1024_squared():
+    Wn, H = 1100, 1030
+    inputs = made_up_inputs(21, Wn, H, 3, special=False)
+    want = both_ways(*inputs, "1100x1030", device=False, box=0, radius=1, match_color=False, min_taps=3, clip_history=4, normal_cos=0.3)
+    assert (want[4] == 1).mean() > 0.1 and (want[4] == 0).mean() > 0.3
+
+
+# ---- 3. synthetic records and special values ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("seed", range(12))
+def test_synthetic_records_and_special_values(seed):
+    """NaN, infinities, denormals and -0.0 in cur, value, moments, length, normals and colours; dead blocks"""
+    rng = np.random.default_rng(2000 + seed)
+    Wn, H = int(rng.integers(1, 100)), int(rng.integers(1, 140))
+    channels = 3 if seed % 2 else 1
+    cur, hits, value, moments, length = made_up_inputs(3000 + seed, Wn, H, channels)
+    if Wn > 8 and H > 8:
+        hits["object"][2:6, 3:8] = -1
+        hits["flags"][Wn - 4:, H - 3:] |= 2
+    kw = dict(COMBOS[seed % 6], match_color=bool(seed % 4 < 2), normal_cos=(0.3, 1.0, -1.0, 0.9)[seed % 4])
+    want = both_ways(cur, hits, value, moments, length, f"seed {seed} {Wn}x{H}", in_place=seed % 2 == 0, **kw)
+    dead = clamp_ref.dead_records(hits)
+    assert_same(want[0][dead], value[dead], "dead pixels pass through")
+    assert (want[4][dead] == 0).all()
+
+
+# ---- 4. in place, and the optional outputs --------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("channels", [3, 1])
+def test_in_place_is_out_of_place_and_the_optional_outputs_may_be_null(channels):
+    Wn, H = 37, 131
+    inputs = made_up_inputs(50 + channels, Wn, H, channels)
+    lib = capi.load_library()
+    for kw in KWS:
+        want = clamp_ref.clamp(*inputs, **kw)
+        assert (want[4] == 1).sum() >= 100
+        for in_place in (False, True):
+            for optional in (False, True):
+                got = device_clamp(*inputs, want, in_place=in_place, optional=optional, **kw)
+                assert_all_same(got, want, f"in place {in_place}, optional {optional}, {kw}")
+        # the host call in place, without its optional outputs, with the kernel's time
+        value, moments, length = (np.array(a, copy=True) for a in inputs[2:])
+        ms = C.c_double(-1.0)
+        params = clamp_params(channels, **kw)
+        capi.check(lib.rt_history_clamp(0, C.byref(params), Wn, H, inputs[0].ctypes.data, inputs[1].ctypes.data, value.ctypes.data,
+                                        moments.ctypes.data, length.ctypes.data, value.ctypes.data, moments.ctypes.data,
+                                        length.ctypes.data, None, None, C.byref(ms)))
+        assert_all_same((value, moments, length), want, f"the host call in place {kw}")
+        assert ms.value > 0.0
+        # the call on its own output changes nothing
+        again = history_clamp(inputs[0], inputs[1], value, moments, length, **kw)
+        assert_all_same(again[:4], want[:4], f"twice {kw}")
+        assert not (again[4] == 1).any()
+
+
+# ---- 5. strips ---------------------------------------------------------------------------------------------------------------------------
+
+def test_a_strip_differs_from_the_frames_columns_only_within_radius_columns_of_its_edges():
+    cur, hits, value, moments, length = rendered_pair("spheres_equal", 96, 64)[3]
+    x0, x1 = 20, 80
+    part = lambda a: np.ascontiguousarray(a[x0:x1])
+    for kw in COMBOS:
+        full = history_clamp(cur, hits, value, moments, length, **kw)
+        strip = both_ways(part(cur), part(hits), part(value), part(moments), part(length), "strip", device=False, **kw)
+        r = kw["radius"]
+        assert_all_same([s[r:x1 - x0 - r] for s in strip], [f[x0 + r:x1 - r] for f in full], f"strip {kw}")
+
+
+# ---- 6. the device path on one stream --------------------------------------------------------------------------------------------------------
+
+def accumulate_then_clamp(stream_ptr, params, clamp, cams, table, W, H, d_cur, d_hits, d_prev, outs):
+    """rt_motion_accumulate_device and rt_history_clamp_device, in place on its outputs, enqueued back to back"""
+    lib = capi.load_library()
+    capi.check(lib.rt_motion_accumulate_device(0, C.byref(params), C.byref(cams[0]), C.byref(cams[1]), W, H, 0, W, table.data_ptr(),
+                                               table.numel() // 12, d_cur.data_ptr(), d_hits.data_ptr(), *[t.data_ptr() for t in d_prev],
+                                               *[t.data_ptr() for t in outs[:5]], stream_ptr))
+    in_place = [t.data_ptr() for t in outs[:3]]
+    capi.check(lib.rt_history_clamp_device(0, C.byref(clamp), W, H, d_cur.data_ptr(), d_hits.data_ptr(), *in_place, *in_place,
+                                           outs[3].data_ptr(), outs[5].data_ptr(), stream_ptr))
+
+
+def test_device_entry_follows_the_accumulation_on_one_stream_eager_and_replayed_from_a_graph():
+    """rt_motion_accumulate_device and rt_history_clamp_device enqueued back to back with no host wait between them, the clamp in
+    place on the accumulation's outputs; then the same two calls captured on the same side stream and replayed once: the
+    replayed words are the eager ones and the definition's.  Both calls only enqueue, so the capture allocates nothing."""
+    import torch
+    W, H = 61, 37
+    cam_prev, cam, prev_hits, hits = motion_scenes.records("sphere_leaves", W, H)
+    table = motion_scenes.table("sphere_leaves")
+    cur = (F(0.5) * hits["color"] + np.random.default_rng(5).random((W, H, 3), dtype=F) * F(0.05)).astype(F)
+    value, moments, length = made_up_history(6, W, H, 3)
+    kw = dict(box=0, radius=1, match_color=True, min_taps=3, clip_history=2)
+    acc = motion_ref.accumulate(cur, hits, cam, (cam_prev, prev_hits, value, moments, length), table, match_color=True)
+    want = clamp_ref.clamp(cur, hits, acc[0], acc[1], acc[2], **kw)
+    assert (want[4] == 1).sum() >= 20 and (~acc[4]).sum() >= 1000
+    on = lambda a: poisoned._on_device(np.ascontiguousarray(a).reshape(-1).view(np.int32))
+    d_cur, d_hits, d_table = on(cur), on(hits), on(table)
+    d_prev = [on(a) for a in (prev_hits, value, moments, length)]
+    n = W * H
+    new = lambda: [torch.zeros((n * w,), dtype=torch.int32, device="cuda") for w in (3, 2, 1, 1)] + \
+        [torch.zeros((n,), dtype=torch.uint8, device="cuda") for _ in range(2)]
+    eager, replayed = new(), new()
+    params, clamp = temporal_params(3, match_color=True), clamp_params(3, **kw)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    accumulate_then_clamp(side.cuda_stream, params, clamp, (cam_prev, cam), d_table, W, H, d_cur, d_hits, d_prev, eager)
+    side.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        accumulate_then_clamp(torch.cuda.current_stream().cuda_stream, params, clamp, (cam_prev, cam), d_table, W, H, d_cur, d_hits,
+                              d_prev, replayed)
+    torch.cuda.synchronize()
+    assert all(int(b.abs().max()) == 0 for b in replayed[:4])                    # captured, not run
+    graph.replay()
+    torch.cuda.synchronize()
+    shapes = ((W, H, 3), (W, H, 2), (W, H), (W, H))
+    for outs, what in ((eager, "eager"), (replayed, "replayed")):
+        got = [t.cpu().numpy().view(F).reshape(s) for t, s in zip(outs[:4], shapes)] + [outs[5].cpu().numpy().reshape(W, H)]
+        assert_all_same(got, want, f"one stream, {what}")
+        assert_same(outs[4].cpu().numpy().reshape(W, H).view(np.bool_), acc[4], f"{what}: the accumulation's flags")
+    del graph
+    # refusals launch nothing
+    lib = capi.load_library()
+    g = Guarded(n * 3)
+    ptrs = [d_cur.data_ptr(), d_hits.data_ptr()] + [t.data_ptr() for t in eager[:3]]
+    for bad, out_value, word in (((ptrs[0], ptrs[1] + 8) + tuple(ptrs[2:]), g.ptr, "16-byte"),
+                                 ((ptrs[0] + 2,) + tuple(ptrs[1:]), g.ptr, "4-byte"),
+                                 (tuple(ptrs), ptrs[0], "d_cur or d_hits"), (tuple(ptrs), ptrs[2] + 4, "partially")):
+        rc = lib.rt_history_clamp_device(0, C.byref(clamp), W, H, *bad, out_value, ptrs[3], ptrs[4], None, None, None)
+        assert rc == capi.RT_ERR_INVALID and word in lib.rt_last_error().decode(), (word, lib.rt_last_error().decode())
+    rc = lib.rt_history_clamp_device(99, C.byref(clamp), W, H, *ptrs, g.ptr, ptrs[3], ptrs[4], None, None, None)
+    assert rc == capi.RT_ERR_INVALID and "device index" in lib.rt_last_error().decode()
+    torch.cuda.synchronize()
+    assert g.sentinels_left() == g.n and g.guards_untouched()
+
+
+# ---- 7. the composed calls ---------------------------------------------------------------------------------------------------------------
+
+SEQUENCE = [motion_scenes.REST, motion_scenes.REST, motion_scenes.SHIFTED, dict(motion_scenes.SHIFTED, angle=0.3, axis=(0.3, -0.2, 1.0))]
+CAMERAS = ["equal", "equal", "equal", "truck"]                   # the current camera of camera_pair()
+
+
+def sequence_tables():
+    from tilecoderaytracer_amd import object_motions
+    hosts = [motion_scenes.host(p) for p in SEQUENCE]
+    return hosts, [None] + [object_motions(a.desc, b.desc) for a, b in zip(hosts, hosts[1:])]
+
+
+def test_temporal_history_push_with_a_clamp_equals_the_public_calls():
+    W, H = 61, 37
+    kw = dict(max_history=8, match_color=True)
+    ckw = dict(box=1, radius=2, min_taps=2, clip_history=2, gamma=1.0)
+    hosts, tables = sequence_tables()
+    history, plain = TemporalHistory(W, H, 3, **kw), TemporalHistory(W, H, 3, **kw)
+    assert history.clamp_flags is None
+    state = plain_state = None
+    clipped = 0
+    for k, (host, cam_name, table) in enumerate(zip(hosts, CAMERAS, tables)):
+        cam = motion_scenes.camera_pair(cam_name)[1]
+        r = Renderer(host)
+        own, r._cam = r._cam, C.pointer(cam)
+        cur, hits = r.render_gbuffer(W, H, 3)
+        r._cam = own
+        r.close()
+        acc = motion_accumulate(cur, hits, cam, state, table, **kw)
+        value, moments, length, variance, cflags = history_clamp(cur, hits, acc[0], acc[1], acc[2], **ckw)
+        if k == 2:                                               # a frame pushed as two strips: each is clamped as a strip
+            parts = [history.push(cur[:23], hits[:23], cam, 0, 23, motions=table, clamp=ckw),
+                     history.push(cur[23:], hits[23:], cam, 23, motions=table, clamp=ckw)]
+            got = [np.concatenate([a, b]) for a, b in zip(*parts)]
+            halves = [history_clamp(cur[s], hits[s], acc[0][s], acc[1][s], acc[2][s], **ckw) for s in (slice(0, 23), slice(23, W))]
+            value, moments, length, variance, cflags = (np.concatenate([a, b]) for a, b in zip(*halves))
+        else:
+            got = history.push(cur, hits, cam, motions=table, clamp=ckw)
+        assert_same(got[0], value, f"push {k}: value")
+        assert_same(got[1], variance, f"push {k}: variance")
+        assert_same(got[2], acc[4], f"push {k}: flags")
+        assert_same(history.clamp_flags.cpu().numpy().reshape(W, H), cflags, f"push {k}: clamp flags")
+        state = (cam, hits, value, moments, length)
+        kept = history.state()
+        for a, b, name in zip(kept[2:], state[2:], NAMES):
+            assert_same(a, b, f"state after push {k}: {name}")
+        clipped += int((cflags == 1).sum())
+        # clamp=None is the push as it was
+        want = motion_accumulate(cur, hits, cam, plain_state, table, **kw)
+        assert_all_same(plain.push(cur, hits, cam, motions=table), (want[0], want[3], want[4]), f"plain push {k}")
+        plain_state = (cam, hits) + want[:3]
+    assert clipped >= 50 and plain.clamp_flags is None
+    with pytest.raises(capi.RtError):
+        history.push(cur, hits, cam, clamp=dict(radius=4))
+    with pytest.raises(TypeError):
+        TemporalHistory(W, H, 3).push(cur, hits, cam, clamp=dict(channels=3))
+
+
+@pytest.mark.parametrize("term", ["direct", "ao"])
+def test_render_animated_and_render_accumulated_with_a_clamp_are_the_composition_of_the_public_calls(term):
+    W, H, depth = 45, 38, 3
+    hosts, tables = sequence_tables()
+    renderers = [Renderer(h) for h in hosts]
+    cams = [motion_scenes.camera_pair(n)[1] for n in CAMERAS]
+    kw = dict(max_history=8, match_color=True)
+    ckw = dict(box=0, radius=1, min_taps=2, clip_history=2)
+    term_kw = dict(ao=dict(radius=2.0), direct=dict())[term]
+    state = plain_state = None
+    clipped = 0
+    for k, (r, cam, table) in enumerate(zip(renderers, cams, tables)):
+        own = r._cam
+        r._cam = C.pointer(cam)
+        if term == "direct":
+            r.set_shadow_seed(k)
+        rgb, hits = r.render_gbuffer(W, H, depth)
+        cur = rgb if term == "direct" else r.ambient_occlusion(hits, 1, seed=k, **term_kw)
+        r._cam = own
+        acc = motion_accumulate(cur, hits, cam, state, table, **kw)
+        value, moments, length, variance, cflags = history_clamp(cur, hits, acc[0], acc[1], acc[2], **ckw)
+        state = (cam, hits, value, moments, length)
+        clipped += int((cflags == 1).sum())
+        plain = motion_accumulate(cur, hits, cam, plain_state, table, **kw)
+        plain_state = (cam, hits) + plain[:3]
+    frames = list(zip(renderers, cams, tables))
+    got = render_animated(frames, W, H, depth, term=term, samples=1, clamp=ckw, **kw, **term_kw)
+    assert_all_same(got, (value, variance, acc[4]), f"render_animated {term} with a clamp")
+    got = render_animated(frames, W, H, depth, term=term, samples=1, **kw, **term_kw)
+    assert_all_same(got, (plain[0], plain[3], plain[4]), f"render_animated {term}, clamp=None")
+    assert clipped >= 20 and not np.array_equal(value, plain[0])
+    # render_accumulated: one renderer, the camera alone moves
+    r = renderers[0]
+    path = [motion_scenes.camera_pair(n)[1] for n in ("equal", "equal", "truck")]
+    state = plain_state = None
+    for k, cam in enumerate(path):
+        own = r._cam
+        r._cam = C.pointer(cam)
+        if term == "direct":
+            r.set_shadow_seed(k)
+        rgb, hits = r.render_gbuffer(W, H, depth)
+        cur = rgb if term == "direct" else r.ambient_occlusion(hits, 1, seed=k, **term_kw)
+        r._cam = own
+        acc = temporal_accumulate(cur, hits, cam, state, **kw)
+        value, moments, length, variance, cflags = history_clamp(cur, hits, acc[0], acc[1], acc[2], **ckw)
+        state = (cam, hits, value, moments, length)
+        plain = temporal_accumulate(cur, hits, cam, plain_state, **kw)
+        plain_state = (cam, hits) + plain[:3]
+    got = r.render_accumulated(path, W, H, depth, term=term, samples=1, clamp=ckw, **kw, **term_kw)
+    assert_all_same(got, (value, variance, acc[4]), f"render_accumulated {term} with a clamp")
+    got = r.render_accumulated(path, W, H, depth, term=term, samples=1, **kw, **term_kw)
+    assert_all_same(got, (plain[0], plain[3], plain[4]), f"render_accumulated {term}, clamp=None")
+    for r in renderers:
+        r.close()
+
+
+# ---- 8. the kernel form that was not kept ------------------------------------------------------------------------------------------------------
+
+def test_both_kernel_forms_where_the_library_has_them():
+    """A build with -DRT_CLAMP_VARIANTS=1, named in TCRT_LIBRARY, has both forms of the window's reads and the switch between
+    them: each is held to the reference.  The library proper has one form and no switch."""
+    lib = capi.load_library()
+    if not hasattr(lib, "rt_internal_clamp_variant"):
+        return
+    lib.rt_internal_clamp_variant.argtypes, lib.rt_internal_clamp_variant.restype = [C.c_int], C.c_int
+    kept = lib.rt_internal_clamp_variant(0)
+    try:
+        for form in (0, 1):
+            lib.rt_internal_clamp_variant(form)
+            for Wn, H in ((1, 1), (2, 3), (5, 70), (67, 130)):
+                for k, kw in enumerate(COMBOS):
+                    both_ways(*made_up_inputs(Wn + H + k, Wn, H, 3 if k % 2 else 1), f"form {form} {Wn}x{H}", in_place=k % 2 == 0, **kw)
+    finally:
+        lib.rt_internal_clamp_variant(kept)

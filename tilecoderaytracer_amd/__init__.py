@@ -18,8 +18,9 @@ from .renderer import svgf_filter, svgf_params  # noqa: F401
 from .renderer import motion_accumulate, object_motions, render_animated  # noqa: F401
 from .renderer import mirror_params  # noqa: F401
 from .renderer import glass_params  # noqa: F401
+from .renderer import clamp_params, history_clamp  # noqa: F401
 
 __all__ = ["RtError", "load_library", "library_path", "HostScene", "Renderer", "adaptive_flags", "denoise", "encode_image",
            "indirect_rays", "lens_rays", "subsample_hits", "upsample_guided", "TemporalHistory", "temporal_accumulate",
            "temporal_params", "svgf_filter", "svgf_params", "motion_accumulate", "object_motions", "render_animated",
-           "mirror_params", "glass_params"]
+           "mirror_params", "glass_params", "clamp_params", "history_clamp"]

@@ -87,6 +87,14 @@ class RtSvgfParams(C.Structure):
                 ("epsilon", C.c_float)]
 
 
+class RtClampParams(C.Structure):
+    """include/rt_clamp.h: channels (1 or 3), box (0 extremes, 1 moments), radius (1..3), match_color (0 / 1), the fewest counted
+    taps a pixel is clipped with (1..49), the length a clipped pixel keeps at most (1..65535), the normals' cosine a tap must keep
+    (-1..1) and the moments box's width in standard deviations (>= 0)."""
+    _fields_ = [("channels", C.c_int32), ("box", C.c_int32), ("radius", C.c_int32), ("match_color", C.c_int32),
+                ("min_taps", C.c_int32), ("clip_history", C.c_int32), ("normal_cos", C.c_float), ("gamma", C.c_float)]
+
+
 class RtAoParams(C.Structure):
     """include/rt_capi_ao.h: n (n x n directions per record, 1..8), the radius a direction is followed for, the seed, the first
     record's key, channels (1, or 3 equal ones)."""
@@ -473,6 +481,12 @@ def load_library():
         lib.rt_svgf_filter.restype = lib.rt_svgf_filter_device.restype = i
         lib.rt_svgf_scratch_bytes.argtypes = [C.POINTER(RtSvgfParams), i, i]
         lib.rt_svgf_scratch_bytes.restype = C.c_uint64
+    # include/rt_clamp.h (likewise absent from older builds)
+    if hasattr(lib, "rt_history_clamp"):
+        lib.rt_capi_clamp_version.restype = i
+        lib.rt_history_clamp.argtypes = [i, C.POINTER(RtClampParams), i, i] + [vp] * 10 + [C.POINTER(C.c_double)]
+        lib.rt_history_clamp_device.argtypes = [i, C.POINTER(RtClampParams), i, i] + [vp] * 11
+        lib.rt_history_clamp.restype = lib.rt_history_clamp_device.restype = i
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):
         lib.rt_capi_launch_version.restype = i

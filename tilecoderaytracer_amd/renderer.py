@@ -322,6 +322,7 @@ class TemporalHistory:
                                moments=new(n * 2, torch.float32), length=new(n, torch.float32)) for _ in range(2)]
             self._variance, self._flags = new(n, torch.float32), new(n, torch.uint8)
         self._filtered = self._scratch = None                          # filter_device()'s outputs and scratch, made on first use
+        self.clamp_flags = None                                        # push_device(clamp=...)'s byte plane, made on first use
         self.reset()
 
     def reset(self):
@@ -333,19 +334,29 @@ class TemporalHistory:
         C.memmove(C.byref(cam), _camera_ptr(camera), C.sizeof(cam))
         return cam
 
-    def push_device(self, value, hits, camera, x0=0, x1=None, stream=None, motions=None):
+    def push_device(self, value, hits, camera, x0=0, x1=None, stream=None, motions=None, clamp=None):
         """push() of torch tensors on the device (float32 value, the records as 12 int32 words each), enqueued on `stream` (the
         current one by default) without a host wait -> the strip's (value, variance, flags) as views of this history's buffers,
         valid until the next frame's push.  motions: None, a float32 (n, 12) numpy table, which is uploaded, or a float32 device
-        tensor of 12 n words, used as it is and kept alive until the next push (include/rt_motion.h)."""
+        tensor of 12 n words, used as it is and kept alive until the next push (include/rt_motion.h).  clamp: None, or a dict of
+        clamp_params()'s keywords (but channels): the strip just written is clipped to this frame's neighbourhood in place in
+        this history's own set, on the same stream (include/rt_clamp.h, rt_history_clamp_device) -- the returned value and
+        variance are then the clamped ones, what history_clamp() of the accumulated strip gives bit for bit, and clamp_flags
+        (uint8, W * H) holds the strip's clamp flags."""
         import torch
         W, H, ch = self.W, self.H, self.channels
         x0, x1 = int(x0), W if x1 is None else int(x1)
+        clamp = None if clamp is None else clamp_params(ch, **clamp)
         if x0 != self._next_column or not x0 < x1 <= W:
             raise ValueError(f"a frame's strips are pushed in ascending order: expected a strip from column {self._next_column}")
         n = (x1 - x0) * H
         if value.numel() != n * ch or hits.numel() * hits.element_size() != n * 48:
             raise ValueError(f"columns {x0}:{x1} need {n * ch} values and {n} records")
+        if clamp is not None:
+            # the clamp's parameters are refused before anything is enqueued: the call without buffers, whose last check is theirs
+            rc = self._lib.rt_history_clamp_device(self._device, C.byref(clamp), x1 - x0, H, *([None] * 11))
+            if b"is NULL" not in self._lib.rt_last_error():
+                capi.check(rc)
         if x0 == 0:
             self._cam = self._copy_camera(camera)
         old, new = self._sets[self.frames % 2], self._sets[(self.frames + 1) % 2]
@@ -371,16 +382,26 @@ class TemporalHistory:
                 self._motions = motions                                 # (alive while the launch may read it)
                 capi.check(self._lib.rt_motion_accumulate_device(*head, motions.data_ptr() if motions.numel() else None,
                                                                  motions.numel() // 12, *tail))
+            if clamp is not None:
+                if self.clamp_flags is None:
+                    with torch.cuda.stream(stream):                     # (the fill is ordered before the clamp's stores)
+                        self.clamp_flags = torch.zeros((W * H,), dtype=torch.uint8, device="cuda")
+                in_place = [t.data_ptr() for t in out[:3]]
+                capi.check(self._lib.rt_history_clamp_device(self._device, C.byref(clamp), x1 - x0, H, value.data_ptr(),
+                                                             part(new["hits"], 12).data_ptr(), *in_place, *in_place,
+                                                             out[3].data_ptr(), part(self.clamp_flags, 1).data_ptr(),
+                                                             stream.cuda_stream))
         self._next_column = x1
         if x1 == W:                                                     # the frame is whole: swap the sets
             self.frames, self._next_column, self._cam_prev = self.frames + 1, 0, self._cam
         return out[0], out[3], out[4]
 
-    def push(self, rgb, hits, camera, x0=0, x1=None, motions=None):
+    def push(self, rgb, hits, camera, x0=0, x1=None, motions=None, clamp=None):
         """Columns [x0, x1) of the next frame, seen by `camera`: rgb float32 (Wn, H) or (Wn, H, 3) by this history's channels,
         hits HIT_DTYPE (Wn, H) -> (value of rgb's shape, variance float32 (Wn, H), flags bool (Wn, H)), temporal_accumulate()'s
-        bit for bit -- with motions (push_device()'s), motion_accumulate()'s.  A frame's strips are pushed in ascending order
-        from column 0; the strip that ends at W completes the frame and swaps the two sets."""
+        bit for bit -- with motions (push_device()'s), motion_accumulate()'s; with clamp (push_device()'s), value and variance
+        are history_clamp()'s of those.  A frame's strips are pushed in ascending order from column 0; the strip that ends at W
+        completes the frame and swaps the two sets."""
         import torch
         hits = _frame_records(hits)
         rgb = np.ascontiguousarray(rgb, dtype=np.float32)
@@ -390,7 +411,7 @@ class TemporalHistory:
         with torch.cuda.device(self._device):
             d_rgb = torch.tensor(rgb.reshape(-1), device="cuda")
             d_hits = torch.tensor(hits.reshape(-1).view(np.int32), device="cuda")      # (a copy: the caller's may be read-only)
-            value, variance, flags = self.push_device(d_rgb, d_hits, camera, x0, x1, motions=motions)
+            value, variance, flags = self.push_device(d_rgb, d_hits, camera, x0, x1, motions=motions, clamp=clamp)
             return (value.cpu().numpy().reshape(shape), variance.cpu().numpy().reshape(hits.shape),
                     flags.cpu().numpy().reshape(hits.shape).view(np.bool_))
 
@@ -461,6 +482,41 @@ def svgf_filter(value, hits, moments, length, device=0, **params):
                                                   moments.ctypes.data, length.ctypes.data, out.ctypes.data, variance.ctypes.data,
                                                   estimate.ctypes.data, None))
     return out, variance, estimate
+
+
+def clamp_params(channels=3, box=0, radius=1, match_color=True, min_taps=3, clip_history=4, normal_cos=0.9, gamma=1.0):
+    """history_clamp's keywords -> an RtClampParams (include/rt_clamp.h); the library checks the values."""
+    return capi.RtClampParams(int(channels), int(box), int(radius), int(match_color), int(min_taps), int(clip_history),
+                              float(normal_cos), float(gamma))
+
+
+def history_clamp(cur, hits, value, moments, length, device=0, **params):
+    """An accumulated frame clipped to this frame's neighbourhood (include/rt_clamp.h, rt_history_clamp): cur float32 (Wn, H) --
+    one channel -- or (Wn, H, 3) and hits HIT_DTYPE (Wn, H), what temporal_accumulate() or motion_accumulate() was given for the
+    frame (a whole frame or a strip); value of cur's shape, moments float32 (Wn, H, 2) and length float32 (Wn, H), what it
+    returned -> (value, moments, length, variance float32 (Wn, H), flags uint8 (Wn, H): 1 clipped, 2 left alone for fewer than
+    min_taps taps).  Where a pixel's value lies outside the box of the samples on its surface around it -- box 0: their
+    extremes, box 1: mean -/+ gamma standard deviations -- it is moved onto the box, its length cut to clip_history and its
+    moments shifted.  params: clamp_params()'s keywords but channels, which cur's shape gives.  Runs on GPU `device`; there is no
+    CPU path."""
+    hits = _frame_records(hits)
+    cur, value = np.ascontiguousarray(cur, dtype=np.float32), np.ascontiguousarray(value, dtype=np.float32)
+    moments, length = np.ascontiguousarray(moments, dtype=np.float32), np.ascontiguousarray(length, dtype=np.float32)
+    channels = 3 if cur.ndim == 3 else 1
+    Wn, H = hits.shape
+    if cur.shape != hits.shape + ((3,) if channels == 3 else ()) or value.shape != cur.shape:
+        raise ValueError(f"cur and value must be {hits.shape} or {hits.shape + (3,)}, not {cur.shape} and {value.shape}")
+    if moments.shape != (Wn, H, 2) or length.shape != (Wn, H):
+        raise ValueError(f"moments must be {(Wn, H, 2)} and length {(Wn, H)}, not {moments.shape} and {length.shape}")
+    pr = clamp_params(channels, **params)
+    out, out_moments, out_len = np.empty(cur.shape, dtype=np.float32), np.empty((Wn, H, 2), dtype=np.float32), \
+        np.empty((Wn, H), dtype=np.float32)
+    variance, flags = np.empty((Wn, H), dtype=np.float32), np.empty((Wn, H), dtype=np.uint8)
+    capi.check(capi.load_library().rt_history_clamp(int(device), C.byref(pr), Wn, H, cur.ctypes.data, hits.ctypes.data,
+                                                    value.ctypes.data, moments.ctypes.data, length.ctypes.data, out.ctypes.data,
+                                                    out_moments.ctypes.data, out_len.ctypes.data, variance.ctypes.data,
+                                                    flags.ctypes.data, None))
+    return out, out_moments, out_len, variance, flags
 
 
 _TRANSFERS = {"srgb": capi.RT_TRANSFER_SRGB, "linear": capi.RT_TRANSFER_LINEAR, "custom": capi.RT_TRANSFER_CUSTOM}
@@ -1273,7 +1329,7 @@ class Renderer:
             return plane, guide
         return colours, guide
 
-    def render_accumulated(self, cameras, W, H, max_depth, term="indirect", samples=1, filter=None, mirrors=None, **kw):
+    def render_accumulated(self, cameras, W, H, max_depth, term="indirect", samples=1, filter=None, mirrors=None, clamp=None, **kw):
         """A sequence of W x H frames, one per camera of `cameras` (RtCameraDesc), accumulated on the GPU where they were made
         (include/rt_temporal.h): frame k is the G-buffer at max_depth and its term sampled with seed k -- "indirect": the
         colours plus indirect_diffuse(hits, samples, seed=k, base=rgb); "ao": ambient_occlusion(hits, samples, seed=k), one
@@ -1286,7 +1342,9 @@ class Renderer:
         mirrors: None, or a dict of max_bounces, min_reflective and optionally compact, or min_transmissive and glass_compact (include/rt_mirror.h, rt_mirror_compact.h,
         rt_glass.h, rt_glass_compact.h): the term is gathered at the terminal
         records of the pixel rays ("indirect": weighted as render_indirect(mirrors=...) does) and the history and the filter
-        are given the guide records in place of the G-buffer's."""
+        are given the guide records in place of the G-buffer's.  clamp: None, or a dict of clamp_params()'s keywords (but
+        channels), given to every push (include/rt_clamp.h): each frame's history is clipped to that frame's neighbourhood
+        before the next one blends into it, history_clamp() after every temporal_accumulate() bit for bit."""
         import torch
         if term not in ("indirect", "ao", "direct"):
             raise ValueError(f'term must be "indirect", "ao" or "direct", not {term!r}')
@@ -1309,7 +1367,7 @@ class Renderer:
                     self.render_gbuffer_device(W, H, max_depth, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
                     if mirrors is not None:
                         value, guide = self._accumulated_term_mirrored(W, H, term, samples, k, kw, mirrors, colours, plane, stream)
-                        value, variance, flags = history.push_device(value, guide, camera, stream=stream)
+                        value, variance, flags = history.push_device(value, guide, camera, stream=stream, clamp=clamp)
                         continue
                     if term == "indirect":
                         self.indirect_diffuse_device(W * H, records.data_ptr(), colours.data_ptr(), colours.data_ptr(),
@@ -1317,7 +1375,8 @@ class Renderer:
                     elif term == "ao":
                         self.ambient_occlusion_device(W * H, H, records.data_ptr(), plane.data_ptr(), samples=samples, seed=k,
                                                       stream=stream.cuda_stream, **kw)
-                    value, variance, flags = history.push_device(plane if term == "ao" else colours, records, camera, stream=stream)
+                    value, variance, flags = history.push_device(plane if term == "ao" else colours, records, camera, stream=stream,
+                                                                 clamp=clamp)
                 if filter is not None:
                     value, variance = history.filter_device(stream=stream, **filter)
                 shape = (W, H) if term == "ao" else (W, H, 3)
@@ -1385,14 +1444,14 @@ class Renderer:
         return li
 
 
-def render_animated(frames, W, H, max_depth, term="indirect", samples=1, filter=None, **kw):
+def render_animated(frames, W, H, max_depth, term="indirect", samples=1, filter=None, clamp=None, **kw):
     """Renderer.render_accumulated() for a scene whose objects move (include/rt_motion.h): frames is a sequence of (Renderer,
     camera, motions or None), one per W x H frame -- the Renderer of that frame's pose (all on one device), its camera (an
     RtCameraDesc) and the motion table from that pose to the previous frame's (object_motions(); push_device()'s motions; the
     first frame's is never read).  Frame k is its renderer's G-buffer at max_depth and its term sampled with seed k, as
     render_accumulated() makes them, pushed into one TemporalHistory with the frame's table, with no host wait and no download
-    between the frames.  kw and filter are render_accumulated()'s.  -> the last frame's (value, variance, flags), what
-    motion_accumulate() over the public calls' frames gives bit for bit."""
+    between the frames.  kw, filter and clamp are render_accumulated()'s.  -> the last frame's (value, variance, flags), what
+    motion_accumulate() -- with clamp, followed by history_clamp() -- over the public calls' frames gives bit for bit."""
     import torch
     if term not in ("indirect", "ao", "direct"):
         raise ValueError(f'term must be "indirect", "ao" or "direct", not {term!r}')
@@ -1423,7 +1482,7 @@ def render_animated(frames, W, H, max_depth, term="indirect", samples=1, filter=
                     r.ambient_occlusion_device(W * H, H, records.data_ptr(), plane.data_ptr(), samples=samples, seed=k,
                                                stream=stream.cuda_stream, **kw)
                 value, variance, flags = history.push_device(plane if term == "ao" else colours, records, camera, stream=stream,
-                                                             motions=motions)
+                                                             motions=motions, clamp=clamp)
             if filter is not None:
                 value, variance = history.filter_device(stream=stream, **filter)
             shape = (W, H) if term == "ao" else (W, H, 3)
