@@ -566,6 +566,16 @@ int pack_materials_and_lights(const rt_scene *s, Packing &P) {
             }
         }
     }
+    /* SPECULAR GATE (rt_tables.h, RT_LIGHT_COLOURS_WILD): scene creation refuses no colour, so the kernel is told */
+    bool colours_wild = false;
+    for (size_t l = 1; l < P.lights.size(); l += RT_LIGHT_QUADS)
+        for (int c = 0; c < 3; ++c) colours_wild = colours_wild || !std::isfinite(P.lights[l].v[c]);
+    if (colours_wild)
+        for (size_t l = 1; l < P.lights.size(); l += RT_LIGHT_QUADS) {
+            uint32_t word;
+            std::memcpy(&word, &P.lights[l].v[3], 4);
+            P.lights[l].v[3] = bits_to_float(word | RT_LIGHT_COLOURS_WILD);
+        }
     if (s->images_used) {
         pack_images(s, P);
         return RT_OK;

@@ -1721,15 +1721,74 @@ __device__ __forceinline__ bool in_shade_fast(const RtParams &p, const float4 *l
  * widen, which is exact by nearest_hit_items()'s argument (a candidate more is tested and found no nearer, or not blocking),
  * and every ray sees the arithmetic of nearest_hit_fast() / in_shade_fast() on its own operands. */
 
+/* Build switches of the twin path's shading ("Twin tiles: shading"), each 1 by default:
+ * RT_TWIN_SPECULAR_GATE: a (ray, light) region whose lanes all have specular factor +-0 skips the specular term;
+ * RT_TWIN_PACKED_BOUNDS: the bundle boxes are reduced with lane swaps, several chains to a register. */
+#ifndef RT_TWIN_SPECULAR_GATE
+#define RT_TWIN_SPECULAR_GATE 1
+#endif
+#ifndef RT_TWIN_PACKED_BOUNDS
+#define RT_TWIN_PACKED_BOUNDS 1
+#endif
+
+#if RT_TWIN_PACKED_BOUNDS
+/* wave_bounds3_range() for the twin tiles, the six chains packed: every chain a minimum -- the upper three arrive negated, `nhi`
+ * = -vhi (a lane without a value: +inf in all six), and are negated back as scalars.  v_min of negated operands is the negated
+ * v_max of the operands for every pair: both order -0 below +0 and both skip a NaN, so the six floats are wave_bounds3_range()'s
+ * bit for bit -- but for WHICH NaN comes out when all 64 operands of a chain are NaNs, which no comparison of the culls sees.
+ *   v_permlane32_swap a, b leaves a = {a.lo32, b.lo32}, b = {a.hi32, b.hi32}: one v_min folds both chains' halves, chain a's
+ *     partial results in lanes 0-31, chain b's in lanes 32-63; three swaps and three minima make [A|B], [C|D], [E|F];
+ *   v_permlane16_swap a, c exchanges a's odd rows of 16 lanes with c's even rows: a = c = rows {A, C, B, D} by pairs, and one
+ *     v_min leaves each of the four chains one row to finish: four butterfly steps, results in lanes 0, 16, 32 and 48;
+ *   [E|F] takes the same four steps and row_bcast:15 into rows 1 and 3: results in lanes 31 and 63.
+ * 17 vector instructions for wave_bounds3_range()'s 36.  A DPP operand or a swapped register written by the vector instruction
+ * before needs two wait states: the two row chains alternate with one s_nop between, and the lone row_bcast step, which follows
+ * its own chain's last step, waits one more.  All 64 lanes must be active. */
+__device__ __forceinline__ void wave_bounds3_packed(const V3 vlo, const V3 nhi, V3 *lo, V3 *hi) {
+    float a = vlo.x, b = nhi.x, c = vlo.y, d = nhi.y, e = vlo.z, f = nhi.z;
+#define RT_DPP_STEP(ctrl) "v_min_f32_dpp %0, %0, %0 " ctrl "\n v_min_f32_dpp %4, %4, %4 " ctrl "\n s_nop 0\n"
+    asm volatile("s_nop 1\n"
+                 "v_permlane32_swap_b32 %0, %1\n v_permlane32_swap_b32 %2, %3\n v_permlane32_swap_b32 %4, %5\n"
+                 "v_min_f32 %0, %0, %1\n v_min_f32 %2, %2, %3\n v_min_f32 %4, %4, %5\n"
+                 "s_nop 1\n"
+                 "v_permlane16_swap_b32 %0, %2\n"
+                 "v_min_f32 %0, %0, %2\n"
+                 "s_nop 1\n"
+                 RT_DPP_STEP("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
+                 RT_DPP_STEP("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
+                 RT_DPP_STEP("row_half_mirror row_mask:0xf bank_mask:0xf")
+                 RT_DPP_STEP("row_mirror row_mask:0xf bank_mask:0xf")
+                 "s_nop 0\n"                             /* (two wait states after the row_mirror step's write of %4) */
+                 "v_min_f32_dpp %4, %4, %4 row_bcast:15 row_mask:0xa bank_mask:0xf\n"
+                 "s_nop 1\n"
+                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
+#undef RT_DPP_STEP
+    const uint32_t sign = 0x80000000u;
+    *lo = mk(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 0)),        /* rows A, C, B, D of a: x, y */
+             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 16)),
+             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), 31)));
+    *hi = mk(__uint_as_float((uint32_t)__builtin_amdgcn_readlane(__float_as_int(a), 32) ^ sign),
+             __uint_as_float((uint32_t)__builtin_amdgcn_readlane(__float_as_int(a), 48) ^ sign),
+             __uint_as_float((uint32_t)__builtin_amdgcn_readlane(__float_as_int(e), 63) ^ sign));
+}
+#endif
+
 /* the box of two per-lane points over the lanes' rays in use: each lane's own minimum and maximum first (v_min / v_max skip a
  * NaN, as the reduction does), then ONE reduction */
 __device__ __forceinline__ void wave_bounds3_twin(const V3 v0, const bool use0, const V3 v1, const bool use1, V3 *lo, V3 *hi) {
     const float inf = __builtin_huge_valf();
     const V3 vlo = mk(fminf(use0 ? v0.x : inf, use1 ? v1.x : inf), fminf(use0 ? v0.y : inf, use1 ? v1.y : inf),
                       fminf(use0 ? v0.z : inf, use1 ? v1.z : inf));
+#if RT_TWIN_PACKED_BOUNDS
+    /* (the lane's maximum as the minimum of the negated values: -fmaxf(x, y) == fminf(-x, -y), wave_bounds3_packed()) */
+    const V3 nhi = mk(fminf(use0 ? -v0.x : inf, use1 ? -v1.x : inf), fminf(use0 ? -v0.y : inf, use1 ? -v1.y : inf),
+                      fminf(use0 ? -v0.z : inf, use1 ? -v1.z : inf));
+    wave_bounds3_packed(vlo, nhi, lo, hi);
+#else
     const V3 vhi = mk(fmaxf(use0 ? v0.x : -inf, use1 ? v1.x : -inf), fmaxf(use0 ? v0.y : -inf, use1 ? v1.y : -inf),
                       fmaxf(use0 ? v0.z : -inf, use1 ? v1.z : -inf));
     wave_bounds3_range(vlo, vhi, lo, hi);
+#endif
 }
 
 /* The exact tests of one candidate for both rays: sphere_hit_distance(), infinite_plane_hit_distance() and
@@ -2219,13 +2278,14 @@ __device__ __forceinline__ V3 eye_ray_direction(const RtParams &p, const V3 o, c
 /* What one light that is not blocked adds to a shading ray's colour C, in place: cosineShade, src/RayTracer.cpp:654-701, then
  * the specular term, :561-588.  N: the hit's normal, d: the ray's direction, light_ray: normalize(light - P); the material's
  * colour and factors, the light's colour and intensity; normals_are_unit: render_tile(); soft, visible: SOFT SHADOWS, f = m / S.
+ * specular_live: wave-uniform, false only where the specular term adds +-0 in every lane (render_tile_twin()); else `true`.
  * A macro, as RT_FOUR_SPHERES_VQ: as a function -- colour by value, by reference, the condition inside -- it compiled 22 to 65 of
  * the G-buffer, refraction and soft-shadow kernels to other code, some to more instructions (scripts/isa_same.py).
  * normal_dir: the CollisionObject ctor, Ray(point, normal), re-normalises, src/SceneObject.h:62.  (The rare path goes through an
  * opaque copy: left to itself the compiler computes the square root and the three divides before the light loop, on every
  * bounce level of every tile, speculatively -- 55 instructions and two spilled registers.) */
 #define RT_LIGHT_TERMS(soft, C, N, d, light_ray, normals_are_unit, object_color, diffuse_factor, specular_factor, light_color,   \
-                       intensity, visible)                                                                                      \
+                       intensity, visible, specular_live)                                                                       \
     do {                                                                                                                        \
         V3 normal_dir = N;                                                                                                      \
         if (!normals_are_unit) normal_dir = renormalize3(not_speculated(N));                                                    \
@@ -2242,17 +2302,19 @@ __device__ __forceinline__ V3 eye_ray_direction(const RtParams &p, const V3 o, c
             C.y = (C.y > 1.0f) ? 1.0f : C.y;                                                                                    \
             C.z = (C.z > 1.0f) ? 1.0f : C.z;                                                                                    \
         }                                                                                                                       \
-        V3 Nn = normal_dir;                                        /* specular, :561-588; third normalisation, :566-567 */      \
-        if (!normals_are_unit) Nn = renormalize3(not_speculated(normal_dir));                                                   \
-        const V3 R = sub3(light_ray, scale3(Nn, 2.0f * dot3(light_ray, Nn)));                                                   \
-        const float dot = dot3(d, R);                                                                                           \
-        if (dot > (float)0) {                                                                                                   \
-            float pow_factor = dot;                                                                                             \
-            _Pragma("unroll")                                                                                                   \
-            for (int j = 0; j < 19; ++j) pow_factor *= dot;                                                                     \
-            float spec_factor = pow_factor * specular_factor;                                                                   \
-            if constexpr (soft) spec_factor = spec_factor * visible;                                                            \
-            C = add3(C, scale3(light_color, spec_factor));                                                                      \
+        if (specular_live) {                                                                                                    \
+            V3 Nn = normal_dir;                                    /* specular, :561-588; third normalisation, :566-567 */      \
+            if (!normals_are_unit) Nn = renormalize3(not_speculated(normal_dir));                                               \
+            const V3 R = sub3(light_ray, scale3(Nn, 2.0f * dot3(light_ray, Nn)));                                               \
+            const float dot = dot3(d, R);                                                                                       \
+            if (dot > (float)0) {                                                                                               \
+                float pow_factor = dot;                                                                                         \
+                _Pragma("unroll")                                                                                               \
+                for (int j = 0; j < 19; ++j) pow_factor *= dot;                                                                 \
+                float spec_factor = pow_factor * specular_factor;                                                               \
+                if constexpr (soft) spec_factor = spec_factor * visible;                                                        \
+                C = add3(C, scale3(light_color, spec_factor));                                                                  \
+            }                                                                                                                   \
         }                                                                                                                       \
     } while (0)
 
@@ -2599,7 +2661,7 @@ __device__ __forceinline__ void render_tile(const RtParams &p, const float4 *lds
                     const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
                     const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
                     const V3 object_color = entry_colour<kImages>(p, lds, m0, __float_as_uint(m1.w), texsel);
-                    RT_LIGHT_TERMS(kSoft, C, N, d, light_ray, normals_are_unit, object_color, m0.w, m1.x, xyz(l1), l0.w, visible);
+                    RT_LIGHT_TERMS(kSoft, C, N, d, light_ray, normals_are_unit, object_color, m0.w, m1.x, xyz(l1), l0.w, visible, true);
                 }
             }
         }
@@ -2901,6 +2963,9 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
                 const float4 l0 = lds[p.lights_off + l * RT_LIGHT_QUADS];
                 const float4 l1 = lds[p.lights_off + l * RT_LIGHT_QUADS + 1];
                 const unsigned long long culled = l == 0 ? (culled_both & 0xFFFFFFFFull) : (culled_both >> 32);
+#if RT_TWIN_SPECULAR_GATE
+                const bool colours_wild = ((uint32_t)__builtin_amdgcn_readfirstlane(__float_as_int(l1.w)) & RT_LIGHT_COLOURS_WILD) != 0u;
+#endif
                 /* inShade, :743-771 */
                 float dist0, dist1;
                 const V3 light_ray0 = normalize3(sub3(xyz(l0), r[0].P), &dist0);
@@ -2917,7 +2982,15 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
                         const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
                         const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
                         const V3 object_color = entry_colour<false>(p, lds, m0, __float_as_uint(m1.w), q.texsel);
-                        RT_LIGHT_TERMS(false, q.C, q.N, q.d, light_ray, normals_are_unit, object_color, m0.w, m1.x, xyz(l1), l0.w, 1.0f);
+#if RT_TWIN_SPECULAR_GATE
+                        /* SPECULAR GATE: the lanes here are the ones that run the terms; where each has
+                         * specular factor +-0 and the scene's light colours are finite the term adds +-0 to a C that is not -0 */
+                        const bool specular_live = colours_wild || wave_any(m1.x != 0.0f);    /* (a NaN factor is live) */
+#else
+                        constexpr bool specular_live = true;
+#endif
+                        RT_LIGHT_TERMS(false, q.C, q.N, q.d, light_ray, normals_are_unit, object_color, m0.w, m1.x, xyz(l1), l0.w, 1.0f,
+                                       specular_live);
                     }
                 }
             }

@@ -72,6 +72,10 @@
 #define RT_LIGHT_QUADS  2
 #define RT_MAT_QUADS    2
 #define RT_TEX_QUADS    2
+/* A light's rows: {position.xyz, intensity}, {colour.xyz, bits(Scene index | flags)}.  RT_LIGHT_COLOURS_WILD, the same in every
+ * row of a scene: some light's colour has a component that is not finite -- then no product with a light's colour is known to
+ * be +-0 (rt_kernel.hip, SPECULAR GATE). */
+#define RT_LIGHT_COLOURS_WILD 0x80000000u
 
 /* item kinds: RT_KIND_* of rt_capi.h (0 sphere, 1 infinite plane, 2 finite
  * plane), plus axis-aligned finite planes: kind = 4 + axis of the normal (0 x, 1 y, 2 z).
