@@ -570,11 +570,23 @@ int pack_materials_and_lights(const rt_scene *s, Packing &P) {
     bool colours_wild = false;
     for (size_t l = 1; l < P.lights.size(); l += RT_LIGHT_QUADS)
         for (int c = 0; c < 3; ++c) colours_wild = colours_wild || !std::isfinite(P.lights[l].v[c]);
-    if (colours_wild)
+    /* DEAD REFLECTIONS (rt_tables.h, RT_SCENE_VALUES_WILD): a reflection folded with a colour of +-0 is dropped only where every
+     * number a colour is built from is finite and at most 1 in magnitude (`!(|v| <= 1)`: a NaN is wild) */
+    bool values_wild = false;
+    const auto wild = [](const float v) { return !(std::fabs(v) <= 1.0f); };
+    for (const rt_object_desc &o : s->objects) {         /* (a light is an object: its colour and intensity are among these) */
+        for (int c = 0; c < 3; ++c) values_wild = values_wild || wild(o.color[c]);
+        values_wild = values_wild || wild(o.diffuse) || wild(o.specular) || wild(o.reflective) || wild(o.intensity);
+    }
+    for (const rt_texture_desc &x : s->textures)
+        for (int c = 0; c < 3; ++c) values_wild = values_wild || wild(x.light[c]) || wild(x.dark[c]);
+    for (int c = 0; c < 3; ++c) values_wild = values_wild || wild(s->null_color[c]);
+    const uint32_t flags = (colours_wild ? RT_LIGHT_COLOURS_WILD : 0u) | (values_wild ? RT_SCENE_VALUES_WILD : 0u);
+    if (flags)
         for (size_t l = 1; l < P.lights.size(); l += RT_LIGHT_QUADS) {
             uint32_t word;
             std::memcpy(&word, &P.lights[l].v[3], 4);
-            P.lights[l].v[3] = bits_to_float(word | RT_LIGHT_COLOURS_WILD);
+            P.lights[l].v[3] = bits_to_float(word | flags);
         }
     if (s->images_used) {
         pack_images(s, P);

@@ -1723,7 +1723,11 @@ __device__ __forceinline__ bool in_shade_fast(const RtParams &p, const float4 *l
 
 /* Build switches of the twin path's shading ("Twin tiles: shading"), each 1 by default:
  * RT_TWIN_SPECULAR_GATE: a (ray, light) region whose lanes all have specular factor +-0 skips the specular term;
- * RT_TWIN_PACKED_BOUNDS: the bundle boxes are reduced with lane swaps, several chains to a register. */
+ * RT_TWIN_PACKED_BOUNDS: the bundle boxes are reduced with lane swaps, several chains to a register;
+ * RT_TWIN_DEAD_REFLECTIONS: a ray whose reflection would be folded with a colour of +-0 ends instead of reflecting. */
+#ifndef RT_TWIN_DEAD_REFLECTIONS
+#define RT_TWIN_DEAD_REFLECTIONS 1
+#endif
 #ifndef RT_TWIN_SPECULAR_GATE
 #define RT_TWIN_SPECULAR_GATE 1
 #endif
@@ -2873,6 +2877,18 @@ __device__ __forceinline__ float4 *twin_stack_entry(const RtParams &p, float4 *w
     return stack_entry(p, wlds, bounce_stack, 2 * level + ray, 2 * level + ray < p.stack_lds_levels, 2);
 }
 
+#if RT_TWIN_DEAD_REFLECTIONS
+/* DEAD REFLECTIONS: whether the colour that fold_child() would receive as `oc` for a hit of material `mat` -- entry_colour() of
+ * the hit, as phase 3 and the unwind pass it -- is +-0 in all three components.  Per lane, on the bits: -0 is zero, the smallest
+ * denormal and a NaN are not. */
+__device__ __forceinline__ bool dead_reflection(const RtParams &p, const float4 *lds, const int mat, const int texsel) {
+    const float4 m0 = lds[p.mat_off + mat * RT_MAT_QUADS];
+    const uint32_t mbits = __float_as_uint(lds[p.mat_off + mat * RT_MAT_QUADS + 1].w);
+    const V3 oc = entry_colour<false>(p, lds, m0, mbits, texsel);
+    return ((__float_as_uint(oc.x) | __float_as_uint(oc.y) | __float_as_uint(oc.z)) << 1) == 0u;
+}
+#endif
+
 /* `wave_in`: the number of the twin's first tile (an even tile row of its macro tile) */
 __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4 *lds, float4 *wlds,
                                                  const uint32_t *__restrict__ ctl_words, float *__restrict__ out,
@@ -2901,6 +2917,12 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
     }
     int levels = 0;           /* wave-uniform: levels any ray entered */
     V3 box_lo = r[0].o, box_hi = r[0].o;        /* the eye at level 0, afterwards the shading points of the level before */
+#if RT_TWIN_DEAD_REFLECTIONS
+    /* DEAD REFLECTIONS: off where the host found a value that is not finite or above 1 in magnitude (the flag is in every
+     * light's row; a scene without lights keeps the skip off) and at depths where the bound on a colour is no longer finite */
+    const bool tame = p.n_lights > 0 && p.max_depth < (1 << 20) &&
+                      ((uint32_t)__builtin_amdgcn_readfirstlane(__float_as_int(lds[p.lights_off + 1].w)) & RT_SCENE_VALUES_WILD) == 0u;
+#endif
 
     for (int level = 0; level <= p.max_depth; ++level) {
         if (!wave_any(r[0].alive || r[1].alive)) break;
@@ -3009,6 +3031,13 @@ __device__ __forceinline__ void render_tile_twin(const RtParams &p, const float4
                     const float4 m1 = lds[p.mat_off + mat * RT_MAT_QUADS + 1];
                     q.C = fold_child(q.C, null_color, m1.y, entry_colour<false>(p, lds, m0, __float_as_uint(m1.w), q.texsel));
                     q.alive = false;
+#if RT_TWIN_DEAD_REFLECTIONS
+                } else if (reflective_factor > (float)0 && tame && dead_reflection(p, lds, mat, q.texsel)) {
+                    /* DEAD REFLECTION: the unwind would fold this ray's child as local + (f * C_next) * oc
+                     * with oc = +-0 in every component; in a tame scene C_next is finite, the product +-0, and the sum `local`,
+                     * which C holds already.  No push, no reflected ray; `top` stays */
+                    q.alive = false;
+#endif
                 } else if (reflective_factor > (float)0) {
                     const V3 reflected = reflected_ray(q.N, q.d);
                     *twin_stack_entry(p, wlds, bounce_stack, level, k) =

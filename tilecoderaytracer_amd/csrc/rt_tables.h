@@ -74,8 +74,12 @@
 #define RT_TEX_QUADS    2
 /* A light's rows: {position.xyz, intensity}, {colour.xyz, bits(Scene index | flags)}.  RT_LIGHT_COLOURS_WILD, the same in every
  * row of a scene: some light's colour has a component that is not finite -- then no product with a light's colour is known to
- * be +-0 (rt_kernel.hip, SPECULAR GATE). */
+ * be +-0 (rt_kernel.hip, SPECULAR GATE).  RT_SCENE_VALUES_WILD, likewise in every row: some colour component (an object's, a
+ * checkerboard's, the null colour's), factor (diffuse, specular, reflective) or intensity of the scene is a NaN, infinite or of
+ * magnitude above 1 -- then a reflected ray's colour is not known to be finite (rt_kernel.hip, DEAD REFLECTIONS).  Both are 0
+ * in a scene with neither: its rows are what they were before the flags existed. */
 #define RT_LIGHT_COLOURS_WILD 0x80000000u
+#define RT_SCENE_VALUES_WILD  0x40000000u
 
 /* item kinds: RT_KIND_* of rt_capi.h (0 sphere, 1 infinite plane, 2 finite
  * plane), plus axis-aligned finite planes: kind = 4 + axis of the normal (0 x, 1 y, 2 z).
