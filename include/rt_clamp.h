@@ -56,9 +56,9 @@
  * strip differs from the frame's columns only within `radius` columns of its edges.  Cutting len below rt_svgf_params.min_history
  * makes rt_svgf_filter estimate that pixel's variance spatially: that is the intended hand-over.
  *
- * Not provided: the clip fused into the accumulate kernel (a clip before the blend), temporal-gradient (A-SVGF) weights, several
- * GPUs, the counting build, supersampled frames (they have no records), a command-line flag (the executable has no animated
- * scene).  Not tested: buffers past 2^32 bytes (every offset is a 64-bit element index by construction).  Not tested either, and
+ * Not provided: the clip fused into the accumulate kernel (a clip before the blend), temporal-gradient (A-SVGF) weights (they are
+ * include/rt_gradient.h's, a call of its own that runs before this one), several GPUs, the counting build, supersampled frames
+ * (they have no records), a command-line flag (the executable has no animated scene).  Not tested: buffers past 2^32 bytes (every offset is a 64-bit element index by construction).  Not tested either, and
  * deliberately never launched: a rectangle of H = 1 with Wn >= 268 435 453.  The checks admit it (Wn * H <= 533 333 333); its one
  * row of tiles is 2^26 or more workgroups of 64 x 4 threads, 2^32 or more threads along x, and what HIP does with such a launch --
  * refuse it, or run a truncated grid -- is not known here.

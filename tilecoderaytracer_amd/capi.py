@@ -95,6 +95,14 @@ class RtClampParams(C.Structure):
                 ("min_taps", C.c_int32), ("clip_history", C.c_int32), ("normal_cos", C.c_float), ("gamma", C.c_float)]
 
 
+class RtGradientParams(C.Structure):
+    """include/rt_gradient.h: channels (1 or 3), scale (one cell per s x s pixels, 2..8), radius (0..2: a window of (2r+2)^2
+    cells), match_color (0 / 1), the normals' cosine a cell must keep (-1..1), the gain on the relative gradient (>= 0), the
+    weight at or below which a pixel is left alone (0..1) and the cells' light at or below which there is no gradient (>= 0)."""
+    _fields_ = [("channels", C.c_int32), ("scale", C.c_int32), ("radius", C.c_int32), ("match_color", C.c_int32),
+                ("normal_cos", C.c_float), ("gain", C.c_float), ("lambda_min", C.c_float), ("den_floor", C.c_float)]
+
+
 class RtAoParams(C.Structure):
     """include/rt_capi_ao.h: n (n x n directions per record, 1..8), the radius a direction is followed for, the seed, the first
     record's key, channels (1, or 3 equal ones)."""
@@ -487,6 +495,12 @@ def load_library():
         lib.rt_history_clamp.argtypes = [i, C.POINTER(RtClampParams), i, i] + [vp] * 10 + [C.POINTER(C.c_double)]
         lib.rt_history_clamp_device.argtypes = [i, C.POINTER(RtClampParams), i, i] + [vp] * 11
         lib.rt_history_clamp.restype = lib.rt_history_clamp_device.restype = i
+    # include/rt_gradient.h (likewise absent from older builds)
+    if hasattr(lib, "rt_gradient_reweight"):
+        lib.rt_capi_gradient_version.restype = i
+        lib.rt_gradient_reweight.argtypes = [i, C.POINTER(RtGradientParams), i, i] + [vp] * 15 + [C.POINTER(C.c_double)]
+        lib.rt_gradient_reweight_device.argtypes = [i, C.POINTER(RtGradientParams), i, i] + [vp] * 16
+        lib.rt_gradient_reweight.restype = lib.rt_gradient_reweight_device.restype = i
     # include/rt_capi_launch.h (likewise absent from older builds)
     if hasattr(lib, "rt_get_launch_kernel"):
         lib.rt_capi_launch_version.restype = i

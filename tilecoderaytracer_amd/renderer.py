@@ -323,6 +323,7 @@ class TemporalHistory:
             self._variance, self._flags = new(n, torch.float32), new(n, torch.uint8)
         self._filtered = self._scratch = None                          # filter_device()'s outputs and scratch, made on first use
         self.clamp_flags = None                                        # push_device(clamp=...)'s byte plane, made on first use
+        self.gradient_lambda = self.gradient_flags = None              # push_device(gradient=...)'s planes, made on first use
         self.reset()
 
     def reset(self):
@@ -334,7 +335,7 @@ class TemporalHistory:
         C.memmove(C.byref(cam), _camera_ptr(camera), C.sizeof(cam))
         return cam
 
-    def push_device(self, value, hits, camera, x0=0, x1=None, stream=None, motions=None, clamp=None):
+    def push_device(self, value, hits, camera, x0=0, x1=None, stream=None, motions=None, clamp=None, gradient=None):
         """push() of torch tensors on the device (float32 value, the records as 12 int32 words each), enqueued on `stream` (the
         current one by default) without a host wait -> the strip's (value, variance, flags) as views of this history's buffers,
         valid until the next frame's push.  motions: None, a float32 (n, 12) numpy table, which is uploaded, or a float32 device
@@ -342,11 +343,21 @@ class TemporalHistory:
         clamp_params()'s keywords (but channels): the strip just written is clipped to this frame's neighbourhood in place in
         this history's own set, on the same stream (include/rt_clamp.h, rt_history_clamp_device) -- the returned value and
         variance are then the clamped ones, what history_clamp() of the accumulated strip gives bit for bit, and clamp_flags
-        (uint8, W * H) holds the strip's clamp flags."""
+        (uint8, W * H) holds the strip's clamp flags.  gradient: None, or a dict of now_lo, then_lo, lo_hits and optionally
+        then_hits -- device tensors: the STRIP's cell frames and their records (include/rt_gradient.h; float32, and the records
+        as 12 int32 words each) -- plus gradient_params()'s keywords (but channels): the strip just written is re-blended by its
+        temporal gradient in place in this history's own set, on the same stream (rt_gradient_reweight_device), after the
+        accumulate call and before the clamp -- the returned value and variance are then what gradient_reweight() of the
+        accumulated strip gives bit for bit (followed by history_clamp() with clamp), and gradient_lambda (float32, W * H) and
+        gradient_flags (uint8, W * H) hold the strip's weights and flags."""
         import torch
         W, H, ch = self.W, self.H, self.channels
         x0, x1 = int(x0), W if x1 is None else int(x1)
         clamp = None if clamp is None else clamp_params(ch, **clamp)
+        if gradient is not None:
+            gradient = dict(gradient)
+            cells = [gradient.pop(k) for k in ("now_lo", "then_lo", "lo_hits")] + [gradient.pop("then_hits", None)]
+            gradient = gradient_params(ch, **gradient)
         if x0 != self._next_column or not x0 < x1 <= W:
             raise ValueError(f"a frame's strips are pushed in ascending order: expected a strip from column {self._next_column}")
         n = (x1 - x0) * H
@@ -357,6 +368,16 @@ class TemporalHistory:
             rc = self._lib.rt_history_clamp_device(self._device, C.byref(clamp), x1 - x0, H, *([None] * 11))
             if b"is NULL" not in self._lib.rt_last_error():
                 capi.check(rc)
+        if gradient is not None:
+            # likewise the gradient's parameters, and the cell buffers' sizes
+            rc = self._lib.rt_gradient_reweight_device(self._device, C.byref(gradient), x1 - x0, H, *([None] * 16))
+            if b"is NULL" not in self._lib.rt_last_error():
+                capi.check(rc)
+            s = gradient.scale
+            n_lo = ((x1 - x0 + s - 1) // s) * ((H + s - 1) // s)
+            if any(t.numel() != n_lo * ch for t in cells[:2]) or \
+                    any(t is not None and t.numel() * t.element_size() != n_lo * 48 for t in cells[2:]):
+                raise ValueError(f"columns {x0}:{x1} at scale {s} need {n_lo * ch} cell values and {n_lo} cell records")
         if x0 == 0:
             self._cam = self._copy_camera(camera)
         old, new = self._sets[self.frames % 2], self._sets[(self.frames + 1) % 2]
@@ -382,6 +403,17 @@ class TemporalHistory:
                 self._motions = motions                                 # (alive while the launch may read it)
                 capi.check(self._lib.rt_motion_accumulate_device(*head, motions.data_ptr() if motions.numel() else None,
                                                                  motions.numel() // 12, *tail))
+            if gradient is not None:
+                if self.gradient_lambda is None:
+                    with torch.cuda.stream(stream):                     # (the fills are ordered before the call's stores)
+                        self.gradient_lambda = torch.zeros((W * H,), dtype=torch.float32, device="cuda")
+                        self.gradient_flags = torch.zeros((W * H,), dtype=torch.uint8, device="cuda")
+                in_place = [t.data_ptr() for t in out[:3]]
+                capi.check(self._lib.rt_gradient_reweight_device(
+                    self._device, C.byref(gradient), x1 - x0, H, value.data_ptr(), part(new["hits"], 12).data_ptr(), *in_place,
+                    *[None if t is None else t.data_ptr() for t in cells], *in_place, out[3].data_ptr(),
+                    part(self.gradient_lambda, 1).data_ptr(), part(self.gradient_flags, 1).data_ptr(), stream.cuda_stream))
+                self._cells = cells                                     # (alive while the launch may read them)
             if clamp is not None:
                 if self.clamp_flags is None:
                     with torch.cuda.stream(stream):                     # (the fill is ordered before the clamp's stores)
@@ -396,12 +428,13 @@ class TemporalHistory:
             self.frames, self._next_column, self._cam_prev = self.frames + 1, 0, self._cam
         return out[0], out[3], out[4]
 
-    def push(self, rgb, hits, camera, x0=0, x1=None, motions=None, clamp=None):
+    def push(self, rgb, hits, camera, x0=0, x1=None, motions=None, clamp=None, gradient=None):
         """Columns [x0, x1) of the next frame, seen by `camera`: rgb float32 (Wn, H) or (Wn, H, 3) by this history's channels,
         hits HIT_DTYPE (Wn, H) -> (value of rgb's shape, variance float32 (Wn, H), flags bool (Wn, H)), temporal_accumulate()'s
         bit for bit -- with motions (push_device()'s), motion_accumulate()'s; with clamp (push_device()'s), value and variance
-        are history_clamp()'s of those.  A frame's strips are pushed in ascending order from column 0; the strip that ends at W
-        completes the frame and swaps the two sets."""
+        are history_clamp()'s of those; with gradient (push_device()'s, its now_lo, then_lo, lo_hits and then_hits being arrays:
+        float32 (Wl, Hl[, 3]) and HIT_DTYPE (Wl, Hl)), gradient_reweight() comes between the two.  A frame's strips are pushed in
+        ascending order from column 0; the strip that ends at W completes the frame and swaps the two sets."""
         import torch
         hits = _frame_records(hits)
         rgb = np.ascontiguousarray(rgb, dtype=np.float32)
@@ -411,7 +444,15 @@ class TemporalHistory:
         with torch.cuda.device(self._device):
             d_rgb = torch.tensor(rgb.reshape(-1), device="cuda")
             d_hits = torch.tensor(hits.reshape(-1).view(np.int32), device="cuda")      # (a copy: the caller's may be read-only)
-            value, variance, flags = self.push_device(d_rgb, d_hits, camera, x0, x1, motions=motions, clamp=clamp)
+            if gradient is not None:
+                gradient = dict(gradient)
+                for k in ("now_lo", "then_lo"):
+                    gradient[k] = torch.tensor(np.ascontiguousarray(gradient[k], dtype=np.float32).reshape(-1), device="cuda")
+                for k in ("lo_hits", "then_hits"):
+                    if gradient.get(k) is not None:
+                        gradient[k] = torch.tensor(_frame_records(gradient[k]).reshape(-1).view(np.int32), device="cuda")
+            value, variance, flags = self.push_device(d_rgb, d_hits, camera, x0, x1, motions=motions, clamp=clamp,
+                                                      gradient=gradient)
             return (value.cpu().numpy().reshape(shape), variance.cpu().numpy().reshape(hits.shape),
                     flags.cpu().numpy().reshape(hits.shape).view(np.bool_))
 
@@ -517,6 +558,51 @@ def history_clamp(cur, hits, value, moments, length, device=0, **params):
                                                     out_moments.ctypes.data, out_len.ctypes.data, variance.ctypes.data,
                                                     flags.ctypes.data, None))
     return out, out_moments, out_len, variance, flags
+
+
+def gradient_params(channels=3, scale=2, radius=1, match_color=True, normal_cos=0.9, gain=2.0, lambda_min=0.0, den_floor=1e-6):
+    """gradient_reweight's keywords -> an RtGradientParams (include/rt_gradient.h); the library checks the values."""
+    return capi.RtGradientParams(int(channels), int(scale), int(radius), int(match_color), float(normal_cos), float(gain),
+                                 float(lambda_min), float(den_floor))
+
+
+def gradient_reweight(cur, hits, value, moments, length, now_lo, then_lo, lo_hits, then_hits=None, device=0, **params):
+    """An accumulated frame re-blended by its temporal gradient (include/rt_gradient.h, rt_gradient_reweight): cur float32
+    (Wn, H) -- one channel -- or (Wn, H, 3) and hits HIT_DTYPE (Wn, H), what temporal_accumulate() or motion_accumulate() was given
+    for the frame (a whole frame or a strip); value of cur's shape, moments float32 (Wn, H, 2) and length float32 (Wn, H), what
+    it returned; now_lo and then_lo float32 (Wl, Hl) or (Wl, Hl, 3), Wl = ceil(Wn / scale) and Hl = ceil(H / scale): the term at
+    every scale-th pixel in this frame's scene and in the previous frame's, shaded with the same random numbers; lo_hits HIT_DTYPE
+    (Wl, Hl), the records now_lo was made from, and then_hits, None or those then_lo was made from -> (value, moments, length,
+    variance float32 (Wn, H), lam float32 (Wn, H), flags uint8 (Wn, H): 1 re-blended, 2 left alone for no counted cell, 3
+    restarted).  params: gradient_params()'s keywords but channels, which cur's shape gives.  Runs on GPU `device`; there is no
+    CPU path."""
+    hits, lo_hits = _frame_records(hits), _frame_records(lo_hits)
+    then_hits = None if then_hits is None else _frame_records(then_hits)
+    cur, value = np.ascontiguousarray(cur, dtype=np.float32), np.ascontiguousarray(value, dtype=np.float32)
+    moments, length = np.ascontiguousarray(moments, dtype=np.float32), np.ascontiguousarray(length, dtype=np.float32)
+    now_lo, then_lo = np.ascontiguousarray(now_lo, dtype=np.float32), np.ascontiguousarray(then_lo, dtype=np.float32)
+    channels = 3 if cur.ndim == 3 else 1
+    tail = (3,) if channels == 3 else ()
+    Wn, H = hits.shape
+    if cur.shape != hits.shape + tail or value.shape != cur.shape:
+        raise ValueError(f"cur and value must be {hits.shape} or {hits.shape + (3,)}, not {cur.shape} and {value.shape}")
+    if moments.shape != (Wn, H, 2) or length.shape != (Wn, H):
+        raise ValueError(f"moments must be {(Wn, H, 2)} and length {(Wn, H)}, not {moments.shape} and {length.shape}")
+    pr = gradient_params(channels, **params)
+    s = pr.scale
+    lo = (-(-Wn // s), -(-H // s)) if 2 <= s <= 8 else lo_hits.shape      # (a refused scale: the library says so)
+    if lo_hits.shape != lo or now_lo.shape != lo + tail or then_lo.shape != lo + tail or \
+            (then_hits is not None and then_hits.shape != lo):
+        raise ValueError(f"at scale {s} the cell frames must be {lo + tail} and their records {lo}")
+    out, out_moments, out_len = np.empty(cur.shape, dtype=np.float32), np.empty((Wn, H, 2), dtype=np.float32), \
+        np.empty((Wn, H), dtype=np.float32)
+    variance, lam, flags = np.empty((Wn, H), dtype=np.float32), np.empty((Wn, H), dtype=np.float32), np.empty((Wn, H), dtype=np.uint8)
+    capi.check(capi.load_library().rt_gradient_reweight(
+        int(device), C.byref(pr), Wn, H, cur.ctypes.data, hits.ctypes.data, value.ctypes.data, moments.ctypes.data,
+        length.ctypes.data, now_lo.ctypes.data, then_lo.ctypes.data, lo_hits.ctypes.data,
+        None if then_hits is None else then_hits.ctypes.data, out.ctypes.data, out_moments.ctypes.data, out_len.ctypes.data,
+        variance.ctypes.data, lam.ctypes.data, flags.ctypes.data, None))
+    return out, out_moments, out_len, variance, lam, flags
 
 
 _TRANSFERS = {"srgb": capi.RT_TRANSFER_SRGB, "linear": capi.RT_TRANSFER_LINEAR, "custom": capi.RT_TRANSFER_CUSTOM}
@@ -1444,14 +1530,22 @@ class Renderer:
         return li
 
 
-def render_animated(frames, W, H, max_depth, term="indirect", samples=1, filter=None, clamp=None, **kw):
+def render_animated(frames, W, H, max_depth, term="indirect", samples=1, filter=None, clamp=None, gradient=None, **kw):
     """Renderer.render_accumulated() for a scene whose objects move (include/rt_motion.h): frames is a sequence of (Renderer,
     camera, motions or None), one per W x H frame -- the Renderer of that frame's pose (all on one device), its camera (an
     RtCameraDesc) and the motion table from that pose to the previous frame's (object_motions(); push_device()'s motions; the
     first frame's is never read).  Frame k is its renderer's G-buffer at max_depth and its term sampled with seed k, as
     render_accumulated() makes them, pushed into one TemporalHistory with the frame's table, with no host wait and no download
     between the frames.  kw, filter and clamp are render_accumulated()'s.  -> the last frame's (value, variance, flags), what
-    motion_accumulate() -- with clamp, followed by history_clamp() -- over the public calls' frames gives bit for bit."""
+    motion_accumulate() -- with clamp, followed by history_clamp() -- over the public calls' frames gives bit for bit.
+    gradient: None, or a dict of gradient_params()'s keywords (but channels), s its scale (include/rt_gradient.h): for every
+    frame k >= 1 a (W/s) x (H/s) G-buffer is rendered under frame k's camera on frame k's renderer and on frame k-1's, the term
+    is evaluated on both with the same samples, seed k and key0 0 ("direct": set_shadow_seed(k) on both, which is where frame
+    k-1's renderer's seed is left), and the two results and the two record sets go to the push, all on the one stream with no
+    host wait.  ValueError if W or H is not a multiple of s.  The result is then what, frame by frame, motion_accumulate(),
+    gradient_reweight(now_lo, then_lo, lo_hits, then_hits) from frame 1 on -- the cell frames made by the public calls:
+    render_gbuffer(W/s, H/s) of both renderers under the frame's camera and the term of each -- and, with clamp,
+    history_clamp() give bit for bit.  Frame 0 and gradient=None are the calls without it, word for word."""
     import torch
     if term not in ("indirect", "ao", "direct"):
         raise ValueError(f'term must be "indirect", "ao" or "direct", not {term!r}')
@@ -1461,6 +1555,16 @@ def render_animated(frames, W, H, max_depth, term="indirect", samples=1, filter=
     device = int(frames[0][0]._device)
     if any(int(r._device) != device for r, _, _ in frames):
         raise ValueError("the frames' renderers must be on one device")
+    if gradient is not None:
+        # refused before anything is rendered: the call without buffers, whose last check is the parameters' and the rectangle's
+        gradient, lib = dict(gradient), capi.load_library()
+        pr = gradient_params(1 if term == "ao" else 3, **gradient)
+        rc = lib.rt_gradient_reweight_device(device, C.byref(pr), W, H, *([None] * 16))
+        if b"is NULL" not in lib.rt_last_error():
+            capi.check(rc)
+        scale = pr.scale
+        if W % scale or H % scale:
+            raise ValueError(f"W and H must be multiples of the gradient's scale {scale}, not {W} x {H}")
     names = ("match_color", "max_history", "normal_cos", "plane_eps", "alpha", "alpha_moments")
     history = TemporalHistory(W, H, 1 if term == "ao" else 3, device, **{k: kw.pop(k) for k in names if k in kw})
     own = [(r, r._cam) for r, _, _ in frames]
@@ -1470,10 +1574,35 @@ def render_animated(frames, W, H, max_depth, term="indirect", samples=1, filter=
             records = torch.empty((W * H * 12,), dtype=torch.int32, device="cuda")
             plane = torch.empty((W * H,), dtype=torch.float32, device="cuda") if term == "ao" else None
             stream = torch.cuda.current_stream()
+            if gradient is not None:
+                Wl, Hl = W // scale, H // scale
+                lo = [dict(colours=torch.empty((Wl * Hl * 3,), dtype=torch.float32, device="cuda"),
+                           records=torch.empty((Wl * Hl * 12,), dtype=torch.int32, device="cuda"),
+                           plane=torch.empty((Wl * Hl,), dtype=torch.float32, device="cuda") if term == "ao" else None)
+                      for _ in range(2)]
             for k, (r, camera, motions) in enumerate(frames):
                 r._cam = C.pointer(camera)
                 if term == "direct":
                     r.set_shadow_seed(k)
+                cells = None
+                if gradient is not None and k >= 1:
+                    # the two cell frames: this frame's points, shaded in this frame's scene and in the previous frame's
+                    then = frames[k - 1][0]
+                    then._cam = C.pointer(camera)
+                    if term == "direct":
+                        then.set_shadow_seed(k)
+                    for q, b in ((r, lo[0]), (then, lo[1])):
+                        q.render_gbuffer_device(Wl, Hl, max_depth, 0, Wl, b["colours"].data_ptr(), b["records"].data_ptr(),
+                                                stream.cuda_stream)
+                        if term == "indirect":
+                            q.indirect_diffuse_device(Wl * Hl, b["records"].data_ptr(), b["colours"].data_ptr(),
+                                                      b["colours"].data_ptr(), stream.cuda_stream, samples=samples, seed=k, **kw)
+                        elif term == "ao":
+                            q.ambient_occlusion_device(Wl * Hl, Hl, b["records"].data_ptr(), b["plane"].data_ptr(), samples=samples,
+                                                       seed=k, stream=stream.cuda_stream, **kw)
+                    name = "plane" if term == "ao" else "colours"
+                    cells = dict(gradient, now_lo=lo[0][name], then_lo=lo[1][name], lo_hits=lo[0]["records"],
+                                 then_hits=lo[1]["records"])
                 r.render_gbuffer_device(W, H, max_depth, 0, W, colours.data_ptr(), records.data_ptr(), stream.cuda_stream)
                 if term == "indirect":
                     r.indirect_diffuse_device(W * H, records.data_ptr(), colours.data_ptr(), colours.data_ptr(), stream.cuda_stream,
@@ -1482,7 +1611,7 @@ def render_animated(frames, W, H, max_depth, term="indirect", samples=1, filter=
                     r.ambient_occlusion_device(W * H, H, records.data_ptr(), plane.data_ptr(), samples=samples, seed=k,
                                                stream=stream.cuda_stream, **kw)
                 value, variance, flags = history.push_device(plane if term == "ao" else colours, records, camera, stream=stream,
-                                                             motions=motions, clamp=clamp)
+                                                             motions=motions, clamp=clamp, gradient=cells)
             if filter is not None:
                 value, variance = history.filter_device(stream=stream, **filter)
             shape = (W, H) if term == "ao" else (W, H, 3)
