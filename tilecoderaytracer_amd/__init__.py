@@ -20,9 +20,10 @@ from .renderer import mirror_params  # noqa: F401
 from .renderer import glass_params  # noqa: F401
 from .renderer import clamp_params, history_clamp  # noqa: F401
 from .renderer import gradient_params, gradient_reweight  # noqa: F401
+from .renderer import paths_params  # noqa: F401
 
 __all__ = ["RtError", "load_library", "library_path", "HostScene", "Renderer", "adaptive_flags", "denoise", "encode_image",
            "indirect_rays", "lens_rays", "subsample_hits", "upsample_guided", "TemporalHistory", "temporal_accumulate",
            "temporal_params", "svgf_filter", "svgf_params", "motion_accumulate", "object_motions", "render_animated",
            "mirror_params", "glass_params", "clamp_params", "history_clamp",
-           "gradient_params", "gradient_reweight"]
+           "gradient_params", "gradient_reweight", "paths_params"]

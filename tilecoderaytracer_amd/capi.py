@@ -153,6 +153,22 @@ class RtIndirectInfo(C.Structure):
                 ("trace_ms", C.c_double), ("query_ms", C.c_double), ("resolve_ms", C.c_double)]
 
 
+RT_PATHS_MAX_BOUNCES = 8
+
+
+class RtPathsParams(C.Structure):
+    """include/rt_paths.h: RtIndirectParams' seven fields in their order, then the most rays a path traces (1..8)."""
+    _fields_ = RtIndirectParams._fields_ + [("bounces", C.c_int32)]
+
+
+class RtPathsInfo(C.Structure):
+    """include/rt_paths.h: the scene's last rt_indirect_paths* call -- its records, rays traced over all bounces, chunks of
+    records, the five stages' HIP-event times and the paths alive at every bounce."""
+    _fields_ = [("records", C.c_int64), ("rays", C.c_int64), ("chunks", C.c_int32), ("raygen_ms", C.c_double),
+                ("trace_ms", C.c_double), ("query_ms", C.c_double), ("step_ms", C.c_double), ("resolve_ms", C.c_double),
+                ("alive", C.c_int64 * RT_PATHS_MAX_BOUNCES)]
+
+
 RT_MIRROR_MAX_BOUNCES = 64
 
 
@@ -427,6 +443,14 @@ def load_library():
         lib.rt_get_indirect_info.argtypes = [vp, C.POINTER(RtIndirectInfo)]
         for name in ("rt_indirect_rays", "rt_indirect_rays_device", "rt_indirect_diffuse", "rt_indirect_diffuse_device",
                      "rt_get_indirect_info"):
+            getattr(lib, name).restype = i
+    # include/rt_paths.h (likewise absent from older builds)
+    if hasattr(lib, "rt_indirect_paths"):
+        lib.rt_paths_version.restype = i
+        lib.rt_indirect_paths.argtypes = [vp, C.POINTER(RtPathsParams), i, vp, vp, vp]
+        lib.rt_indirect_paths_device.argtypes = [vp, C.POINTER(RtPathsParams), i, vp, vp, vp, vp]
+        lib.rt_get_paths_info.argtypes = [vp, C.POINTER(RtPathsInfo)]
+        for name in ("rt_indirect_paths", "rt_indirect_paths_device", "rt_get_paths_info"):
             getattr(lib, name).restype = i
     # include/rt_mirror.h (likewise absent from older builds)
     if hasattr(lib, "rt_mirror_records"):

@@ -40,6 +40,9 @@
  *                       default 1), the term scaled by GAIN (finite, default 1), directions hashed with SEED (default 0); gather
  *                       rays that meet a light first count black (emitters 0).  One GPU, instead of --ssaa, --adaptive and
  *                       --lens, without --ao or --denoise.  Composes with --ppm and --out as --lens does
+ *   --indirect-bounces B  with --indirect: every gather ray is followed for up to B bounces (1..8, default 1), one new direction
+ *                       at every diffuse hit (rt_indirect_paths, include/rt_paths.h, in rt_indirect_diffuse's place; 1 is that
+ *                       call itself).  An option of its own: a fifth field of --indirect stays the usage error it has been
  *   --gather-scale S[:SIGMA_PLANE[:refine]]  with --indirect or --ao: gather for every S-th pixel in both directions only (2..8)
  *                       and carry the term to every pixel by rt_upsample_guided (include/rt_capi_upsample.h: 3 normal squarings,
  *                       plane sigma SIGMA_PLANE >= 0, default 0: none); `refine`: the holes it reports are gathered at full
@@ -72,6 +75,7 @@
 #include "../../../include/rt_capi_gbuffer.h"
 #include "../../../include/rt_capi_image.h"
 #include "../../../include/rt_capi_indirect.h"
+#include "../../../include/rt_paths.h"
 #include "../../../include/rt_capi_lens.h"
 #include "../../../include/rt_capi_soft.h"
 #include "../../../include/rt_capi_ssaa.h"
@@ -96,6 +100,7 @@ static int usage(const char *argv0) {
                  "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n"
                  "          [--ao N[:RADIUS] --ao-ppm FILE] [--adaptive 1|2|4[:COLOR[:COS]] [--adaptive-mask FILE]]\n"
                  "          [--lens N[:APERTURE[:FOCUS[:SEED]]]] [--indirect N[:DEPTH[:GAIN[:SEED]]]]\n"
+                 "          [--indirect-bounces B]\n"
                  "          [--gather-scale S[:SIGMA_PLANE[:refine]]] [--accumulate K[:ALPHA]]\n"
                  "          [--svgf IT[:SIGMA_L[:MIN_HISTORY]]]\n", argv0);
     return 1;
@@ -109,6 +114,7 @@ int main(int argc, char **argv) {
     std::string adaptive_arg, mask_path;         /* --adaptive K[:COLOR[:COS]], --adaptive-mask FILE (include/rt_capi_adaptive.h) */
     std::string lens_arg;                        /* --lens N[:APERTURE[:FOCUS[:SEED]]] (include/rt_capi_lens.h) */
     std::string indirect_arg;                    /* --indirect N[:DEPTH[:GAIN[:SEED]]] (include/rt_capi_indirect.h) */
+    std::string bounces_arg;                     /* --indirect-bounces B (include/rt_paths.h) */
     std::string gather_arg;                      /* --gather-scale S[:SIGMA_PLANE[:refine]] (include/rt_capi_upsample.h) */
     bool has_gather = false;
     std::string accumulate_arg;                  /* --accumulate K[:ALPHA] (include/rt_temporal.h) */
@@ -139,6 +145,7 @@ int main(int argc, char **argv) {
         else if (a == "--adaptive-mask" && i + 1 < argc) mask_path = argv[++i];
         else if (a == "--lens" && i + 1 < argc) lens_arg = argv[++i];
         else if (a == "--indirect" && i + 1 < argc) indirect_arg = argv[++i];
+        else if (a == "--indirect-bounces" && i + 1 < argc) bounces_arg = argv[++i];
         else if (a == "--gather-scale" && i + 1 < argc) gather_arg = argv[++i], has_gather = true;
         else if (a == "--accumulate" && i + 1 < argc) accumulate_arg = argv[++i], has_accumulate = true;
         else if (a == "--svgf" && i + 1 < argc) svgf_arg = argv[++i], has_svgf = true;
@@ -261,6 +268,23 @@ int main(int argc, char **argv) {
         if (gpus > 1 || ssaa > 1 || !adaptive_arg.empty() || !lens_arg.empty() || !denoise.empty() || !ao_arg.empty())
             return usage(argv[0]);
     }
+    int bounces = 1;
+    if (!bounces_arg.empty()) {
+        /* B and nothing else, with --indirect: what rt_indirect_paths would refuse is refused here */
+        char *end = nullptr;
+        const long b = std::strtol(bounces_arg.c_str(), &end, 10);
+        if (indirect_arg.empty() || bounces_arg[0] < '0' || bounces_arg[0] > '9' || *end != '\0' || b < 1 || b > RT_PATHS_MAX_BOUNCES)
+            return usage(argv[0]);
+        bounces = (int)b;
+    }
+    /* the indirect term of n records onto base (or alone): rt_indirect_diffuse, or with --indirect-bounces above 1
+     * rt_indirect_paths of the same parameters */
+    const auto indirect_term = [&](rt_scene *scene, const rt_indirect_params &g, int n, const rt_hit *records, const float *base,
+                                   float *values) {
+        if (bounces == 1) return rt_indirect_diffuse(scene, &g, n, records, base, values);
+        const rt_paths_params q = {g.samples, g.gather_depth, g.chunk_records, g.emitters, g.seed, g.key0, g.gain, bounces};
+        return rt_indirect_paths(scene, &q, n, records, base, values);
+    };
     rt_upsample_params up = {0, 3, 3, 0, 0, 0.0f, 0.0f};
     bool refine = false;
     if (has_gather) {
@@ -502,12 +526,20 @@ int main(int argc, char **argv) {
                     rc = gather_scaled(hits, [&](int n, int, const rt_hit *records, uint32_t key0, float *values) {
                              rt_indirect_params g = ind;
                              g.key0 = key0;
-                             return rt_indirect_diffuse(scene, &g, n, records, nullptr, values);
+                             return indirect_term(scene, g, n, records, nullptr, values);
                          }, 1, 0.0f, pixels.data(), pixels.data(), "Indirect diffuse ");
                 else
-                    rc = rt_indirect_diffuse(scene, &ind, W * H, hits.data(), pixels.data(), pixels.data());
+                    rc = indirect_term(scene, ind, W * H, hits.data(), pixels.data(), pixels.data());
                 rt_indirect_info info;
-                if (rc == RT_OK && rt_get_indirect_info(scene, &info) == RT_OK)
+                rt_paths_info paths;
+                if (rc == RT_OK && bounces > 1 && rt_get_paths_info(scene, &paths) == RT_OK) {
+                    std::printf("Indirect paths             : %d x %d paths of up to %d bounces at depth %d, gain %g, seed %u: %lld rays in %d "
+                                "chunk(s); ray generation %f ms, trace %f ms, query %f ms, step %f ms, resolve %f ms; alive",
+                                ind.samples, ind.samples, bounces, ind.gather_depth, (double)ind.gain, ind.seed, (long long)paths.rays,
+                                paths.chunks, paths.raygen_ms, paths.trace_ms, paths.query_ms, paths.step_ms, paths.resolve_ms);
+                    for (int b = 0; b < bounces; ++b) std::printf(" %lld", (long long)paths.alive[b]);
+                    std::printf("\n");
+                } else if (rc == RT_OK && rt_get_indirect_info(scene, &info) == RT_OK)
                     std::printf("Indirect diffuse           : %d x %d gather rays at depth %d, gain %g, seed %u: %lld rays in %d chunk(s); "
                                 "ray generation %f ms, trace %f ms, query %f ms, resolve %f ms\n", ind.samples, ind.samples,
                                 ind.gather_depth, (double)ind.gain, ind.seed, (long long)info.rays, info.chunks, info.raygen_ms,

@@ -354,6 +354,14 @@ extern "C" {
 
 int rt_capi_indirect_version(void) { return RT_CAPI_INDIRECT_VERSION; }
 
+/* rt_internal.h: the chunk's ray generation, for rt_paths.hip's bounce 0 */
+int rt_internal_indirect_raygen(int samples, uint32_t seed, uint32_t key, uint32_t m, const void *d_hits, void *d_rays,
+                                void *hip_stream) {
+    rt_indirect_params pr{};
+    pr.samples = samples, pr.seed = seed;
+    return enqueue_raygen(pr, key, m, d_hits, d_rays, static_cast<hipStream_t>(hip_stream));
+}
+
 int rt_indirect_rays_device(const rt_indirect_params *pr, int n, const void *d_hits, int device, void *d_out_rays, void *hip_stream) {
     int rc = check_rays_args(pr, n, d_hits, d_out_rays, true);
     if (rc == RT_OK) rc = rt_internal_check_device(device);

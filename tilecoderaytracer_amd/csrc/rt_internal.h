@@ -31,7 +31,7 @@ typedef struct rt_internal_unit {
     double (*stage_ms)(void *state, uint64_t seq);
 } rt_internal_unit;
 enum { RT_INTERNAL_UNIT_ADAPTIVE, RT_INTERNAL_UNIT_LENS, RT_INTERNAL_UNIT_INDIRECT, RT_INTERNAL_UNIT_MIRROR,
-       RT_INTERNAL_UNIT_MIRROR_COMPACT, RT_INTERNAL_UNIT_GLASS, RT_INTERNAL_UNIT_GLASS_COMPACT, RT_INTERNAL_UNITS };
+       RT_INTERNAL_UNIT_MIRROR_COMPACT, RT_INTERNAL_UNIT_PATHS, RT_INTERNAL_UNIT_GLASS, RT_INTERNAL_UNIT_GLASS_COMPACT, RT_INTERNAL_UNITS };
 
 /* rt_capi.hip: the text behind rt_last_error(); returns code */
 int rt_internal_set_error(int code, const char *msg);
@@ -83,6 +83,13 @@ int rt_internal_object_reflective(rt_scene *s, const float **d_rf, int *n_object
 int rt_internal_object_glass(rt_scene *s, const float4 **d_table, int *n_objects);
 /* a device buffer that only grows (the device is synchronised before the old one is freed) */
 int rt_internal_grow(void **buf, size_t *bytes, size_t need);
+
+/* ---- rt_indirect.hip, for rt_paths.hip (include/rt_paths.h) ---- */
+/* One rt_indirect_raygen_kernel launch, exactly as rt_indirect_diffuse_device enqueues it for a chunk: the n x n gather rays
+ * (include/rt_capi_indirect.h) of m records at d_hits, record p sampling with key + p, 24 bytes each at d_rays; m n^2 < 2^31.
+ * Device pointers, nothing checked, no wait. */
+int rt_internal_indirect_raygen(int samples, uint32_t seed, uint32_t key, uint32_t m, const void *d_hits, void *d_rays,
+                                void *hip_stream);
 
 /* ---- rt_mirror_compact.hip ---- */
 /* Its instantiation of rt_scan.h's two-level scan, enqueued on hip_stream exactly as the call enqueues it for a bounce's counts
