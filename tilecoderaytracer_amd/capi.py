@@ -169,6 +169,16 @@ class RtPathsInfo(C.Structure):
                 ("alive", C.c_int64 * RT_PATHS_MAX_BOUNCES)]
 
 
+class RtPathsCompactInfo(C.Structure):
+    """include/rt_paths_compact.h: the scene's last rt_indirect_paths_compact* call -- its records, the rays its ray batches were
+    asked (records * S + the sum of alive[b >= 1]), chunks, ray batches and hit queries launched, stream waits made, the five
+    stages' HIP-event times and the paths alive at every bounce."""
+    _fields_ = [("records", C.c_int64), ("rays", C.c_int64), ("chunks", C.c_int32), ("traces", C.c_int32),
+                ("queries", C.c_int32), ("syncs", C.c_int32), ("raygen_ms", C.c_double), ("trace_ms", C.c_double),
+                ("query_ms", C.c_double), ("step_ms", C.c_double), ("resolve_ms", C.c_double),
+                ("alive", C.c_int64 * RT_PATHS_MAX_BOUNCES)]
+
+
 RT_MIRROR_MAX_BOUNCES = 64
 
 
@@ -451,6 +461,14 @@ def load_library():
         lib.rt_indirect_paths_device.argtypes = [vp, C.POINTER(RtPathsParams), i, vp, vp, vp, vp]
         lib.rt_get_paths_info.argtypes = [vp, C.POINTER(RtPathsInfo)]
         for name in ("rt_indirect_paths", "rt_indirect_paths_device", "rt_get_paths_info"):
+            getattr(lib, name).restype = i
+    # include/rt_paths_compact.h (likewise)
+    if hasattr(lib, "rt_indirect_paths_compact"):
+        lib.rt_paths_compact_version.restype = i
+        lib.rt_indirect_paths_compact.argtypes = [vp, C.POINTER(RtPathsParams), i, vp, vp, vp]
+        lib.rt_indirect_paths_compact_device.argtypes = [vp, C.POINTER(RtPathsParams), i, vp, vp, vp, vp]
+        lib.rt_get_paths_compact_info.argtypes = [vp, C.POINTER(RtPathsCompactInfo)]
+        for name in ("rt_indirect_paths_compact", "rt_indirect_paths_compact_device", "rt_get_paths_compact_info"):
             getattr(lib, name).restype = i
     # include/rt_mirror.h (likewise absent from older builds)
     if hasattr(lib, "rt_mirror_records"):

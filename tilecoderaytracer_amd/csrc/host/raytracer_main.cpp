@@ -43,6 +43,9 @@
  *   --indirect-bounces B  with --indirect: every gather ray is followed for up to B bounces (1..8, default 1), one new direction
  *                       at every diffuse hit (rt_indirect_paths, include/rt_paths.h, in rt_indirect_diffuse's place; 1 is that
  *                       call itself).  An option of its own: a fifth field of --indirect stays the usage error it has been
+ *   --indirect-compact  with --indirect: the term is computed by rt_indirect_paths_compact (include/rt_paths_compact.h) whatever B
+ *                       is: the same frame bit for bit, only the paths still alive are traced at every bounce after the first,
+ *                       and the host waits for the device once per bounce
  *   --gather-scale S[:SIGMA_PLANE[:refine]]  with --indirect or --ao: gather for every S-th pixel in both directions only (2..8)
  *                       and carry the term to every pixel by rt_upsample_guided (include/rt_capi_upsample.h: 3 normal squarings,
  *                       plane sigma SIGMA_PLANE >= 0, default 0: none); `refine`: the holes it reports are gathered at full
@@ -76,6 +79,7 @@
 #include "../../../include/rt_capi_image.h"
 #include "../../../include/rt_capi_indirect.h"
 #include "../../../include/rt_paths.h"
+#include "../../../include/rt_paths_compact.h"
 #include "../../../include/rt_capi_lens.h"
 #include "../../../include/rt_capi_soft.h"
 #include "../../../include/rt_capi_ssaa.h"
@@ -100,7 +104,7 @@ static int usage(const char *argv0) {
                  "          [--soft I:N[:R] ...] [--denoise IT[:SIGMA[:K]]] [--ppm FILE [--exposure E]]\n"
                  "          [--ao N[:RADIUS] --ao-ppm FILE] [--adaptive 1|2|4[:COLOR[:COS]] [--adaptive-mask FILE]]\n"
                  "          [--lens N[:APERTURE[:FOCUS[:SEED]]]] [--indirect N[:DEPTH[:GAIN[:SEED]]]]\n"
-                 "          [--indirect-bounces B]\n"
+                 "          [--indirect-bounces B] [--indirect-compact]\n"
                  "          [--gather-scale S[:SIGMA_PLANE[:refine]]] [--accumulate K[:ALPHA]]\n"
                  "          [--svgf IT[:SIGMA_L[:MIN_HISTORY]]]\n", argv0);
     return 1;
@@ -115,6 +119,7 @@ int main(int argc, char **argv) {
     std::string lens_arg;                        /* --lens N[:APERTURE[:FOCUS[:SEED]]] (include/rt_capi_lens.h) */
     std::string indirect_arg;                    /* --indirect N[:DEPTH[:GAIN[:SEED]]] (include/rt_capi_indirect.h) */
     std::string bounces_arg;                     /* --indirect-bounces B (include/rt_paths.h) */
+    bool indirect_compact = false;               /* --indirect-compact (include/rt_paths_compact.h) */
     std::string gather_arg;                      /* --gather-scale S[:SIGMA_PLANE[:refine]] (include/rt_capi_upsample.h) */
     bool has_gather = false;
     std::string accumulate_arg;                  /* --accumulate K[:ALPHA] (include/rt_temporal.h) */
@@ -146,6 +151,7 @@ int main(int argc, char **argv) {
         else if (a == "--lens" && i + 1 < argc) lens_arg = argv[++i];
         else if (a == "--indirect" && i + 1 < argc) indirect_arg = argv[++i];
         else if (a == "--indirect-bounces" && i + 1 < argc) bounces_arg = argv[++i];
+        else if (a == "--indirect-compact") indirect_compact = true;
         else if (a == "--gather-scale" && i + 1 < argc) gather_arg = argv[++i], has_gather = true;
         else if (a == "--accumulate" && i + 1 < argc) accumulate_arg = argv[++i], has_accumulate = true;
         else if (a == "--svgf" && i + 1 < argc) svgf_arg = argv[++i], has_svgf = true;
@@ -277,12 +283,14 @@ int main(int argc, char **argv) {
             return usage(argv[0]);
         bounces = (int)b;
     }
+    if (indirect_compact && indirect_arg.empty()) return usage(argv[0]);
     /* the indirect term of n records onto base (or alone): rt_indirect_diffuse, or with --indirect-bounces above 1
-     * rt_indirect_paths of the same parameters */
+     * rt_indirect_paths of the same parameters, or with --indirect-compact rt_indirect_paths_compact of them */
     const auto indirect_term = [&](rt_scene *scene, const rt_indirect_params &g, int n, const rt_hit *records, const float *base,
                                    float *values) {
-        if (bounces == 1) return rt_indirect_diffuse(scene, &g, n, records, base, values);
+        if (bounces == 1 && !indirect_compact) return rt_indirect_diffuse(scene, &g, n, records, base, values);
         const rt_paths_params q = {g.samples, g.gather_depth, g.chunk_records, g.emitters, g.seed, g.key0, g.gain, bounces};
+        if (indirect_compact) return rt_indirect_paths_compact(scene, &q, n, records, base, values);
         return rt_indirect_paths(scene, &q, n, records, base, values);
     };
     rt_upsample_params up = {0, 3, 3, 0, 0, 0.0f, 0.0f};
@@ -532,7 +540,16 @@ int main(int argc, char **argv) {
                     rc = indirect_term(scene, ind, W * H, hits.data(), pixels.data(), pixels.data());
                 rt_indirect_info info;
                 rt_paths_info paths;
-                if (rc == RT_OK && bounces > 1 && rt_get_paths_info(scene, &paths) == RT_OK) {
+                rt_paths_compact_info compact;
+                if (rc == RT_OK && indirect_compact && rt_get_paths_compact_info(scene, &compact) == RT_OK) {
+                    std::printf("Indirect paths (compact)   : %d x %d paths of up to %d bounces at depth %d, gain %g, seed %u: %lld rays in %d "
+                                "chunk(s), %d traces, %d queries, %d syncs; ray generation %f ms, trace %f ms, query %f ms, step %f ms, "
+                                "resolve %f ms; alive", ind.samples, ind.samples, bounces, ind.gather_depth, (double)ind.gain, ind.seed,
+                                (long long)compact.rays, compact.chunks, compact.traces, compact.queries, compact.syncs, compact.raygen_ms,
+                                compact.trace_ms, compact.query_ms, compact.step_ms, compact.resolve_ms);
+                    for (int b = 0; b < bounces; ++b) std::printf(" %lld", (long long)compact.alive[b]);
+                    std::printf("\n");
+                } else if (rc == RT_OK && bounces > 1 && rt_get_paths_info(scene, &paths) == RT_OK) {
                     std::printf("Indirect paths             : %d x %d paths of up to %d bounces at depth %d, gain %g, seed %u: %lld rays in %d "
                                 "chunk(s); ray generation %f ms, trace %f ms, query %f ms, step %f ms, resolve %f ms; alive",
                                 ind.samples, ind.samples, bounces, ind.gather_depth, (double)ind.gain, ind.seed, (long long)paths.rays,

@@ -31,7 +31,8 @@ typedef struct rt_internal_unit {
     double (*stage_ms)(void *state, uint64_t seq);
 } rt_internal_unit;
 enum { RT_INTERNAL_UNIT_ADAPTIVE, RT_INTERNAL_UNIT_LENS, RT_INTERNAL_UNIT_INDIRECT, RT_INTERNAL_UNIT_MIRROR,
-       RT_INTERNAL_UNIT_MIRROR_COMPACT, RT_INTERNAL_UNIT_PATHS, RT_INTERNAL_UNIT_GLASS, RT_INTERNAL_UNIT_GLASS_COMPACT, RT_INTERNAL_UNITS };
+       RT_INTERNAL_UNIT_MIRROR_COMPACT, RT_INTERNAL_UNIT_PATHS, RT_INTERNAL_UNIT_GLASS, RT_INTERNAL_UNIT_PATHS_COMPACT,
+       RT_INTERNAL_UNIT_GLASS_COMPACT, RT_INTERNAL_UNITS };
 
 /* rt_capi.hip: the text behind rt_last_error(); returns code */
 int rt_internal_set_error(int code, const char *msg);
@@ -93,7 +94,7 @@ int rt_internal_indirect_raygen(int samples, uint32_t seed, uint32_t key, uint32
 
 /* ---- rt_mirror_compact.hip ---- */
 /* Its instantiation of rt_scan.h's two-level scan, enqueued on hip_stream exactly as the call enqueues it for a bounce's counts
- * (the call itself goes through here, and so does rt_glass_compact.hip, which has no scan kernels of its own), so that a test can give the scan more counts than any batch that fits a device would:
+ * (the call itself goes through here, and so do rt_glass_compact.hip and rt_paths_compact.hip, which have no scan kernels of their own), so that a test can give the scan more counts than any batch that fits a device would:
  * of n_counts > 0 counts, d_offsets[i] = the sum of the counts before i in i's group of kScanBlock (n_counts words),
  * d_group_sums[g] and d_group_base[g] = group g's sum and the sum of the groups before it (ceil(n_counts / kScanBlock) words
  * each), *d_total = the sum of all.  Device pointers, nothing checked, no wait. */

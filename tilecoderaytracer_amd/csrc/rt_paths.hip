@@ -10,8 +10,9 @@
  *            its ray (24 bytes), the ray's colour (12), the ray's record (48), its throughput T (12) and its sum acc (12), 108
  *            bytes a path.  A path that has ended is one whose stored T is (0, 0, 0): that is what the definition's third stop
  *            rule makes of it anyway, so aliveness costs no word of its own.  The step masks a light's colour, accumulates,
- *            multiplies T, decides, and writes the next ray (rt_capi_ao.h's arithmetic for n = 1, s = 0, a text of its own as
- *            rt_glass_step_kernel's is) or six zeros.  The first step reads no T and no acc (T_0 = 1: the path lives if its
+ *            multiplies T, decides, and writes the next ray (rt_capi_ao.h's arithmetic for n = 1, s = 0) or six zeros -- a text
+ *            of its own, as rt_glass_step_kernel's is; rt_paths_body.h holds the same arithmetic as functions for
+ *            rt_paths_compact.hip (THE STEP KEEPS ITS OWN TEXT, below, says why there are two).  The first step reads no T and no acc (T_0 = 1: the path lives if its
  *            record does), the last one writes neither T nor a ray.
  *   resolve  per record the sequential sum of its S paths' acc, the divide, the weight, the base: rt_indirect_resolve_kernel's
  *            arithmetic with no gather records.
@@ -29,6 +30,7 @@
 
 #include "../../include/rt_paths.h"
 #include "rt_host.h"
+#include "rt_paths_body.h"
 
 #pragma clang fp contract(off)
 
@@ -50,39 +52,23 @@ static_assert(sizeof(rt_hit) == 48, "rt_capi_query.h layout");
 
 namespace {
 
-constexpr int kBlock = 256;                            /* step: paths a workgroup; resolve: lanes a workgroup */
-constexpr int kResolveSamples = 1024;                  /* resolve: paths a workgroup -- 1024 / S records */
-constexpr int kMaxSamples = RT_INDIRECT_MAX_SAMPLES;   /* n */
-constexpr int kMaxBounces = RT_PATHS_MAX_BOUNCES;      /* B */
+constexpr int kBlock = kPathsBlock;                    /* step: paths a workgroup; resolve: lanes a workgroup */
+constexpr int kResolveSamples = kPathsResolveSamples;  /* resolve: paths a workgroup -- 1024 / S records */
+constexpr int kMaxBounces = kPathsMaxBounces;          /* B */
 constexpr size_t kPathBytes = 108;                     /* a path's scratch: ray 24, colour 12, record 48, T 12, acc 12 */
 constexpr size_t kChunkBytes = (size_t)256 << 20;      /* the default chunk: its scratch within 256 MiB */
-constexpr long long kMaxBatchRays = 0x7fffffffLL - 64; /* rt_trace_rays' grid limit for a flat list (include/rt_capi_rays.h) */
-constexpr int kMaxRecords = 533333333;                 /* rt_render_gbuffer's record limit */
-constexpr int kHitWords = 12, kHitFlagsWord = 11;      /* an rt_hit in 4-byte words; its flags (byte 44) */
-constexpr uint32_t kGolden = 0x9e3779b9u;
-/* alive[b] is kept as kCountSlots partial counts, one 128-byte line each: a wavefront adds to the slot of its number.  One
- * counter a bounce serialised a million same-address atomics a step at 4096 x 4096, n = 2 -- 12.8 ms a step against 0.5 ms for a
- * copy of the step's bytes (profiles/paths_experiments.txt) */
-constexpr uint32_t kCountSlots = 128, kCountStride = 16;                 /* slots a bounce; 64-bit words from slot to slot */
+constexpr uint32_t kGolden = kPathsGolden;
+constexpr uint32_t kCountSlots = kPathsCountSlots, kCountStride = kPathsCountStride;   /* alive[]'s partial counts (rt_paths_body.h) */
 constexpr size_t kCountWords = (size_t)kMaxBounces * kCountSlots * kCountStride;
-
-/* resolve: a record's 3 S floats in LDS, padded to an odd stride so that the sums' reads spread over the banks */
-constexpr int lds_stride(int S) { return (3 * S) | 1; }
-constexpr int lds_floats() {
-    int most = 0;
-    for (int n = 1; n <= kMaxSamples; ++n) most = std::max(most, (kResolveSamples / (n * n)) * lds_stride(n * n));
-    return most;
-}
-static_assert(lds_floats() * 4 <= 16384, "resolve: LDS");
 
 } // namespace
 
-/* the 32-bit integer hash "lowbias32" (include/rt_capi_soft.h) */
-__device__ __forceinline__ uint32_t rt_paths_hash(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
+/* THE STEP KEEPS ITS OWN TEXT.  Its arithmetic -- the mask, the accumulation, the throughput, the stop rule, the next ray -- is
+ * also rt_paths_body.h's rt_paths_accumulate, rt_paths_decide and rt_paths_next_ray, which rt_paths_compact.hip's kernels are made
+ * of.  This kernel was written before them, and calling any of the three from it changed the instructions of its two
+ * instantiations that are not LAST (the scheduler moved the multiplications and the key's addition; five forms were tried,
+ * DESIGN.md section 35), so by the rule of DESIGN.md section 31 it stays as it was measured.  The two texts are held together by
+ * tests/test_paths_compact_gpu.py, which compares the two units' outputs word for word on every frame. */
 /* The step after bounce b of the `total` paths of a chunk (total < 2^31), one lane a path, path r = p S + s of the chunk at
  * slot r of every array: colours[3 r ..] and gather[3 r ..] (three float4: the record, read as three 16-byte loads a lane) are
  * what the bounce's ray batch and hit query returned for rays[6 r ..]; T[3 r ..] and acc[3 r ..] are the path's own.
@@ -105,8 +91,8 @@ __global__ __launch_bounds__(kBlock) void rt_paths_step_kernel(uint32_t total, u
     bool live = false;
     if (in) {
         if (FIRST) {
-            const int32_t *h = hits + (size_t)(r / S) * kHitWords;
-            live = h[0] >= 0 && (h[kHitFlagsWord] & RT_HIT_LIGHT) == 0;
+            const int32_t *h = hits + (size_t)(r / S) * kPathsHitWords;
+            live = h[0] >= 0 && (h[kPathsHitFlagsWord] & RT_HIT_LIGHT) == 0;
         } else {
             Tx = T[3 * (size_t)r], Ty = T[3 * (size_t)r + 1], Tz = T[3 * (size_t)r + 2];
             live = !(Tx == 0.0f && Ty == 0.0f && Tz == 0.0f);
@@ -178,41 +164,12 @@ __global__ __launch_bounds__(kBlock) void rt_paths_step_kernel(uint32_t total, u
     o[3] = Px + Dx, o[4] = Py + Dy, o[5] = Pz + Dz;
 }
 
-/* out[3 p + c] = base[3 p + c] + term.c of the header for the m records of a chunk: path s of record p has its sum at
- * acc[3 (p S + s) ..].  rt_indirect_resolve_kernel's text without the gather records (the steps have masked already): a workgroup
- * takes kResolveSamples / S records, reads their paths' floats as the consecutive words they are into LDS (lds_stride(S) floats
- * a record), then one lane per record and channel sums its S values in order, divides, multiplies by the weight, adds the base
- * and stores.  A word of the output is read (base) and stored by the same lane, once: out == base is allowed. */
+/* the resolve of the m records of a chunk: rt_paths_body.h's rt_paths_resolve, the grid ceil(m / (kResolveSamples / S)) */
 __global__ __launch_bounds__(kBlock) void rt_paths_resolve_kernel(uint32_t m, int S, float gain, const float *__restrict__ acc,
                                                                   const int32_t *__restrict__ hits, const float *__restrict__ kd,
                                                                   int n_objects, const float *base, float *out) {
-    __shared__ float lds[lds_floats()];
-    const uint32_t group = (uint32_t)kResolveSamples / (uint32_t)S;
-    const uint32_t g0 = blockIdx.x * group;
-    const uint32_t records = min(group, m - g0);                         /* (g0 < m: the grid is ceil(m / group)) */
-    const uint32_t per = 3u * (uint32_t)S, stride = (uint32_t)lds_stride(S), words = records * per;
-    const float *src = acc + (size_t)per * (size_t)g0;
-    for (uint32_t i = threadIdx.x; i < words; i += (uint32_t)kBlock) {
-        const uint32_t px = i / per;
-        lds[px * stride + (i - px * per)] = src[i];
-    }
-    __syncthreads();
-    for (uint32_t t = threadIdx.x; t < 3u * records; t += (uint32_t)kBlock) {
-        const uint32_t px = t / 3u, c = t - 3u * px;
-        const float *v = lds + px * stride + c;
-        float sum = v[0];
-        for (int s = 1; s < S; ++s) sum = sum + v[3 * s];
-        const float mean = sum / (float)S;
-        const int32_t *h = hits + (size_t)(g0 + px) * kHitWords;
-        const int32_t object = h[0];
-        float term = 0.0f;
-        if (object >= 0 && (h[kHitFlagsWord] & RT_HIT_LIGHT) == 0) {
-            const float k = object < n_objects ? kd[object] : 0.0f;
-            term = ((__int_as_float(h[8 + c]) * k) * gain) * mean;
-        }
-        const size_t at = 3 * (size_t)(g0 + px) + c;
-        out[at] = base ? base[at] + term : term;
-    }
+    __shared__ float lds[rt_paths_lds_floats()];
+    rt_paths_resolve(lds, m, S, gain, acc, hits, kd, n_objects, base, out);
 }
 
 namespace {
@@ -232,40 +189,8 @@ struct RtPathsState {
 
 unsigned blocks_of(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
-/* the header's checks in its order (device: the device variant's alignments as well) */
-int check_args(const rt_scene *s, const rt_paths_params *pr, int n, const void *hits, const void *base, const void *out, bool device) {
-    if (!s) return fail(RT_ERR_INVALID, "scene is NULL");
-    if (!pr) return fail(RT_ERR_INVALID, "params is NULL");
-    if (pr->samples < 1 || pr->samples > kMaxSamples)
-        return fail(RT_ERR_INVALID, "samples must be 1.." + std::to_string(kMaxSamples) + " (got " + std::to_string(pr->samples) + ")");
-    if (pr->bounces < 1 || pr->bounces > kMaxBounces)
-        return fail(RT_ERR_INVALID, "bounces must be 1.." + std::to_string(kMaxBounces) + " (got " + std::to_string(pr->bounces) + ")");
-    if (pr->gather_depth < 0) return fail(RT_ERR_INVALID, "gather_depth must not be negative");
-    if (pr->chunk_records < 0) return fail(RT_ERR_INVALID, "chunk_records must not be negative");
-    if (pr->emitters != 0 && pr->emitters != 1)
-        return fail(RT_ERR_INVALID, "emitters must be 0 or 1 (got " + std::to_string(pr->emitters) + ")");
-    if (!std::isfinite(pr->gain)) return fail(RT_ERR_INVALID, "gain must be finite");
-    if (n < 0) return fail(RT_ERR_INVALID, "n < 0");
-    if (n > 0 && !hits) return fail(RT_ERR_INVALID, "hits pointer is NULL");
-    if (n > 0 && !out) return fail(RT_ERR_INVALID, "output pointer is NULL");
-    if (n > kMaxRecords) return fail(RT_ERR_INVALID, "more than " + std::to_string(kMaxRecords) + " records");
-    if (device && ((uintptr_t)hits & 15u) != 0) return fail(RT_ERR_INVALID, "d_hits must be 16-byte aligned");
-    if (device && ((uintptr_t)out & 3u) != 0) return fail(RT_ERR_INVALID, "d_out_rgb must be 4-byte aligned");
-    if (device && base && ((uintptr_t)base & 3u) != 0) return fail(RT_ERR_INVALID, "d_base_rgb must be 4-byte aligned");
-    if (rt_internal_scene_soft(s))
-        return fail(RT_ERR_INVALID, "the indirect paths refuse a scene with area lights: a ray batch keys their shadow samples by "
-                                    "the ray index (include/rt_capi_soft.h), so the result would change with chunk_records");
-    return RT_OK;
-}
-
-/* the records a launch gathers for: the caller's chunk_records, or the default -- as many as keep the scratch within
- * kChunkBytes, at least one -- never more than kMaxBatchRays rays' worth, nor than the batch has */
-int chunk_records(const rt_paths_params &pr, int n) {
-    const long long S = (long long)pr.samples * pr.samples;                          /* paths a record; <= 64 */
-    long long c = pr.chunk_records > 0 ? pr.chunk_records : std::max<long long>(1, (long long)(kChunkBytes / (kPathBytes * (size_t)S)));
-    c = std::min(c, kMaxBatchRays / S);
-    return (int)std::min<long long>(c, n);
-}
+/* the records a launch gathers for (rt_paths_body.h) */
+int chunk_records(const rt_paths_params &pr, int n) { return rt_paths_chunk_records(pr, n, kPathBytes, kChunkBytes); }
 
 /* the last call's stage times from its events and its counts from the device, once */
 int collect(RtPathsState *a) {
@@ -343,7 +268,7 @@ int run(rt_scene *s, const rt_paths_params &pr, int n, const void *d_hits, const
     const unsigned group = (unsigned)(kResolveSamples / S);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const uint32_t m = (uint32_t)std::min(chunk, n - i0);
-        const uint32_t total = m * (uint32_t)S;                           /* <= kMaxBatchRays */
+        const uint32_t total = m * (uint32_t)S;                           /* <= kPathsMaxBatchRays */
         const int n_rays = (int)total;
         const char *hits = static_cast<const char *>(d_hits) + (size_t)i0 * 48;
         const uint32_t key = pr.key0 + (uint32_t)i0;                      /* the chunk's first record's; its first path's: */
@@ -390,7 +315,7 @@ int rt_paths_version(void) { return RT_PATHS_VERSION; }
 
 int rt_indirect_paths_device(rt_scene *s, const rt_paths_params *pr, int n, const void *d_hits, const void *d_base_rgb, void *d_out_rgb,
                              void *hip_stream) {
-    const int rc = check_args(s, pr, n, d_hits, d_base_rgb, d_out_rgb, true);
+    const int rc = rt_paths_check_args(s, pr, n, d_hits, d_base_rgb, d_out_rgb, true);
     if (rc || n == 0) return rc;
     const rt_paths_params p = *pr;
     rt_internal_lock(s);
@@ -399,7 +324,7 @@ int rt_indirect_paths_device(rt_scene *s, const rt_paths_params *pr, int n, cons
 }
 
 int rt_indirect_paths(rt_scene *s, const rt_paths_params *pr, int n, const rt_hit *hits, const float *base_rgb, float *out_rgb) {
-    int rc = check_args(s, pr, n, hits, base_rgb, out_rgb, false);
+    int rc = rt_paths_check_args(s, pr, n, hits, base_rgb, out_rgb, false);
     if (rc || n == 0) return rc;
     const rt_paths_params p = *pr;
     rt_internal_lock(s);

@@ -1008,7 +1008,7 @@ class Renderer:
 
     def indirect_diffuse_scaled(self, hits, scale, samples=4, gather_depth=1, gain=1.0, seed=0, key0=0, emitters=False,
                                 chunk_records=0, base=None, normal_squarings=3, sigma_plane=0.0, refine=False,
-                                key0_refine=0x80000000, return_flags=False, bounces=1):
+                                key0_refine=0x80000000, return_flags=False, bounces=1, compact=False):
         """indirect_diffuse() gathered for every scale-th pixel in both directions only and carried to every pixel of the frame
         hits (HIT_DTYPE (Wn, H)) by upsample_guided() (include/rt_capi_upsample.h) -> float32 (Wn, H, 3), and with return_flags
         also the holes, bool (Wn, H).  DEFINITION: cells = subsample_hits(hits, scale, white=True); lo = indirect_diffuse(cells,
@@ -1018,10 +1018,10 @@ class Renderer:
         and each pixel multiplies by its own albedo.  refine: the holes, in ascending pixel order (np.flatnonzero(flags)), are
         then gathered as one more batch of their own full-colour, full-resolution records with key0 = key0_refine and no base,
         and base + term (term, without a base: one fp32 add a word) is written over the fallback.  chunk_records never changes
-        the result.  bounces: given to both indirect_diffuse() calls."""
+        the result.  bounces and compact: given to both indirect_diffuse() calls."""
         hits = _frame_records(hits)
         kw = dict(samples=samples, gather_depth=gather_depth, gain=gain, seed=seed, emitters=emitters, chunk_records=chunk_records,
-                  bounces=bounces)
+                  bounces=bounces, compact=compact)
         cells = subsample_hits(hits, scale, True, self._device)
         lo = self.indirect_diffuse(cells, key0=key0, **kw)
         out, flags = upsample_guided(hits, lo, scale, normal_squarings, False, True, sigma_plane, 0.0, base, True, self._device)
@@ -1051,7 +1051,7 @@ class Renderer:
         return cells, Wl, Hl
 
     def indirect_diffuse(self, hits, samples=4, gather_depth=1, gain=1.0, seed=0, key0=0, emitters=False, chunk_records=0,
-                         base=None, bounces=1):
+                         base=None, bounces=1, compact=False):
         """One diffuse bounce for every hit record (include/rt_capi_indirect.h, rt_indirect_diffuse): samples x samples gather
         rays per record in ambient_occlusion()'s directions, traced at gather_depth, averaged and weighted by the record's
         colour, its object's diffuse coefficient and gain.  hits: C-contiguous HIT_DTYPE of any shape, as render_gbuffer() and
@@ -1060,9 +1060,10 @@ class Renderer:
         gather ray whose first hit is a light counts black, since the record's direct shading has that light already.
         -> float32 hits.shape + (3,).  chunk_records (the most records gathered per launch, 0: the default) never changes the
         result; indirect_info() tells what each stage cost.  bounces 1: this call; any other count is indirect_paths()
-        (include/rt_paths.h), which the library checks."""
-        if bounces != 1:
-            return self.indirect_paths(hits, bounces, samples, gather_depth, gain, seed, key0, emitters, chunk_records, base)
+        (include/rt_paths.h), which the library checks.  compact: indirect_paths(compact=True) whatever bounces is."""
+        if bounces != 1 or compact:
+            return self.indirect_paths(hits, bounces, samples, gather_depth, gain, seed, key0, emitters, chunk_records, base,
+                                       compact)
         hits = _records(hits)
         params = indirect_params(samples, gather_depth, gain, seed, key0, emitters, chunk_records)
         if base is not None:
@@ -1075,13 +1076,14 @@ class Renderer:
         return out
 
     def indirect_diffuse_device(self, n, hits_ptr, base_ptr, out_ptr, stream=0, samples=4, gather_depth=1, gain=1.0, seed=0, key0=0,
-                                emitters=False, chunk_records=0, bounces=1):
+                                emitters=False, chunk_records=0, bounces=1, compact=False):
         """Enqueue the indirect term of n records (48 bytes each, hits_ptr 16-byte aligned) into 3 n float32 at out_ptr, added to
         the 3 n float32 at base_ptr unless that is 0 (base_ptr == out_ptr: in place), on a HIP stream (no sync: nothing is read
-        back).  bounces 1: rt_indirect_diffuse_device; any other count is indirect_paths_device()."""
-        if bounces != 1:
+        back).  bounces 1: rt_indirect_diffuse_device; any other count is indirect_paths_device().  compact:
+        indirect_paths_device(compact=True) whatever bounces is -- that call WAITS for the stream."""
+        if bounces != 1 or compact:
             return self.indirect_paths_device(n, hits_ptr, base_ptr, out_ptr, stream, bounces, samples, gather_depth, gain, seed,
-                                              key0, emitters, chunk_records)
+                                              key0, emitters, chunk_records, compact)
         params = indirect_params(samples, gather_depth, gain, seed, key0, emitters, chunk_records)
         capi.check(self._lib.rt_indirect_diffuse_device(self._scene, C.byref(params), n, C.c_void_p(hits_ptr),
                                                         C.c_void_p(base_ptr or None), C.c_void_p(out_ptr), C.c_void_p(stream)))
@@ -1094,12 +1096,14 @@ class Renderer:
         return info
 
     def indirect_paths(self, hits, bounces=2, samples=4, gather_depth=1, gain=1.0, seed=0, key0=0, emitters=False,
-                       chunk_records=0, base=None):
+                       chunk_records=0, base=None, compact=False):
         """Diffuse light paths of up to `bounces` rays for every hit record (include/rt_paths.h, rt_indirect_paths): each of
         indirect_diffuse()'s samples x samples gather rays is followed from diffuse hit to diffuse hit, one new direction a hit,
         and what every bounce's ray brings in is added, weighted by the surfaces the path has left.  The arguments and the
         result are indirect_diffuse()'s; with bounces 1 so is every word.  paths_info() tells what each stage cost and how many
-        paths were alive at every bounce."""
+        paths were alive at every bounce.  compact: trace only the paths still alive (include/rt_paths_compact.h,
+        rt_indirect_paths_compact): the same words, fewer rays traced, one host wait per bounce; paths_compact_info() then
+        describes the call, and paths_info() does not."""
         hits = _records(hits)
         params = paths_params(samples, gather_depth, gain, seed, key0, emitters, chunk_records, bounces)
         if base is not None:
@@ -1107,24 +1111,35 @@ class Renderer:
             if base.shape != hits.shape + (3,):
                 raise ValueError(f"base must have shape {hits.shape + (3,)}, not {base.shape}")
         out = np.empty(hits.shape + (3,), dtype=np.float32)
-        capi.check(self._lib.rt_indirect_paths(self._scene, C.byref(params), hits.size, hits.ctypes.data,
-                                               base.ctypes.data if base is not None else None, out.ctypes.data))
+        call = self._lib.rt_indirect_paths_compact if compact else self._lib.rt_indirect_paths
+        capi.check(call(self._scene, C.byref(params), hits.size, hits.ctypes.data, base.ctypes.data if base is not None else None,
+                        out.ctypes.data))
         return out
 
     def indirect_paths_device(self, n, hits_ptr, base_ptr, out_ptr, stream=0, bounces=2, samples=4, gather_depth=1, gain=1.0, seed=0,
-                              key0=0, emitters=False, chunk_records=0):
+                              key0=0, emitters=False, chunk_records=0, compact=False):
         """Enqueue indirect_paths() of n records (48 bytes each, hits_ptr 16-byte aligned) into 3 n float32 at out_ptr, added to
         the 3 n float32 at base_ptr unless that is 0 (base_ptr == out_ptr: in place), on a HIP stream (no sync: nothing is read
-        back)."""
+        back).  compact: rt_indirect_paths_compact_device (include/rt_paths_compact.h) -- the same words over the paths still
+        alive; it WAITS for the stream once per bounce, so the stream must not be capturing, and returns with its last step and
+        its resolve possibly still running."""
         params = paths_params(samples, gather_depth, gain, seed, key0, emitters, chunk_records, bounces)
-        capi.check(self._lib.rt_indirect_paths_device(self._scene, C.byref(params), n, C.c_void_p(hits_ptr),
-                                                      C.c_void_p(base_ptr or None), C.c_void_p(out_ptr), C.c_void_p(stream)))
+        call = self._lib.rt_indirect_paths_compact_device if compact else self._lib.rt_indirect_paths_device
+        capi.check(call(self._scene, C.byref(params), n, C.c_void_p(hits_ptr), C.c_void_p(base_ptr or None), C.c_void_p(out_ptr),
+                        C.c_void_p(stream)))
 
     def paths_info(self):
         """The last indirect_paths*() of this scene (include/rt_paths.h, rt_paths_info): records, rays, chunks, the five stage
         times and alive[b], the paths alive at bounce b."""
         info = capi.RtPathsInfo()
         capi.check(self._lib.rt_get_paths_info(self._scene, C.byref(info)))
+        return info
+
+    def paths_compact_info(self):
+        """The last indirect_paths*(compact=True) of this scene (include/rt_paths_compact.h, rt_paths_compact_info): records, the
+        rays actually traced, chunks, ray batches, hit queries and stream waits, the five stage times and alive[b]."""
+        info = capi.RtPathsCompactInfo()
+        capi.check(self._lib.rt_get_paths_compact_info(self._scene, C.byref(info)))
         return info
 
     def _render_ao_scaled(self, W, H, samples, radius, seed, channels, scale, normal_squarings, sigma_plane, refine, key0_refine):
@@ -1195,7 +1210,7 @@ class Renderer:
             return out.cpu().numpy().reshape(W, H, 3)                 # the one download
 
     def render_indirect(self, W, H, max_depth, samples=4, gather_depth=1, gain=1.0, seed=0, emitters=False, denoise=None, scale=1,
-                        normal_squarings=3, sigma_plane=0.0, refine=False, key0_refine=0x80000000, mirrors=None, bounces=1):
+                        normal_squarings=3, sigma_plane=0.0, refine=False, key0_refine=0x80000000, mirrors=None, bounces=1, compact=False):
         """A W x H frame with one diffuse bounce added, computed on the GPU where its records were made
         (include/rt_capi_indirect.h): rt_render_gbuffer_device and rt_indirect_diffuse_device -- the frame's colours the base,
         in place -- enqueued on one stream with no host wait between them, then one download -> float32 (W, H, 3).  The result
@@ -1215,10 +1230,14 @@ class Renderer:
         is gathered at the terminal records of the pixel rays and multiplied by the path's weight before it is added -- with
         (_, hits, _, weight, _) = render_gbuffer_mirrored(W, H, max_depth, ...), rgb + weight * indirect_diffuse(hits, ...), one
         fp32 multiply and one fp32 add, bit for bit.  bounces: indirect_diffuse()'s, in every one of these compositions (any count
-        but 1: rt_indirect_paths_device, include/rt_paths.h, in rt_indirect_diffuse_device's place)."""
+        but 1: rt_indirect_paths_device, include/rt_paths.h, in rt_indirect_diffuse_device's place).  compact:
+        rt_indirect_paths_compact_device (include/rt_paths_compact.h) in that place, whatever bounces is -- the same frame bit for
+        bit, but the call then WAITS for the stream once per bounce and chunk instead of only before the download."""
         import torch
         device = int(self._device)
         kw = dict(samples=samples, gather_depth=gather_depth, gain=gain, seed=seed, emitters=emitters, bounces=bounces)
+        if compact:
+            kw["compact"] = True
         if mirrors is not None:
             if scale != 1 or denoise is not None:
                 raise ValueError("mirrors needs scale 1 and no denoise")
